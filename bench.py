@@ -16,11 +16,28 @@ batch fixed at 65536 and split by rows over the ranks ("scaling": "strong"; the 
 the rows a batch touches travel in two all-to-alls per step, the small tensors in one all-reduce -- RCCL).  The
 weak case (65536 rows PER GPU) is the `weak_scaling` sub-record.
 
-Prints ONE JSON line (rank 0).  ``roofline`` describes the LONGEST kernel group of the step (HIP
-events on the model's stream, measured live; ``traffic`` from two rocprofv3 --pmc passes this
-script runs on itself), ``cpu_baseline`` the CPU restatements of the same step timed on this
-node's host cores on a bounded sample: a multithreaded C implementation pinned to one socket
-(the headline baseline) and the single-threaded numpy oracle.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: it
+builds the data set and the model, runs untimed steps (those of --full's per-kernel pass, then
+those that bring the clocks up) and the W warm-up steps, times exactly K steps, and prints
+`metric`, `value`, `unit`, `ms_per_step`, ... (`roofline` and `cpu_baseline` null).
+
+    --full              everything else as well: the memory ceilings of this box, the per-kernel
+                        table (HIP events), the in-step kernel times, the deferred-read-back and fp32-MFMA
+                        passes, seeds 1, 2 and U[0.5, 2] weights, weak scaling at N > 1, the loglinear /
+                        additive full-softmax / C4 / small-batch / query sub-records, the CPU baselines
+                        and the full record (sidecar file + stderr).  ``roofline`` then describes the
+                        LONGEST kernel group of the step (HIP events on the model's stream, measured live;
+                        ``traffic`` from two rocprofv3 --pmc passes this script runs on itself),
+                        ``cpu_baseline`` the CPU restatements of the same step timed on this node's host
+                        cores on a bounded sample: a multithreaded C implementation pinned to one socket
+                        (the headline baseline) and the single-threaded numpy oracle.
+    --dump-outputs DIR  after the timed steps: what the last timed step returned (its loss) and the
+                        parameters it left behind (R_w, R_e where the model has one, W, b), as
+                        DIR/<name>.npy (float64 loss, float32 tensors), 64 MB at most: where the tables
+                        are larger, a fixed seeded sample of their rows (the same rows for the same
+                        shapes).  The inputs depend on the arguments only, so two builds can be compared
+                        file for file.  A plain run takes the steps of the --full run's per-kernel pass
+                        untimed first: both runs compute the same outputs.
 """
 import argparse
 import gc
@@ -316,6 +333,23 @@ def timed_steps(model, dist, num_batches, steps, warmup, timing=True):
         # loglinear reuses this timing slot for the per-distinct-word sums of dJ / r
         timings['per_word_dz_sums'] = timings.pop('entity_grad_reduce')
     return dist.all_reduce_max(dt), timings, float(last)
+
+
+def replay_steps(model, num_batches, steps, warmup=2):
+    """The batches and next-batch hints of timed_steps(timing=True) -- its warm-up, its two steps and its K steps --
+    untimed, without HIP events: the model ends in the state the per-kernel pass of a --full run leaves it in, so that
+    the timed steps of a plain run compute what those of a --full run compute."""
+    eng = model._engine
+    for i in range(warmup):
+        eng.hint_next_batch((i + 1) % num_batches if i + 1 < warmup else warmup % num_batches)
+        model.train_fn(i % num_batches)
+    for i in range(2):
+        eng.hint_next_batch((warmup + i + 1) % num_batches)
+        model.train_fn((warmup + i) % num_batches)
+    for i in range(steps):
+        eng.hint_next_batch((warmup + i + 1) % num_batches if i + 1 < steps else None)
+        model.train_fn((warmup + i) % num_batches)
+    eng.hint_next_batch(None)
 
 
 def instep_pass(model, num_batches, steps):
@@ -1165,6 +1199,33 @@ def write_full_record(full):
     return None
 
 
+DUMP_LIMIT = 64 << 20     # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(model, path, last_loss, rank):
+    """--dump-outputs: the loss of the last timed step and the parameters it left behind, DIR/<name>.npy.  Where they
+    exceed DUMP_LIMIT, every table keeps the same fraction of its rows, drawn with a fixed seed from its shape alone.
+    Data parallel: COLLECTIVE (the word table is gathered) -- every rank calls it, rank 0 writes."""
+    tables = model.get_representations()
+    if not isinstance(tables, (tuple, list)):
+        tables = (tables,)
+    arrays = [('loss', np.array([last_loss], dtype=np.float64))]
+    arrays += list(zip(('R_w', 'R_e'), tables))
+    arrays += [('W', model.get_dense_weights()), ('b', model.get_dense_bias())]
+    if rank != 0:
+        return
+    total = sum(a.nbytes for _, a in arrays)
+    keep = min(1.0, 0.99 * DUMP_LIMIT / total)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays:
+        a = np.asarray(a)
+        if keep < 1.0 and a.ndim == 2:
+            k = max(1, int(a.shape[0] * keep))
+            rows = np.sort(np.random.RandomState(a.shape[0]).choice(a.shape[0], size=k, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -1182,6 +1243,11 @@ def main():
     ap.add_argument('--seed', type=int, default=0, help='seed of the synthetic data set (SURVEY 8-d: seeds 0..2)')
     ap.add_argument('--weights', choices=['ones', 'uniform'], default='ones',
                     help='instance weights: 1 (LSE, --no_instance_weights) or U[0.5, 2] (SURVEY 8-d second run)')
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything beside the headline (ceilings, per-kernel table, sub-records, CPU baselines); '
+                         'the --no-* options below apply to such a run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s loss and the parameters it left behind as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=12.0)
     ap.add_argument('--no-loglinear-extra', action='store_true')
@@ -1195,6 +1261,8 @@ def main():
     ap.add_argument('--profile-query-inner', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--query-shape', default='10000,100000,128,100', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # one process per GPU, started here; this process only waits for them
@@ -1246,6 +1314,63 @@ def main():
         timed_steps(model, dist, args.num_batches, args.steps, args.warmup, timing=False)
         return
 
+    def headline(dt, last_loss, comm):
+        """The headline part of the record: the number, its unit and the configuration it was taken on."""
+        return {
+            'metric': 'training_pairs_per_sec', 'value': args.steps * Bg / dt, 'unit': 'pairs/s',
+            'n_gpus': N, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': 1000.0 * dt / args.steps, 'higher_is_better': True,
+            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'config': {
+                'workload': ('C2 LSE: %s V_w=%d V_e=%d d=%d window=%d batch=%d%s' % (
+                    {'vectorspace': 'VectorSpaceLanguageModel (NCE z=%d, Adam)' % z,
+                     'loglinear': 'LanguageModel (full softmax, Adadelta)',
+                     'vectorspace_softmax': 'VectorSpaceSoftmaxLanguageModel (additive full softmax, Adam)'}[kind],
+                    Vw, Ve, d, n, Bg, ('' if de == d else ' d_e=%d' % de) + ('' if N == 1 else ' (global; %d rows per GPU)' % Bl))),
+                'global_batch': Bg, 'per_gpu_batch': Bl,
+                'parallelism': 'dp%d' % N if N == 1 else 'dp%d, %s' % (N, (comm or {}).get('exchange', 'data parallel')),
+                'id_dtype': str(X.dtype), 'lambda': 0.01, 'seed': args.seed,
+                'dataset_instances': int(len(X)), 'dataset_batches': int(len(X) // Bg), 'upload_index_s': round(upload_s, 3),
+                'instance_weights': '1' if args.weights == 'ones' else 'U[0.5, 2]',
+                'gemm_arithmetic': ('fp32 MFMA (SERT_GEMM_FP32=1)' if os.environ.get('SERT_GEMM_FP32', '0') not in ('', '0') else
+                                    'fp32 operands, fp32 accumulators, fp32 results; each operand is split exactly into three bf16 '
+                                    'pieces and a product runs as six bf16 MFMA products (gemm_x3.h): against float64 the error is '
+                                    'that of the fp32 accumulation, as on the fp32 MFMA kernels (tests/test_gpu_gemm.py, same bounds)'),
+            },
+            'last_loss': last_loss,
+        }
+
+    def add_comm(out, comm):
+        if comm:
+            if comm.get('transport') == 'rccl' and comm.get('rccl_ranks') != N:
+                raise SystemExit('RCCL communicator spans %r ranks, --gpus %d' % (comm.get('rccl_ranks'), N))
+            out['rccl_ranks'] = comm.get('rccl_ranks')
+            out['comm_bytes_per_step'] = comm.get('comm_bytes_per_step')
+            out['comm'] = comm
+
+    if not args.full:
+        # a plain run: the headline and nothing else -- the steps of the per-kernel pass untimed (K + 4 steps: the timed
+        # steps then compute what a --full run's do), then timed_steps: the untimed steps that bring the clocks up, W
+        # warm-up steps and exactly K timed steps between barrier + synchronise
+        replay_steps(model, args.num_batches, args.steps)
+        dt, _, last_loss = timed_steps(model, dist, args.num_batches, args.steps, args.warmup, timing=False)
+        if args.dump_outputs:
+            dump_outputs(model, args.dump_outputs, last_loss, ctx.rank)
+        comm = getattr(model, 'comm_info', lambda: None)()
+        device_info = _capi.device_info(model._engine.cfg.device)
+        del model
+        if ctx.rank == 0:
+            out = headline(dt, last_loss, comm)
+            out.update(roofline=None, cpu_baseline=None, device=device_info)
+            add_comm(out, comm)
+            sys.stdout.flush()
+            line = json.dumps(compact_record(out))
+            assert len(line) < LINE_LIMIT, len(line)
+            os.write(json_fd, (line + '\n').encode())
+        dist.barrier()
+        dist.shutdown()
+        return
+
     # Order of the measurements.  A GPU that sat idle while the host generated the data set and built the
     # inverted index needs some tens of milliseconds of load to reach its operating clocks: the same 20 steps
     # read 319 us/step straight after the build, 304 in a second region and 295 from the third on
@@ -1272,6 +1397,8 @@ def main():
     dt_instr, timings, _ = timed_steps(model, dist, args.num_batches, args.steps, 2, timing=True)
     dt, _, last_loss = timed_steps(model, dist, args.num_batches, args.steps, args.warmup, timing=False)
     value = args.steps * Bg / dt
+    if args.dump_outputs:
+        dump_outputs(model, args.dump_outputs, last_loss, ctx.rank)
     # (behind the number: the same K steps once more with every kernel's own dispatch timed IN the step)
     # (its own step count: a 20-step run holds five or six passes of the lazy update that read everything among its launches, a 100-step one
     #  a quarter -- the in-step average is taken over at least 100 steps whatever K is)
@@ -1362,27 +1489,8 @@ def main():
             roofline['traffic_note'] = traffic_source
         step_flops = sum(w_['flops'] for k, w_ in work.items() if w_['kind'] == 'mfma' and k in kernels)
         kernel_sum_us = sum(v['us'] for v in kernels.values())
-        out = {
-            'metric': 'training_pairs_per_sec', 'value': value, 'unit': 'pairs/s',
-            'n_gpus': N, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': 1000.0 * dt / args.steps, 'higher_is_better': True,
-            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {
-                'workload': ('C2 LSE: %s V_w=%d V_e=%d d=%d window=%d batch=%d%s' % (
-                    {'vectorspace': 'VectorSpaceLanguageModel (NCE z=%d, Adam)' % z,
-                     'loglinear': 'LanguageModel (full softmax, Adadelta)',
-                     'vectorspace_softmax': 'VectorSpaceSoftmaxLanguageModel (additive full softmax, Adam)'}[kind],
-                    Vw, Ve, d, n, Bg, ('' if de == d else ' d_e=%d' % de) + ('' if N == 1 else ' (global; %d rows per GPU)' % Bl))),
-                'global_batch': Bg, 'per_gpu_batch': Bl,
-                'parallelism': 'dp%d' % N if N == 1 else 'dp%d, %s' % (N, (comm or {}).get('exchange', 'data parallel')),
-                'id_dtype': str(X.dtype), 'lambda': 0.01, 'seed': args.seed,
-                'dataset_instances': int(len(X)), 'dataset_batches': int(len(X) // Bg), 'upload_index_s': round(upload_s, 3),
-                'instance_weights': '1' if args.weights == 'ones' else 'U[0.5, 2]',
-                'gemm_arithmetic': ('fp32 MFMA (SERT_GEMM_FP32=1)' if os.environ.get('SERT_GEMM_FP32', '0') not in ('', '0') else
-                                    'fp32 operands, fp32 accumulators, fp32 results; each operand is split exactly into three bf16 '
-                                    'pieces and a product runs as six bf16 MFMA products (gemm_x3.h): against float64 the error is '
-                                    'that of the fp32 accumulation, as on the fp32 MFMA kernels (tests/test_gpu_gemm.py, same bounds)'),
-            },
+        out = headline(dt, last_loss, comm)
+        out.update({
             'roofline': roofline,
             'memory_ceilings': (dict(ceilings, note='measured in this process on this box (sert_bench_memory): float4 stream copy / '
                                      'read over 1.2 GB, vs_gather_mean over uniformly random rows (window 10), adam_l2 over '
@@ -1401,9 +1509,8 @@ def main():
             'kernels': kernels,
             'kernel_us_instep': {k: round(v, 2) for k, v in us_instep.items()},
             'kernel_launches_instep': {k: round(v, 2) for k, v in launches_instep.items()},
-            'last_loss': last_loss,
             'device': device_info,
-        }
+        })
         if gemm_fp32 is not None:
             out['gemm_fp32_mfma_path'] = gemm_fp32
         if seed_runs is not None:
@@ -1413,12 +1520,7 @@ def main():
         if shared_device:
             out['memory_ceilings_note'] = ('%d ranks share one device (test transport): no ceilings were measured; per-kernel '
                                            'fractions that need one are null, times are those of kernels competing for one GPU' % N)
-        if comm:
-            if comm.get('transport') == 'rccl' and comm.get('rccl_ranks') != N:
-                raise SystemExit('RCCL communicator spans %r ranks, --gpus %d' % (comm.get('rccl_ranks'), N))
-            out['rccl_ranks'] = comm.get('rccl_ranks')
-            out['comm_bytes_per_step'] = comm.get('comm_bytes_per_step')
-            out['comm'] = comm
+        add_comm(out, comm)
         if weak is not None:
             out['weak_scaling'] = weak
 

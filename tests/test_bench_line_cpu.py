@@ -5,6 +5,8 @@ import json
 import os
 import re
 
+import numpy as np
+
 import bench
 from tests import util as U
 
@@ -112,3 +114,47 @@ def test_traffic_lookup_finds_the_dominant_loglinear_kernel_in_a_committed_count
     assert tbg['per_word_dz_sums']['hip_kernel'].startswith('segsum_rows_plus_ll'), tbg['per_word_dz_sums']
     assert tbg['per_word_dz_sums']['hbm_bytes'] > 1.5e9, tbg['per_word_dz_sums']
     assert tbg['loss']['hip_kernel'].startswith('ll_row_wave') and tbg['gemm_fwd']['hip_kernel'].startswith('gemm_x3<false, false, 1')
+
+
+class _FakeModel(object):
+    """The getters bench.dump_outputs calls, over host arrays (the vectorspace model's tables)."""
+
+    def __init__(self, rng, Vw, Ve, d):
+        self.Rw, self.Re = rng.randn(Vw, d).astype(np.float32), rng.randn(Ve, d).astype(np.float32)
+        self.W, self.b = rng.randn(d, d).astype(np.float32), rng.randn(d).astype(np.float32)
+
+    def get_representations(self):
+        return self.Rw, self.Re
+
+    def get_dense_weights(self):
+        return self.W
+
+    def get_dense_bias(self):
+        return self.b
+
+
+def test_dumped_outputs_are_complete_below_the_limit_and_a_fixed_sample_above(tmp_path, monkeypatch):
+    """--dump-outputs: every output whole while they fit the limit; above it a fixed sample of rows -- the same rows for the
+    same shapes, whatever the values -- that keeps the files under the limit; float64 loss, float32 tensors."""
+    m = _FakeModel(np.random.RandomState(0), 5000, 300, 32)
+    bench.dump_outputs(m, str(tmp_path / 'whole'), 1.25, rank=0)
+    got = {f[:-4]: np.load(str(tmp_path / 'whole' / f)) for f in os.listdir(str(tmp_path / 'whole'))}
+    assert sorted(got) == ['R_e', 'R_w', 'W', 'b', 'loss']
+    assert got['loss'].dtype == np.float64 and got['loss'][0] == 1.25
+    for k, a in (('R_w', m.Rw), ('R_e', m.Re), ('W', m.W), ('b', m.b)):
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], a), k
+
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 200000)
+    m2 = _FakeModel(np.random.RandomState(1), 5000, 300, 32)
+    dirs = []
+    for tag, mm in (('a', m), ('b', m2)):
+        bench.dump_outputs(mm, str(tmp_path / tag), 0.5, rank=0)
+        dirs.append(str(tmp_path / tag))
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0])) <= 200000
+    a, b = np.load(os.path.join(dirs[0], 'R_w.npy')), np.load(os.path.join(dirs[1], 'R_w.npy'))
+    assert 0 < a.shape[0] < 5000 and a.shape == b.shape and a.shape[1] == 32
+    rows = [int(np.flatnonzero((m.Rw == r).all(axis=1))[0]) for r in a]
+    assert rows == sorted(rows) and np.array_equal(m2.Rw[rows], b)    # the same rows of both models
+
+    bench.dump_outputs(m, str(tmp_path / 'other_rank'), 0.5, rank=1)
+    assert not os.path.exists(str(tmp_path / 'other_rank'))

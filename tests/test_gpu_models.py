@@ -704,7 +704,7 @@ def test_bench_launches_its_own_ranks(hip_lib):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'SERT_RDZV_DIR'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(U.ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--batch', '4096', '--vocab', '20000', '--num-batches', '2'],
+                        '--batch', '4096', '--vocab', '20000', '--num-batches', '2', '--full'],
                        env=env, cwd=U.ROOT, stdout=subprocess.PIPE, timeout=900)
     assert r.returncode == 0
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -735,6 +735,42 @@ def test_bench_launches_its_own_ranks(hip_lib):
     assert all(v <= 1.0 for _, v in fracs(full)), [kv for kv in fracs(full) if kv[1] > 1.0]
 
     assert all(v <= 1.0 for _, v in fracs(rec)), [kv for kv in fracs(rec) if kv[1] > 1.0]
+
+
+def test_plain_bench_line_and_its_dumped_outputs(hip_lib, tmp_path):
+    """python bench.py without --full: one line with the headline keys and none of the extra records, exactly --steps timed
+    steps; --dump-outputs writes the last timed step's loss and parameters, bit for bit the same in a second run and in a
+    --full run (its extra records switched off) of the same arguments."""
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'SERT_RDZV_DIR'):
+        env.pop(k, None)
+    full = ['--full', '--no-cpu-baseline', '--no-loglinear-extra', '--no-query-extra', '--no-c4-extra', '--no-small-extra',
+            '--no-seed-extra', '--no-live-pmc']
+    recs, dumps = [], []
+    for tag, extra in (('a', []), ('b', []), ('full', full)):
+        out = str(tmp_path / tag)
+        r = subprocess.run([sys.executable, os.path.join(U.ROOT, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2',
+                            '--batch', '4096', '--vocab', '20000', '--num-batches', '4', '--dump-outputs', out] + extra,
+                           env=env, cwd=U.ROOT, stdout=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0
+        lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)})
+    rec = recs[0]
+    assert rec['metric'] == 'training_pairs_per_sec' and rec['unit'] == 'pairs/s' and rec['higher_is_better'] is True
+    assert rec['dtype'] == 'f32' and rec['steps'] == 7 and rec['warmup'] == 2 and rec['n_gpus'] == 1
+    assert rec['ms_per_step'] > 0 and abs(rec['value'] - 7 * 4096 / (7 * rec['ms_per_step'] / 1000.0)) <= 1e-4 * rec['value']
+    assert rec['config']['global_batch'] == 4096 and np.isfinite(rec['last_loss'])
+    for k in ('kernel_us', 'loglinear', 'c4', 'query', 'seeds', 'gemm_fp32_mfma_path', 'full_record'):
+        assert k not in rec, k
+    assert rec['roofline'] is None and rec['cpu_baseline'] is None
+    assert sorted(dumps[0]) == ['R_e', 'R_w', 'W', 'b', 'loss']
+    assert dumps[0]['R_w'].shape == (20000, 128) and dumps[0]['R_w'].dtype == np.float32
+    assert float(dumps[0]['loss'][0]) == pytest.approx(rec['last_loss'], rel=1e-5)
+    assert 'kernel_us' in recs[2] and recs[2]['last_loss'] == rec['last_loss']
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]) and np.array_equal(dumps[0][k], dumps[2][k]), k
 
 
 def test_loglinear_distinct_word_path_is_deterministic_and_matches_per_token_path(hip_lib, tmp_path):
