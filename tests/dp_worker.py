@@ -32,8 +32,13 @@ def run_c2(kind):
     out['loss1'] = np.float64(m.train_fn(1))
     out['loss2'] = np.float64(m.train_fn(0))
     out['eval0'] = np.float64(m.test_fn(0))
+    # (the moments of R_e, W and b as well: the tensors the all-reduce's global 1/B scaling feeds, which the
+    #  parameters cannot show under Adam)
     for name, which in (('Rw', C.T_RW), ('Re', C.T_RE), ('W', C.T_W), ('b', C.T_B),
-                        ('opt_state0_rw', C.T_STATE0_RW), ('opt_state1_rw', C.T_STATE1_RW)):
+                        ('opt_state0_rw', C.T_STATE0_RW), ('opt_state1_rw', C.T_STATE1_RW),
+                        ('opt_state0_re', C.T_STATE0_RE), ('opt_state1_re', C.T_STATE1_RE),
+                        ('opt_state0_w', C.T_STATE0_W), ('opt_state1_w', C.T_STATE1_W),
+                        ('opt_state0_b', C.T_STATE0_B), ('opt_state1_b', C.T_STATE1_B)):
         out[name] = m._engine.get_tensor(which).copy()
     info = m.comm_info()
     out['exchange'] = np.str_(info['exchange_kind'] if info else 'none')

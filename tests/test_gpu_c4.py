@@ -50,6 +50,25 @@ def max_rel(a, b):
     return float(np.abs(a - b).max()) / max(1e-30, float(np.abs(b).max()))
 
 
+def check_state_rows(eng, ora, rows, log=None):
+    """Every parameter and both optimiser moments (util.oracle_state's names) against the oracle, max_rel style (no
+    float64 copies), one tensor read at a time.  rows: {table name: [row sets]} -- each set is bounded on its own (the
+    rows a batch touches; a sample of untouched ones, whose state only the L2 term moves, is far below the
+    touched rows' and would vanish inside their maximum); W and b whole."""
+    ref = U.oracle_state(ora)
+    shapes = U.state_shapes(eng.cfg)
+    for k in ref:
+        moment, _, par = k.rpartition('.')
+        which = U.STATE_IDS[par][0 if not moment else (1 if moment in ('m', 'accu') else 2)]
+        got = eng.get_tensor(which, shapes[par])
+        for sel in rows.get(par, [slice(None)]):
+            e = max_rel(got[sel], ref[k][sel])
+            assert e < PARAM_TOL, (k, e)
+            if log is not None:
+                log.append('%s rel %.1e' % (k, e))
+        del got
+
+
 def test_c4_vectorspace_oracle_parity_at_full_table_sizes(hip_lib, c4_tables):
     B, steps, lam = 256, 2, 0.01
     rng = np.random.RandomState(5)
@@ -60,9 +79,11 @@ def test_c4_vectorspace_oracle_parity_at_full_table_sizes(hip_lib, c4_tables):
     eng = U.vs_engine(p, B, N_WIN, Z, lam, keep_grads=0)
     eng.upload_dataset(C.SPLIT_TRAIN, X, y_int=y, w=w)
     ora = O.VectorSpaceOracle(B, N_WIN, Z, p['Rw'], p['Re'], p['W'], p['b'], lam)
+    negs = []
     for s in range(steps):
         sl = slice(s * B, (s + 1) * B)
         neg = rng.randint(0, VE, size=(B, Z)).astype(np.int64)
+        negs.append(neg)
         ref = ora.train_step(X[sl], y[sl], w[sl], neg)
         got = eng.train_batch(s, neg)
         assert abs(got - ref) <= LOSS_TOL * abs(ref), (s, got, ref)
@@ -75,6 +96,14 @@ def test_c4_vectorspace_oracle_parity_at_full_table_sizes(hip_lib, c4_tables):
     untouched = np.setdiff1d(np.arange(VW), np.unique(X))[:1000]
     assert np.abs(m_rw[untouched]).max() > 0.0          # the L2 term reached them
     assert max_rel(m_rw[untouched], ora.opt.m[1][untouched]) < PARAM_TOL
+    del m_rw
+    # every parameter and both Adam moments: the rows the batches touch, and a sample of untouched rows, on their own
+    words = np.unique(X)
+    ents = np.unique(np.concatenate([y.astype(np.int64)] + [g.ravel() for g in negs]))
+    log = []
+    check_state_rows(eng, ora, {'R_w': [words, np.setdiff1d(np.arange(VW), words)[::500]],
+                                'R_e': [ents, np.setdiff1d(np.arange(VE), ents)[::50]]}, log)
+    print('\n'.join(log))
     neg = rng.randint(0, VE, size=(B, Z)).astype(np.int64)
     ev, ev_ref = eng.eval_batch(C.SPLIT_TRAIN, 1, neg), ora.eval_loss(X[B:], y[B:], neg)
     assert abs(ev - ev_ref) <= LOSS_TOL * abs(ev_ref)
@@ -102,6 +131,11 @@ def test_c4_loglinear_oracle_parity_at_full_table_sizes(hip_lib, c4_tables):
     assert max_rel(eng.get_tensor(C.T_RW), ora.R_w) < PARAM_TOL
     assert max_rel(eng.get_tensor(C.T_W), ora.W) < PARAM_TOL
     assert max_rel(eng.get_tensor(C.T_B), ora.b) < PARAM_TOL
+    # every parameter, accu and delta: the touched word rows and a sample of untouched ones on their own; W, b whole
+    words = np.unique(X)
+    log = []
+    check_state_rows(eng, ora, {'R_w': [words, np.setdiff1d(np.arange(VW), words)[::500]]}, log)
+    print('\n'.join(log))
     ev, ev_ref = eng.eval_batch(C.SPLIT_TRAIN, 0), ora.eval_loss(X[:B], y[:B])
     assert abs(ev - ev_ref) <= LOSS_TOL * abs(ev_ref)
     eng.close()

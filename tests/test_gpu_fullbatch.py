@@ -32,10 +32,8 @@ from tests.util import C, O
 pytestmark = pytest.mark.gpu
 
 LOSS_TOL = 1e-5       # per-step loss, relative
-TENSOR_TOL = 1e-4     # parameters (and here: optimiser moments), relative to the tensor's max
-ROW_TOL32 = 2e-4      # row-wise, against the float32 oracle (sequential fp32 sums on the oracle's side)
-ROW_TOL64 = 5e-5      # row-wise, against the float64 evaluation of the same oracle
-ROW_TOL32_DENSE = 1e-3   # W, b against the float32 oracle: batch-long cancelling sums on both sides (see above)
+# tensor bounds: util.TENSOR_TOL (1e-4 of the tensor's max), util.ROW_TOL32 / ROW_TOL64 / ROW_TOL32_DENSE row by row,
+# applied by util.check_tensor / util.check_state (second moments: twice the row bound)
 
 
 def _zipf_tokens(rng, N, n, Vw):
@@ -52,24 +50,6 @@ def _vs_problem(seed, N, n, Vw, Ve, dw, de):
     p['w'] = rng.uniform(0.5, 2.0, N).astype(np.float32)
     p['rng'] = rng
     return p
-
-
-def _check_tensor(name, got, ref32, ref64=None, rows=None, row_tol32=ROW_TOL32):
-    """global + row-wise bounds for one (rows, cols) tensor; returns the figures for the log line."""
-    g = U.rel_err(got, ref32)
-    assert g < TENSOR_TOL, (name, 'rel_err', g)
-    r32, at32 = U.row_err(got, ref32, rows)
-    assert r32 < row_tol32, (name, 'row_err vs float32 oracle', r32, 'row', at32, 'tolerance', row_tol32,
-                             'W, b and their moments take %g against the FLOAT32 oracle -- batch-long cancelling sums, the '
-                             'oracle\'s own BLAS sum is 3.7e-4 off row-wise at C4 -- and the float64 bound (%g) does the '
-                             'testing where a float64 reference is given' % (ROW_TOL32_DENSE, ROW_TOL64))
-    out = '%s rel %.1e row32 %.1e' % (name, g, r32)
-    if ref64 is not None:
-        r64, at64 = U.row_err(got, ref64, rows)
-        o64, _ = U.row_err(ref32, ref64, rows)
-        assert r64 < ROW_TOL64, (name, 'row_err vs float64 oracle', r64, 'row', at64)
-        out += ' row64 %.1e (oracle32 vs 64: %.1e)' % (r64, o64)
-    return out
 
 
 def _vs_run(hip_lib, dims, steps, seed, check64):
@@ -100,16 +80,10 @@ def _vs_run(hip_lib, dims, steps, seed, check64):
                 m = eng.get_tensor(ids[name][1], shapes[name])
                 m32 = ora.opt.m[opt_index[name]].reshape(shapes[name])
                 m64 = (0.1 * g64[opt_index[name]]).reshape(shapes[name]) if check64 else None
-                log.append(_check_tensor('m1.' + name, m, m32, m64, rows=touched if name == 'Rw' else None,
-                                         row_tol32=ROW_TOL32_DENSE if name in ('W', 'b') else ROW_TOL32))
-    for name in ('Rw', 'Re', 'W', 'b'):
-        k = opt_index[name]
-        par, m, v = (eng.get_tensor(t, shapes[name]) for t in ids[name])
-        rt = ROW_TOL32_DENSE if name in ('W', 'b') else ROW_TOL32
-        log.append(_check_tensor(name, par, ora.params()[k].reshape(shapes[name])))
-        log.append(_check_tensor('m.' + name, m, ora.opt.m[k].reshape(shapes[name]), row_tol32=rt))
-        # v is a sum of squares: twice the relative error of g row by row
-        log.append(_check_tensor('v.' + name, v, ora.opt.v[k].reshape(shapes[name]), row_tol32=2 * rt))
+                log.append(U.check_tensor('m1.' + name, m, m32, m64, rows=touched if name == 'Rw' else None,
+                                          row_tol32=U.ROW_TOL32_DENSE if name in ('W', 'b') else U.ROW_TOL32))
+    # every parameter, m and v (v is a sum of squares: twice the relative error of g row by row)
+    log += U.check_state(U.engine_state(eng), U.oracle_state(ora))
     eng.close()
     print('\n'.join(log))
 
@@ -156,16 +130,9 @@ def test_loglinear_c2_dims_at_the_largest_oracle_batch(hip_lib):
         got = eng.train_batch(s)
         assert abs(got - ref) <= LOSS_TOL * abs(ref), (s, got, ref)
         log.append('step %d loss %.7f (oracle %.7f)' % (s, got, ref))
-    shapes = {'Rw': (Vw, d), 'W': (d, Ve), 'b': (1, Ve)}
-    ids = {'Rw': (C.T_RW, C.T_STATE0_RW, C.T_STATE1_RW), 'W': (C.T_W, C.T_STATE0_W, C.T_STATE1_W),
-           'b': (C.T_B, C.T_STATE0_B, C.T_STATE1_B)}
-    for k, name in enumerate(('Rw', 'W', 'b')):               # parameter order [R_w, W, b], models.py:543
-        par, accu, delta = (eng.get_tensor(t, shapes[name]) for t in ids[name])
-        rt = ROW_TOL32_DENSE if name in ('W', 'b') else ROW_TOL32
-        log.append(_check_tensor(name, par, ora.params()[k].reshape(shapes[name])))
-        # Adadelta: accu = running mean of g^2, delta = running mean of update^2 -- squares: 2x the row bound
-        log.append(_check_tensor('accu.' + name, accu, ora.opt.accu[k].reshape(shapes[name]), row_tol32=2 * rt))
-        log.append(_check_tensor('delta.' + name, delta, ora.opt.delta[k].reshape(shapes[name]), row_tol32=2 * rt))
+    # parameter order [R_w, W, b], models.py:543; Adadelta: accu = running mean of g^2, delta = running mean of
+    # update^2 -- squares: 2x the row bound
+    log += U.check_state(U.engine_state(eng), U.oracle_state(ora))
     eng.close()
     print('\n'.join(log))
 
@@ -190,14 +157,6 @@ def test_additive_full_softmax_at_the_benchmarked_batch(hip_lib):
         got = eng.train_batch(s)
         assert abs(got - ref) <= LOSS_TOL * abs(ref), (s, got, ref)
         log.append('step %d loss %.7f (oracle %.7f)' % (s, got, ref))
-    shapes = {'Rw': (Vw, d), 'Re': (Ve, d), 'W': (d, d), 'b': (1, d)}
-    ids = {'Rw': (C.T_RW, C.T_STATE0_RW, C.T_STATE1_RW), 'Re': (C.T_RE, C.T_STATE0_RE, C.T_STATE1_RE),
-           'W': (C.T_W, C.T_STATE0_W, C.T_STATE1_W), 'b': (C.T_B, C.T_STATE0_B, C.T_STATE1_B)}
-    for k, name in enumerate(('Re', 'Rw', 'W', 'b')):
-        par, m, v = (eng.get_tensor(t, shapes[name]) for t in ids[name])
-        rt = ROW_TOL32_DENSE if name in ('W', 'b') else ROW_TOL32
-        log.append(_check_tensor(name, par, ora.params()[k].reshape(shapes[name])))
-        log.append(_check_tensor('m.' + name, m, ora.opt.m[k].reshape(shapes[name]), row_tol32=rt))
-        log.append(_check_tensor('v.' + name, v, ora.opt.v[k].reshape(shapes[name]), row_tol32=2 * rt))
+    log += U.check_state(U.engine_state(eng), U.oracle_state(ora))
     eng.close()
     print('\n'.join(log))

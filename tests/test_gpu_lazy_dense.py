@@ -74,6 +74,8 @@ def test_alternating_lazy_and_dense_steps(hip_lib, kind, lazy_max, monkeypatch):
             losses.append(eng.train_batch(b, negs[s]) if negs else eng.train_batch(b))
         outs.append((losses, eng.get_tensor(C.T_RW).copy(), eng.get_tensor(C.T_STATE0_RW).copy(),
                      eng.get_tensor(C.T_STATE1_RW).copy(), eng.get_tensor(C.T_W).copy()))
+        if not keep and hints:
+            state = U.engine_state(eng)
         eng.close()
     assert same_loss(outs[1][0], outs[2][0])
     for a, b_ in zip(outs[1][1:], outs[2][1:]):
@@ -100,3 +102,10 @@ def test_alternating_lazy_and_dense_steps(hip_lib, kind, lazy_max, monkeypatch):
     assert U.rel_err(Rw, ora.R_w) < 1e-4
     err, row = U.row_err(Rw, ora.R_w)
     assert err < 1e-3, (err, row)        # (every row against its own norm: one update too many on an untouched row shows here)
+    # the whole state of the product run: the word table's moments under the same row bound as the table (1e-3, twice
+    # that for the second moment), every other parameter and both its moments under util.check_state's bounds
+    ref = U.oracle_state(ora)
+    log = U.check_state(state, ref, names=[k for k in ref if k.rpartition('.')[2] != 'R_w'])
+    for k in [k for k in ref if k.rpartition('.')[2] == 'R_w' and '.' in k]:
+        log.append(U.check_tensor(k, state[k], ref[k], row_tol32=(2 if k.split('.')[0] in U.SECOND_MOMENTS else 1) * 1e-3))
+    print('\n'.join(log))

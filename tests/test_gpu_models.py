@@ -63,6 +63,8 @@ def test_vectorspace_model_epoch_matches_oracle(hip_lib):
     assert abs(mean_loss - np.mean(ref_losses)) < 1e-5 * abs(np.mean(ref_losses))
     Rw, Re = m.get_representations()
     assert U.rel_err(Rw, ora.R_w) < 1e-4 and U.rel_err(Re, ora.R_e) < 1e-4
+    # every parameter (W, b too) and both Adam moments after the epoch
+    print('\n'.join(U.check_state(U.engine_state(m._engine), U.oracle_state(ora))))
     te_mean, te_std = m.train_error()
     ref = [ora.eval_loss(Xt[j*B:(j+1)*B], yt[j*B:(j+1)*B], negs[('e', j)]) for j in range(5)]
     assert abs(te_mean - np.mean(ref)) < 1e-5 * abs(np.mean(ref))
@@ -99,6 +101,8 @@ def test_loglinear_model_csr_labels(hip_lib):
         got = m.train_fn(j)
         assert abs(got - ref) <= 1e-5 * abs(ref)
     assert U.rel_err(m.get_representations(), ora.R_w) < 1e-4
+    # every parameter and Adadelta's accu / delta
+    print('\n'.join(U.check_state(U.engine_state(m._engine), U.oracle_state(ora))))
     # validation set empty -> mean of nothing, as in the reference (nan + warning)
     state = m.get_state()
     assert len(state) == 2
@@ -691,7 +695,8 @@ def test_two_ranks_at_c2_size_match_single_process(hip_lib, tmp_path):
     assert float(two['comm_bytes_per_step']) < 0.8 * float(two['zero1_bytes_per_step'])
     for key in ('loss0', 'loss1', 'loss2', 'eval0'):
         assert abs(float(two[key]) - float(one[key])) <= 2e-5 * abs(float(one[key])), key
-    for key in ('Rw', 'Re', 'W', 'b', 'opt_state0_rw', 'opt_state1_rw'):
+    for key in ('Rw', 'Re', 'W', 'b', 'opt_state0_rw', 'opt_state1_rw', 'opt_state0_re', 'opt_state1_re',
+                'opt_state0_w', 'opt_state1_w', 'opt_state0_b', 'opt_state1_b'):
         assert U.rel_err(two[key], one[key]) < 2e-5, key
 
 

@@ -27,7 +27,7 @@ LOSS_TOL, ACT_TOL, GRAD_TOL, PARAM_TOL = 1e-5, 2e-5, 1e-4, 1e-4
 VARIANTS_BUILD = 'variants' in os.path.basename(os.environ.get('SERT_LIB', ''))
 
 
-@pytest.mark.parametrize('dims', [
+VS_STEP_DIMS = [
     dict(B=64, n=5, z=4, Vw=500, Ve=37, dw=32, de=48),      # vector path, NPL=1
     dict(B=96, n=3, z=7, Vw=200, Ve=11, dw=30, de=70),      # scalar path, NPL=2, ragged tiles
     dict(B=256, n=10, z=10, Vw=3000, Ve=1000, dw=128, de=128),  # C2-shaped
@@ -40,9 +40,39 @@ VARIANTS_BUILD = 'variants' in os.path.basename(os.environ.get('SERT_LIB', ''))
     dict(B=1030, n=2, z=3, Vw=500, Ve=40, dw=96, de=64),        # strip GEMMs with idle waves (N = 64 / 96), K = 96 / 64
     dict(B=20000, n=5, z=3, Vw=300, Ve=40, dw=32, de=16),       # three dense heavy words (> 4096 occurrences each: segsum_heavy), the rest through the tree
     dict(B=6000, n=5, z=2, Vw=300, Ve=30, dw=300, de=32),       # one dense heavy word at d_w = 300 (64 lanes x 2 chunks)
-])
+]
+
+
+def _check_rowloss(eng, f, w):
+    """T_ACT_ROWLOSS row by row against the oracle (include/sert_hip.h: rowloss[i] = w_i * loss_i in a training
+    step, before the 1/B of the mean): at batch 65536 one wrong row moves the mean by ~1.5e-5, at the loss bound."""
+    ref = np.asarray(w, np.float64) * np.asarray(f['loss'], np.float64)
+    got = eng.get_tensor(C.T_ACT_ROWLOSS, ref.shape)
+    err = np.abs(got - ref) / np.maximum(np.abs(ref), 1e-3 * np.abs(ref).mean())
+    assert err.max() < ACT_TOL, ('row loss', int(err.argmax()), float(err.max()), got[err.argmax()], ref[err.argmax()])
+
+
+@pytest.mark.parametrize('dims', VS_STEP_DIMS)
 @pytest.mark.parametrize('egrad', ['default', 'sorted'] + (['strip_gemm', 'roles_gemm'] if VARIANTS_BUILD else []))
 def test_vectorspace_steps(hip_lib, dims, egrad, monkeypatch):
+    _vectorspace_steps(dims, egrad, monkeypatch, keep=1)
+
+
+@pytest.mark.parametrize('dims', VS_STEP_DIMS)
+@pytest.mark.parametrize('egrad', ['default', 'sorted'])
+def test_vectorspace_steps_product_path(hip_lib, dims, egrad, monkeypatch):
+    """keep_grads = 0 twin of test_vectorspace_steps: same problems, same explicit negatives, no tensor read until the
+    last step (a read flushes the lazy word-table rows and settles the tail: another schedule), then the loss of
+    every step and the whole state -- parameters, m, v -- against the float32 and the float64 oracle.  Branches only
+    this setting takes (csrc/host): the W / b combine + L2 + Adam in the step's tail without a stored gradient
+    (vs_tail<false>, optimizer_and_loss.inc: every shape here, W is never "big"); the touched-row bitmaps of the word
+    table (use_touched_now: d_w % 4 == 0, i.e. all but the d_w = 30 shape); the entity-table update deferred behind
+    the tail or issued behind the entity chain (defer_re / defer_small: two streams, tail present); the lazy
+    word-table update (launch_lazy_word_update: tables of >= 4 M elements, here the 70000 x 300 one)."""
+    _vectorspace_steps(dims, egrad, monkeypatch, keep=0)
+
+
+def _vectorspace_steps(dims, egrad, monkeypatch, keep):
     # entity gradient: V_e <= 2048 takes the sort-free bucket + register-accumulator path by default;
     # 'sorted' forces the counting-sort + chunked-reduce path every vocabulary size can take;
     # 'strip_gemm' switches the opt-in strip-streaming projection GEMMs on (gemm_strip.h)
@@ -60,16 +90,22 @@ def test_vectorspace_steps(hip_lib, dims, egrad, monkeypatch):
     p = U.make_vs_problem(0, B * steps, n, z, dims['Vw'], dims['Ve'], dims['dw'], dims['de'],
                           zipf=True)
     lam = 0.01
-    eng = U.vs_engine(p, B, n, z, lam)
+    eng = U.vs_engine(p, B, n, z, lam, keep_grads=keep)
     eng.upload_dataset(C.SPLIT_TRAIN, p['X'], y_int=p['y'], w=p['w'])
     ora = O.VectorSpaceOracle(B, n, z, p['Rw'], p['Re'], p['W'], p['b'], lam)
+    o64 = None if keep else O.VectorSpaceOracle(B, n, z, p['Rw'], p['Re'], p['W'], p['b'], lam, dtype=np.float64)
     for s in range(steps):
         sl = slice(s * B, (s + 1) * B)
         neg = p['rng'].randint(0, dims['Ve'], size=(B, z)).astype(np.int64)
         loss_ref, grads_ref, f = ora.loss_and_grads(p['X'][sl], p['y'][sl], p['w'][sl], neg)
         ora.opt.update(ora.params(), grads_ref)
+        if o64 is not None:
+            o64.train_step(p['X'][sl], p['y'][sl], p['w'][sl], neg)
         loss = eng.train_batch(s, neg)
         assert abs(loss - loss_ref) <= LOSS_TOL * abs(loss_ref), (s, loss, loss_ref)
+        if not keep:
+            continue
+        _check_rowloss(eng, f, p['w'][sl])
         assert U.rel_err(eng.get_tensor(C.T_ACT_H, (B, dims['dw'])), f['h']) < ACT_TOL
         assert U.rel_err(eng.get_tensor(C.T_ACT_T, (B, dims['de'])), f['t']) < ACT_TOL
         assert U.rel_err(eng.get_tensor(C.T_ACT_DA, (B, dims['de'])), f['da']) < GRAD_TOL
@@ -83,6 +119,9 @@ def test_vectorspace_steps(hip_lib, dims, egrad, monkeypatch):
     assert U.rel_err(eng.get_tensor(C.T_RE), ora.R_e.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_W), ora.W.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_B), ora.b.ravel()) < PARAM_TOL
+    # the whole state: parameters and both Adam moments (the parameters alone do not see a gradient's scale)
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora),
+                                   None if o64 is None else U.oracle_state(o64))))
     # eval: unweighted, unregularised, no update
     neg = p['rng'].randint(0, dims['Ve'], size=(B, z)).astype(np.int64)
     before = eng.get_tensor(C.T_RW).copy()
@@ -394,14 +433,13 @@ def test_vectorspace_predict(hip_lib):
     eng.close()
 
 
-@pytest.mark.parametrize('labels', ['int', 'csr'])
-@pytest.mark.parametrize('dims', [
+LL_STEP_DIMS = [
     dict(B=32, n=4, Vw=300, Ve=53, d=24),
     dict(B=64, n=5, Vw=10000, Ve=100, d=64),     # C1-shaped
     dict(B=40, n=3, Vw=500, Ve=1000, d=30),
     dict(B=33, n=6, Vw=400, Ve=400, d=20),        # one wave per row, two float4 chunks per lane (ll_row_wave<2>)
     dict(B=21, n=7, Vw=300, Ve=2048, d=12),       # ... eight chunks per lane: the largest row the wave kernel takes
-    dict(B=8, n=10, Vw=300, Ve=3500, d=16),       # 154 KB slab: fused kernel
+    dict(B=8, n=10, Vw=300, Ve=3500, d=16),       # (n V + V) 4 = 154 000 B > 150 KB: just above the fused limit, streaming path
     dict(B=8, n=12, Vw=300, Ve=4000, d=16),       # > LDS: streaming path, one segment
     dict(B=5, n=5, Vw=300, Ve=12000, d=16),       # streaming path, 3 segments, 16-byte rows
     dict(B=4, n=4, Vw=200, Ve=9001, d=12),        # streaming path, ragged last segment, scalar rows
@@ -409,24 +447,40 @@ def test_vectorspace_predict(hip_lib):
     dict(B=37, n=6, Vw=400, Ve=300, d=32),        # ... another count of distinct words (odd / even K on 16-byte loaders)
     dict(B=512, n=8, Vw=3000, Ve=4096, d=128),    # dW = G^T.dZ of > 2 GFLOP: dW, combine and W, b update on the side stream;
                                                   # an odd number of distinct words through the 16-byte k-major loaders
-])
-def test_loglinear_steps(hip_lib, dims, labels):
+    # both sides of every boundary of ll_forward's training loss dispatch (step_softmax_loglinear.inc), at small B:
+    # one wave per row for V_e % 4 == 0 and V_e <= 2048, ll_row_wave<E> with E = ceil(V_e / 256) rounded up to 1/2/4/8
+    dict(B=9, n=3, Vw=300, Ve=256, d=16),         # ll_row_wave<1>, full last chunk
+    dict(B=9, n=3, Vw=300, Ve=260, d=16),         # ll_row_wave<2>, ragged last chunk (one float4 in the second)
+    dict(B=9, n=3, Vw=300, Ve=516, d=16),         # ll_row_wave<4> (three chunks used), ragged
+    dict(B=9, n=3, Vw=300, Ve=1028, d=16),        # ll_row_wave<8> (five chunks used), ragged
+    dict(B=9, n=3, Vw=300, Ve=2052, d=16),        # V_e % 4 == 0 but above 2048: ll_row_from_table<512>
+    dict(B=8, n=10, Vw=300, Ve=3400, d=16),       # (n V + V) 4 = 149 600 B: just under the 150 KB fused limit
+]
+
+
+def _ll_steps_run(dims, labels, keep):
     B, n = dims['B'], dims['n']
     steps = 3
     p = U.make_ll_problem(1, B * steps, n, dims['Vw'], dims['Ve'], dims['d'], labels)
     lam = 0.01
-    eng = U.ll_engine(p, B, n, lam)
+    eng = U.ll_engine(p, B, n, lam, keep_grads=keep)
     if labels == 'int':
         eng.upload_dataset(C.SPLIT_TRAIN, p['X'], y_int=p['y'], w=p['w'])
     else:
         eng.upload_dataset(C.SPLIT_TRAIN, p['X'], csr=p['y'], w=p['w'])
     ora = O.LogLinearOracle(B, n, p['Rw'], p['W'], p['b'], lam)
+    o64 = None if keep else O.LogLinearOracle(B, n, p['Rw'], p['W'], p['b'], lam, dtype=np.float64)
     for s in range(steps):
         sl = slice(s * B, (s + 1) * B)
         loss_ref, grads_ref, f = ora.loss_and_grads(p['X'][sl], p['ydense'][sl], p['w'][sl])
         ora.opt.update(ora.params(), grads_ref)
+        if o64 is not None:
+            o64.train_step(p['X'][sl], p['ydense'][sl], p['w'][sl])
         loss = eng.train_batch(s)
         assert abs(loss - loss_ref) <= LOSS_TOL * abs(loss_ref), (s, loss, loss_ref)
+        if not keep:
+            continue
+        _check_rowloss(eng, f, p['w'][sl])
         dRw, dW, db = grads_ref
         assert U.rel_err(eng.get_tensor(C.T_GRAD_W), dW.ravel()) < GRAD_TOL
         assert U.rel_err(eng.get_tensor(C.T_GRAD_B), db.ravel()) < GRAD_TOL
@@ -434,6 +488,9 @@ def test_loglinear_steps(hip_lib, dims, labels):
     assert U.rel_err(eng.get_tensor(C.T_RW), ora.R_w.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_W), ora.W.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_B), ora.b.ravel()) < PARAM_TOL
+    # the whole state: parameters, Adadelta's accu and delta
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora),
+                                   None if o64 is None else U.oracle_state(o64))))
     ev = eng.eval_batch(C.SPLIT_TRAIN, 0)
     ev_ref = ora.eval_loss(p['X'][:B], p['ydense'][:B])
     assert abs(ev - ev_ref) <= LOSS_TOL * abs(ev_ref)
@@ -442,6 +499,25 @@ def test_loglinear_steps(hip_lib, dims, labels):
     _, Pref = ora.token_distributions(p['X'][:7])
     assert U.rel_err(P, Pref) < 1e-5
     eng.close()
+
+
+@pytest.mark.parametrize('labels', ['int', 'csr'])
+@pytest.mark.parametrize('dims', LL_STEP_DIMS)
+def test_loglinear_steps(hip_lib, dims, labels):
+    _ll_steps_run(dims, labels, keep=1)
+
+
+@pytest.mark.parametrize('labels', ['int', 'csr'])
+@pytest.mark.parametrize('dims', LL_STEP_DIMS)
+def test_loglinear_steps_product_path(hip_lib, dims, labels):
+    """keep_grads = 0 twin of test_loglinear_steps: same problems, no tensor read until the last step, then the loss of
+    every step and the whole state (parameters, accu, delta) against the float32 and the float64 oracle.  Branches
+    only this setting takes (csrc/host): the dG = dZ.W^T GEMM whose epilogue stores row u as row uwords[u] of the
+    word-table gradient (step_softmax_loglinear.inc: distinct-word mode and !keep_grads, where the 64x64-tile kernel
+    takes the launch -- U d >= 16384, e.g. the C1-shaped and the V_e = 4096 shapes); the touched-row bitmaps of the
+    word table (use_touched_now: d % 4 == 0, all shapes here); the dW / combine / W, b update on the side stream at
+    V_e = 4096 (two streams, dW above the size bound) without a stored gradient."""
+    _ll_steps_run(dims, labels, keep=0)
 
 
 def test_loglinear_dense_heavy_words(hip_lib):
@@ -693,11 +769,21 @@ def test_vectorspace_edge_shapes(hip_lib, dims):
     for s in range(2):
         sl = slice(s * B, (s + 1) * B)
         neg = p['rng'].randint(0, dims['Ve'], size=(B, z)).astype(np.int64)
-        ref = ora.train_step(p['X'][sl], p['y'][sl], p['w'][sl], neg)
+        ref, grads, f = ora.loss_and_grads(p['X'][sl], p['y'][sl], p['w'][sl], neg)
+        ora.opt.update(ora.params(), grads)
         got = eng.train_batch(s, neg)
         assert abs(got - ref) <= LOSS_TOL * abs(ref)
+        # keep_grads = 1: the gradients themselves, globally and row by row (dW, db: the dense bound of util.py)
+        for name, which, g in (('dR_e', C.T_GRAD_RE, grads[0]), ('dR_w', C.T_GRAD_RW, grads[1]),
+                               ('dW', C.T_GRAD_W, grads[2]), ('db', C.T_GRAD_B, grads[3])):
+            g = g.reshape(1, -1) if g.ndim == 1 else g
+            U.check_tensor(name, eng.get_tensor(which, g.shape), g,
+                           row_tol32=U.ROW_TOL32_DENSE if name in ('dW', 'db') else U.ROW_TOL32)
+        _check_rowloss(eng, f, p['w'][sl])
     assert U.rel_err(eng.get_tensor(C.T_RW), ora.R_w.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_RE), ora.R_e.ravel()) < PARAM_TOL
+    # W, b and both Adam moments of every parameter: read nowhere else at these shapes
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora))))
     with pytest.raises(C.SertError):
         eng.train_batch(3)            # beyond the data (an incomplete tail batch does not exist)
     eng.close()
@@ -749,17 +835,35 @@ def test_model_with_empty_validation_and_short_data(hip_lib):
         m.train()
 
 
-@pytest.mark.parametrize('dims', [
+FS_STEP_DIMS = [
     dict(B=64, n=5, Vw=500, Ve=37, dw=32, de=48),
     dict(B=96, n=3, Vw=200, Ve=1000, dw=30, de=68),
     dict(B=256, n=10, Vw=3000, Ve=1000, dw=128, de=128),     # C2-shaped
-])
+]
+
+
+@pytest.mark.parametrize('dims', FS_STEP_DIMS)
 @pytest.mark.parametrize('tile', [None, 40])
 def test_vectorspace_softmax_variant_steps(hip_lib, dims, tile, monkeypatch):
     """Additive full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX) vs its oracle; tile = 40: the logits
     exist for 40 rows at a time (the path that keeps the C4 configuration's 26 GB logit matrix at 1.6 GB:
     per row tile logits, cross-entropy, dR_e += dZ^T.p through the accumulating GEMM epilogue, dp = dZ.R_e;
     ragged last tile)."""
+    _softmax_steps(dims, tile, monkeypatch, keep=1)
+
+
+@pytest.mark.parametrize('dims', FS_STEP_DIMS)
+@pytest.mark.parametrize('tile', [None, 40])
+def test_vectorspace_softmax_variant_steps_product_path(hip_lib, dims, tile, monkeypatch):
+    """keep_grads = 0 twin of test_vectorspace_softmax_variant_steps: no tensor read until the last step, then the loss
+    of every step and the whole state (parameters, m, v) against the float32 and the float64 oracle.  Branches only
+    this setting takes (csrc/host): the touched-row bitmaps of the word table (use_touched_now: d_w % 4 == 0, the
+    d_w = 32 and 128 shapes); no stored gradient for the dense update of R_e, W and b, whose gradient buffers are
+    scratch (vs_tail is vectorspace-only: this kind updates W and b in the optimiser's own launches)."""
+    _softmax_steps(dims, tile, monkeypatch, keep=0)
+
+
+def _softmax_steps(dims, tile, monkeypatch, keep):
     if tile:
         monkeypatch.setenv('SERT_FS_TILE_ROWS', str(tile))
     B, n = dims['B'], dims['n']
@@ -768,18 +872,24 @@ def test_vectorspace_softmax_variant_steps(hip_lib, dims, tile, monkeypatch):
     eng = C.Engine(kind=C.KIND_VECTORSPACE_SOFTMAX, batch_size=B, global_batch_size=B, window_size=n,
                    vocab_size=dims['Vw'], num_entities=dims['Ve'], word_dim=dims['dw'],
                    entity_dim=dims['de'], num_negatives=0, id_bytes=p['X'].dtype.itemsize, device=0,
-                   keep_grads=1, deterministic=1, lambda_=0.01, lr=1e-3, beta1=0.9, beta2=0.999,
+                   keep_grads=keep, deterministic=1, lambda_=0.01, lr=1e-3, beta1=0.9, beta2=0.999,
                    eps=1e-8, seed=1)
     for which, a in ((C.T_RW, p['Rw']), (C.T_RE, p['Re']), (C.T_W, p['W']), (C.T_B, p['b'])):
         eng.set_tensor(which, a)
     eng.upload_dataset(C.SPLIT_TRAIN, p['X'], y_int=p['y'], w=p['w'])
     ora = O.VectorSpaceSoftmaxOracle(B, n, p['Rw'], p['Re'], p['W'], p['b'], 0.01)
+    o64 = None if keep else O.VectorSpaceSoftmaxOracle(B, n, p['Rw'], p['Re'], p['W'], p['b'], 0.01, dtype=np.float64)
     for s in range(steps):
         sl = slice(s * B, (s + 1) * B)
         loss_ref, grads_ref, f = ora.loss_and_grads(p['X'][sl], p['y'][sl], p['w'][sl])
         ora.opt.update(ora.params(), grads_ref)
+        if o64 is not None:
+            o64.train_step(p['X'][sl], p['y'][sl], p['w'][sl])
         loss = eng.train_batch(s)
         assert abs(loss - loss_ref) <= LOSS_TOL * abs(loss_ref), (s, loss, loss_ref)
+        if not keep:
+            continue
+        _check_rowloss(eng, f, p['w'][sl])
         dRe, dRw, dW, db = grads_ref
         assert U.rel_err(eng.get_tensor(C.T_GRAD_RE), dRe.ravel()) < GRAD_TOL
         assert U.rel_err(eng.get_tensor(C.T_GRAD_RW), dRw.ravel()) < GRAD_TOL
@@ -787,6 +897,8 @@ def test_vectorspace_softmax_variant_steps(hip_lib, dims, tile, monkeypatch):
         assert U.rel_err(eng.get_tensor(C.T_GRAD_B), db.ravel()) < GRAD_TOL
     assert U.rel_err(eng.get_tensor(C.T_RW), ora.R_w.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_RE), ora.R_e.ravel()) < PARAM_TOL
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora),
+                                   None if o64 is None else U.oracle_state(o64))))
     ev = eng.eval_batch(C.SPLIT_TRAIN, 0)
     ev_ref = ora.eval_loss(p['X'][:B], p['y'][:B])
     assert abs(ev - ev_ref) <= LOSS_TOL * abs(ev_ref)
@@ -933,6 +1045,8 @@ def test_parameters_after_100_steps(hip_lib, kind):
         pairs = [(C.T_RW, ora.R_w), (C.T_W, ora.W), (C.T_B, ora.b)]
     for which, ref in pairs:
         assert U.rel_err(eng.get_tensor(which), np.asarray(ref).ravel()) < 1e-4, which
+    # and both optimiser moments of every parameter (Adam's parameters do not see a constant gradient factor)
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora))))
     eng.close()
 
 
@@ -958,6 +1072,8 @@ def test_loglinear_dg_rows_stored_through_the_row_map(hip_lib):
         assert U.rel_err(eng.get_tensor(which), np.asarray(ref).ravel()) < PARAM_TOL, which
     # Adadelta's accumulators of the word table: a row that took a wrong gradient row shows here first
     assert U.rel_err(eng.get_tensor(C.T_STATE0_RW), ora.opt.accu[0].ravel()) < PARAM_TOL
+    # ... and row by row, with delta and the state of W and b
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora))))
     eng.close()
 
 
@@ -1006,6 +1122,9 @@ def test_loglinear_with_saturated_probabilities(hip_lib, dims, keep):
             assert U.rel_err(eng.get_tensor(C.T_GRAD_RW), dRw.ravel()) < GRAD_TOL
     assert U.rel_err(eng.get_tensor(C.T_W), ora.W.ravel()) < PARAM_TOL
     assert U.rel_err(eng.get_tensor(C.T_RW), ora.R_w.ravel()) < PARAM_TOL
+    if not keep:
+        # the distinct-word path's whole state, against the FLOAT32 oracle only: the clip masks are fp32 decisions
+        print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora))))
     eng.close()
 
 

@@ -64,6 +64,8 @@ def test_every_skip_shape_against_the_dense_launch_and_the_oracle(hip_lib, kind,
                 eng.set_step(eng.get_step())                # (so does a write of the step counter)
         counts = eng.update_counts()
         outs.append((losses, eng.get_tensor(C.T_RW).copy(), eng.get_tensor(C.T_STATE0_RW).copy(), eng.get_tensor(C.T_STATE1_RW).copy(), counts))
+        if not keep:
+            state = U.engine_state(eng)
         eng.close()
     # the forms that ran: keep_grads = 1 the dense launch every step; the product configuration the named shape of
     # dense_update_skip, as passes that read everything and as sparse ones
@@ -94,3 +96,6 @@ def test_every_skip_shape_against_the_dense_launch_and_the_oracle(hip_lib, kind,
     k = 1 if kind == 'vectorspace' else 0          # oracle parameter order [R_e, R_w, W, b] / [R_w, W, b]
     s0, s1 = (ora.opt.m[k], ora.opt.v[k]) if kind == 'vectorspace' else (ora.opt.accu[k], ora.opt.delta[k])
     assert U.rel_err(outs[1][2].reshape(Vw, d), s0) < 1e-4 and U.rel_err(outs[1][3].reshape(Vw, d), s1) < 1e-4
+    # the rest of the product run's state -- R_e, W, b and their moments (vectorspace), W, b and theirs (loglinear) --
+    # and the word table's moments row by row
+    print('\n'.join(U.check_state(state, U.oracle_state(ora))))

@@ -180,6 +180,9 @@ def test_timed_mode_loglinear_at_the_w3c_settings(hip_lib):
         assert U.rel_err(got[k], want[k]) < 1e-4, (k, U.rel_err(got[k], want[k]))
     err, row = U.row_err(got['R_w'], want['R_w'])
     assert err < 1e-4, (err, row)
+    # the bias with both Adadelta accumulators, and accu of the word table row by row (util.check_state's bounds)
+    print('\n'.join(U.check_state(U.engine_state(eng), U.oracle_state(ora),
+                                   names=['b', 'accu.b', 'delta.b', 'accu.R_w', 'delta.R_w'])))
     del model
 
 

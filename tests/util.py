@@ -107,3 +107,112 @@ def ll_engine(p, B, n, lam, device=0, keep_grads=1, global_batch=None):
     e.set_tensor(C.T_W, p['W'])
     e.set_tensor(C.T_B, p['b'])
     return e
+
+
+# --------------------------------------------------------------------------- #
+# Parameters AND optimiser state against the oracle
+# --------------------------------------------------------------------------- #
+# Neither the loss (forward only) nor the parameters see how large a gradient is: Adam's first update is
+# lr * sign(g) wherever |g| >> sqrt(eps / (1 - beta2)), m_hat / sqrt(v_hat) does not change when every step's gradient
+# is scaled by one positive factor, and Adadelta's first update saturates at +-sqrt(eps / (1 - rho)).  The moments
+# do: m = (1 - beta1) g, v = (1 - beta2) g^2, accu = (1 - rho) g^2 after one step from a zero state.
+
+TENSOR_TOL = 1e-4        # parameters (and optimiser moments), relative to the tensor's max
+ROW_TOL32 = 2e-4         # row-wise, against the float32 oracle (sequential fp32 sums on the oracle's side)
+ROW_TOL64 = 5e-5         # row-wise, against the float64 evaluation of the same oracle
+ROW_TOL32_DENSE = 1e-3   # W, b and their moments against the float32 oracle: batch-long cancelling sums on both sides
+
+# tensor ids of a parameter and of its two optimiser moments (STATE0 = Adam m / Adadelta accu, STATE1 = v / delta)
+STATE_IDS = {'R_w': (C.T_RW, C.T_STATE0_RW, C.T_STATE1_RW), 'R_e': (C.T_RE, C.T_STATE0_RE, C.T_STATE1_RE),
+             'W': (C.T_W, C.T_STATE0_W, C.T_STATE1_W), 'b': (C.T_B, C.T_STATE0_B, C.T_STATE1_B)}
+# the oracle's parameter order (models.py:542-543): [R_e, R_w, W, b] (vectorspace, both kinds) or [R_w, W, b]
+VS_PARAMS, LL_PARAMS = ('R_e', 'R_w', 'W', 'b'), ('R_w', 'W', 'b')
+SECOND_MOMENTS = ('v', 'accu', 'delta')     # sums of squares: twice the row-wise relative error of g
+
+
+def state_shapes(cfg):
+    """(rows, cols) of every parameter of an engine config; b as one row."""
+    if cfg.kind == C.KIND_LOGLINEAR:
+        return {'R_w': (cfg.vocab_size, cfg.word_dim), 'W': (cfg.word_dim, cfg.num_entities),
+                'b': (1, cfg.num_entities)}
+    return {'R_w': (cfg.vocab_size, cfg.word_dim), 'R_e': (cfg.num_entities, cfg.entity_dim),
+            'W': (cfg.word_dim, cfg.entity_dim), 'b': (1, cfg.entity_dim)}
+
+
+def engine_state(eng, kind=None):
+    """Every parameter and both optimiser moments of an engine, named as oracle_state names them.  Read through
+    get_tensor: each read flushes the lazy word-table rows and settles the tail first."""
+    kind = eng.cfg.kind if kind is None else kind
+    assert kind == eng.cfg.kind, (kind, eng.cfg.kind)
+    moments = ('accu', 'delta') if kind == C.KIND_LOGLINEAR else ('m', 'v')
+    out = {}
+    for name, shape in state_shapes(eng.cfg).items():
+        par, s0, s1 = STATE_IDS[name]
+        out[name] = eng.get_tensor(par, shape)
+        out[moments[0] + '.' + name] = eng.get_tensor(s0, shape)
+        out[moments[1] + '.' + name] = eng.get_tensor(s1, shape)
+    return out
+
+
+def oracle_state(ora):
+    """The same dict from an oracle object, in the oracle's dtype.  Entries are reshaped VIEWS of the oracle's arrays
+    (no copies of 600 MB tables): the optimiser updates them in place, so take the dict after the last step."""
+    params = ora.params()
+    names = VS_PARAMS if len(params) == 4 else LL_PARAMS
+    assert len(params) == len(names)
+    if hasattr(ora.opt, 'accu'):
+        moments = (('accu', ora.opt.accu), ('delta', ora.opt.delta))
+    else:
+        moments = (('m', ora.opt.m), ('v', ora.opt.v))
+    out = {}
+    for k, name in enumerate(names):
+        shape = (1, -1) if name == 'b' else params[k].shape
+        out[name] = np.asarray(params[k]).reshape(shape)
+        for mname, arrs in moments:
+            out[mname + '.' + name] = np.asarray(arrs[k]).reshape(shape)
+    return out
+
+
+def check_tensor(name, got, ref32, ref64=None, rows=None, row_tol32=ROW_TOL32, row_tol64=ROW_TOL64):
+    """global + row-wise bounds for one (rows, cols) tensor; returns the figures for the log line."""
+    g = rel_err(got, ref32)
+    assert g < TENSOR_TOL, (name, 'rel_err', g)
+    r32, at32 = row_err(got, ref32, rows)
+    assert r32 < row_tol32, (name, 'row_err vs float32 oracle', r32, 'row', at32, 'tolerance', row_tol32,
+                             'W, b and their moments take %g against the FLOAT32 oracle -- batch-long cancelling sums, the '
+                             'oracle\'s own BLAS sum is 3.7e-4 off row-wise at C4 -- and the float64 bound (%g) does the '
+                             'testing where a float64 reference is given' % (ROW_TOL32_DENSE, ROW_TOL64))
+    out = '%s rel %.1e row32 %.1e' % (name, g, r32)
+    if ref64 is not None:
+        r64, at64 = row_err(got, ref64, rows)
+        o64, _ = row_err(ref32, ref64, rows)
+        assert r64 < row_tol64, (name, 'row_err vs float64 oracle', r64, 'row', at64, 'tolerance', row_tol64)
+        out += ' row64 %.1e (oracle32 vs 64: %.1e)' % (r64, o64)
+    return out
+
+
+def state_row_tol32(name):
+    """Row bound against the float32 oracle for one state entry: ROW_TOL32 for the parameters and the tables' moments,
+    ROW_TOL32_DENSE for the moments of W and b, twice either for a second moment."""
+    moment, _, par = name.rpartition('.')
+    if not moment:
+        return ROW_TOL32
+    rt = ROW_TOL32_DENSE if par in ('W', 'b') else ROW_TOL32
+    return 2 * rt if moment in SECOND_MOMENTS else rt
+
+
+def check_state(got, ref32, ref64=None, rows=None, names=None, prefix=''):
+    """Check every entry of oracle_state(...) -- parameters and both moments -- globally and row by row.
+    got / ref32 / ref64: dicts of engine_state / oracle_state.  rows: {parameter name: row indices} restricts the
+    row-wise maximum of that parameter and its moments (e.g. the rows a batch touches); names: a subset of the keys.
+    Returns the log lines."""
+    names = list(ref32) if names is None else list(names)
+    missing = [k for k in names if k not in got]
+    assert not missing, ('state entries not read', missing)
+    log = []
+    for k in names:
+        sub = (rows or {}).get(k.rpartition('.')[2])
+        square = k.rpartition('.')[0] in SECOND_MOMENTS
+        log.append(prefix + check_tensor(k, got[k], ref32[k], None if ref64 is None else ref64[k], rows=sub,
+                                         row_tol32=state_row_tol32(k), row_tol64=(2 if square else 1) * ROW_TOL64))
+    return log
