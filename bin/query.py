@@ -10,7 +10,11 @@ Writes ``<run_out>_debug``, ``<run_out>_ep`` (topics per entity) and
 ``<run_out>_ef`` (entities per topic) (query.py:94, :149-156).
 
 Additive flags: --no_batch (score one query at a time like the reference
-instead of all queries in one device call), --device.
+instead of all queries in one device call), --device.  Both model kinds take
+the batched path by default: vectorspace through VectorSpaceCallback.process_batch,
+loglinear through LogLinearPredictFn.rank_queries + LogLinearCallback.process_batch
+(the per-token distributions stay on the device; every entity is ranked and --top
+is ignored, as in the reference, query.py:199-236).
 """
 import argparse
 import collections

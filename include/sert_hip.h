@@ -205,6 +205,35 @@ int sert_predict_project(sert_model* m, const float* avg, int64_t num_queries, f
  * distributions out (rows, n, V_e).  rows need not equal batch_size. */
 int sert_predict_tokens(sert_model* m, const void* ids, int64_t rows, float* out);
 
+/* ---- loglinear query ranking (bin/query.py:199-236, batched) ----------- */
+
+/* Per-query status of sert_ll_rank_queries */
+enum {
+    SERT_LL_STATUS_DEVICE = 0, /* ranked on the device */
+    SERT_LL_STATUS_HOST = 1    /* the joint's sum S is 0 or not finite: the reference's `joint /= joint.sum()` gives NaN
+                                  and logs the non-normalised-mass error (query.py:213-219); the caller runs the query
+                                  through the per-token host path (sert_predict_tokens + LogLinearCallback.process).
+                                  Its idx / score rows and joint entropy are not meaningful. */
+};
+
+/* WordBatcher -> predict_fn -> LogLinearCallback.process for Q queries at once (sert/inference.py:28-143, :170-174;
+ * bin/query.py:199-236): the per-token entity distributions are computed once per distinct token and never leave the
+ * device.  For every query q with tokens[offsets[q] .. offsets[q+1]) (ids < vocab_size, at least one per query):
+ *   L_e = sum_t (p_te > 0 ? log p_te : 0) in token order, j_e = exp(L_e), score_e = j_e / sum_e j_e
+ *     (inference.py:174 product with log 0 -> 0, query.py:213-214 renormalisation)
+ *   idx_out (Q, kk) int32 / score_out (Q, kk) f32: the kk best entities, score descending, entity index ascending
+ *     (query.py:231 argsort reversed, ties in a fixed order); kk = V_e for k = -1 (every entity, as the reference ranks)
+ *     or k >= V_e, else k
+ *   joint_entropy_out (Q) f32: normalised base-2 entropy of the joint (query.py:222-226 _debug line)
+ *   token_entropy_out (offsets[Q]) f32: normalised base-2 entropy of every token's distribution (query.py:209)
+ *   status_out (Q) int32: SERT_LL_STATUS_*
+ * A query's results do not depend on the other queries of the call or on how the call is cut into chunks
+ * (SERT_LL_RANK_BUDGET: device bytes per chunk, default 2 GiB).  Same preconditions as sert_predict_tokens; like it,
+ * COLLECTIVE in data parallel (the word table is first all-gathered). */
+int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
+                         int32_t* idx_out, float* score_out, float* joint_entropy_out, float* token_entropy_out,
+                         int32_t* status_out);
+
 /* ---- entity scoring (bin/query.py:239-370, batched) --------------------- */
 
 typedef struct sert_scorer sert_scorer;

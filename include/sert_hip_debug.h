@@ -57,6 +57,13 @@ int sert_debug_word_index_sum(const void* ids, int id_bytes, int64_t num_batches
                               int dense_heavy, int64_t batch, const float* src, int d, float divisor, float* grad_out,
                               int64_t* stats);
 
+/* Test hook: the aggregate and ranking kernels of sert_ll_rank_queries on per-token distributions the caller provides,
+ * P (offsets[Q], V) f32 host, rows in query order; same outputs as sert_ll_rank_queries.  Pins the device ranking to the
+ * reference's recorded LogLinearCallback outputs (tests/test_gpu_ll_rank.py). */
+int sert_debug_ll_rank_distributions(int device, const float* P, const int64_t* offsets, int64_t num_queries, int32_t V,
+                                     int32_t k, int32_t* idx_out, float* score_out, float* joint_entropy_out,
+                                     float* token_entropy_out, int32_t* status_out);
+
 /* Micro-benchmark of the fp32 MFMA GEMM on device-resident random operands:
  * C (M,N) = op(A).op(B); ta/tb as in gemm.h; epi 0 = store, 1 = +bias, 2 = tanh(+bias);
  * splits > 1 = split-K partial slabs.  Returns the average launch time in *avg_us

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('SERT_LIB') or os.path.join(_HERE, 'libsert_hip.so')
 
 KIND_LOGLINEAR, KIND_VECTORSPACE, KIND_VECTORSPACE_SOFTMAX = 0, 1, 2
 SPLIT_TRAIN, SPLIT_VALIDATE = 0, 1
+LL_STATUS_DEVICE, LL_STATUS_HOST = 0, 1      # sert_ll_rank_queries' per-query status
 
 T_RW, T_RE, T_W, T_B = 0, 1, 2, 3
 T_STATE0_RW, T_STATE0_RE, T_STATE0_W, T_STATE0_B = 4, 5, 6, 7
@@ -30,13 +31,13 @@ EXPORTS = [
     'sert_set_eval_draws', 'sert_get_eval_draws', 'sert_negatives_of_step',
     'sert_upload_dataset', 'sert_train_batch', 'sert_hint_next_batch', 'sert_train_batches',
     'sert_eval_batch', 'sert_eval_batches',
-    'sert_predict_project', 'sert_predict_tokens', 'sert_score_topk',
+    'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_score_topk',
     'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_scores',
     'sert_host_alloc', 'sert_host_free',
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_poison_scratch',
+    'sert_debug_update_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 
@@ -117,6 +118,7 @@ def load():
     lib.sert_eval_batches.argtypes = [vp, ctypes.c_int, ctypes.c_void_p, i64, ctypes.c_void_p]
     lib.sert_predict_project.argtypes = [vp, fp, i64, fp]
     lib.sert_predict_tokens.argtypes = [vp, fp, i64, fp]
+    lib.sert_ll_rank_queries.argtypes = [vp, fp, fp, i64, i32, fp, fp, fp, fp, fp]
     lib.sert_score_topk.argtypes = [ctypes.c_int, fp, i64, i32, fp, i64, i32, fp, fp]
     lib.sert_scorer_create.argtypes = [ctypes.c_int, fp, i64, i32, ctypes.POINTER(vp)]
     lib.sert_scorer_destroy.argtypes = [vp]
@@ -318,6 +320,13 @@ class Engine(object):
         check(self._lib.sert_predict_tokens(self._h, ids.ctypes.data, rows, out.ctypes.data))
         return out
 
+    def ll_rank_queries(self, token_lists, k=None):
+        """sert_ll_rank_queries: (idx (Q, kk) int32, score (Q, kk) f32, joint_entropy (Q,), token_entropy (T,),
+        status (Q,) int32, offsets (Q + 1,) int64); kk = V_e for k None or k >= V_e."""
+        tokens, offsets = _concat_queries(token_lists)
+        return _ll_rank_call(self.cfg.num_entities, offsets, k, lambda kk, outs: self._lib.sert_ll_rank_queries(
+            self._h, tokens.ctypes.data, offsets.ctypes.data, offsets.size - 1, kk, *outs), tokens.size)
+
     # data parallel
     def comm_init(self, unique_id, rank, world):
         assert len(unique_id) == COMM_ID_BYTES
@@ -396,6 +405,41 @@ def comm_unique_id():
     buf = ctypes.create_string_buffer(COMM_ID_BYTES)
     check(load().sert_comm_unique_id(buf))
     return buf.raw
+
+
+def _concat_queries(token_lists):
+    lengths = np.fromiter((len(t) for t in token_lists), dtype=np.int64, count=len(token_lists))
+    offsets = np.zeros(len(token_lists) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    tokens = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int64) for t in token_lists])
+                                  if len(token_lists) else np.zeros(0, np.int64), dtype=np.int32)
+    return tokens, offsets
+
+
+def _ll_rank_call(num_entities, offsets, k, call, num_tokens):
+    q = offsets.size - 1
+    kk = num_entities if k is None or k >= num_entities else int(k)
+    idx = np.empty((q, kk), dtype=np.int32)
+    score = np.empty((q, kk), dtype=np.float32)
+    joint_h = np.empty(q, dtype=np.float32)
+    token_h = np.empty(num_tokens, dtype=np.float32)
+    status = np.empty(q, dtype=np.int32)
+    outs = [a.ctypes.data for a in (idx, score, joint_h, token_h, status)]
+    check(call(-1 if k is None else int(k), outs))
+    return idx, score, joint_h, token_h, status, offsets
+
+
+def debug_ll_rank_distributions(distributions, offsets, k=None, device=0):
+    """sert_debug_ll_rank_distributions: the ranking kernels of sert_ll_rank_queries on per-token distributions
+    (offsets[-1], V_e) given here; same outputs as Engine.ll_rank_queries."""
+    lib = load()
+    P = np.ascontiguousarray(distributions, dtype=np.float32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    assert P.ndim == 2 and P.shape[0] == offsets[-1]
+    lib.sert_debug_ll_rank_distributions.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                     ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 5
+    return _ll_rank_call(P.shape[1], offsets, k, lambda kk, outs: lib.sert_debug_ll_rank_distributions(
+        device, P.ctypes.data, offsets.ctypes.data, offsets.size - 1, P.shape[1], kk, *outs), P.shape[0])
 
 
 def score_topk(entities, projections, k, device=0):

@@ -1,0 +1,269 @@
+// Batched loglinear query ranking (include/sert_hip.h: sert_ll_rank_queries; include/sert_hip_debug.h:
+// sert_debug_ll_rank_distributions).  Replaces, for all queries of a call at once, the reference's
+// WordBatcher -> predict_fn -> LogLinearCallback.process chain (sert/inference.py:28-143, :170-174;
+// bin/query.py:199-236): the per-token distributions stay on the device (kernels_ll_rank.h).
+
+// Logits GEMM in slabs of this many rows: every launch has the shape (kLLRankRows, V_e, d_w), whatever the number of
+// queries or distinct tokens, so launch_gemm picks the same kernel and tiling for every slab -- a token's distribution
+// (and so a query's ranking) does not depend on the other queries of the call or on the chunking.
+static const int kLLRankRows = 1024;
+
+// SERT_LL_RANK_BUDGET: device bytes one chunk of a call may use (distributions, gathered rows, joint rows, sort scratch)
+static size_t ll_rank_budget() {
+    const char* e = knob("SERT_LL_RANK_BUDGET");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (size_t)v : ((size_t)2 << 30);
+}
+
+enum { LL_RANK_TOPK = 0, LL_RANK_LDS = 1, LL_RANK_CSORT = 2 };
+static int ll_rank_mode(int V, int kk) {
+    if (kk <= kTopKMax && kk < V) return LL_RANK_TOPK;
+    return V <= kLLRankLdsMax ? LL_RANK_LDS : LL_RANK_CSORT;
+}
+
+// device scratch of one call, sized for its largest chunk
+struct LLRankScratch {
+    uint32_t* ids = nullptr;       // distinct token ids of the chunk (padded to whole slabs with id 0)
+    int32_t* tok_row = nullptr;    // row of every token of the chunk
+    int64_t* offs = nullptr;       // chunk-relative query offsets
+    float *G = nullptr, *P = nullptr, *J = nullptr, *tok_h = nullptr, *joint_h = nullptr, *val = nullptr;
+    int32_t *status = nullptr, *idx = nullptr;
+    int32_t *ka = nullptr, *va = nullptr, *kb = nullptr, *vb = nullptr, *hist = nullptr, *bin_total = nullptr;
+    ~LLRankScratch() {
+        for (void* p : {(void*)ids, (void*)tok_row, (void*)offs, (void*)G, (void*)P, (void*)J, (void*)tok_h, (void*)joint_h,
+                        (void*)val, (void*)status, (void*)idx, (void*)ka, (void*)va, (void*)kb, (void*)vb, (void*)hist,
+                        (void*)bin_total})
+            (void)hipFree(p);
+    }
+};
+
+static size_t ll_rank_sort_bytes(int mode, int64_t n) {
+    if (mode != LL_RANK_CSORT) return 0;
+    return (size_t)n * 16 + (size_t)kSortMaxBins * cdiv(n, kSortTile) * 4;
+}
+
+static int ll_rank_alloc(LLRankScratch& w, int mode, int64_t rows, int64_t T, int64_t Qc, int V, int d, int kk) {
+    SERT_TRY(dmalloc(&w.ids, (size_t)rows));
+    SERT_TRY(dmalloc(&w.tok_row, (size_t)T));
+    SERT_TRY(dmalloc(&w.offs, (size_t)Qc + 1));
+    if (d > 0) SERT_TRY(dmalloc(&w.G, (size_t)rows * d));
+    if (d > 0) SERT_TRY(dmalloc(&w.P, (size_t)rows * V));
+    SERT_TRY(dmalloc(&w.J, (size_t)Qc * V));
+    SERT_TRY(dmalloc(&w.tok_h, (size_t)rows));
+    SERT_TRY(dmalloc(&w.joint_h, (size_t)Qc));
+    SERT_TRY(dmalloc(&w.status, (size_t)Qc));
+    SERT_TRY(dmalloc(&w.idx, (size_t)Qc * kk));
+    SERT_TRY(dmalloc(&w.val, (size_t)Qc * kk));
+    if (mode == LL_RANK_CSORT) {
+        const size_t n = (size_t)Qc * V;
+        SERT_TRY(dmalloc(&w.ka, n)); SERT_TRY(dmalloc(&w.va, n));
+        SERT_TRY(dmalloc(&w.kb, n)); SERT_TRY(dmalloc(&w.vb, n));
+        SERT_TRY(dmalloc(&w.hist, (size_t)kSortMaxBins * cdiv((int64_t)n, kSortTile)));
+        SERT_TRY(dmalloc(&w.bin_total, (size_t)kSortMaxBins));
+    }
+    return 0;
+}
+
+// one stable counting-sort digit pass (kernels_sort.h)
+static void ll_rank_sort_pass(hipStream_t s, LLRankScratch& w, const int32_t* kin, const int32_t* vin, int32_t* kout,
+                              int32_t* vout, int n, int shift, int nb) {
+    const int tiles = cdiv(n, kSortTile);
+    hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nb, tiles, w.hist, (int32_t*)nullptr, 0);
+    hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nb, 4)), dim3(256), 0, s, w.hist, 1 << nb, tiles, w.bin_total);
+    hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nb, tiles, w.hist,
+                       w.bin_total);
+}
+
+// the two float32 constants of math_utils.entropy(..., base=2, normalize=True): float(log(2)), float(log(V) / log(2))
+static float ll_ln2_f() { return (float)log(2.0); }
+static float ll_log2v_f(int V) { return (float)(log((double)V) / log(2.0)); }
+
+// P holds the chunk's per-token distributions (rows indexed by w.tok_row), w.offs its Qc + 1 query offsets: joint rows,
+// entropies, status and the ranking (w.idx / w.val, Qc x kk) on stream s
+
+static int ll_rank_chunk(hipStream_t s, LLRankScratch& w, const float* P, int Qc, int V, int kk, int mode) {
+    hipLaunchKernelGGL(ll_query_aggregate, dim3(Qc), dim3(256), 0, s, P, w.tok_row, w.offs, V, ll_ln2_f(), ll_log2v_f(V),
+                       w.J, w.joint_h, w.status);
+    if (mode == LL_RANK_TOPK) {
+        hipLaunchKernelGGL(topk_rows<true>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val, (float*)nullptr);
+    } else if (mode == LL_RANK_LDS) {
+        if (V <= 1024)      hipLaunchKernelGGL(ll_rank_lds<1024>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
+        else if (V <= 2048) hipLaunchKernelGGL(ll_rank_lds<2048>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
+        else if (V <= 4096) hipLaunchKernelGGL(ll_rank_lds<4096>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
+        else                hipLaunchKernelGGL(ll_rank_lds<kLLRankLdsMax>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
+    } else {
+        // score key in 11 + 11 + 10-bit digits over iota values, then the query index: stability keeps, inside a query,
+        // the score order and, among equal scores, the entity order
+        const int n = Qc * V;
+        hipLaunchKernelGGL(ll_score_keys, dim3(grid_for(n)), dim3(256), 0, s, w.J, n, w.ka);
+        ll_rank_sort_pass(s, w, w.ka, nullptr, w.kb, w.vb, n, 0, 11);
+        ll_rank_sort_pass(s, w, w.kb, w.vb, w.ka, w.va, n, 11, 11);
+        ll_rank_sort_pass(s, w, w.ka, w.va, w.kb, w.vb, n, 22, 10);
+        int qbits = 1;
+        while ((1 << qbits) < Qc) ++qbits;
+        hipLaunchKernelGGL(ll_query_keys, dim3(grid_for(n)), dim3(256), 0, s, w.vb, n, V, w.kb);
+        ll_rank_sort_pass(s, w, w.kb, w.vb, w.ka, w.va, n, 0, qbits);
+        hipLaunchKernelGGL(ll_emit_sorted, dim3(grid_for((int64_t)Qc * kk)), dim3(256), 0, s, w.va, w.J, Qc, V, kk, w.idx, w.val);
+    }
+    SERT_HIP(hipGetLastError());
+    return 0;
+}
+
+static int ll_rank_copy_out(hipStream_t s, LLRankScratch& w, int64_t q0, int Qc, int kk, int32_t* idx_out, float* score_out,
+                            float* joint_entropy_out, int32_t* status_out) {
+    SERT_HIP(hipMemcpyAsync(idx_out + q0 * kk, w.idx, (size_t)Qc * kk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SERT_HIP(hipMemcpyAsync(score_out + q0 * kk, w.val, (size_t)Qc * kk * sizeof(float), hipMemcpyDeviceToHost, s));
+    SERT_HIP(hipMemcpyAsync(joint_entropy_out + q0, w.joint_h, (size_t)Qc * sizeof(float), hipMemcpyDeviceToHost, s));
+    SERT_HIP(hipMemcpyAsync(status_out + q0, w.status, (size_t)Qc * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+static int ll_rank_check_offsets(const int64_t* offsets, int64_t Q) {
+    if (offsets[0] != 0) SERT_FAIL("offsets[0] must be 0");
+    for (int64_t q = 0; q < Q; ++q)
+        if (offsets[q + 1] <= offsets[q]) SERT_FAIL("every query needs at least one token (offsets must increase)");
+    return 0;
+}
+
+int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
+                         int32_t* idx_out, float* score_out, float* joint_entropy_out, float* token_entropy_out,
+                         int32_t* status_out) {
+    refresh_gemm_choice();
+    if (!m || !tokens || !offsets || !idx_out || !score_out || !joint_entropy_out || !token_entropy_out || !status_out)
+        SERT_FAIL("null argument");
+    if (is_vs(m)) SERT_FAIL("sert_ll_rank_queries ranks with the loglinear model");
+    if (k == 0 || k < -1) SERT_FAIL("k must be -1 (all entities) or positive");
+    if (num_queries <= 0) return 0;
+    SERT_TRY(ll_rank_check_offsets(offsets, num_queries));
+    const auto& c = m->cfg;
+    const int V = c.num_entities, d = c.word_dim;
+    const int64_t T = offsets[num_queries];
+    for (int64_t t = 0; t < T; ++t)
+        if (tokens[t] < 0 || tokens[t] >= c.vocab_size) SERT_FAIL("token id out of range [0, vocab_size)");
+    SERT_HIP(hipSetDevice(c.device));
+    SERT_TRY(ensure_full_rw(m));
+    SERT_TRY(ensure_rw_current(m, -1));
+    const int kk = (k < 0 || k >= V) ? V : k;
+    const int mode = ll_rank_mode(V, kk);
+
+    // ---- chunks: consecutive queries while distinct rows x V_e + joint rows + sort scratch fit the budget ----
+    const size_t budget = ll_rank_budget();
+    auto bytes = [&](int64_t D, int64_t Qc) -> size_t {
+        const size_t rows = (size_t)cdiv(D, kLLRankRows) * kLLRankRows;
+        return rows * ((size_t)d + V + 2) * 4 + (size_t)Qc * ((size_t)V * 4 + (size_t)kk * 8) + ll_rank_sort_bytes(mode, Qc * (int64_t)V);
+    };
+    const int64_t q_cap = mode == LL_RANK_CSORT ? std::min<int64_t>(kSortMaxBins, (int64_t)(INT32_MAX / V)) : (int64_t)INT32_MAX;
+    std::vector<int64_t> bounds{0};
+    std::vector<int64_t> chunk_of(c.vocab_size, -1);
+    std::vector<int32_t> qtok;
+    int64_t D = 0, q0 = 0, maxD = 0, maxT = 0, maxQ = 0;
+    for (int64_t q = 0; q < num_queries; ++q) {
+        qtok.assign(tokens + offsets[q], tokens + offsets[q + 1]);
+        std::sort(qtok.begin(), qtok.end());
+        qtok.erase(std::unique(qtok.begin(), qtok.end()), qtok.end());
+        const int64_t chunk = (int64_t)bounds.size() - 1;
+        int64_t fresh = 0;
+        for (int32_t w : qtok) fresh += chunk_of[w] != chunk;
+        if (q > q0 && (q - q0 >= q_cap || bytes(D + fresh, q - q0 + 1) > budget)) {
+            maxD = std::max(maxD, D); maxQ = std::max(maxQ, q - q0); maxT = std::max(maxT, offsets[q] - offsets[q0]);
+            bounds.push_back(q);
+            q0 = q; D = 0;
+            fresh = (int64_t)qtok.size();
+        }
+        const int64_t cur = (int64_t)bounds.size() - 1;
+        for (int32_t w : qtok) chunk_of[w] = cur;
+        D += fresh;
+    }
+    maxD = std::max(maxD, D); maxQ = std::max(maxQ, num_queries - q0); maxT = std::max(maxT, T - offsets[q0]);
+    bounds.push_back(num_queries);
+
+    hipStream_t s = m->stream;
+    SERT_HIP(hipStreamSynchronize(s));
+    LLRankScratch w;
+    const int64_t max_rows = (int64_t)cdiv(maxD, kLLRankRows) * kLLRankRows;
+    SERT_TRY(ll_rank_alloc(w, mode, max_rows, maxT, maxQ, V, d, kk));
+
+    std::vector<int32_t> row_of(c.vocab_size, -1);
+    std::vector<uint32_t> ids;
+    std::vector<int32_t> tok_row;
+    std::vector<int64_t> offs;
+    std::vector<float> tok_h;
+    for (size_t ci = 0; ci + 1 < bounds.size(); ++ci) {
+        const int64_t a = bounds[ci], b = bounds[ci + 1], Qc = b - a, t0 = offsets[a], Tc = offsets[b] - t0;
+        // distinct tokens of the chunk in order of first appearance
+        ids.clear(); tok_row.resize(Tc); offs.resize(Qc + 1);
+        for (int64_t t = 0; t < Tc; ++t) {
+            const int32_t tok = tokens[t0 + t];
+            if (row_of[tok] < 0) { row_of[tok] = (int32_t)ids.size(); ids.push_back((uint32_t)tok); }
+            tok_row[t] = row_of[tok];
+        }
+        for (uint32_t id : ids) row_of[id] = -1;
+        for (int64_t q = 0; q <= Qc; ++q) offs[q] = offsets[a + q] - t0;
+        const int64_t Dc = (int64_t)ids.size();
+        const int64_t rows = (int64_t)cdiv(Dc, kLLRankRows) * kLLRankRows;
+        ids.resize(rows, 0u);        // (padding rows: token 0, computed and never read)
+        SERT_HIP(hipMemcpyAsync(w.ids, ids.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipMemcpyAsync(w.tok_row, tok_row.data(), Tc * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipMemcpyAsync(w.offs, offs.data(), (Qc + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        // the predict_fn chain of sert_predict_tokens, on the distinct tokens
+        if (d % 4 == 0)
+            hipLaunchKernelGGL((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+        else
+            hipLaunchKernelGGL((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+        for (int64_t r0 = 0; r0 < rows; r0 += kLLRankRows)
+            launch_gemm<false, false, EPI_BIAS>(s, w.G + (size_t)r0 * d, m->W, w.P + (size_t)r0 * V, m->b, kLLRankRows, V, d, d, V, V);
+        hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);
+        hipLaunchKernelGGL(ll_row_entropy, dim3((unsigned)Dc), dim3(256), 0, s, w.P, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
+        SERT_TRY(ll_rank_chunk(s, w, w.P, (int)Qc, V, kk, mode));
+        SERT_TRY(ll_rank_copy_out(s, w, a, (int)Qc, kk, idx_out, score_out, joint_entropy_out, status_out));
+        tok_h.resize(Dc);
+        SERT_HIP(hipMemcpyAsync(tok_h.data(), w.tok_h, Dc * sizeof(float), hipMemcpyDeviceToHost, s));
+        SERT_HIP(hipStreamSynchronize(s));
+        for (int64_t t = 0; t < Tc; ++t) token_entropy_out[t0 + t] = tok_h[tok_row[t]];
+    }
+    return 0;
+}
+
+// Test hook: the aggregate and ranking kernels of sert_ll_rank_queries on per-token distributions the caller provides.
+int sert_debug_ll_rank_distributions(int device, const float* P, const int64_t* offsets, int64_t num_queries, int32_t V,
+                                     int32_t k, int32_t* idx_out, float* score_out, float* joint_entropy_out,
+                                     float* token_entropy_out, int32_t* status_out) {
+    if (!P || !offsets || !idx_out || !score_out || !joint_entropy_out || !token_entropy_out || !status_out || V <= 0 ||
+        k == 0 || k < -1)
+        SERT_FAIL("bad argument");
+    if (num_queries <= 0) return 0;
+    SERT_TRY(ll_rank_check_offsets(offsets, num_queries));
+    const int64_t T = offsets[num_queries];
+    const int kk = (k < 0 || k >= V) ? V : k;
+    const int mode = ll_rank_mode(V, kk);
+    if (mode == LL_RANK_CSORT && (num_queries > kSortMaxBins || num_queries * (int64_t)V > INT32_MAX))
+        SERT_FAIL("too many queries x entities for one sorted chunk");
+    SERT_HIP(hipSetDevice(device));
+    hipStream_t s;
+    SERT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    int rc = 0;
+    {
+        LLRankScratch w;
+        float* dP = nullptr;
+        auto body = [&]() -> int {
+            SERT_TRY(ll_rank_alloc(w, mode, T, T, num_queries, V, 0, kk));
+            SERT_TRY(dmalloc(&dP, (size_t)T * V));
+            std::vector<int32_t> rows(T);
+            for (int64_t t = 0; t < T; ++t) rows[t] = (int32_t)t;
+            SERT_HIP(hipMemcpyAsync(dP, P, (size_t)T * V * sizeof(float), hipMemcpyHostToDevice, s));
+            SERT_HIP(hipMemcpyAsync(w.tok_row, rows.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            SERT_HIP(hipMemcpyAsync(w.offs, offsets, (num_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(ll_row_entropy, dim3((unsigned)T), dim3(256), 0, s, dP, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
+            SERT_TRY(ll_rank_chunk(s, w, dP, (int)num_queries, V, kk, mode));
+            SERT_TRY(ll_rank_copy_out(s, w, 0, (int)num_queries, kk, idx_out, score_out, joint_entropy_out, status_out));
+            SERT_HIP(hipMemcpyAsync(token_entropy_out, w.tok_h, T * sizeof(float), hipMemcpyDeviceToHost, s));
+            SERT_HIP(hipStreamSynchronize(s));
+            return 0;
+        };
+        rc = body();
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(dP);
+    }
+    (void)hipStreamDestroy(s);
+    return rc;
+}

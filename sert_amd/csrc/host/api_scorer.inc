@@ -95,7 +95,7 @@ static int scorer_topk_materialised(sert_scorer* sc, const float* P, int64_t Q, 
 #endif
             launch_gemm<false, true, EPI_STORE>(st, P + q0 * dim, sc->E, S, nullptr, (int)qn, (int)V, dim,
                                                 dim, dim, (int)V);
-        hipLaunchKernelGGL(topk_rows, dim3((unsigned)qn), dim3(256), 0, st, S, (int)V, k, idx + q0 * k,
+        hipLaunchKernelGGL(topk_rows<false>, dim3((unsigned)qn), dim3(256), 0, st, S, (int)V, k, idx + q0 * k,
                            val + q0 * k, (float*)nullptr);
         if (sc->bf16) {   // same exact_dot scores and order as the bf16-prefiltered path reports
             int sn = 2;

@@ -72,6 +72,8 @@ constexpr int kTopKCand = 2048;   // LDS capacity for the threshold-bin candidat
 // score = (cos + 1)/2 (query.py:352-357), computed in fp32.
 // thr_out (optional): instead of the (index, score) lists, only the RAW cosine of the
 // k-th best element is written per row (the sampled threshold of the fused path).
+// RAW: emit the score itself instead of (cos + 1)/2 (the loglinear ranking, kernels_ll_rank.h).
+template <bool RAW>
 __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, int V, int k,
                                                  int32_t* __restrict__ idx_out,
                                                  float* __restrict__ val_out,
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, in
         const unsigned long long kv = keys[i];
         idx_out[(size_t)blockIdx.x * k + i] = (int32_t)(uint32_t)kv;
         const float cosv = key_to_float((uint32_t)(kv >> 32));
-        val_out[(size_t)blockIdx.x * k + i] = (cosv + 1.0f) / 2.0f;
+        val_out[(size_t)blockIdx.x * k + i] = RAW ? cosv : (cosv + 1.0f) / 2.0f;
     }
 }
 

@@ -26,6 +26,7 @@
 #include "kernels_score_bf16.h"
 #include "kernels_egrad.h"
 #include "kernels_ll.h"
+#include "kernels_ll_rank.h"
 #include "kernels_membench.h"
 #include "kernels_opt.h"
 #include "kernels_score.h"
@@ -284,6 +285,8 @@ extern "C" {
 #include "host/api_data_train.inc"
 
 #include "host/api_scorer.inc"
+
+#include "host/api_ll_rank.inc"
 
 #include "host/api_comm.inc"
 

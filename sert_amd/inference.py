@@ -14,7 +14,9 @@ vocabulary_size, result_callback)`` returns an object with
 Additive: ``create(..., batched=True)`` returns a BatchedEmbeddingMapper that
 defers all queries to ``process()`` and pushes them through predict_fn and the
 callback's ``process_batch`` in ONE device call each (the 10k x 100k scoring
-config of BASELINE.json).
+config of BASELINE.json); for loglinear (a predict_fn with ``rank_queries``) a
+BatchedWordRanker that ranks all queued queries in one ``rank_queries`` call, the
+per-token distributions staying on the device.
 """
 import logging
 
@@ -30,6 +32,8 @@ def create(predict_fn, word_representations,
     if not result_callback.should_average_input():
         ids = np.min_scalar_type(vocabulary_size - 1)          # id width of the packed batches (inference.py:10)
         logging.info('Instance elements will be stored using %s.', ids)
+        if batched and hasattr(result_callback, 'process_batch') and hasattr(predict_fn, 'rank_queries'):
+            return BatchedWordRanker(predict_fn, batch_size, window_size, ids, result_callback)
         return WordBatcher(predict_fn, batch_size, window_size, ids, result_callback)
     mapper = BatchedEmbeddingMapper if batched and hasattr(result_callback, 'process_batch') else EmbeddingMapper
     return mapper(predict_fn, word_representations, result_callback)
@@ -96,6 +100,60 @@ class WordBatcher(object):
         for (_, payload, kwargs), s0, T in zip(self._queue, starts, lengths):
             self.callback(payload, per_token[s0:s0 + T], **kwargs)
         self._queue, self._rows = [], 0
+
+
+class QueryRanking(object):
+    """What ``rank_queries`` returns for Q queries (sert_ll_rank_queries): ``idx`` / ``score`` (Q, kk) best first,
+    ``joint_entropy`` (Q,), ``token_entropy[q]`` the per-token entropies of query q, ``status`` (Q,) (``HOST``: the
+    joint's sum is 0 or not finite, the query must take the host path), ``k`` as asked.  ``distributions_of(q)``,
+    set by the front end, returns the (T, V_e) per-token distributions of query q as the unbatched path computes them."""
+
+    DEVICE, HOST = 0, 1
+
+    def __init__(self, idx, score, joint_entropy, token_entropy, status, k=None):
+        self.idx, self.score, self.joint_entropy = idx, score, joint_entropy
+        self.token_entropy, self.status, self.k = token_entropy, status, k
+        self.distributions_of = None
+
+    def __len__(self):
+        return len(self.status)
+
+
+class BatchedWordRanker(object):
+    """All loglinear queries at once (additive): ``submit`` queues, ``process`` ranks every queued query with ONE
+    ``predict_fn.rank_queries`` call and hands the ranking to ``callback.process_batch``.  A query that the device
+    cannot rank (status HOST) gets its distributions from a one-query WordBatcher of the same (batch_size, window_size)
+    shape, so that predict_fn runs at the shape the unbatched path uses and the query's output is that path's."""
+
+    def __init__(self, predict_fn, batch_size, window_size, instance_dtype, result_callback, k=None):
+        assert hasattr(result_callback, 'process_batch') and hasattr(predict_fn, 'rank_queries')
+        self.predict_fn, self.callback = predict_fn, result_callback
+        self.batch_size, self.window_size, self.instance_dtype = batch_size, window_size, instance_dtype
+        self.k = k
+        self.pending = []
+
+    def submit(self, query_tokens, **kwargs):
+        assert len(query_tokens) > 0
+        if -(-len(query_tokens) // self.window_size) > self.batch_size:
+            raise RuntimeError()        # (as WordBatcher: more tokens than one batch holds, inference.py:124-125)
+        self.pending.append((list(query_tokens), kwargs))
+
+    def _distributions(self, tokens):
+        got = []
+        batcher = WordBatcher(self.predict_fn, self.batch_size, self.window_size, self.instance_dtype,
+                              lambda payload, distribution: got.append(distribution))
+        batcher.submit(tokens)
+        batcher.process()
+        return got[0]
+
+    def process(self):
+        if not self.pending:
+            return
+        payloads = [p for p, _ in self.pending]
+        ranking = self.predict_fn.rank_queries(payloads, k=self.k)
+        ranking.distributions_of = lambda q: self._distributions(payloads[q])
+        self.callback.process_batch(payloads, ranking, [kw for _, kw in self.pending])
+        self.pending = []
 
 
 class EmbeddingMapper(object):

@@ -27,6 +27,7 @@ import scipy.sparse as sparse
 
 from sert_amd import _capi
 from sert_amd import distributed
+from sert_amd import inference
 
 
 class _EpochPass(object):
@@ -509,6 +510,20 @@ class LogLinearPredictFn(object):
             self._engine.set_tensor(_capi.T_W, self.W)
             self._engine.set_tensor(_capi.T_B, self.b)
         return self._engine
+
+    def rank_queries(self, token_lists, k=None):
+        """Additive: rank the entities for every query of ``token_lists`` (lists of word ids) in one device call
+        (sert_ll_rank_queries) -- what __call__ + scoring.LogLinearCallback.process give one query at a time, without
+        the (T, V_e) distributions leaving the device.  k None ranks every entity.  Returns an inference.QueryRanking."""
+        if self._model is not None:
+            eng = self._model._engine
+        elif self._engine is not None:
+            eng = self._engine
+        else:       # (the id width WordBatcher's batches will have: the host path reuses this engine)
+            eng = self._get_engine(np.min_scalar_type(self.R_w.shape[0] - 1).itemsize)
+        idx, score, joint_h, token_h, status, offsets = eng.ll_rank_queries(token_lists, k)
+        token_entropy = [token_h[offsets[q]:offsets[q + 1]] for q in range(len(token_lists))]
+        return inference.QueryRanking(idx.astype(np.int64), score, joint_h, token_entropy, status, k=k)
 
     def __call__(self, batch, mask=None):
         batch = _as_id_array(batch)

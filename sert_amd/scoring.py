@@ -7,6 +7,8 @@ topic_id=...)`` -- and reports a ranking through
   LogLinearCallback    result = (T, V_e) per-token entity distributions.
                        Score = product over the tokens (zeros skipped),
                        renormalised; EVERY entity is ranked (query.py:199-236).
+                       ``process_batch`` takes the ranking of all queries of a
+                       run from ONE device call (sert_ll_rank_queries).
   VectorSpaceCallback  result = (1, d_e) query projection.  Score of an entity =
                        (cosine + 1) / 2 against the L2-normalised entity table;
                        the best --top entities (or all) are ranked
@@ -82,6 +84,40 @@ class LogLinearCallback(Callback):
         # ascending argsort read backwards = best first; all V_e entities are ranked
         order = np.argsort(joint)[::-1]
         self.rank_callback(topic_id, order, joint[order])
+
+    def process_batch(self, payloads, ranking, kwargs_list):
+        """Additive: the queries of a run ranked on the device (inference.QueryRanking, from
+        LogLinearPredictFn.rank_queries).  Per query, in order: the same ``_debug`` line, the same
+        non-normalised-mass error and the same rank_callback call as ``process``.  A query whose status is
+        HOST (joint sum 0 or not finite) goes through ``process`` itself, on the distributions
+        ``ranking.distributions_of`` computes for it.
+
+        ``topic_projections`` holds, for a device-ranked query, its normalised joint in entity order when
+        ``ranking.k`` is None, else the scores of its ranked k best in rank order (``process`` stores the
+        raveled per-token distributions)."""
+        etype = type(math_utils.entropy(np.full(2, 0.5, np.float32), base=2, normalize=True))
+        for q, (payload, kw) in enumerate(zip(payloads, kwargs_list)):
+            topic_id = kw['topic_id']
+            if ranking.status[q] == inference.QueryRanking.HOST:
+                self(payload, ranking.distributions_of(q), **kw)
+                continue
+            idx, score = ranking.idx[q], ranking.score[q]
+            if ranking.k is None:
+                joint = np.empty(score.shape[0], dtype=score.dtype)
+                joint[idx] = score
+                self._remember(topic_id, joint)
+                mass = joint.sum()
+                if not np.isclose(mass, 1.0):
+                    logging.error('Encountered non-normalized distribution for topic "%s" '
+                                  '(mass=%.10f).', topic_id, mass)
+            else:
+                self._remember(topic_id, score)
+            if self.f_debug_out is not None:
+                words = [self.tokens[token] for token in payload]
+                self.f_debug_out.write('Topic {0} {1}: {2}\n'.format(
+                    topic_id, etype(ranking.joint_entropy[q]),
+                    list(zip(words, [etype(h) for h in ranking.token_entropy[q]]))))
+            self.rank_callback(topic_id, idx, score)
 
 
 class VectorSpaceCallback(Callback):
