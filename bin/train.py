@@ -19,7 +19,10 @@ args.ignore_weights but never defines it, train.py:81), --seed, --device,
 dumped with --save_optimizer_state: same results as the uninterrupted run), --gpus N
 (data parallel over N GPUs of this node, one process each, started by this script;
 --batch_size is the GLOBAL batch).  Any launcher that sets RANK / LOCAL_RANK / WORLD_SIZE
-works as well.
+works as well.  --eval_topics FILE... --eval_qrels NAME=FILE... [--eval_top K]: retrieval
+quality (NDCG, MAP, reciprocal rank, P@5) of the live model on every named qrel set, on the
+device, before epoch 1 and after every epoch; written to <model_output>_retrieval.json and
+the best epoch by the first set's NDCG logged at the end (sert_amd/evaluation.py).
 """
 import argparse
 import logging
@@ -44,6 +47,35 @@ MODELS = {
     'vectorspace_softmax': models.VectorSpaceSoftmaxLanguageModel,
 }
 
+def named_file(value):
+    """NAME=FILE -> (NAME, FILE), e.g. validation=qrel_validation."""
+    name, sep, path = value.partition('=')
+    if not sep or not name:
+        raise argparse.ArgumentTypeError('expected NAME=FILE, got %r' % value)
+    return name, au.existing_file_path(path)
+
+
+def retrieval_evaluators(args, model, words, entity_indices_inv):
+    """[(set name, RetrievalEvaluator)] of --eval_topics / --eval_qrels, in the order given."""
+    from sert_amd import evaluation
+    from sert_amd.utils import trec_utils
+    handles = [open(name, 'r') for name in args.eval_topics]
+    try:
+        topics = trec_utils.parse_topics(handles)
+    finally:
+        for handle in handles:
+            handle.close()
+    k = getattr(args, 'eval_top', None)
+    if k is None and args.type is not models.LanguageModel:
+        k = min(100, len(entity_indices_inv))       # (the product-search setting, --top 100)
+    evaluators = []
+    for name, path in args.eval_qrels:
+        with open(path, 'r') as f:
+            qrels = trec_utils.parse_qrels(f)
+        evaluators.append((name, evaluation.RetrievalEvaluator(model, topics, qrels, words, entity_indices_inv, k)))
+    return evaluators
+
+
 # (flag, keyword arguments) -- the reference's surface first (train.py:28-61)
 FLAGS = [
     ('--loglevel', dict(type=str, default='INFO')),
@@ -66,6 +98,10 @@ FLAGS = [
     ('--save_optimizer_state', dict(action='store_true', default=False)),
     ('--resume', dict(type=au.existing_file_path, default=None)),
     ('--gpus', dict(type=au.positive_int, default=1)),
+    # retrieval evaluation per epoch; absent from the namespace (which is pickled into every dump) unless given
+    ('--eval_topics', dict(type=au.existing_file_path, nargs='+', default=argparse.SUPPRESS)),
+    ('--eval_qrels', dict(type=named_file, nargs='+', default=argparse.SUPPRESS, metavar='NAME=FILE')),
+    ('--eval_top', dict(type=au.positive_int, default=argparse.SUPPRESS)),
 ]
 
 
@@ -103,7 +139,13 @@ def initial_word_representations(args, words, tokens):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    evaluate_retrieval = hasattr(args, 'eval_topics') or hasattr(args, 'eval_qrels')
+    if evaluate_retrieval and not (hasattr(args, 'eval_topics') and hasattr(args, 'eval_qrels')):
+        parser.error('--eval_topics and --eval_qrels go together')
+    if hasattr(args, 'eval_top') and not evaluate_retrieval:
+        parser.error('--eval_top needs --eval_topics and --eval_qrels')
     if args.entity_representation_size is None:
         args.entity_representation_size = args.word_representation_size
     # the model class itself travels in the dumped namespace (train.py:68)
@@ -137,6 +179,7 @@ def main(argv=None):
         # args of prepare, word -> entry(.id), id -> word; the entity maps that
         # follow in the stream are only needed at query time
         data_args, words, tokens = (pickle.load(f) for _ in range(3))
+        entity_indices_inv = pickle.load(f) if evaluate_retrieval else None
 
     options = dict(
         batch_size=args.batch_size,
@@ -146,6 +189,7 @@ def main(argv=None):
         regularization_lambda=args.regularization_lambda,
         training_set=training_set,
         validation_set=validation_set)
+    eval_words = words if evaluate_retrieval else None
     del words, tokens
 
     if args.type is models.LanguageModel:
@@ -166,11 +210,14 @@ def main(argv=None):
     if checkpoint is not None:
         training.restore(model, checkpoint)
 
+    extras = {}
+    if evaluate_retrieval:
+        extras['retrieval'] = retrieval_evaluators(args, model, eval_words, entity_indices_inv)
     train(model, args.iterations, args.model_output,
           abort_threshold=1e-5, early_stopping=False,
           additional_args=[args],
           save_optimizer_state=args.save_optimizer_state,
-          resume_from=checkpoint)
+          resume_from=checkpoint, **extras)
 
     distributed.shutdown()
 

@@ -234,6 +234,55 @@ int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* of
                          int32_t* idx_out, float* score_out, float* joint_entropy_out, float* token_entropy_out,
                          int32_t* status_out);
 
+/* ---- retrieval evaluation on the live model (product-search.sh:136-170, W3C-expert-finding.sh:108-124) ---- */
+
+typedef struct sert_reval sert_reval;
+
+/* columns of sert_reval_run's metrics_out */
+enum {
+    SERT_REVAL_NDCG = 0,        /* NDCG at the ranked depth (trec_eval ndcg_cut_K; ndcg when every entity is ranked) */
+    SERT_REVAL_MAP = 1,         /* average precision over the ranked depth */
+    SERT_REVAL_RECIP_RANK = 2,
+    SERT_REVAL_P5 = 3,
+    SERT_REVAL_NUM_REL_RET = 4, /* relevant entities among the ranked ones */
+    SERT_REVAL_NUM_METRICS = 5
+};
+
+/* Replaces, for a model that is being trained, the reference's way to one retrieval figure per epoch: dump the model, start
+ * bin/query.py on it, run trec_eval on the run file (product-search.sh:136-170).  Topics and relevance judgements are uploaded
+ * ONCE, to the model's device; the handle borrows `m`, which must outlive it.
+ *   tokens / offsets   the topics as a ragged int32 array, as for sert_ll_rank_queries: topic q owns
+ *                      tokens[offsets[q] .. offsets[q+1]) (ids < vocab_size, at least one per topic)
+ *   rel_indptr (Q+1) / rel_entities / rel_gains   the judgements as CSR per topic: entity indices < num_entities, strictly
+ *                      ascending inside a topic, gains f32; an entity counts as relevant when its gain is > 0
+ *   ideal_dcg (Q) f64  the topic's ideal DCG at the ranked depth, num_rel (Q) its number of relevant entities: computed by
+ *                      the caller in float64 over ALL judgements of the topic, those of entities the model does not know included
+ *   k                  entities ranked per topic.  loglinear: -1 = every entity (as the reference ranks), or positive.
+ *                      vectorspace kinds: 1 .. min(num_entities, 1024), the range of sert_scorer_topk; other values are refused.
+ * The ranked depth kk is num_entities for k = -1 or k >= num_entities, else k. */
+int sert_reval_create(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_topics,
+                      const int64_t* rel_indptr, const int32_t* rel_entities, const float* rel_gains,
+                      const double* ideal_dcg, const int32_t* num_rel, int32_t k, sert_reval** out);
+
+/* Rank every topic with the parameters AS THEY ARE on the device now and compute the per-topic metrics there; only the results
+ * cross to the host.  The parameters are first brought up to date as for sert_get_tensor (lazily updated word rows, deferred
+ * entity and dense updates); a batch announced with sert_hint_next_batch stays announced.  No parameter, optimiser state or
+ * sampler position changes: training continues as if the call had not happened.
+ *   vectorspace kinds: mean of the topic's word rows (fp32, token order, one division: bit for bit numpy's mean of the rows) ->
+ *     sert_predict_project's GEMM -> the kernels of sert_scorer_topk against the live entity table.  The ranking is the one
+ *     sert_get_tensor -> mean -> sert_predict_project -> sert_scorer_create -> sert_scorer_topk gives on the same parameters.
+ *   loglinear: the chunks and kernels of sert_ll_rank_queries.
+ *   metrics_out (Q, SERT_REVAL_NUM_METRICS) f64, accumulated in float64 on the device in a fixed order.  Ties in the score
+ *     are ranked by lowest entity index (trec_eval re-sorts a run file's ties by entity id descending; the ranking evaluated
+ *     here is the device's).
+ *   status_out (Q) int32: SERT_LL_STATUS_*; a loglinear topic reported SERT_LL_STATUS_HOST has no meaningful metrics or
+ *     ranking, the caller evaluates it through the per-token host path.  Always DEVICE for the vectorspace kinds.
+ *   idx_out (Q, kk) int32 / score_out (Q, kk) f32: the ranking itself, or both NULL.
+ * Like sert_ll_rank_queries, COLLECTIVE in data parallel (the word table is first all-gathered): every rank calls it, in the
+ * same order (collective; tested at world size 1 only). */
+int sert_reval_run(sert_reval* r, double* metrics_out, int32_t* status_out, int32_t* idx_out, float* score_out);
+int sert_reval_destroy(sert_reval* r);
+
 /* ---- entity scoring (bin/query.py:239-370, batched) --------------------- */
 
 typedef struct sert_scorer sert_scorer;

@@ -103,6 +103,11 @@ enum { SERT_MEMBENCH_COPY = 0, SERT_MEMBENCH_READ = 1, SERT_MEMBENCH_GATHER = 2,
 int sert_bench_memory(int device, int kind, size_t bytes, size_t table_bytes, int row_bytes,
                       int window, size_t gap_bytes, int blocks, int iters, double* avg_us);
 
+/* Test hook: the number of chunks a sert_reval handle (sert_hip.h) ranks its topics in -- 1 for the vectorspace kinds, for
+ * loglinear what SERT_LL_RANK_BUDGET gave when the handle was created; < 0 on error. */
+struct sert_reval;
+int sert_debug_reval_chunks(struct sert_reval* r);
+
 #ifdef __cplusplus
 }
 #endif

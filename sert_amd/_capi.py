@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get('SERT_LIB') or os.path.join(_HERE, 'libsert_hip.so')
 KIND_LOGLINEAR, KIND_VECTORSPACE, KIND_VECTORSPACE_SOFTMAX = 0, 1, 2
 SPLIT_TRAIN, SPLIT_VALIDATE = 0, 1
 LL_STATUS_DEVICE, LL_STATUS_HOST = 0, 1      # sert_ll_rank_queries' per-query status
+# columns of sert_reval_run's metrics
+REVAL_NDCG, REVAL_MAP, REVAL_RECIP_RANK, REVAL_P5, REVAL_NUM_REL_RET, REVAL_NUM_METRICS = 0, 1, 2, 3, 4, 5
 
 T_RW, T_RE, T_W, T_B = 0, 1, 2, 3
 T_STATE0_RW, T_STATE0_RE, T_STATE0_W, T_STATE0_B = 4, 5, 6, 7
@@ -32,12 +34,13 @@ EXPORTS = [
     'sert_upload_dataset', 'sert_train_batch', 'sert_hint_next_batch', 'sert_train_batches',
     'sert_eval_batch', 'sert_eval_batches',
     'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_score_topk',
+    'sert_reval_create', 'sert_reval_run', 'sert_reval_destroy',
     'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_scores',
     'sert_host_alloc', 'sert_host_free',
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions',
+    'sert_debug_update_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 
@@ -119,6 +122,9 @@ def load():
     lib.sert_predict_project.argtypes = [vp, fp, i64, fp]
     lib.sert_predict_tokens.argtypes = [vp, fp, i64, fp]
     lib.sert_ll_rank_queries.argtypes = [vp, fp, fp, i64, i32, fp, fp, fp, fp, fp]
+    lib.sert_reval_create.argtypes = [vp, fp, fp, i64, fp, fp, fp, fp, fp, i32, ctypes.POINTER(vp)]
+    lib.sert_reval_run.argtypes = [vp, fp, fp, fp, fp]
+    lib.sert_reval_destroy.argtypes = [vp]
     lib.sert_score_topk.argtypes = [ctypes.c_int, fp, i64, i32, fp, i64, i32, fp, fp]
     lib.sert_scorer_create.argtypes = [ctypes.c_int, fp, i64, i32, ctypes.POINTER(vp)]
     lib.sert_scorer_destroy.argtypes = [vp]
@@ -578,6 +584,66 @@ class Scorer(object):
         for b in (getattr(self, '_pin_q', None), getattr(self, '_pin_idx', None), getattr(self, '_pin_val', None)):
             if b is not None:
                 b.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RetrievalEval(object):
+    """Owner of one sert_reval handle: topics and relevance judgements resident on the engine's device, ``run()`` ranks
+    every topic with the engine's parameters as they are now and returns the per-topic metrics computed there.
+
+    token_lists: per topic its token ids (at least one); judgements: per topic (entities int, ascending; gains float);
+    ideal_dcg / num_rel: per topic, float64 / int, over ALL its judgements (sert_hip.h); k: None = every entity
+    (loglinear only).  The engine must stay alive as long as this object."""
+
+    def __init__(self, engine, token_lists, judgements, ideal_dcg, num_rel, k=None):
+        self._lib = load()
+        self._engine = engine
+        self._h = None
+        self._tokens, self._offsets = _concat_queries(token_lists)
+        q = len(token_lists)
+        assert len(judgements) == q and len(ideal_dcg) == q and len(num_rel) == q
+        indptr = np.zeros(q + 1, dtype=np.int64)
+        np.cumsum([len(e) for e, _ in judgements], out=indptr[1:])
+        ents = np.ascontiguousarray(np.concatenate([np.asarray(e, dtype=np.int64) for e, _ in judgements])
+                                    if q else np.zeros(0, np.int64), dtype=np.int32)
+        gains = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.float64) for _, g in judgements])
+                                     if q else np.zeros(0), dtype=np.float32)
+        idcg = np.ascontiguousarray(ideal_dcg, dtype=np.float64)
+        nrel = np.ascontiguousarray(num_rel, dtype=np.int32)
+        v = engine.cfg.num_entities
+        self.num_topics = q
+        self.depth = v if k is None or k >= v else int(k)
+        h = ctypes.c_void_p()
+        check(self._lib.sert_reval_create(engine._h, self._tokens.ctypes.data, self._offsets.ctypes.data, q,
+                                          indptr.ctypes.data, ents.ctypes.data, gains.ctypes.data, idcg.ctypes.data,
+                                          nrel.ctypes.data, -1 if k is None else int(k), ctypes.byref(h)))
+        self._h = h
+
+    def run(self, return_ranking=False):
+        """-> (metrics (Q, REVAL_NUM_METRICS) float64, status (Q,) int32[, idx (Q, depth) int32, score (Q, depth) f32])."""
+        metrics = np.empty((self.num_topics, REVAL_NUM_METRICS), dtype=np.float64)
+        status = np.empty(self.num_topics, dtype=np.int32)
+        idx = score = None
+        if return_ranking:
+            idx = np.empty((self.num_topics, self.depth), dtype=np.int32)
+            score = np.empty((self.num_topics, self.depth), dtype=np.float32)
+        check(self._lib.sert_reval_run(self._h, metrics.ctypes.data, status.ctypes.data, _addr(idx), _addr(score)))
+        return (metrics, status, idx, score) if return_ranking else (metrics, status)
+
+    def num_chunks(self):
+        """sert_debug_reval_chunks (test hook): chunks the topics are ranked in."""
+        self._lib.sert_debug_reval_chunks.argtypes = [ctypes.c_void_p]
+        return int(self._lib.sert_debug_reval_chunks(self._h))
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sert_reval_destroy(self._h)
+            self._h = None
 
     def __del__(self):
         try:

@@ -29,7 +29,9 @@ struct LLRankScratch {
     float *G = nullptr, *P = nullptr, *J = nullptr, *tok_h = nullptr, *joint_h = nullptr, *val = nullptr;
     int32_t *status = nullptr, *idx = nullptr;
     int32_t *ka = nullptr, *va = nullptr, *kb = nullptr, *vb = nullptr, *hist = nullptr, *bin_total = nullptr;
+    bool own_inputs = true;        // false: ids / tok_row / offs point into arrays somebody else owns (sert_reval: uploaded once)
     ~LLRankScratch() {
+        if (!own_inputs) ids = nullptr, tok_row = nullptr, offs = nullptr;
         for (void* p : {(void*)ids, (void*)tok_row, (void*)offs, (void*)G, (void*)P, (void*)J, (void*)tok_h, (void*)joint_h,
                         (void*)val, (void*)status, (void*)idx, (void*)ka, (void*)va, (void*)kb, (void*)vb, (void*)hist,
                         (void*)bin_total})
@@ -43,9 +45,11 @@ static size_t ll_rank_sort_bytes(int mode, int64_t n) {
 }
 
 static int ll_rank_alloc(LLRankScratch& w, int mode, int64_t rows, int64_t T, int64_t Qc, int V, int d, int kk) {
-    SERT_TRY(dmalloc(&w.ids, (size_t)rows));
-    SERT_TRY(dmalloc(&w.tok_row, (size_t)T));
-    SERT_TRY(dmalloc(&w.offs, (size_t)Qc + 1));
+    if (w.own_inputs) {
+        SERT_TRY(dmalloc(&w.ids, (size_t)rows));
+        SERT_TRY(dmalloc(&w.tok_row, (size_t)T));
+        SERT_TRY(dmalloc(&w.offs, (size_t)Qc + 1));
+    }
     if (d > 0) SERT_TRY(dmalloc(&w.G, (size_t)rows * d));
     if (d > 0) SERT_TRY(dmalloc(&w.P, (size_t)rows * V));
     SERT_TRY(dmalloc(&w.J, (size_t)Qc * V));
@@ -125,35 +129,36 @@ static int ll_rank_check_offsets(const int64_t* offsets, int64_t Q) {
     return 0;
 }
 
-int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
-                         int32_t* idx_out, float* score_out, float* joint_entropy_out, float* token_entropy_out,
-                         int32_t* status_out) {
-    refresh_gemm_choice();
-    if (!m || !tokens || !offsets || !idx_out || !score_out || !joint_entropy_out || !token_entropy_out || !status_out)
-        SERT_FAIL("null argument");
-    if (is_vs(m)) SERT_FAIL("sert_ll_rank_queries ranks with the loglinear model");
-    if (k == 0 || k < -1) SERT_FAIL("k must be -1 (all entities) or positive");
-    if (num_queries <= 0) return 0;
-    SERT_TRY(ll_rank_check_offsets(offsets, num_queries));
+// How a call's queries are cut into chunks: consecutive queries while distinct rows x V_e + joint rows + sort scratch fit
+// the budget.  bounds[c] .. bounds[c + 1] are the queries of chunk c; max_* size the scratch for the largest chunk.
+struct LLRankPlan {
+    std::vector<int64_t> bounds;
+    int64_t max_rows = 0, max_tokens = 0, max_queries = 0;
+    int kk = 0, mode = 0;
+};
+
+static int ll_rank_check_tokens(const sert_model* m, const int32_t* tokens, int64_t T) {
+    for (int64_t t = 0; t < T; ++t)
+        if (tokens[t] < 0 || tokens[t] >= m->cfg.vocab_size) SERT_FAIL("token id out of range [0, vocab_size)");
+    return 0;
+}
+
+static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
+                         LLRankPlan& plan) {
     const auto& c = m->cfg;
     const int V = c.num_entities, d = c.word_dim;
     const int64_t T = offsets[num_queries];
-    for (int64_t t = 0; t < T; ++t)
-        if (tokens[t] < 0 || tokens[t] >= c.vocab_size) SERT_FAIL("token id out of range [0, vocab_size)");
-    SERT_HIP(hipSetDevice(c.device));
-    SERT_TRY(ensure_full_rw(m));
-    SERT_TRY(ensure_rw_current(m, -1));
     const int kk = (k < 0 || k >= V) ? V : k;
     const int mode = ll_rank_mode(V, kk);
-
-    // ---- chunks: consecutive queries while distinct rows x V_e + joint rows + sort scratch fit the budget ----
+    plan.kk = kk; plan.mode = mode;
     const size_t budget = ll_rank_budget();
     auto bytes = [&](int64_t D, int64_t Qc) -> size_t {
         const size_t rows = (size_t)cdiv(D, kLLRankRows) * kLLRankRows;
         return rows * ((size_t)d + V + 2) * 4 + (size_t)Qc * ((size_t)V * 4 + (size_t)kk * 8) + ll_rank_sort_bytes(mode, Qc * (int64_t)V);
     };
     const int64_t q_cap = mode == LL_RANK_CSORT ? std::min<int64_t>(kSortMaxBins, (int64_t)(INT32_MAX / V)) : (int64_t)INT32_MAX;
-    std::vector<int64_t> bounds{0};
+    std::vector<int64_t>& bounds = plan.bounds;
+    bounds.assign(1, 0);
     std::vector<int64_t> chunk_of(c.vocab_size, -1);
     std::vector<int32_t> qtok;
     int64_t D = 0, q0 = 0, maxD = 0, maxT = 0, maxQ = 0;
@@ -176,45 +181,84 @@ int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* of
     }
     maxD = std::max(maxD, D); maxQ = std::max(maxQ, num_queries - q0); maxT = std::max(maxT, T - offsets[q0]);
     bounds.push_back(num_queries);
+    plan.max_rows = (int64_t)cdiv(maxD, kLLRankRows) * kLLRankRows;
+    plan.max_tokens = maxT;
+    plan.max_queries = maxQ;
+}
+
+// the device inputs of one chunk (queries a .. b): its distinct token ids in order of first appearance, padded to whole
+// slabs with id 0 (computed and never read); the row of every token; chunk-relative query offsets.  Returns the number of
+// distinct tokens.  row_of: vocab_size entries, all -1 on entry and on return.
+static int64_t ll_rank_chunk_inputs(const int32_t* tokens, const int64_t* offsets, int64_t a, int64_t b, std::vector<int32_t>& row_of,
+                                    std::vector<uint32_t>& ids, std::vector<int32_t>& tok_row, std::vector<int64_t>& offs) {
+    const int64_t Qc = b - a, t0 = offsets[a], Tc = offsets[b] - t0;
+    ids.clear(); tok_row.resize(Tc); offs.resize(Qc + 1);
+    for (int64_t t = 0; t < Tc; ++t) {
+        const int32_t tok = tokens[t0 + t];
+        if (row_of[tok] < 0) { row_of[tok] = (int32_t)ids.size(); ids.push_back((uint32_t)tok); }
+        tok_row[t] = row_of[tok];
+    }
+    for (uint32_t id : ids) row_of[id] = -1;
+    for (int64_t q = 0; q <= Qc; ++q) offs[q] = offsets[a + q] - t0;
+    const int64_t Dc = (int64_t)ids.size();
+    ids.resize((size_t)cdiv(Dc, kLLRankRows) * kLLRankRows, 0u);
+    return Dc;
+}
+
+// One chunk on the device, inputs in w.ids / w.tok_row / w.offs: the predict_fn chain of sert_predict_tokens on the Dc
+// distinct tokens (`rows` with the padding), their entropies, then ll_rank_chunk.  Both sert_ll_rank_queries and
+// sert_reval_run rank through here, so a query's ranking does not depend on the caller.
+static int ll_rank_chunk_device(sert_model* m, hipStream_t s, LLRankScratch& w, int64_t Dc, int64_t rows, int Qc, int kk, int mode) {
+    const int V = m->cfg.num_entities, d = m->cfg.word_dim;
+    if (d % 4 == 0)
+        hipLaunchKernelGGL((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+    else
+        hipLaunchKernelGGL((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+    for (int64_t r0 = 0; r0 < rows; r0 += kLLRankRows)
+        launch_gemm<false, false, EPI_BIAS>(s, w.G + (size_t)r0 * d, m->W, w.P + (size_t)r0 * V, m->b, kLLRankRows, V, d, d, V, V);
+    hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);
+    hipLaunchKernelGGL(ll_row_entropy, dim3((unsigned)Dc), dim3(256), 0, s, w.P, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
+    return ll_rank_chunk(s, w, w.P, Qc, V, kk, mode);
+}
+
+int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
+                         int32_t* idx_out, float* score_out, float* joint_entropy_out, float* token_entropy_out,
+                         int32_t* status_out) {
+    refresh_gemm_choice();
+    if (!m || !tokens || !offsets || !idx_out || !score_out || !joint_entropy_out || !token_entropy_out || !status_out)
+        SERT_FAIL("null argument");
+    if (is_vs(m)) SERT_FAIL("sert_ll_rank_queries ranks with the loglinear model");
+    if (k == 0 || k < -1) SERT_FAIL("k must be -1 (all entities) or positive");
+    if (num_queries <= 0) return 0;
+    SERT_TRY(ll_rank_check_offsets(offsets, num_queries));
+    const auto& c = m->cfg;
+    const int V = c.num_entities, d = c.word_dim;
+    SERT_TRY(ll_rank_check_tokens(m, tokens, offsets[num_queries]));
+    SERT_HIP(hipSetDevice(c.device));
+    SERT_TRY(ensure_full_rw(m));
+    SERT_TRY(ensure_rw_current(m, -1));
+    LLRankPlan plan;
+    ll_rank_plan(m, tokens, offsets, num_queries, k, plan);
+    const int kk = plan.kk, mode = plan.mode;
 
     hipStream_t s = m->stream;
     SERT_HIP(hipStreamSynchronize(s));
     LLRankScratch w;
-    const int64_t max_rows = (int64_t)cdiv(maxD, kLLRankRows) * kLLRankRows;
-    SERT_TRY(ll_rank_alloc(w, mode, max_rows, maxT, maxQ, V, d, kk));
+    SERT_TRY(ll_rank_alloc(w, mode, plan.max_rows, plan.max_tokens, plan.max_queries, V, d, kk));
 
     std::vector<int32_t> row_of(c.vocab_size, -1);
     std::vector<uint32_t> ids;
     std::vector<int32_t> tok_row;
     std::vector<int64_t> offs;
     std::vector<float> tok_h;
-    for (size_t ci = 0; ci + 1 < bounds.size(); ++ci) {
-        const int64_t a = bounds[ci], b = bounds[ci + 1], Qc = b - a, t0 = offsets[a], Tc = offsets[b] - t0;
-        // distinct tokens of the chunk in order of first appearance
-        ids.clear(); tok_row.resize(Tc); offs.resize(Qc + 1);
-        for (int64_t t = 0; t < Tc; ++t) {
-            const int32_t tok = tokens[t0 + t];
-            if (row_of[tok] < 0) { row_of[tok] = (int32_t)ids.size(); ids.push_back((uint32_t)tok); }
-            tok_row[t] = row_of[tok];
-        }
-        for (uint32_t id : ids) row_of[id] = -1;
-        for (int64_t q = 0; q <= Qc; ++q) offs[q] = offsets[a + q] - t0;
-        const int64_t Dc = (int64_t)ids.size();
-        const int64_t rows = (int64_t)cdiv(Dc, kLLRankRows) * kLLRankRows;
-        ids.resize(rows, 0u);        // (padding rows: token 0, computed and never read)
+    for (size_t ci = 0; ci + 1 < plan.bounds.size(); ++ci) {
+        const int64_t a = plan.bounds[ci], b = plan.bounds[ci + 1], Qc = b - a, t0 = offsets[a], Tc = offsets[b] - t0;
+        const int64_t Dc = ll_rank_chunk_inputs(tokens, offsets, a, b, row_of, ids, tok_row, offs);
+        const int64_t rows = (int64_t)ids.size();
         SERT_HIP(hipMemcpyAsync(w.ids, ids.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         SERT_HIP(hipMemcpyAsync(w.tok_row, tok_row.data(), Tc * sizeof(int32_t), hipMemcpyHostToDevice, s));
         SERT_HIP(hipMemcpyAsync(w.offs, offs.data(), (Qc + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        // the predict_fn chain of sert_predict_tokens, on the distinct tokens
-        if (d % 4 == 0)
-            hipLaunchKernelGGL((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
-        else
-            hipLaunchKernelGGL((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
-        for (int64_t r0 = 0; r0 < rows; r0 += kLLRankRows)
-            launch_gemm<false, false, EPI_BIAS>(s, w.G + (size_t)r0 * d, m->W, w.P + (size_t)r0 * V, m->b, kLLRankRows, V, d, d, V, V);
-        hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);
-        hipLaunchKernelGGL(ll_row_entropy, dim3((unsigned)Dc), dim3(256), 0, s, w.P, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
-        SERT_TRY(ll_rank_chunk(s, w, w.P, (int)Qc, V, kk, mode));
+        SERT_TRY(ll_rank_chunk_device(m, s, w, Dc, rows, (int)Qc, kk, mode));
         SERT_TRY(ll_rank_copy_out(s, w, a, (int)Qc, kk, idx_out, score_out, joint_entropy_out, status_out));
         tok_h.resize(Dc);
         SERT_HIP(hipMemcpyAsync(tok_h.data(), w.tok_h, Dc * sizeof(float), hipMemcpyDeviceToHost, s));

@@ -1,10 +1,10 @@
 // Part of sert_hip.hip (one translation unit; included there, inside its namespace / extern "C" block): C ABI: the query-time scorer (normalise, bf16 prefilter, exact re-scoring, top-k), pinned host memory.
 
-int sert_scorer_create(int device, const float* entities, int64_t V, int32_t dim, sert_scorer** out) {
-    if (!entities || !out) SERT_FAIL("null argument");
-    if (V <= 0 || dim <= 0) SERT_FAIL("bad sizes");
+// streams, events and the table buffers of a scorer for a (V, dim) entity table; the table itself comes from scorer_load_table
+static int scorer_alloc(int device, int64_t V, int32_t dim, sert_scorer** out) {
     SERT_HIP(hipSetDevice(device));
     sert_scorer* sc = new sert_scorer();
+    *out = sc;                    // (set first: a caller that fails below destroys what was made so far)
     sc->device = device;
     sc->V = V;
     sc->dim = dim;
@@ -13,18 +13,47 @@ int sert_scorer_create(int device, const float* entities, int64_t V, int32_t dim
     SERT_HIP(hipEventCreateWithFlags(&sc->ev_ready, hipEventDisableTiming));
     SERT_HIP(hipEventCreateWithFlags(&sc->ev_done, hipEventDisableTiming));
     SERT_TRY(dmalloc(&sc->E, (size_t)V * dim));
-    SERT_HIP(hipMemcpyAsync(sc->E, entities, (size_t)V * dim * sizeof(float), hipMemcpyHostToDevice, sc->stream));
-    hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(V, 4)), dim3(256), 0, sc->stream, sc->E, V, dim);
     // large tables: bf16 copy for the prefilter GEMM (SERT_SCORE_FP32=1 keeps the fp32 filter)
     static const bool fp32_only = knob("SERT_SCORE_FP32") != nullptr;
     sc->bf16 = !fp32_only && V >= 32768 && dim % 4 == 0;
     if (sc->bf16) {
         sc->kp = (int)round_up(dim, 32);
         SERT_TRY(dmalloc(&sc->E16, (size_t)V * sc->kp));
-        hipLaunchKernelGGL(to_bf16_rows, dim3(grid_for(V * sc->kp)), dim3(256), 0, sc->stream, sc->E, V, dim,
-                           sc->kp, sc->E16);
     }
-    SERT_HIP(hipStreamSynchronize(sc->stream));
+    return 0;
+}
+
+// (Re)load the entity table from `entities` (host or device, un-normalised, not modified): copy, L2-normalise, bf16 copy --
+// enqueued on stream s, which the caller synchronises before the scorer's own streams use the table.
+static int scorer_load_table(sert_scorer* sc, const float* entities, hipMemcpyKind kind, hipStream_t s) {
+    const int64_t V = sc->V;
+    const int dim = sc->dim;
+    SERT_HIP(hipMemcpyAsync(sc->E, entities, (size_t)V * dim * sizeof(float), kind, s));
+    hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(V, 4)), dim3(256), 0, s, sc->E, V, dim);
+    if (sc->bf16)
+        hipLaunchKernelGGL(to_bf16_rows, dim3(grid_for(V * sc->kp)), dim3(256), 0, s, sc->E, V, dim,
+                           sc->kp, sc->E16);
+    sc->bf16_demoted = false;     // (a verdict on the previous table's rows)
+    return 0;
+}
+
+int sert_scorer_create(int device, const float* entities, int64_t V, int32_t dim, sert_scorer** out) {
+    if (!entities || !out) SERT_FAIL("null argument");
+    if (V <= 0 || dim <= 0) SERT_FAIL("bad sizes");
+    sert_scorer* sc = nullptr;
+    auto body = [&]() -> int {
+        SERT_TRY(scorer_alloc(device, V, dim, &sc));
+        SERT_TRY(scorer_load_table(sc, entities, hipMemcpyHostToDevice, sc->stream));
+        SERT_HIP(hipStreamSynchronize(sc->stream));
+        return 0;
+    };
+    const int rc = body();
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        sert_scorer_destroy(sc);
+        g_last_error = keep;
+        return rc;
+    }
     *out = sc;
     return 0;
 }
@@ -111,12 +140,15 @@ static int scorer_topk_materialised(sert_scorer* sc, const float* P, int64_t Q, 
 
 // Fused path (kernels_score.h): sampled thresholds, GEMM with a filtering epilogue,
 // selection from the candidate lists; flagged rows are redone by the materialising path.
-// proj / idx_out / score_out: the caller's host arrays.  The projections are uploaded chunk
-// by chunk and each chunk's results are copied out while later chunks compute; *copied_out
-// tells the caller that the host arrays are complete (no row needed the exact fallback).
+// proj / idx_out / score_out: the caller's arrays, all three on the host or (dev) all three on the
+// scorer's device.  The projections are brought in chunk by chunk and each chunk's results are
+// copied out while later chunks compute; *copied_out tells the caller that the output arrays are
+// complete (no row needed the exact fallback).  The kernels do not depend on where the arrays live.
 static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int k, int rs, int32_t* idx_out,
-                             float* score_out, bool* copied_out) {
+                             float* score_out, bool* copied_out, bool dev) {
     *copied_out = false;
+    const hipMemcpyKind kind_in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind kind_out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     hipStream_t s = sc->stream;
     const int64_t V = sc->V;
     const int dim = sc->dim;
@@ -167,10 +199,10 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
     SERT_HIP(hipMemsetAsync(sc->nflag, 0, sizeof(int), s));
     SERT_HIP(hipEventRecord(sc->ev_ready, s));           // nflag zeroed, earlier work on s done
     SERT_HIP(hipStreamWaitEvent(sc->stream2, sc->ev_ready, 0));
-    auto copy_out = [&](int64_t q0, int64_t qn, hipStream_t st) {   // (pageable destination: returns when done)
-        hipError_t e = hipMemcpyAsync(idx_out + q0 * k, sc->idx + q0 * k, (size_t)qn * k * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    auto copy_out = [&](int64_t q0, int64_t qn, hipStream_t st) {   // (host, pageable: returns when done; device: asynchronous on st -- ev_done and the synchronisation of s below join both streams before this function returns)
+        hipError_t e = hipMemcpyAsync(idx_out + q0 * k, sc->idx + q0 * k, (size_t)qn * k * sizeof(int32_t), kind_out, st);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(score_out + q0 * k, sc->val + q0 * k, (size_t)qn * k * sizeof(float), hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(score_out + q0 * k, sc->val + q0 * k, (size_t)qn * k * sizeof(float), kind_out, st);
         return e;
     };
     int64_t t = 0;
@@ -179,7 +211,7 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         const int set = (int)(t & 1);
         hipStream_t st = set ? sc->stream2 : s;
         float* Pw = sc->P + q0 * dim;
-        SERT_HIP(hipMemcpyAsync(Pw, proj + q0 * dim, (size_t)qn * dim * sizeof(float), hipMemcpyHostToDevice, st));
+        SERT_HIP(hipMemcpyAsync(Pw, proj + q0 * dim, (size_t)qn * dim * sizeof(float), kind_in, st));
         hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(qn, 4)), dim3(256), 0, st, Pw, qn, dim);
         const float* P = Pw;
         float* Ss = sc->Ss + (size_t)set * QT * Vs;
@@ -263,7 +295,9 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
     return 0;
 }
 
-int sert_scorer_topk(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, int32_t* idx_out, float* score_out) {
+// sert_scorer_topk on the caller's host arrays, or (dev) on arrays of the scorer's device (sert_reval_run: the projections
+// never leave it).  Same path choice and kernels either way.
+static int scorer_topk_io(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, int32_t* idx_out, float* score_out, bool dev) {
     if (!sc || !proj || !idx_out || !score_out) SERT_FAIL("null argument");
     if (Q < 0 || k <= 0) SERT_FAIL("bad sizes");
     if (k > sc->V) SERT_FAIL("k exceeds the number of entities");
@@ -295,18 +329,23 @@ int sert_scorer_topk(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
     const bool fused = !never_fuse && V >= 32768 && dim % 4 == 0 && rs <= kTopKMax &&
                        cdiv(V, kScoreStride) >= 8 * (int64_t)rs;
     bool copied = false;
-    if (fused) SERT_TRY(scorer_topk_fused(sc, proj, Q, k, rs, idx_out, score_out, &copied));
+    if (fused) SERT_TRY(scorer_topk_fused(sc, proj, Q, k, rs, idx_out, score_out, &copied, dev));
     else {
-        SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
         SERT_TRY(scorer_topk_materialised(sc, sc->P, Q, k, sc->idx, sc->val));
     }
     SERT_HIP(hipGetLastError());
     if (copied) return 0;
-    SERT_HIP(hipMemcpyAsync(idx_out, sc->idx, (size_t)Q * k * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SERT_HIP(hipMemcpyAsync(score_out, sc->val, (size_t)Q * k * sizeof(float), hipMemcpyDeviceToHost, s));
+    const hipMemcpyKind kind_out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    SERT_HIP(hipMemcpyAsync(idx_out, sc->idx, (size_t)Q * k * sizeof(int32_t), kind_out, s));
+    SERT_HIP(hipMemcpyAsync(score_out, sc->val, (size_t)Q * k * sizeof(float), kind_out, s));
     SERT_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+int sert_scorer_topk(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, int32_t* idx_out, float* score_out) {
+    return scorer_topk_io(sc, proj, Q, k, idx_out, score_out, false);
 }
 
 int sert_scorer_scores(sert_scorer* sc, const float* proj, int64_t Q, float* score_out) {

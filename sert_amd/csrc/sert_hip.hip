@@ -29,6 +29,7 @@
 #include "kernels_ll_rank.h"
 #include "kernels_membench.h"
 #include "kernels_opt.h"
+#include "kernels_reval.h"
 #include "kernels_score.h"
 #include "kernels_seg.h"
 #include "kernels_sort.h"
@@ -287,6 +288,8 @@ extern "C" {
 #include "host/api_scorer.inc"
 
 #include "host/api_ll_rank.inc"
+
+#include "host/api_reval.inc"
 
 #include "host/api_comm.inc"
 

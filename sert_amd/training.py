@@ -14,6 +14,7 @@ code here is organised differently):
   * a dump is a stream of pickles: the extra objects (the CLI namespace) followed
     by ``model.get_state()`` (train.py:289-300).
 """
+import json
 import logging
 import os
 import pickle
@@ -101,7 +102,7 @@ class EpochDriver(object):
     """State of one training run: error histories and the dump routine."""
 
     def __init__(self, model, output_path, extra_objects=(),
-                 save_optimizer_state=False):
+                 save_optimizer_state=False, retrieval=None):
         assert isinstance(model, models.ModelInterface)
         self.model = model
         self.output_path = output_path
@@ -110,6 +111,46 @@ class EpochDriver(object):
         self.means = {'training': [], 'validation': []}
         self.stddevs = {'training': [], 'validation': []}
         self.writes_files = distributed.get_context().rank == 0
+        # additive: [(set name, evaluation.RetrievalEvaluator)] and what they reported, epoch -> set -> means
+        self.retrieval = list(retrieval or [])
+        self.retrieval_history = {}
+
+    def measure_retrieval(self, epoch):
+        """Retrieval quality of the live model on every named qrel set (collective in data parallel);
+        one log line per set, the history rewritten to <output>_retrieval.json by rank 0."""
+        if not self.retrieval:
+            return
+        entry = {}
+        for name, evaluator in self.retrieval:
+            entry[name] = evaluator.evaluate(per_topic=False)
+            logging.info('Epoch %d: retrieval on %s: %s', epoch, name,
+                         ' '.join('%s=%.6f' % (k, v) if k != 'num_q' else 'num_q=%d' % v
+                                  for k, v in entry[name].items()))
+        self.retrieval_history[str(epoch)] = entry
+        if self.writes_files:
+            with open(self.output_path + '_retrieval.json', 'w') as f:
+                json.dump(self.retrieval_history, f, indent=1, sort_keys=True)
+
+    def best_retrieval_epoch(self):
+        """(epoch, NDCG) with the highest NDCG on the FIRST named set; the earliest epoch on a tie
+        (product-search.sh:158-162 leaves ties to sort)."""
+        if not self.retrieval or not self.retrieval_history:
+            return None
+        first = self.retrieval[0][0]
+        best = None
+        for epoch in sorted(int(e) for e in self.retrieval_history):
+            entry = self.retrieval_history[str(epoch)].get(first)
+            if entry is None:
+                continue
+            value = next(v for k, v in entry.items() if k.startswith('ndcg'))
+            if best is None or value > best[1]:
+                best = (epoch, value)
+        return best
+
+    def report_best(self):
+        best = self.best_retrieval_epoch()
+        if best is not None:
+            logging.info('Best epoch by %s NDCG: %d (%.6f).', self.retrieval[0][0], best[0], best[1])
 
     def measure(self):
         for split, fn in (('training', self.model.train_error),
@@ -129,6 +170,8 @@ class EpochDriver(object):
                        'numpy_random_state': np.random.get_state(),
                        'epoch': epoch,
                        'errors': {'means': self.means, 'stddevs': self.stddevs}}
+            if self.retrieval:
+                trailer['retrieval'] = self.retrieval_history
         if not self.writes_files:
             return
         filename = '{0}_{1}.bin'.format(self.output_path, epoch)
@@ -199,12 +242,15 @@ def restore(model, checkpoint):
 
 def train(model, num_epochs, output_path,
           abort_threshold=1e-5, early_stopping=False,
-          additional_args=[], save_optimizer_state=False, resume_from=None):
+          additional_args=[], save_optimizer_state=False, resume_from=None, retrieval=None):
     """The reference's epoch driver (train.py:262-348).  ``resume_from`` (additive): a
     checkpoint from read_checkpoint already applied with restore(); the driver then continues
-    behind the epoch it was written at instead of starting with measure + dump 0."""
+    behind the epoch it was written at instead of starting with measure + dump 0.
+    ``retrieval`` (additive): [(set name, evaluation.RetrievalEvaluator)] -- evaluated wherever the
+    errors are measured, written to <output_path>_retrieval.json; the best epoch by the first
+    set's NDCG is logged at the end."""
     assert isinstance(abort_threshold, float)
-    run = EpochDriver(model, output_path, additional_args, save_optimizer_state)
+    run = EpochDriver(model, output_path, additional_args, save_optimizer_state, retrieval)
 
     first_epoch = 1
     if resume_from is not None and resume_from.get('trailer') is not None:
@@ -212,9 +258,11 @@ def train(model, num_epochs, output_path,
         run.means = {k: list(v) for k, v in trailer['errors']['means'].items()}
         run.stddevs = {k: list(v) for k, v in trailer['errors']['stddevs'].items()}
         first_epoch = int(trailer['epoch']) + 1
+        run.retrieval_history = dict(trailer.get('retrieval', {}))
         logging.info('Resuming behind epoch %d.', first_epoch - 1)
     else:
         run.measure()
+        run.measure_retrieval(0)
         run.dump(0)
 
     for epoch in range(first_epoch, num_epochs + 1):
@@ -226,6 +274,7 @@ def train(model, num_epochs, output_path,
         logging.info('Epoch %d: measuring training/validation error.', epoch)
         run.measure()
         run.report()
+        run.measure_retrieval(epoch)
         run.dump(epoch)
 
         assert np.all(np.isfinite(run.means['training'][-1]))
@@ -234,9 +283,12 @@ def train(model, num_epochs, output_path,
             assert np.all(np.isfinite(run.means['validation'][-1]))
             if run.validation_got_worse():
                 logging.info('Validation error stopped decreasing; aborting.')
+                run.report_best()
                 return
 
         if run.stalled(abort_threshold):
             logging.error('No learning was performed during '
                           'the last iteration; aborting.')
+            run.report_best()
             return
+    run.report_best()

@@ -98,6 +98,20 @@ def average_precision(ranked_entities, relevance):
     return total / num_rel
 
 
+def reciprocal_rank(ranked_entities, relevance):
+    """trec_eval's recip_rank: 1 / rank of the first relevant entity, 0 when none was retrieved."""
+    for i, e in enumerate(ranked_entities, 1):
+        if relevance.get(e, 0.0) > 0:
+            return 1.0 / i
+    return 0.0
+
+
+def precision_at(ranked_entities, relevance, k=5):
+    """trec_eval's P_k: relevant entities among the first k ranks over k -- over k, not over the
+    number retrieved: a shorter ranking is not rewarded."""
+    return sum(1 for e in ranked_entities[:k] if relevance.get(e, 0.0) > 0) / float(k)
+
+
 def evaluate_run(run, qrels, k=100):
     """Mean NDCG@k and MAP over the topics that have relevance judgements."""
     ndcgs, aps = [], []
