@@ -272,7 +272,7 @@ int sert_train_batch(sert_model* m, int64_t batch_index, const int64_t* negative
             const double waited_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_spin0).count();
             if (waited_ms < next_query_ms) continue;
             next_query_ms = waited_ms + 50.0;
-            const hipError_t q = hipStreamQuery(m->tail_pending ? m->tail_stream : m->stream);   // (the stream the publishing kernel is on)
+            const hipError_t q = hipStreamQuery(m->stream);   // (the stream the publishing kernel is on)
             if (q == hipSuccess) {
                 if (*flag == want) break;
                 SERT_FAIL("training step completed without publishing its loss");

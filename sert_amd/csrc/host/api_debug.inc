@@ -136,8 +136,6 @@ int sert_synchronize(sert_model* m) {
     SERT_HIP(hipStreamSynchronize(m->stream));
     SERT_HIP(hipStreamSynchronize(m->stream2));
     if (m->stream3) SERT_HIP(hipStreamSynchronize(m->stream3));
-    if (m->stream4) SERT_HIP(hipStreamSynchronize(m->stream4));
-    if (m->tail_stream) SERT_HIP(hipStreamSynchronize(m->tail_stream));
     if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
     return 0;
 }

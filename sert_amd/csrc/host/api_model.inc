@@ -115,7 +115,7 @@ static int sharded_state_io(sert_model* m, int i, int k, float* host_out, const 
 // stand in front of a D2H copy (host transport) or a collective whose readers are peers, and an agent-scope release does
 // not make the gradients visible to those (advisor, round 5).
 static int create_intra_events(sert_model* m, bool device_scope) {
-    hipEvent_t* evs[] = {&m->ev_word_opt, &m->ev_early, &m->ev_join3, &m->ev_step_done, &m->ev_neg, &m->ev_opt_fork,
+    hipEvent_t* evs[] = {&m->ev_join3, &m->ev_step_done, &m->ev_neg, &m->ev_opt_fork,
                          &m->ev_dense, &m->ev_small, &m->ev_re, &m->ev_fork, &m->ev_join};
     const unsigned flags = hipEventDisableTiming | (device_scope ? (unsigned)hipEventDisableSystemFence : 0u);
     for (hipEvent_t* e : evs) {
@@ -198,22 +198,13 @@ static int create_resources(sert_model* m) {
     const auto& c = m->cfg;
     SERT_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     SERT_HIP(hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
-    // The opt-in schedules that need a third / fourth queue create them; by default they do not exist:
+    // The opt-in schedule that needs a third queue (SERT_STREAMS=3) creates it; by default it does not exist:
     // HIP maps streams onto FOUR hardware queues, and a fifth stream -- the communication stream of a
     // data-parallel model -- would share one with the main stream (its kernels then queue behind the
     // main stream's, and every cross-stream event costs 10-30 us instead of ~6)
     {
         const char* e3 = knob("SERT_STREAMS");
-        const bool want3 = (e3 && atoi(e3) >= 3) || (variant_knob("SERT_DW_THIRD") && atoi(variant_knob("SERT_DW_THIRD")) != 0);
-        const bool want4 = variant_knob("SERT_ADAM_SPLIT") && atoi(variant_knob("SERT_ADAM_SPLIT")) != 0;
-        if (want3) SERT_HIP(hipStreamCreateWithFlags(&m->stream3, hipStreamNonBlocking));
-        if (want4) SERT_HIP(hipStreamCreateWithFlags(&m->stream4, hipStreamNonBlocking));
-        // (experiment, round 6 item 17 -- measured slower: a variants build with SERT_TAIL_QUEUE=1 only)
-        if (m->cfg.kind == SERT_KIND_VECTORSPACE && !m->cfg.inference_only && variant_knob("SERT_TAIL_QUEUE") && atoi(variant_knob("SERT_TAIL_QUEUE")) == 1) {
-            SERT_HIP(hipStreamCreateWithFlags(&m->tail_stream, hipStreamNonBlocking));
-            SERT_HIP(hipEventCreateWithFlags(&m->ev_tail_go, hipEventDisableTiming | hipEventDisableSystemFence));
-            SERT_HIP(hipEventCreateWithFlags(&m->ev_tail_done, hipEventDisableTiming | hipEventDisableSystemFence));
-        }
+        if (e3 && atoi(e3) >= 3) SERT_HIP(hipStreamCreateWithFlags(&m->stream3, hipStreamNonBlocking));
     }
     // Events that only order this device's own streams against each other need no SYSTEM-scope release (the cache
     // write-back + invalidate that makes device memory visible to the host and to other devices): every kernel ends with
@@ -404,8 +395,6 @@ int sert_destroy(sert_model* m) {
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     if (m->stream2) (void)hipStreamSynchronize(m->stream2);   // (work that ran ahead of the host)
     if (m->stream3) (void)hipStreamSynchronize(m->stream3);
-    if (m->stream4) (void)hipStreamSynchronize(m->stream4);
-    if (m->tail_stream) (void)hipStreamSynchronize(m->tail_stream);
     if (m->comm_stream) (void)hipStreamSynchronize(m->comm_stream);
     if (m->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(m->comm);
     if (m->ev_rest_ready) (void)hipEventDestroy(m->ev_rest_ready);
@@ -456,12 +445,6 @@ int sert_destroy(sert_model* m) {
     for (hipEvent_t e : {m->ev_step_done, m->ev_neg, m->ev_opt_fork, m->ev_small, m->ev_re, m->ev_dense, m->ev_loss})
         if (e) (void)hipEventDestroy(e);
     if (m->stream3) (void)hipStreamDestroy(m->stream3);
-    if (m->stream4) (void)hipStreamDestroy(m->stream4);
-    if (m->ev_tail_go) (void)hipEventDestroy(m->ev_tail_go);
-    if (m->ev_tail_done) (void)hipEventDestroy(m->ev_tail_done);
-    if (m->tail_stream) (void)hipStreamDestroy(m->tail_stream);
-    for (hipEvent_t e : {m->ev_word_opt, m->ev_early})
-        if (e) (void)hipEventDestroy(e);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
     return 0;
@@ -507,7 +490,6 @@ int sert_get_tensor(sert_model* m, int which, float* host, size_t count) {
     SERT_TRY(ensure_rw_current(m, -1));                     // (lazy word-table update: flush before anyone looks)
     if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
     if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
-    SERT_TRY(settle_tail(m));                               // (a tail on its own queue writes W, b and their moments)
     SERT_HIP(hipMemcpyAsync(host, t.ptr, count * sizeof(float), hipMemcpyDeviceToHost, m->stream));
     SERT_HIP(hipStreamSynchronize(m->stream));
     return 0;

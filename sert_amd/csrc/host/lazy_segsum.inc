@@ -46,17 +46,7 @@ static int ensure_rw_current(sert_model* m, int64_t batch, int64_t t_applied) {
 
 // A deferred entity-table update (side-heavy schedule) must have landed before the main stream reads R_e,
 // its optimiser state or dR_e again.
-// ... and so must the step's TAIL where it ran on a queue of its own (round 6, optimizer_and_loss: tail_queue): it updates W and b and
-// reads dW's slabs, the loss partials and the sums of squares -- the next reader or writer of any of them on the main stream waits here.
-static int settle_tail(sert_model* m) {
-    if (m->tail_pending) {
-        SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_tail_done, 0));
-        m->tail_pending = false;
-    }
-    return 0;
-}
 static int settle_entity_update(sert_model* m) {
-    SERT_TRY(settle_tail(m));
     if (m->re_pending) {
         SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_re, 0));
         m->re_pending = false;
@@ -164,13 +154,8 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             // level 0 + the heavy words' partial sums / level 1 + their combine: one launch each
             PlusJob j = l == 0 ? hjob : heavy_combine_job();
             j.slot_is_row = (l == 0 && bx.slot_is_row) ? 1 : 0;
-            int ni = nitems;
-            // timing knock-outs (variants build, WRONG results; tools/experiments/r05_plus_ko.sh): 1 = the tree alone, 2 = the stream alone
-            static const int ko = variant_knob("SERT_KO_PLUS") ? atoi(variant_knob("SERT_KO_PLUS")) : 0;
-            if (ko == 1 && l == 0) j.extra = 0;
-            if (ko == 2 && l == 0) ni = 0;
-            hipLaunchKernelGGL(segsum_rows_plus, dim3(j.extra + cdiv(ni, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows, items,
-                               ni, m->g_rw, pout, d, divisor, j);
+            hipLaunchKernelGGL(segsum_rows_plus, dim3(j.extra + cdiv(nitems, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows, items,
+                               nitems, m->g_rw, pout, d, divisor, j);
             if (l == 1) heavy_combined = true;
             continue;
         }

@@ -23,8 +23,9 @@ static int reduce_rowloss(sert_model* m, hipStream_t st) {
 // One streaming optimiser launch over `count` elements (kernels_opt.h).
 static void launch_stream_opt(sert_model* m, hipStream_t st, float* p, float* g, float* s0, float* s1, size_t count,
                               int nb, const AdamArgs& aa, const AdadeltaArgs& da, float* sq,
-                              const uint32_t* bits, unsigned row_len, int rows_mode = kRowsAll, float* sq_new = nullptr) {
+                              const uint32_t* bits, unsigned row_len, float* sq_new = nullptr) {
     const bool keep = m->cfg.keep_grads != 0;
+    const int rows_mode = kRowsAll;   // (kernels_opt.h keeps the rows_mode parameter of its kernels; the host always passes kRowsAll)
     if (is_vs(m)) {
         if (keep) hipLaunchKernelGGL((adam_l2<true>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, aa, sq, bits, row_len, rows_mode, sq_new);
         else      hipLaunchKernelGGL((adam_l2<false>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, aa, sq, bits, row_len, rows_mode, sq_new);
@@ -44,36 +45,6 @@ static void optimizer_args(const sert_model* m, int64_t t, AdamArgs* aa, Adadelt
         const float tf = (float)t;
         aa->a_t = c.lr * sqrtf(1.0f - powf(c.beta2, tf)) / (1.0f - powf(c.beta1, tf));
     }
-}
-
-// The word-table rows no token of this batch points to (their gradient is the L2 term alone)
-// are not read by the batch's forward either: their update is issued NOW, at the start of the
-// committed step, on its own stream, and runs beside forward and backward; optimizer_and_loss
-// then only has the touched rows left on the critical path.
-// Measured at C2 and C4 (profiles/r02b_variants.txt): SLOWER than one launch behind the backward
-// (0.376 -> 0.391 ms at C2, 2.13 -> 2.25 ms at C4) -- the step is memory-system-bound from end to
-// end, a second queue adds no bandwidth, and two row-filtered launches stream worse than one dense
-// one.  Kept as an opt-in (SERT_ADAM_SPLIT=1) with its tests; off by default.
-static bool adam_split_enabled() {
-    static const bool on = variant_knob("SERT_ADAM_SPLIT") && atoi(variant_knob("SERT_ADAM_SPLIT")) != 0;
-    return on;
-}
-static int issue_untouched_rows_update(sert_model* m, const uint32_t* bits) {
-    m->early_issued = false;
-    m->early_sq = 0;
-    const bool split = adam_split_enabled();
-    if (!split || !bits || !m->use_touched || is_dp(m) || m->timing.enabled || m->nstreams < 2) return 0;
-    AdamArgs aa; AdadeltaArgs da;
-    optimizer_args(m, m->step + 1, &aa, &da);
-    // (the previous step's touched-row launch may have updated rows this launch owns)
-    SERT_HIP(hipStreamWaitEvent(m->stream4, m->ev_word_opt, 0));
-    const int nb = (int)std::min<int64_t>(kOptBlocks, cdiv(cdiv(m->n_rw, 4), 256));
-    launch_stream_opt(m, m->stream4, m->rw, m->g_rw, m->s0_rw, m->s1_rw, m->n_rw, nb, aa, da, m->red_sq, bits,
-                      (unsigned)m->cfg.word_dim, kRowsUntouched);
-    SERT_HIP(hipEventRecord(m->ev_early, m->stream4));
-    m->early_issued = true;
-    m->early_sq = nb;
-    return 0;
 }
 
 // The LAZY forms of the word table's dense update (kernels_opt.h: dense_update_skip / dense_update_lazy) -- one launch on the main stream.
@@ -112,7 +83,7 @@ static int launch_lazy_word_update(sert_model* m, const ParamTensor& t, const ui
         //  SERT_SKIP_BLOCKS in a variants build, tools/experiments/r05_skip_blocks.sh)
         static const int skip_blocks_knob = variant_knob("SERT_SKIP_BLOCKS") ? atoi(variant_knob("SERT_SKIP_BLOCKS")) : 0;
         const int nb_dense = nb;
-        const int nb = std::max(1, std::min<int>(skip_blocks_knob > 0 ? std::min(skip_blocks_knob, 4 * kOptBlocks) : skip_grid(nb_dense, t.n),
+        const int nb = std::max(1, std::min<int>(skip_blocks_knob > 0 ? std::min(skip_blocks_knob, 4 * kOptBlocks) : nb_dense,
                                                  (int)cdiv(nrows, 8u)));
         nb_skip = nb;
 #define SERT_SKIP_LAUNCH(ADAM, LPR, CPL)                                                                                   \
@@ -164,8 +135,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     m->step += 1;
     AdamArgs aa; AdadeltaArgs da;
     optimizer_args(m, m->step, &aa, &da);
-    // (partials [0, early_sq) belong to the untouched-row launch issued at the start of the step)
-    int n_sq = m->early_issued ? m->early_sq : 0;
+    int n_sq = 0;
     const bool exchanged = m->comm && !m->timing.enabled;
     // single GPU: the small tensors are updated on the side stream WHILE the word table
     // streams on the main one (independent tensors; every gradient is complete here)
@@ -241,7 +211,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             // (and for tables of 4 M elements and more: a small one lives in the caches, where the dense launch costs
             //  nothing to save -- the reference's C1, 640 k parameters: 91 us dense, 95 us lazy)
             static const bool lazy_small = variant_knob("SERT_LAZY_SMALL_TABLES") != nullptr;
-            if (i == 0 && tf && !m->early_issued && m->rw_last[0] && !c.keep_grads && c.word_dim % 4 == 0 &&
+            if (i == 0 && tf && m->rw_last[0] && !c.keep_grads && c.word_dim % 4 == 0 &&
                 m->cur_touched_frac <= lazy_max && (t.n >= ((size_t)1 << 22) || lazy_small)) {
                 n_sq += launch_lazy_word_update(m, t, tf, next_bits, nb, aa, da, m->red_sq + n_sq);
                 continue;
@@ -256,8 +226,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             const bool on_side = side_small && ((i == 1 && m->side_heavy) || (i >= 2 && m->ll_dw_side));
             launch_stream_opt(m, on_side ? ss : m->stream, t.p, t.g, t.s0, t.s1, t.n, nb, aa, da,
                               m->red_sq + n_sq, tf,
-                              i == 0 ? (unsigned)c.word_dim : 1u,
-                              (i == 0 && tf && m->early_issued) ? kRowsTouched : kRowsAll);
+                              i == 0 ? (unsigned)c.word_dim : 1u);
             n_sq += nb;
             continue;
         }
@@ -374,11 +343,6 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     };
     if (tail_splits > 0) {
         small_tensors(ss, 0x2u);          // R_e; W and b are updated by the tail launch below
-    } else if (split_small && dw_third_queue(m)) {
-        small_tensors(m->stream3, 0xCu);  // W, b: behind dW and its combine on the third queue
-        SERT_HIP(hipEventRecord(m->ev_join3, m->stream3));
-        SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_join3, 0));
-        small_tensors(ss, 0x2u);          // R_e
     } else if (split_small) {
         small_tensors(m->stream, 0xCu);   // W, b
         small_tensors(ss, 0x2u);          // R_e
@@ -405,23 +369,13 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     // The entity table's L2 + Adam, behind the join: the tail does not wait for it.  Nothing reads R_e, its state or dR_e before the next
     // loss kernel (settle_entity_update), so it streams its 0.96 GB beside the next step's gather and projection GEMM.  It also leaves
     // the sums of squares of the UPDATED table: the next step's regularisation term.
-    // Experiment (round 6 item 16, variants build: SERT_RE_BEHIND_TAIL=1): BEHIND the tail instead of beside it (an event of the main stream
-    // behind the tail launch).  The tail then takes 18 us instead of 137 at C4 -- and the next step's gather 203 instead of 76: the step is
-    // the same 1.30-1.34 ms either way (the two queues share one memory system).  Off.
-    static const bool re_behind_tail = variant_knob("SERT_RE_BEHIND_TAIL") && atoi(variant_knob("SERT_RE_BEHIND_TAIL")) == 1;
-    auto launch_deferred_re = [&]() -> int {
+    if (defer_re) {
         const ParamTensor t = param_tensor(m, 1);
-        launch_stream_opt(m, ss, t.p, t.g, t.s0, t.s1, t.n, re_nb, aa, da, m->red_sq + re_sq_lo, nullptr, 1u, kRowsAll,
+        launch_stream_opt(m, ss, t.p, t.g, t.s0, t.s1, t.n, re_nb, aa, da, m->red_sq + re_sq_lo, nullptr, 1u,
                           m->re_sq + re_nxt * re_cap);
         m->re_sq_for[re_nxt] = m->step + 1;
         SERT_HIP(hipEventRecord(m->ev_re, ss));
         m->re_pending = true;
-        return 0;
-    };
-    if (defer_re && !(re_behind_tail && tail_splits > 0)) SERT_TRY(launch_deferred_re());
-    if (m->early_issued) {   // the untouched rows' sum of squares (and their update) must have landed
-        SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_early, 0));
-        m->early_issued = false;
     }
     {
         ScopedTimer t(m, TG_FINALIZE);
@@ -432,36 +386,10 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         const float* lp = is_dp(m) ? m->g_loss : (m->loss_from_rows ? m->rowloss : m->red_loss);
         const int nl = is_dp(m) ? 1 : n_loss_partials;
         unsigned* flag = publish ? reinterpret_cast<unsigned*>(loss_dst + 4) : nullptr;
-        // timing knock-out (variants build, WRONG loss: the sums of squares of the word table are read while its update runs):
-        // the tail on the SIDE stream behind the entity chain -- what taking it off the main queue would buy (r06 experiments, item 6)
-        static const bool ko_tail_side = variant_knob("SERT_KO_TAIL_SIDE") != nullptr;
-        const bool tail_side = ko_tail_side && tail_splits > 0 && m->dw_side_first && defer_small && side_small;
-        hipStream_t ts = tail_side ? ss : m->stream;
-        // Experiment (round 6 item 17; variants build, SERT_TAIL_QUEUE=1): the tail on a QUEUE OF ITS OWN.  It is the last kernel of the step on
-        // the main stream and needs nothing the next step's gather touches: on its own queue -- behind an event of the main stream recorded
-        // here, behind dW's event -- it runs BESIDE the next step's gather, and only the next projection (which reads W and b) waits for it
-        // (settle_tail).  Bit-identical and SLOWER at every size (C2 0.2279-0.2304 against 0.2194-0.2198 ms, 8192 rows 0.111-0.116 against
-        // 0.094-0.095): two more hand-overs between queues (~10 us each) for 10 us of overlap.
-        static const int tail_queue_knob = variant_knob("SERT_TAIL_QUEUE") ? atoi(variant_knob("SERT_TAIL_QUEUE")) : -1;
-        const bool tail_queue = tail_queue_knob == 1 && tail_splits > 0 && !tail_side && !m->tail_early && publish &&
-                                !is_dp(m) && !m->timing.enabled && !c.keep_grads && m->nstreams >= 2 && m->tail_stream != nullptr &&
-                                c.batch_size >= m->tail_queue_min_batch;
-        if (tail_queue) {
-            SERT_HIP(hipEventRecord(m->ev_tail_go, m->stream));
-            SERT_HIP(hipStreamWaitEvent(m->tail_stream, m->ev_tail_go, 0));
-            if (m->dw_side_first) SERT_HIP(hipStreamWaitEvent(m->tail_stream, m->ev_dense, 0));
-            ts = m->tail_stream;
-        }
-        if (tail_splits > 0 && m->tail_early) {
-            // (knock-out: W and b were updated behind dW on the side stream; only the loss is left -- the next projection waits for ev_dense)
-            hipLaunchKernelGGL(finalize_loss, dim3(1), dim3(256), 0, m->stream, lp, nl, m->red_sq, n_sq, inv_batch, reg_scale, loss_dst, flag,
-                               publish ? ++m->loss_seq : 0u, (const float*)nullptr);
-            m->w_early_pending = true;
-        } else
         if (tail_splits > 0) {
-            if (m->dw_side_first && !tail_side && !tail_queue) SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_dense, 0));   // (dW / db slabs: side stream)
+            if (m->dw_side_first) SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_dense, 0));   // (dW / db slabs: side stream)
             TailArgs ta;
-            ta.part = m->tail_part ? m->tail_part : m->part; ta.splits = tail_splits; ta.stride = m->tail_stride;
+            ta.part = m->part; ta.splits = tail_splits; ta.stride = m->tail_stride;
             ta.W = m->W; ta.b = m->b; ta.s0_w = m->s0_w; ta.s1_w = m->s1_w; ta.s0_b = m->s0_b; ta.s1_b = m->s1_b;
             ta.g_w = m->g_w; ta.g_b = m->g_b;
             ta.n_w = (unsigned)m->n_w; ta.n_b = (unsigned)m->n_b;
@@ -478,30 +406,13 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             if (++m->tail_launch_seq == 0) ++m->tail_launch_seq;   // (0 = "never written")
             ta.launch_seq = m->tail_launch_seq;
             const int nb = cdiv((int64_t)(m->n_w + m->n_b), 64);
-            if (c.keep_grads) hipLaunchKernelGGL((vs_tail<true>), dim3(nb), dim3(1024), 0, ts, ta);
-            else              hipLaunchKernelGGL((vs_tail<false>), dim3(nb), dim3(1024), 0, ts, ta);
-            if (tail_queue) {
-                SERT_HIP(hipEventRecord(m->ev_tail_done, m->tail_stream));
-                m->tail_pending = true;
-            }
-            if (tail_side) {     // (the next projection reads W: it waits for this, see step_forward_backward)
-                SERT_HIP(hipEventRecord(m->ev_re, ss));
-                m->re_pending = true;
-                m->w_pending = true;
-            }
+            if (c.keep_grads) hipLaunchKernelGGL((vs_tail<true>), dim3(nb), dim3(1024), 0, m->stream, ta);
+            else              hipLaunchKernelGGL((vs_tail<false>), dim3(nb), dim3(1024), 0, m->stream, ta);
         } else
         hipLaunchKernelGGL(finalize_loss, dim3(1), dim3(256), 0, m->stream, lp, nl, m->red_sq,
                            n_sq, inv_batch, reg_scale, loss_dst, flag, publish ? ++m->loss_seq : 0u,
                            is_dp(m) ? (const float*)m->g_sq : (const float*)nullptr);
     }
-    if (defer_re && re_behind_tail && tail_splits > 0) {
-        SERT_HIP(hipEventRecord(m->ev_opt_fork, m->stream));
-        SERT_HIP(hipStreamWaitEvent(ss, m->ev_opt_fork, 0));
-        SERT_TRY(launch_deferred_re());
-    }
-    // (opt-in split optimiser: the next step's untouched-row launch, on its own stream, may start
-    // once this step has read its sum-of-squares partials and updated the rows it owns)
-    if (adam_split_enabled() && !is_dp(m) && !m->timing.enabled) SERT_HIP(hipEventRecord(m->ev_word_opt, m->stream));
     if (any_ag) {
         // the loss leaves first; the next kernel that reads a parameter waits for the last slab
         SERT_HIP(hipEventRecord(m->ev_ag_done, m->comm_stream));
@@ -594,9 +505,6 @@ static int step_forward_backward(sert_model* m, const DataSplit& ds, int64_t bat
     // the main stream's first kernels go out BEFORE the prologue's host calls: the GPU
     // starts on gather + projection while the host is still enqueueing
     if (is_vs(m) && !is_fs(m)) {
-        if (m->w_pending) { SERT_TRY(settle_entity_update(m)); m->w_pending = false; }   // (W, b updated on the side stream)
-        SERT_TRY(settle_tail(m));      // (the previous step's tail on its own queue: the projection reads W and b)
-        if (m->w_early_pending) { SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_dense, 0)); m->w_early_pending = false; }
         if (m->projected_batch != batch_index) SERT_TRY(vs_project(m, ds, batch_index));
         m->projected_batch = -1;
     }
@@ -682,9 +590,6 @@ static int train_step_async(sert_model* m, int64_t batch_index, const int64_t* n
     if (have_fb) m->spec_fb_batch = -1;     // consumed
     else discard_run_ahead(m);              // a run-ahead for something else: discard it cleanly
     const uint32_t* bits = ds.idx_touched_bits ? ds.idx_touched_bits + (size_t)batch_index * ds.bit_words : nullptr;
-    // this step is committed: the rows its batch does not touch are updated beside it
-    if (!have_fb) m->use_touched = use_touched_now(m);
-    SERT_TRY(issue_untouched_rows_update(m, bits));
     if (!have_fb) SERT_TRY(step_forward_backward(m, ds, batch_index, negatives, &fused_pre));
     SERT_TRY(allreduce_rest(m));
     m->cur_touched_frac = (size_t)batch_index < ds.idx_batches.size()

@@ -104,8 +104,6 @@ static bool ext_events() {
 // ends with a cache write-back): two per step instead of three.  SERT_FORK_LATE=0 restores the
 // fork right behind the NCE kernel with dW on the main stream.
 static bool side_heavy_mode(const sert_model* m);
-// Grid of dense_update_skip given the dense launches' grid for the same table (kOptBlocks, twice that from 2^24 elements).
-static int skip_grid(int nb_dense, size_t /*elements*/) { return nb_dense; }
 
 static bool fork_late_mode(const sert_model* m) {
     static const bool on = !(variant_knob("SERT_FORK_LATE") && atoi(variant_knob("SERT_FORK_LATE")) == 0);
@@ -127,15 +125,6 @@ static bool fork_at_nce(const sert_model* m) {
 static bool fork_at_nce_dw(const sert_model* m) {
     static const bool on = variant_knob("SERT_FORK_AT") && !strcmp(variant_knob("SERT_FORK_AT"), "nce_dw");
     return on && fork_at_nce(m);
-}
-
-// Late fork + a THIRD queue for the MFMA-bound dW GEMM, its combine and the W, b update: they only
-// need da and h, so they can run beside the cache-bound segmented sum instead of in front of it.
-// The queue waits on the same completion signal as the side stream (free for the main stream) and
-// is joined in front of the loss finalisation.  SERT_DW_THIRD=0 keeps them on the main stream.
-static bool dw_third_queue(const sert_model* m) {
-    static const bool on = variant_knob("SERT_DW_THIRD") && atoi(variant_knob("SERT_DW_THIRD")) != 0;
-    return on && fork_late_mode(m) && !fork_at_nce(m);   // (the W update must stay behind the dh GEMM)
 }
 
 // Single GPU, BIG entity table (more than 2^22 elements: the sorted entity-gradient chain and a streaming
@@ -342,9 +331,7 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         const int total = B * (c.num_negatives + 1);
         const int V = c.num_entities;
         m->re_in_parts = false;
-        static const bool ko_egrad = variant_knob("SERT_KO_EGRAD") != nullptr;   // timing knock-out (wrong results)
-        if (ko_egrad) {
-        } else if (m->epart) {
+        if (m->epart) {
             // small entity vocabulary: no global sort -- pairs bucketed by entity range per sub-group,
             // then row groups x entity ranges with the accumulators in LDS (kernels_egrad.h)
             const int de4 = de / 4, c1 = c.num_negatives + 1;
@@ -476,7 +463,6 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
             m->neg_alt_step = m->step + 1;
         }
         if (fork_late && !fork_nce) SERT_HIP(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
-        if (fork_late && dw_third_queue(m)) SERT_HIP(hipStreamWaitEvent(m->stream3, m->ev_fork, 0));
         return 0;
     };
     auto word_table_sum = [&]() -> int {
@@ -493,15 +479,9 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         // Third stream: dW and dh are both 512-workgroup launches (2 waves per SIMD, too
         // few to hide their own latencies) -- side by side they fill each other's bubbles.
         hipStream_t sd = (m->timing.enabled || m->nstreams < 3) ? m->stream : m->stream3;
-        // Single GPU, two streams: dW, db and the loss partials only feed the small-tensor
-        // optimiser and the loss, both of which already sit behind the entity chain on the side
-        // stream -- issued there (behind that chain) they leave the main stream with nothing but
-        // the dependency chain loss -> dh -> segmented sum -> word-table optimiser.
-        // (measured: 0.376 -> 0.386 ms at C2 -- off by default, SERT_DW_SIDE=1 to try it)
-        static const bool dw_side = variant_knob("SERT_DW_SIDE") && atoi(variant_knob("SERT_DW_SIDE")) != 0;
-        if ((dw_side || side_heavy) && m->lazy_join) sd = m->stream2;
+        // (side_heavy: on the side stream behind the entity chain, see side_heavy_mode)
+        if (side_heavy && m->lazy_join) sd = m->stream2;
         if (m->dp_late_join || m->dw_side_first) sd = m->stream2;
-        if (fork_late && m->lazy_join && dw_third_queue(m)) sd = m->stream3;
         if (sd != m->stream && sd != m->stream2 && !fork_late) SERT_HIP(hipStreamWaitEvent(sd, m->ev_fork, 0));
         // ~1024 workgroup items in all, at most 512 slabs (the optimum at one output tile: 512 slabs
         // of 128 rows) and at least 64 rows per slab.  With nine output tiles (d = 300) that is 114
@@ -552,21 +532,6 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
             mn + de < ((size_t)1 << 31)) {
             m->tail_splits = splits;
             m->tail_stride = stride;
-            m->tail_part = m->part;
-            // Experiment (round 6 item 14, variants build: SERT_COMBINE_SIDE=1): with dW / db first on the SIDE stream their split-K combine
-            // there too, right behind the GEMM (the tail's own summation order: reduce_partials_g<16>), so that the tail reads 66 kB of sums
-            // instead of the slabs.  Bit-identical and SLOWER at every batch size (C2 0.2294-0.2304 against 0.2226-0.2229 ms): the tail is a
-            // latency-bound launch whatever it reads, and the combine lengthens the side chain.
-            static const bool combine_side_off = !(variant_knob("SERT_COMBINE_SIDE") && atoi(variant_knob("SERT_COMBINE_SIDE")) == 1);
-            if (!combine_side_off && m->dw_side_first && sd == m->stream2 && splits > 1 && !c.keep_grads) {
-                ScopedTimer t(m, TG_SPLITK, sd);
-                const size_t count = stride;
-                hipLaunchKernelGGL((reduce_partials_g<16>), dim3((unsigned)((count + 63) / 64)), dim3(1024), 0, sd, (const float*)m->part, splits, stride,
-                                   count, m->g_w, mn, m->g_b, (const int32_t*)nullptr, 0);
-                m->tail_splits = 1;
-                m->tail_part = m->g_w;         // (g_w | g_b are adjacent in the flat gradient buffer: one "slab" of mn + de sums)
-                if (m->g_b != m->g_w + mn) SERT_FAIL("internal: g_W and g_b are not adjacent");
-            }
         } else {
             ScopedTimer t(m, TG_SPLITK);
             launch_reduce_partials(sd, m->part,
@@ -574,31 +539,6 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         }
         // the loss partials only depend on the NCE kernel too
         SERT_TRY(reduce_rowloss(m, sd));
-        // timing knock-out (variants build, WRONG loss; r06 experiments item 9): the dW combine + W, b update right behind dW on the side
-        // stream, the loss left to a one-workgroup launch behind the word table's update -- what splitting the tail that way would buy
-        static const bool ko_tail_early = variant_knob("SERT_KO_TAIL_EARLY") != nullptr;
-        m->tail_early = false;
-        if (ko_tail_early && m->tail_splits > 0 && m->dw_side_first && sd == m->stream2 && !c.keep_grads && !m->timing.enabled) {
-            AdamArgs aa2; AdadeltaArgs da2;
-            optimizer_args(m, m->step + 1, &aa2, &da2);
-            TailArgs ta;
-            ta.part = m->tail_part ? m->tail_part : m->part; ta.splits = m->tail_splits; ta.stride = m->tail_stride;
-            ta.W = m->W; ta.b = m->b; ta.s0_w = m->s0_w; ta.s1_w = m->s1_w; ta.s0_b = m->s0_b; ta.s1_b = m->s1_b;
-            ta.g_w = m->g_w; ta.g_b = m->g_b;
-            ta.n_w = (unsigned)m->n_w; ta.n_b = (unsigned)m->n_b;
-            ta.aa = aa2;
-            ta.loss_partials = m->red_loss; ta.n_loss = 0;
-            ta.sq_partials = m->red_sq; ta.n_sq = 0;
-            ta.sq_alt = nullptr; ta.sq_alt_lo = 0; ta.sq_alt_hi = 0;
-            ta.inv_batch = 1.f; ta.reg_scale = 0.f;
-            ta.out = m->d_loss; ta.host_flag = nullptr; ta.seq = 0u;
-            ta.blk = m->tail_blk;
-            if (++m->tail_launch_seq == 0) ++m->tail_launch_seq;
-            ta.launch_seq = m->tail_launch_seq;
-            const int nbt = cdiv((int64_t)(m->n_w + m->n_b), 64);
-            hipLaunchKernelGGL((vs_tail<false>), dim3(nbt), dim3(1024), 0, sd, ta);
-            m->tail_early = true;
-        }
         if (m->dw_side_first) SERT_HIP(hipEventRecord(m->ev_dense, sd));   // (the tail waits for this, not for the chain behind it)
         if (sd != m->stream && sd != m->stream2 && !fork_late) SERT_HIP(hipEventRecord(m->ev_join3, sd));
         return 0;
@@ -632,26 +572,17 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
     // fork, as in round 5: 0.2381-0.2404 / 0.2346-0.2360), 131072 0.4190-0.4222 / 0.4040-0.4142.
     SERT_TRY(early_bucket());
     SERT_TRY(early_sort());
-    static const bool chain_behind_tree = variant_knob("SERT_CHAIN_BEHIND_TREE") != nullptr;
     m->dw_side_first = fork_nce_dw ||
-                       (!dw_first_off && fork_late && !fork_nce && !side_heavy && m->lazy_join && !fused_bwd && !dw_third_queue(m) &&
+                       (!dw_first_off && fork_late && !fork_nce && !side_heavy && m->lazy_join && !fused_bwd &&
                         !m->pt_big[2] && c.kind == SERT_KIND_VECTORSPACE &&
                         (dw_first_always || (((size_t)B * dw * sizeof(float) <= ((size_t)24 << 20) || m->bucket_early) && m->epart)));
     // (m->epart: the sort-free entity chain of small entity tables.  Behind the counting sort of a larger one the side stream is
     //  the longer of the two already: the reference's product-search settings, V_e = 32768, 205.8 -> 214.5 us with dW in front)
-    static const int dp_late_mode = variant_knob("SERT_DP_LATE") ? atoi(variant_knob("SERT_DP_LATE")) : 1;   // 0: off; 2: dW behind the chain
-    const bool dp_late = dp_late_mode != 0 && is_dp(m) && !m->host_ar && m->comm && !m->timing.enabled && m->nstreams == 2 && !side_heavy && !fork_nce &&
+    static const bool dp_late_off = variant_knob("SERT_DP_LATE") && atoi(variant_knob("SERT_DP_LATE")) == 0;
+    const bool dp_late = !dp_late_off && is_dp(m) && !m->host_ar && m->comm && !m->timing.enabled && m->nstreams == 2 && !side_heavy && !fork_nce &&
                          !fork_late;
     m->dp_late_join = dp_late;
-    if (side_heavy && chain_behind_tree && m->sort_early) {
-        // (experiment, round 6 item 13: with the key sort beside the forward, the rest of the sorted entity chain -- chunked reduce, fix-up, then
-        //  dW -- forked behind the word gradient's TREE instead of behind the loss kernel: beside the update, not beside the tree)
-        SERT_TRY(dh_gemm());
-        SERT_TRY(word_table_sum());
-        m->fork_bound = false;         // (not the loss kernel's completion signal: a record behind the tree)
-        SERT_TRY(entity_grad());       // (records its fork on the main stream HERE: behind the tree)
-        SERT_TRY(dense_grad());
-    } else if (side_heavy) {
+    if (side_heavy) {
         SERT_TRY(entity_grad());       // side, forked on the loss kernel's completion
         SERT_TRY(dh_gemm());           // main (its completion is ev_dense)
         SERT_TRY(word_table_sum());    // main
@@ -679,12 +610,7 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         // data parallel: the word-table gradient first, so that its exchange (rows' all-to-all or
         // reduce-scatter) overlaps dW and the entity chain (dW in front of the segmented sum instead:
         // 0.362 -> 0.370 ms with a world of one -- the hand-over then sits bare on the critical path)
-        if (dp_late && dp_late_mode == 2) {
-            SERT_TRY(entity_grad());
-            SERT_TRY(dh_gemm());
-            SERT_TRY(word_table_sum());
-            SERT_TRY(dense_grad());        // (side, behind the entity chain)
-        } else if (dp_late) {
+        if (dp_late) {
             // the side stream takes dW, db and the loss sum FIRST (beside dh and the segmented sum), then the entity chain:
             // behind that chain they ran beside the word table's Adam, three times as long, and the small all-reduce --
             // which waits for them -- ended 35 us after the Adam (0.330 ms; this order: 0.29)
@@ -694,12 +620,10 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
             // trace, tools/experiments/r05_hip_trace.sh with SERT_FORCE_COMM=1): the launches go out in order of
             // criticality -- the main stream's dh GEMM first; issued behind the six side-stream launches it started 27 us
             // after the loss kernel had finished (C2, world of one).
-            static const bool dx_last = variant_knob("SERT_DP_DX_LAST") != nullptr;   // (the round-4 order, for the A/B)
-            if (!dx_last) SERT_TRY(dh_gemm());
+            SERT_TRY(dh_gemm());
             SERT_TRY(dense_grad());
             m->fork_bound = true;          // (the fork is recorded: the entity chain only has to follow in stream order)
             SERT_TRY(entity_grad());
-            if (dx_last) SERT_TRY(dh_gemm());
             SERT_TRY(word_table_sum());
         } else {
             SERT_TRY(entity_grad());
@@ -725,6 +649,5 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_join, 0));
     }
     if (!m->timing.enabled && m->nstreams >= 3) SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_join3, 0));
-    (void)row0;
     return 0;
 }

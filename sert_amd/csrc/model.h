@@ -101,7 +101,7 @@ struct sert_model {
     bool fork_bound = false;         // ev_fork rides on the NCE kernel's completion signal (no record needed)
     bool egrad_ranges = false;       // SERT_EGRAD_RANGES=1 at sert_create: the one-launch range kernel for few pairs over a mid-size table (opt-in)
     bool egrad_force_sort = false;   // SERT_EGRAD_SORT=1 at sert_create: the sorted entity-gradient path whatever the shape
-    bool events_device_scope = false;  // the intra-model events carry hipEventDisableSystemFence (no communicator; sert_hip.hip: create_intra_events)
+    bool events_device_scope = false;  // the intra-model events carry hipEventDisableSystemFence (no communicator; host/api_model.inc: create_intra_events)
     bool lazy_join = false;          // this step: the main stream never waits for the entity chain
     int num_cus = 256;               // compute units of the device (persistent launches: one workgroup per CU)
     bool proj_fused = false;         // gather + mean-pool + projection in one launch where the shape allows (kernels_proj.h; opt-in, SERT_PROJ_FUSED=1)
@@ -115,12 +115,6 @@ struct sert_model {
     // the previous step's launch (re_sq[k]: partials of the updated table, for optimiser step re_sq_for[k])
     hipEvent_t ev_re = nullptr;
     bool re_pending = false;
-    bool tail_early = false, w_early_pending = false;   // (knock-out SERT_KO_TAIL_EARLY: see sert_hip.hip)
-    hipStream_t tail_stream = nullptr;   // the step's tail on a queue of its own (optimizer_and_loss: tail_queue)
-    hipEvent_t ev_tail_go = nullptr, ev_tail_done = nullptr;
-    bool tail_pending = false;
-    int tail_queue_min_batch = 0;
-    bool w_pending = false;          // W, b were updated on the side stream too (same event): the next projection waits
     float* re_sq = nullptr;          // [2][2 * kOptBlocks]
     int64_t re_sq_for[2] = {-1, -1};
     int n_loss_partials = 0;
@@ -132,8 +126,8 @@ struct sert_model {
     int nstreams = 2;
     int64_t hint_next = -1;        // sert_hint_next_batch
     bool neg_side_ready = false;   // this step's negatives were drawn on the side stream during the previous step
-    bool sort_early = false;       // this step's entity keys were sorted in front of the fork (sert_hip.hip: vs_backward, early_sort)
-    bool bucket_early = false;     // this step's egrad_bucket ran in front of the fork (sert_hip.hip: vs_backward)
+    bool sort_early = false;       // this step's entity keys were sorted in front of the fork (host/step_vectorspace.inc: vs_backward, early_sort)
+    bool bucket_early = false;     // this step's egrad_bucket ran in front of the fork (host/step_vectorspace.inc: vs_backward)
     // lazy dense update of the word table (kernels_opt.h: dense_update_lazy)
     int32_t* rw_last[2] = {nullptr, nullptr};   // per word row: updates applied to its stored (p, state0, state1)
     int rw_last_cur = 0;           // which of the two holds the current values
@@ -218,16 +212,8 @@ struct sert_model {
     float2* ll_tokstat = nullptr; float* ll_lse = nullptr; float2* ll_jstat = nullptr;
     float4* ll_rowinfo = nullptr; float* ll_rpart = nullptr; float* ll_r = nullptr;
     // single GPU: the word-gradient table is neither zeroed nor read where no token of the
-    // batch points (static per-batch row bitmaps, DataSplit::idx_touched_bits) ...
+    // batch points (static per-batch row bitmaps, DataSplit::idx_touched_bits)
     bool use_touched = false;
-    // ... and the optimiser of those untouched rows -- rows the batch's own forward never reads --
-    // is issued at the START of the step on its own stream, beside forward and backward
-    // (opt-in, SERT_ADAM_SPLIT=1: measured SLOWER than one launch behind the backward, see sert_hip.hip)
-    hipStream_t stream4 = nullptr;
-    hipEvent_t ev_word_opt = nullptr;   // the touched rows' update of the previous step was issued (main stream)
-    hipEvent_t ev_early = nullptr;      // this step's untouched-row update is complete (stream4)
-    bool early_issued = false;          // this step's untouched-row launch is in flight
-    int early_sq = 0;                   // ... and wrote this many sum-of-squares partials to red_sq[0..)
 
     // loglinear, logits per DISTINCT word of the batch (duplicate tokens share a row):
     float* Zu = nullptr;          // (U, V_e) logits
@@ -243,7 +229,6 @@ struct sert_model {
     // single-GPU vectorspace step: split-K combine + W, b update + loss finalisation as one launch
     // (kernels_opt.h: vs_tail).  tail_splits > 0: this step's dW / db still sit in `part` as that
     // many partial slabs, tail_stride elements apart
-    const float* tail_part = nullptr;   // where the tail finds dW | db: the split-K slabs, or their sums (combined on the side stream)
     unsigned long long* tail_blk = nullptr;
     unsigned tail_launch_seq = 0;
     int tail_splits = 0;
