@@ -25,6 +25,11 @@ extern "C" {
  * shape met the oracle (tests/test_gpu_skip_shapes.py). */
 int sert_debug_update_counts(sert_model* m, int64_t* out, int n);
 
+/* Tail launches of the single-GPU vectorspace step (split-K combine of dW / db, the W, b update, the loss) since sert_create
+ * -- host counters, test hook: out[0] launched alone (vs_tail), out[1] launched as the leading workgroups of the next
+ * batch's gather (vs_gather_mean_tail: hinted steps, sert_hint_next_batch).  n <= 2.  (tests/test_gpu_tail_in_gather.py) */
+int sert_debug_tail_counts(sert_model* m, int64_t* out, int n);
+
 /* Test hook: overwrite the step's gradient scratch -- the flat buffer [g_Rw | g_Re | g_W | g_b | loss, sum of squares] with
  * quiet NaNs, the per-entity sorted-run bounds behind it with the wrong run [0, 1) -- after waiting for the device.  A step
  * whose negatives were drawn ahead launches NO prologue (nothing is zeroed): it relies on every value it reads having been

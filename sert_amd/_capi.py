@@ -40,7 +40,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 
@@ -400,6 +400,13 @@ class Engine(object):
         check(self._lib.sert_debug_update_counts(self._h, v, 10))
         names = ('dense', 'lazy', 'skip_32_1', 'skip_64_1', 'skip_32_3', 'skip_64_2', 'skip_64_3', 'skip_64_4', 'skip_full', 'skip_sparse')
         return dict(zip(names, (int(x) for x in v)))
+
+    def tail_counts(self):
+        """sert_debug_tail_counts (test hook): the vectorspace step's tail launches since creation, alone and inside a gather."""
+        v = (ctypes.c_int64 * 2)()
+        self._lib.sert_debug_tail_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+        check(self._lib.sert_debug_tail_counts(self._h, v, 2))
+        return {'alone': int(v[0]), 'in_gather': int(v[1])}
 
     def timings(self):
         n = self._lib.sert_timing_count(self._h)

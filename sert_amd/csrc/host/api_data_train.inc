@@ -217,10 +217,7 @@ int sert_train_batch(sert_model* m, int64_t batch_index, const int64_t* negative
     m->lazy_next = hint;
     auto prefetch_next = [&]() -> int {
         const DataSplit& ds = m->split[SERT_SPLIT_TRAIN];
-        // (keep_grads: the caller may read this batch's activations after the call)
-        if (hint < 0 || m->timing.enabled || m->cfg.keep_grads) return 0;
-        if ((hint + 1) * (int64_t)m->cfg.batch_size > ds.N) return 0;
-        if (can_speculate_step(m)) {
+        if (will_run_ahead(m, hint)) {
             // the whole forward + backward of the announced batch runs ahead: it depends on the
             // parameters (final: this step's update is already in the stream), the data and the
             // step counter only, and writes activations / gradient scratch only.  The UPDATE of
@@ -229,7 +226,12 @@ int sert_train_batch(sert_model* m, int64_t batch_index, const int64_t* negative
             SERT_TRY(step_forward_backward(m, ds, hint, nullptr, &fused));
             m->spec_fb_batch = hint;
             m->spec_fb_step = m->step;
-        } else if (is_vs(m) && !is_fs(m)) {
+            return 0;
+        }
+        // (keep_grads: the caller may read this batch's activations after the call)
+        if (hint < 0 || m->timing.enabled || m->cfg.keep_grads) return 0;
+        if ((hint + 1) * (int64_t)m->cfg.batch_size > ds.N) return 0;
+        if (is_vs(m) && !is_fs(m)) {
             // data parallel: the parameter-only part (by rows: behind the fetch of the rows it reads)
             if (m->xr_on) SERT_TRY(xr_fetch_params(m, hint));
             SERT_TRY(vs_project(m, ds, hint));
@@ -254,8 +256,19 @@ int sert_train_batch(sert_model* m, int64_t batch_index, const int64_t* negative
     // synchronisation on the per-step read-back the reference's epoch loop performs
     // (sert/models.py:369-379): 0.412 -> 0.396 ms/step at C2.  Everything the step did is
     // stream-ordered before that kernel, so the parameters are final when the number appears.
-    SERT_TRY(train_step_async(m, batch_index, negatives, m->h_loss_dev, true));
-    SERT_TRY(prefetch_next());
+    // A step whose announced next batch will run ahead right behind it leaves its tail launch (vs_tail: dW / db combine, the
+    // W, b update, the loss) to that batch's gather launch (kernels_vs.h: vs_gather_mean_tail; vs_project).  Whatever
+    // prefetch_next does -- nothing, an error -- a tail no gather carried is launched on its own before the host waits:
+    // a step is never left without its publisher.  (SERT_TAIL_IN_GATHER=0, variants build: every tail alone.)
+    static const bool no_fold = variant_knob("SERT_TAIL_IN_GATHER") && atoi(variant_knob("SERT_TAIL_IN_GATHER")) == 0;
+    // (single-GPU vectorspace: will_run_ahead then implies keep_grads off and word_dim % 4 == 0 -- the VEC == 4 gather --
+    //  through use_touched_now; a gather launch of another form flushes the tail in front of itself, vs_project)
+    m->tail_defer = !no_fold && !is_dp(m) && is_vs(m) && !is_fs(m) && will_run_ahead(m, hint);
+    int rc = train_step_async(m, batch_index, negatives, m->h_loss_dev, true);
+    m->tail_defer = false;
+    if (rc == 0) rc = prefetch_next();
+    flush_pending_tail(m);
+    if (rc != 0) return rc;
     const unsigned want = m->loss_seq;
     volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(m->h_loss + 4);
     // A faulted step never publishes: ask the stream -- but RARELY.  hipStreamQuery on a stream whose last command carries no

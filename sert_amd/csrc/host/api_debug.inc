@@ -23,6 +23,12 @@ int sert_debug_update_counts(sert_model* m, int64_t* out, int n) {
     return 0;
 }
 
+int sert_debug_tail_counts(sert_model* m, int64_t* out, int n) {
+    if (!m || !out || n < 1 || n > 2) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = m->tail_counts[i];
+    return 0;
+}
+
 int sert_debug_row_lists(const uint32_t* allbits, int world, int rank, int64_t num_batches, int64_t bit_words,
                          int64_t rows_per_rank, int64_t vocab, int64_t batch, int32_t* serve_cnt, int32_t* fetch_cnt,
                          int32_t* serve_rows, int32_t* fetch_rows, int32_t* union_rows, int32_t* ptr, int32_t* ent,

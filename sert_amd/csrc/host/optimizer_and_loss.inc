@@ -406,8 +406,17 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             if (++m->tail_launch_seq == 0) ++m->tail_launch_seq;   // (0 = "never written")
             ta.launch_seq = m->tail_launch_seq;
             const int nb = cdiv((int64_t)(m->n_w + m->n_b), 64);
-            if (c.keep_grads) hipLaunchKernelGGL((vs_tail<true>), dim3(nb), dim3(1024), 0, m->stream, ta);
-            else              hipLaunchKernelGGL((vs_tail<false>), dim3(nb), dim3(1024), 0, m->stream, ta);
+            if (m->tail_defer && publish && !c.keep_grads) {
+                // a hinted step: the gather launch of the run-ahead step carries these workgroups (vs_project); the wait
+                // for ev_dense above stays where it is -- it also keeps that gather from overwriting H under dW
+                m->tail_args = ta;
+                m->tail_nb = nb;
+                m->tail_pending = true;
+            } else {
+                ++m->tail_counts[0];
+                if (c.keep_grads) hipLaunchKernelGGL((vs_tail<true>), dim3(nb), dim3(1024), 0, m->stream, ta);
+                else              hipLaunchKernelGGL((vs_tail<false>), dim3(nb), dim3(1024), 0, m->stream, ta);
+            }
         } else
         hipLaunchKernelGGL(finalize_loss, dim3(1), dim3(256), 0, m->stream, lp, nl, m->red_sq,
                            n_sq, inv_batch, reg_scale, loss_dst, flag, publish ? ++m->loss_seq : 0u,
@@ -572,6 +581,13 @@ static bool can_speculate_step(const sert_model* m) {
     }
     if (is_vs(m) && !is_fs(m)) return use_touched_now(m) && fused_prologue_applies_with(m, true);
     return true;   // loglinear / full-softmax: the whole step lives on the main stream
+}
+
+// Will sert_train_batch send the whole forward + backward of the announced batch `hint` out behind the step it is issuing?
+// ONE predicate for the two places that must agree: prefetch_next, which does it, and the deferral of the step's tail
+// launch into that run-ahead's gather launch.
+static bool will_run_ahead(const sert_model* m, int64_t hint) {
+    return hint >= 0 && (hint + 1) * (int64_t)m->cfg.batch_size <= m->split[SERT_SPLIT_TRAIN].N && can_speculate_step(m);
 }
 
 static int train_step_async(sert_model* m, int64_t batch_index, const int64_t* negatives,

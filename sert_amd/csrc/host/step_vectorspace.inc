@@ -27,6 +27,16 @@ static int vs_negatives(sert_model* m, const int64_t* negatives, uint64_t stream
     return 0;
 }
 
+// A deferred tail (optimizer_and_loss) that no gather launch carried: the plain vs_tail, now.  In front of anything that
+// reads W or b, and before the host waits for the step's loss.
+static void flush_pending_tail(sert_model* m) {
+    if (!m->tail_pending) return;
+    m->tail_pending = false;
+    ScopedTimer t(m, TG_FINALIZE);
+    ++m->tail_counts[0];
+    hipLaunchKernelGGL((vs_tail<false>), dim3(m->tail_nb), dim3(1024), 0, m->stream, m->tail_args);
+}
+
 // gather + mean-pool + projection: needs neither the negatives nor the gradient buffers
 static int vs_project(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     const auto& c = m->cfg;
@@ -38,6 +48,7 @@ static int vs_project(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     // rows.  SERT_GEMM_FP32=1 (the fused kernel multiplies on the bf16 pipe) keeps the two launches too.
 #ifdef SERT_VARIANTS
     if (m->proj_fused && gemm_x3_enabled() && vs_project_fused_ok(B, n, dw, de, m->n_rw)) {
+        flush_pending_tail(m);
         if (m->T_alt) std::swap(m->T, m->T_alt);     // (see below: this projection goes to the other buffer)
         ScopedTimer t(m, TG_GATHER);
         SERT_ID_DISPATCH(c.id_bytes, {
@@ -57,18 +68,27 @@ static int vs_project(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             // profiles/r05_experiments.txt, item 32.
 #ifdef SERT_VARIANTS
             const int nhot = (ds.idx_tok_slot && (size_t)batch_index < ds.dense_cnt_of.size()) ? ds.dense_cnt_of[(size_t)batch_index] : 0;
-            if (dw % 4 == 0 && nhot > 0 && (size_t)nhot * dw * sizeof(float) <= 48 * 1024)
+            if (dw % 4 == 0 && nhot > 0 && (size_t)nhot * dw * sizeof(float) <= 48 * 1024) {
+                flush_pending_tail(m);
                 hipLaunchKernelGGL((vs_gather_mean_hot<IdT>), dim3(std::min<int64_t>(grid_for((int64_t)B * dw / 4, 256, 1 << 20), 8 * m->num_cus)),
                                    dim3(256), (size_t)nhot * dw * sizeof(float), m->stream, X, (const uint8_t*)ds.idx_tok_slot + row0 * n,
                                    (const int32_t*)ds.idx_dense_words + (size_t)batch_index * kHeavyMax, nhot, (const float*)m->rw, m->H, B, n, dw);
-            else
+            } else
 #endif
-            if (dw % 4 == 0)
+            if (dw % 4 == 0 && m->tail_pending) {
+                // the previous step's tail: the leading workgroups of this launch (kernels_vs.h: vs_gather_mean_tail)
+                m->tail_pending = false;
+                ++m->tail_counts[1];
+                hipLaunchKernelGGL((vs_gather_mean_tail<IdT>), dim3(m->tail_nb + grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
+                                   dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw, m->tail_args, (unsigned)m->tail_nb);
+            } else if (dw % 4 == 0) {
                 hipLaunchKernelGGL((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
                                    dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
-            else
+            } else {
+                flush_pending_tail(m);
                 hipLaunchKernelGGL((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
                                    dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+            }
         });
     }
     // The entity-gradient chain of the PREVIOUS step reads that step's projection rows on the side stream, and the main stream

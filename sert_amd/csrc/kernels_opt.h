@@ -790,25 +790,53 @@ struct TailArgs {
     unsigned launch_seq;          // != 0, different from the previous launch's
 };
 
-template <bool STORE_G>
-__global__ __launch_bounds__(1024) void vs_tail(const TailArgs t) {
-    __shared__ float red[16][64];
-    __shared__ double dred[2][16];
-    const int l = threadIdx.x & 63, g = threadIdx.x >> 6;
+// The body, for workgroup `blk` of `nblk` tail workgroups of NT threads (1024: vs_tail below; 256: the leading workgroups of
+// kernels_vs.h: vs_gather_mean_tail).  The arithmetic is laid out over 1024 VIRTUAL threads -- sixteen waves g of 64 lanes --
+// whatever NT is: a thread of a narrower workgroup plays 1024 / NT of them in turn (thread x is virtual thread x + NT * j,
+// same lane, wave g = x / 64 + (NT / 64) * j), so every sum has the same terms in the same order and the bits do not depend
+// on NT.  red: [16][64] floats, dred: [2][16] doubles of LDS.
+template <bool STORE_G, int NT>
+__device__ __forceinline__ void vs_tail_body(const TailArgs& t, const unsigned blk, const unsigned nblk, float (*red)[64],
+                                             double (*dred)[16]) {
+    static_assert(NT == 1024 || NT == 256, "vs_tail's and vs_gather_mean_tail's workgroups");
+    constexpr int J = 1024 / NT, NW = NT / 64;
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
     const unsigned count = t.n_w + t.n_b;
-    const unsigned i = blockIdx.x * 64u + (unsigned)l;
-    float a = 0.f;
+    const unsigned i = blk * 64u + (unsigned)l;
+    // (wave g adds slabs g, g + 16, ... in that order; a narrow workgroup's waves keep the loads of all their J virtual
+    //  waves in flight together -- one after the other they were J times as many dependent round trips)
+    float a[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) a[j] = 0.f;
     if (i < count) {
-#pragma unroll 8
-        for (int s = g; s < t.splits; s += 16) a += t.part[(size_t)s * t.stride + i];
+        int s0 = 0;
+        // Unroll: J = 4 keeps sixteen loads in flight per thread.  No more than that: the combined kernel's registers are
+        // the larger of its two paths -- as it is, vs_gather_mean_tail takes 68 VGPRs with 32-bit ids and 76 with 8- and
+        // 16-bit ids, two more than vs_gather_mean<., 4> and the same 7 / 6 waves per SIMD; 72 is the step from 7 to 6
+        // (DESIGN.md section 3).
+        constexpr int kTrips = J == 1 ? 8 : 4;
+#pragma unroll kTrips
+        for (; s0 + 16 <= t.splits; s0 += 16) {
+#pragma unroll
+            for (int j = 0; j < J; ++j) a[j] += t.part[(size_t)(s0 + w + NW * j) * t.stride + i];
+        }
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if (s0 + w + NW * j < t.splits) a[j] += t.part[(size_t)(s0 + w + NW * j) * t.stride + i];
     }
-    red[g][l] = a;
-    double ls = 0.0, sq = 0.0;
-    for (int k = blockIdx.x * 1024 + threadIdx.x; k < t.n_loss; k += gridDim.x * 1024) ls += (double)t.loss_partials[k];
-    for (int k = blockIdx.x * 1024 + threadIdx.x; k < t.n_sq; k += gridDim.x * 1024)
-        sq += (double)((k >= t.sq_alt_lo && k < t.sq_alt_hi) ? t.sq_alt[k - t.sq_alt_lo] : t.sq_partials[k]);
+#pragma unroll
+    for (int j = 0; j < J; ++j) red[w + NW * j][l] = a[j];
+    double ls[J], sq[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int vt = (int)threadIdx.x + NT * j;
+        ls[j] = 0.0; sq[j] = 0.0;
+        for (int k = blk * 1024 + vt; k < t.n_loss; k += nblk * 1024) ls[j] += (double)t.loss_partials[k];
+        for (int k = blk * 1024 + vt; k < t.n_sq; k += nblk * 1024)
+            sq[j] += (double)((k >= t.sq_alt_lo && k < t.sq_alt_hi) ? t.sq_alt[k - t.sq_alt_lo] : t.sq_partials[k]);
+    }
     __syncthreads();
-    if (g == 0 && i < count) {
+    if (w == 0 && i < count) {      // (virtual wave 0)
         float q[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) q[k] = (red[4 * k][l] + red[4 * k + 1][l]) + (red[4 * k + 2][l] + red[4 * k + 3][l]);
@@ -821,7 +849,7 @@ __global__ __launch_bounds__(1024) void vs_tail(const TailArgs t) {
             { float unused = 0.f; adam_elem(pp, gg, m, v, aa, omb1, omb2, ssf, unused); }
             t.W[i] = pp; t.s0_w[i] = m; t.s1_w[i] = v;
             if (STORE_G) t.g_w[i] = gg;
-            sq += (double)ssf;
+            sq[0] += (double)ssf;
         } else {
             const unsigned j = i - t.n_w;
             aa.l2k = 0.f;
@@ -832,11 +860,14 @@ __global__ __launch_bounds__(1024) void vs_tail(const TailArgs t) {
         }
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        ls += __shfl_xor(ls, off);
-        sq += __shfl_xor(sq, off);
+    for (int j = 0; j < J; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            ls[j] += __shfl_xor(ls[j], off);
+            sq[j] += __shfl_xor(sq[j], off);
+        }
+        if (l == 0) { dred[0][w + NW * j] = ls[j]; dred[1][w + NW * j] = sq[j]; }
     }
-    if (l == 0) { dred[0][g] = ls; dred[1][g] = sq; }
     __syncthreads();
     if (threadIdx.x < 4) {
         // each fp64 sum travels as a (hi, lo) pair of floats -- hi = (float)x, lo = (float)(x - hi): 48 bits of the
@@ -845,37 +876,41 @@ __global__ __launch_bounds__(1024) void vs_tail(const TailArgs t) {
         const int which = threadIdx.x >> 1;
         double x = 0.0;
 #pragma unroll
-        for (int w = 0; w < 16; ++w) x += dred[which][w];
+        for (int k = 0; k < 16; ++k) x += dred[which][k];
         const float hi = (float)x;
         const float piece = (threadIdx.x & 1) ? (float)(x - (double)hi) : hi;
         const unsigned long long word = ((unsigned long long)t.launch_seq << 32) | (unsigned long long)__float_as_uint(piece);
-        __hip_atomic_store(t.blk + 4 * blockIdx.x + threadIdx.x, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(t.blk + 4 * blk + threadIdx.x, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (blockIdx.x != gridDim.x - 1) return;
+    if (blk != nblk - 1) return;
     // ---- the collector: wait for every workgroup's four words, add them in workgroup order ----
     // (the only wait of the launch; it cannot deadlock: no other workgroup ever waits, so they all run to
     // completion whatever the dispatch order -- also under serialised dispatch, where this one is simply last)
     __syncthreads();
-    double c0 = 0.0, c1 = 0.0;
-    for (unsigned k = threadIdx.x; k < gridDim.x; k += 1024) {
-        unsigned long long w[4];
+    double c0[J], c1[J];
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            do { w[j] = __hip_atomic_load(t.blk + 4 * k + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((unsigned)(w[j] >> 32) != t.launch_seq);
-        c0 += (double)__uint_as_float((unsigned)w[0]) + (double)__uint_as_float((unsigned)w[1]);
-        c1 += (double)__uint_as_float((unsigned)w[2]) + (double)__uint_as_float((unsigned)w[3]);
-    }
+    for (int j = 0; j < J; ++j) {
+        c0[j] = 0.0; c1[j] = 0.0;
+        for (unsigned k = threadIdx.x + NT * j; k < nblk; k += 1024) {
+            unsigned long long wd[4];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        c0 += __shfl_xor(c0, off);
-        c1 += __shfl_xor(c1, off);
+            for (int q = 0; q < 4; ++q)
+                do { wd[q] = __hip_atomic_load(t.blk + 4 * k + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((unsigned)(wd[q] >> 32) != t.launch_seq);
+            c0[j] += (double)__uint_as_float((unsigned)wd[0]) + (double)__uint_as_float((unsigned)wd[1]);
+            c1[j] += (double)__uint_as_float((unsigned)wd[2]) + (double)__uint_as_float((unsigned)wd[3]);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            c0[j] += __shfl_xor(c0[j], off);
+            c1[j] += __shfl_xor(c1[j], off);
+        }
+        if (l == 0) { dred[0][w + NW * j] = c0[j]; dred[1][w + NW * j] = c1[j]; }
     }
-    if (l == 0) { dred[0][g] = c0; dred[1][g] = c1; }
     __syncthreads();
     if (threadIdx.x == 0) {
         double loss_sum = 0.0, sq_sum = 0.0;
 #pragma unroll
-        for (int w = 0; w < 16; ++w) { loss_sum += dred[0][w]; sq_sum += dred[1][w]; }
+        for (int k = 0; k < 16; ++k) { loss_sum += dred[0][k]; sq_sum += dred[1][k]; }
         const float data = (float)loss_sum * t.inv_batch;
         const float reg = t.reg_scale * (float)sq_sum;
         t.out[0] = data + reg;
@@ -883,6 +918,13 @@ __global__ __launch_bounds__(1024) void vs_tail(const TailArgs t) {
         t.out[2] = reg;
         if (t.host_flag) __hip_atomic_store(t.host_flag, t.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+template <bool STORE_G>
+__global__ __launch_bounds__(1024) void vs_tail(const TailArgs t) {
+    __shared__ float red[16][64];
+    __shared__ double dred[2][16];
+    vs_tail_body<STORE_G, 1024>(t, blockIdx.x, gridDim.x, red, dred);
 }
 
 }  // namespace sert

@@ -1,6 +1,7 @@
 // vectorspace / LSE kernels (sert/models.py:1024-1118), gfx950.
 #pragma once
 #include "common.h"
+#include "kernels_opt.h"   // (TailArgs, vs_tail_body: vs_gather_mean_tail)
 
 namespace sert {
 
@@ -12,15 +13,16 @@ namespace sert {
 #ifndef SERT_GATHER_GC
 #define SERT_GATHER_GC 10   // window positions fetched per trip (25 us vs 35 at C2)
 #endif
+// (the body, for workgroup `blk` of `nblk`: the launch below and vs_gather_mean_tail, whose gather workgroups sit behind the
+//  step tail's)
 template <typename IdT, int VEC>
-__global__ __launch_bounds__(256) void vs_gather_mean(const IdT* __restrict__ X,
-                                                      const float* __restrict__ Rw,
-                                                      float* __restrict__ H, int B, int n, int d) {
+__device__ __forceinline__ void vs_gather_mean_body(const IdT* __restrict__ X, const float* __restrict__ Rw,
+                                                    float* __restrict__ H, int B, int n, int d, unsigned blk, unsigned nblk) {
     const int chunks = d / VEC;
     const int64_t total = (int64_t)B * chunks;
     const float fn = (float)n;
-    for (int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; tid < total;
-         tid += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t tid = blk * (int64_t)blockDim.x + threadIdx.x; tid < total;
+         tid += (int64_t)nblk * blockDim.x) {
         const int row = (int)(tid / chunks);
         const int c = (int)(tid - (int64_t)row * chunks) * VEC;
         const IdT* xr = X + (size_t)row * n;
@@ -50,6 +52,34 @@ __global__ __launch_bounds__(256) void vs_gather_mean(const IdT* __restrict__ X,
             H[(size_t)row * d + c] = a / fn;
         }
     }
+}
+template <typename IdT, int VEC>
+__global__ __launch_bounds__(256) void vs_gather_mean(const IdT* __restrict__ X,
+                                                      const float* __restrict__ Rw,
+                                                      float* __restrict__ H, int B, int n, int d) {
+    vs_gather_mean_body<IdT, VEC>(X, Rw, H, B, n, d, blockIdx.x, gridDim.x);
+}
+
+// ---- the PREVIOUS step's tail inside this batch's gather launch -------------------------------------
+// A hinted step (sert_hint_next_batch) does not launch its vs_tail (kernels_opt.h): the launch -- 17 MB of partial slabs,
+// 16.5 k Adam elements and the loss at C2 -- held the main queue for 12-15 us of launch, drain and collector latency, and
+// nothing behind it on that queue needs its result before the projection of the run-ahead step: this gather reads R_w and
+// the ids only.  So its `tail_blocks` workgroups LEAD this launch (256 threads each, every thread playing four of
+// vs_tail's: vs_tail_body, the same bits) and the gather's follow, block index rebased; the kernel boundary behind the
+// launch orders W, b and the loss in front of the projection as the boundary behind vs_tail did.  The collector is the
+// last TAIL workgroup: every workgroup it waits for has a lower index, is dispatched before it and never waits, and no
+// gather workgroup waits on anything.
+template <typename IdT>
+__global__ __launch_bounds__(256) void vs_gather_mean_tail(const IdT* __restrict__ X, const float* __restrict__ Rw,
+                                                           float* __restrict__ H, int B, int n, int d, const TailArgs t,
+                                                           unsigned tail_blocks) {
+    __shared__ float red[16][64];
+    __shared__ double dred[2][16];
+    if (blockIdx.x < tail_blocks) {      // (workgroup-uniform)
+        vs_tail_body<false, 256>(t, blockIdx.x, tail_blocks, red, dred);
+        return;
+    }
+    vs_gather_mean_body<IdT, 4>(X, Rw, H, B, n, d, blockIdx.x - tail_blocks, gridDim.x - tail_blocks);
 }
 
 // ---- K5: negative sampler (Philox4x32-10) ----------------------------------

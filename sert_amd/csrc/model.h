@@ -5,6 +5,7 @@
 #include "common.h"
 #include "word_index.h"
 #include "kernels_xchg.h"
+#include "kernels_opt.h"   // (TailArgs: a deferred tail is kept by value)
 #include "../../include/sert_hip.h"
 #include "../../include/sert_hip_debug.h"   // (test hooks + micro-benchmarks: declared apart from the boundary)
 
@@ -233,6 +234,15 @@ struct sert_model {
     unsigned tail_launch_seq = 0;
     int tail_splits = 0;
     size_t tail_stride = 0;
+    // A hinted step DEFERS that launch: its workgroups lead the gather launch of the run-ahead step (kernels_vs.h:
+    // vs_gather_mean_tail; host/step_vectorspace.inc: vs_project).  tail_defer: sert_train_batch allows it for the step it is
+    // issuing; tail_pending: tail_args / tail_nb wait for that gather -- never beyond the sert_train_batch that set them
+    // (flush_pending_tail launches whatever no gather picked up as the plain vs_tail).
+    bool tail_defer = false;
+    bool tail_pending = false;
+    sert::TailArgs tail_args;
+    int tail_nb = 0;
+    int64_t tail_counts[2] = {0, 0};   // tails launched [0] alone (vs_tail), [1] inside a gather: sert_debug_tail_counts
     float* red_loss = nullptr;    // loss partials [kOptBlocks]
     float* red_sq = nullptr;      // sumsq partials [3 * kOptBlocks]
     float* d_loss = nullptr;      // [3] loss, data term, reg term (device)
