@@ -228,6 +228,15 @@ __device__ __forceinline__ float key_to_float(uint32_t k) {
 #define SERT_CLIP_LO 1e-7f
 #define SERT_CLIP_HI 0.99999988079071044921875f
 
+// clip(t, -(1-eps), 1-eps) (sert/models.py:1065-1068) and clip(s, eps, 1-eps) (:900, :290) as numpy and Theano compute them: a
+// NaN stays a NaN (fminf / fmaxf return the OTHER operand for one -- a NaN probability became 1e-7 and its loss finite).
+__device__ __forceinline__ float clip_unit(float t) {
+    return t > SERT_CLIP_HI ? SERT_CLIP_HI : (t < -SERT_CLIP_HI ? -SERT_CLIP_HI : t);
+}
+__device__ __forceinline__ float clip_prob(float s) {
+    return s > SERT_CLIP_HI ? SERT_CLIP_HI : (s < SERT_CLIP_LO ? SERT_CLIP_LO : s);
+}
+
 // T.nnet.sigmoid, float32 C implementation of Theano 0.8.2 [upstream]:
 // x < -88 -> 0 ; x > 15 -> 1 ; else 1/(1+exp(-x))
 __device__ __forceinline__ float theano_sigmoid(float x) {

@@ -64,7 +64,9 @@ __device__ __forceinline__ float fast_tanh(float x) {
     // these short-K GEMMs (gemm_strip.h), 64 tanh per lane and tile: 34.5 -> 32.0 us at C2
     const float e = __builtin_amdgcn_exp2f(2.8853900817779268f * fminf(ax, 10.0f));
     const float big = copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f), x);
-    return ax < 0.25f ? poly : big;
+    // (a NaN takes the polynomial, which keeps it: fminf above drops it and `big` would be +-1 -- a NaN pre-activation
+    //  silently became a saturated unit; every other input selects as before)
+    return ax >= 0.25f ? big : poly;
 }
 
 struct GemmArgs {

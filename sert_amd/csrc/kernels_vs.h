@@ -155,6 +155,20 @@ __global__ void convert_i64_to_i32(const int64_t* __restrict__ in, int32_t* __re
         out[i] = (int32_t)in[i];
 }
 
+// A NaN projection must reach the loss (numpy and Theano clip a NaN to a NaN; the batch loop stops on a non-finite loss,
+// models.py:372-379), but p = fminf(fmaxf(t, -hi), hi) turns it into the unit -hi and the row's loss stays finite.  Replacing
+// that clip with NaN-keeping selects is value-identical for every finite t yet changes how the compiler contracts the dot
+// products behind it (measured: parameters one ulp apart after 110 steps).  So the clip stays as it is and the NaN travels
+// beside it: +-0 when every unit of the row (sixteen lanes, NCH float4 each; |t| <= 1) is finite -- adding it changes no
+// bit of a non-negative loss -- and NaN otherwise.
+template <int NCH>
+__device__ __forceinline__ float row_nan(const float4 (&t)[NCH]) {
+    float tsum = 0.f;
+#pragma unroll
+    for (int q = 0; q < NCH; ++q) tsum += (t[q].x + t[q].y) + (t[q].z + t[q].w);
+    return row16_sum(tsum) * 0.0f;
+}
+
 // ---- K6: fused NCE score + loss + gradient ----------------------------------
 // 16 lanes per batch row i (16 rows per 256-thread workgroup); lane l owns the
 // float4 column chunks l, l+16, ... of the d_e-wide vectors, so one candidate's
@@ -228,11 +242,11 @@ __global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
         const float u = row16_sum(part);
 #if defined(SERT_VARIANTS) && defined(KO_MATH)   // timing knock-out (wrong results), variants build only
         const float sig = u * 0.01f + 0.5f;
-        const float s = fminf(fmaxf(sig, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float s = clip_prob(sig);
         loss -= s;
 #else
         const float sig = theano_sigmoid(u);
-        const float s = fminf(fmaxf(sig, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float s = clip_prob(sig);
         loss -= (j == 0) ? logf(s) : logf(1.0f - s);
 #endif
         if (TRAIN) {
@@ -268,6 +282,7 @@ __global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
             *reinterpret_cast<float4*>(DA + (size_t)i * de + 4 * c) = o;
         }
     }
+    loss += row_nan(t);
     if (l == 0 && valid) rowloss[i] = wi * loss;
     if (wg_loss) {
         if (l == 0) wg_red[threadIdx.x >> 4] = valid ? wi * loss : 0.f;
@@ -346,9 +361,9 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
     const float g = wi * inv_batch;
     const bool act = l <= z;
     const float sig = theano_sigmoid(my_u);
-    const float s = fminf(fmaxf(sig, SERT_CLIP_LO), SERT_CLIP_HI);
+    const float s = clip_prob(sig);
     const float term = (l == 0) ? logf(s) : logf(1.0f - s);
-    const float loss = -row16_sum(act ? term : 0.f);
+    const float loss = -row16_sum(act ? term : 0.f) + row_nan(t);
     if (TRAIN) {
         const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
         float du = 0.f;
@@ -436,11 +451,11 @@ __global__ __launch_bounds__(256) void vs_nce_scalar(const float* __restrict__ T
         const float u = wave_sum(part);
 #if defined(SERT_VARIANTS) && defined(KO_MATH)   // timing knock-out (wrong results), variants build only
         const float sig = u * 0.01f + 0.5f;
-        const float s = fminf(fmaxf(sig, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float s = clip_prob(sig);
         loss -= s;
 #else
         const float sig = theano_sigmoid(u);
-        const float s = fminf(fmaxf(sig, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float s = clip_prob(sig);
         loss -= (j == 0) ? logf(s) : logf(1.0f - s);
 #endif
         if (TRAIN) {
@@ -466,6 +481,11 @@ __global__ __launch_bounds__(256) void vs_nce_scalar(const float* __restrict__ T
             if (c < de) DA[(size_t)i * de + c] = inside ? dp[q] * (1.0f - t[q] * t[q]) : 0.f;
         }
     }
+    // (a NaN unit of the row: see row_nan)
+    float tsum = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) tsum += t[q];
+    loss += wave_sum(tsum) * 0.0f;
     if (lane == 0) rowloss[i] = wi * loss;
 }
 
@@ -511,7 +531,7 @@ __global__ __launch_bounds__(256) void fs_softmax_ce(float* __restrict__ Z,
 #pragma unroll
         for (int u = 0; u < EPL; ++u) pyl = (lane + 64 * u == yi) ? x[u] : pyl;
         const float py = wave_sum(pyl) / sm;
-        const float pyc = fminf(fmaxf(py, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float pyc = clip_prob(py);
         if (lane == 0) rowloss[i] = -wi * logf(pyc);
         if (TRAIN) {
             const bool inside = (py >= SERT_CLIP_LO) && (py <= SERT_CLIP_HI);
@@ -531,7 +551,7 @@ __global__ __launch_bounds__(256) void fs_softmax_ce(float* __restrict__ Z,
     for (int e = lane; e < V; e += 64) sm += __expf(z[e] - mx);
     sm = wave_sum(sm);
     const float py = __expf(z[yi] - mx) / sm;
-    const float pyc = fminf(fmaxf(py, SERT_CLIP_LO), SERT_CLIP_HI);
+    const float pyc = clip_prob(py);
     if (lane == 0) rowloss[i] = -wi * logf(pyc);
     if (TRAIN) {
         const bool inside = (py >= SERT_CLIP_LO) && (py <= SERT_CLIP_HI);
@@ -558,7 +578,7 @@ __global__ void vs_tanh_backward(float* __restrict__ DP, const float* __restrict
 __global__ void vs_clip(const float* __restrict__ T, float* __restrict__ P, size_t count) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count;
          i += (size_t)gridDim.x * blockDim.x)
-        P[i] = fminf(fmaxf(T[i], -SERT_CLIP_HI), SERT_CLIP_HI);
+        P[i] = clip_unit(T[i]);
 }
 
 // out = tanh(avg.W + b) is done by the GEMM with the EPI_BIAS_TANH epilogue.

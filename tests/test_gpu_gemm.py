@@ -179,3 +179,122 @@ def test_k_range_forms_on_seeded_random_shapes(hip_lib):
         got = C.debug_gemm_longk(A, B, splits, tb=tb)
         ref = A.astype(np.float64) @ (B.astype(np.float64).T if tb else B.astype(np.float64))
         assert np.abs(got - ref).max() < 2e-6 * max(1.0, np.sqrt(K / splits / 128.0), np.sqrt(K / 128.0) / 8), (case, M, N, K, splits, tb)
+
+
+# --------------------------------------------------------------------------- #
+# the tanh epilogue (fast_tanh, gemm.h) over its whole range, and NaN
+# --------------------------------------------------------------------------- #
+# one shape per kernel family that has the epilogue, (M, N) of the list above with K = 8: gemm_x3.h (M >= 16384), the
+# 128x128-tile kernel (1024 big tiles, K < 256) and the 64x64-tile one (fewer than 512 big tiles)
+TANH_SHAPES = [(16384 + 7, 128), (4096, 4096), (1000, 300)]
+
+
+def _ulp(x, k):
+    """x moved by k units in the last place, away from zero for k > 0."""
+    x = np.float32(x)
+    for _ in range(abs(k)):
+        x = np.nextafter(x, np.float32(np.inf if (k > 0) == (x > 0) else 0) if x != 0 else np.float32(k), dtype=np.float32)
+    return x
+
+
+def _tanh_values():
+    """Pre-activations through both branches of fast_tanh and across its thresholds: 0, the switch at |x| = 0.25 (and one
+    ulp to either side), a grid over [-30, 30], the band where float32 tanh saturates (7.9 ... 9.1), the clamp at 10 (and
+    one ulp to either side), 88, 1e30, infinity."""
+    v = [0.0, -0.0]
+    for s in (1.0, -1.0):
+        v += [s * 0.25, s * _ulp(0.25, -1), s * _ulp(0.25, 1), s * 7.9, s * 9.1, s * np.float32(12 * np.log(2.0)), s * 10.0,
+              s * _ulp(10.0, -1), s * _ulp(10.0, 1), s * 88.0, s * 1e30, s * np.inf, s * 1e-30, s * 1e-3]
+    v += list(np.linspace(-30, 30, 81))
+    return np.array(v, dtype=np.float32)
+
+
+@pytest.mark.parametrize('M,N', TANH_SHAPES)
+def test_tanh_epilogue_over_its_whole_range(hip_lib, M, N):
+    """K = 8 and exact products: A.B is a row-dependent multiple of 0.25 in {-0.5, ..., 0.5} whatever the summation order
+    (terms +-1, +-2, +-0.5 that cancel in pairs, and the shift), the bias places the values of _tanh_values -- rows with
+    shift 0 see them exactly, the others one rounded sum away.  Element by element against float64 tanh under the bound
+    of test_gemm_dispatch_against_float64 for epi = 2: where |a| is large tanh' ~ 0, so a wrong branch (the polynomial
+    past 0.25, a missing clamp, a NaN from Inf / Inf) is far outside it."""
+    K = 8
+    vals = _tanh_values()
+    bias = vals[np.arange(N) % len(vals)]
+    shift = ((np.arange(M) % 5) - 2).astype(np.float32) * np.float32(0.25)
+    A = np.tile(np.array([1, -1, 2, -2, 0.5, -0.5, 0, 0], np.float32), (M, 1))
+    A[:, 6] = shift
+    B = np.ones((K, N), np.float32)
+    got = C.debug_gemm(A, B, epi=2, bias=bias)
+    with np.errstate(invalid='ignore'):
+        pre = shift[:, None] + bias[None, :]                 # float32: the one rounding the kernel's acc + bias makes
+    assert np.all(np.isfinite(pre) | np.isinf(pre))
+    ref = np.tanh(pre.astype(np.float64))
+    assert np.all(np.isfinite(got))
+    err = np.abs(got - ref)
+    worst = np.unravel_index(err.argmax(), err.shape)
+    assert err.max() < 3e-6, (worst, pre[worst], got[worst], ref[worst])
+    assert np.all(np.abs(got) <= 1) and np.array_equal(np.signbit(got), np.signbit(pre))    # tanh(-0.0) = -0.0 included
+    # shift 0: the planted values themselves; saturation is exact
+    row = got[2]
+    assert np.all(row[np.abs(bias) >= 10] == np.sign(bias[np.abs(bias) >= 10])) and np.all(row[bias == 0] == 0)
+
+
+@pytest.mark.parametrize('M,N', TANH_SHAPES)
+def test_tanh_epilogue_keeps_a_nan_in_its_row(hip_lib, M, N):
+    """A NaN in A[r, :] under the tanh epilogue: row r non-finite and only row r, as np.tanh gives it (fminf(NaN, 10) = 10
+    and NaN < 0.25 is false: fast_tanh once returned +-1 for a NaN)."""
+    K = 8
+    rng = np.random.RandomState(M + N)
+    A = rng.uniform(-1, 1, (M, K)).astype(np.float32)
+    B = rng.uniform(-1, 1, (K, N)).astype(np.float32)
+    bias = rng.uniform(-12, 12, N).astype(np.float32)
+    rows = [3, M // 2 + 1, M - 1]
+    for k, r in enumerate(rows):
+        A[r, (3 * k) % K] = np.nan
+    got = C.debug_gemm(A, B, epi=2, bias=bias)
+    bad = ~np.isfinite(got)
+    assert bad[rows].all(), [int(bad[r].sum()) for r in rows]
+    bad[rows] = False
+    assert not bad.any()
+
+
+def test_predict_project_and_training_step_keep_a_nan(hip_lib):
+    """predict_project of a block with one NaN row returns NaN in that row and the other rows unchanged (np.tanh does);
+    and a training step whose batch touches a word row holding one NaN returns a non-finite loss, as the oracle's is --
+    lambda = 0, so the L2 term does not carry the NaN into the loss: it has to travel through tanh, the clip of t, the
+    sigmoid and the clip of s (fast_tanh and each fminf / fmaxf on the way once dropped it, and the batch loop's non-finite-loss guard,
+    sert/models.py:372-379, never fired while the parameters filled with NaN).  Both NCE forms and the softmax variant."""
+    from oracle import sert_oracle as O
+    from tests import util as U
+    for z, de in ((4, 48), (20, 32), (7, 70), (0, 48)):      # vs_nce_regs, vs_nce, vs_nce_scalar, fs_softmax_ce
+        B, n, Vw, Ve, dw = 64, 5, 500, 37, 32
+        p = U.make_vs_problem(3, B, n, z, Vw, Ve, dw, de, zipf=True)
+        p['W'] *= np.float32(20.0)                   # saturated units beside the NaN ones
+        if z:
+            eng = U.vs_engine(p, B, n, z, 0.0)
+        else:
+            eng = C.Engine(kind=C.KIND_VECTORSPACE_SOFTMAX, batch_size=B, global_batch_size=B, window_size=n, vocab_size=Vw,
+                           num_entities=Ve, word_dim=dw, entity_dim=de, num_negatives=0, id_bytes=p['X'].dtype.itemsize,
+                           device=0, keep_grads=1, deterministic=1, lambda_=0.0, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=1)
+            for which, a in ((C.T_RW, p['Rw']), (C.T_RE, p['Re']), (C.T_W, p['W']), (C.T_B, p['b'])):
+                eng.set_tensor(which, a)
+        avg = p['rng'].uniform(-1, 1, (9, dw)).astype(np.float32)
+        clean = eng.predict_project(avg)
+        avg[4, 7] = np.nan
+        out = eng.predict_project(avg)
+        assert np.isnan(out[4]).all() and np.isnan(np.tanh(avg @ p['W'] + p['b'])[4]).all()
+        keep = np.arange(9) != 4
+        assert np.array_equal(out[keep], clean[keep])
+        # one NaN in the word row of the first token of the batch's last row
+        p['Rw'][int(p['X'][B - 1, 0]), dw - 1] = np.nan
+        eng.set_tensor(C.T_RW, p['Rw'])
+        eng.upload_dataset(C.SPLIT_TRAIN, p['X'], y_int=p['y'], w=p['w'])
+        neg = p['rng'].randint(0, Ve, size=(B, z)).astype(np.int64) if z else None
+        with np.errstate(invalid='ignore'):
+            if z:
+                ref = O.VectorSpaceOracle(B, n, z, p['Rw'], p['Re'], p['W'], p['b'], 0.0).train_step(p['X'], p['y'], p['w'], neg)
+            else:
+                ref = O.VectorSpaceSoftmaxOracle(B, n, p['Rw'], p['Re'], p['W'], p['b'], 0.0).train_step(p['X'], p['y'], p['w'])
+        assert not np.isfinite(ref)
+        loss = eng.train_batch(0, neg) if z else eng.train_batch(0)
+        assert not np.isfinite(loss), (z, de, loss)
+        eng.close()
