@@ -3,7 +3,8 @@
  *
  * NOT part of the drop-in boundary (include/sert_hip.h is): nothing here replaces a reference function and no product code
  * path (sert_amd/models.py, inference.py, scoring.py, training.py, bin/) calls these.  They exist so that
- *   - every GEMM kernel of the library can be pinned against float64 on host arrays (tests/test_gpu_gemm.py),
+ *   - every GEMM kernel of the library can be pinned against float64, and against products known to the bit, on host
+ *     arrays (tests/test_gpu_gemm.py), and the kernel a shape is routed to can be asked for (sert_debug_gemm_route),
  *   - the host-side index / exchange-list builders can be checked without a GPU (tests/test_word_index_cpu.py,
  *     tests/test_row_exchange_cpu.py),
  *   - bench.py can measure the denominators of its roofline fractions on the box it runs on (sert_bench_memory).
@@ -91,6 +92,27 @@ int sert_debug_gemm_splitk(int device, int M, int N, int K, int splits, const fl
  * through the split launch + order-fixed combine of the loglinear dG = dZ.W^T over a large entity vocabulary
  * (sert/models.py:846-849, autodiff). */
 int sert_debug_gemm_longk(int device, int tb, int M, int N, int K, int splits, const float* A, const float* B, float* C);
+
+/* Host only, no device is touched (test hook): the kernel the three hooks above would launch for a shape -- `form` one of
+ * SERT_GEMM_FORM_*, ta / tb as sert_debug_gemm takes them (SPLITK is A^T.B, LONGK A.op(B)), `splits` as the split forms take
+ * it (ignored for PLAIN), `align` the byte alignment of both operands (16 or more: device allocations; 4: an operand that
+ * starts anywhere).  Asked of the predicates the launchers themselves ask (gemm.h, gemm_x3.h), under the process's
+ * SERT_GEMM_FP32.  Returns a SERT_GEMM_ROUTE_* code; < 0 on a bad argument.  tests/test_x3_split_cpu.py asserts through it
+ * that the shapes of the exact-product tests reach every kernel form of the product build. */
+enum { SERT_GEMM_FORM_PLAIN = 0, SERT_GEMM_FORM_SPLITK = 1, SERT_GEMM_FORM_LONGK = 2 };
+enum {
+    SERT_GEMM_ROUTE_F32_TILE64 = 1,      /* gemm.h: 64 x 64 tiles */
+    SERT_GEMM_ROUTE_F32_TILE128 = 2,     /*         128 x 128 tiles, persistent */
+    SERT_GEMM_ROUTE_F32_TILE128X160 = 3, /*         128 x 160 tiles */
+    SERT_GEMM_ROUTE_X3_128_VEC = 4,      /* gemm_x3.h: 128 x 128 tiles, 16-byte loaders */
+    SERT_GEMM_ROUTE_X3_128_SCALAR = 5,   /*            128 x 128 tiles, dword loaders (any alignment) */
+    SERT_GEMM_ROUTE_X3_256 = 6,          /*            256 x 256 tiles */
+    SERT_GEMM_ROUTE_X3_320 = 7,          /*            256 x 320 tiles */
+    SERT_GEMM_ROUTE_X3_TA_SINGLE = 8,    /*            A^T.B, one 128 x 128 tile per k range */
+    SERT_GEMM_ROUTE_X3_TA_320X160 = 9,   /*            A^T.B, 320 x 160 tiles of ten waves */
+    SERT_GEMM_ROUTE_X3_TA_TILES = 10     /*            A^T.B, 128 x 128 tiles over M and N */
+};
+int sert_debug_gemm_route(int form, int ta, int tb, int M, int N, int K, int splits, int align);
 
 /* Memory-system micro-benchmarks: the denominators a step's memory-bound kernels are priced
  * against (no reference counterpart; measurement only).  Average launch time over `iters`

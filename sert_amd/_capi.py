@@ -39,7 +39,7 @@ EXPORTS = [
     'sert_host_alloc', 'sert_host_free',
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
-    'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
+    'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
     'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -736,6 +736,23 @@ def debug_gemm_longk(A, B, splits, tb=0, device=0):
     lib.sert_debug_gemm_longk.argtypes = [ctypes.c_int] * 6 + [ctypes.c_void_p] * 3
     check(lib.sert_debug_gemm_longk(device, int(tb), M, N, K, int(splits), _addr(A), _addr(B), _addr(out)))
     return out
+
+
+GEMM_FORM_PLAIN, GEMM_FORM_SPLITK, GEMM_FORM_LONGK = 0, 1, 2
+# sert_debug_gemm_route's codes (include/sert_hip_debug.h: SERT_GEMM_ROUTE_*), in order from 1
+GEMM_ROUTES = ('f32_tile64', 'f32_tile128', 'f32_tile128x160', 'x3_128_vec', 'x3_128_scalar', 'x3_256', 'x3_320',
+               'x3_ta_single', 'x3_ta_320x160', 'x3_ta_tiles')
+
+
+def debug_gemm_route(form, M, N, K, ta=0, tb=0, splits=1, align=16):
+    """The kernel debug_gemm (GEMM_FORM_PLAIN), debug_gemm_splitk or debug_gemm_longk would launch for a shape, by name
+    (GEMM_ROUTES) -- sert_debug_gemm_route: host only, the launchers' own predicates."""
+    lib = load()
+    lib.sert_debug_gemm_route.argtypes = [ctypes.c_int] * 8
+    code = lib.sert_debug_gemm_route(int(form), int(ta), int(tb), int(M), int(N), int(K), int(splits), int(align))
+    if code < 1 or code > len(GEMM_ROUTES):
+        raise SertError('sert_debug_gemm_route: %s' % (lib.sert_last_error() or b'').decode())
+    return GEMM_ROUTES[code - 1]
 
 
 def bench_memory(kind, nbytes, table_bytes=0, row_bytes=512, window=10, gap_bytes=0, blocks=0, iters=20, device=0):

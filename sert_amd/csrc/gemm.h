@@ -805,6 +805,63 @@ inline bool gemm_x3_enabled() {
     return gemm_fp32_latch() == 0;
 }
 
+// ---- the routing of a contraction: every choice between kernels that launch_gemm and the launchers of gemm_x3.h make is one
+// of the predicates below, and sert_debug_gemm_route (include/sert_hip_debug.h) reports what they answer for a shape without
+// touching a device -- tests/test_x3_split_cpu.py asserts through it that the shapes of the exact-product tests
+// (tests/test_gpu_gemm.py) reach every kernel form.  (The opt-in kernels of a -DSERT_VARIANTS build are not routes.)
+enum GemmRoute {
+    ROUTE_F32_SMALL = 1, ROUTE_F32_TILE128 = 2, ROUTE_F32_N160 = 3,                             // gemm.h
+    ROUTE_X3_128_VEC = 4, ROUTE_X3_128_SCALAR = 5, ROUTE_X3_256 = 6, ROUTE_X3_320 = 7,           // gemm_x3.h, A.op(B)
+    ROUTE_X3_TA_SINGLE = 8, ROUTE_X3_TA_320X160 = 9, ROUTE_X3_TA_TILES = 10,                    // gemm_x3.h, A^T.B
+};
+inline int x3_route(bool tb, const float* A, const float* B, int M, int N, int K, int lda, int ldb, int splits);
+inline int x3_ta_route(int M, int N);
+
+// Does the launch go to gemm_x3.h?  (splits, kper as launch_gemm normalised them: one k range = (1, K))
+inline bool gemm_takes_x3(bool ta, bool tb, int epi, bool csb, bool rowmap, const float* A, const float* B, int M, int N, int K,
+                          int lda, int ldb, int splits, int kper) {
+    if (ta) {
+        return !tb && epi == EPI_STORE && !rowmap && (splits == 1 || kper % 16 == 0) && gemm_x3_enabled() &&
+               x3_shape_ok(true, false, A, B, M, N, K, lda, ldb, splits);
+    }
+    return !csb && (epi == EPI_STORE || epi == EPI_BIAS || epi == EPI_BIAS_TANH) &&
+           (splits == 1 || (epi == EPI_STORE && kper % 16 == 0)) && !rowmap && gemm_x3_enabled() &&
+           x3_shape_ok(false, tb, A, B, M, N, K, lda, ldb, splits);
+}
+// the fp32 tile kernels' vector path: every 16-byte piece aligned and wholly inside or outside
+// (an operand stored k-major -- A of A^T.B, B of A.B -- is contiguous along the tile's M / N axis and its k
+//  remainder is a per-row mask: only an operand that is contiguous along k needs K and kper in whole pieces.
+//  The loglinear dW = G^T.dZ has K = the batch's distinct words, any number: 160 -> 117 us at C2 dims)
+inline bool gemm_f32_vec(bool ta, bool tb, const float* A, const float* B, int M, int N, int K, int lda, int ldb, int kper) {
+    const bool k_pieces = (K % 4 == 0) && (kper % 4 == 0);
+    return (lda % 4 == 0) && (ldb % 4 == 0) && lda < (1 << 22) && ldb < (1 << 22) && (((uintptr_t)A) % 16 == 0) &&
+           (((uintptr_t)B) % 16 == 0) && (k_pieces || (ta && !tb)) &&
+           (ta ? (M % 4 == 0) : true) && (tb ? true : (N % 4 == 0));
+}
+// ... and which of this file's kernels takes a launch that does not
+inline int gemm_f32_route(bool ta, bool tb, int epi, bool csb, const float* A, const float* B, int M, int N, int K, int lda, int ldb,
+                          int splits, int kper) {
+    // small problem (fewer than two 128x128 tiles per CU): 64x64 tiles, one workgroup each
+    static const bool no_small = variant_knob("SERT_GEMM_NO_SMALL") != nullptr;
+    // below TWO 128x128 tiles per CU the 64x64 tiles win or draw (round 3 sweep at d = 128: 384 tiles
+    // 30.5 -> 26.3 us, the loglinear dG with 347 tiles and K = 1000 162 -> 126 us; 256 and 512 tiles: equal):
+    // a CU that gets a second big tile sets the time of the launch, four times as many small ones spread evenly
+    static const long long small_below = variant_knob("SERT_GEMM_SMALL_BELOW") ? atoll(variant_knob("SERT_GEMM_SMALL_BELOW")) : 512;   // tuning knob
+    // ... and AT two big tiles per CU for a short K (the C2 projections: 512 tiles, K = 128), since the 64x64
+    // kernel loads its tiles through buffer loads: 31.3 -> 30.1 and 28.8 -> 27.7 us, C2 step 295.5 -> 292.2 us;
+    // at K = 1000 the big tiles keep the boundary (186 against 197 us)
+    const long long big_tiles = (long long)cdiv(M, GM) * cdiv(N, GN);
+    if (!ta && !csb && epi != EPI_FILTER && epi != EPI_ACCUM && splits == 1 && !no_small &&
+        (big_tiles < small_below || (big_tiles == small_below && K <= 512)) && (long long)M * N >= 4 * SM * SM)
+        return ROUTE_F32_SMALL;
+    // N just above a multiple of 128 (d = 300): 160-column tiles pad less (gemm_f32_mfma_n160)
+    static const bool no_n160 = variant_knob("SERT_GEMM_NO_N160") != nullptr;   // cross-check knob
+    if (!no_n160 && gemm_f32_vec(ta, tb, A, B, M, N, K, lda, ldb, kper) && epi != EPI_FILTER &&
+        (long long)cdiv(N, GN2) * GN2 * 11 <= (long long)cdiv(N, GN) * GN * 10)   // >= 10 % less padding
+        return ROUTE_F32_N160;
+    return ROUTE_F32_TILE128;
+}
+
 // rowmap / mapped_C / mapped (optional): when the launch goes to the 64x64-tile kernel, row r of the product is
 // stored as row rowmap[r] of mapped_C (leading dimension ldc) instead of row r of C, and *mapped is set.
 template <bool TA, bool TB, int EPI, bool CSB = false>
@@ -816,14 +873,13 @@ inline void launch_gemm(hipStream_t s, const float* A, const float* B, float* C,
     if (splits <= 1) { splits = 1; kper = K; }
     if (mapped) *mapped = false;
     if constexpr (TA && !TB && EPI == EPI_STORE) {
-        if (!rowmap && (splits == 1 || kper % 16 == 0) && gemm_x3_enabled() && x3_shape_ok(true, false, A, B, M, N, K, lda, ldb, splits)) {
+        if (gemm_takes_x3(TA, TB, EPI, CSB, rowmap != nullptr, A, B, M, N, K, lda, ldb, splits, kper)) {
             launch_gemm_x3_ta<CSB>(s, A, B, C, M, N, K, lda, ldb, ldc, splits, kper, splits > 1 ? c_split_stride : 0);
             return;
         }
     }
     if constexpr (!TA && !CSB && (EPI == EPI_STORE || EPI == EPI_BIAS || EPI == EPI_BIAS_TANH)) {
-        if ((splits == 1 || (EPI == EPI_STORE && kper % 16 == 0)) && !rowmap && gemm_x3_enabled() &&
-            x3_shape_ok(false, TB, A, B, M, N, K, lda, ldb, splits)) {
+        if (gemm_takes_x3(TA, TB, EPI, CSB, rowmap != nullptr, A, B, M, N, K, lda, ldb, splits, kper)) {
             launch_gemm_x3<TB, EPI>(s, A, B, C, bias, M, N, K, lda, ldb, ldc, splits, kper, c_split_stride);
             return;
         }
@@ -843,18 +899,8 @@ inline void launch_gemm(hipStream_t s, const float* A, const float* B, float* C,
 #endif
     GemmArgs g;
     g.rowmap = nullptr;
-    // small problem (fewer than two 128x128 tiles per CU): 64x64 tiles, one workgroup each
-    static const bool no_small = variant_knob("SERT_GEMM_NO_SMALL") != nullptr;
-    // below TWO 128x128 tiles per CU the 64x64 tiles win or draw (round 3 sweep at d = 128: 384 tiles
-    // 30.5 -> 26.3 us, the loglinear dG with 347 tiles and K = 1000 162 -> 126 us; 256 and 512 tiles: equal):
-    // a CU that gets a second big tile sets the time of the launch, four times as many small ones spread evenly
-    static const long long small_below = variant_knob("SERT_GEMM_SMALL_BELOW") ? atoll(variant_knob("SERT_GEMM_SMALL_BELOW")) : 512;   // tuning knob
-    // ... and AT two big tiles per CU for a short K (the C2 projections: 512 tiles, K = 128), since the 64x64
-    // kernel loads its tiles through buffer loads: 31.3 -> 30.1 and 28.8 -> 27.7 us, C2 step 295.5 -> 292.2 us;
-    // at K = 1000 the big tiles keep the boundary (186 against 197 us)
-    const long long big_tiles = (long long)cdiv(M, GM) * cdiv(N, GN);
-    if (!TA && !CSB && EPI != EPI_FILTER && EPI != EPI_ACCUM && splits == 1 && !no_small &&
-        (big_tiles < small_below || (big_tiles == small_below && K <= 512)) && (long long)M * N >= 4 * SM * SM) {
+    const int route = gemm_f32_route(TA, TB, EPI, CSB, A, B, M, N, K, lda, ldb, splits, kper);
+    if (route == ROUTE_F32_SMALL) {
         g.cand = nullptr; g.cnt = nullptr; g.cap = 0;
         g.A = A; g.B = B; g.C = C; g.bias = bias;
         g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -875,17 +921,8 @@ inline void launch_gemm(hipStream_t s, const float* A, const float* B, float* C,
     g.tiles_m = cdiv(M, GM); g.tiles_n = cdiv(N, GN);
     g.c_split_stride = c_split_stride;
     g.vecA = g.vecB = 0;
-    // vector path: every 16-byte piece aligned and wholly inside or outside
-    // (an operand stored k-major -- A of A^T.B, B of A.B -- is contiguous along the tile's M / N axis and its k
-    //  remainder is a per-row mask: only an operand that is contiguous along k needs K and kper in whole pieces.
-    //  The loglinear dW = G^T.dZ has K = the batch's distinct words, any number: 160 -> 117 us at C2 dims)
-    const bool k_pieces = (K % 4 == 0) && (kper % 4 == 0);
-    const bool vec = (lda % 4 == 0) && (ldb % 4 == 0) && lda < (1 << 22) && ldb < (1 << 22) && (((uintptr_t)A) % 16 == 0) &&
-                     (((uintptr_t)B) % 16 == 0) && (k_pieces || (TA && !TB)) &&
-                     (TA ? (M % 4 == 0) : true) && (TB ? true : (N % 4 == 0));
-    // N just above a multiple of 128 (d = 300): 160-column tiles pad less (gemm_f32_mfma_n160)
-    static const bool no_n160 = variant_knob("SERT_GEMM_NO_N160") != nullptr;   // cross-check knob
-    if (!no_n160 && vec && EPI != EPI_FILTER && (long long)cdiv(N, GN2) * GN2 * 11 <= (long long)cdiv(N, GN) * GN * 10) {   // >= 10 % less padding
+    const bool vec = gemm_f32_vec(TA, TB, A, B, M, N, K, lda, ldb, kper);
+    if (route == ROUTE_F32_N160) {
         g.tiles_n = cdiv(N, GN2);
         const long long total160 = (long long)g.tiles_m * g.tiles_n * splits;
         const int grid160 = (int)std::min<long long>(total160, 256 * 3);

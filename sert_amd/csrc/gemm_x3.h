@@ -2,8 +2,11 @@
 //   x = x0 + x1 + x2   (x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1); 3 x 8 significant bits = the 24 of fp32),
 // and a product a.b is the six bf16 products a_p b_q with p + q <= 2, accumulated in fp32 by
 // v_mfma_f32_32x32x16_bf16.  The three dropped products are below 2^-24 |a||b|: against float64 the six-term sum
-// is 100 x closer than an fp32 fmaf chain (tests/test_gpu_gemm.py), so what is left is the fp32 accumulation
-// the fp32 MFMA path (gemm.h) has as well.  Six bf16 MFMAs of depth 16 occupy a SIMD for 6 x 32 cycles where
+// is 100 x closer than an fp32 fmaf chain (the arithmetic, in NumPy: tests/test_x3_split_cpu.py), so what is left is the
+// fp32 accumulation the fp32 MFMA path (gemm.h) has as well.  That THIS kernel forms every one of the six products, each
+// plane read from its own k, in every tile shape and loader variant, is pinned on the device by operands whose product is
+// known to the bit (tests/x3_families.py, the exact-product tests of tests/test_gpu_gemm.py); the float64 tests there bound
+// the accumulation.  Six bf16 MFMAs of depth 16 occupy a SIMD for 6 x 32 cycles where
 // the fp32 MFMA needs 8 x 64 for the same depth: the dense contractions of the training step
 // (sert/models.py:1057-1061 and their autodiff) are matrix-pipe-bound at d = 300 (gemm.h: 86 TF of 157)
 // and load/latency-bound at d = 128, and this kernel takes 2.7 x less of the pipe.
@@ -467,6 +470,20 @@ inline bool x3_pf2() {
 }
 #endif
 
+// The kernel form a product that x3_shape_ok admitted takes (GemmRoute, gemm.h): 128 x 128 tiles with 16-byte or -- any
+// alignment -- dword loaders, or, for a big aligned product wider than 128 columns, 256-row tiles of 256 or 320 columns
+inline int x3_route(bool tb, const float* A, const float* B, int M, int N, int K, int lda, int ldb, int splits) {
+    const bool vec = lda % 4 == 0 && K % 4 == 0 && ((uintptr_t)A) % 16 == 0 && (!tb || (ldb % 4 == 0 && ((uintptr_t)B) % 16 == 0));
+    const bool big = vec && x3_big_size(M, N, K, std::max(1, splits));
+    if (N <= 128 || !big) return vec ? ROUTE_X3_128_VEC : ROUTE_X3_128_SCALAR;
+    return x3_tile_cols(N) == 256 ? ROUTE_X3_256 : ROUTE_X3_320;
+}
+// ... and of A^T.B: one 128 x 128 tile, 320 x 160 tiles of ten waves (128 < M <= 320), or 128 x 128 tiles over M and N
+inline int x3_ta_route(int M, int N) {
+    if (M <= 128 && N <= 128) return ROUTE_X3_TA_SINGLE;
+    return (M <= 320 && M > 128) ? ROUTE_X3_TA_320X160 : ROUTE_X3_TA_TILES;
+}
+
 template <bool TB, int EPI>
 inline void launch_gemm_x3(hipStream_t s, const float* A, const float* B, float* C, const float* bias, int M, int N, int K,
                            int lda, int ldb, int ldc, int splits, int kper, size_t c_split_stride) {
@@ -483,9 +500,9 @@ inline void launch_gemm_x3(hipStream_t s, const float* A, const float* B, float*
         return;
     }
 #endif
-    const bool vec = lda % 4 == 0 && K % 4 == 0 && ((uintptr_t)A) % 16 == 0 && (!TB || (ldb % 4 == 0 && ((uintptr_t)B) % 16 == 0));
-    const bool big = vec && x3_big_size(M, N, K, g.splits);
-    if (N <= 128 || !big) {
+    const int route = x3_route(TB, A, B, M, N, K, lda, ldb, g.splits);
+    if (route == ROUTE_X3_128_VEC || route == ROUTE_X3_128_SCALAR) {
+        const bool vec = route == ROUTE_X3_128_VEC;
         g.tiles_m = cdiv(M, 128); g.tiles_n = cdiv(N, 128);
 #ifdef SERT_VARIANTS
         if (vec && x3_pf2()) SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2, true, 2>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
@@ -493,7 +510,7 @@ inline void launch_gemm_x3(hipStream_t s, const float* A, const float* B, float*
 #endif
         if (vec) SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
         else     SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2, false>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
-    } else if (x3_tile_cols(N) == 256) {
+    } else if (route == ROUTE_X3_256) {
         g.tiles_m = cdiv(M, 256); g.tiles_n = cdiv(N, 256);
         SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 4, 2, 2, 4>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(512), 0, s, g);
     } else {
@@ -510,14 +527,15 @@ inline void launch_gemm_x3_ta(hipStream_t s, const float* A, const float* B, flo
     g.A = A; g.B = B; g.C = C; g.bias = nullptr; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.kper = kper; g.splits = splits; g.c_split_stride = c_split_stride;
     g.tiles_m = 1;
-    if (M <= 128 && N <= 128) {
+    const int route = x3_ta_route(M, N);
+    if (route == ROUTE_X3_TA_SINGLE) {
         g.tiles_n = 1;
 #ifdef SERT_VARIANTS
         if (x3_pf2()) SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2, true, 2>), dim3(splits == 1 ? 1 : 8 * cdiv(splits, 8)), dim3(256), 0, s, g);
         else
 #endif
         SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2>), dim3(splits == 1 ? 1 : 8 * cdiv(splits, 8)), dim3(256), 0, s, g);
-    } else if (M <= 320 && M > 128) {
+    } else if (route == ROUTE_X3_TA_320X160) {
         // 320 x 160 tiles, ten waves of 32 x 160 (80 accumulator registers: three waves fit a SIMD)
         g.tiles_n = cdiv(N, 160);
         SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 10, 1, 1, 5>), dim3(splits == 1 ? g.tiles_n : 8 * g.tiles_n * cdiv(splits, 8)), dim3(640), 0, s, g);

@@ -251,6 +251,42 @@ int sert_bench_gemm(int device, int ta, int tb, int epi, int M, int N, int K, in
     return 0;
 }
 
+// the k ranges of the two split forms below: whole GK steps per range, no empty range at the end
+static inline int debug_k_ranges(int K, int splits, int* kper) {
+    *kper = (int)round_up(cdiv(K, splits), GK);
+    return cdiv(K, *kper);
+}
+
+// Host only: the GemmRoute (gemm.h) the three hooks below end in for a shape -- the predicates launch_gemm, launch_gemm_x3 and
+// launch_gemm_x3_ta ask, on operands of which only the alignment exists.  < 0: bad argument.
+static_assert(ROUTE_F32_SMALL == SERT_GEMM_ROUTE_F32_TILE64 && ROUTE_F32_TILE128 == SERT_GEMM_ROUTE_F32_TILE128 &&
+              ROUTE_F32_N160 == SERT_GEMM_ROUTE_F32_TILE128X160 && ROUTE_X3_128_VEC == SERT_GEMM_ROUTE_X3_128_VEC &&
+              ROUTE_X3_128_SCALAR == SERT_GEMM_ROUTE_X3_128_SCALAR && ROUTE_X3_256 == SERT_GEMM_ROUTE_X3_256 &&
+              ROUTE_X3_320 == SERT_GEMM_ROUTE_X3_320 && ROUTE_X3_TA_SINGLE == SERT_GEMM_ROUTE_X3_TA_SINGLE &&
+              ROUTE_X3_TA_320X160 == SERT_GEMM_ROUTE_X3_TA_320X160 && ROUTE_X3_TA_TILES == SERT_GEMM_ROUTE_X3_TA_TILES,
+              "GemmRoute (gemm.h) is the header's SERT_GEMM_ROUTE_*");
+int sert_debug_gemm_route(int form, int ta, int tb, int M, int N, int K, int splits, int align) {
+    refresh_gemm_choice();
+    if (form < 0 || form > 2 || M <= 0 || N <= 0 || K <= 0 || splits <= 0 || align <= 0) {
+        (void)::sert::fail(__FILE__, __LINE__, "bad argument");
+        return -1;
+    }
+    const float* A = reinterpret_cast<const float*>((uintptr_t)align);   // (never dereferenced)
+    const float* B = A;
+    int kper = K;
+    bool csb = false;
+    if (form == SERT_GEMM_FORM_PLAIN) splits = 1;
+    else {
+        if (form == SERT_GEMM_FORM_SPLITK) { ta = 1; tb = 0; csb = true; } else ta = 0;
+        splits = debug_k_ranges(K, splits, &kper);
+        if (splits <= 1) { splits = 1; kper = K; }      // (launch_gemm: one k range is no split)
+    }
+    const int lda = ta ? M : K, ldb = tb ? K : N;
+    if (gemm_takes_x3(ta != 0, tb != 0, EPI_STORE, csb, false, A, B, M, N, K, lda, ldb, splits, kper))
+        return ta ? x3_ta_route(M, N) : x3_route(tb != 0, A, B, M, N, K, lda, ldb, splits);
+    return gemm_f32_route(ta != 0, tb != 0, EPI_STORE, csb, A, B, M, N, K, lda, ldb, splits, kper);
+}
+
 // C = epi(op(A).op(B)) for host arrays, through launch_gemm -- i.e. through whichever kernel a shape is routed to in a
 // training step (tests/test_gpu_gemm.py pins every kernel of gemm.h / gemm_stream.h against float64 this way).
 int sert_debug_gemm(int device, int ta, int tb, int epi, int M, int N, int K, const float* A, const float* B,
@@ -295,8 +331,8 @@ int sert_debug_gemm_splitk(int device, int M, int N, int K, int splits, const fl
     SERT_HIP(hipSetDevice(device));
     hipStream_t s;
     SERT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    int kper = (int)round_up(cdiv(K, splits), GK);
-    splits = cdiv(K, kper);
+    int kper = 0;
+    splits = debug_k_ranges(K, splits, &kper);
     const size_t na = (size_t)K * M, nb = (size_t)K * N, stride = (size_t)M * N + N;
     float *dA = nullptr, *dB = nullptr, *dP = nullptr, *dO = nullptr;
     auto body = [&]() -> int {
@@ -325,8 +361,8 @@ int sert_debug_gemm_longk(int device, int tb, int M, int N, int K, int splits, c
     SERT_HIP(hipSetDevice(device));
     hipStream_t s;
     SERT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    int kper = (int)round_up(cdiv(K, splits), GK);
-    splits = cdiv(K, kper);
+    int kper = 0;
+    splits = debug_k_ranges(K, splits, &kper);
     const size_t na = (size_t)M * K, nb = (size_t)K * N, mn = (size_t)M * N;
     float *dA = nullptr, *dB = nullptr, *dP = nullptr, *dO = nullptr;
     auto body = [&]() -> int {

@@ -3,10 +3,13 @@ step uses, so a shape lands on the kernel the step would run it on: the bf16-pip
 (gemm_x3.h: 128 row tiles or more -- M >= 16384 for N <= 128, M >= 32768 above --, A not transposed, or A^T.B over K >= 4096; SERT_GEMM_FP32=1 sends those shapes to the fp32 MFMA kernels too), the
 128x128-tile kernel, the 64x64-tile one, the 128x160-tile one (N just above a multiple of 128) and -- against a variants build (SERT_LIB=.../libsert_variants.so) with
 SERT_GEMM_DIRECT_MIN_K=256 / SERT_GEMM_STREAM=1 -- the two kernels of round 4 that feed A straight from global memory into
-v_mfma_f32_16x16x4_f32 (variants/gemm_direct.h, variants/gemm_stream.h; measured equal or slower, not in the product)."""
+v_mfma_f32_16x16x4_f32 (variants/gemm_direct.h, variants/gemm_stream.h; measured equal or slower, not in the product).
+The float64 bounds price the fp32 accumulation; that gemm_x3.h forms each of its six piece products, every plane from its own
+k, is pinned further down by operands whose product is known to the bit (tests/x3_families.py)."""
 import numpy as np
 import pytest
 
+from tests import x3_families as F
 from tests.util import C
 
 pytestmark = pytest.mark.gpu
@@ -179,6 +182,124 @@ def test_k_range_forms_on_seeded_random_shapes(hip_lib):
         got = C.debug_gemm_longk(A, B, splits, tb=tb)
         ref = A.astype(np.float64) @ (B.astype(np.float64).T if tb else B.astype(np.float64))
         assert np.abs(got - ref).max() < 2e-6 * max(1.0, np.sqrt(K / splits / 128.0), np.sqrt(K / 128.0) / 8), (case, M, N, K, splits, tb)
+
+
+# --------------------------------------------------------------------------- #
+# every piece product of gemm_x3.h, to the bit (tests/x3_families.py; that the families reject a kernel with one product
+# missing or one plane misrouted, on every element, is proved on the CPU: tests/test_x3_split_cpu.py)
+# --------------------------------------------------------------------------- #
+# (form, M, N, K, splits, tb): every shape that reaches a kernel form of its own (F.PLAIN_X3 ...: asserted through
+# sert_debug_gemm_route in tests/test_x3_split_cpu.py), both B layouts of sert_debug_gemm, and one shape per fp32 kernel -- the
+# same expectations hold for a true float32 product, which is what all of them get under SERT_GEMM_FP32=1
+EXACT_CASES = ([('plain', M, N, K, 1, tb) for (M, N, K), _ in F.PLAIN_X3 + F.PLAIN_F32 for tb in (0, 1)] +
+               [('splitk', M, N, K, splits, 0) for (M, N, K, splits), _ in F.SPLITK] +
+               [('longk', M, N, K, splits, tb) for (M, N, K, splits, tb), _ in F.LONGK])
+exact_cases = pytest.mark.parametrize('form,M,N,K,splits,tb', EXACT_CASES, ids=['%s-%dx%dx%d-s%d-tb%d' % c for c in EXACT_CASES])
+
+
+def _product(form, A, B, splits, tb, epi=0, bias=None):
+    """op(A) (M, K) . op(B) (K, N) through one of the three hooks, each operand laid out as the form stores it
+    -> (C, column sums of B or None)."""
+    if form == 'plain':
+        return C.debug_gemm(A, F.stored(B, tb), tb=tb, epi=epi, bias=bias), None
+    if form == 'splitk':
+        return C.debug_gemm_splitk(F.stored(A, True), B, splits)
+    return C.debug_gemm_longk(A, F.stored(B, tb), splits, tb=tb), None
+
+
+def _kper(form, K, splits):
+    return None if form == 'plain' else F.k_range(K, splits)
+
+
+def _same_bits(got, expected, what):
+    assert np.all(np.isfinite(got)), what                  # (the output is pre-filled with NaN: every element was written)
+    if not np.array_equal(got, expected):
+        bad = np.argwhere(got != expected)
+        i, j = bad[0]
+        raise AssertionError('%s: %d of %d elements differ, rows %d..%d, columns %d..%d; first [%d, %d]: got %r, expected %r'
+                             % (what, len(bad), got.size, bad[:, 0].min(), bad[:, 0].max(), bad[:, 1].min(), bad[:, 1].max(),
+                                i, j, got[i, j], expected[i, j]))
+
+
+def _column_sums_hold(colsum, B, K, splits):
+    """The column sums that ride along the split-K form, under the bound of test_split_k_with_column_sums_against_float64."""
+    tol = 2e-6 * max(1.0, np.sqrt(K / splits / 128.0), np.sqrt(K / 128.0) / 8)
+    assert np.all(np.isfinite(colsum))
+    assert np.abs(colsum - B.astype(np.float64).sum(axis=0)).max() < tol
+
+
+def _shrink(form, K):
+    """Split-K form: a power of two that brings a dense B of magnitudes [0.5, 2) down to the 1 / sqrt(K) the column-sum bound
+    was written for (exact: it moves exponents only)."""
+    return F.pow2(-int(np.ceil(np.log2(np.sqrt(K)))) - 1) if form == 'splitk' else np.float32(1)
+
+
+@exact_cases
+def test_selection_times_full_mantissa_is_exact(hip_lib, form, M, N, K, splits, tb):
+    """One +-2^e per row of op(A), B with all three pieces non-zero everywhere: C[i, j] = +-2^e B[k_i, j] bit for bit -- the
+    products a0.b0, a0.b1, a0.b2 and the k every plane of B is read from.  sert_debug_gemm: also with a bias of small
+    integers behind it (acc + bias is one float32 addition: the expectation makes the same one)."""
+    A, B, expected = F.selection_a(M, N, K, 0, _kper(form, K, splits))
+    B, expected = B * _shrink(form, K), expected * _shrink(form, K)
+    got, colsum = _product(form, A, B, splits, tb)
+    _same_bits(got, expected, 'store')
+    if form == 'splitk':
+        _column_sums_hold(colsum, B, K, splits)
+    if form == 'plain':
+        bias = F.rng_of(9, N).integers(-3, 4, N).astype(np.float32)
+        _same_bits(_product(form, A, B, splits, tb, epi=1, bias=bias)[0], expected + bias[None, :], 'bias')
+
+
+@exact_cases
+def test_full_mantissa_times_selection_is_exact(hip_lib, form, M, N, K, splits, tb):
+    """The mirror image: one +-2^e per column of op(B), A with all three pieces non-zero: C[i, j] = +-2^e A[i, k_j] -- the
+    products a0.b0, a1.b0, a2.b0 and the k every plane of A is read from."""
+    A, B, expected = F.selection_b(M, N, K, 0, _kper(form, K, splits))
+    got, colsum = _product(form, A, B, splits, tb)
+    _same_bits(got, expected, 'store')
+    if form == 'splitk':
+        _column_sums_hold(colsum, B, K, splits)            # (one non-zero per column: the sum is that value)
+    if form == 'plain':
+        bias = F.rng_of(9, N).integers(-3, 4, N).astype(np.float32)
+        _same_bits(_product(form, A, B, splits, tb, epi=1, bias=bias)[0], expected + bias[None, :], 'bias')
+
+
+@exact_cases
+def test_two_piece_operands_keep_the_a1_b1_product(hip_lib, form, M, N, K, splits, tb):
+    """Operands of two bfloat16 pieces each (x2 = 0): an output is one product made of the four exact partial products
+    a0.b0, a0.b1, a1.b0, a1.b1 -- three float32 additions, 1.5 ulp under round-to-nearest; the bound is F.ULP_BOUND = 4 ulp of
+    the exact product (derived, with room for an accumulator that truncates; not measured).  Without a1.b1 every element
+    is 31 ulp or more away (tests/test_x3_split_cpu.py)."""
+    A, B, exact = F.two_piece_pair(M, N, K, 0, _kper(form, K, splits))
+    B, exact = B * _shrink(form, K), exact * float(_shrink(form, K))
+    got, colsum = _product(form, A, B, splits, tb)
+    assert np.all(np.isfinite(got))
+    off = np.abs(got.astype(np.float64) - exact) / F.ulp_of(exact)
+    worst = np.unravel_index(off.argmax(), off.shape)
+    print('two-piece %s %dx%dx%d tb=%d: worst %.2f ulp' % (form, M, N, K, tb, off[worst]))
+    assert off[worst] <= F.ULP_BOUND, (worst, off[worst], got[worst], exact[worst])
+    if form == 'splitk':
+        _column_sums_hold(colsum, B, K, splits)
+
+
+@exact_cases
+def test_power_of_two_scaling_commutes_with_the_product(hip_lib, form, M, N, K, splits, tb):
+    """Dense U(-1, 1) operands as they are, and with row i of op(A) times 2^r_i and column j of op(B) times 2^c_j, r and c
+    in [-30, 30]: no piece of a scaled operand is subnormal, so every rounding on the way lands on the scaled value and
+    the second product is the first times 2^(r_i + c_j) bit for bit (store epilogue).  The column sums of the split-K form are
+    float32 additions of B's elements in a fixed order: they scale the same way."""
+    A, B, r, c = F.scaled_pair(M, N, K, 0)
+    A2, B2 = F.scale_rows(A, r), F.scale_cols(B, c)
+    assert F.smallest_piece_is_normal(A2) and F.smallest_piece_is_normal(B2)
+    got, colsum = _product(form, A, B, splits, tb)
+    got2, colsum2 = _product(form, A2, B2, splits, tb)
+    assert np.all(np.isfinite(got))
+    nz = np.abs(got[got != 0])
+    assert nz.min() >= 2.0 ** -60 and nz.max() <= 2.0 ** 60       # (the scaled expectation itself neither under- nor overflows)
+    _same_bits(got2, F.scale_cols(F.scale_rows(got, r), c), 'scaled')
+    if form == 'splitk':
+        _column_sums_hold(colsum, B, K, splits)
+        assert np.array_equal(colsum2, colsum * F.pow2(c))
 
 
 # --------------------------------------------------------------------------- #
