@@ -311,6 +311,17 @@ int sert_scorer_topk(sert_scorer* s, const float* proj, int64_t num_queries, int
  * unset / > 1024 (query.py:250-260 ranks every entity); the caller orders them. */
 int sert_scorer_scores(sert_scorer* s, const float* proj, int64_t num_queries, float* score_out);
 
+/* All cosines (no selection, no (cos + 1)/2): cos_out (Q, V_e) f32, bit for bit the values sert_scorer_topk orders by and
+ * derives its scores from on this table.  (cos + 1)/2 is not injective in fp32 -- two cosines below 0.5 in magnitude can
+ * share a score -- so a caller that ranks every entity sorts THESE, under the order of sert_scorer_topk (descending, -0
+ * equal to +0, NaN after every number, ties by lowest entity index), and applies (cos + 1)/2 afterwards: the first k of that
+ * ranking are then sert_scorer_topk's k -- exactly for V_e < 32768 and under SERT_SCORE_FP32=1.  For a bf16-prefiltered table
+ * the cosines are the exact_dot32 ones; a row the fused path hands to the materialising path, every row of a table whose
+ * prefilter was demoted and every row under SERT_SCORE_MATERIALISE=1 pick their k entities on the GEMM's cosines before
+ * they are re-scored, so two entities within an fp32 rounding of each other across rank k can swap between the two.
+ * An all-zero entity row or query has no direction: its cosines are NaN. */
+int sert_scorer_cosines(sert_scorer* s, const float* proj, int64_t num_queries, float* cos_out);
+
 /* Page-locked host memory for the arrays that cross this boundary on every query call (the
  * (Q, d) projections in, the (Q, k) indices and scores out).  The reference hands numpy arrays
  * to sklearn (query.py:304-318); a caller that builds its query block in such a buffer and reads

@@ -31,6 +31,22 @@ int sert_debug_update_counts(sert_model* m, int64_t* out, int n);
  * batch's gather (vs_gather_mean_tail: hinted steps, sert_hint_next_batch).  n <= 2.  (tests/test_gpu_tail_in_gather.py) */
 int sert_debug_tail_counts(sert_model* m, int64_t* out, int n);
 
+/* Which path the rows of a scorer's sert_scorer_topk calls took since sert_scorer_create -- host counters, test hook: out[0]
+ * calls that took the fused path (sampled thresholds, filtering GEMM), out[1] those of them that filtered in bf16, out[2] the
+ * query chunks of the fused calls, out[3] rows the fused path flagged and handed to the materialising path, out[4] rows of calls
+ * that went to the materialising path directly, out[5] 1 while the table's bf16 prefilter is demoted to the fp32 filter.
+ * n <= 6.  tests/test_gpu_score_contract.py asserts through this that its shapes reach the path they are there for. */
+int sert_debug_scorer_counts(sert_scorer* s, int64_t* out, int n);
+
+/* Test hook: the scorer's own selection kernels on cosines the caller provides, S (Q, V) f32 host -- values no dot product
+ * of the library produces can be fed this way (every accumulator starts at +0, so a cosine of -0 never comes out of one).
+ * mode 0: topk_rows<false> on S as the materialising path runs it.  mode 1: topk_from_groups on the per-(row, 64-entity
+ * group) lists the fp32 filtering epilogue would leave for the threshold `thr` (elements with S >= thr, keyed by plain
+ * desc_key, 16 slots per group, candidate capacity 1024); a row that kernel flags (fewer than k or more than 1024
+ * candidates, an overflowed group) comes back with idx -1.  idx_out / score_out (Q, k): entity and (cos + 1)/2. */
+int sert_debug_scorer_select(int device, int mode, const float* S, int64_t num_queries, int32_t V, int32_t k, float thr,
+                             int32_t* idx_out, float* score_out);
+
 /* Test hook: overwrite the step's gradient scratch -- the flat buffer [g_Rw | g_Re | g_W | g_b | loss, sum of squares] with
  * quiet NaNs, the per-entity sorted-run bounds behind it with the wrong run [0, 1) -- after waiting for the device.  A step
  * whose negatives were drawn ahead launches NO prologue (nothing is zeroed): it relies on every value it reads having been

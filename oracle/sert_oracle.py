@@ -523,6 +523,24 @@ def vectorspace_rank(projection, R_e, top=None):
     return order, sc[order]
 
 
+def rank_order(values, top=None):
+    """THE order of every path that ranks cosine scores ("One ranking order"), for one row of values:
+      * descending value;
+      * equal values by lowest entity index, +0 and -0 being equal;
+      * a NaN of either sign after every number, the NaNs among themselves by lowest index;
+      * min(top, len(values)) results, distinct indices -- an all-NaN row gives 0, 1, 2, ...
+    Written out as three explicit sort keys (is-NaN, -value with the NaNs and zeros made one value each, index) rather than
+    left to what a library sort does with a NaN or a signed zero.  Returns the int64 indices."""
+    v = np.asarray(values).reshape(-1)
+    nan = np.isnan(v)
+    neg = np.where(nan, 0.0, -v.astype(np.float64))      # float32 -> float64 is exact and monotonic
+    neg = np.where(neg == 0.0, 0.0, neg)                 # -0 -> +0
+    order = np.lexsort((np.arange(v.size), neg, nan))    # last key first: NaN flag, then value, then index
+    if top is not None and top < order.size:
+        order = order[:top]
+    return order.astype(np.int64)
+
+
 def aggregate_product(distribution):
     """inference.aggregate_distribution(mode='product') (inference.py:173-174):
     exp(sum(log P)) with log(0) treated as 0."""

@@ -35,12 +35,12 @@ EXPORTS = [
     'sert_eval_batch', 'sert_eval_batches',
     'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_score_topk',
     'sert_reval_create', 'sert_reval_run', 'sert_reval_destroy',
-    'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_scores',
+    'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_scores', 'sert_scorer_cosines',
     'sert_host_alloc', 'sert_host_free',
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 
@@ -130,6 +130,7 @@ def load():
     lib.sert_scorer_destroy.argtypes = [vp]
     lib.sert_scorer_topk.argtypes = [vp, fp, i64, i32, fp, fp]
     lib.sert_scorer_scores.argtypes = [vp, fp, i64, fp]
+    lib.sert_scorer_cosines.argtypes = [vp, fp, i64, fp]
     lib.sert_host_alloc.argtypes = [ctypes.POINTER(vp), sz]
     lib.sert_host_free.argtypes = [vp]
     lib.sert_comm_unique_id.argtypes = [ctypes.c_char_p]
@@ -509,6 +510,21 @@ class PinnedBuffer(object):
             pass
 
 
+def debug_scorer_select(cosines, k, mode, thr=-np.inf, device=0):
+    """sert_debug_scorer_select (test hook): the scorer's selection kernels on caller-provided cosines (Q, V); mode 0
+    topk_rows, mode 1 topk_from_groups on the lists of the elements >= thr.  (idx, score)."""
+    s = np.ascontiguousarray(cosines, dtype=np.float32)
+    assert s.ndim == 2
+    idx = np.empty((s.shape[0], k), dtype=np.int32)
+    val = np.empty((s.shape[0], k), dtype=np.float32)
+    lib = load()
+    lib.sert_debug_scorer_select.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
+    check(lib.sert_debug_scorer_select(device, mode, s.ctypes.data, s.shape[0], s.shape[1], k, float(thr), idx.ctypes.data,
+                                       val.ctypes.data))
+    return idx, val
+
+
 class Scorer(object):
     """Persistent device copy of the (L2-normalised) entity table + top-k scoring
     (sert_scorer_* in include/sert_hip.h).
@@ -563,8 +579,27 @@ class Scorer(object):
         check(self._lib.sert_scorer_scores(self._h, p.ctypes.data, p.shape[0], out.ctypes.data))
         return out
 
+    def cosines(self, projections):
+        """(Q, V_e) float32: the cosines topk() orders by and derives its scores from, bit for bit."""
+        p = np.ascontiguousarray(projections, dtype=np.float32)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        assert p.shape[1] == self.dim
+        out = np.empty((p.shape[0], self.num_entities), dtype=np.float32)
+        check(self._lib.sert_scorer_cosines(self._h, p.ctypes.data, p.shape[0], out.ctypes.data))
+        return out
+
+    def debug_path_counts(self):
+        """sert_debug_scorer_counts (test hook): [fused calls, of those bf16-filtered, fused chunks, flagged rows, rows of
+        directly materialised calls, bf16 prefilter demoted]."""
+        v = (ctypes.c_int64 * 6)()
+        self._lib.sert_debug_scorer_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+        check(self._lib.sert_debug_scorer_counts(self._h, v, 6))
+        return [int(x) for x in v]
+
     def rank(self, projections, k=None):
-        """(idx, score) per query, best first; k=None ranks every entity."""
+        """(idx, score) per query, best first; k=None ranks every entity.  One order whatever k: the cosine descending
+        (-0 equal to +0), NaN after every number, ties by lowest entity index -- so rank(p, k) is the head of rank(p)."""
         if k is not None and k <= min(self.num_entities, 1024):
             return self.topk(projections, k)
         # no device top-k for this k: full score rows, a bounded number of queries at a time
@@ -578,10 +613,12 @@ class Scorer(object):
         idx = np.empty((p.shape[0], keep), dtype=np.int32)
         val = np.empty((p.shape[0], keep), dtype=np.float32)
         for lo in range(0, p.shape[0], step):
-            sc = self.scores(p[lo:lo + step])
-            order = np.argsort(-sc, axis=1, kind='stable')[:, :keep]   # ties: lowest index first
+            # the device orders the COSINE; (cos + 1)/2 maps several cosines to one score, so the score is applied after
+            # the sort.  -cos + 0: -0 and +0 become one value; NaN sorts last in numpy; stable: lowest index first
+            cos = self.cosines(p[lo:lo + step])
+            order = np.argsort(-cos + np.float32(0), axis=1, kind='stable')[:, :keep]
             idx[lo:lo + step] = order
-            val[lo:lo + step] = np.take_along_axis(sc, order, axis=1)
+            val[lo:lo + step] = (np.take_along_axis(cos, order, axis=1) + np.float32(1)) / np.float32(2)
         return idx, val
 
     def close(self):

@@ -223,6 +223,17 @@ __device__ __forceinline__ float key_to_float(uint32_t k) {
     return __uint_as_float(u);
 }
 
+// desc_key under the cosine scorer's order ("One ranking order"): -0 takes +0's key, so that the two tie and the
+// lowest entity index decides, and a NaN of either sign takes the last key, after every number (key_to_float gives a NaN back
+// for it).  List entries of that key still sort before the ~0 padding of the bitonic sorts: their low word is an entity index.
+__device__ __forceinline__ uint32_t score_key(float f) {
+    if (f != f) return 0xffffffffu;
+    const uint32_t u = __float_as_uint(f);
+    return u == 0x80000000u ? 0x7fffffffu : desc_key(f);
+}
+// the same on a key that desc_key made of a number (the fp32 filter's lists hold no NaN: `v >= thr` is false for one)
+__device__ __forceinline__ uint32_t score_key_of_desc_key(uint32_t k) { return k == 0x80000000u ? 0x7fffffffu : k; }
+
 // clip bounds of the reference as fp32 constants: 1e-7 and float32(1 - 1e-7)
 // = 1 - 2^-23 (sert/models.py:200, :290, :900, :1067-1068)
 #define SERT_CLIP_LO 1e-7f

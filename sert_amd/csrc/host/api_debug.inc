@@ -29,6 +29,64 @@ int sert_debug_tail_counts(sert_model* m, int64_t* out, int n) {
     return 0;
 }
 
+int sert_debug_scorer_counts(sert_scorer* sc, int64_t* out, int n) {
+    if (!sc || !out || n < 1 || n > 6) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = i < 5 ? sc->path_counts[i] : (sc->bf16_demoted ? 1 : 0);
+    return 0;
+}
+
+int sert_debug_scorer_select(int device, int mode, const float* S, int64_t Q, int32_t V, int32_t k, float thr,
+                             int32_t* idx_out, float* score_out) {
+    if (!S || !idx_out || !score_out || Q <= 0 || V <= 0 || k <= 0 || k > V || k > kTopKMax || mode < 0 || mode > 1)
+        SERT_FAIL("bad argument");
+    SERT_HIP(hipSetDevice(device));
+    const int ngroups = (int)cdiv(V, 64), gcap = 16, ccap = 1024;
+    float* dS = nullptr; float* dval = nullptr; int32_t* didx = nullptr;
+    unsigned long long* dcand = nullptr; unsigned char* dcnt = nullptr; int* dflag = nullptr;
+    auto body = [&]() -> int {
+        SERT_TRY(dmalloc(&dval, (size_t)Q * k));
+        SERT_TRY(dmalloc(&didx, (size_t)Q * k));
+        SERT_HIP(hipMemset(didx, 0xff, (size_t)Q * k * sizeof(int32_t)));       // a flagged row stays -1
+        SERT_HIP(hipMemset(dval, 0, (size_t)Q * k * sizeof(float)));
+        if (mode == 0) {
+            SERT_TRY(dmalloc(&dS, (size_t)Q * V));
+            SERT_HIP(hipMemcpy(dS, S, (size_t)Q * V * sizeof(float), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(topk_rows<false>, dim3((unsigned)Q), dim3(256), 0, 0, dS, (int)V, (int)k, didx, dval, (float*)nullptr);
+        } else {
+            // the lists as the fp32 filter epilogue leaves them: per (row, 64-entity group) the elements with S >= thr in
+            // ascending entity order, keyed by plain desc_key (a NaN fails the compare there as here)
+            std::vector<unsigned long long> cand((size_t)Q * ngroups * gcap, 0ull);
+            std::vector<unsigned char> cnt((size_t)Q * ngroups, 0);
+            for (int64_t q = 0; q < Q; ++q)
+                for (int32_t e = 0; e < V; ++e) {
+                    const float v = S[q * V + e];
+                    if (!(v >= thr)) continue;
+                    uint32_t u; memcpy(&u, &v, 4);
+                    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+                    const size_t g = (size_t)q * ngroups + e / 64;
+                    if (cnt[g] < gcap) cand[g * gcap + cnt[g]] = ((unsigned long long)(~u) << 32) | (uint32_t)e;
+                    if (cnt[g] < 255) ++cnt[g];
+                }
+            SERT_TRY(dmalloc(&dcand, cand.size()));
+            SERT_TRY(dmalloc(&dcnt, cnt.size()));
+            SERT_TRY(dmalloc(&dflag, (size_t)Q + 1));
+            SERT_HIP(hipMemcpy(dcand, cand.data(), cand.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+            SERT_HIP(hipMemcpy(dcnt, cnt.data(), cnt.size(), hipMemcpyHostToDevice));
+            SERT_HIP(hipMemset(dflag, 0, ((size_t)Q + 1) * sizeof(int)));
+            hipLaunchKernelGGL(topk_from_groups, dim3((unsigned)Q), dim3(256), (size_t)ccap * sizeof(unsigned long long), 0,
+                               dcand, dcnt, ngroups, gcap, (int)k, didx, dval, 0, dflag, dflag + 1, ccap, (int*)nullptr);
+        }
+        SERT_HIP(hipGetLastError());
+        SERT_HIP(hipDeviceSynchronize());
+        SERT_HIP(hipMemcpy(idx_out, didx, (size_t)Q * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        SERT_HIP(hipMemcpy(score_out, dval, (size_t)Q * k * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = body();
+    (void)hipFree(dS); (void)hipFree(dval); (void)hipFree(didx); (void)hipFree(dcand); (void)hipFree(dcnt); (void)hipFree(dflag);
+    return rc;
+}
+
 int sert_debug_row_lists(const uint32_t* allbits, int world, int rank, int64_t num_batches, int64_t bit_words,
                          int64_t rows_per_rank, int64_t vocab, int64_t batch, int32_t* serve_cnt, int32_t* fetch_cnt,
                          int32_t* serve_rows, int32_t* fetch_rows, int32_t* union_rows, int32_t* ptr, int32_t* ent,

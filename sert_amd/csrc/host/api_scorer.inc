@@ -184,7 +184,7 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
     if (sc->cap_flag < Q) {
         (void)hipFree(sc->flag_list); (void)hipFree(sc->nflag);
         sc->flag_list = nullptr; sc->nflag = nullptr; sc->cap_flag = 0;
-        SERT_TRY(dmalloc(&sc->flag_list, (size_t)Q));
+        SERT_TRY(dmalloc(&sc->flag_list, (size_t)(2 * Q)));   // the list, and behind it one flag per row (topk_from_groups)
         SERT_TRY(dmalloc(&sc->nflag, (size_t)1));
         sc->cap_flag = Q;
     }
@@ -252,10 +252,17 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
             hipLaunchKernelGGL(topk_from_groups_rescore, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
                                (const uint32_t*)cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
                                sc->nflag, sc->flag_list, ccap, P, sc->E, dim, thr, bf16_delta(dim));
-        else
+        else {
             hipLaunchKernelGGL(topk_from_groups, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
                                cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
-                               sc->nflag, sc->flag_list, ccap);
+                               sc->nflag, sc->flag_list, ccap, sc->flag_list + sc->cap_flag);
+            if (sc->bf16) {   // demoted table: its scores stay the exact_dot ones every other path of this scorer reports
+                int sn = 2;
+                while (sn < k) sn <<= 1;
+                hipLaunchKernelGGL(rescore_topk_rows, dim3((unsigned)qn), dim3(256), (size_t)sn * sizeof(unsigned long long),
+                                   st, P, sc->E, dim, k, sc->idx + q0 * k, sc->val + q0 * k, sc->flag_list + sc->cap_flag + q0);
+            }
+        }
         // results of the previous chunk (other stream) travel while this one computes
         if (t >= 1) SERT_HIP(copy_out(q0 - QT, QT, set ? s : sc->stream2));
     }
@@ -268,6 +275,7 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
     int nf = 0;
     SERT_HIP(hipMemcpyAsync(&nf, sc->nflag, sizeof(int), hipMemcpyDeviceToHost, s));
     SERT_HIP(hipStreamSynchronize(s));
+    sc->path_counts[0] += 1; sc->path_counts[1] += use_bf16 ? 1 : 0; sc->path_counts[2] += t; sc->path_counts[3] += nf;
     if (nf == 0) { *copied_out = true; return 0; }
     if (use_bf16 && (int64_t)nf * 4 > Q && Q >= 64) sc->bf16_demoted = true;
     // rows the sample misjudged: recompute exactly (ascending order, for reproducibility)
@@ -334,6 +342,7 @@ static int scorer_topk_io(sert_scorer* sc, const float* proj, int64_t Q, int32_t
         SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
         SERT_TRY(scorer_topk_materialised(sc, sc->P, Q, k, sc->idx, sc->val));
+        sc->path_counts[4] += Q;
     }
     SERT_HIP(hipGetLastError());
     if (copied) return 0;
@@ -348,7 +357,9 @@ int sert_scorer_topk(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
     return scorer_topk_io(sc, proj, Q, k, idx_out, score_out, false);
 }
 
-int sert_scorer_scores(sert_scorer* sc, const float* proj, int64_t Q, float* score_out) {
+// every entity's value for Q queries: (cos + 1)/2 of the GEMM's cosine, or (raw) the cosine itself AS sert_scorer_topk ORDERS
+// AND REPORTS IT -- the exact_dot32 one for a bf16-prefiltered table, the GEMM's otherwise
+static int scorer_all(sert_scorer* sc, const float* proj, int64_t Q, float* score_out, bool raw) {
     if (!sc || !proj || !score_out) SERT_FAIL("null argument");
     if (Q <= 0) return 0;
     SERT_HIP(hipSetDevice(sc->device));
@@ -370,13 +381,24 @@ int sert_scorer_scores(sert_scorer* sc, const float* proj, int64_t Q, float* sco
     hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
     for (int64_t q0 = 0; q0 < Q; q0 += QT) {
         const int64_t qn = std::min(QT, Q - q0);
-        launch_gemm<false, true, EPI_STORE>(s, sc->P + q0 * dim, sc->E, sc->S, nullptr, (int)qn, (int)V, dim,
-                                            dim, dim, (int)V);
-        hipLaunchKernelGGL(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S, (size_t)(qn * V));
+        if (raw && sc->bf16)
+            hipLaunchKernelGGL(exact_cosine_rows, dim3((unsigned)std::min<int64_t>(cdiv(V, 8), 1024), (unsigned)qn), dim3(256), 0, s,
+                               sc->P + q0 * dim, sc->E, V, dim, sc->S);
+        else
+            launch_gemm<false, true, EPI_STORE>(s, sc->P + q0 * dim, sc->E, sc->S, nullptr, (int)qn, (int)V, dim,
+                                                dim, dim, (int)V);
+        if (!raw) hipLaunchKernelGGL(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S, (size_t)(qn * V));
         SERT_HIP(hipMemcpyAsync(score_out + q0 * V, sc->S, (size_t)qn * V * sizeof(float), hipMemcpyDeviceToHost, s));
         SERT_HIP(hipStreamSynchronize(s));
     }
     return 0;
+}
+
+int sert_scorer_scores(sert_scorer* sc, const float* proj, int64_t Q, float* score_out) {
+    return scorer_all(sc, proj, Q, score_out, false);
+}
+int sert_scorer_cosines(sert_scorer* sc, const float* proj, int64_t Q, float* cos_out) {
+    return scorer_all(sc, proj, Q, cos_out, true);
 }
 
 int sert_host_alloc(void** out, size_t bytes) {

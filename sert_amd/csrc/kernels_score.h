@@ -59,6 +59,10 @@ __device__ __forceinline__ void topk_scan_row(const float* __restrict__ row, int
 
 constexpr int kTopKCand = 2048;   // LDS capacity for the threshold-bin candidates
 
+// the key a row is ordered by: the scorer's (score_key: -0 ties with +0, NaN last) or, RAW, the loglinear ranker's plain one
+template <bool RAW>
+__device__ __forceinline__ uint32_t rank_key(float x) { return RAW ? desc_key(x) : score_key(x); }
+
 // Top-k of one row of cosine scores, one workgroup (256 threads) per query.
 //   pass 1 (1 read)  2048-bin histogram of the top 11 bits of the order-preserving
 //                    key -> the bin holding the k-th best score
@@ -94,7 +98,7 @@ __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, in
     for (int i = tid; i < sort_n; i += 256) keys[i] = ~0ull;
     if (tid == 0) { s_count = 0; s_ncand = 0; s_bin = 0; s_need = 0; }
     __syncthreads();
-    topk_scan_row(row, V, [&](float x, int) { atomicAdd(&hist[desc_key(x) >> 21], 1u); });
+    topk_scan_row(row, V, [&](float x, int) { atomicAdd(&hist[rank_key<RAW>(x) >> 21], 1u); });
     __syncthreads();
     // locate the bin of the k-th best: 8 consecutive bins per thread + block scan
     uint32_t local[8], sum = 0;
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, in
     if (fits) {
         // ---- pass 2: winners + candidates ---------------------------------------
         topk_scan_row(row, V, [&](float x, int e) {
-            const uint32_t key = desc_key(x);
+            const uint32_t key = rank_key<RAW>(x);
             const uint32_t bin = key >> 21;
             if (bin < tbin) {
                 keys[atomicAdd(&s_count, 1u)] = ((unsigned long long)key << 32) | (uint32_t)e;
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, in
             const uint32_t prefix = s_prefix;
             const int shift_hi = 8 * (pass + 1);
             topk_scan_row(row, V, [&](float x, int) {
-                const uint32_t key = desc_key(x);
+                const uint32_t key = rank_key<RAW>(x);
                 const bool match = (pass == 3) || ((key >> shift_hi) == prefix);
                 if (match) atomicAdd(&hist[(key >> (8 * pass)) & 0xffu], 1u);
             });
@@ -188,7 +192,7 @@ __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, in
         if (tid == 0) { s_count = 0; s_ties = 0; }
         __syncthreads();
         topk_scan_row(row, V, [&](float x, int e) {
-            const uint32_t key = desc_key(x);
+            const uint32_t key = rank_key<RAW>(x);
             if (key < thr) keys[atomicAdd(&s_count, 1u)] = ((unsigned long long)key << 32) | (uint32_t)e;
         });
         __syncthreads();
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, in
         const int lane = tid & 63, wv = tid >> 6;
         for (int e0 = 0; e0 < V; e0 += 256) {
             const int e = e0 + tid;
-            const bool is_tie = (e < V) && (desc_key(row[e]) == thr);
+            const bool is_tie = (e < V) && (rank_key<RAW>(row[e]) == thr);
             const unsigned long long bal = __ballot(is_tie);
             const uint32_t before_in_wave = __popcll(bal & ((1ull << lane) - 1ull));
             if (lane == 0) wave_cnt[wv] = __popcll(bal);
@@ -257,7 +261,7 @@ __global__ __launch_bounds__(256) void kth_largest_rows(const float* __restrict_
         const uint32_t prefix = s_prefix;
         const int shift_hi = 8 * (pass + 1);
         topk_scan_row(row, V, [&](float x, int) {
-            const uint32_t key = desc_key(x);
+            const uint32_t key = score_key(x);
             const bool match = (pass == 3) || ((key >> shift_hi) == prefix);
             if (match) atomicAdd(&hist[(key >> (8 * pass)) & 0xffu], 1u);
         });
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(256) void approx_kth_rows(const float* __restrict__
     const int tid = threadIdx.x;
     const float* row = S + (size_t)blockIdx.x * V;
     uint32_t best = 0xffffffffu;                       // desc_key: smaller = larger score
-    topk_scan_row(row, V, [&](float x, int) { best = min(best, desc_key(x)); });
+    topk_scan_row(row, V, [&](float x, int) { best = min(best, score_key(x)); });
     keys[tid] = best;
     __syncthreads();
     for (int size = 2; size <= 256; size <<= 1) {
@@ -332,12 +336,13 @@ constexpr int kCandCap = 4096;   // upper bound of the per-row candidate capacit
 // One workgroup per query: gather the row's per-group lists (EPI_FILTER layout) into
 // LDS, sort (score desc, index asc), emit the k best.  Rows with an overflowed group,
 // fewer than k candidates or more than kCandCap are flagged for the materialising path.
+// row_flag (optional, indexed like flag_list's entries): 1 for a flagged row, 0 for a row that got its result.
 __global__ __launch_bounds__(256) void topk_from_groups(const unsigned long long* __restrict__ cand,
                                                         const unsigned char* __restrict__ gcnt, int ngroups,
                                                         int gcap, int k, int32_t* __restrict__ idx_out,
                                                         float* __restrict__ val_out, int q_base,
                                                         int* __restrict__ nflag, int* __restrict__ flag_list,
-                                                        int ccap) {
+                                                        int ccap, int* __restrict__ row_flag = nullptr) {
     // ccap (a power of two <= kCandCap) keys of dynamic LDS: sized by the host for the expected
     // candidate count, so that 8 workgroups fit a CU instead of the 4 a 32 KB array allows
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
@@ -367,14 +372,21 @@ __global__ __launch_bounds__(256) void topk_from_groups(const unsigned long long
     }
     const unsigned total = scan[255];
     if (s_bad || total < (unsigned)k || total > (unsigned)ccap) {     // workgroup-uniform
-        if (tid == 0) flag_list[atomicAdd(nflag, 1)] = q_base + q;
+        if (tid == 0) {
+            flag_list[atomicAdd(nflag, 1)] = q_base + q;
+            if (row_flag) row_flag[q_base + q] = 1;      // no result in this row yet (rescore_topk_rows passes it over)
+        }
         return;
     }
+    if (tid == 0 && row_flag) row_flag[q_base + q] = 0;
     unsigned pos = scan[tid] - mine;
     for (int g = g0; g < g1; ++g) {
         const unsigned c = gc[g];
         const unsigned long long* src = cand + ((size_t)q * ngroups + g) * gcap;
-        for (unsigned j = 0; j < c; ++j) keys[pos + j] = src[j];
+        for (unsigned j = 0; j < c; ++j) {     // (the filter epilogue wrote desc_key: -0 gets +0's key here, not there)
+            const unsigned long long kv = src[j];
+            keys[pos + j] = ((unsigned long long)score_key_of_desc_key((uint32_t)(kv >> 32)) << 32) | (uint32_t)kv;
+        }
         pos += c;
     }
     int sort_n = 2;

@@ -94,7 +94,7 @@ __device__ __forceinline__ void rescore_sort_emit(unsigned long long* keys, int 
         if (l == 0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (i0 + j < m) keys[i0 + j] = ((unsigned long long)desc_key(sc[j]) << 32) | e[j];
+                if (i0 + j < m) keys[i0 + j] = ((unsigned long long)score_key(sc[j]) << 32) | e[j];
         }
     }
     for (int i = m + tid; i < sort_n; i += 256) keys[i] = ~0ull;
@@ -122,14 +122,28 @@ __device__ __forceinline__ void rescore_sort_emit(unsigned long long* keys, int 
 // get the same exact_dot scores and ordering as the fused path's.
 __global__ __launch_bounds__(256) void rescore_topk_rows(const float* __restrict__ P, const float* __restrict__ E,
                                                          int d, int k, int32_t* __restrict__ idx,
-                                                         float* __restrict__ val) {
+                                                         float* __restrict__ val, const int* __restrict__ row_flag = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     const int q = blockIdx.x;
+    if (row_flag && row_flag[q]) return;    // a row topk_from_groups flagged: the materialising path fills it (workgroup-uniform)
     for (int i = threadIdx.x; i < k; i += 256) keys[i] = (uint32_t)idx[(size_t)q * k + i];
     __syncthreads();
     int sort_n = 2;
     while (sort_n < k) sort_n <<= 1;
     rescore_sort_emit(keys, k, sort_n, P + (size_t)q * d, E, d, k, idx + (size_t)q * k, val + (size_t)q * k);
+}
+
+// C (Q, V) = the exact_dot32 cosine of every (query, entity) pair: the values the scorer of a bf16-prefiltered table reports,
+// for the caller that ranks every entity (sert_scorer_cosines).  One half-wave per pair; grid (entity blocks, Q).
+__global__ __launch_bounds__(256) void exact_cosine_rows(const float* __restrict__ P, const float* __restrict__ E, int64_t V,
+                                                         int d, float* __restrict__ C) {
+    const int half = threadIdx.x >> 5, l = threadIdx.x & 31;
+    const float* prow = P + (size_t)blockIdx.y * d;
+    float* crow = C + (size_t)blockIdx.y * V;
+    for (int64_t e = (int64_t)blockIdx.x * 8 + half; e < V; e += (int64_t)gridDim.x * 8) {
+        const float a = exact_dot32(prow, E + (size_t)e * d, d, l);
+        if (l == 0) crow[e] = a;
+    }
 }
 
 // exclusive prefix sum of one value per thread over a 256-thread workgroup (wave shuffles + 4

@@ -349,4 +349,8 @@ struct sert_scorer {
     int kp = 0;
     uint16_t* E16 = nullptr; uint16_t* P16 = nullptr;
     int64_t cap_p16 = 0;
+    // which path the rows took since sert_scorer_create (host counters, read by sert_debug_scorer_counts): [0] fused calls,
+    // [1] those that filtered in bf16, [2] query chunks of the fused calls, [3] rows the fused path flagged and handed to the
+    // materialising path, [4] rows of calls that went to the materialising path directly
+    int64_t path_counts[5] = {0, 0, 0, 0, 0};
 };

@@ -596,18 +596,7 @@ def test_score_topk_mass_ties(hip_lib, V):
     assert np.all(val[0] == val[0][0])
 
 
-def _check_topk_against_oracle(E, Pj, idx, val, k):
-    E64, P64 = E.astype(np.float64), Pj.astype(np.float64)
-    for q in range(Pj.shape[0]):
-        order, sc = O.vectorspace_rank(P64[q], E64, top=k)
-        full = None
-        for r in np.nonzero(idx[q] != order)[0]:
-            # identical ranking except where the fp64 score gap is below 1e-6
-            if full is None:
-                full = O.vectorspace_scores(P64[q], E64)
-            assert abs(full[idx[q][r]] - sc[r]) < 1e-6
-        assert np.abs(val[q] - sc).max() < 1e-6
-        assert len(set(idx[q].tolist())) == k
+_check_topk_against_oracle = U.check_topk_against_oracle
 
 
 @pytest.mark.parametrize('V,d,Q,k', [(40000, 16, 37, 10), (65536, 32, 130, 100), (50001, 64, 9, 1000),

@@ -172,6 +172,50 @@ def test_vectorspace_ranking_and_metrics_equal_the_query_path(hip_lib, Ve, de, d
     eng.close()
 
 
+@pytest.mark.parametrize('Ve,de,dw', [(500, 24, 32)])
+def test_vectorspace_ranking_and_metrics_equal_the_query_path_with_a_zero_row_and_a_tie(hip_lib, Ve, de, dw):
+    """The case the test above keeps out (it asserts a tie-free ranking): a table with an all-zero entity row -- no
+    direction, NaN score, last at full depth -- and a relevant entity that duplicates a lower-index irrelevant one.  The
+    evaluator's ranking stays bit-equal to the query path's ("One ranking order"), the metrics within 1e-9 of
+    the host functions on that ranking."""
+    eng, p = _train_vs(Ve, de, 23, dw)
+    rng = np.random.RandomState(5)
+    lists = _queries(rng, p['Rw'].shape[0], 15)
+    probe = _reval(eng, lists, [{} for _ in lists], 5)
+    top = probe.run(return_ranking=True)[2][:, 0]
+    probe.close()
+    Re = eng.get_tensor(C.T_RE, p['Re'].shape)
+    lo, hi = sorted((int(top[0]), (int(top[0]) + 7) % Ve))
+    zero = (hi + 11) % Ve
+    assert zero != lo
+    Re[hi] = Re[lo] = Re[int(top[0])].copy()
+    Re[zero] = 0
+    eng.set_tensor(C.T_RE, Re)
+    for k in (Ve, 100, 5):
+        # hi relevant, its lower-index twin lo judged by nobody; each topic's own best entity as well, unless it is the pair
+        rels = [dict({hi: 1.0, zero: 2.0}, **({} if int(top[q]) in (lo, hi) else {int(top[q]): 0.5})) for q in range(len(lists))]
+        assert all(lo not in rel for rel in rels)
+        ev = _reval(eng, lists, rels, k)
+        metrics, status, idx, score = ev.run(return_ranking=True)
+        ev.close()
+        Rw = eng.get_tensor(C.T_RW, p['Rw'].shape)
+        avg = np.stack([Rw[t, :].mean(axis=0) for t in lists])
+        scorer = C.Scorer(eng.get_tensor(C.T_RE, p['Re'].shape))
+        ref_idx, ref_val = (a.copy() for a in scorer.rank(eng.predict_project(avg), k))
+        scorer.close()
+        assert np.all(status == C.LL_STATUS_DEVICE)
+        assert np.array_equal(idx, ref_idx) and U.same_bits(score, ref_val), k
+        for q in range(len(lists)):
+            at = idx[q].tolist()
+            if lo in at and hi in at:
+                assert at.index(hi) == at.index(lo) + 1 and score[q, at.index(hi)] == score[q, at.index(lo)]
+        assert idx[0, 0] == lo and idx[0, 1] == hi
+        if k == Ve:
+            assert np.all(idx[:, -1] == zero) and np.isnan(score[:, -1]).all() and not np.isnan(score[:, :-1]).any()
+        _check_metrics(metrics, idx, rels, 'vectorspace zero row + tie k=%d' % k)
+    eng.close()
+
+
 def test_tied_entities_rank_by_lowest_index(hip_lib):
     """Two identical entity rows: the evaluator ranks the lower index first and scores that ranking."""
     eng, p = _train_vs(300, 24, 22)

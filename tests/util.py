@@ -216,3 +216,142 @@ def check_state(got, ref32, ref64=None, rows=None, names=None, prefix=''):
         log.append(prefix + check_tensor(k, got[k], ref32[k], None if ref64 is None else ref64[k], rows=sub,
                                          row_tol32=state_row_tol32(k), row_tol64=(2 if square else 1) * ROW_TOL64))
     return log
+
+
+# --------------------------------------------------------------------------- #
+# The cosine scorer: the Gaussian-data check, and problems whose ranking is known exactly
+# --------------------------------------------------------------------------- #
+
+def check_topk_against_oracle(E, Pj, idx, val, k):
+    """(idx, val) of a top-k call against the float64 oracle: identical ranking except where the fp64 score gap is below
+    1e-6, scores within 1e-6, k distinct entities."""
+    E64, P64 = E.astype(np.float64), Pj.astype(np.float64)
+    for q in range(Pj.shape[0]):
+        order, sc = O.vectorspace_rank(P64[q], E64, top=k)
+        full = None
+        for r in np.nonzero(idx[q] != order)[0]:
+            if full is None:
+                full = O.vectorspace_scores(P64[q], E64)
+            assert abs(full[idx[q][r]] - sc[r]) < 1e-6
+        assert np.abs(val[q] - sc).max() < 1e-6
+        assert len(set(idx[q].tolist())) == k
+
+
+# Exact problems.  Rows have entries in {0, +-1} with exactly 1, 4 or 16 of them non-zero: the norm is 1, 2 or 4, the unit row
+# has entries +-1, +-1/2 or +-1/4, every product of two entries is a multiple of 1/16 and a cosine is a sum of at most 16 of
+# them, in [-1, 1] -- a multiple of 1/16 with at most 5 significant bits at every partial sum, in ANY summation order.  That is
+# exact in fp32 and in bf16 (8 significant bits), so whatever GEMM, dot product or prefilter the scorer runs, it must produce
+# 16 cos = <p, e> 16 / (|p| |e|) as an integer, and the ranking -- mass ties at 33 levels included -- is known from integer
+# arithmetic alone.  tests/test_score_contract_cpu.py proves the claim on every shape below; it is the licence for the GPU
+# tests to demand equal indices and bit-equal values with no exemption.
+EXACT_NNZ = (1, 4, 16)
+# (seed, V, d, Q, mix of entity rows over EXACT_NNZ) by name; the queries are an even mix
+EXACT_SHAPES = {
+    'tiny': (101, 50, 16, 6, (0.3, 0.3, 0.4)),
+    'k_is_v': (102, 300, 16, 6, (0.3, 0.3, 0.4)),
+    'unaligned_rows': (103, 4099, 20, 6, (0.3, 0.3, 0.4)),        # V % 4 = 3: every row but each fourth starts off 16 bytes
+    'mid': (104, 5000, 16, 6, (0.3, 0.3, 0.4)),
+    'radix_fallback': (105, 6000, 16, 6, (0.8, 0.1, 0.1)),         # most rows one-hot: thousands tied at 0 and at +-1/4
+    'fused_smallest': (106, 32768, 16, 12, (0.5, 0.1, 0.4)),
+    'fused_ragged': (107, 40001, 16, 12, (0.5, 0.1, 0.4)),
+    'prefix': (108, 40000, 16, 12, (0.5, 0.1, 0.4)),
+    'fused_dense': (110, 40001, 16, 12, (0.08, 0.02, 0.9)),        # enough entities above 1/2 for k = 1024 to keep fused rows
+}
+
+
+def exact_rows(rng, rows, d, mix):
+    """(rows, d) int8 in {0, +-1}: exactly 1, 4 or 16 non-zeros per row (drawn with probabilities `mix`) at random places."""
+    assert d >= max(EXACT_NNZ)
+    nnz = rng.choice(EXACT_NNZ, size=rows, p=mix)
+    places = np.argsort(rng.rand(rows, d), axis=1) < nnz[:, None]     # a row of a permutation: exactly nnz entries below nnz
+    signs = rng.randint(0, 2, size=(rows, d)) * 2 - 1
+    return (places * signs).astype(np.int8)
+
+
+def exact_score_problem(name):
+    """dict: E (V, d) / P (Q, d) float32 in {0, +-1}, and Ei / Pi the same as int8."""
+    seed, V, d, Q, mix = EXACT_SHAPES[name]
+    rng = np.random.RandomState(seed)
+    Ei = exact_rows(rng, V, d, mix)
+    Pi = exact_rows(rng, Q, d, (1 / 3.0, 1 / 3.0, 1 / 3.0))
+    Pi[:3] = exact_rows(np.random.RandomState(seed + 1000), 3, d, (0, 0, 1))[:3]   # 16 non-zeros: few ties at the top
+    return dict(E=Ei.astype(np.float32), P=Pi.astype(np.float32), Ei=Ei, Pi=Pi)
+
+
+def exact_cos16(Pi, Ei):
+    """(Q, V) int64 = 16 cos, in integer arithmetic: <p, e> * 16 / (|p| |e|), the norms 1, 2 or 4."""
+    Pi, Ei = np.asarray(Pi, dtype=np.int64), np.asarray(Ei, dtype=np.int64)
+    isqrt = {1: 1, 4: 2, 16: 4}
+    nq = np.array([isqrt[int(n)] for n in (Pi != 0).sum(axis=1)], dtype=np.int64)
+    ne = np.array([isqrt[int(n)] for n in (Ei != 0).sum(axis=1)], dtype=np.int64)
+    dots = np.zeros((Pi.shape[0], Ei.shape[0]), dtype=np.int64)
+    for c in range(Pi.shape[1]):                  # (an integer matmul, column by column: no BLAS for int64)
+        dots += Pi[:, c, None] * Ei[None, :, c]
+    den = nq[:, None] * ne[None, :]
+    assert np.all((dots * 16) % den == 0)
+    return dots * 16 // den
+
+
+def exact_expected(c16, k=None, nan_entities=(), nan_queries=()):
+    """The contract's (idx, val) for integer cosines c16 (Q, V): rank_order of every row, val = (c16 + 16) / 32 as float32.
+    Entities / queries listed as NaN (zero, NaN or infinite rows: no direction) score NaN against everything."""
+    cos = c16.astype(np.float32) / np.float32(16)
+    cos[:, list(nan_entities)] = np.nan
+    cos[list(nan_queries), :] = np.nan
+    keep = cos.shape[1] if k is None else k
+    idx = np.stack([O.rank_order(row, keep) for row in cos]).astype(np.int32)
+    val = (np.take_along_axis(cos, idx.astype(np.int64), axis=1) + np.float32(1)) / np.float32(2)
+    return idx, val
+
+
+def same_bits(a, b):
+    """float32 arrays equal bit for bit, any NaN equal to any NaN (a NaN's payload is not part of the contract)."""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
+
+
+def score_key(cos):
+    """The scorer's 32-bit descending key of float32 cosines (csrc/common.h score_key), in numpy: ascending key = descending
+    value, -0 as +0, NaN last."""
+    c = np.ascontiguousarray(cos, dtype=np.float32)
+    u = (c + np.float32(0)).view(np.uint32)                       # -0 + 0 = +0
+    asc = np.where(u & 0x80000000, ~u, u | 0x80000000).astype(np.uint32)
+    return np.where(np.isnan(c), np.uint32(0xffffffff), ~asc).astype(np.uint32)
+
+
+def threshold_bin_load(name, k):
+    """Per query of an exact problem: how many entities share the 11-bit key bin of the k-th best -- what topk_rows has to
+    fit into its 2048-entry candidate list."""
+    p = exact_score_problem(name)
+    cos = exact_cos16(p['Pi'], p['Ei']).astype(np.float32) / np.float32(16)
+    out = []
+    for row in cos:
+        hist = np.bincount(score_key(row) >> 21, minlength=2048)
+        out.append(int(hist[np.searchsorted(np.cumsum(hist), k)]))
+    return out
+
+
+def gaussian_score_problem(V, d, Q, seed=41):
+    rng = np.random.RandomState(seed)
+    return rng.randn(V, d).astype(np.float32), np.tanh(rng.randn(Q, d)).astype(np.float32)
+
+
+def oracle_cosines_f32(E, P):
+    """(Q, V) float32 cosines the way the oracle's float32 path computes them (unit rows, one matrix product)."""
+    En = E / np.linalg.norm(E, axis=1)[:, None].astype(np.float32)
+    Pn = P / np.linalg.norm(P, axis=1)[:, None].astype(np.float32)
+    return (Pn @ En.T).astype(np.float32)
+
+
+def count_score_collisions(cos, depth):
+    """Number of rows of float32 cosines (Q, V) whose first `depth` entities (rank_order) hold two entities with one
+    emitted score (cos + 1)/2 and two different cosines -- where ordering the score and ordering the cosine can part."""
+    n = 0
+    for row in cos:
+        c = row[O.rank_order(row, depth)]
+        sc = (c + np.float32(1)) / np.float32(2)
+        n += int(np.any((sc[1:] == sc[:-1]) & (c[1:] != c[:-1])))
+    return n
