@@ -307,15 +307,35 @@ int sert_scorer_destroy(sert_scorer* s);
 int sert_scorer_topk(sert_scorer* s, const float* proj, int64_t num_queries, int32_t k,
                      int32_t* idx_out, float* score_out);
 
-/* All scores (no selection): score_out (Q, V_e) f32 = (cos + 1)/2.  For --top
- * unset / > 1024 (query.py:250-260 ranks every entity); the caller orders them. */
+/* The full ranking (query.py:250-260: --top unset ranks every entity; so do --top above 1024 and above V_e), on the device.
+ * k = -1 ranks every entity, k >= 1 the k best; the ranked depth kk is num_entities for k = -1 or k >= num_entities, else k
+ * (the convention of sert_ll_rank_queries); k = 0 and k < -1 are refused.  idx_out / score_out (Q, kk) host arrays.
+ * The order is sert_scorer_topk's: the COSINE descending (-0 equal to +0), a NaN of either sign after every number, ties and
+ * the NaNs among themselves by lowest entity index; score = (cos + 1)/2 applied after the ordering; kk distinct indices
+ * always.  The cosines ordered come from the branch sert_scorer_cosines takes (exact_dot32 for a bf16-prefiltered table, the
+ * fp32 GEMM otherwise), in launches of at most 512 rows, so for kk > 1024 the call with k is the head of the call with -1 by
+ * construction.  They are sert_scorer_cosines' bit for bit as long as that call's block stays on the fp32 GEMM kernels: not
+ * for d_e >= 256 with 1024 queries or more in a block (nor from 16 384 queries at any d_e), where its GEMM runs on the
+ * split-bf16 kernels and entities within a rounding of each other can be ordered differently by the two.  kk <= 1024 IS sert_scorer_topk(kk) (and carries its caveat for a bf16-prefiltered table, see
+ * sert_scorer_cosines); above, V_e <= 8192 sorts each query in one workgroup's LDS, larger tables by stable counting-sort
+ * passes (csrc/kernels_score_rank.h).  Queries are cut into chunks whose device footprint fits SERT_SCORE_RANK_BUDGET bytes
+ * (default 2 GiB; at least one query); a chunk's results travel to the host while the next chunk is sorted.  For kk > 1024 a
+ * query's result does not depend on the chunking or on the other queries of the call.  The kk <= 1024 path is cut by the
+ * same budget into sert_scorer_topk calls: it equals one sert_scorer_topk of the whole block when it is one chunk, and
+ * otherwise as far as sert_scorer_topk's own GEMM does not change kernels with the row count (it does for d_e >= 256 at
+ * 1024 rows). */
+int sert_scorer_rank(sert_scorer* s, const float* proj, int64_t num_queries, int32_t k,
+                     int32_t* idx_out, float* score_out);
+
+/* All scores (no selection): score_out (Q, V_e) f32 = (cos + 1)/2.  Not a ranking: (cos + 1)/2 is not injective in fp32,
+ * so whoever needs the order asks sert_scorer_rank (or orders sert_scorer_cosines, below). */
 int sert_scorer_scores(sert_scorer* s, const float* proj, int64_t num_queries, float* score_out);
 
 /* All cosines (no selection, no (cos + 1)/2): cos_out (Q, V_e) f32, bit for bit the values sert_scorer_topk orders by and
  * derives its scores from on this table.  (cos + 1)/2 is not injective in fp32 -- two cosines below 0.5 in magnitude can
- * share a score -- so a caller that ranks every entity sorts THESE, under the order of sert_scorer_topk (descending, -0
- * equal to +0, NaN after every number, ties by lowest entity index), and applies (cos + 1)/2 afterwards: the first k of that
- * ranking are then sert_scorer_topk's k -- exactly for V_e < 32768 and under SERT_SCORE_FP32=1.  For a bf16-prefiltered table
+ * share a score -- so sert_scorer_rank, and a caller that ranks on the host, sorts THESE, under the order of sert_scorer_topk
+ * (descending, -0 equal to +0, NaN after every number, ties by lowest entity index), and applies (cos + 1)/2 afterwards: the
+ * first k of that ranking are then sert_scorer_topk's k -- exactly for V_e < 32768 and under SERT_SCORE_FP32=1.  For a bf16-prefiltered table
  * the cosines are the exact_dot32 ones; a row the fused path hands to the materialising path, every row of a table whose
  * prefilter was demoted and every row under SERT_SCORE_MATERIALISE=1 pick their k entities on the GEMM's cosines before
  * they are re-scored, so two entities within an fp32 rounding of each other across rank k can swap between the two.

@@ -47,6 +47,20 @@ int sert_debug_scorer_counts(sert_scorer* s, int64_t* out, int n);
 int sert_debug_scorer_select(int device, int mode, const float* S, int64_t num_queries, int32_t V, int32_t k, float thr,
                              int32_t* idx_out, float* score_out);
 
+/* Which path the rows of a scorer's sert_scorer_rank calls took since sert_scorer_create -- host counters, test hook: out[0]
+ * calls, out[1] their query chunks (SERT_SCORE_RANK_BUDGET; at most 2048 queries and fewer than 2^31 elements per sorted
+ * chunk), rows ranked by out[2] the top-k path (kk <= 1024), out[3] the LDS sort (V_e <= 8192), out[4] the counting-sort
+ * passes, out[5] microseconds the copies of the results to the host took on the scorer's second stream, between events
+ * recorded around them (LDS and counting-sort rows only: the top-k path copies inside sert_scorer_topk).  n <= 6. */
+int sert_debug_scorer_rank_counts(sert_scorer* s, int64_t* out, int n);
+
+/* Test hook: the ranking kernels of sert_scorer_rank on cosines the caller provides, S (Q, V) f32 host -- the only way to
+ * feed them -0, NaNs of both signs and infinities.  The path goes by V alone: the LDS sort up to 8192, the counting-sort
+ * passes above (Q <= 2048 and Q V < 2^31 there); the top-k kernels have sert_debug_scorer_select.  k = -1 or positive, ranked
+ * depth kk as sert_scorer_rank.  idx_out / score_out (Q, kk): entity and (cos + 1)/2. */
+int sert_debug_scorer_rank_select(int device, const float* S, int64_t num_queries, int32_t V, int32_t k, int32_t* idx_out,
+                                  float* score_out);
+
 /* Test hook: overwrite the step's gradient scratch -- the flat buffer [g_Rw | g_Re | g_W | g_b | loss, sum of squares] with
  * quiet NaNs, the per-entity sorted-run bounds behind it with the wrong run [0, 1) -- after waiting for the device.  A step
  * whose negatives were drawn ahead launches NO prologue (nothing is zeroed): it relies on every value it reads having been

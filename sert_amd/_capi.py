@@ -35,12 +35,12 @@ EXPORTS = [
     'sert_eval_batch', 'sert_eval_batches',
     'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_score_topk',
     'sert_reval_create', 'sert_reval_run', 'sert_reval_destroy',
-    'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_scores', 'sert_scorer_cosines',
+    'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_rank', 'sert_scorer_scores', 'sert_scorer_cosines',
     'sert_host_alloc', 'sert_host_free',
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 
@@ -129,6 +129,7 @@ def load():
     lib.sert_scorer_create.argtypes = [ctypes.c_int, fp, i64, i32, ctypes.POINTER(vp)]
     lib.sert_scorer_destroy.argtypes = [vp]
     lib.sert_scorer_topk.argtypes = [vp, fp, i64, i32, fp, fp]
+    lib.sert_scorer_rank.argtypes = [vp, fp, i64, i32, fp, fp]
     lib.sert_scorer_scores.argtypes = [vp, fp, i64, fp]
     lib.sert_scorer_cosines.argtypes = [vp, fp, i64, fp]
     lib.sert_host_alloc.argtypes = [ctypes.POINTER(vp), sz]
@@ -525,6 +526,22 @@ def debug_scorer_select(cosines, k, mode, thr=-np.inf, device=0):
     return idx, val
 
 
+def debug_scorer_rank_select(cosines, k=None, device=0):
+    """sert_debug_scorer_rank_select (test hook): the ranking kernels of sert_scorer_rank on caller-provided cosines (Q, V) --
+    the LDS sort for V <= 8192, the counting-sort passes above.  (idx, score), (Q, kk)."""
+    s = np.ascontiguousarray(cosines, dtype=np.float32)
+    assert s.ndim == 2
+    keep = s.shape[1] if k is None else min(int(k), s.shape[1])
+    idx = np.empty((s.shape[0], keep), dtype=np.int32)
+    val = np.empty((s.shape[0], keep), dtype=np.float32)
+    lib = load()
+    lib.sert_debug_scorer_rank_select.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.c_void_p, ctypes.c_void_p]
+    check(lib.sert_debug_scorer_rank_select(device, s.ctypes.data, s.shape[0], s.shape[1], -1 if k is None else int(k),
+                                            idx.ctypes.data, val.ctypes.data))
+    return idx, val
+
+
 class Scorer(object):
     """Persistent device copy of the (L2-normalised) entity table + top-k scoring
     (sert_scorer_* in include/sert_hip.h).
@@ -597,23 +614,42 @@ class Scorer(object):
         check(self._lib.sert_debug_scorer_counts(self._h, v, 6))
         return [int(x) for x in v]
 
-    def rank(self, projections, k=None):
+    def debug_rank_counts(self):
+        """sert_debug_scorer_rank_counts (test hook): [rank calls that reached the library, their query chunks, rows ranked by
+        the top-k path, by the LDS sort, by the counting-sort passes, microseconds the copies of the two sorts' results took
+        on the second stream]."""
+        v = (ctypes.c_int64 * 6)()
+        self._lib.sert_debug_scorer_rank_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+        check(self._lib.sert_debug_scorer_rank_counts(self._h, v, 6))
+        return [int(x) for x in v]
+
+    def rank(self, projections, k=None, on_device=True):
         """(idx, score) per query, best first; k=None ranks every entity.  One order whatever k: the cosine descending
-        (-0 equal to +0), NaN after every number, ties by lowest entity index -- so rank(p, k) is the head of rank(p)."""
+        (-0 equal to +0), NaN after every number, ties by lowest entity index -- so rank(p, k) is the head of rank(p).
+        k <= min(V_e, 1024) is topk() (views of the scorer's page-locked buffers); everything else is ranked on the device by
+        sert_scorer_rank into ordinary arrays of the caller's (a 10 000 x 100 000 ranking is 8 GB: not to be page-locked).
+        on_device=False: the same ranking by ordering sert_scorer_cosines on the host (the comparison path of the tests and
+        of tools/score_rank_bench.py)."""
+        if k is not None and k <= 0:
+            raise SertError('Scorer.rank: k must be None (every entity) or positive')
         if k is not None and k <= min(self.num_entities, 1024):
             return self.topk(projections, k)
-        # no device top-k for this k: full score rows, a bounded number of queries at a time
-        # (the reference scores one query at a time, query.py:304-318; 10k queries x 100k
-        # entities in one block would be 4 GB of host memory)
-        p = np.asarray(projections, dtype=np.float32)
+        p = np.ascontiguousarray(projections, dtype=np.float32)
         if p.ndim == 1:
             p = p.reshape(1, -1)
+        assert p.shape[1] == self.dim
         keep = self.num_entities if k is None else min(k, self.num_entities)
-        step = max(1, self.MAX_HOST_SCORES // self.num_entities)
         idx = np.empty((p.shape[0], keep), dtype=np.int32)
         val = np.empty((p.shape[0], keep), dtype=np.float32)
+        if on_device:
+            check(self._lib.sert_scorer_rank(self._h, p.ctypes.data, p.shape[0], -1 if k is None else int(k), idx.ctypes.data,
+                                             val.ctypes.data))
+            return idx, val
+        # full cosine rows, a bounded number of queries at a time (the reference scores one query at a time,
+        # query.py:304-318; 10k queries x 100k entities in one block would be 4 GB of host memory)
+        step = max(1, self.MAX_HOST_SCORES // self.num_entities)
         for lo in range(0, p.shape[0], step):
-            # the device orders the COSINE; (cos + 1)/2 maps several cosines to one score, so the score is applied after
+            # the COSINE is ordered; (cos + 1)/2 maps several cosines to one score, so the score is applied after
             # the sort.  -cos + 0: -0 and +0 become one value; NaN sorts last in numpy; stable: lowest index first
             cos = self.cosines(p[lo:lo + step])
             order = np.argsort(-cos + np.float32(0), axis=1, kind='stable')[:, :keep]

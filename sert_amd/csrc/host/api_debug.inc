@@ -87,6 +87,41 @@ int sert_debug_scorer_select(int device, int mode, const float* S, int64_t Q, in
     return rc;
 }
 
+int sert_debug_scorer_rank_counts(sert_scorer* sc, int64_t* out, int n) {
+    if (!sc || !out || n < 1 || n > 6) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = sc->rank_counts[i];
+    return 0;
+}
+
+int sert_debug_scorer_rank_select(int device, const float* S, int64_t Q, int32_t V, int32_t k, int32_t* idx_out, float* score_out) {
+    if (!S || !idx_out || !score_out || Q <= 0 || V <= 0 || k == 0 || k < -1) SERT_FAIL("bad argument");
+    const int kk = (k < 0 || k >= V) ? V : k;
+    const int mode = V <= kLLRankLdsMax ? SCORE_RANK_LDS : SCORE_RANK_CSORT;
+    const int64_t n = Q * (int64_t)V;
+    if (mode == SCORE_RANK_CSORT && (Q > kSortMaxBins || n > ((int64_t)1 << 31) - ((int64_t)1 << 20)))
+        SERT_FAIL("too many queries x entities for one sorted chunk");
+    SERT_HIP(hipSetDevice(device));
+    float* dS = nullptr; float* dval = nullptr; int32_t* didx = nullptr; int32_t* dkeys = nullptr; int32_t* dhist = nullptr;
+    auto body = [&]() -> int {
+        SERT_TRY(dmalloc(&dS, (size_t)n));
+        SERT_TRY(dmalloc(&dval, (size_t)Q * kk));
+        SERT_TRY(dmalloc(&didx, (size_t)Q * kk));
+        if (mode == SCORE_RANK_CSORT) {
+            SERT_TRY(dmalloc(&dkeys, (size_t)4 * n));
+            SERT_TRY(dmalloc(&dhist, (size_t)score_rank_hist_ints(n)));
+        }
+        SERT_HIP(hipMemcpy(dS, S, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        SERT_TRY(score_rank_sort(0, mode, dS, (int)Q, (int)V, kk, dkeys, dhist, didx, dval));
+        SERT_HIP(hipDeviceSynchronize());
+        SERT_HIP(hipMemcpy(idx_out, didx, (size_t)Q * kk * sizeof(int32_t), hipMemcpyDeviceToHost));
+        SERT_HIP(hipMemcpy(score_out, dval, (size_t)Q * kk * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = body();
+    (void)hipFree(dS); (void)hipFree(dval); (void)hipFree(didx); (void)hipFree(dkeys); (void)hipFree(dhist);
+    return rc;
+}
+
 int sert_debug_row_lists(const uint32_t* allbits, int world, int rank, int64_t num_batches, int64_t bit_words,
                          int64_t rows_per_rank, int64_t vocab, int64_t batch, int32_t* serve_cnt, int32_t* fetch_cnt,
                          int32_t* serve_rows, int32_t* fetch_rows, int32_t* union_rows, int32_t* ptr, int32_t* ent,

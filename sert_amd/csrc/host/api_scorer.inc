@@ -65,6 +65,13 @@ int sert_scorer_destroy(sert_scorer* sc) {
     (void)hipFree(sc->Ss); (void)hipFree(sc->thr); (void)hipFree(sc->cand); (void)hipFree(sc->cnt);
     (void)hipFree(sc->nflag); (void)hipFree(sc->flag_list); (void)hipFree(sc->Pc); (void)hipFree(sc->idx_c);
     (void)hipFree(sc->val_c); (void)hipFree(sc->E16); (void)hipFree(sc->P16);
+    (void)hipFree(sc->rP); (void)hipFree(sc->rS); (void)hipFree(sc->rkeys); (void)hipFree(sc->rhist);
+    for (int b = 0; b < 2; ++b) {
+        (void)hipFree(sc->ridx[b]); (void)hipFree(sc->rval[b]);
+        if (sc->ev_rsorted[b]) (void)hipEventDestroy(sc->ev_rsorted[b]);
+        if (sc->ev_rcopy0[b]) (void)hipEventDestroy(sc->ev_rcopy0[b]);
+        if (sc->ev_rcopied[b]) (void)hipEventDestroy(sc->ev_rcopied[b]);
+    }
     if (sc->ev_ready) (void)hipEventDestroy(sc->ev_ready);
     if (sc->ev_done) (void)hipEventDestroy(sc->ev_done);
     if (sc->stream2) (void)hipStreamDestroy(sc->stream2);
@@ -357,6 +364,19 @@ int sert_scorer_topk(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
     return scorer_topk_io(sc, proj, Q, k, idx_out, score_out, false);
 }
 
+// S (qn, V) = the cosines of qn normalised projections P against the table, on stream st: the exact_dot32 ones (`exact`: what
+// the top-k of a bf16-prefiltered table reports) or the GEMM's.  The one place sert_scorer_scores, sert_scorer_cosines and
+// sert_scorer_rank fill a slab, so the three agree bit for bit.
+static void scorer_cosine_slab(sert_scorer* sc, hipStream_t st, const float* P, int64_t qn, float* S, bool exact) {
+    const int64_t V = sc->V;
+    const int dim = sc->dim;
+    if (exact)
+        hipLaunchKernelGGL(exact_cosine_rows, dim3((unsigned)std::min<int64_t>(cdiv(V, 8), 1024), (unsigned)qn), dim3(256), 0, st,
+                           P, sc->E, V, dim, S);
+    else
+        launch_gemm<false, true, EPI_STORE>(st, P, sc->E, S, nullptr, (int)qn, (int)V, dim, dim, dim, (int)V);
+}
+
 // every entity's value for Q queries: (cos + 1)/2 of the GEMM's cosine, or (raw) the cosine itself AS sert_scorer_topk ORDERS
 // AND REPORTS IT -- the exact_dot32 one for a bf16-prefiltered table, the GEMM's otherwise
 static int scorer_all(sert_scorer* sc, const float* proj, int64_t Q, float* score_out, bool raw) {
@@ -381,12 +401,7 @@ static int scorer_all(sert_scorer* sc, const float* proj, int64_t Q, float* scor
     hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
     for (int64_t q0 = 0; q0 < Q; q0 += QT) {
         const int64_t qn = std::min(QT, Q - q0);
-        if (raw && sc->bf16)
-            hipLaunchKernelGGL(exact_cosine_rows, dim3((unsigned)std::min<int64_t>(cdiv(V, 8), 1024), (unsigned)qn), dim3(256), 0, s,
-                               sc->P + q0 * dim, sc->E, V, dim, sc->S);
-        else
-            launch_gemm<false, true, EPI_STORE>(s, sc->P + q0 * dim, sc->E, sc->S, nullptr, (int)qn, (int)V, dim,
-                                                dim, dim, (int)V);
+        scorer_cosine_slab(sc, s, sc->P + q0 * dim, qn, sc->S, raw && sc->bf16);
         if (!raw) hipLaunchKernelGGL(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S, (size_t)(qn * V));
         SERT_HIP(hipMemcpyAsync(score_out + q0 * V, sc->S, (size_t)qn * V * sizeof(float), hipMemcpyDeviceToHost, s));
         SERT_HIP(hipStreamSynchronize(s));

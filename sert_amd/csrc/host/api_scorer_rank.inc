@@ -1,0 +1,210 @@
+// Part of sert_hip.hip (one translation unit; included there, inside its extern "C" block): C ABI: full rankings of the cosine
+// scorer on the device (include/sert_hip.h: sert_scorer_rank; include/sert_hip_debug.h: sert_debug_scorer_rank_*).  Replaces
+// the host ordering of VectorSpaceCallback for --top unset, above 1024 or above the table size (bin/query.py:250-260).
+
+// The slab GEMM runs in launches of at most this many rows.  Every fp32 kernel launch_gemm picks at splits = 1 computes an
+// output element from its own row and column only, with one and the same MFMA sequence over k, so their results agree bit for
+// bit; the split-bf16 kernels (gemm_x3.h) do not, and they take a product of 1024 rows or more.  Below that a chunk's cosines
+// are the fp32 kernels' whatever the number of queries: a query's ranking does not depend on the chunking or on the other
+// queries of the call, and the cosines are those sert_scorer_cosines returns for a block of fewer than 1024 queries.
+static const int kScoreRankRows = 512;
+
+// SERT_SCORE_RANK_BUDGET: device bytes one query chunk of sert_scorer_rank may use (score_rank_bytes)
+static size_t score_rank_budget() {
+    const char* e = knob("SERT_SCORE_RANK_BUDGET");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (size_t)v : ((size_t)2 << 30);
+}
+
+enum { SCORE_RANK_TOPK = 0, SCORE_RANK_LDS = 1, SCORE_RANK_CSORT = 2 };
+
+static int64_t score_rank_hist_ints(int64_t n) { return (int64_t)kSortMaxBins * cdiv(n, kSortTile) + kSortMaxBins; }
+
+// device footprint of a chunk of Qc queries: the slab, the two (Qc, kk) result sets and, for the LSD passes, the four key /
+// value arrays with their histogram and bin totals
+static size_t score_rank_bytes(int mode, int64_t Qc, int64_t V, int kk) {
+    size_t b = (size_t)Qc * V * 4 + (size_t)Qc * kk * 16;
+    if (mode == SCORE_RANK_CSORT) b += (size_t)Qc * V * 16 + (size_t)score_rank_hist_ints(Qc * V) * 4;
+    return b;
+}
+
+// queries per chunk of a call of Q: as many as fit the budget, at least one; a sorted chunk (LSD passes) holds at most
+// kSortMaxBins queries (the query index is one digit) and fewer than 2^31 elements (csort_* index with int; the margin keeps
+// the last tile's and the grid-stride loops' indices below 2^31 as well)
+static int64_t score_rank_chunk_queries(int mode, int64_t Q, int64_t V, int kk) {
+    int64_t hi = Q;
+    if (mode == SCORE_RANK_CSORT) hi = std::min<int64_t>(hi, std::min<int64_t>(kSortMaxBins, (((int64_t)1 << 31) - ((int64_t)1 << 20)) / V));
+    const size_t budget = score_rank_budget();
+    int64_t lo = 1;                       // (bytes grows with Qc: the largest Qc in [1, hi] within the budget)
+    hi = std::max<int64_t>(hi, 1);
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo + 1) / 2;
+        if (score_rank_bytes(mode, mid, V, kk) <= budget) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The ranking kernels on a slab S (Qc, V) of cosines, stream s: the first kk of every row into idx / val (Qc, kk).
+// mode LDS: V <= kLLRankLdsMax.  mode CSORT: keys = four arrays of Qc V int32, hist = score_rank_hist_ints(Qc V) int32.
+static int score_rank_sort(hipStream_t s, int mode, const float* S, int Qc, int V, int kk, int32_t* keys, int32_t* hist,
+                           int32_t* idx, float* val) {
+    if (mode == SCORE_RANK_LDS) {
+        if (V <= 1024)      hipLaunchKernelGGL(score_rank_lds<1024>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        else if (V <= 2048) hipLaunchKernelGGL(score_rank_lds<2048>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        else if (V <= 4096) hipLaunchKernelGGL(score_rank_lds<4096>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        else                hipLaunchKernelGGL(score_rank_lds<kLLRankLdsMax>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+    } else {
+        // score key in 11 + 11 + 10-bit digits over iota values, then the query index: stability keeps, inside a query, the
+        // key order and, among equal keys, the entity order (as ll_rank_chunk)
+        const int n = Qc * V, tiles = cdiv(n, kSortTile);
+        int32_t *ka = keys, *va = keys + (size_t)n, *kb = keys + (size_t)2 * n, *vb = keys + (size_t)3 * n;
+        int32_t* bin_total = hist + (size_t)kSortMaxBins * tiles;
+        auto pass = [&](const int32_t* kin, const int32_t* vin, int32_t* kout, int32_t* vout, int shift, int nb) {
+            hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nb, tiles, hist, (int32_t*)nullptr, 0);
+            hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nb, 4)), dim3(256), 0, s, hist, 1 << nb, tiles, bin_total);
+            hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nb, tiles, hist, bin_total);
+        };
+        hipLaunchKernelGGL(score_rank_keys, dim3(grid_for(n)), dim3(256), 0, s, S, n, ka);
+        pass(ka, nullptr, kb, vb, 0, 11);
+        pass(kb, vb, ka, va, 11, 11);
+        pass(ka, va, kb, vb, 22, 10);
+        int qbits = 1;
+        while ((1 << qbits) < Qc) ++qbits;
+        hipLaunchKernelGGL(ll_query_keys, dim3(grid_for(n)), dim3(256), 0, s, vb, n, V, kb);
+        pass(kb, vb, ka, va, 0, qbits);
+        hipLaunchKernelGGL(score_rank_emit, dim3(grid_for((int64_t)Qc * kk)), dim3(256), 0, s, va, S, Qc, V, kk, idx, val);
+    }
+    SERT_HIP(hipGetLastError());
+    return 0;
+}
+
+// the scratch of a call whose largest chunk holds Qc queries (sert_scorer members r*: nothing the other calls use)
+static int score_rank_scratch(sert_scorer* sc, int mode, int64_t Q, int64_t Qc, int kk) {
+    const int64_t V = sc->V;
+    for (int b = 0; b < 2; ++b) {
+        if (!sc->ev_rsorted[b]) SERT_HIP(hipEventCreateWithFlags(&sc->ev_rsorted[b], hipEventDisableTiming));
+        if (!sc->ev_rcopy0[b]) SERT_HIP(hipEventCreate(&sc->ev_rcopy0[b]));      // (timed: the pair brackets a chunk's copies)
+        if (!sc->ev_rcopied[b]) SERT_HIP(hipEventCreate(&sc->ev_rcopied[b]));
+    }
+    if (sc->cap_rp < Q) {
+        (void)hipFree(sc->rP); sc->rP = nullptr; sc->cap_rp = 0;
+        SERT_TRY(dmalloc(&sc->rP, (size_t)Q * sc->dim));
+        sc->cap_rp = Q;
+    }
+    if (sc->cap_rs < Qc * V) {
+        (void)hipFree(sc->rS); sc->rS = nullptr; sc->cap_rs = 0;
+        SERT_TRY(dmalloc(&sc->rS, (size_t)(Qc * V)));
+        sc->cap_rs = Qc * V;
+    }
+    if (sc->cap_rout < Qc * kk) {
+        for (int b = 0; b < 2; ++b) {
+            (void)hipFree(sc->ridx[b]); (void)hipFree(sc->rval[b]);
+            sc->ridx[b] = nullptr; sc->rval[b] = nullptr;
+        }
+        sc->cap_rout = 0;
+        for (int b = 0; b < 2; ++b) {
+            SERT_TRY(dmalloc(&sc->ridx[b], (size_t)(Qc * kk)));
+            SERT_TRY(dmalloc(&sc->rval[b], (size_t)(Qc * kk)));
+        }
+        sc->cap_rout = Qc * kk;
+    }
+    if (mode == SCORE_RANK_CSORT) {
+        if (sc->cap_rkeys < 4 * Qc * V) {
+            (void)hipFree(sc->rkeys); sc->rkeys = nullptr; sc->cap_rkeys = 0;
+            SERT_TRY(dmalloc(&sc->rkeys, (size_t)(4 * Qc * V)));
+            sc->cap_rkeys = 4 * Qc * V;
+        }
+        const int64_t hn = score_rank_hist_ints(Qc * V);
+        if (sc->cap_rhist < hn) {
+            (void)hipFree(sc->rhist); sc->rhist = nullptr; sc->cap_rhist = 0;
+            SERT_TRY(dmalloc(&sc->rhist, (size_t)hn));
+            sc->cap_rhist = hn;
+        }
+    }
+    return 0;
+}
+
+int sert_scorer_rank(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, int32_t* idx_out, float* score_out) {
+    if (!sc || !proj || !idx_out || !score_out) SERT_FAIL("null argument");
+    if (k == 0 || k < -1) SERT_FAIL("k must be -1 (every entity) or positive");
+    if (Q < 0) SERT_FAIL("bad sizes");
+    if (Q == 0) return 0;
+    const int64_t V = sc->V;
+    const int dim = sc->dim;
+    const int kk = (k < 0 || k >= V) ? (int)V : k;
+    const int mode = kk <= kTopKMax ? SCORE_RANK_TOPK : (V <= kLLRankLdsMax ? SCORE_RANK_LDS : SCORE_RANK_CSORT);
+    const int64_t Qc = score_rank_chunk_queries(mode, Q, V, kk);
+    const int64_t nchunks = cdiv(Q, Qc);
+    sc->rank_counts[0] += 1;
+    if (mode == SCORE_RANK_TOPK) {
+        // sert_scorer_topk itself on every chunk.  One chunk (any call the budget holds whole) is sert_scorer_topk(kk) of the
+        // call; a call the budget cuts equals it as long as that call's own GEMM keeps one kernel family whatever its row
+        // count -- not for d_e >= 256, where a block of 1024 rows or more goes to the split-bf16 kernels and its chunks may not
+        for (int64_t q0 = 0; q0 < Q; q0 += Qc) {
+            const int64_t qn = std::min(Qc, Q - q0);
+            SERT_TRY(scorer_topk_io(sc, proj + q0 * dim, qn, kk, idx_out + q0 * kk, score_out + q0 * kk, false));
+            sc->rank_counts[1] += 1; sc->rank_counts[2] += qn;
+        }
+        return 0;
+    }
+    SERT_HIP(hipSetDevice(sc->device));
+    SERT_TRY(score_rank_scratch(sc, mode, Q, Qc, kk));
+    hipStream_t s = sc->stream, s2 = sc->stream2;
+    double copy_ms = 0.0;
+    bool timed[2] = {false, false};
+    // the time the copies of result set b took on the second stream, between the two events around them
+    auto harvest = [&](int b) -> int {
+        if (!timed[b]) return 0;
+        float ms = 0.f;
+        SERT_HIP(hipEventSynchronize(sc->ev_rcopied[b]));
+        SERT_HIP(hipEventElapsedTime(&ms, sc->ev_rcopy0[b], sc->ev_rcopied[b]));
+        copy_ms += ms;
+        timed[b] = false;
+        return 0;
+    };
+    // chunk c's results to the caller's arrays on the second stream, behind its sort (a pageable destination: the call
+    // returns when the bytes have arrived -- the next chunk's sort, enqueued before, runs meanwhile)
+    auto copy_out = [&](int64_t c) -> int {
+        const int b = (int)(c & 1);
+        const int64_t q0 = c * Qc, qn = std::min(Qc, Q - q0);
+        SERT_TRY(harvest(b));                                     // (chunk c - 2's copies: long done)
+        SERT_HIP(hipStreamWaitEvent(s2, sc->ev_rsorted[b], 0));
+        SERT_HIP(hipEventRecord(sc->ev_rcopy0[b], s2));
+        SERT_HIP(hipMemcpyAsync(idx_out + q0 * kk, sc->ridx[b], (size_t)qn * kk * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+        SERT_HIP(hipMemcpyAsync(score_out + q0 * kk, sc->rval[b], (size_t)qn * kk * sizeof(float), hipMemcpyDeviceToHost, s2));
+        SERT_HIP(hipEventRecord(sc->ev_rcopied[b], s2));
+        timed[b] = true;
+        return 0;
+    };
+    auto body = [&]() -> int {
+        SERT_HIP(hipMemcpyAsync(sc->rP, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->rP, Q, dim);
+        for (int64_t c = 0; c < nchunks; ++c) {
+            const int b = (int)(c & 1);
+            const int64_t q0 = c * Qc, qn = std::min(Qc, Q - q0);
+            if (c >= 2) SERT_HIP(hipStreamWaitEvent(s, sc->ev_rcopied[b], 0));      // (chunk c - 2 has left this result set)
+            for (int64_t r0 = 0; r0 < qn; r0 += kScoreRankRows)
+                scorer_cosine_slab(sc, s, sc->rP + (q0 + r0) * dim, std::min<int64_t>(kScoreRankRows, qn - r0), sc->rS + (size_t)r0 * V, sc->bf16);
+            SERT_TRY(score_rank_sort(s, mode, sc->rS, (int)qn, (int)V, kk, sc->rkeys, sc->rhist, sc->ridx[b], sc->rval[b]));
+            SERT_HIP(hipEventRecord(sc->ev_rsorted[b], s));
+            if (c >= 1) SERT_TRY(copy_out(c - 1));
+            sc->rank_counts[1] += 1; sc->rank_counts[mode == SCORE_RANK_LDS ? 3 : 4] += qn;
+        }
+        SERT_TRY(copy_out(nchunks - 1));
+        SERT_HIP(hipStreamSynchronize(s2));
+        SERT_HIP(hipStreamSynchronize(s));
+        SERT_TRY(harvest(0));
+        SERT_TRY(harvest(1));
+        return 0;
+    };
+    const int rc = body();
+    if (rc != 0) {      // nothing of this call stays queued: the next one reuses the scratch, and the caller its arrays
+        const std::string keep = g_last_error;
+        (void)hipStreamSynchronize(s2);
+        (void)hipStreamSynchronize(s);
+        g_last_error = keep;
+        return rc;
+    }
+    sc->rank_counts[5] += (int64_t)(copy_ms * 1000.0);
+    return 0;
+}

@@ -31,6 +31,7 @@
 #include "kernels_opt.h"
 #include "kernels_reval.h"
 #include "kernels_score.h"
+#include "kernels_score_rank.h"
 #include "kernels_seg.h"
 #include "kernels_sort.h"
 #include "kernels_vs.h"
@@ -286,6 +287,8 @@ extern "C" {
 #include "host/api_scorer.inc"
 
 #include "host/api_ll_rank.inc"
+
+#include "host/api_scorer_rank.inc"
 
 #include "host/api_reval.inc"
 
