@@ -318,7 +318,7 @@ int sert_scorer_topk(sert_scorer* s, const float* proj, int64_t num_queries, int
  * for d_e >= 256 with 1024 queries or more in a block (nor from 16 384 queries at any d_e), where its GEMM runs on the
  * split-bf16 kernels and entities within a rounding of each other can be ordered differently by the two.  kk <= 1024 IS sert_scorer_topk(kk) (and carries its caveat for a bf16-prefiltered table, see
  * sert_scorer_cosines); above, V_e <= 8192 sorts each query in one workgroup's LDS, larger tables by stable counting-sort
- * passes (csrc/kernels_score_rank.h).  Queries are cut into chunks whose device footprint fits SERT_SCORE_RANK_BUDGET bytes
+ * passes (csrc/kernels_rank.h).  Queries are cut into chunks whose device footprint fits SERT_SCORE_RANK_BUDGET bytes
  * (default 2 GiB; at least one query); a chunk's results travel to the host while the next chunk is sorted.  For kk > 1024 a
  * query's result does not depend on the chunking or on the other queries of the call.  The kk <= 1024 path is cut by the
  * same budget into sert_scorer_topk calls: it equals one sert_scorer_topk of the whole block when it is one chunk, and

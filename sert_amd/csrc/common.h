@@ -232,6 +232,10 @@ __device__ __forceinline__ uint32_t score_key(float f) {
     const uint32_t u = __float_as_uint(f);
     return u == 0x80000000u ? 0x7fffffffu : desc_key(f);
 }
+// the key a row is ordered by (topk_rows, kernels_score.h; the full rankings, kernels_rank.h): the scorer's (score_key: -0
+// ties with +0, NaN last) or, RAW, the loglinear ranker's plain one
+template <bool RAW>
+__device__ __forceinline__ uint32_t rank_key(float x) { return RAW ? desc_key(x) : score_key(x); }
 // the same on a key that desc_key made of a number (the fp32 filter's lists hold no NaN: `v >= thr` is false for one)
 __device__ __forceinline__ uint32_t score_key_of_desc_key(uint32_t k) { return k == 0x80000000u ? 0x7fffffffu : k; }
 

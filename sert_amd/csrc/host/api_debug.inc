@@ -96,29 +96,26 @@ int sert_debug_scorer_rank_counts(sert_scorer* sc, int64_t* out, int n) {
 int sert_debug_scorer_rank_select(int device, const float* S, int64_t Q, int32_t V, int32_t k, int32_t* idx_out, float* score_out) {
     if (!S || !idx_out || !score_out || Q <= 0 || V <= 0 || k == 0 || k < -1) SERT_FAIL("bad argument");
     const int kk = (k < 0 || k >= V) ? V : k;
-    const int mode = V <= kLLRankLdsMax ? SCORE_RANK_LDS : SCORE_RANK_CSORT;
+    const int mode = V <= kRankLdsMax ? RANK_LDS : RANK_CSORT;
     const int64_t n = Q * (int64_t)V;
-    if (mode == SCORE_RANK_CSORT && (Q > kSortMaxBins || n > ((int64_t)1 << 31) - ((int64_t)1 << 20)))
-        SERT_FAIL("too many queries x entities for one sorted chunk");
+    if (mode == RANK_CSORT && !rank_chunk_fits(Q, V)) SERT_FAIL("too many queries x entities for one sorted chunk");
     SERT_HIP(hipSetDevice(device));
-    float* dS = nullptr; float* dval = nullptr; int32_t* didx = nullptr; int32_t* dkeys = nullptr; int32_t* dhist = nullptr;
+    float* dS = nullptr; float* dval = nullptr; int32_t* didx = nullptr;
+    RankSortScratch r;
     auto body = [&]() -> int {
         SERT_TRY(dmalloc(&dS, (size_t)n));
         SERT_TRY(dmalloc(&dval, (size_t)Q * kk));
         SERT_TRY(dmalloc(&didx, (size_t)Q * kk));
-        if (mode == SCORE_RANK_CSORT) {
-            SERT_TRY(dmalloc(&dkeys, (size_t)4 * n));
-            SERT_TRY(dmalloc(&dhist, (size_t)score_rank_hist_ints(n)));
-        }
+        if (mode == RANK_CSORT) SERT_TRY(rank_scratch_reserve(r, n));
         SERT_HIP(hipMemcpy(dS, S, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        SERT_TRY(score_rank_sort(0, mode, dS, (int)Q, (int)V, kk, dkeys, dhist, didx, dval));
+        SERT_TRY(rank_rows_full(0, mode, /*raw=*/false, dS, (int)Q, (int)V, kk, r, didx, dval));
         SERT_HIP(hipDeviceSynchronize());
         SERT_HIP(hipMemcpy(idx_out, didx, (size_t)Q * kk * sizeof(int32_t), hipMemcpyDeviceToHost));
         SERT_HIP(hipMemcpy(score_out, dval, (size_t)Q * kk * sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     };
     const int rc = body();
-    (void)hipFree(dS); (void)hipFree(dval); (void)hipFree(didx); (void)hipFree(dkeys); (void)hipFree(dhist);
+    (void)hipFree(dS); (void)hipFree(dval); (void)hipFree(didx); rank_scratch_free(r);
     return rc;
 }
 

@@ -15,10 +15,10 @@ static size_t ll_rank_budget() {
     return v > 0 ? (size_t)v : ((size_t)2 << 30);
 }
 
-enum { LL_RANK_TOPK = 0, LL_RANK_LDS = 1, LL_RANK_CSORT = 2 };
+// which kernels rank the joint rows: topk_rows for a proper prefix of up to kTopKMax, a full ranking otherwise (host/rank_rows.inc)
 static int ll_rank_mode(int V, int kk) {
-    if (kk <= kTopKMax && kk < V) return LL_RANK_TOPK;
-    return V <= kLLRankLdsMax ? LL_RANK_LDS : LL_RANK_CSORT;
+    if (kk <= kTopKMax && kk < V) return RANK_TOPK;
+    return V <= kRankLdsMax ? RANK_LDS : RANK_CSORT;
 }
 
 // device scratch of one call, sized for its largest chunk
@@ -28,21 +28,16 @@ struct LLRankScratch {
     int64_t* offs = nullptr;       // chunk-relative query offsets
     float *G = nullptr, *P = nullptr, *J = nullptr, *tok_h = nullptr, *joint_h = nullptr, *val = nullptr;
     int32_t *status = nullptr, *idx = nullptr;
-    int32_t *ka = nullptr, *va = nullptr, *kb = nullptr, *vb = nullptr, *hist = nullptr, *bin_total = nullptr;
+    RankSortScratch sort;          // the LSD passes' (kernels_rank.h)
     bool own_inputs = true;        // false: ids / tok_row / offs point into arrays somebody else owns (sert_reval: uploaded once)
     ~LLRankScratch() {
         if (!own_inputs) ids = nullptr, tok_row = nullptr, offs = nullptr;
         for (void* p : {(void*)ids, (void*)tok_row, (void*)offs, (void*)G, (void*)P, (void*)J, (void*)tok_h, (void*)joint_h,
-                        (void*)val, (void*)status, (void*)idx, (void*)ka, (void*)va, (void*)kb, (void*)vb, (void*)hist,
-                        (void*)bin_total})
+                        (void*)val, (void*)status, (void*)idx})
             (void)hipFree(p);
+        rank_scratch_free(sort);
     }
 };
-
-static size_t ll_rank_sort_bytes(int mode, int64_t n) {
-    if (mode != LL_RANK_CSORT) return 0;
-    return (size_t)n * 16 + (size_t)kSortMaxBins * cdiv(n, kSortTile) * 4;
-}
 
 static int ll_rank_alloc(LLRankScratch& w, int mode, int64_t rows, int64_t T, int64_t Qc, int V, int d, int kk) {
     if (w.own_inputs) {
@@ -58,24 +53,8 @@ static int ll_rank_alloc(LLRankScratch& w, int mode, int64_t rows, int64_t T, in
     SERT_TRY(dmalloc(&w.status, (size_t)Qc));
     SERT_TRY(dmalloc(&w.idx, (size_t)Qc * kk));
     SERT_TRY(dmalloc(&w.val, (size_t)Qc * kk));
-    if (mode == LL_RANK_CSORT) {
-        const size_t n = (size_t)Qc * V;
-        SERT_TRY(dmalloc(&w.ka, n)); SERT_TRY(dmalloc(&w.va, n));
-        SERT_TRY(dmalloc(&w.kb, n)); SERT_TRY(dmalloc(&w.vb, n));
-        SERT_TRY(dmalloc(&w.hist, (size_t)kSortMaxBins * cdiv((int64_t)n, kSortTile)));
-        SERT_TRY(dmalloc(&w.bin_total, (size_t)kSortMaxBins));
-    }
+    if (mode == RANK_CSORT) SERT_TRY(rank_scratch_reserve(w.sort, (int64_t)Qc * V));
     return 0;
-}
-
-// one stable counting-sort digit pass (kernels_sort.h)
-static void ll_rank_sort_pass(hipStream_t s, LLRankScratch& w, const int32_t* kin, const int32_t* vin, int32_t* kout,
-                              int32_t* vout, int n, int shift, int nb) {
-    const int tiles = cdiv(n, kSortTile);
-    hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nb, tiles, w.hist, (int32_t*)nullptr, 0);
-    hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nb, 4)), dim3(256), 0, s, w.hist, 1 << nb, tiles, w.bin_total);
-    hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nb, tiles, w.hist,
-                       w.bin_total);
 }
 
 // the two float32 constants of math_utils.entropy(..., base=2, normalize=True): float(log(2)), float(log(V) / log(2))
@@ -84,33 +63,15 @@ static float ll_log2v_f(int V) { return (float)(log((double)V) / log(2.0)); }
 
 // P holds the chunk's per-token distributions (rows indexed by w.tok_row), w.offs its Qc + 1 query offsets: joint rows,
 // entropies, status and the ranking (w.idx / w.val, Qc x kk) on stream s
-
 static int ll_rank_chunk(hipStream_t s, LLRankScratch& w, const float* P, int Qc, int V, int kk, int mode) {
     hipLaunchKernelGGL(ll_query_aggregate, dim3(Qc), dim3(256), 0, s, P, w.tok_row, w.offs, V, ll_ln2_f(), ll_log2v_f(V),
                        w.J, w.joint_h, w.status);
-    if (mode == LL_RANK_TOPK) {
+    if (mode == RANK_TOPK) {
         hipLaunchKernelGGL(topk_rows<true>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val, (float*)nullptr);
-    } else if (mode == LL_RANK_LDS) {
-        if (V <= 1024)      hipLaunchKernelGGL(ll_rank_lds<1024>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
-        else if (V <= 2048) hipLaunchKernelGGL(ll_rank_lds<2048>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
-        else if (V <= 4096) hipLaunchKernelGGL(ll_rank_lds<4096>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
-        else                hipLaunchKernelGGL(ll_rank_lds<kLLRankLdsMax>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val);
-    } else {
-        // score key in 11 + 11 + 10-bit digits over iota values, then the query index: stability keeps, inside a query,
-        // the score order and, among equal scores, the entity order
-        const int n = Qc * V;
-        hipLaunchKernelGGL(ll_score_keys, dim3(grid_for(n)), dim3(256), 0, s, w.J, n, w.ka);
-        ll_rank_sort_pass(s, w, w.ka, nullptr, w.kb, w.vb, n, 0, 11);
-        ll_rank_sort_pass(s, w, w.kb, w.vb, w.ka, w.va, n, 11, 11);
-        ll_rank_sort_pass(s, w, w.ka, w.va, w.kb, w.vb, n, 22, 10);
-        int qbits = 1;
-        while ((1 << qbits) < Qc) ++qbits;
-        hipLaunchKernelGGL(ll_query_keys, dim3(grid_for(n)), dim3(256), 0, s, w.vb, n, V, w.kb);
-        ll_rank_sort_pass(s, w, w.kb, w.vb, w.ka, w.va, n, 0, qbits);
-        hipLaunchKernelGGL(ll_emit_sorted, dim3(grid_for((int64_t)Qc * kk)), dim3(256), 0, s, w.va, w.J, Qc, V, kk, w.idx, w.val);
+        SERT_HIP(hipGetLastError());
+        return 0;
     }
-    SERT_HIP(hipGetLastError());
-    return 0;
+    return rank_rows_full(s, mode, /*raw=*/true, w.J, Qc, V, kk, w.sort, w.idx, w.val);
 }
 
 static int ll_rank_copy_out(hipStream_t s, LLRankScratch& w, int64_t q0, int Qc, int kk, int32_t* idx_out, float* score_out,
@@ -130,7 +91,7 @@ static int ll_rank_check_offsets(const int64_t* offsets, int64_t Q) {
 }
 
 // How a call's queries are cut into chunks: consecutive queries while distinct rows x V_e + joint rows + sort scratch fit
-// the budget.  bounds[c] .. bounds[c + 1] are the queries of chunk c; max_* size the scratch for the largest chunk.
+// the budget and, for the LSD passes, one sorted chunk (rank_chunk_fits).  bounds[c] .. bounds[c + 1] are the queries of chunk c; max_* size the scratch for the largest chunk.
 struct LLRankPlan {
     std::vector<int64_t> bounds;
     int64_t max_rows = 0, max_tokens = 0, max_queries = 0;
@@ -154,9 +115,11 @@ static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64
     const size_t budget = ll_rank_budget();
     auto bytes = [&](int64_t D, int64_t Qc) -> size_t {
         const size_t rows = (size_t)cdiv(D, kLLRankRows) * kLLRankRows;
-        return rows * ((size_t)d + V + 2) * 4 + (size_t)Qc * ((size_t)V * 4 + (size_t)kk * 8) + ll_rank_sort_bytes(mode, Qc * (int64_t)V);
+        // (the sort scratch without the 8 KiB of its bin totals: they have never been counted, and counting them would move
+        //  the chunk bounds of a given budget)
+        const size_t sort = mode == RANK_CSORT ? rank_scratch_bytes(Qc * (int64_t)V) - (size_t)kSortMaxBins * 4 : 0;
+        return rows * ((size_t)d + V + 2) * 4 + (size_t)Qc * ((size_t)V * 4 + (size_t)kk * 8) + sort;
     };
-    const int64_t q_cap = mode == LL_RANK_CSORT ? std::min<int64_t>(kSortMaxBins, (int64_t)(INT32_MAX / V)) : (int64_t)INT32_MAX;
     std::vector<int64_t>& bounds = plan.bounds;
     bounds.assign(1, 0);
     std::vector<int64_t> chunk_of(c.vocab_size, -1);
@@ -169,7 +132,7 @@ static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64
         const int64_t chunk = (int64_t)bounds.size() - 1;
         int64_t fresh = 0;
         for (int32_t w : qtok) fresh += chunk_of[w] != chunk;
-        if (q > q0 && (q - q0 >= q_cap || bytes(D + fresh, q - q0 + 1) > budget)) {
+        if (q > q0 && ((mode == RANK_CSORT && !rank_chunk_fits(q - q0 + 1, V)) || bytes(D + fresh, q - q0 + 1) > budget)) {
             maxD = std::max(maxD, D); maxQ = std::max(maxQ, q - q0); maxT = std::max(maxT, offsets[q] - offsets[q0]);
             bounds.push_back(q);
             q0 = q; D = 0;
@@ -280,7 +243,7 @@ int sert_debug_ll_rank_distributions(int device, const float* P, const int64_t* 
     const int64_t T = offsets[num_queries];
     const int kk = (k < 0 || k >= V) ? V : k;
     const int mode = ll_rank_mode(V, kk);
-    if (mode == LL_RANK_CSORT && (num_queries > kSortMaxBins || num_queries * (int64_t)V > INT32_MAX))
+    if (mode == RANK_CSORT && !rank_chunk_fits(num_queries, V))
         SERT_FAIL("too many queries x entities for one sorted chunk");
     SERT_HIP(hipSetDevice(device));
     hipStream_t s;

@@ -65,7 +65,7 @@ int sert_scorer_destroy(sert_scorer* sc) {
     (void)hipFree(sc->Ss); (void)hipFree(sc->thr); (void)hipFree(sc->cand); (void)hipFree(sc->cnt);
     (void)hipFree(sc->nflag); (void)hipFree(sc->flag_list); (void)hipFree(sc->Pc); (void)hipFree(sc->idx_c);
     (void)hipFree(sc->val_c); (void)hipFree(sc->E16); (void)hipFree(sc->P16);
-    (void)hipFree(sc->rP); (void)hipFree(sc->rS); (void)hipFree(sc->rkeys); (void)hipFree(sc->rhist);
+    (void)hipFree(sc->rP); (void)hipFree(sc->rS); rank_scratch_free(sc->rsort);
     for (int b = 0; b < 2; ++b) {
         (void)hipFree(sc->ridx[b]); (void)hipFree(sc->rval[b]);
         if (sc->ev_rsorted[b]) (void)hipEventDestroy(sc->ev_rsorted[b]);

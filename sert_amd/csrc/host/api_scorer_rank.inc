@@ -16,66 +16,29 @@ static size_t score_rank_budget() {
     return v > 0 ? (size_t)v : ((size_t)2 << 30);
 }
 
-enum { SCORE_RANK_TOPK = 0, SCORE_RANK_LDS = 1, SCORE_RANK_CSORT = 2 };
+// which kernels rank the rows of a call: topk_rows up to kTopKMax results, a full ranking above (host/rank_rows.inc)
+static int score_rank_mode(int64_t V, int kk) {
+    if (kk <= kTopKMax) return RANK_TOPK;
+    return V <= kRankLdsMax ? RANK_LDS : RANK_CSORT;
+}
 
-static int64_t score_rank_hist_ints(int64_t n) { return (int64_t)kSortMaxBins * cdiv(n, kSortTile) + kSortMaxBins; }
-
-// device footprint of a chunk of Qc queries: the slab, the two (Qc, kk) result sets and, for the LSD passes, the four key /
-// value arrays with their histogram and bin totals
+// device footprint of a chunk of Qc queries: the slab, the two (Qc, kk) result sets and, for the LSD passes, their scratch
 static size_t score_rank_bytes(int mode, int64_t Qc, int64_t V, int kk) {
     size_t b = (size_t)Qc * V * 4 + (size_t)Qc * kk * 16;
-    if (mode == SCORE_RANK_CSORT) b += (size_t)Qc * V * 16 + (size_t)score_rank_hist_ints(Qc * V) * 4;
+    if (mode == RANK_CSORT) b += rank_scratch_bytes(Qc * V);
     return b;
 }
 
-// queries per chunk of a call of Q: as many as fit the budget, at least one; a sorted chunk (LSD passes) holds at most
-// kSortMaxBins queries (the query index is one digit) and fewer than 2^31 elements (csort_* index with int; the margin keeps
-// the last tile's and the grid-stride loops' indices below 2^31 as well)
+// queries per chunk of a call of Q: as many as fit the budget and, for the LSD passes, one sorted chunk (rank_chunk_fits);
+// at least one
 static int64_t score_rank_chunk_queries(int mode, int64_t Q, int64_t V, int kk) {
-    int64_t hi = Q;
-    if (mode == SCORE_RANK_CSORT) hi = std::min<int64_t>(hi, std::min<int64_t>(kSortMaxBins, (((int64_t)1 << 31) - ((int64_t)1 << 20)) / V));
     const size_t budget = score_rank_budget();
-    int64_t lo = 1;                       // (bytes grows with Qc: the largest Qc in [1, hi] within the budget)
-    hi = std::max<int64_t>(hi, 1);
+    int64_t lo = 1, hi = std::max<int64_t>(Q, 1);      // (both conditions are monotone in Qc: the largest Qc in [1, hi] meeting them)
     while (lo < hi) {
         const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (score_rank_bytes(mode, mid, V, kk) <= budget) lo = mid; else hi = mid - 1;
+        if ((mode != RANK_CSORT || rank_chunk_fits(mid, V)) && score_rank_bytes(mode, mid, V, kk) <= budget) lo = mid; else hi = mid - 1;
     }
     return lo;
-}
-
-// The ranking kernels on a slab S (Qc, V) of cosines, stream s: the first kk of every row into idx / val (Qc, kk).
-// mode LDS: V <= kLLRankLdsMax.  mode CSORT: keys = four arrays of Qc V int32, hist = score_rank_hist_ints(Qc V) int32.
-static int score_rank_sort(hipStream_t s, int mode, const float* S, int Qc, int V, int kk, int32_t* keys, int32_t* hist,
-                           int32_t* idx, float* val) {
-    if (mode == SCORE_RANK_LDS) {
-        if (V <= 1024)      hipLaunchKernelGGL(score_rank_lds<1024>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-        else if (V <= 2048) hipLaunchKernelGGL(score_rank_lds<2048>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-        else if (V <= 4096) hipLaunchKernelGGL(score_rank_lds<4096>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-        else                hipLaunchKernelGGL(score_rank_lds<kLLRankLdsMax>, dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-    } else {
-        // score key in 11 + 11 + 10-bit digits over iota values, then the query index: stability keeps, inside a query, the
-        // key order and, among equal keys, the entity order (as ll_rank_chunk)
-        const int n = Qc * V, tiles = cdiv(n, kSortTile);
-        int32_t *ka = keys, *va = keys + (size_t)n, *kb = keys + (size_t)2 * n, *vb = keys + (size_t)3 * n;
-        int32_t* bin_total = hist + (size_t)kSortMaxBins * tiles;
-        auto pass = [&](const int32_t* kin, const int32_t* vin, int32_t* kout, int32_t* vout, int shift, int nb) {
-            hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nb, tiles, hist, (int32_t*)nullptr, 0);
-            hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nb, 4)), dim3(256), 0, s, hist, 1 << nb, tiles, bin_total);
-            hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nb, tiles, hist, bin_total);
-        };
-        hipLaunchKernelGGL(score_rank_keys, dim3(grid_for(n)), dim3(256), 0, s, S, n, ka);
-        pass(ka, nullptr, kb, vb, 0, 11);
-        pass(kb, vb, ka, va, 11, 11);
-        pass(ka, va, kb, vb, 22, 10);
-        int qbits = 1;
-        while ((1 << qbits) < Qc) ++qbits;
-        hipLaunchKernelGGL(ll_query_keys, dim3(grid_for(n)), dim3(256), 0, s, vb, n, V, kb);
-        pass(kb, vb, ka, va, 0, qbits);
-        hipLaunchKernelGGL(score_rank_emit, dim3(grid_for((int64_t)Qc * kk)), dim3(256), 0, s, va, S, Qc, V, kk, idx, val);
-    }
-    SERT_HIP(hipGetLastError());
-    return 0;
 }
 
 // the scratch of a call whose largest chunk holds Qc queries (sert_scorer members r*: nothing the other calls use)
@@ -108,19 +71,7 @@ static int score_rank_scratch(sert_scorer* sc, int mode, int64_t Q, int64_t Qc, 
         }
         sc->cap_rout = Qc * kk;
     }
-    if (mode == SCORE_RANK_CSORT) {
-        if (sc->cap_rkeys < 4 * Qc * V) {
-            (void)hipFree(sc->rkeys); sc->rkeys = nullptr; sc->cap_rkeys = 0;
-            SERT_TRY(dmalloc(&sc->rkeys, (size_t)(4 * Qc * V)));
-            sc->cap_rkeys = 4 * Qc * V;
-        }
-        const int64_t hn = score_rank_hist_ints(Qc * V);
-        if (sc->cap_rhist < hn) {
-            (void)hipFree(sc->rhist); sc->rhist = nullptr; sc->cap_rhist = 0;
-            SERT_TRY(dmalloc(&sc->rhist, (size_t)hn));
-            sc->cap_rhist = hn;
-        }
-    }
+    if (mode == RANK_CSORT) SERT_TRY(rank_scratch_reserve(sc->rsort, Qc * V));
     return 0;
 }
 
@@ -132,11 +83,11 @@ int sert_scorer_rank(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
     const int64_t V = sc->V;
     const int dim = sc->dim;
     const int kk = (k < 0 || k >= V) ? (int)V : k;
-    const int mode = kk <= kTopKMax ? SCORE_RANK_TOPK : (V <= kLLRankLdsMax ? SCORE_RANK_LDS : SCORE_RANK_CSORT);
+    const int mode = score_rank_mode(V, kk);
     const int64_t Qc = score_rank_chunk_queries(mode, Q, V, kk);
     const int64_t nchunks = cdiv(Q, Qc);
     sc->rank_counts[0] += 1;
-    if (mode == SCORE_RANK_TOPK) {
+    if (mode == RANK_TOPK) {
         // sert_scorer_topk itself on every chunk.  One chunk (any call the budget holds whole) is sert_scorer_topk(kk) of the
         // call; a call the budget cuts equals it as long as that call's own GEMM keeps one kernel family whatever its row
         // count -- not for d_e >= 256, where a block of 1024 rows or more goes to the split-bf16 kernels and its chunks may not
@@ -185,10 +136,10 @@ int sert_scorer_rank(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
             if (c >= 2) SERT_HIP(hipStreamWaitEvent(s, sc->ev_rcopied[b], 0));      // (chunk c - 2 has left this result set)
             for (int64_t r0 = 0; r0 < qn; r0 += kScoreRankRows)
                 scorer_cosine_slab(sc, s, sc->rP + (q0 + r0) * dim, std::min<int64_t>(kScoreRankRows, qn - r0), sc->rS + (size_t)r0 * V, sc->bf16);
-            SERT_TRY(score_rank_sort(s, mode, sc->rS, (int)qn, (int)V, kk, sc->rkeys, sc->rhist, sc->ridx[b], sc->rval[b]));
+            SERT_TRY(rank_rows_full(s, mode, /*raw=*/false, sc->rS, (int)qn, (int)V, kk, sc->rsort, sc->ridx[b], sc->rval[b]));
             SERT_HIP(hipEventRecord(sc->ev_rsorted[b], s));
             if (c >= 1) SERT_TRY(copy_out(c - 1));
-            sc->rank_counts[1] += 1; sc->rank_counts[mode == SCORE_RANK_LDS ? 3 : 4] += qn;
+            sc->rank_counts[1] += 1; sc->rank_counts[mode == RANK_LDS ? 3 : 4] += qn;
         }
         SERT_TRY(copy_out(nchunks - 1));
         SERT_HIP(hipStreamSynchronize(s2));

@@ -315,7 +315,6 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
 // Stable sort of the (entity id, pair index) keys of this step: cand -> cand_sorted,
 // iota -> pair_sorted (kernels_sort.h), LSD over ceil(bits/11) digits.
 static int entity_key_sort(sert_model* m, int total, hipStream_t st, const int32_t* keys = nullptr) {
-    const int tiles = cdiv(total, kSortTile);
     const int bits = m->sort_bits;
     const int passes = cdiv(bits, kSortMaxBits);
     const int width = cdiv(bits, passes);
@@ -329,13 +328,8 @@ static int entity_key_sort(sert_model* m, int total, hipStream_t st, const int32
         int32_t* vout = to_final ? m->pair_sorted : m->sort_v_tmp;
         // (first digit: also clears run_start / run_end, which the chunked reduce only writes for entities it meets --
         //  a step whose negatives were drawn ahead has no prologue launch to clear them)
-        hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, st, kin, total, shift, 1 << nb,
-                           tiles, m->sort_hist, p == 0 ? m->run_start : (int32_t*)nullptr,
-                           p == 0 ? (int)(2 * round_up(m->cfg.num_entities, 4)) : 0);
-        hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nb, 4)), dim3(256), 0, st,
-                           m->sort_hist, 1 << nb, tiles, m->sort_bin_total);
-        hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, st, kin, vin, kout, vout,
-                           total, shift, nb, tiles, m->sort_hist, m->sort_bin_total);
+        csort_pass(st, kin, vin, kout, vout, total, shift, nb, m->sort_hist, m->sort_bin_total,
+                   p == 0 ? m->run_start : (int32_t*)nullptr, p == 0 ? (int)(2 * round_up(m->cfg.num_entities, 4)) : 0);
         kin = kout;
         vin = vout;
     }

@@ -1,7 +1,8 @@
 // Batched loglinear query ranking (bin/query.py:199-236 LogLinearCallback.process, sert/inference.py:170-174
 // aggregate_distribution(mode='product')), gfx950.  The per-token distributions come from the predict_fn chain
 // (ll_gather_rows -> launch_gemm<EPI_BIAS> -> ll_softmax_rows, kernels_ll.h), one row per distinct token of a chunk;
-// everything below reads them in place, so the (T, V_e) distributions never leave the device.
+// everything below reads them in place, so the (T, V_e) distributions never leave the device.  The joint rows are ranked by
+// topk_rows<true> (kernels_score.h) or by the full-ranking kernels in their RAW form (kernels_rank.h).
 //
 // Every float32 value here keeps its denormals (HIP's default on gfx950: .amdhsa_float_denorm_mode_32 = 3) and the
 // transcendental calls are the full-precision logf / expf, so a joint in the denormal range is the small number the
@@ -12,7 +13,6 @@
 namespace sert {
 
 enum { kLLRankDevice = 0, kLLRankHost = 1 };     // per-query status (include/sert_hip.h: SERT_LL_STATUS_*)
-constexpr int kLLRankLdsMax = 8192;             // V_e up to this: the whole ranking sorted in one workgroup's LDS
 
 // ---- the host's float32 sums, in the host's order ------------------------------------------------------------------
 // The scores and entropies the reference reports are float32 NumPy / SciPy results (joint.sum(), scipy.stats.entropy
@@ -170,59 +170,6 @@ __global__ __launch_bounds__(256) void ll_query_aggregate(const float* __restric
     __syncthreads();
     const float h = np_entropy_norm2(Jq, V, ln2_f, log2v_f, leaf, csum, &bcast);
     if (tid == 0) { status[q] = kLLRankDevice; joint_h[q] = h; }
-}
-
-// Full ranking of one row of J (V <= N) in LDS: N 64-bit keys (desc_key(score) << 32 | entity), bitonic sort, the first
-// kk written.  Order: score descending, entity index ascending.  N = 8192 is 64 KiB of LDS (two workgroups per CU).
-template <int N>
-__global__ __launch_bounds__(256) void ll_rank_lds(const float* __restrict__ J, int V, int kk, int32_t* __restrict__ idx_out,
-                                                   float* __restrict__ val_out) {
-    __shared__ unsigned long long keys[N];
-    const int tid = threadIdx.x;
-    const float* row = J + (size_t)blockIdx.x * V;
-    int sort_n = 2;
-    while (sort_n < V) sort_n <<= 1;
-    for (int i = tid; i < sort_n; i += 256)
-        keys[i] = i < V ? ((unsigned long long)desc_key(row[i]) << 32) | (uint32_t)i : ~0ull;
-    __syncthreads();
-    for (int size = 2; size <= sort_n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < sort_n / 2; i += 256) {
-                const int lo = 2 * i - (i & (stride - 1));
-                const int hi = lo + stride;
-                const bool up = ((lo & size) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < kk; i += 256) {
-        const unsigned long long kv = keys[i];
-        idx_out[(size_t)blockIdx.x * kk + i] = (int32_t)(uint32_t)kv;
-        val_out[(size_t)blockIdx.x * kk + i] = key_to_float((uint32_t)(kv >> 32));
-    }
-}
-
-// Keys of the LSD passes (kernels_sort.h) for the rankings above kLLRankLdsMax entities:
-//   the order-preserving 32-bit score key of every (query, entity) element ...
-__global__ void ll_score_keys(const float* __restrict__ J, int n, int32_t* __restrict__ keys) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) keys[i] = (int32_t)desc_key(J[i]);
-}
-//   ... then the query index of every element, read from its value (the flat index q V + e)
-__global__ void ll_query_keys(const int32_t* __restrict__ vals, int n, int V, int32_t* __restrict__ keys) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) keys[i] = vals[i] / V;
-}
-// After the passes query q's elements sit at [q V, (q+1) V) in ranking order: its first kk as (entity, score).
-__global__ void ll_emit_sorted(const int32_t* __restrict__ vals, const float* __restrict__ J, int Q, int V, int kk,
-                               int32_t* __restrict__ idx_out, float* __restrict__ val_out) {
-    const size_t total = (size_t)Q * kk;
-    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t q = t / kk, i = t - q * kk;
-        const int32_t v = vals[q * V + i];
-        idx_out[t] = v - (int32_t)(q * V);
-        val_out[t] = J[v];
-    }
 }
 
 }  // namespace sert

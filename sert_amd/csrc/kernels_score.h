@@ -59,10 +59,6 @@ __device__ __forceinline__ void topk_scan_row(const float* __restrict__ row, int
 
 constexpr int kTopKCand = 2048;   // LDS capacity for the threshold-bin candidates
 
-// the key a row is ordered by: the scorer's (score_key: -0 ties with +0, NaN last) or, RAW, the loglinear ranker's plain one
-template <bool RAW>
-__device__ __forceinline__ uint32_t rank_key(float x) { return RAW ? desc_key(x) : score_key(x); }
-
 // Top-k of one row of cosine scores, one workgroup (256 threads) per query.
 //   pass 1 (1 read)  2048-bin histogram of the top 11 bits of the order-preserving
 //                    key -> the bin holding the k-th best score
@@ -76,7 +72,7 @@ __device__ __forceinline__ uint32_t rank_key(float x) { return RAW ? desc_key(x)
 // score = (cos + 1)/2 (query.py:352-357), computed in fp32.
 // thr_out (optional): instead of the (index, score) lists, only the RAW cosine of the
 // k-th best element is written per row (the sampled threshold of the fused path).
-// RAW: emit the score itself instead of (cos + 1)/2 (the loglinear ranking, kernels_ll_rank.h).
+// RAW: emit the score itself instead of (cos + 1)/2 (the loglinear ranking, host/api_ll_rank.inc).
 template <bool RAW>
 __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, int V, int k,
                                                  int32_t* __restrict__ idx_out,

@@ -2,7 +2,8 @@
 // gfx950.  Purpose-built for the entity-gradient keys (kernels_egrad.h):
 // B*(1+z) ~ 10^5..10^6 keys, key range = V_e.  Generic library radix sorts fall
 // back to a ~20-launch merge sort at this size (145 us measured with rocPRIM);
-// this is 3 launches per digit.
+// this is 3 launches per digit (csort_pass, below the kernels).  The full rankings of kernels_rank.h sort through the same
+// passes.
 //
 //   csort_hist      per tile (256 x kSortKpt keys): digit histogram (LDS int atomics: the
 //                   COUNTS are order-independent)        -> hist[bin][tile]
@@ -154,6 +155,16 @@ __global__ __launch_bounds__(256) void csort_scatter(const int32_t* __restrict__
         if (active && (peers & lt_mask) == 0) mine[d] += __popcll(peers);  // group leader
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+// One stable digit pass on stream s: (kin, vin) -> (kout, vout) by bits [shift, shift + nbits) of the key.  hist holds
+// kSortMaxBins x tiles int32, bin_total kSortMaxBins; zero / zero_n: see csort_hist.
+static inline void csort_pass(hipStream_t s, const int32_t* kin, const int32_t* vin, int32_t* kout, int32_t* vout, int n, int shift,
+                              int nbits, int32_t* hist, int32_t* bin_total, int32_t* zero = nullptr, int zero_n = 0) {
+    const int tiles = cdiv(n, kSortTile);
+    hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nbits, tiles, hist, zero, zero_n);
+    hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nbits, 4)), dim3(256), 0, s, hist, 1 << nbits, tiles, bin_total);
+    hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nbits, tiles, hist, bin_total);
 }
 
 }  // namespace sert

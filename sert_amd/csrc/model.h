@@ -6,6 +6,7 @@
 #include "word_index.h"
 #include "kernels_xchg.h"
 #include "kernels_opt.h"   // (TailArgs: a deferred tail is kept by value)
+#include "kernels_rank.h"  // (RankSortScratch: the scorer keeps its ranker's scratch)
 #include "../../include/sert_hip.h"
 #include "../../include/sert_hip_debug.h"   // (test hooks + micro-benchmarks: declared apart from the boundary)
 
@@ -354,13 +355,12 @@ struct sert_scorer {
     // materialising path, [4] rows of calls that went to the materialising path directly
     int64_t path_counts[5] = {0, 0, 0, 0, 0};
     // sert_scorer_rank (host/api_scorer_rank.inc): scratch of its own, grown on demand, so that the cap_* bookkeeping of the
-    // other calls is not disturbed.  rP (Q, dim) normalised projections; rS (Qc, V) the cosine slab of one query chunk; rkeys
-    // the four key / value arrays of the LSD passes (Qc V each) and rhist their histogram + bin totals; ridx / rval two sets of
-    // (Qc, kk) results: chunk i's set travels to the host on stream2 while chunk i + 1 is sorted into the other
+    // other calls is not disturbed.  rP (Q, dim) normalised projections; rS (Qc, V) the cosine slab of one query chunk; rsort
+    // the scratch of the LSD passes (kernels_rank.h); ridx / rval two sets of (Qc, kk) results: chunk i's set travels to the host on stream2 while chunk i + 1 is sorted into the other
     float* rP = nullptr; float* rS = nullptr;
-    int32_t* rkeys = nullptr; int32_t* rhist = nullptr;
+    sert::RankSortScratch rsort;
     int32_t* ridx[2] = {nullptr, nullptr}; float* rval[2] = {nullptr, nullptr};
-    int64_t cap_rp = 0, cap_rs = 0, cap_rkeys = 0, cap_rhist = 0, cap_rout = 0;
+    int64_t cap_rp = 0, cap_rs = 0, cap_rout = 0;
     hipEvent_t ev_rsorted[2] = {nullptr, nullptr}, ev_rcopy0[2] = {nullptr, nullptr}, ev_rcopied[2] = {nullptr, nullptr};
     // [0] sert_scorer_rank calls, [1] their query chunks, rows ranked by [2] the top-k path, [3] the LDS sort, [4] the LSD
     // passes, [5] microseconds the copies of [3] and [4]'s results took on the second stream (sert_debug_scorer_rank_counts)

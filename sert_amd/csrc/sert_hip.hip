@@ -29,9 +29,9 @@
 #include "kernels_ll_rank.h"
 #include "kernels_membench.h"
 #include "kernels_opt.h"
+#include "kernels_rank.h"
 #include "kernels_reval.h"
 #include "kernels_score.h"
-#include "kernels_score_rank.h"
 #include "kernels_seg.h"
 #include "kernels_sort.h"
 #include "kernels_vs.h"
@@ -272,6 +272,8 @@ static void invalidate_speculation(sert_model* m) {
 #include "host/step_softmax_loglinear.inc"
 
 #include "host/optimizer_and_loss.inc"
+
+#include "host/rank_rows.inc"
 
 }  // namespace sert
 

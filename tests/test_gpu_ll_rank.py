@@ -83,6 +83,60 @@ def test_pinned_to_the_reference_golden_vectors(hip_lib):
             np.testing.assert_allclose(th, g['ll_entropies_%d' % i], rtol=1e-5)
 
 
+TIE_LEVELS = np.array([1.0, 2.0, 3.0, 5.0, 8.0], np.float32)
+TIE_OFFSETS = [0, 1, 3, 5]       # three queries of one, two and two tokens
+
+
+def _tied_distributions(V):
+    """(5, V) token rows, every entry one of five positive levels, each row normalised in float32: entities that drew the
+    same levels in a query's tokens go through the same float32 operations and share one joint value, bit for bit."""
+    rng = np.random.RandomState(V)
+    P = TIE_LEVELS[rng.randint(0, TIE_LEVELS.size, (TIE_OFFSETS[-1], V))]
+    return P / P.sum(axis=1, dtype=np.float32, keepdims=True)
+
+
+def _in_tie_runs(values):
+    """How many elements of `values` share their value with another one."""
+    _, counts = np.unique(values, return_counts=True)
+    return int(counts[counts >= 2].sum())
+
+
+@pytest.mark.parametrize('V', [300, 8200])
+def test_full_ranking_orders_ties_by_entity_index(hip_lib, V):
+    """The full ranking of joint rows (k = -1: the in-LDS sort at V = 300, the LSD passes at V = 8200) where whole runs of
+    entities share one joint value: every query is ranked on the device, idx is a permutation, score is non-increasing,
+    idx ascends inside every run of equal score bits, and score[i] is entity idx[i]'s joint value -- the joint row
+    scattered back through idx holds the same values, bit for bit, as the row a call with the queries in reversed order
+    gives.  The inputs put at least half of every query's entities into a tie (checked on the host path's float64 joint
+    and on the device's scores); the scores also meet the comparison rule against the host path."""
+    P = _tied_distributions(V)
+    Q = len(TIE_OFFSETS) - 1
+    idx, score, _, _, status, _ = C.debug_ll_rank_distributions(P, TIE_OFFSETS, None)
+    # the same queries, last first
+    rows = np.concatenate([np.arange(TIE_OFFSETS[q], TIE_OFFSETS[q + 1]) for q in reversed(range(Q))])
+    offs_r = np.concatenate([[0], np.cumsum([TIE_OFFSETS[q + 1] - TIE_OFFSETS[q] for q in reversed(range(Q))])])
+    idx_r, score_r, _, _, status_r, _ = C.debug_ll_rank_distributions(P[rows], offs_r, None)
+    for q in range(Q):
+        dist = P[TIE_OFFSETS[q]:TIE_OFFSETS[q + 1]]
+        L, S = host_log_joint(dist)
+        assert _in_tie_runs(L) >= V / 2, (q, _in_tie_runs(L))
+        assert status[q] == C.LL_STATUS_DEVICE and status_r[Q - 1 - q] == C.LL_STATUS_DEVICE
+        i, s = idx[q].astype(np.int64), score[q]
+        bits = s.view(np.uint32)
+        assert np.array_equal(np.sort(i), np.arange(V))
+        assert np.all(s[1:] <= s[:-1])
+        same = bits[1:] == bits[:-1]
+        assert _in_tie_runs(bits) >= V / 2, (q, _in_tie_runs(bits))
+        assert np.all(i[1:][same] > i[:-1][same])
+        J = np.empty(V, np.float32)
+        J[i] = s
+        J_r = np.empty(V, np.float32)
+        J_r[idx_r[Q - 1 - q].astype(np.int64)] = score_r[Q - 1 - q]
+        assert np.array_equal(np.sort(J.view(np.uint32)), np.sort(J_r.view(np.uint32)))
+        assert np.array_equal(bits, J_r.view(np.uint32)[i])
+        check_ranking(i, s, np.exp(L) / S, *tolerances(dist.shape[0], L, S))
+
+
 def _engine_problem(seed, Vw, Ve, d, Q, T_max):
     rng = np.random.RandomState(seed)
     Rw = rng.uniform(-0.5, 0.5, (Vw, d)).astype(np.float32)
