@@ -144,7 +144,14 @@ int sert_negatives_of_step(sert_model* m, int64_t position, int evaluation, int6
  *   x        (N, n) token ids, id_bytes wide, row-major
  *   y_int    (N,) int32 labels, or NULL when the labels are CSR
  *   csr_*    CSR label matrix (N, V_e) f32 (loglinear without --one_hot_classes,
- *            models.py:66-89 densifies it per batch); NULL when y_int given
+ *            models.py:66-89 densifies it per batch); NULL when y_int given.
+ *            The contract: csr_indptr (N + 1) starts at 0 and does not decrease; the columns of a row
+ *            (csr_indices) lie in [0, V_e) and are STRICTLY INCREASING -- canonical CSR, no duplicate
+ *            column, as scipy's sum_duplicates() leaves it; anything else is refused here (the loss
+ *            kernels add a row's label entries to its gradient from different threads, so two entries
+ *            of one column would race).  A row may hold any number of labels from none (loss 0, no
+ *            gradient) to V_e; the values (csr_data) are arbitrary finite floats -- a stored 0, rows
+ *            that do not sum to 1.
  *   w        (N,) f32 instance weights, NULL = all ones (train split only)
  * In data-parallel mode every rank uploads the rows it owns of every global
  * batch (see sert_amd/distributed.py). */

@@ -31,6 +31,23 @@ int sert_debug_update_counts(sert_model* m, int64_t* out, int n);
  * batch's gather (vs_gather_mean_tail: hinted steps, sert_hint_next_batch).  n <= 2.  (tests/test_gpu_tail_in_gather.py) */
 int sert_debug_tail_counts(sert_model* m, int64_t* out, int n);
 
+/* The loss form the LAST loglinear forward of this model launched (sert_train_batch, sert_eval_batch, ...) -- host record, test
+ * hook, no device is touched: out[0] one of SERT_LL_FORM_*, out[1] its template parameter (WAVE: float4 chunks per lane 1 / 2 /
+ * 4 / 8; TABLE and FUSED_ROW: threads per row 128 / 512; STREAM: 1 = 16-byte rows (V_e % 4 == 0), 0 = scalar rows), out[2] 1 for
+ * the training instance of the form and 0 for the evaluating one, out[3] 1 when the logits were read from the distinct-word
+ * table through the per-token slots, out[4] the segments per row of the streaming form (0 otherwise).  n <= 5; all zero before
+ * the first forward.  tests/test_gpu_ll_csr.py asserts through this that every label structure reaches the kernel it is there
+ * for: a threshold of the dispatch that moves takes the case off its kernel, and the test says so. */
+enum {
+    SERT_LL_FORM_NONE = 0,
+    SERT_LL_FORM_WAVE = 1,       /* ll_row_wave<E>: one wave per row, labels serially on the owner lane */
+    SERT_LL_FORM_TABLE = 2,      /* ll_row_from_table<NT>: per-thread label fix-up list */
+    SERT_LL_FORM_FUSED_ROW = 3,  /* ll_fused_row<TRAIN, NT>: the (n, V_e) slab in LDS, per-thread label fix-up list */
+    SERT_LL_FORM_STREAM = 4,     /* ll_s_*: label fix-ups in memory (ll_s_rowloss, ll_s_labfix) */
+    SERT_LL_FORM_ROWWISE = 5     /* ll_softmax_rows + ll_window (cross-check knob of a variants build) */
+};
+int sert_debug_ll_loss_form(sert_model* m, int32_t* out, int n);
+
 /* Which path the rows of a scorer's sert_scorer_topk calls took since sert_scorer_create -- host counters, test hook: out[0]
  * calls that took the fused path (sampled thresholds, filtering GEMM), out[1] those of them that filtered in bf16, out[2] the
  * query chunks of the fused calls, out[3] rows the fused path flagged and handed to the materialising path, out[4] rows of calls

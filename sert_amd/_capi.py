@@ -25,6 +25,8 @@ T_GRAD_RW, T_GRAD_RE, T_GRAD_W, T_GRAD_B = 12, 13, 14, 15
 T_ACT_H, T_ACT_T, T_ACT_DA, T_ACT_DH, T_ACT_ROWLOSS = 16, 17, 18, 19, 20
 
 COMM_ID_BYTES = 128
+# SERT_LL_FORM_* of include/sert_hip_debug.h, by value
+LL_FORMS = ('none', 'wave', 'table', 'fused_row', 'stream', 'rowwise')
 
 # every symbol include/sert_hip.h declares
 EXPORTS = [
@@ -40,7 +42,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 
@@ -262,6 +264,10 @@ class Engine(object):
             keep.append(y_int)
             y_addr = y_int.ctypes.data
         if csr is not None:
+            # the C ABI takes canonical CSR only (strictly increasing columns per row, include/sert_hip.h): rows that scipy
+            # knows to be unsorted are sorted here; duplicate columns are the caller's to sum (sum_duplicates)
+            if not getattr(csr, 'has_sorted_indices', True):
+                csr = csr.sorted_indices()
             indptr = np.ascontiguousarray(csr.indptr, dtype=np.int64)
             indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
             data = np.ascontiguousarray(csr.data, dtype=np.float32)
@@ -409,6 +415,13 @@ class Engine(object):
         self._lib.sert_debug_tail_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
         check(self._lib.sert_debug_tail_counts(self._h, v, 2))
         return {'alone': int(v[0]), 'in_gather': int(v[1])}
+
+    def ll_loss_form(self):
+        """sert_debug_ll_loss_form (test hook): the loss form the last loglinear forward launched."""
+        v = (ctypes.c_int32 * 5)()
+        self._lib.sert_debug_ll_loss_form.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_ll_loss_form(self._h, v, 5))
+        return {'form': LL_FORMS[int(v[0])], 'param': int(v[1]), 'train': bool(v[2]), 'slots': bool(v[3]), 'segments': int(v[4])}
 
     def timings(self):
         n = self._lib.sert_timing_count(self._h)

@@ -37,6 +37,16 @@ int sert_upload_dataset(sert_model* m, int split, const void* x, const int32_t* 
             const int64_t nnz = csr_indptr[N];
             for (int64_t i = 0; i < nnz; ++i)
                 if (csr_indices[i] < 0 || csr_indices[i] >= Ve) SERT_FAIL("label column out of range [0, num_entities) in csr_indices");
+            // strictly increasing columns per row (include/sert_hip.h): the loss kernels add a row's label entries to dJ from
+            // different threads without atomics -- two entries of one column would race
+            for (int64_t r = 0; r < N; ++r)
+                for (int64_t i = csr_indptr[r] + 1; i < csr_indptr[r + 1]; ++i)
+                    if (csr_indices[i] <= csr_indices[i - 1]) {
+                        char msg[160];
+                        snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
+                                 (long long)r, (int)csr_indices[i]);
+                        SERT_FAIL(msg);
+                    }
         }
     }
     DataSplit& d = m->split[split];

@@ -161,7 +161,10 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     const size_t row0 = (size_t)batch_index * B;
     const int64_t rows = (int64_t)B * n;
     const size_t fused_lds = ((size_t)n * V + V) * sizeof(float);
-    const bool fused = fused_lds <= 150 * 1024 && ds.max_labels_per_row <= 1024;
+    // (the label bound is the capacity of the fused kernels' per-thread fix-up lists, whichever NT is launched below:
+    //  kernels_ll.h, kLlFusedLabels / LlLabelFix)
+    const bool fused = fused_lds <= 150 * 1024 && ds.max_labels_per_row <= kLlFusedLabels;
+    m->ll_form[0] = SERT_LL_FORM_NONE; m->ll_form[1] = 0; m->ll_form[2] = TRAIN ? 1 : 0;
     // Duplicate tokens share their logit row (Z[r,:] = R_w[X[r],:].W + b depends on the word
     // only): in a training step the gather and all three GEMMs run on the batch's DISTINCT
     // words (Zipfian batches: a third of the tokens), the loss kernel reads the table through
@@ -207,7 +210,9 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     const int64_t* indptr = ds.csr_indptr ? ds.csr_indptr + row0 : nullptr;
     const float* w = TRAIN ? ds.w + row0 : nullptr;
     const int32_t* slot = m->ll_dedup ? ds.idx_slots + (size_t)batch_index * rows : nullptr;
-    // fused path: the row's (n, V) slab lives in LDS; CSR rows with > 1024 labels fall back
+    m->ll_form[3] = slot ? 1 : 0;
+    m->ll_form[4] = fused ? 0 : cdiv(V, kLlSeg);
+    // fused path: the row's (n, V) slab lives in LDS; a split with a CSR row of > kLlFusedLabels labels falls back
     if (fused) {
         ScopedTimer t(m, TG_LOSS);
         if (m->ll_dedup)   // the per-token log-softmax, once per distinct word
@@ -220,7 +225,7 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         // 512, 320 at 640 (one wave per token, but only two workgroups fit a CU)
         // (distinct-word mode: the kernel writes dJ_i into J and r_ik into ll_r instead of dL/dZ)
         static const bool slab = variant_knob("SERT_LL_SLAB") != nullptr;   // cross-check knob
-        if (TRAIN && m->ll_dedup && n <= 64 && !slab) {
+        if (TRAIN && m->ll_dedup && n <= kLlTableWindow && !slab) {
             // distinct-word mode: no LDS slab, the n table rows are read once, coalesced along e
             const size_t lds = ((size_t)V + n) * sizeof(float);
             // a row is latency-bound (a handful of barriers), not work-bound: 128-thread workgroups
@@ -230,26 +235,31 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             // up to 2048 entities (V_e % 4 == 0): one WAVE per row, the row in registers, no LDS and no barrier
             static const bool no_wave = variant_knob("SERT_LL_NO_ROW_WAVE") != nullptr;   // cross-check knob
 #define SERT_LL_WAVE(E)                                                                                        \
+    m->ll_form[0] = SERT_LL_FORM_WAVE; m->ll_form[1] = E;                                                       \
     hipLaunchKernelGGL((ll_row_wave<E>), dim3(cdiv(B, 4)), dim3(256), 0, m->stream, (const float*)m->Zu, slot, y, \
                        indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, B, n, V, inv_batch, m->J, m->ll_r)
             // (its row fetches are buffer loads off one descriptor of the table: 32-bit byte offsets)
             if (!no_wave && V % 4 == 0 && V <= 2048 && (size_t)m->ll_U * V * sizeof(float) < ((size_t)1 << 32)) {
                 const int e4 = cdiv(V / 4, 64);
-                if (e4 <= 1) SERT_LL_WAVE(1);
-                else if (e4 <= 2) SERT_LL_WAVE(2);
-                else if (e4 <= 4) SERT_LL_WAVE(4);
-                else SERT_LL_WAVE(8);
+                if (e4 <= 1) { SERT_LL_WAVE(1); }
+                else if (e4 <= 2) { SERT_LL_WAVE(2); }
+                else if (e4 <= 4) { SERT_LL_WAVE(4); }
+                else { SERT_LL_WAVE(8); }
             } else
 #undef SERT_LL_WAVE
-            if (V <= nt128_below)
+            if (V <= nt128_below) {
+                m->ll_form[0] = SERT_LL_FORM_TABLE; m->ll_form[1] = 128;
                 hipLaunchKernelGGL((ll_row_from_table<128>), dim3(B), dim3(128), lds, m->stream, (const float*)m->Zu,
                                    slot, y, indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch,
                                    m->J, m->ll_r);
-            else
+            } else {
+                m->ll_form[0] = SERT_LL_FORM_TABLE; m->ll_form[1] = 512;
                 hipLaunchKernelGGL((ll_row_from_table<512>), dim3(B), dim3(512), lds, m->stream, (const float*)m->Zu,
                                    slot, y, indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch,
                                    m->J, m->ll_r);
+            }
         } else {
+            m->ll_form[0] = SERT_LL_FORM_FUSED_ROW; m->ll_form[1] = 512;
             hipLaunchKernelGGL((ll_fused_row<TRAIN, 512>), dim3(B), dim3(512), fused_lds, m->stream,
                                m->ll_dedup ? m->J : m->Z, (const float*)m->Zu, slot, y, indptr, ds.csr_indices,
                                ds.csr_data, w, m->rowloss, n, V, inv_batch, m->ll_r);
@@ -257,12 +267,14 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     } else if (rowwise) {
         // the plain row-per-workgroup kernels (kept as a cross-check of the streaming path)
         ScopedTimer t(m, TG_LOSS);
+        m->ll_form[0] = SERT_LL_FORM_ROWWISE;
         hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(rows, 4)), dim3(256), 0, m->stream, m->Z, rows,
                            V);
         hipLaunchKernelGGL((ll_window<TRAIN>), dim3(B), dim3(256), 0, m->stream, m->Z, m->J, y,
                            indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch);
     } else {
         ScopedTimer t(m, TG_LOSS);
+        m->ll_form[0] = SERT_LL_FORM_STREAM; m->ll_form[1] = V % 4 == 0 ? 1 : 0;
         if (V % 4 == 0) SERT_TRY((ll_stream_loss<TRAIN, true>(m, ds, row0, y, indptr, w, inv_batch, slot)));
         else            SERT_TRY((ll_stream_loss<TRAIN, false>(m, ds, row0, y, indptr, w, inv_batch, slot)));
     }

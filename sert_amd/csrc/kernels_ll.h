@@ -150,6 +150,22 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
     }
 }
 
+// Labels of one CSR row that the workgroup-per-row loss kernels below (ll_fused_row, ll_row_from_table) take.  A label
+// entry e needs its Q_e dQ_e added to dJ_e AFTER the dense pass has overwritten J, so every thread keeps the entries it
+// met -- labels l0 + tid, l0 + tid + NT, ... -- in registers: kLlFusedLabels / NT of them per thread, NT * that = exactly
+// kLlFusedLabels per row whatever NT is.  ll_forward (host/step_softmax_loglinear.inc) asks THIS constant before it takes
+// the fused forms; a split with a longer row goes to the streaming kernels, which keep the entries in memory (labfix).
+// (ll_row_wave handles its labels serially on the owner lane: no limit.)
+constexpr int kLlFusedLabels = 1024;
+// The longest window the distinct-word training kernels (ll_row_wave, ll_row_from_table) take; ll_forward sends a longer
+// one to ll_fused_row, which sums its J in float64.
+constexpr int kLlTableWindow = 64;
+template <int NT>
+struct LlLabelFix {
+    static_assert(NT > 0 && kLlFusedLabels % NT == 0, "the threads of a row share kLlFusedLabels label entries evenly");
+    static constexpr int kPerThread = kLlFusedLabels / NT;
+};
+
 // Fused per-row loglinear loss: softmax over entities per token, window
 // log-product, renormalisation, clipped cross-entropy and the whole backward to
 // dL/dZ, with the row's (n, V) logit slab held in LDS -- ONE read of Z and ONE
@@ -265,11 +281,23 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
         __syncthreads();
     }
     // 3. window log-product J_e = sum_k log clip(P_ke) and its softmax   models.py:200-210
+    //    A window longer than kLlTableWindow is summed in float64 and rounded once, as the reference sums it (Theano's Sum
+    //    accumulates float32 in float64): n log-probabilities of about -log V_e reach several hundred, where an fp32 ulp
+    //    is 3e-5 and n sequential roundings put 1e-4 of relative error on every Q_e -- inside the gradient bounds, but
+    //    Adadelta's squared-update moment of b multiplies it past its own (measured: 4.8e-4 at n = 65, V_e = 300).
+    //    Shorter windows keep the fp32 sum, bit for bit.
     float mx = -INFINITY;
     for (int e = tid; e < V; e += NT) {
         float a = 0.f;
+        if (n > kLlTableWindow) {
+            double a64 = 0.0;
 #pragma unroll 5
-        for (int k = 0; k < n; ++k) a += fminf(fmaxf(S[(size_t)k * V + e], LOGLO), LOGHI);
+            for (int k = 0; k < n; ++k) a64 += (double)fminf(fmaxf(S[(size_t)k * V + e], LOGLO), LOGHI);
+            a = (float)a64;
+        } else {
+#pragma unroll 5
+            for (int k = 0; k < n; ++k) a += fminf(fmaxf(S[(size_t)k * V + e], LOGLO), LOGHI);
+        }
         Jl[e] = a;
         mx = fmaxf(mx, a);
     }
@@ -300,24 +328,31 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
     sdq = block_sum_n<NW>(sdq, red);
     // 5. dJ_e = Q_e (dQ_e - s): label entries first need the un-overwritten J
     //    -> keep their (e, Q_e dQ_e) in registers, write the dense part, then add
-    float fix_val[4];
-    int fix_e[4];
-    int nfix = 0;
-    bool overflow = false;
-    for (int64_t l = l0 + tid; l < l1; l += NT) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
-        const float q = expf(Jl[e] - mx) / se;
-        const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
-        const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-        if (nfix < 4) { fix_e[nfix] = e; fix_val[nfix] = q * (inside ? -(g * yv) / qc : 0.f); ++nfix; }
-        else overflow = true;
+    //    (trip f of the label loop is entry f: kPerThread trips cover every row the host sends here, LlLabelFix)
+    constexpr int NFIX = LlLabelFix<NT>::kPerThread;
+    float fix_val[NFIX];
+    int fix_e[NFIX];
+#pragma unroll
+    for (int f = 0; f < NFIX; ++f) {
+        const int64_t l = l0 + tid + (int64_t)f * NT;
+        fix_e[f] = -1;
+        fix_val[f] = 0.f;
+        if (l < l1) {
+            const int e = y_int ? y_int[i] : indices[l];
+            const float yv = y_int ? 1.f : data[l];
+            const float q = expf(Jl[e] - mx) / se;
+            const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
+            fix_e[f] = e;
+            fix_val[f] = q * (inside ? -(g * yv) / qc : 0.f);
+        }
     }
-    (void)overflow;   // > 1024 labels on one instance is outside this kernel's contract (host checks)
     __syncthreads();
     for (int e = tid; e < V; e += NT) Jl[e] = -(expf(Jl[e] - mx) / se) * sdq;
     __syncthreads();
-    for (int f = 0; f < nfix; ++f) Jl[fix_e[f]] += fix_val[f];
+#pragma unroll
+    for (int f = 0; f < NFIX; ++f)
+        if (fix_e[f] >= 0) Jl[fix_e[f]] += fix_val[f];
     __syncthreads();
     // 6. per token: dZ_k = P_k (dP_k - <dP_k, P_k>) with dP = dJ*mask/P, i.e.
     //    dZ_ke = mask_ke dJ_e - P_ke r_k,  r_k = sum_e mask_ke dJ_e;  straight to HBM
@@ -456,19 +491,28 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
     float loss = 0.f, sdq = 0.f;
     int64_t l0 = 0, l1 = 1;
     if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
-    float fix_val[4];
-    int fix_e[4];
-    int nfix = 0;
-    for (int64_t l = l0 + tid; l < l1; l += NT) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
-        const float q = expf(Jl[e] - mx) / se;
-        const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
-        loss -= yv * logf(qc);
-        const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-        const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
-        sdq += qdq;
-        if (nfix < 4) { fix_e[nfix] = e; fix_val[nfix] = qdq; ++nfix; }
+    // (trip f of the label loop is entry f of the thread's fix-up list: kPerThread trips cover every row the host sends
+    //  here, LlLabelFix -- 8 at NT = 128, 2 at NT = 512)
+    constexpr int NFIX = LlLabelFix<NT>::kPerThread;
+    float fix_val[NFIX];
+    int fix_e[NFIX];
+#pragma unroll
+    for (int f = 0; f < NFIX; ++f) {
+        const int64_t l = l0 + tid + (int64_t)f * NT;
+        fix_e[f] = -1;
+        fix_val[f] = 0.f;
+        if (l < l1) {
+            const int e = y_int ? y_int[i] : indices[l];
+            const float yv = y_int ? 1.f : data[l];
+            const float q = expf(Jl[e] - mx) / se;
+            const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+            loss -= yv * logf(qc);
+            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
+            const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
+            sdq += qdq;
+            fix_e[f] = e;
+            fix_val[f] = qdq;
+        }
     }
     loss = block_sum_n<NW>(loss, red);
     if (tid == 0) rowloss[i] = wi * loss;
@@ -476,7 +520,9 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
     // 3. dJ_e = Q_e (dQ_e - s): dense part, then the label entries
     for (int e = tid; e < V; e += NT) Jl[e] = -(expf(Jl[e] - mx) / se) * sdq;
     __syncthreads();
-    for (int f = 0; f < nfix; ++f) Jl[fix_e[f]] += fix_val[f];
+#pragma unroll
+    for (int f = 0; f < NFIX; ++f)
+        if (fix_e[f] >= 0) Jl[fix_e[f]] += fix_val[f];
     __syncthreads();
     float tot = 0.f;
     float* dj_out = dJ_out + (size_t)i * V;

@@ -226,6 +226,7 @@ struct sert_model {
     bool ll_dedup = false;        // this step ran on the distinct-word table
     float* ll_rsum = nullptr;     // (U) per-word sums of r_ik
     int ll_U = 0;
+    int32_t ll_form[5] = {0, 0, 0, 0, 0};   // the loss form ll_forward launched last: sert_debug_ll_loss_form (sert_hip_debug.h)
     float* skbuf = nullptr;       // split-K partials of the long-K dX GEMMs (grown on demand)
     size_t skbuf_count = 0;
     // single-GPU vectorspace step: split-K combine + W, b update + loss finalisation as one launch
