@@ -261,6 +261,72 @@ __device__ __forceinline__ float theano_sigmoid(float x) {
     return 1.0f / (1.0f + expf(-x));
 }
 
+// ---- 16-byte WRITE-THROUGH stores (sc1) ---------------------------------------------------------------------------
+// A plain (or nt) store leaves its line dirty in the XCD's L2 until the release at the end of the launch writes every
+// dirty line back in one piece, while the queue does nothing else; an sc1 store sends the line on as it is written and
+// drops it from that L2 (a later reader of the bytes then finds them beyond its XCD's L2).  Which of the step's streaming
+// outputs go out this way is a compile-time choice, one bit of SERT_WT_STORES per kernel family (DESIGN.md section 3;
+// measured with tools/build_variant.sh NAME -DSERT_WT_STORES=0x.. , profiles/r11_experiments.txt).  Same bytes, same
+// values: only the flavour of the store instruction differs.
+//   * Through the buffer-store builtin (cache policy bit 4 = sc1 on gfx94x / gfx95x), so that the compiler tracks the
+//     store in vmcnt: a first version issued it from inline assembly, which let the compiler overwrite the data registers
+//     while the store was still reading them (round 4).
+//   * The descriptor is built from `base`, which must be wave-uniform (a kernel argument: it then lives in SGPRs); the
+//     per-lane byte offset is 32 bits wide, and the descriptor's range is no guard: the CALLER stores only from lanes
+//     that stored before.  store16<BIT> takes any element offset and sends the pieces that lie 2 GiB or more behind
+//     `base` through the plain store, so no shape the library accepts is cut off.
+typedef float sert_wt_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store16_wt(float* base, unsigned byte_off, const float4& v) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0xffffffff, 0x00020000);
+    sert_wt_f4 x = {v.x, v.y, v.z, v.w};
+    __builtin_amdgcn_raw_buffer_store_b128(x, rs, (int)byte_off, 0, /*sc1*/ 1 << 4);
+}
+enum {
+    kWtGather = 0x01,   // vs_gather_mean / vs_gather_mean_tail: H
+    kWtNce = 0x02,      // vs_nce / vs_nce_regs: DA
+    kWtSeg = 0x04,      // the word-gradient tree (kernels_seg.h): final rows, partial rows, the heavy words' partial rows
+    kWtParam = 0x08,    // adam_l2 / dense_update_lazy / dense_update_skip: p
+    kWtState = 0x10,    // ... m and v (in place of their nt stores)
+    kWtEgrad = 0x20,    // egrad_acc: the partial entity-gradient tables (side queue)
+};
+// Default: H and the tree's rows (round 11, C2: -2.5 % per step, every run of the change ahead of every run of the parent,
+// no other record of bench.py --full slower).  Not p (C2 another -0.3 %, inside the noise, and the W3C loglinear settings
+// +1.1 % in every run), not DA (equal), not the partial entity-gradient tables (equal), not m / v (slower than their nt
+// stores: 0.2127 -> 0.2157).  profiles/r11_experiments.txt.
+#ifndef SERT_WT_STORES
+#define SERT_WT_STORES 0x05
+#endif
+// The lane's piece through store16_wt if it lies less than 2 GiB behind `base`; false (nothing stored) otherwise.  The guard
+// is per lane and in the kernel on purpose, not a check on the host: the tables these stores walk may be larger than
+// 2 GiB (the library accepts them), and a host check could only refuse such a model or pick another kernel for it.  Here the
+// far pieces of a large tensor take the store they always took and every piece below 2 GiB is written through; the cost is
+// one compare and a second store form in the kernel (registers: profiles/r11_experiments.txt, item 0).  No shape of the
+// test suite reaches the far side (a tensor of 2 GiB and more); it is the parent's plain store, unchanged.
+__device__ __forceinline__ bool store16_wt_near(float* base, size_t elem_off, const float4& v) {
+    if (elem_off >= ((size_t)1 << 29)) return false;
+    store16_wt(base, (unsigned)elem_off * 4u, v);
+    return true;
+}
+template <int BIT>
+__device__ __forceinline__ void store16(float* base, size_t elem_off, const float4& v) {
+    if constexpr ((SERT_WT_STORES & BIT) != 0) {
+        if (store16_wt_near(base, elem_off, v)) return;
+    }
+    *reinterpret_cast<float4*>(base + elem_off) = v;
+}
+// the optimiser state: streaming (nt) unless its bit asks for write-through; -DSERT_ADAM_NO_NT: plain
+__device__ __forceinline__ void store16_state(float* base, size_t elem_off, const float4& v) {
+    if constexpr ((SERT_WT_STORES & kWtState) != 0) {
+        if (store16_wt_near(base, elem_off, v)) return;
+    }
+#ifndef SERT_ADAM_NO_NT
+    sert_wt_f4 t = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(t, reinterpret_cast<sert_wt_f4*>(base + elem_off));
+#else
+    *reinterpret_cast<float4*>(base + elem_off) = v;
+#endif
+}
+
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 }  // namespace sert

@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void egrad_acc(const int32_t* __restrict__ ent
             const float4 x = rp[((size_t)k * 16 + e) * de4 + c];
             s4.x += x.x; s4.y += x.y; s4.z += x.z; s4.w += x.w;
         }
-        reinterpret_cast<float4*>(partial + ((size_t)g * V + e0 + e) * de)[c] = s4;
+        store16<kWtEgrad>(partial, ((size_t)g * V + e0 + e) * de + 4 * c, s4);
     }
 }
 

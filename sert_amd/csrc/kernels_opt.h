@@ -122,13 +122,10 @@ __global__ __launch_bounds__(256) void adam_l2(float* __restrict__ p, float* __r
         adam_elem(pp.y, gg.y, mm.y, vv.y, a, omb1, omb2, ss, ssn);
         adam_elem(pp.z, gg.z, mm.z, vv.z, a, omb1, omb2, ss, ssn);
         adam_elem(pp.w, gg.w, mm.w, vv.w, a, omb1, omb2, ss, ssn);
-#ifndef SERT_ADAM_NO_NT
-        p4[i] = pp;
-        { nt_f4 t; t.x = mm.x; t.y = mm.y; t.z = mm.z; t.w = mm.w; __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(m) + i); }
-        { nt_f4 t; t.x = vv.x; t.y = vv.y; t.z = vv.z; t.w = vv.w; __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(v) + i); }
-#else
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
-#endif
+        // (p: plain or write-through, m / v: nt, write-through or plain -- store16 / store16_state, common.h)
+        store16<kWtParam>(p, i << 2, pp);
+        store16_state(m, i << 2, mm);
+        store16_state(v, i << 2, vv);
         if (STORE_G) g4[i] = gg;
     }
     if (blockIdx.x == 0 && !bits) {   // (< 4 element tail; a row-filtered table has none)
@@ -364,9 +361,9 @@ __global__ __launch_bounds__(256) void dense_update_lazy(float* __restrict__ p, 
                 adadelta_elem(pp.w, gg.w, mm.w, vv.w, da, omr, ss);
             }
         }
-        p4[i] = pp;
-        { nt_f4 t; t.x = mm.x; t.y = mm.y; t.z = mm.z; t.w = mm.w; __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(s0) + i); }
-        { nt_f4 t; t.x = vv.x; t.y = vv.y; t.z = vv.z; t.w = vv.w; __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(s1) + i); }
+        store16<kWtParam>(p, i << 2, pp);
+        store16_state(s0, i << 2, mm);
+        store16_state(s1, i << 2, vv);
     }
     if (lz.update) {
         const float tot = block_sum_256(ss, red);
@@ -554,9 +551,9 @@ __global__ __launch_bounds__(256, SERT_SKIP_WAVES(CPL)) void dense_update_skip(f
                         adadelta_elem(pp[c].z, gg.z, mm[c].z, vv[c].z, da, omr, s);
                         adadelta_elem(pp[c].w, gg.w, mm[c].w, vv[c].w, da, omr, s);
                     }
-                    p4[i] = pp[c];
-                    { nt_f4 t; t.x = mm[c].x; t.y = mm[c].y; t.z = mm[c].z; t.w = mm[c].w; __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(s0) + i); }
-                    { nt_f4 t; t.x = vv[c].x; t.y = vv[c].y; t.z = vv[c].z; t.w = vv[c].w; __builtin_nontemporal_store(t, reinterpret_cast<nt_f4*>(s1) + i); }
+                    store16<kWtParam>(p, i << 2, pp[c]);
+                    store16_state(s0, i << 2, mm[c]);
+                    store16_state(s1, i << 2, vv[c]);
                 }
             }
             const float rowsum = lane_group_sum<LPR>(s, lane);
@@ -811,9 +808,10 @@ __device__ __forceinline__ void vs_tail_body(const TailArgs& t, const unsigned b
     if (i < count) {
         int s0 = 0;
         // Unroll: J = 4 keeps sixteen loads in flight per thread.  No more than that: the combined kernel's registers are
-        // the larger of its two paths -- as it is, vs_gather_mean_tail takes 68 VGPRs with 32-bit ids and 76 with 8- and
-        // 16-bit ids, two more than vs_gather_mean<., 4> and the same 7 / 6 waves per SIMD; 72 is the step from 7 to 6
-        // (DESIGN.md section 3).
+        // the larger of its two paths -- with plain stores of H (SERT_WT_STORES bit 0x01 off) vs_gather_mean_tail takes 68 VGPRs with 32-bit ids and 76 with 8- and
+        // 16-bit ids, two more than vs_gather_mean<., 4> and the same 7 / 6 waves per SIMD; 72 is the step from 7 to 6.  With the
+        // default's write-through H the kernel asks for seven waves (kernels_vs.h: SERT_GATHER_WAVES) and takes 64 VGPRs, eight
+        // waves, with every id width, against 55 for vs_gather_mean<., 4>.
         constexpr int kTrips = J == 1 ? 8 : 4;
 #pragma unroll kTrips
         for (; s0 + 16 <= t.splits; s0 += 16) {

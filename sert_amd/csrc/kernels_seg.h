@@ -156,12 +156,12 @@ __device__ __forceinline__ void segsum_rows_body(const int bx_, const int by_, c
             a.y = ((lp.y >= LOGLO && lp.y <= LOGHI) ? a.y : 0.f) - __expf(lp.y) * rs;
             a.z = ((lp.z >= LOGLO && lp.z <= LOGHI) ? a.z : 0.f) - __expf(lp.z) * rs;
             a.w = ((lp.w >= LOGLO && lp.w <= LOGHI) ? a.w : 0.f) - __expf(lp.w) * rs;
-            *reinterpret_cast<float4*>(final_dst + o) = a;
+            store16<kWtSeg>(final_dst, o, a);
         } else if (it.z >= 0) {
             a.x /= divisor; a.y /= divisor; a.z /= divisor; a.w /= divisor;
-            *reinterpret_cast<float4*>(final_dst + (size_t)(DST_SLOT ? it.w : it.z) * d + 4 * c) = a;
+            store16<kWtSeg>(final_dst, (size_t)(DST_SLOT ? it.w : it.z) * d + 4 * c, a);
         } else {
-            *reinterpret_cast<float4*>(partial_dst + (size_t)(-(it.z + 1)) * d + 4 * c) = a;
+            store16<kWtSeg>(partial_dst, (size_t)(-(it.z + 1)) * d + 4 * c, a);
         }
     }
 }
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(1024) void segsum_upper_fused(const float* __restri
         if (it.z < 0) return;
         float4 a = sum_rows(it.x, it.y);
         a.x /= divisor; a.y /= divisor; a.z /= divisor; a.w /= divisor;
-        if (on) *reinterpret_cast<float4*>(final_dst + (size_t)it.z * d + 4 * c) = a;
+        if (on) store16<kWtSeg>(final_dst, (size_t)it.z * d + 4 * c, a);
         return;
     }
     const int4 h = heavy[blockIdx.x - nb_normal];     // {first chunk item, chunk items, word, -}
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(1024) void segsum_upper_fused(const float* __restri
             s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w;
         }
         s.x /= divisor; s.y /= divisor; s.z /= divisor; s.w /= divisor;
-        *reinterpret_cast<float4*>(final_dst + (size_t)h.z * d + 4 * c) = s;
+        store16<kWtSeg>(final_dst, (size_t)h.z * d + 4 * c, s);
     }
 }
 
@@ -623,7 +623,7 @@ __device__ __forceinline__ void heavy_rows_body(const int rblk, const int slab, 
             const float4 o = lds[half][h][l];
             float4 a = acc[h];
             a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
-            reinterpret_cast<float4*>(job.part)[((size_t)rblk * kHeavyMax + half * 8 + h) * d4 + ch] = a;
+            store16<kWtSeg>(job.part, (((size_t)rblk * kHeavyMax + half * 8 + h) * d4 + ch) << 2, a);
         }
     }
 }
@@ -650,7 +650,7 @@ __device__ __forceinline__ void heavy_combine_body(const int h, const int slab, 
 #pragma unroll
         for (int q = 1; q < 8; ++q) { const float4 v = lds[q][l]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
         a.x /= divisor; a.y /= divisor; a.z /= divisor; a.w /= divisor;
-        reinterpret_cast<float4*>(final_dst)[(size_t)job.words[h] * d4 + ch] = a;
+        store16<kWtSeg>(final_dst, ((size_t)job.words[h] * d4 + ch) << 2, a);
     }
 }
 
@@ -728,8 +728,8 @@ __device__ __forceinline__ void heavy_rows_body64(const int rblk, const int slab
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
             const float4 o = lds[half][h][lane];
-            reinterpret_cast<float4*>(job.part)[((size_t)rblk * kHeavyMax + half * 8 + h) * d4 + ch] =
-                make_float4(acc2[h][0].x + o.x, acc2[h][0].y + o.y, acc2[h][1].x + o.z, acc2[h][1].y + o.w);
+            store16<kWtSeg>(job.part, (((size_t)rblk * kHeavyMax + half * 8 + h) * d4 + ch) << 2,
+                            make_float4(acc2[h][0].x + o.x, acc2[h][0].y + o.y, acc2[h][1].x + o.z, acc2[h][1].y + o.w));
         }
     }
 }
@@ -764,7 +764,7 @@ __device__ __forceinline__ void heavy_combine_ll_body64(const int h, const int s
         a.y = ((lp.y >= LOGLO && lp.y <= LOGHI) ? a.y : 0.f) - __expf(lp.y) * rs;
         a.z = ((lp.z >= LOGLO && lp.z <= LOGHI) ? a.z : 0.f) - __expf(lp.z) * rs;
         a.w = ((lp.w >= LOGLO && lp.w <= LOGHI) ? a.w : 0.f) - __expf(lp.w) * rs;
-        *reinterpret_cast<float4*>(final_dst + o) = a;
+        store16<kWtSeg>(final_dst, o, a);
     }
 }
 
@@ -817,7 +817,7 @@ __global__ __launch_bounds__(256) void segsum_heavy_combine_ll(const float* __re
         a.y = ((lp.y >= LOGLO && lp.y <= LOGHI) ? a.y : 0.f) - __expf(lp.y) * rs;
         a.z = ((lp.z >= LOGLO && lp.z <= LOGHI) ? a.z : 0.f) - __expf(lp.z) * rs;
         a.w = ((lp.w >= LOGLO && lp.w <= LOGHI) ? a.w : 0.f) - __expf(lp.w) * rs;
-        *reinterpret_cast<float4*>(final_dst + o) = a;
+        store16<kWtSeg>(final_dst, o, a);
     }
 }
 

@@ -21,8 +21,10 @@ __device__ __forceinline__ void vs_gather_mean_body(const IdT* __restrict__ X, c
     const int chunks = d / VEC;
     const int64_t total = (int64_t)B * chunks;
     const float fn = (float)n;
+    // (the wave's first piece, kept in SGPRs beside the lane's own tid: the base of the write-through store below)
+    int64_t tid_w = blk * (int64_t)blockDim.x + __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
     for (int64_t tid = blk * (int64_t)blockDim.x + threadIdx.x; tid < total;
-         tid += (int64_t)nblk * blockDim.x) {
+         tid += (int64_t)nblk * blockDim.x, tid_w += (int64_t)nblk * blockDim.x) {
         const int row = (int)(tid / chunks);
         const int c = (int)(tid - (int64_t)row * chunks) * VEC;
         const IdT* xr = X + (size_t)row * n;
@@ -45,7 +47,13 @@ __device__ __forceinline__ void vs_gather_mean_body(const IdT* __restrict__ X, c
                     if (k0 + q < n) { a.x += v[q].x; a.y += v[q].y; a.z += v[q].z; a.w += v[q].w; }
             }
             a.x /= fn; a.y /= fn; a.z /= fn; a.w /= fn;
-            *reinterpret_cast<float4*>(H + (size_t)row * d + c) = a;
+            if constexpr ((SERT_WT_STORES & kWtGather) != 0) {
+                // row * d + c = 4 * tid: the wave's 64 lanes store 64 consecutive 16-byte pieces, so the wave's first piece is
+                // the base and the lane's offset is 16 * lane, whatever the size of H (store16_wt, common.h)
+                store16_wt(H + 4 * tid_w, 16u * (threadIdx.x & 63u), a);
+            } else {
+                *reinterpret_cast<float4*>(H + (size_t)row * d + c) = a;
+            }
         } else {
             float a = 0.f;
             for (int k = 0; k < n; ++k) a += Rw[(size_t)xr[k] * d + c];
@@ -53,8 +61,15 @@ __device__ __forceinline__ void vs_gather_mean_body(const IdT* __restrict__ X, c
         }
     }
 }
+// With the write-through store of H the register allocator takes 74 VGPRs where the plain store takes 66 (32-bit ids; six
+// waves per SIMD instead of seven): asked for seven waves it fits without scratch (profiles/r11_experiments.txt).
+#if (SERT_WT_STORES & 0x01)
+#define SERT_GATHER_WAVES __attribute__((amdgpu_waves_per_eu(7)))
+#else
+#define SERT_GATHER_WAVES
+#endif
 template <typename IdT, int VEC>
-__global__ __launch_bounds__(256) void vs_gather_mean(const IdT* __restrict__ X,
+__global__ __launch_bounds__(256) SERT_GATHER_WAVES void vs_gather_mean(const IdT* __restrict__ X,
                                                       const float* __restrict__ Rw,
                                                       float* __restrict__ H, int B, int n, int d) {
     vs_gather_mean_body<IdT, VEC>(X, Rw, H, B, n, d, blockIdx.x, gridDim.x);
@@ -70,7 +85,7 @@ __global__ __launch_bounds__(256) void vs_gather_mean(const IdT* __restrict__ X,
 // last TAIL workgroup: every workgroup it waits for has a lower index, is dispatched before it and never waits, and no
 // gather workgroup waits on anything.
 template <typename IdT>
-__global__ __launch_bounds__(256) void vs_gather_mean_tail(const IdT* __restrict__ X, const float* __restrict__ Rw,
+__global__ __launch_bounds__(256) SERT_GATHER_WAVES void vs_gather_mean_tail(const IdT* __restrict__ X, const float* __restrict__ Rw,
                                                            float* __restrict__ H, int B, int n, int d, const TailArgs t,
                                                            unsigned tail_blocks) {
     __shared__ float red[16][64];
@@ -279,7 +294,7 @@ __global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
             o.y = (t[q].y >= -SERT_CLIP_HI && t[q].y <= SERT_CLIP_HI) ? dp[q].y * (1.0f - t[q].y * t[q].y) : 0.f;
             o.z = (t[q].z >= -SERT_CLIP_HI && t[q].z <= SERT_CLIP_HI) ? dp[q].z * (1.0f - t[q].z * t[q].z) : 0.f;
             o.w = (t[q].w >= -SERT_CLIP_HI && t[q].w <= SERT_CLIP_HI) ? dp[q].w * (1.0f - t[q].w * t[q].w) : 0.f;
-            *reinterpret_cast<float4*>(DA + (size_t)i * de + 4 * c) = o;
+            store16<kWtNce>(DA, (size_t)i * de + 4 * c, o);
         }
     }
     loss += row_nan(t);
@@ -396,7 +411,7 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
             o.y = (t[q].y >= -SERT_CLIP_HI && t[q].y <= SERT_CLIP_HI) ? dp[q].y * (1.0f - t[q].y * t[q].y) : 0.f;
             o.z = (t[q].z >= -SERT_CLIP_HI && t[q].z <= SERT_CLIP_HI) ? dp[q].z * (1.0f - t[q].z * t[q].z) : 0.f;
             o.w = (t[q].w >= -SERT_CLIP_HI && t[q].w <= SERT_CLIP_HI) ? dp[q].w * (1.0f - t[q].w * t[q].w) : 0.f;
-            *reinterpret_cast<float4*>(DA + (size_t)i * de + 4 * c) = o;
+            store16<kWtNce>(DA, (size_t)i * de + 4 * c, o);
         }
     }
     if (l == 0 && valid) rowloss[i] = wi * loss;
