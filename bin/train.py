@@ -22,7 +22,11 @@ dumped with --save_optimizer_state: same results as the uninterrupted run), --gp
 works as well.  --eval_topics FILE... --eval_qrels NAME=FILE... [--eval_top K]: retrieval
 quality (NDCG, MAP, reciprocal rank, P@5) of the live model on every named qrel set, on the
 device, before epoch 1 and after every epoch; written to <model_output>_retrieval.json and
-the best epoch by the first set's NDCG logged at the end (sert_amd/evaluation.py).
+the best epoch by the first set's NDCG logged at the end (sert_amd/evaluation.py).  K is the
+evaluated depth, any positive number for either model kind (default: every entity for
+loglinear, min(100, entities) for vectorspace); K at or above the number of entities means
+every entity, and the NDCG entry is then named 'ndcg' instead of 'ndcg_cut_K'.  A vectorspace
+depth above 1024 is evaluated without ranking, by counting the judged entities' ranks.
 """
 import argparse
 import logging
@@ -101,7 +105,10 @@ FLAGS = [
     # retrieval evaluation per epoch; absent from the namespace (which is pickled into every dump) unless given
     ('--eval_topics', dict(type=au.existing_file_path, nargs='+', default=argparse.SUPPRESS)),
     ('--eval_qrels', dict(type=named_file, nargs='+', default=argparse.SUPPRESS, metavar='NAME=FILE')),
-    ('--eval_top', dict(type=au.positive_int, default=argparse.SUPPRESS)),
+    ('--eval_top', dict(type=au.positive_int, default=argparse.SUPPRESS, metavar='K',
+                        help='evaluated depth: any K >= 1 for either model kind; K at or above the number of entities '
+                             'evaluates every entity (the NDCG entry is then named ndcg).  Default: every entity for '
+                             'loglinear, min(100, entities) for vectorspace.')),
 ]
 
 

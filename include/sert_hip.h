@@ -265,7 +265,8 @@ enum {
  *   ideal_dcg (Q) f64  the topic's ideal DCG at the ranked depth, num_rel (Q) its number of relevant entities: computed by
  *                      the caller in float64 over ALL judgements of the topic, those of entities the model does not know included
  *   k                  entities ranked per topic.  loglinear: -1 = every entity (as the reference ranks), or positive.
- *                      vectorspace kinds: 1 .. min(num_entities, 1024), the range of sert_scorer_topk; other values are refused.
+ *                      vectorspace kinds: 1 .. min(num_entities, 1024), the range of sert_scorer_topk; other values are refused
+ *                      (any depth: the counted evaluator, sert_hip_reval_counted.h).
  * The ranked depth kk is num_entities for k = -1 or k >= num_entities, else k. */
 int sert_reval_create(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_topics,
                       const int64_t* rel_indptr, const int32_t* rel_entities, const float* rel_gains,
@@ -289,6 +290,11 @@ int sert_reval_create(sert_model* m, const int32_t* tokens, const int64_t* offse
  * same order (collective; tested at world size 1 only). */
 int sert_reval_run(sert_reval* r, double* metrics_out, int32_t* status_out, int32_t* idx_out, float* score_out);
 int sert_reval_destroy(sert_reval* r);
+
+/* Evaluation at any depth for the vectorspace kinds -- k = -1, k above 1024 -- by counting the judged entities' ranks instead
+ * of ranking: the counted evaluator's create call and the call that returns the ranks of its last run are declared in
+ * sert_hip_reval_counted.h, which is part of this boundary. */
+#include "sert_hip_reval_counted.h"
 
 /* ---- entity scoring (bin/query.py:239-370, batched) --------------------- */
 

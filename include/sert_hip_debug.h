@@ -182,6 +182,14 @@ int sert_bench_memory(int device, int kind, size_t bytes, size_t table_bytes, in
 struct sert_reval;
 int sert_debug_reval_chunks(struct sert_reval* r);
 
+/* Test hook: the counting kernel of the counted evaluator (sert_hip_reval_counted.h; csrc/kernels_reval.h: reval_count_ranks)
+ * alone, on cosines the caller provides, cos (Q, V) f32 host -- the only way to feed it -0, NaNs of both signs and
+ * infinities.  rel_indptr (Q + 1) / rel_ent: per row the judged entities, each in [0, V), any order; ranks_out
+ * (rel_indptr[Q]) int32: 1 + the number of entities that precede the judged one under the scorer's order.  Q <= 65535,
+ * Q V <= 2^31.  The tile (8 or 32 judged entities in registers) goes by the longest list, the row form by V % 4. */
+int sert_debug_count_ranks(int device, const float* cos, int64_t Q, int64_t V, const int64_t* rel_indptr, const int32_t* rel_ent,
+                           int32_t* ranks_out);
+
 #ifdef __cplusplus
 }
 #endif

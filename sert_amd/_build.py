@@ -23,6 +23,7 @@ def _stale():
         deps += [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith('.inc')]
     deps.append(os.path.join(INCLUDE, 'sert_hip.h'))
     deps.append(os.path.join(INCLUDE, 'sert_hip_debug.h'))
+    deps.append(os.path.join(INCLUDE, 'sert_hip_reval_counted.h'))
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -43,8 +43,11 @@ EXPORTS = [
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
     'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_count_ranks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
+# ... and include/sert_hip_reval_counted.h, which sert_hip.h includes (the evaluator by rank counting)
+EXPORTS_REVAL_COUNTED = ['sert_reval_create_counted', 'sert_reval_judged_ranks']
 
 
 # int (*sert_alltoall_fn)(void* user, const float* send, const int64_t* send_offsets, const int64_t* send_counts,
@@ -125,6 +128,8 @@ def load():
     lib.sert_predict_tokens.argtypes = [vp, fp, i64, fp]
     lib.sert_ll_rank_queries.argtypes = [vp, fp, fp, i64, i32, fp, fp, fp, fp, fp]
     lib.sert_reval_create.argtypes = [vp, fp, fp, i64, fp, fp, fp, fp, fp, i32, ctypes.POINTER(vp)]
+    lib.sert_reval_create_counted.argtypes = lib.sert_reval_create.argtypes
+    lib.sert_reval_judged_ranks.argtypes = [vp, fp]
     lib.sert_reval_run.argtypes = [vp, fp, fp, fp, fp]
     lib.sert_reval_destroy.argtypes = [vp]
     lib.sert_score_topk.argtypes = [ctypes.c_int, fp, i64, i32, fp, i64, i32, fp, fp]
@@ -555,6 +560,24 @@ def debug_scorer_rank_select(cosines, k=None, device=0):
     return idx, val
 
 
+def debug_count_ranks(cosines, judged, device=0):
+    """sert_debug_count_ranks (test hook): the counting kernel of the counted evaluator on caller-provided cosines (Q, V);
+    judged: per row the judged entity indices.  -> per row an int32 array: the 1-based rank of each judged entity under the
+    scorer's order."""
+    s = np.ascontiguousarray(cosines, dtype=np.float32)
+    assert s.ndim == 2 and len(judged) == s.shape[0]
+    indptr = np.zeros(s.shape[0] + 1, dtype=np.int64)
+    np.cumsum([len(e) for e in judged], out=indptr[1:])
+    ents = np.ascontiguousarray(np.concatenate([np.asarray(e, dtype=np.int64) for e in judged]), dtype=np.int32)
+    ranks = np.zeros(len(ents), dtype=np.int32)
+    lib = load()
+    lib.sert_debug_count_ranks.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p]
+    check(lib.sert_debug_count_ranks(device, s.ctypes.data, s.shape[0], s.shape[1], indptr.ctypes.data, ents.ctypes.data,
+                                     ranks.ctypes.data))
+    return [ranks[indptr[q]:indptr[q + 1]] for q in range(s.shape[0])]
+
+
 class Scorer(object):
     """Persistent device copy of the (L2-normalised) entity table + top-k scoring
     (sert_scorer_* in include/sert_hip.h).
@@ -691,9 +714,10 @@ class RetrievalEval(object):
 
     token_lists: per topic its token ids (at least one); judgements: per topic (entities int, ascending; gains float);
     ideal_dcg / num_rel: per topic, float64 / int, over ALL its judgements (sert_hip.h); k: None = every entity
-    (loglinear only).  The engine must stay alive as long as this object."""
+    (loglinear, or counted).  counted=True: the evaluator by rank counting (sert_reval_create_counted: vectorspace kinds,
+    any depth, no ranking -- ``judged_ranks()`` instead).  The engine must stay alive as long as this object."""
 
-    def __init__(self, engine, token_lists, judgements, ideal_dcg, num_rel, k=None):
+    def __init__(self, engine, token_lists, judgements, ideal_dcg, num_rel, k=None, counted=False):
         self._lib = load()
         self._engine = engine
         self._h = None
@@ -711,10 +735,13 @@ class RetrievalEval(object):
         v = engine.cfg.num_entities
         self.num_topics = q
         self.depth = v if k is None or k >= v else int(k)
+        self.counted = bool(counted)
+        self.rel_indptr = indptr
         h = ctypes.c_void_p()
-        check(self._lib.sert_reval_create(engine._h, self._tokens.ctypes.data, self._offsets.ctypes.data, q,
-                                          indptr.ctypes.data, ents.ctypes.data, gains.ctypes.data, idcg.ctypes.data,
-                                          nrel.ctypes.data, -1 if k is None else int(k), ctypes.byref(h)))
+        create = self._lib.sert_reval_create_counted if counted else self._lib.sert_reval_create
+        check(create(engine._h, self._tokens.ctypes.data, self._offsets.ctypes.data, q,
+                     indptr.ctypes.data, ents.ctypes.data, gains.ctypes.data, idcg.ctypes.data,
+                     nrel.ctypes.data, -1 if k is None else int(k), ctypes.byref(h)))
         self._h = h
 
     def run(self, return_ranking=False):
@@ -722,11 +749,20 @@ class RetrievalEval(object):
         metrics = np.empty((self.num_topics, REVAL_NUM_METRICS), dtype=np.float64)
         status = np.empty(self.num_topics, dtype=np.int32)
         idx = score = None
+        if return_ranking and self.counted:
+            raise SertError('a counted RetrievalEval makes no ranking: judged_ranks() has the ranks, Scorer.rank a ranking')
         if return_ranking:
             idx = np.empty((self.num_topics, self.depth), dtype=np.int32)
             score = np.empty((self.num_topics, self.depth), dtype=np.float32)
         check(self._lib.sert_reval_run(self._h, metrics.ctypes.data, status.ctypes.data, _addr(idx), _addr(score)))
         return (metrics, status, idx, score) if return_ranking else (metrics, status)
+
+    def judged_ranks(self):
+        """Counted evaluators: the 1-based ranks the last run() found, int32, aligned with the concatenated judgement lists
+        (topic q owns [rel_indptr[q], rel_indptr[q + 1])); not cut at the depth."""
+        ranks = np.zeros(int(self.rel_indptr[-1]), dtype=np.int32)
+        check(self._lib.sert_reval_judged_ranks(self._h, ranks.ctypes.data))
+        return ranks
 
     def num_chunks(self):
         """sert_debug_reval_chunks (test hook): chunks the topics are ranked in."""

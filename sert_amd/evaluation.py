@@ -8,6 +8,13 @@ are uploaded to the model's device once, ``evaluate()`` ranks every topic with t
 as they are at that moment and computes the per-topic metrics on the device
 (include/sert_hip.h: sert_reval_*).  Only the (topics, 5) float64 figures come back.
 
+DEPTH.  A loglinear model ranks any depth.  A vectorspace model ranks up to min(entities, 1024)
+entities per topic through the top-k kernels; for every other depth -- ``k=None`` (every
+entity), k above 1024, k above the number of entities -- the evaluator does not rank at all:
+every figure depends only on the ranks of the topic's judged entities, and those are counted
+in one pass over the topic's cosine row (sert_reval_create_counted; DESIGN.md, "Evaluation
+depth without a sort").  ``metrics_from_ranks`` is that definition on the host.
+
 Population (``trec_utils.evaluate_run``'s rule): the means run over the topics OF THE QREL
 FILE.  A judged topic that is absent from the topics file, or none of whose terms is in the
 vocabulary (bin/query.py:129-137 skips it), scores 0 on every metric.
@@ -56,6 +63,37 @@ def host_metrics(ranked_entities, relevance, depth):
             'recip_rank': trec_utils.reciprocal_rank(ranked, relevance),
             'P_5': trec_utils.precision_at(ranked, relevance, 5),
             'num_rel_ret': float(sum(1 for e in ranked if relevance.get(e, 0.0) > 0))}
+
+
+def metrics_from_ranks(ranks, gains, depth, ideal_dcg, num_rel):
+    """The evaluator's metrics of one topic from the 1-based RANKS of its judged entities (those the model knows), in
+    float64: what the device computes for a counted handle (csrc/kernels_reval.h: reval_metrics_from_ranks), restated.
+
+    ranks / gains: aligned, one entry per judged entity; ranks pairwise distinct.  Only entries of rank <= depth count.
+    ideal_dcg / num_rel: over ALL the topic's judgements, as ``ideal_dcg()`` and the number of gains > 0 give them.
+    -> dict over METRICS, equal to ``host_metrics`` on any ranking that places those entities at those ranks."""
+    inside = [(int(r), float(g)) for r, g in zip(ranks, gains) if int(r) <= depth]
+    dcg = 0.0
+    for r, g in inside:                         # (every judged entity, whatever the sign of its gain: trec_utils.ndcg_at_k)
+        dcg += g / math.log2(r + 1)
+    hit_ranks = sorted(r for r, g in inside if g > 0)
+    ap = 0.0
+    for h, r in enumerate(hit_ranks, 1):        # (h: the hits of rank <= r)
+        ap += h / float(r)
+    return {'ndcg': dcg / ideal_dcg if ideal_dcg > 0 else 0.0,
+            'map': ap / num_rel if num_rel > 0 else 0.0,
+            'recip_rank': 1.0 / hit_ranks[0] if hit_ranks else 0.0,
+            'P_5': sum(1 for r in hit_ranks if r <= 5) / 5.0,
+            'num_rel_ret': float(len(hit_ranks))}
+
+
+TOPK_MAX = 1024       # the deepest ranking of sert_scorer_topk, and so of a vectorspace handle of sert_reval_create
+
+
+def uses_counting(kind, k, num_entities):
+    """Whether RetrievalEvaluator evaluates a model of `kind` at depth k through a counted handle: a vectorspace kind at any
+    depth sert_reval_create refuses for it (k None, above 1024, above the number of entities)."""
+    return kind != _capi.KIND_LOGLINEAR and (k is None or k > min(num_entities, TOPK_MAX))
 
 
 ZERO = dict((name, 0.0) for name in METRICS)
@@ -149,7 +187,8 @@ class RetrievalEvaluator(object):
         self._eval = None
         if self.arrays.device_topics:
             a = self.arrays
-            self._eval = _capi.RetrievalEval(model._engine, a.token_lists, a.judgements, a.ideal_dcg, a.num_rel, k)
+            counted = uses_counting(model._engine.cfg.kind, k, a.num_entities)
+            self._eval = _capi.RetrievalEval(model._engine, a.token_lists, a.judgements, a.ideal_dcg, a.num_rel, k, counted=counted)
 
     def _host_topic(self, tokens, relevance):
         """A loglinear topic the device could not rank (joint sum 0 or not finite): the per-token host path of

@@ -12,6 +12,16 @@ reference's per-epoch selection also pays (product-search.sh:136-170), are NOT c
 Shapes: (a) product search: V_e = 32 768, d_w = 300, d_e = 128, 1 000 topics of 1-12 tokens, k = 100;
 (b) C5: 10 000 topics x V_e = 100 000, d = 128, k = 100; (c) loglinear at the W3C shape: V_e = 715, d = 300, 100 topics,
 every entity ranked.  Median of --calls calls after --warmup.
+
+--depths K ... (vectorspace shapes): the same shapes at other depths, 'none' = every entity -- above 1024 the evaluator counts
+the judged entities' ranks instead of ranking (sert_reval_create_counted; DESIGN.md, "Evaluation depth without a sort"), and the
+other side is Scorer.rank(proj, k) on the device (sert_scorer_rank) followed by the trec_utils functions; that call ALONE on
+the same projections is recorded beside it (rank_alone_ms_*).  The host side of a deep ranking is slow (Python over Q x depth
+entries), so the other side is timed --baseline_calls times after --baseline_warmup, and ONCE without warm-up where Q x depth
+exceeds 1e8 (baseline_calls in the record says which).
+
+    python tools/reval_bench.py --shapes product_search c5 --depths none 1000 --baseline_calls 3 --baseline_warmup 1 \
+        --out profiles/r10_reval_counted.json
 """
 import argparse
 import json
@@ -60,15 +70,18 @@ def make_engine(s, rng):
 
 def host_figures(idx, rels, depth):
     ndcg = ap = 0.0
+    slow = idx.size > 1e8          # (minutes of Python: say that it is alive)
     for q, rel in enumerate(rels):
+        if slow and q % 1000 == 0:
+            print('# host metrics: topic %d of %d' % (q, len(rels)), file=sys.stderr, flush=True)
         ranked = idx[q].tolist()
         ndcg += trec_utils.ndcg_at_k(ranked, rel, depth)
         ap += trec_utils.average_precision(ranked, rel)
     return ndcg / len(rels), ap / len(rels)
 
 
-def parent_path(eng, s, lists, rels, depth):
-    """One evaluation without the evaluator; -> (mean ndcg, mean ap)."""
+def parent_path(eng, s, lists, rels, depth, keep=None):
+    """One evaluation without the evaluator; -> (mean ndcg, mean ap).  keep: a dict that receives the projections."""
     Rw = eng.get_tensor(C.T_RW, (s['Vw'], s['dw']))
     eng.get_tensor(C.T_W)
     eng.get_tensor(C.T_B)                  # (get_state: predict_fn carries W and b)
@@ -78,7 +91,10 @@ def parent_path(eng, s, lists, rels, depth):
         avg = np.empty((len(lists), s['dw']), dtype=np.float32)
         for i, tokens in enumerate(lists):
             avg[i] = Rw[tokens, :].mean(axis=0)
-        idx, _ = scorer.rank(eng.predict_project(avg), s['k'])
+        proj = eng.predict_project(avg)
+        if keep is not None:
+            keep['proj'] = proj
+        idx, _ = scorer.rank(proj, s['k'])
         out = host_figures(idx, rels, depth)
         scorer.close()
         return out
@@ -97,7 +113,7 @@ def timed(fn, warmup, calls):
     return float(np.median(times)) * 1e3, float(min(times)) * 1e3, last
 
 
-def run_shape(name, s, warmup, calls):
+def run_shape(name, s, warmup, calls, baseline_warmup=None, baseline_calls=None):
     rng = np.random.RandomState(7)
     eng = make_engine(s, rng)
     lists = [rng.randint(0, s['Vw'], size=rng.randint(1, s['max_len'] + 1)).tolist() for _ in range(s['topics'])]
@@ -122,11 +138,31 @@ def run_shape(name, s, warmup, calls):
     eval_ms, eval_min, eval_fig = timed(lambda: figures(ev.evaluate(per_topic=False)), warmup, calls)
     full_ms, full_min, full_fig = timed(lambda: figures(ev.evaluate()), warmup, calls)
     run_ms, run_min, _ = timed(device_part, warmup, calls)
-    parent_ms, parent_min, parent_fig = timed(lambda: parent_path(eng, s, lists, rels, depth), warmup, calls)
+    bw, bc = (warmup if baseline_warmup is None else baseline_warmup), (calls if baseline_calls is None else baseline_calls)
+    if len(lists) * depth > 1e8:
+        bw, bc = 0, 1
+    keep = {}
+    parent_ms, parent_min, parent_fig = timed(lambda: parent_path(eng, s, lists, rels, depth, keep), bw, bc)
     assert eval_fig == full_fig
+    rank_alone = {}
+    if s['kind'] == 'vectorspace':
+        # the ranking call of the other side alone, on the projections it ranked: a scorer on the same table, created outside the clock
+        scorer = C.Scorer(eng.get_tensor(C.T_RE, (s['Ve'], s['de'])))
+        ms, lo, _ = timed(lambda: scorer.rank(keep['proj'], s['k'])[0].shape, bw, bc)
+        scorer.close()
+        # the counted handle's run() at this depth, whichever handle the evaluator picked for it
+        ar = ev.arrays
+        ch = C.RetrievalEval(eng, ar.token_lists, ar.judgements, ar.ideal_dcg, ar.num_rel, s['k'], counted=True)
+        cms, clo, _ = timed(lambda: ch.run()[0].shape, warmup, calls)
+        ch.close()
+        rank_alone = dict(rank_alone_ms_median=ms, rank_alone_ms_min=lo, counted_run_ms_median=cms, counted_run_ms_min=clo,
+                          counted_run_over_rank_alone=cms / ms)
+    counted = bool(getattr(ev._eval, 'counted', False))
     ev.close()
     eng.close()
-    rec = dict(s, shape=name, depth=depth, calls=calls, warmup=warmup,
+    rec = dict(s, shape=name, depth=depth, calls=calls, warmup=warmup, counted=counted, baseline_calls=bc, baseline_warmup=bw,
+               **rank_alone)
+    rec.update(
                evaluate_ms_median=eval_ms, evaluate_ms_min=eval_min,
                evaluate_with_per_topic_ms_median=full_ms, evaluate_with_per_topic_ms_min=full_min,
                device_run_ms_median=run_ms, device_run_ms_min=run_min,
@@ -143,12 +179,21 @@ def main():
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--shapes', nargs='+', default=list(SHAPES), choices=list(SHAPES))
+    ap.add_argument('--depths', nargs='+', default=['shape'], help="depths of the vectorspace shapes: 'shape' (the shape's own k), 'none' (every entity) or a number")
+    ap.add_argument('--baseline_calls', type=int, default=None, help='calls of the other side (default: --calls)')
+    ap.add_argument('--baseline_warmup', type=int, default=None, help='warm-up calls of the other side (default: --warmup)')
     args = ap.parse_args()
+    runs = []
+    for name in args.shapes:
+        for d in (args.depths if SHAPES[name]['kind'] == 'vectorspace' else ['shape']):
+            runs.append((name, SHAPES[name] if d == 'shape' else dict(SHAPES[name], k=None if d == 'none' else int(d))))
     C.require_gpu()
     result = {'device': C.device_info(0), 'what': 'median wall time of one evaluation.  evaluate: RetrievalEvaluator.evaluate(per_topic=False), the call of '
               'the epoch driver; evaluate_with_per_topic: evaluate() with its dict per topic; device_run: RetrievalEval.run alone; '
-              'parent_path: get_tensor x 3-4 -> Scorer / ll_rank_queries -> NumPy means -> trec_utils in Python.  Same process, same parameters',
-              'shapes': [run_shape(name, SHAPES[name], args.warmup, args.calls) for name in args.shapes]}
+              'parent_path: get_tensor x 3-4 -> Scorer / ll_rank_queries -> NumPy means -> trec_utils in Python (baseline_calls calls after '
+              'baseline_warmup); rank_alone: the Scorer.rank call of parent_path alone on the same projections; counted: the evaluator '
+              'counts ranks instead of ranking.  Same process, same parameters',
+              'shapes': [run_shape(name, s, args.warmup, args.calls, args.baseline_warmup, args.baseline_calls) for name, s in runs]}
     if args.out:
         with open(args.out, 'w') as f:
             json.dump(result, f, indent=1, sort_keys=True)
