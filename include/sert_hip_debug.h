@@ -48,6 +48,21 @@ enum {
 };
 int sert_debug_ll_loss_form(sert_model* m, int32_t* out, int n);
 
+/* What the LAST vectorspace backward of this model launched for dR_e, the entity-table gradient (csrc/kernels_egrad.h, dispatch
+ * in csrc/host/step_vectorspace.inc) -- host record written where the launches are made, test hook, no device is touched:
+ * out[0] one of SERT_EGRAD_PATH_*.  BUCKET: out[1] rows per sub-group, out[2] sub-groups, out[3] sub-groups per row group,
+ * out[4] row groups, out[5] ranges of 16 entities, out[6] 1 when egrad_group_sum was launched and 0 when the sum of the group
+ * tables was left to the optimiser.  SORTED: out[7] key bits of the counting sort, out[8] its digit passes, out[9] / out[10] VEC
+ * and NCH of egrad_chunk_reduce<VEC, NCH>, out[11] one of SERT_EGRAD_FIXUP_*.  The entries of the path not taken are 0.  n <= 12;
+ * all zero before the first backward.  tests/test_gpu_egrad_keys.py asserts through this that every key structure of
+ * tests/egrad_key_cases.py reaches the kernels it is there for. */
+enum { SERT_EGRAD_PATH_NONE = 0, SERT_EGRAD_PATH_BUCKET = 1, SERT_EGRAD_PATH_SORTED = 2 };
+enum {
+    SERT_EGRAD_FIXUP_WAVE = 1,       /* egrad_fixup<VEC>: one wave per entity */
+    SERT_EGRAD_FIXUP_WORKGROUP = 2   /* egrad_fixup_wg<VEC>: one workgroup per entity (V_e < 256) */
+};
+int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n);
+
 /* Which path the rows of a scorer's sert_scorer_topk calls took since sert_scorer_create -- host counters, test hook: out[0]
  * calls that took the fused path (sampled thresholds, filtering GEMM), out[1] those of them that filtered in bf16, out[2] the
  * query chunks of the fused calls, out[3] rows the fused path flagged and handed to the materialising path, out[4] rows of calls

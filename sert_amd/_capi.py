@@ -27,6 +27,9 @@ T_ACT_H, T_ACT_T, T_ACT_DA, T_ACT_DH, T_ACT_ROWLOSS = 16, 17, 18, 19, 20
 COMM_ID_BYTES = 128
 # SERT_LL_FORM_* of include/sert_hip_debug.h, by value
 LL_FORMS = ('none', 'wave', 'table', 'fused_row', 'stream', 'rowwise')
+# SERT_EGRAD_PATH_* / SERT_EGRAD_FIXUP_*, by value
+EGRAD_PATHS = ('none', 'bucket', 'sorted')
+EGRAD_FIXUPS = ('none', 'wave', 'workgroup')
 
 # every symbol include/sert_hip.h declares
 EXPORTS = [
@@ -42,7 +45,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
     'sert_debug_count_ranks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -427,6 +430,22 @@ class Engine(object):
         self._lib.sert_debug_ll_loss_form.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
         check(self._lib.sert_debug_ll_loss_form(self._h, v, 5))
         return {'form': LL_FORMS[int(v[0])], 'param': int(v[1]), 'train': bool(v[2]), 'slots': bool(v[3]), 'segments': int(v[4])}
+
+    def egrad_plan(self):
+        """sert_debug_egrad_plan (test hook): what the last vectorspace backward launched for the entity-table gradient.
+        {'path': 'none'} before the first backward; the keys of the path taken otherwise."""
+        v = (ctypes.c_int32 * 12)()
+        self._lib.sert_debug_egrad_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_egrad_plan(self._h, v, 12))
+        v = [int(x) for x in v]
+        path = EGRAD_PATHS[v[0]]
+        if path == 'bucket':
+            return {'path': path, 'sub_rows': v[1], 'num_sub': v[2], 'subs_per_group': v[3], 'groups': v[4], 'ranges': v[5],
+                    'group_sum': bool(v[6])}
+        if path == 'sorted':
+            return {'path': path, 'sort_bits': v[7], 'passes': v[8], 'vec': v[9], 'nch': v[10], 'fixup': EGRAD_FIXUPS[v[11]]}
+        assert not any(v), v
+        return {'path': path}
 
     def timings(self):
         n = self._lib.sert_timing_count(self._h)

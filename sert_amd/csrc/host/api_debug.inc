@@ -36,6 +36,13 @@ int sert_debug_ll_loss_form(sert_model* m, int32_t* out, int n) {
     return 0;
 }
 
+int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n) {
+    if (!m || !out || n < 1 || n > 12) SERT_FAIL("bad argument");
+    if (!is_vs(m)) SERT_FAIL("not a vectorspace model");
+    for (int i = 0; i < n; ++i) out[i] = m->eg_plan[i];
+    return 0;
+}
+
 int sert_debug_scorer_counts(sert_scorer* sc, int64_t* out, int n) {
     if (!sc || !out || n < 1 || n > 6) SERT_FAIL("bad argument");
     for (int i = 0; i < n; ++i) out[i] = i < 5 ? sc->path_counts[i] : (sc->bf16_demoted ? 1 : 0);

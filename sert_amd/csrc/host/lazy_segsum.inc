@@ -320,6 +320,7 @@ static int entity_key_sort(sert_model* m, int total, hipStream_t st, const int32
     const int width = cdiv(bits, passes);
     const int32_t* kin = keys ? keys : m->cand;
     const int32_t* vin = nullptr;  // value of element i is i
+    m->eg_plan[7] = bits; m->eg_plan[8] = passes;
     for (int p = 0; p < passes; ++p) {
         const int shift = p * width;
         const int nb = std::min(width, bits - shift);

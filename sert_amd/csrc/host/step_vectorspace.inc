@@ -284,6 +284,7 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
     const int fused_grid = 0;
 #endif
     m->bucket_early = false;
+    for (int32_t& v : m->eg_plan) v = 0;
     auto early_bucket = [&]() -> int {
         // Round 6: the PARTITION of this step's (pair, entity) keys by entity range (egrad_bucket, 19 us at C2) needs the
         // labels and the negatives only -- not the loss kernel's coefficients -- and this step's negatives were drawn on this
@@ -368,6 +369,9 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
 #define SERT_EL_ARGS m->eg_entries, m->eg_offs, m->coef, m->T, c1, de, V, m->eg_sub_rows, m->eg_num_sub, \
                      m->eg_subs_per_group, m->eg_groups, m->eg_ranges, m->epart
                 hipLaunchKernelGGL((egrad_acc<2>), dim3(grid), dim3(256), lds, st, SERT_EL_ARGS);
+                m->eg_plan[0] = SERT_EGRAD_PATH_BUCKET;
+                m->eg_plan[1] = m->eg_sub_rows; m->eg_plan[2] = m->eg_num_sub; m->eg_plan[3] = m->eg_subs_per_group;
+                m->eg_plan[4] = m->eg_groups; m->eg_plan[5] = m->eg_ranges;
 #undef SERT_EL_ARGS
             }
             // Single GPU: the only reader of dR_e is the small-tensor optimiser, which adds the row
@@ -380,6 +384,7 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
                 const size_t table4 = (size_t)V * de4;
                 hipLaunchKernelGGL(egrad_group_sum, dim3(grid_for((int64_t)table4)), dim3(256), 0, st, m->epart, m->eg_groups,
                                    table4, m->g_re);
+                m->eg_plan[6] = 1;
             }
 #ifdef SERT_VARIANTS
         } else if (egrad_ranges_ok(m, total)) {
@@ -395,6 +400,7 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
             SERT_TRY(entity_key_sort(m, total, st));
         }
         const int chunks = cdiv(total, kEChunk);
+        m->eg_plan[0] = SERT_EGRAD_PATH_SORTED;
         dim3 cgrid(cdiv(chunks, 16)), fgrid(cdiv(V, 4)), blk(256);
 #define SERT_EG_ARGS m->cand_sorted, m->pair_sorted, m->coef, m->T, total, c.num_negatives + 1, de, \
                      m->g_re, m->ehead, m->etail, m->run_start, m->run_end
@@ -402,12 +408,13 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
             ScopedTimer t(m, TG_EGRAD, st);
             if (de % 4 == 0) {
                 const int nch = cdiv(de / 4, 16);
-                if (nch <= 1)      hipLaunchKernelGGL((egrad_chunk_reduce<4, 1>), cgrid, blk, 0, st, SERT_EG_ARGS);
-                else if (nch <= 2) hipLaunchKernelGGL((egrad_chunk_reduce<4, 2>), cgrid, blk, 0, st, SERT_EG_ARGS);
-                else if (nch <= 5) hipLaunchKernelGGL((egrad_chunk_reduce<4, 5>), cgrid, blk, 0, st, SERT_EG_ARGS);
-                else               hipLaunchKernelGGL((egrad_chunk_reduce<4, 8>), cgrid, blk, 0, st, SERT_EG_ARGS);
+                if (nch <= 1)      { hipLaunchKernelGGL((egrad_chunk_reduce<4, 1>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 1; }
+                else if (nch <= 2) { hipLaunchKernelGGL((egrad_chunk_reduce<4, 2>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 2; }
+                else if (nch <= 5) { hipLaunchKernelGGL((egrad_chunk_reduce<4, 5>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 5; }
+                else               { hipLaunchKernelGGL((egrad_chunk_reduce<4, 8>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 8; }
             } else {
                 hipLaunchKernelGGL((egrad_chunk_reduce<1, 4>), cgrid, blk, 0, st, SERT_EG_ARGS);
+                m->eg_plan[9] = 1; m->eg_plan[10] = 4;
             }
         }
         {
@@ -417,16 +424,20 @@ static int vs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
                 if (few) {
                     hipLaunchKernelGGL((egrad_fixup_wg<4>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
                                        m->ehead, m->etail, m->g_re);
+                    m->eg_plan[11] = SERT_EGRAD_FIXUP_WORKGROUP;
                 } else {
                     hipLaunchKernelGGL((egrad_fixup<4>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
                                        m->ehead, m->etail, m->g_re);
+                    m->eg_plan[11] = SERT_EGRAD_FIXUP_WAVE;
                 }
             } else if (few) {
                 hipLaunchKernelGGL((egrad_fixup_wg<1>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
                                    m->ehead, m->etail, m->g_re);
+                m->eg_plan[11] = SERT_EGRAD_FIXUP_WORKGROUP;
             } else {
                 hipLaunchKernelGGL((egrad_fixup<1>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
                                    m->ehead, m->etail, m->g_re);
+                m->eg_plan[11] = SERT_EGRAD_FIXUP_WAVE;
             }
         }
 #undef SERT_EG_ARGS

@@ -198,6 +198,8 @@ struct sert_model {
     int32_t *sort_hist = nullptr, *sort_bin_total = nullptr;   // counting-sort scratch
     int32_t *sort_k_tmp = nullptr, *sort_v_tmp = nullptr;       // ping-pong (only if > 11 key bits)
     int sort_bits = 1;
+    // what the last vs_backward launched for dR_e, recorded where the launches are made: sert_debug_egrad_plan (sert_hip_debug.h)
+    int32_t eg_plan[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // loglinear activations
     float *G = nullptr;           // (B*n, d) gathered rows
     float *Z = nullptr;           // (B*n, V_e) logits -> probabilities -> dZ

@@ -60,6 +60,21 @@ def test_config_struct_abi(hip_lib):
     assert b'bad kind' in hip_lib.sert_last_error()
 
 
+def test_egrad_plan_hook_refuses_bad_arguments(hip_lib):
+    """sert_debug_egrad_plan (include/sert_hip_debug.h) touches no device: without a model it fails with a message, and the
+    binding knows the values of its two enums by name."""
+    v = (ctypes.c_int32 * 12)()
+    hip_lib.sert_debug_egrad_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    assert hip_lib.sert_debug_egrad_plan(None, v, 12) != 0
+    assert b'bad argument' in hip_lib.sert_last_error()
+    src = open(os.path.join(ROOT, 'include', 'sert_hip_debug.h')).read()
+    assert _capi.EGRAD_PATHS == ('none', 'bucket', 'sorted') and _capi.EGRAD_FIXUPS == ('none', 'wave', 'workgroup')
+    for k, name in enumerate(('NONE', 'BUCKET', 'SORTED')):
+        assert re.search(r'\bSERT_EGRAD_PATH_%s = %d\b' % (name, k), src), name
+    for k, name in ((1, 'WAVE'), (2, 'WORKGROUP')):
+        assert re.search(r'\bSERT_EGRAD_FIXUP_%s = %d\b' % (name, k), src), name
+
+
 @pytest.mark.skipif(_capi.device_count() > 0, reason='needs a GPU-less host')
 def test_fails_loudly_without_gpu(hip_lib):
     from sert_amd import models

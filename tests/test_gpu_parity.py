@@ -34,7 +34,7 @@ VS_STEP_DIMS = [
     dict(B=130, n=4, z=10, Vw=70000, Ve=300, dw=300, de=128),   # uint32 ids, d=300
     dict(B=2100, n=2, z=5, Vw=300, Ve=5000, dw=16, de=32),      # 13 key bits: 2 sort passes, >1 tile/chunk carries
     dict(B=300, n=2, z=20, Vw=50, Ve=3, dw=8, de=300),          # heavy duplicate entities: long carry chains
-    dict(B=5000, n=2, z=10, Vw=300, Ve=2, dw=16, de=256),       # two entities, d_e = 256: LDS path with 2 float4 per lane, queue drains mid-scan
+    dict(B=5000, n=2, z=10, Vw=300, Ve=2, dw=16, de=256),       # two entities, d_e = 256 (above the bucket path's d_e <= 128): the sort, egrad_chunk_reduce<4, 5>, egrad_fixup_wg<4> over runs of ~1700 chunks
     dict(B=4100, n=2, z=3, Vw=300, Ve=2048, dw=16, de=64),      # largest vocabulary of the LDS path, ragged last row group
     dict(B=1100, n=3, z=4, Vw=2000, Ve=50, dw=128, de=128),     # strip GEMMs (gemm_strip.h), ragged last strip
     dict(B=1030, n=2, z=3, Vw=500, Ve=40, dw=96, de=64),        # strip GEMMs with idle waves (N = 64 / 96), K = 96 / 64
