@@ -63,6 +63,70 @@ enum {
 };
 int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n);
 
+/* The SCHEDULE of the vectorspace training step (csrc/step_plan.h): which queue the pieces of the backward and of the update
+ * went to, in what order, and which events order them.  sert_debug_vs_plan: the plan of the step this model issued LAST, out[i]
+ * by SERT_VS_PLAN_*, n <= SERT_VS_PLAN_COUNT -- host record, no device is touched; the default plan (everything on the main
+ * queue) before the first step and for a loglinear model.  sert_debug_vs_facts: the facts that plan was decided from, out[i] by
+ * SERT_VS_FACT_*, n <= SERT_VS_FACT_COUNT.  sert_debug_vs_plan_for: the same pure function on facts the caller
+ * provides, facts[i] by SERT_VS_FACT_* (missing trailing facts take their defaults: no knob set) -- no model, no device; the
+ * knob values are facts here, so the product library answers for a variants build's knobs too.
+ * tests/test_step_plan_cpu.py pins the plan of every schedule, tests/test_gpu_step_plan.py that the steps ran it. */
+enum {  /* facts: what the schedule depends on */
+    SERT_VS_FACT_KIND = 0,          /* SERT_KIND_* */
+    SERT_VS_FACT_HOST_AR, SERT_VS_FACT_COMM,   /* data parallel: host transport / communicator */
+    SERT_VS_FACT_TIMING,            /* sert_timing_enable(m, 1) */
+    SERT_VS_FACT_NSTREAMS,          /* SERT_STREAMS (default 2) */
+    SERT_VS_FACT_N_RE,              /* elements of R_e, saturated at INT32_MAX */
+    SERT_VS_FACT_BIG_RE, SERT_VS_FACT_BIG_W,   /* R_e / W of more than 2^22 elements (a streaming update of its own) */
+    SERT_VS_FACT_KEEP_GRADS,
+    SERT_VS_FACT_BATCH, SERT_VS_FACT_WORD_DIM, SERT_VS_FACT_ENTITY_DIM, SERT_VS_FACT_NUM_NEGATIVES,
+    SERT_VS_FACT_HAS_ENTITIES,
+    SERT_VS_FACT_SORT_FREE,         /* the sort-free entity chain (V_e <= 2048, d_e <= 128) */
+    SERT_VS_FACT_CAND_EARLY,        /* the early sort's key buffer exists */
+    SERT_VS_FACT_NEG_SIDE_READY,    /* this step's negatives were drawn during the previous step */
+    SERT_VS_FACT_HAS_LABELS,
+    SERT_VS_FACT_NEXT_NEG_DRAWN,    /* the next step's negatives exist already */
+    SERT_VS_FACT_DH_STRIP, SERT_VS_FACT_BWD_FUSED_SHAPE,   /* variants build: shape predicates of gemm_strip / vs_bwd_fused */
+    /* the knobs, by value (csrc/step_plan.h: VsKnobs has the defaults) */
+    SERT_VS_FACT_K_EXT_EVENTS, SERT_VS_FACT_K_FORK_LATE,
+    SERT_VS_FACT_K_FORK_AT,         /* SERT_FORK_AT: 0 unset, 1 nce, 2 nce_dw */
+    SERT_VS_FACT_K_SIDE_HEAVY, SERT_VS_FACT_K_RE_DEFER,
+    SERT_VS_FACT_K_EARLY_BUCKET,    /* -1 unset */
+    SERT_VS_FACT_K_NO_EARLY_BUCKET, SERT_VS_FACT_K_EARLY_SORT, SERT_VS_FACT_K_NO_EARLY_SORT,
+    SERT_VS_FACT_K_DW_FIRST,        /* -1 unset */
+    SERT_VS_FACT_K_DP_LATE, SERT_VS_FACT_K_NO_TAIL, SERT_VS_FACT_K_EGRAD_GROUP_SUM, SERT_VS_FACT_K_BWD_FUSED,
+    SERT_VS_FACT_COUNT
+};
+enum {  /* the plan */
+    SERT_VS_PLAN_FORK_AT = 0,       /* SERT_VS_FORK_*: the kernel behind which the side queue starts its chain */
+    SERT_VS_PLAN_FORK_CARRIED,      /* its own completion signal is the fork event */
+    SERT_VS_PLAN_FORK_RECORDED,     /* a hipEventRecord behind the loss kernel is */
+    SERT_VS_PLAN_DH_EVENT,          /* SERT_VS_EVENT_*: what the end of the dh GEMM marks */
+    SERT_VS_PLAN_DH_CARRIED,        /* by its completion signal */
+    SERT_VS_PLAN_ORDER,             /* four entries, SERT_VS_PIECE_*, in order of issue */
+    SERT_VS_PLAN_ENTITY_QUEUE = SERT_VS_PLAN_ORDER + 4, SERT_VS_PLAN_DENSE_QUEUE,   /* SERT_VS_QUEUE_* */
+    SERT_VS_PLAN_SIDE_MEETS_FORK,   /* the side queue waits for the fork in front of the pieces */
+    SERT_VS_PLAN_ENTITY_WAITS_FORK, /* the entity chain's queue waits for it at its head */
+    SERT_VS_PLAN_DENSE_EVENT,       /* SERT_VS_EVENT_*: what the dense gradients record behind themselves */
+    SERT_VS_PLAN_BWD_FUSED,
+    SERT_VS_PLAN_BUCKET_EARLY, SERT_VS_PLAN_SORT_EARLY, SERT_VS_PLAN_DRAW_NEXT_NEG,   /* on the side queue, in front of its fork wait */
+    SERT_VS_PLAN_LAZY_JOIN,         /* the main queue never waits for the entity chain */
+    SERT_VS_PLAN_END_JOIN,          /* it joins the side queue at the end of the backward */
+    SERT_VS_PLAN_DP_LATE_JOIN,      /* the communication queue does */
+    SERT_VS_PLAN_COMBINE_IN_TAIL, SERT_VS_PLAN_RE_IN_PARTS,
+    SERT_VS_PLAN_SIDE_SMALL,        /* the small tensors are updated on the side queue */
+    SERT_VS_PLAN_SMALL_ORDER,       /* SERT_VS_EVENT_*: what orders that queue in front of them */
+    SERT_VS_PLAN_SPLIT_SMALL, SERT_VS_PLAN_DEFER_RE, SERT_VS_PLAN_DEFER_SMALL, SERT_VS_PLAN_RE_ON_SIDE,
+    SERT_VS_PLAN_COUNT
+};
+enum { SERT_VS_FORK_NONE = 0, SERT_VS_FORK_LOSS = 1, SERT_VS_FORK_DH = 2 };
+enum { SERT_VS_PIECE_ENTITY = 0, SERT_VS_PIECE_DH = 1, SERT_VS_PIECE_DENSE = 2, SERT_VS_PIECE_WORD_SUM = 3 };
+enum { SERT_VS_QUEUE_MAIN = 0, SERT_VS_QUEUE_SIDE = 1, SERT_VS_QUEUE_THIRD = 2 };
+enum { SERT_VS_EVENT_NONE = 0, SERT_VS_EVENT_FORK = 1, SERT_VS_EVENT_DENSE = 2, SERT_VS_EVENT_JOIN3 = 3, SERT_VS_EVENT_OPT_FORK = 4 };
+int sert_debug_vs_plan(sert_model* m, int32_t* out, int n);
+int sert_debug_vs_facts(sert_model* m, int32_t* out, int n);
+int sert_debug_vs_plan_for(const int32_t* facts, int nfacts, int32_t* out, int n);
+
 /* Which path the rows of a scorer's sert_scorer_topk calls took since sert_scorer_create -- host counters, test hook: out[0]
  * calls that took the fused path (sampled thresholds, filtering GEMM), out[1] those of them that filtered in bf16, out[2] the
  * query chunks of the fused calls, out[3] rows the fused path flagged and handed to the materialising path, out[4] rows of calls

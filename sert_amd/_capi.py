@@ -30,6 +30,24 @@ LL_FORMS = ('none', 'wave', 'table', 'fused_row', 'stream', 'rowwise')
 # SERT_EGRAD_PATH_* / SERT_EGRAD_FIXUP_*, by value
 EGRAD_PATHS = ('none', 'bucket', 'sorted')
 EGRAD_FIXUPS = ('none', 'wave', 'workgroup')
+# SERT_VS_FACT_* / SERT_VS_PLAN_* (the schedule of the vectorspace step, csrc/step_plan.h), by index; the enums the plan's
+# entries take, by value
+VS_FACTS = ('kind', 'host_ar', 'comm', 'timing', 'nstreams', 'n_re', 'big_re', 'big_w', 'keep_grads', 'batch', 'word_dim',
+            'entity_dim', 'num_negatives', 'has_entities', 'sort_free', 'cand_early', 'neg_side_ready', 'has_labels',
+            'next_neg_drawn', 'dh_strip', 'bwd_fused_shape',
+            'k_ext_events', 'k_fork_late', 'k_fork_at', 'k_side_heavy', 'k_re_defer', 'k_early_bucket', 'k_no_early_bucket',
+            'k_early_sort', 'k_no_early_sort', 'k_dw_first', 'k_dp_late', 'k_no_tail', 'k_egrad_group_sum', 'k_bwd_fused')
+VS_KNOB_DEFAULTS = dict(k_ext_events=1, k_fork_late=1, k_fork_at=0, k_side_heavy=1, k_re_defer=1, k_early_bucket=-1,
+                        k_no_early_bucket=0, k_early_sort=0, k_no_early_sort=0, k_dw_first=-1, k_dp_late=1, k_no_tail=0,
+                        k_egrad_group_sum=0, k_bwd_fused=0)
+VS_PLAN = ('fork_at', 'fork_carried', 'fork_recorded', 'dh_event', 'dh_carried', 'order', 'order', 'order', 'order',
+           'entity_queue', 'dense_queue', 'side_meets_fork', 'entity_waits_fork', 'dense_event', 'bwd_fused', 'bucket_early',
+           'sort_early', 'draw_next_neg', 'lazy_join', 'end_join', 'dp_late_join', 'combine_in_tail', 're_in_parts', 'side_small',
+           'small_order', 'split_small', 'defer_re', 'defer_small', 're_on_side')
+VS_FORKS = ('none', 'loss', 'dh')
+VS_PIECES = ('entity', 'dh', 'dense', 'word_sum')
+VS_QUEUES = ('main', 'side', 'third')
+VS_EVENTS = ('none', 'ev_fork', 'ev_dense', 'ev_join3', 'ev_opt_fork')
 
 # every symbol include/sert_hip.h declares
 EXPORTS = [
@@ -45,7 +63,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
     'sert_debug_count_ranks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -447,10 +465,52 @@ class Engine(object):
         assert not any(v), v
         return {'path': path}
 
+    def vs_plan(self):
+        """sert_debug_vs_plan (test hook): the schedule of the step this model issued last, as vs_plan_for returns it."""
+        v = (ctypes.c_int32 * len(VS_PLAN))()
+        self._lib.sert_debug_vs_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_vs_plan(self._h, v, len(VS_PLAN)))
+        return _vs_plan_dict(v)
+
+    def vs_facts(self):
+        """sert_debug_vs_facts (test hook): the facts the last step's schedule was decided from, by name (VS_FACTS)."""
+        v = (ctypes.c_int32 * len(VS_FACTS))()
+        self._lib.sert_debug_vs_facts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_vs_facts(self._h, v, len(VS_FACTS)))
+        return dict(zip(VS_FACTS, (int(x) for x in v)))
+
     def timings(self):
         n = self._lib.sert_timing_count(self._h)
         return {self._lib.sert_timing_name(self._h, i).decode():
                 self._lib.sert_timing_avg_us(self._h, i) for i in range(n)}
+
+
+def _vs_plan_dict(v):
+    v = [int(x) for x in v]
+    p = {name: bool(v[i]) for i, name in enumerate(VS_PLAN) if name != 'order'}
+    p['fork_at'] = VS_FORKS[v[VS_PLAN.index('fork_at')]]
+    p['order'] = tuple(VS_PIECES[x] for x in v[VS_PLAN.index('order'):][:4])
+    for name in ('entity_queue', 'dense_queue'):
+        p[name] = VS_QUEUES[v[VS_PLAN.index(name)]]
+    for name in ('dh_event', 'dense_event', 'small_order'):
+        p[name] = VS_EVENTS[v[VS_PLAN.index(name)]]
+    return p
+
+
+def vs_plan_for(**facts):
+    """sert_debug_vs_plan_for (test hook, no device): the schedule csrc/step_plan.h decides for the given facts (VS_FACTS by
+    name; a fact not given is 0 -- nstreams 2 -- and a knob not given unset), as a dict: flags as bool, 'fork_at', the queues
+    and the events by name, 'order' as a tuple of piece names."""
+    vals = dict({name: 0 for name in VS_FACTS}, nstreams=2, **VS_KNOB_DEFAULTS)
+    unknown = set(facts) - set(vals)
+    assert not unknown, unknown
+    vals.update(facts)
+    f = (ctypes.c_int32 * len(VS_FACTS))(*[int(vals[name]) for name in VS_FACTS])
+    v = (ctypes.c_int32 * len(VS_PLAN))()
+    lib = load()
+    lib.sert_debug_vs_plan_for.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    check(lib.sert_debug_vs_plan_for(f, len(VS_FACTS), v, len(VS_PLAN)))
+    return _vs_plan_dict(v)
 
 
 def comm_unique_id():

@@ -96,6 +96,10 @@ constexpr bool sert_ext_arity_ok(void (*)(Formal...), Actual&&...) {
 // -DSERT_VARIANTS (tools/build_variant.sh variants -DSERT_VARIANTS; run the suite against it with SERT_LIB=...)
 // and a constant nullptr in the product build: those branches fold away.  59 names are read that way; the
 // training step's schedule experiments that no test and no tool named were retired (HISTORY.md section 5).
+// The knobs of the vectorspace step's SCHEDULE (SERT_SIDE_HEAVY, SERT_RE_DEFER; variants: SERT_EXT_EVENTS, SERT_FORK_LATE, SERT_FORK_AT,
+// SERT_EARLY_BUCKET, SERT_NO_EARLY_BUCKET, SERT_EARLY_SORT, SERT_NO_EARLY_SORT, SERT_DW_FIRST, SERT_DP_LATE, SERT_NO_TAIL,
+// SERT_EGRAD_GROUP_SUM, SERT_BWD_FUSED) are read in ONE place, vs_knobs() (host/step_vectorspace.inc), into VsKnobs (step_plan.h),
+// where vs_plan_step turns them and the step's facts into the plan every launch site follows.
 #include <stdlib.h>
 static inline const char* knob(const char* name) { return getenv(name); }
 #ifdef SERT_VARIANTS

@@ -43,6 +43,27 @@ int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n) {
     return 0;
 }
 
+int sert_debug_vs_plan(sert_model* m, int32_t* out, int n) {
+    if (!m || !out || n < 1 || n > SERT_VS_PLAN_COUNT) SERT_FAIL("bad argument");
+    memcpy(out, &m->plan, (size_t)n * sizeof(int32_t));
+    return 0;
+}
+
+int sert_debug_vs_facts(sert_model* m, int32_t* out, int n) {
+    if (!m || !out || n < 1 || n > SERT_VS_FACT_COUNT) SERT_FAIL("bad argument");
+    memcpy(out, &m->plan_facts, (size_t)n * sizeof(int32_t));
+    return 0;
+}
+
+int sert_debug_vs_plan_for(const int32_t* facts, int nfacts, int32_t* out, int n) {
+    if (!facts || !out || nfacts < 1 || nfacts > SERT_VS_FACT_COUNT || n < 1 || n > SERT_VS_PLAN_COUNT) SERT_FAIL("bad argument");
+    VsStepFacts f;
+    memcpy(&f, facts, (size_t)nfacts * sizeof(int32_t));
+    const VsStepPlan p = vs_plan_step(f);
+    memcpy(out, &p, (size_t)n * sizeof(int32_t));
+    return 0;
+}
+
 int sert_debug_scorer_counts(sert_scorer* sc, int64_t* out, int n) {
     if (!sc || !out || n < 1 || n > 6) SERT_FAIL("bad argument");
     for (int i = 0; i < n; ++i) out[i] = i < 5 ? sc->path_counts[i] : (sc->bf16_demoted ? 1 : 0);

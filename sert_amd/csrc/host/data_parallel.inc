@@ -375,7 +375,7 @@ static int allreduce_word_grad(sert_model* m) { return exchange_grad(m, 0); }
 // [small tensors' gradients | loss sum | owned sum of squares].
 static int allreduce_rest(sert_model* m) {
     if (!is_dp(m)) return 0;
-    if (m->dp_late_join) {
+    if (m->plan.dp_late_join) {
         // (every gradient of the side stream -- a sharded entity table's as well as the replicated remainder -- is
         //  complete before the communication stream touches it; the main stream meets them again behind the collectives)
         SERT_HIP(hipEventRecord(m->ev_join, m->stream2));

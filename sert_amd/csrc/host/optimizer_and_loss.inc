@@ -141,44 +141,38 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     // streams on the main one (independent tensors; every gradient is complete here)
     // (loglinear whose dW stayed on the main stream -- small steps: the W, b update (6-8 us alone) stays there too; its fork
     //  and join cost the main queue 2 x 5.6 us for 25 us of side-stream work: round-5 timeline of the W3C settings)
-    const bool side_small = !is_dp(m) && !m->timing.enabled && m->nstreams >= 2 && (is_vs(m) || m->ll_dw_side);
+    const VsStepPlan& P = m->plan;
+    // (ll_dw_side: ll_backward sets it only on a single GPU, out of timing mode, with a side stream -- the conditions of
+    //  plan.side_small; whoever relaxes them there has to repeat them here)
+    const bool side_small = P.side_small || m->ll_dw_side;
     hipStream_t ss = side_small ? m->stream2 : m->stream;
-    if (side_small && m->lazy_join && fork_late_mode(m)) {
-        // (everything the small tensors need was issued on the side stream itself)
-    } else if (side_small && m->lazy_join) {
-        SERT_HIP(hipStreamWaitEvent(ss, m->ev_dense, 0));
-    } else if (side_small) {
-        SERT_HIP(hipEventRecord(m->ev_opt_fork, m->stream));
-        SERT_HIP(hipStreamWaitEvent(ss, m->ev_opt_fork, 0));
-    }
+    // what orders the side stream in front of them: nothing (late fork: everything the small tensors need was issued on the
+    // side stream itself), the end of the dh GEMM, or a fork of its own here
+    const int small_order = m->ll_dw_side ? SERT_VS_EVENT_OPT_FORK : P.small_order;
+    if (small_order == SERT_VS_EVENT_OPT_FORK) SERT_HIP(hipEventRecord(m->ev_opt_fork, m->stream));
+    if (small_order != SERT_VS_EVENT_NONE) SERT_HIP(hipStreamWaitEvent(ss, vs_event(m, small_order), 0));
     // ---- the big tensors, in the reference's parameter order (models.py:542-543, :1105; the
     // tensors are independent): one streaming launch each -- or, data parallel, one launch per
     // owned piece as soon as its gradient slab has been reduce-scattered, the all-gather of the
     // updated slab right behind it
     bool any_ag = false;
-    const int tail_splits = m->tail_splits;
-    m->tail_splits = 0;
-    // side-heavy schedule: the entity table is updated BEHIND the join of the tail (see below)
-    static const bool no_defer = knob("SERT_RE_DEFER") && atoi(knob("SERT_RE_DEFER")) == 0;
-    const bool defer_re = !no_defer && m->side_heavy && side_small && tail_splits > 0 && m->pt_big[1] && is_vs(m) && !c.keep_grads;
-    // ... and so is a SMALL entity table (C2: 1000 x 128, one optimizer_small launch behind the entity chain on the side
+    // plan.defer_re -- side-heavy schedule: the entity table is updated BEHIND the join of the tail (see below)
+    // plan.defer_small -- ... and so is a SMALL entity table (C2: 1000 x 128, one optimizer_small launch behind the entity chain on the side
     // stream).  Round 4, from the GPU timeline: that launch -- 4 us alone, 12-31 us beside the word table's Adam -- ended
     // when the Adam did, and the tail started 13 us later, behind the cross-queue join.  The tail needs nothing of it but
     // the sums of squares of R_e, which the PREVIOUS step's launch leaves (of the values it writes: same shares, same
     // order, the same bits -- sumsq_new_partial); the update itself only has to land before the next loss kernel
     // (settle_entity_update), so the main stream no longer joins the side stream at the end of a step.
-    const bool defer_small = !no_defer && !defer_re && side_small && tail_splits > 0 && !m->pt_big[1] && is_vs(m) && !is_fs(m) &&
-                             !c.keep_grads && m->lazy_join && fork_late_mode(m) && m->n_re > 0;
     const int re_cur = (int)(m->step & 1), re_nxt = re_cur ^ 1;
     const size_t re_cap = (size_t)2 * kOptBlocks;
-    bool small_needs_join = !defer_small;
+    bool small_needs_join = !P.defer_small;
     int re_sq_lo = 0, re_nb = 0;
     for (int i = 0; i < 4; ++i) {
         if (!m->pt_big[i]) continue;
         const ParamTensor t = param_tensor(m, i);
         if (t.n == 0) continue;
         const int tg = i == 0 ? TG_OPT_WORD : TG_OPTIMIZER;
-        if (i == 1 && defer_re) {
+        if (i == 1 && P.defer_re) {
             // (its slots in the partial array stay where they are: the tail reads them from re_sq)
             const int64_t max_nb = t.n >= ((size_t)1 << 24) ? 2 * kOptBlocks : kOptBlocks;
             re_nb = (int)std::min<int64_t>(max_nb, cdiv(cdiv(t.n, 4), 256));
@@ -223,7 +217,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             //  side stream: a W large enough to be a "big tensor" -- d x V_e >= 2^22, C4 -- is updated THERE, behind dW and
             //  its combine; on the main stream its update read dW's gradient while the side stream was still writing it:
             //  two runs of the C4 loglinear step differed by 0.5 % in W after two steps, tools/experiments/r04_ll_c4_rep.py)
-            const bool on_side = side_small && ((i == 1 && m->side_heavy) || (i >= 2 && m->ll_dw_side));
+            const bool on_side = (i == 1 && P.re_on_side) || (i >= 2 && m->ll_dw_side);
             launch_stream_opt(m, on_side ? ss : m->stream, t.p, t.g, t.s0, t.s1, t.n, nb, aa, da,
                               m->red_sq + n_sq, tf,
                               i == 0 ? (unsigned)c.word_dim : 1u);
@@ -288,9 +282,6 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
                            (int64_t)m->rank * count, (uint32_t)c.num_entities, c.seed, (uint64_t)m->step * 2);
         m->neg_alt_step = m->step;
     }
-    // Late fork (fork_late_mode): dW / db were produced on the main stream, dR_e on the side
-    // stream -- W and b are updated on the main stream, R_e on the side stream, no event between.
-    const bool split_small = side_small && m->lazy_join && fork_late_mode(m);
     auto small_tensors = [&](hipStream_t ss, unsigned mask) {
         // everything small goes into one launch (a kernel boundary costs more than updating it)
         ScopedTimer t(m, TG_OPTIMIZER);
@@ -300,7 +291,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             const ParamTensor t2 = param_tensor(m, i);
             if (m->pt_big[i] || t2.n == 0 || !((mask >> i) & 1u)) continue;
             st.p[k] = t2.p; st.g[k] = t2.g; st.s0[k] = t2.s0; st.s1[k] = t2.s1; st.count[k] = t2.n;
-            const bool parts = (i == 1) && m->re_in_parts;
+            const bool parts = (i == 1) && P.re_in_parts;
             st.gparts[k] = parts ? m->epart : nullptr;
             st.ngroups[k] = parts ? m->eg_groups : 0;
             st.gstride[k] = parts ? (unsigned long long)m->n_re : 0ull;
@@ -313,7 +304,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         for (int i = k; i <= 3; ++i) st.first_block[i] = blocks;
         float* sq = m->red_sq + n_sq;
         float* sq_new = nullptr;
-        if (defer_small && mask == 0x2u && blocks > 0) {
+        if (P.defer_small && mask == 0x2u && blocks > 0) {
             // (R_e alone in this launch: its partial slots [n_sq, n_sq + blocks) are read from re_sq by the tail)
             re_sq_lo = n_sq;
             re_nb = blocks;
@@ -341,15 +332,17 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         }
         n_sq += blocks;
     };
-    if (tail_splits > 0) {
+    if (P.combine_in_tail) {
         small_tensors(ss, 0x2u);          // R_e; W and b are updated by the tail launch below
-    } else if (split_small) {
+    } else if (P.split_small) {
+        // Late fork: dW / db were produced on the main stream, dR_e on the side
+        // stream -- W and b are updated on the main stream, R_e on the side stream, no event between.
         small_tensors(m->stream, 0xCu);   // W, b
         small_tensors(ss, 0x2u);          // R_e
     } else {
         small_tensors(ss, 0xEu);
     }
-    if (defer_re && m->re_sq_for[re_cur] != m->step) {
+    if (P.defer_re && m->re_sq_for[re_cur] != m->step) {
         // no previous deferred launch left this step's sums (first step, another schedule in between, the
         // host replaced the table): the same partials from a read-only pass, in front of the join
         hipLaunchKernelGGL(sumsq_like_adam, dim3(re_nb), dim3(256), 0, ss, (const float*)m->re, m->n_re, m->re_sq + re_cur * re_cap);
@@ -359,7 +352,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         SERT_HIP(hipEventRecord(m->ev_small, ss));
         SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_small, 0));
     }
-    if (defer_small && re_nb > 0) {
+    if (P.defer_small && re_nb > 0) {
         // the update is in the side stream; the next reader of R_e (and, through this stream's order, of the negatives
         // drawn in front of this step's fork) waits for it in settle_entity_update
         m->re_sq_for[re_nxt] = m->step + 1;
@@ -369,7 +362,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     // The entity table's L2 + Adam, behind the join: the tail does not wait for it.  Nothing reads R_e, its state or dR_e before the next
     // loss kernel (settle_entity_update), so it streams its 0.96 GB beside the next step's gather and projection GEMM.  It also leaves
     // the sums of squares of the UPDATED table: the next step's regularisation term.
-    if (defer_re) {
+    if (P.defer_re) {
         const ParamTensor t = param_tensor(m, 1);
         launch_stream_opt(m, ss, t.p, t.g, t.s0, t.s1, t.n, re_nb, aa, da, m->red_sq + re_sq_lo, nullptr, 1u,
                           m->re_sq + re_nxt * re_cap);
@@ -386,17 +379,17 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         const float* lp = is_dp(m) ? m->g_loss : (m->loss_from_rows ? m->rowloss : m->red_loss);
         const int nl = is_dp(m) ? 1 : n_loss_partials;
         unsigned* flag = publish ? reinterpret_cast<unsigned*>(loss_dst + 4) : nullptr;
-        if (tail_splits > 0) {
-            if (m->dw_side_first) SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_dense, 0));   // (dW / db slabs: side stream)
+        if (P.combine_in_tail) {
+            if (P.dense_event == SERT_VS_EVENT_DENSE) SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_dense, 0));   // (dW / db slabs: side stream)
             TailArgs ta;
-            ta.part = m->part; ta.splits = tail_splits; ta.stride = m->tail_stride;
+            ta.part = m->part; ta.splits = m->dw_splits; ta.stride = m->tail_stride;
             ta.W = m->W; ta.b = m->b; ta.s0_w = m->s0_w; ta.s1_w = m->s1_w; ta.s0_b = m->s0_b; ta.s1_b = m->s1_b;
             ta.g_w = m->g_w; ta.g_b = m->g_b;
             ta.n_w = (unsigned)m->n_w; ta.n_b = (unsigned)m->n_b;
             ta.aa = aa;
             ta.loss_partials = lp; ta.n_loss = nl;
             ta.sq_partials = m->red_sq; ta.n_sq = n_sq;
-            const bool alt = defer_re || (defer_small && re_nb > 0);
+            const bool alt = P.defer_re || (P.defer_small && re_nb > 0);
             ta.sq_alt = alt ? m->re_sq + re_cur * re_cap : nullptr;
             ta.sq_alt_lo = alt ? re_sq_lo : 0;
             ta.sq_alt_hi = alt ? re_sq_lo + re_nb : 0;
@@ -477,11 +470,7 @@ static int step_forward_backward(sert_model* m, const DataSplit& ds, int64_t bat
     SERT_TRY(ensure_rw_current(m, batch_index));   // (lazy word-table update: the rows this batch reads must be current)
     // Prologue (zeroing, negative sampling): nothing before the loss kernel needs it, so
     // for the vectorspace step it runs on the side stream beside gather + projection.
-    m->lazy_join = false;
     m->ll_dw_side = false;
-    m->dw_side_first = false;
-    m->dp_late_join = false;
-    m->side_heavy = false;
     const bool side_pre = is_vs(m) && !is_fs(m) && !m->timing.enabled && m->nstreams >= 2;
     // One fused prologue launch on the MAIN stream (sampler + zeroing of the small gradient
     // buffers and the row flags) when nothing big has to be zeroed and the device draws the
@@ -496,7 +485,9 @@ static int step_forward_backward(sert_model* m, const DataSplit& ds, int64_t bat
         std::swap(m->neg, m->neg_alt);
         m->neg_alt_step = -1;
     }
-    m->neg_side_ready = have_neg;      // (this step's negatives are complete in the side stream's order: vs_backward)
+    // The step's schedule (step_plan.h), decided once.  (have_neg: this step's negatives are complete in the side stream's order)
+    m->plan_facts = vs_step_facts(m, ds, have_neg);
+    m->plan = vs_plan_step(m->plan_facts);
     const bool fused_pre = side_pre && negatives == nullptr && fused_prologue_applies(m);
     hipStream_t pre = (side_pre && !fused_pre) ? m->stream2 : m->stream;
     *fused_pre_out = (pre == m->stream);   // no side-stream prologue: no end-of-step event needed

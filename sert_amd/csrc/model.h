@@ -4,6 +4,7 @@
 #include <string>
 #include "common.h"
 #include "word_index.h"
+#include "step_plan.h"
 #include "kernels_xchg.h"
 #include "kernels_opt.h"   // (TailArgs: a deferred tail is kept by value)
 #include "kernels_rank.h"  // (RankSortScratch: the scorer keeps its ranker's scratch)
@@ -99,19 +100,22 @@ struct sert_model {
     hipEvent_t ev_loss = nullptr;    // the step's loss has been copied out
     hipEvent_t ev_dense = nullptr;   // dW, db and the loss partials are complete (main stream)
     bool step_done_pending = false;  // the previous step ended without recording ev_step_done
-    bool re_in_parts = false;        // this step: dR_e is still the row groups' partial tables (summed by the optimiser)
-    bool fork_bound = false;         // ev_fork rides on the NCE kernel's completion signal (no record needed)
+    // The schedule of the training step in flight (step_plan.h): decided once, at the head of step_forward_backward, from
+    // vs_step_facts (kept beside it: sert_debug_vs_facts); the backward, the update (optimizer_and_loss) and allreduce_rest
+    // issue what it says.  The default plan -- everything on the main queue -- for a loglinear step.
+    // INVARIANT: the plan of backward time holds at update time.  Only a run-ahead backward has its update in a later call, and
+    // whatever the plan depends on that can change after sert_create discards a run-ahead: sert_timing_enable through
+    // can_speculate_step (train_step_async reissues the backward); attaching a communicator, uploading data, sert_set_step
+    // and sert_set_tensor through invalidate_speculation; a model whose communicator was destroyed trains no more.  The
+    // knobs are read once per process.
+    sert::VsStepFacts plan_facts;
+    sert::VsStepPlan plan;
     bool egrad_ranges = false;       // SERT_EGRAD_RANGES=1 at sert_create: the one-launch range kernel for few pairs over a mid-size table (opt-in)
     bool egrad_force_sort = false;   // SERT_EGRAD_SORT=1 at sert_create: the sorted entity-gradient path whatever the shape
     bool events_device_scope = false;  // the intra-model events carry hipEventDisableSystemFence (no communicator; host/api_model.inc: create_intra_events)
-    bool lazy_join = false;          // this step: the main stream never waits for the entity chain
     int num_cus = 256;               // compute units of the device (persistent launches: one workgroup per CU)
     bool proj_fused = false;         // gather + mean-pool + projection in one launch where the shape allows (kernels_proj.h; opt-in, SERT_PROJ_FUSED=1)
     bool ll_dw_side = false;         // loglinear, this step: dW, db and their combine were issued on the side stream
-    bool dw_side_first = false;      // this step: dW / db came from the side stream, FIRST in its chain (ev_dense marks them)
-    bool dp_late_join = false;       // data parallel, asynchronous communicator: the side stream (entity chain, dW, db, loss sum) is
-                                     // joined by the COMMUNICATION stream in front of the small all-reduce, not by the main stream
-    bool side_heavy = false;         // this step: entity chain, entity-table optimiser and dW on the side stream (big R_e)
     // side-heavy schedule: the entity table's update is DEFERRED past the step's tail -- it only has to land
     // before the next reader of R_e (the next loss kernel); the sums of squares the tail needs were left by
     // the previous step's launch (re_sq[k]: partials of the updated table, for optimiser step re_sq_for[k])
@@ -127,9 +131,6 @@ struct sert_model {
     // 3 = + dW on a third (0.403: every cross-queue dependency costs 15-25 us of idle GPU)
     int nstreams = 2;
     int64_t hint_next = -1;        // sert_hint_next_batch
-    bool neg_side_ready = false;   // this step's negatives were drawn on the side stream during the previous step
-    bool sort_early = false;       // this step's entity keys were sorted in front of the fork (host/step_vectorspace.inc: vs_backward, early_sort)
-    bool bucket_early = false;     // this step's egrad_bucket ran in front of the fork (host/step_vectorspace.inc: vs_backward)
     // lazy dense update of the word table (kernels_opt.h: dense_update_lazy)
     int32_t* rw_last[2] = {nullptr, nullptr};   // per word row: updates applied to its stored (p, state0, state1)
     int rw_last_cur = 0;           // which of the two holds the current values
@@ -232,11 +233,11 @@ struct sert_model {
     float* skbuf = nullptr;       // split-K partials of the long-K dX GEMMs (grown on demand)
     size_t skbuf_count = 0;
     // single-GPU vectorspace step: split-K combine + W, b update + loss finalisation as one launch
-    // (kernels_opt.h: vs_tail).  tail_splits > 0: this step's dW / db still sit in `part` as that
-    // many partial slabs, tail_stride elements apart
+    // (kernels_opt.h: vs_tail).  plan.combine_in_tail: this step's dW / db still sit in `part` as
+    // dw_splits partial slabs, tail_stride elements apart
     unsigned long long* tail_blk = nullptr;
     unsigned tail_launch_seq = 0;
-    int tail_splits = 0;
+    int dw_splits = 0;
     size_t tail_stride = 0;
     // A hinted step DEFERS that launch: its workgroups lead the gather launch of the run-ahead step (kernels_vs.h:
     // vs_gather_mean_tail; host/step_vectorspace.inc: vs_project).  tail_defer: sert_train_batch allows it for the step it is

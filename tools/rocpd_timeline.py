@@ -3,6 +3,9 @@
 between two consecutive launches of the step's first kernel, with its start offset, duration,
 queue and the idle gap of its queue before it.
     python tools/rocpd_timeline.py results.db [first_kernel_substring] [which_step_from_the_end]
+    python tools/rocpd_timeline.py --sequence results.db
+--sequence: per queue (numbered by first appearance) every kernel of the trace in order of dispatch, name and grid size --
+what two builds that issue the same launches have in common (the interleaving of the queues is timing).
 """
 import re
 import sqlite3
@@ -32,5 +35,21 @@ def main(path, first='vs_gather_mean', back=3):
         (rows[b][1] - t0) / 1e3, sum(r[2] - r[1] for r in rows[a:b]) / 1e3))
 
 
+def sequence(path):
+    db = sqlite3.connect(path)
+    cols = [r[1] for r in db.execute("pragma table_info(kernels)")]
+    q = 'queue_id' if 'queue_id' in cols else ('stream_id' if 'stream_id' in cols else 'tid')
+    grid = [c for c in cols if 'grid' in c.lower()] or ['0']
+    rows = db.execute("select name, %s, %s from kernels order by start" % (q, ', '.join(grid))).fetchall()
+    queues = {}
+    for r in rows:
+        queues.setdefault(r[1], []).append('%s %s' % (short(r[0]), 'x'.join(str(g) for g in r[2:])))
+    for k, seq in enumerate(queues.values()):
+        for line in seq:
+            print('q%d %s' % (k, line))
+
+
 if __name__ == '__main__':
+    if sys.argv[1] == '--sequence':
+        sys.exit(sequence(sys.argv[2]))
     main(sys.argv[1], *(sys.argv[2:3] or ['vs_gather_mean']), *[int(x) for x in sys.argv[3:4]])
