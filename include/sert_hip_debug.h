@@ -63,6 +63,34 @@ enum {
 };
 int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n);
 
+/* What the LAST backward of this model launched for the per-word sums -- the word-table gradient of the vectorspace models
+ * (word_grad_segsum) or dZu of the loglinear model (dzu_from_dj), both in csrc/host/lazy_segsum.inc over the tree of
+ * csrc/word_index.h -- host record written where the launches are made, test hook, no device is touched:
+ * out[0] one of SERT_WGRAD_PATH_*, out[1] levels of the batch's tree, out[2] tree launches made (levels 1 and 2 in one launch
+ * count once), out[3] dense words of the batch, out[4] one of SERT_WGRAD_HEAVY_*, out[5] batch rows per workgroup of the dense
+ * pass, out[6] its row blocks, out[7] 1 when the dense words' combine was launched alone, out[8] 1 when level 0 is sorted by
+ * length with the first row in the descriptor; then per tree launch k < 6: out[10 + 2 k] one of SERT_WGRAD_FORM_*,
+ * out[11 + 2 k] its gridDim.y.  n <= 24; all zero before the first backward.  tests/test_gpu_wgrad_cases.py asserts through this
+ * that every count plan of tests/wgrad_cases.py reaches the kernels it is there for. */
+enum { SERT_WGRAD_PATH_NONE = 0, SERT_WGRAD_PATH_WORD_GRAD = 1, SERT_WGRAD_PATH_DZU = 2 };
+enum {
+    SERT_WGRAD_HEAVY_NONE = 0,
+    SERT_WGRAD_HEAVY_FUSED = 1,         /* extra workgroups of the tree's launches (segsum_rows_plus / segsum_rows_plus_ll) */
+    SERT_WGRAD_HEAVY_TWO_LAUNCHES = 2,  /* segsum_heavy + segsum_heavy_combine in front of the tree */
+    SERT_WGRAD_HEAVY_WIDE = 3           /* segsum_heavy_wide + segsum_heavy_combine_ll behind the tree */
+};
+enum {
+    SERT_WGRAD_FORM_ROWS32 = 1,        /* segsum_rows<32> */
+    SERT_WGRAD_FORM_ROWS64 = 2,        /* segsum_rows<64> (loglinear: <64, true, true[, true]>) */
+    SERT_WGRAD_FORM_SCALAR = 3,        /* segsum_rows_scalar<false> / <true> */
+    SERT_WGRAD_FORM_ROWS_PLUS = 4,     /* segsum_rows_plus */
+    SERT_WGRAD_FORM_ROWS_PLUS_LL = 5,  /* segsum_rows_plus_ll */
+    SERT_WGRAD_FORM_UPPER_FUSED = 6,   /* segsum_upper_fused */
+    SERT_WGRAD_FORM_SCALAR_LL = 7,     /* segsum_rows_scalar<true, true> */
+    SERT_WGRAD_FORM_BUNDLED = 8        /* segsum_rows_bundled (variants build) */
+};
+int sert_debug_wgrad_plan(sert_model* m, int32_t* out, int n);
+
 /* The SCHEDULE of the vectorspace training step (csrc/step_plan.h): which queue the pieces of the backward and of the update
  * went to, in what order, and which events order them.  sert_debug_vs_plan: the plan of the step this model issued LAST, out[i]
  * by SERT_VS_PLAN_*, n <= SERT_VS_PLAN_COUNT -- host record, no device is touched; the default plan (everything on the main
@@ -183,8 +211,9 @@ int sert_debug_row_lists(const uint32_t* allbits, int world, int rank, int64_t n
  * kernels walk it: grad_out[vocab][d] = the word-table gradient of batch `batch` for source rows src[B][d] (dh), i.e.
  * sum over the occurrences of a word of src[row] / divisor.  row_groups > 1: level 0 cut into row ranges (XCD lists);
  * dense_heavy: bit 0 = the batch's heaviest words summed outside the tree, bit 1 = level 0 sorted by item length with every
- * item's first row number in its descriptor (what the vectorspace models upload).  stats[8] = {levels, items, partial rows, final items,
- * dense words, row groups, level-0 items, distinct words}. */
+ * item's first row number in its descriptor (what the vectorspace models upload).  stats[11] = {levels, items, partial rows, final items,
+ * dense words, row groups, level-0 items, distinct words, fused_upper_ok (levels 1 and 2 may run as one launch), heavy_cnt (words
+ * whose level-1 chunks are summed again at level 2 of a three-level tree), level-1 items}. */
 int sert_debug_word_index_sum(const void* ids, int id_bytes, int64_t num_batches, int B, int n, int vocab, int row_groups,
                               int dense_heavy, int64_t batch, const float* src, int d, float divisor, float* grad_out,
                               int64_t* stats);

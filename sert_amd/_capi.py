@@ -30,6 +30,9 @@ LL_FORMS = ('none', 'wave', 'table', 'fused_row', 'stream', 'rowwise')
 # SERT_EGRAD_PATH_* / SERT_EGRAD_FIXUP_*, by value
 EGRAD_PATHS = ('none', 'bucket', 'sorted')
 EGRAD_FIXUPS = ('none', 'wave', 'workgroup')
+WGRAD_PATHS = ('none', 'word_grad', 'dzu')                               # SERT_WGRAD_PATH_*
+WGRAD_HEAVY = ('none', 'fused', 'two_launches', 'wide')                  # SERT_WGRAD_HEAVY_*
+WGRAD_FORMS = ('none', 'rows32', 'rows64', 'scalar', 'rows_plus', 'rows_plus_ll', 'upper_fused', 'scalar_ll', 'bundled')   # SERT_WGRAD_FORM_*
 # SERT_VS_FACT_* / SERT_VS_PLAN_* (the schedule of the vectorspace step, csrc/step_plan.h), by index; the enums the plan's
 # entries take, by value
 VS_FACTS = ('kind', 'host_ar', 'comm', 'timing', 'nstreams', 'n_re', 'big_re', 'big_w', 'keep_grads', 'batch', 'word_dim',
@@ -63,7 +66,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
     'sert_debug_count_ranks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -464,6 +467,24 @@ class Engine(object):
             return {'path': path, 'sort_bits': v[7], 'passes': v[8], 'vec': v[9], 'nch': v[10], 'fixup': EGRAD_FIXUPS[v[11]]}
         assert not any(v), v
         return {'path': path}
+
+    def wgrad_plan(self):
+        """sert_debug_wgrad_plan (test hook): what the last backward launched for the per-word sums (the word-table gradient of a
+        vectorspace model, dZu of a loglinear one).  {'path': 'none'} before the first backward; otherwise 'levels' of the
+        batch's tree, 'launches' [(form, gridDim.y)] of the tree in order, 'dense_cnt', 'heavy' (none / fused / two_launches /
+        wide) with 'heavy_rows' per workgroup and 'heavy_blocks', 'combine_alone', 'slot_is_row'."""
+        v = (ctypes.c_int32 * 24)()
+        self._lib.sert_debug_wgrad_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_wgrad_plan(self._h, v, 24))
+        v = [int(x) for x in v]
+        path = WGRAD_PATHS[v[0]]
+        if path == 'none':
+            assert not any(v), v
+            return {'path': path}
+        assert v[2] <= 6, v
+        return {'path': path, 'levels': v[1], 'launches': [(WGRAD_FORMS[v[10 + 2 * k]], v[11 + 2 * k]) for k in range(v[2])],
+                'dense_cnt': v[3], 'heavy': WGRAD_HEAVY[v[4]], 'heavy_rows': v[5], 'heavy_blocks': v[6],
+                'combine_alone': bool(v[7]), 'slot_is_row': bool(v[8])}
 
     def vs_plan(self):
         """sert_debug_vs_plan (test hook): the schedule of the step this model issued last, as vs_plan_for returns it."""
@@ -883,13 +904,14 @@ def debug_word_index_sum(ids, vocab, src, batch=0, row_groups=1, dense_heavy=Fal
     assert src.shape[0] == B
     d = src.shape[1]
     out = np.empty((vocab, d), dtype=np.float32)
-    stats = np.zeros(8, dtype=np.int64)
+    stats = np.zeros(11, dtype=np.int64)
     lib.sert_debug_word_index_sum.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                               ctypes.c_void_p, ctypes.c_void_p]
     check(lib.sert_debug_word_index_sum(_addr(ids), ids.dtype.itemsize, nb, B, n, int(vocab), int(row_groups), int(bool(dense_heavy)) | (2 if sort_level0 else 0),
                                         int(batch), _addr(src), d, float(divisor), _addr(out), _addr(stats)))
-    keys = ('levels', 'items', 'partial_rows', 'final_items', 'dense_words', 'row_groups', 'level0_items', 'distinct_words')
+    keys = ('levels', 'items', 'partial_rows', 'final_items', 'dense_words', 'row_groups', 'level0_items', 'distinct_words',
+            'fused_upper_ok', 'heavy_cnt', 'level1_items')
     return out, dict(zip(keys, [int(x) for x in stats]))
 
 

@@ -43,6 +43,12 @@ int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n) {
     return 0;
 }
 
+int sert_debug_wgrad_plan(sert_model* m, int32_t* out, int n) {
+    if (!m || !out || n < 1 || n > 24) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = m->wg_plan[i];
+    return 0;
+}
+
 int sert_debug_vs_plan(sert_model* m, int32_t* out, int n) {
     if (!m || !out || n < 1 || n > SERT_VS_PLAN_COUNT) SERT_FAIL("bad argument");
     memcpy(out, &m->plan, (size_t)n * sizeof(int32_t));
@@ -248,6 +254,7 @@ int sert_debug_word_index_sum(const void* ids, int id_bytes, int64_t num_batches
     }
     stats[0] = bx.nlevels; stats[1] = items_total; stats[2] = bx.part_rows; stats[3] = finals; stats[4] = bx.dense_cnt;
     stats[5] = bx.row_groups; stats[6] = bx.item_cnt[0]; stats[7] = bx.num_distinct;
+    stats[8] = bx.fused_upper_ok ? 1 : 0; stats[9] = bx.heavy_cnt; stats[10] = bx.nlevels > 1 ? bx.item_cnt[1] : 0;
     return 0;
 }
 

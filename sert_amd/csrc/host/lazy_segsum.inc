@@ -102,6 +102,11 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
     const int d = m->cfg.word_dim;
     if ((size_t)batch_index >= ds.idx_batches.size()) SERT_FAIL("batch has no word index");
     const BatchIndex& bx = ds.idx_batches[(size_t)batch_index];
+    // (sert_debug_wgrad_plan: what is launched below, recorded beside every launch)
+    int32_t* wp = m->wg_plan;
+    for (int i = 0; i < 24; ++i) wp[i] = 0;
+    wp[0] = SERT_WGRAD_PATH_WORD_GRAD; wp[1] = bx.nlevels; wp[3] = bx.dense_cnt; wp[8] = bx.slot_is_row ? 1 : 0;
+    auto wp_launch = [&](int form, int grid_y) { if (wp[2] < 6) { wp[10 + 2 * wp[2]] = form; wp[11 + 2 * wp[2]] = grid_y; } ++wp[2]; };
     unsigned char* touched = nullptr;   // (row flags are static per batch: DataSplit::idx_touched_bits)
     static const bool no_fused_upper = variant_knob("SERT_SEG_NO_FUSED_UPPER") != nullptr;   // cross-check knob
     const bool fused_upper = !no_fused_upper && bx.fused_upper_ok && ds.idx_heavy && d % 4 == 0 &&
@@ -125,8 +130,10 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             hjob.kind = 1; hjob.rpb = heavy_rows_fused(B); hjob.extra = cdiv(B, hjob.rpb); hjob.src = src; hjob.cnt16 = cnt; hjob.part = m->hpart;
             hjob.words = (const int32_t*)ds.idx_dense_words + (size_t)batch_index * kHeavyMax;
             hjob.nheavy = bx.dense_cnt; hjob.nblocks = hjob.extra; hjob.B = B;
+            wp[4] = SERT_WGRAD_HEAVY_FUSED; wp[5] = hjob.rpb; wp[6] = hjob.extra;
         } else {
         const int nblk = cdiv(B, kHeavyRowsPerBlock);
+        wp[4] = SERT_WGRAD_HEAVY_TWO_LAUNCHES; wp[5] = kHeavyRowsPerBlock; wp[6] = nblk;
         const size_t lds = (size_t)4 * kHeavyMax * 32 * sizeof(float4);   // 32 KB
         hipLaunchKernelGGL(segsum_heavy, dim3(nblk * cdiv(d4, 32)), dim3(1024), lds, m->stream, src, cnt, B, d, m->hpart);
         hipLaunchKernelGGL(segsum_heavy_combine, dim3(bx.dense_cnt, cdiv(d4, 32)), dim3(256), 0, m->stream,
@@ -144,6 +151,7 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             hipLaunchKernelGGL(segsum_upper_fused, dim3(nb_normal + bx.heavy_cnt, cdiv(d / 4, 32)), dim3(1024), 0, m->stream,
                                m->wpart + (size_t)bx.part_off[0] * d, ds.idx_items + bx.item_off[1], nitems, nb_normal,
                                ds.idx_heavy + bx.heavy_off, m->g_rw, d, divisor);
+            wp_launch(SERT_WGRAD_FORM_UPPER_FUSED, cdiv(d / 4, 32));
             break;
         }
         const float* in = (l == 0) ? src : m->wpart + (size_t)bx.part_off[l - 1] * d;
@@ -156,6 +164,7 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             j.slot_is_row = (l == 0 && bx.slot_is_row) ? 1 : 0;
             hipLaunchKernelGGL(segsum_rows_plus, dim3(j.extra + cdiv(nitems, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows, items,
                                nitems, m->g_rw, pout, d, divisor, j);
+            wp_launch(SERT_WGRAD_FORM_ROWS_PLUS, cdiv(d / 4, 32));
             if (l == 1) heavy_combined = true;
             continue;
         }
@@ -165,6 +174,7 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
         if (l == 0 && d % 4 == 0 && bx.bundle_cnt > 0 && ds.idx_bundles && bx.row_groups == 1) {
             hipLaunchKernelGGL(segsum_rows_bundled, dim3(cdiv(bx.bundle_cnt, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows,
                                items, (const int32_t*)ds.idx_bundles + bx.bundle_off, (int)bx.bundle_cnt, m->g_rw, pout, d, divisor);
+            wp_launch(SERT_WGRAD_FORM_BUNDLED, cdiv(d / 4, 32));
             continue;
         }
 #endif
@@ -183,24 +193,30 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             }
             const int ipb = (d / 4 <= 32 || seg32y) ? 8 : 4;
             const int gx = xl.on ? 8 * cdiv(longest, ipb) : cdiv(nitems, ipb);
-            if (d / 4 <= 32)
+            if (d / 4 <= 32) {
                 hipLaunchKernelGGL((segsum_rows<32>), dim3(gx), dim3(256), 0, m->stream,
                                    in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
-            else if (seg32y)
+                wp_launch(SERT_WGRAD_FORM_ROWS32, 1);
+            } else if (seg32y) {
                 hipLaunchKernelGGL((segsum_rows<32>), dim3(gx, cdiv(d / 4, 32)), dim3(256), 0, m->stream,
                                    in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
-            else   // rows wider than 64 float4 chunks (d = 300: 75): the rest goes to further column groups
+                wp_launch(SERT_WGRAD_FORM_ROWS32, cdiv(d / 4, 32));
+            } else {   // rows wider than 64 float4 chunks (d = 300: 75): the rest goes to further column groups
                 hipLaunchKernelGGL((segsum_rows<64>), dim3(gx, cdiv(d / 4, 64)), dim3(256), 0, m->stream,
                                    in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
+                wp_launch(SERT_WGRAD_FORM_ROWS64, cdiv(d / 4, 64));
+            }
         } else {
             hipLaunchKernelGGL((segsum_rows_scalar<false>), dim3(cdiv(nitems, 4), cdiv(d, 64)), dim3(256), 0, m->stream, in,
                                rows, items, nitems, m->g_rw, pout, d, divisor, touched);
+            wp_launch(SERT_WGRAD_FORM_SCALAR, cdiv(d, 64));
         }
     }
     if (heavy_fused && !heavy_combined) {   // (no level 1, or the fused upper levels took it: the combine alone)
         const PlusJob j = heavy_combine_job();
         hipLaunchKernelGGL(segsum_rows_plus, dim3(j.extra, cdiv(d / 4, 32)), dim3(256), 0, m->stream, (const float*)nullptr,
                            (const int32_t*)nullptr, (const int4*)nullptr, 0, m->g_rw, (float*)nullptr, d, divisor, j);
+        wp[7] = 1;
     }
     return 0;
 }
@@ -213,6 +229,11 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
 static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     const int V = m->cfg.num_entities;
     const BatchIndex& bx = ds.idx_batches[(size_t)batch_index];
+    // (sert_debug_wgrad_plan: what is launched below for the V_e-wide sums, recorded beside every launch)
+    int32_t* wp = m->wg_plan;
+    for (int i = 0; i < 24; ++i) wp[i] = 0;
+    wp[0] = SERT_WGRAD_PATH_DZU; wp[1] = bx.nlevels; wp[3] = bx.dense_cnt; wp[8] = bx.slot_is_row ? 1 : 0;
+    auto wp_launch = [&](int form, int grid_y) { if (wp[2] < 6) { wp[10 + 2 * wp[2]] = form; wp[11 + 2 * wp[2]] = grid_y; } ++wp[2]; };
     // odd V_e: the scalar sums and the finishing expression ride the V_e-wide launches (kernels_seg.h: segsum_rows_scalar<true, true>)
     static const bool split_odd = variant_knob("SERT_LL_DZU_SPLIT") != nullptr;   // the three extra launches, for A/B
     const bool fused_odd = V % 4 != 0 && !split_odd;
@@ -238,6 +259,7 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         ll_job.j.cnt16 = ds.idx_dense_counts + (size_t)batch_index * B; ll_job.j.part = m->hpart;
         ll_job.j.nheavy = bx.dense_cnt; ll_job.j.nblocks = ll_job.j.extra; ll_job.j.B = B;
         ll_job.logp = m->Zu; ll_job.rsum = m->ll_rsum;
+        wp[4] = SERT_WGRAD_HEAVY_FUSED; wp[5] = ll_job.j.rpb; wp[6] = ll_job.j.extra;
     }
     for (int l = 0; l < bx.nlevels; ++l) {
         const int nitems = bx.item_cnt[l];
@@ -259,26 +281,31 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
                 if (l == 1) { j.j.kind = 2; j.j.extra = bx.dense_cnt; j.j.src = m->hpart; ll_heavy_combined = true; }
                 hipLaunchKernelGGL(segsum_rows_plus_ll, dim3(j.j.extra + cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0, m->stream, in,
                                    rows, items, nitems, m->dZu, pout, V, dsl, j);
+                wp_launch(SERT_WGRAD_FORM_ROWS_PLUS_LL, cdiv(V / 4, 64));
                 continue;
             }
             hipLaunchKernelGGL((segsum_rows<64, true, true, true>), dim3(cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0,
                                m->stream, in, rows, items, nitems, m->dZu, pout, V, 1.0f,
                                (unsigned char*)nullptr, 1, (const float*)m->Zu,
                                (const float*)m->ll_rsum, dsl);
+            wp_launch(SERT_WGRAD_FORM_ROWS64, cdiv(V / 4, 64));
         } else if (V % 4 == 0) {
             hipLaunchKernelGGL((segsum_rows<64, true, true>), dim3(cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0,
                                m->stream, in, rows, items, nitems, m->dZu, pout, V, 1.0f,
                                (unsigned char*)nullptr, 1, (const float*)m->Zu,
                                (const float*)m->ll_rsum);
+            wp_launch(SERT_WGRAD_FORM_ROWS64, cdiv(V / 4, 64));
         } else if (fused_odd) {
             hipLaunchKernelGGL((segsum_rows_scalar<true, true>), dim3(cdiv(nitems, 4), cdiv(V, 64)), dim3(256), 0, m->stream, in,
                                rows, items, nitems, m->dZu, pout, V, 1.0f, (unsigned char*)nullptr, 1, (const float*)m->Zu,
                                (const float*)((l == 0) ? m->ll_r : m->ll_rpart + (size_t)bx.part_off[l - 1]),
                                (l == 0) ? (const int32_t*)(ds.idx_rows + bx.rows_off) : (const int32_t*)nullptr,
                                m->ll_rsum, m->ll_rpart + (size_t)bx.part_off[l]);
+            wp_launch(SERT_WGRAD_FORM_SCALAR_LL, cdiv(V, 64));
         } else {
             hipLaunchKernelGGL((segsum_rows_scalar<true>), dim3(cdiv(nitems, 4), cdiv(V, 64)), dim3(256), 0, m->stream, in,
                                rows, items, nitems, m->dZu, pout, V, 1.0f, (unsigned char*)nullptr, 1);
+            wp_launch(SERT_WGRAD_FORM_SCALAR, cdiv(V, 64));
         }
     }
     if (ll_heavy_fused && !ll_heavy_combined) {   // (no level 1: the combine alone)
@@ -288,12 +315,14 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         j.j.kind = 2; j.j.extra = bx.dense_cnt; j.j.src = m->hpart;
         hipLaunchKernelGGL(segsum_rows_plus_ll, dim3(j.j.extra, cdiv(V / 4, 64)), dim3(256), 0, m->stream, (const float*)nullptr,
                            (const int32_t*)nullptr, (const int4*)nullptr, 0, m->dZu, (float*)nullptr, V, j.dense, j);
+        wp[7] = 1;
     }
     if (V % 4 == 0 && bx.dense_cnt > 0 && !ll_heavy_fused) {
         // Heavy words: sum_i cnt[i][h] dJ[i, :] by ONE pass over dJ (262 MB at C2 dims) instead of one 4 kB
         // row fetch per occurrence -- a dozen words hold over half of a Zipfian batch's tokens
         const int B = m->cfg.batch_size, d4 = V / 4;
         const int nblk = cdiv(B, kHeavyRowsPerBlock);
+        wp[4] = SERT_WGRAD_HEAVY_WIDE; wp[5] = kHeavyRowsPerBlock; wp[6] = nblk;
         const uint4* cnt = ds.idx_dense_counts + (size_t)batch_index * B;
         static const bool attr_set = hipFuncSetAttribute((const void*)segsum_heavy_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          2 * kHeavyMax * 128 * (int)sizeof(float4)) == hipSuccess;

@@ -201,6 +201,9 @@ struct sert_model {
     int sort_bits = 1;
     // what the last vs_backward launched for dR_e, recorded where the launches are made: sert_debug_egrad_plan (sert_hip_debug.h)
     int32_t eg_plan[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // what the last backward launched for the per-word sums (word_grad_segsum / dzu_from_dj), recorded where the launches are
+    // made: sert_debug_wgrad_plan (sert_hip_debug.h)
+    int32_t wg_plan[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // loglinear activations
     float *G = nullptr;           // (B*n, d) gathered rows
     float *Z = nullptr;           // (B*n, V_e) logits -> probabilities -> dZ

@@ -75,6 +75,21 @@ def test_egrad_plan_hook_refuses_bad_arguments(hip_lib):
         assert re.search(r'\bSERT_EGRAD_FIXUP_%s = %d\b' % (name, k), src), name
 
 
+def test_wgrad_plan_hook_refuses_bad_arguments(hip_lib):
+    """sert_debug_wgrad_plan (include/sert_hip_debug.h) touches no device: without a model it fails with a message, and the
+    binding knows the values of its three enums by name."""
+    v = (ctypes.c_int32 * 24)()
+    hip_lib.sert_debug_wgrad_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    assert hip_lib.sert_debug_wgrad_plan(None, v, 24) != 0
+    assert b'bad argument' in hip_lib.sert_last_error()
+    src = open(os.path.join(ROOT, 'include', 'sert_hip_debug.h')).read()
+    for prefix, names in (('PATH', _capi.WGRAD_PATHS), ('HEAVY', _capi.WGRAD_HEAVY), ('FORM', _capi.WGRAD_FORMS)):
+        for k, name in enumerate(names):
+            if prefix == 'FORM' and k == 0:
+                continue                      # (no launch: the header has no name for it)
+            assert re.search(r'\bSERT_WGRAD_%s_%s = %d\b' % (prefix, name.upper(), k), src), (prefix, name, k)
+
+
 @pytest.mark.skipif(_capi.device_count() > 0, reason='needs a GPU-less host')
 def test_fails_loudly_without_gpu(hip_lib):
     from sert_amd import models
