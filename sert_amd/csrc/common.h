@@ -1,84 +1,12 @@
-// Shared helpers for the gfx950 kernels of libsert_hip.so.
+// Shared by the gfx950 kernels of libsert_hip.so and their host code: the environment switches (knob / variant_knob), the
+// error plumbing (SERT_FAIL / SERT_HIP / SERT_TRY), and the device helpers -- wave and workgroup reductions, ranking keys,
+// the reference's clips and sigmoid, the write-through stores.  How a kernel is started is launch.h; how it is timed,
+// host/timing.inc.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
-
-// An event bound to a kernel's OWN completion signal (hipExtLaunchKernel's stop event) instead of
-// a barrier packet queued behind it: hipEventRecord stalls its queue for ~7 us on this system
-// (the next dispatch waits for the command processor to retire the barrier packet), the stop
-// event of the kernel itself does not.  set_stop_event(ev) arms the NEXT SERT_LAUNCH on this
-// host thread.
-inline hipEvent_t& pending_stop_event() {
-    static thread_local hipEvent_t ev = nullptr;
-    return ev;
-}
-inline void set_stop_event(hipEvent_t ev) { pending_stop_event() = ev; }
-#define SERT_LAUNCH(kernel, grid, block, shmem, stream, ...)                                   \
-    do {                                                                                       \
-        hipEvent_t sert_stop_ev_ = ::pending_stop_event();                                     \
-        ::pending_stop_event() = nullptr;                                                      \
-        if (sert_stop_ev_)                                                                     \
-            hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, nullptr, sert_stop_ev_,  \
-                                  0, __VA_ARGS__);                                             \
-        else                                                                                   \
-            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);               \
-    } while (0)
-
-// ---- in-step kernel timing -------------------------------------------------------------------------------------
-// sert_timing_enable(m, 2): the NORMAL schedule (all streams, run-ahead), with every plain kernel launch inside a timing
-// group bound to a (start, stop) event pair of its own through hipExtLaunchKernelGGL -- the kernel's own dispatch
-// timestamps, no barrier packets, no serialisation: what a kernel takes IN THE STEP, beside whatever the other queue runs
-// (mode 1 times every group alone on one queue).  The hook is thread-local and null outside a timing scope of a model
-// in that mode: one predictable branch per launch.  Launches that carry a completion event of the schedule (SERT_LAUNCH
-// with set_stop_event) keep it and are not timed.
-struct InStepHook {
-    void (*next)(void* ctx, hipEvent_t* start, hipEvent_t* stop);
-    void* ctx;
-};
-inline InStepHook& instep_hook() {
-    static thread_local InStepHook h = {nullptr, nullptr};
-    return h;
-}
-// (hip_ext.h's hipExtLaunchKernelGGL wants the call's argument types to BE the kernel's parameter types; the launches of
-//  this library rely on the implicit conversions and the default arguments that <<<>>> allows: so the timed launch converts
-//  the arguments to the kernel's own parameter types itself, and a call that leaves trailing parameters to their defaults
-//  -- which a function pointer does not carry -- is simply not timed)
-#include <tuple>
-#include <utility>
-template <typename... Formal, typename... Actual, size_t... I>
-inline bool sert_ext_launch_impl(void (*kernel)(Formal...), dim3 grid, dim3 block, unsigned shmem, hipStream_t stream,
-                                 hipEvent_t start, hipEvent_t stop, std::index_sequence<I...>, Actual&&... args) {
-    std::tuple<std::remove_cv_t<Formal>...> tup{static_cast<std::remove_cv_t<Formal>>(std::forward<Actual>(args))...};
-    void* ptrs[sizeof...(Formal) ? sizeof...(Formal) : 1] = {(void*)&std::get<I>(tup)...};
-    return hipExtLaunchKernel((const void*)kernel, grid, block, ptrs, shmem, stream, start, stop, 0) == hipSuccess;
-}
-template <typename... Formal, typename... Actual>
-inline bool sert_ext_launch(void (*kernel)(Formal...), dim3 grid, dim3 block, unsigned shmem, hipStream_t stream,
-                            hipEvent_t start, hipEvent_t stop, Actual&&... args) {
-    if constexpr (sizeof...(Formal) != sizeof...(Actual)) {
-        return false;
-    } else {
-        return sert_ext_launch_impl(kernel, grid, block, shmem, stream, start, stop, std::index_sequence_for<Formal...>{},
-                                    std::forward<Actual>(args)...);
-    }
-}
-template <typename... Formal, typename... Actual>
-constexpr bool sert_ext_arity_ok(void (*)(Formal...), Actual&&...) {
-    return sizeof...(Formal) == sizeof...(Actual);
-}
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)                                                      \
-    do {                                                                                                                 \
-        hipEvent_t sert_a_ = nullptr, sert_b_ = nullptr;                                                                 \
-        if (::instep_hook().next && ::sert_ext_arity_ok(kernel, __VA_ARGS__))                                            \
-            ::instep_hook().next(::instep_hook().ctx, &sert_a_, &sert_b_);                                               \
-        if (!(sert_a_ && ::sert_ext_launch(kernel, dim3(grid), dim3(block), (unsigned)(shmem), stream, sert_a_, sert_b_, \
-                                           __VA_ARGS__)))                                                                \
-            hipLaunchKernelGGLInternal((kernel), grid, block, shmem, stream, __VA_ARGS__);                               \
-    } while (0)
 
 // ---- environment switches -----------------------------------------------------------------------------------
 // The PRODUCT library reads twenty documented variables, through knob(); each is exercised by a test

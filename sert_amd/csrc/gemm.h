@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "common.h"
+#include "launch.h"
 
 namespace sert {
 
@@ -909,8 +910,8 @@ inline void launch_gemm(hipStream_t s, const float* A, const float* B, float* C,
         g.tiles_m = cdiv(M, SM); g.tiles_n = cdiv(N, SM);
         const bool vecs = (lda % 4 == 0) && (ldb % 4 == 0) && lda < (1 << 22) && ldb < (1 << 22) && (((uintptr_t)A) % 16 == 0) &&
                           (((uintptr_t)B) % 16 == 0) && (K % 4 == 0) && (TB ? true : (N % 4 == 0));
-        if (vecs) SERT_LAUNCH((gemm_f32_mfma_small<TB, (EPI == EPI_FILTER || EPI == EPI_ACCUM) ? EPI_STORE : EPI, true>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
-        else      SERT_LAUNCH((gemm_f32_mfma_small<TB, (EPI == EPI_FILTER || EPI == EPI_ACCUM) ? EPI_STORE : EPI, false>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
+        if (vecs) launch((gemm_f32_mfma_small<TB, (EPI == EPI_FILTER || EPI == EPI_ACCUM) ? EPI_STORE : EPI, true>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
+        else      launch((gemm_f32_mfma_small<TB, (EPI == EPI_FILTER || EPI == EPI_ACCUM) ? EPI_STORE : EPI, false>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
         return;
     }
     g.cand = cand; g.cnt = cnt; g.cap = cap;
@@ -926,7 +927,7 @@ inline void launch_gemm(hipStream_t s, const float* A, const float* B, float* C,
         g.tiles_n = cdiv(N, GN2);
         const long long total160 = (long long)g.tiles_m * g.tiles_n * splits;
         const int grid160 = (int)std::min<long long>(total160, 256 * 3);
-        SERT_LAUNCH((gemm_f32_mfma_n160<TA, TB, EPI == EPI_FILTER ? EPI_STORE : EPI, CSB>), dim3(grid160), dim3(256), 0, s, g);
+        launch((gemm_f32_mfma_n160<TA, TB, EPI == EPI_FILTER ? EPI_STORE : EPI, CSB>), dim3(grid160), dim3(256), 0, s, g);
         return;
     }
     const long long total = (long long)g.tiles_m * g.tiles_n * splits;
@@ -938,9 +939,9 @@ inline void launch_gemm(hipStream_t s, const float* A, const float* B, float* C,
     }();
     const int grid = (int)std::min<long long>(total, max_grid);
     const bool full = (M % GM == 0) && (N % GN == 0) && EPI != EPI_FILTER;
-    if (vec && full) SERT_LAUNCH((gemm_f32_mfma<TA, TB, EPI, CSB, true, true>), dim3(grid), dim3(256), 0, s, g);
-    else if (vec)    SERT_LAUNCH((gemm_f32_mfma<TA, TB, EPI, CSB, true, false>), dim3(grid), dim3(256), 0, s, g);
-    else             SERT_LAUNCH((gemm_f32_mfma<TA, TB, EPI, CSB, false, false>), dim3(grid), dim3(256), 0, s, g);
+    if (vec && full) launch((gemm_f32_mfma<TA, TB, EPI, CSB, true, true>), dim3(grid), dim3(256), 0, s, g);
+    else if (vec)    launch((gemm_f32_mfma<TA, TB, EPI, CSB, true, false>), dim3(grid), dim3(256), 0, s, g);
+    else             launch((gemm_f32_mfma<TA, TB, EPI, CSB, false, false>), dim3(grid), dim3(256), 0, s, g);
 }
 
 // out[i] = sum_s part[s*stride + i] over the split-K partial slabs, in a fixed
@@ -952,7 +953,7 @@ __global__ __launch_bounds__(64 * G) void reduce_partials_g(const float* __restr
                                                             size_t stride, size_t count,
                                                             float* __restrict__ out1, size_t n1,
                                                             float* __restrict__ out2,
-                                                            const int32_t* __restrict__ rowmap = nullptr, int ncols = 0) {
+                                                            const int32_t* __restrict__ rowmap, int ncols) {
     // rowmap (optional): out1 is a row-major matrix of `ncols` columns whose row r is stored as row rowmap[r] -- the
     // loglinear dG, whose row u IS the gradient of word uwords[u]: the combine writes it where it belongs instead of a
     // copy kernel behind it (ll_scatter_rows: 5.6 us on the chain of the W3C step)
@@ -995,9 +996,9 @@ inline void launch_reduce_partials(hipStream_t s, const float* part, int splits,
                                    float* out1, size_t n1, float* out2, const int32_t* rowmap = nullptr, int ncols = 0) {
     const dim3 grid((unsigned)((count + 63) / 64));
     if (splits >= 64)
-        hipLaunchKernelGGL((reduce_partials_g<16>), grid, dim3(1024), 0, s, part, splits, stride, count, out1, n1, out2, rowmap, ncols);
+        launch((reduce_partials_g<16>), grid, dim3(1024), 0, s, part, splits, stride, count, out1, n1, out2, rowmap, ncols);
     else
-        hipLaunchKernelGGL((reduce_partials_g<4>), grid, dim3(256), 0, s, part, splits, stride, count, out1, n1, out2, rowmap, ncols);
+        launch((reduce_partials_g<4>), grid, dim3(256), 0, s, part, splits, stride, count, out1, n1, out2, rowmap, ncols);
 }
 
 }  // namespace sert

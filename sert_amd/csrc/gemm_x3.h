@@ -28,6 +28,7 @@
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "launch.h"
 #include "gemm.h"
 
 namespace sert {
@@ -495,8 +496,8 @@ inline void launch_gemm_x3(hipStream_t s, const float* A, const float* B, float*
     if (N <= 128 && K <= 128 && bres_waves && (!TB || (ldb % 4 == 0))) {
         // B resident in LDS, one workgroup per CU, every wave its own 32-row blocks: 23.7 / 21.1 us against 22.4 / 20.6 at C2
         g.tiles_m = cdiv(M, 32); g.tiles_n = 1;
-        if (bres_waves == 4) SERT_LAUNCH((gemm_x3_bres<TB, EPI, 4>), dim3(std::min(256, cdiv(g.tiles_m, 4))), dim3(256), 0, s, g);
-        else SERT_LAUNCH((gemm_x3_bres<TB, EPI, 8>), dim3(std::min(256, cdiv(g.tiles_m, 8))), dim3(512), 0, s, g);
+        if (bres_waves == 4) launch((gemm_x3_bres<TB, EPI, 4>), dim3(std::min(256, cdiv(g.tiles_m, 4))), dim3(256), 0, s, g);
+        else launch((gemm_x3_bres<TB, EPI, 8>), dim3(std::min(256, cdiv(g.tiles_m, 8))), dim3(512), 0, s, g);
         return;
     }
 #endif
@@ -505,17 +506,17 @@ inline void launch_gemm_x3(hipStream_t s, const float* A, const float* B, float*
         const bool vec = route == ROUTE_X3_128_VEC;
         g.tiles_m = cdiv(M, 128); g.tiles_n = cdiv(N, 128);
 #ifdef SERT_VARIANTS
-        if (vec && x3_pf2()) SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2, true, 2>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
+        if (vec && x3_pf2()) launch((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2, true, 2>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
         else
 #endif
-        if (vec) SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
-        else     SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2, false>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
+        if (vec) launch((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
+        else     launch((gemm_x3<false, TB, EPI, false, 2, 2, 2, 2, false>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(256), 0, s, g);
     } else if (route == ROUTE_X3_256) {
         g.tiles_m = cdiv(M, 256); g.tiles_n = cdiv(N, 256);
-        SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 4, 2, 2, 4>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(512), 0, s, g);
+        launch((gemm_x3<false, TB, EPI, false, 4, 2, 2, 4>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(512), 0, s, g);
     } else {
         g.tiles_m = cdiv(M, 256); g.tiles_n = cdiv(N, 320);
-        SERT_LAUNCH((gemm_x3<false, TB, EPI, false, 4, 2, 2, 5>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(512), 0, s, g);
+        launch((gemm_x3<false, TB, EPI, false, 4, 2, 2, 5>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(512), 0, s, g);
     }
 }
 
@@ -531,18 +532,18 @@ inline void launch_gemm_x3_ta(hipStream_t s, const float* A, const float* B, flo
     if (route == ROUTE_X3_TA_SINGLE) {
         g.tiles_n = 1;
 #ifdef SERT_VARIANTS
-        if (x3_pf2()) SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2, true, 2>), dim3(splits == 1 ? 1 : 8 * cdiv(splits, 8)), dim3(256), 0, s, g);
+        if (x3_pf2()) launch((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2, true, 2>), dim3(splits == 1 ? 1 : 8 * cdiv(splits, 8)), dim3(256), 0, s, g);
         else
 #endif
-        SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2>), dim3(splits == 1 ? 1 : 8 * cdiv(splits, 8)), dim3(256), 0, s, g);
+        launch((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2>), dim3(splits == 1 ? 1 : 8 * cdiv(splits, 8)), dim3(256), 0, s, g);
     } else if (route == ROUTE_X3_TA_320X160) {
         // 320 x 160 tiles, ten waves of 32 x 160 (80 accumulator registers: three waves fit a SIMD)
         g.tiles_n = cdiv(N, 160);
-        SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 10, 1, 1, 5>), dim3(splits == 1 ? g.tiles_n : 8 * g.tiles_n * cdiv(splits, 8)), dim3(640), 0, s, g);
+        launch((gemm_x3<true, false, EPI_STORE, CSB, 10, 1, 1, 5>), dim3(splits == 1 ? g.tiles_n : 8 * g.tiles_n * cdiv(splits, 8)), dim3(640), 0, s, g);
     } else {
         // 128 x 128 tiles; the tiles of one k range share an XCD
         g.tiles_m = cdiv(M, 128); g.tiles_n = cdiv(N, 128);
-        SERT_LAUNCH((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2>), dim3(splits == 1 ? g.tiles_m * g.tiles_n : 8 * g.tiles_m * g.tiles_n * cdiv(splits, 8)), dim3(256), 0, s, g);
+        launch((gemm_x3<true, false, EPI_STORE, CSB, 2, 2, 2, 2>), dim3(splits == 1 ? g.tiles_m * g.tiles_n : 8 * g.tiles_m * g.tiles_n * cdiv(splits, 8)), dim3(256), 0, s, g);
     }
 }
 

@@ -364,9 +364,9 @@ static int eval_step_async(sert_model* m, const DataSplit& ds, int64_t batch_ind
         SERT_TRY(ll_forward<false>(m, ds, batch_index));
     }
     const int nb = std::min(kOptBlocks, cdiv(B, 256));
-    hipLaunchKernelGGL(sum_partial, dim3(nb), dim3(256), 0, m->stream, m->rowloss, (size_t)B, m->red_loss);
-    hipLaunchKernelGGL(finalize_loss, dim3(1), dim3(256), 0, m->stream, m->red_loss, nb, m->red_loss, 0,
-                       1.0f / (float)B, 0.0f, dst);
+    launch(sum_partial, dim3(nb), dim3(256), 0, m->stream, m->rowloss, (size_t)B, m->red_loss);
+    launch(finalize_loss, dim3(1), dim3(256), 0, m->stream, m->red_loss, nb, m->red_loss, 0,
+           1.0f / (float)B, 0.0f, dst, nullptr, 0u, nullptr);
     return 0;
 }
 
@@ -504,12 +504,12 @@ int sert_predict_tokens(sert_model* m, const void* ids, int64_t rows, float* out
     SERT_ID_DISPATCH(c.id_bytes, {
         const IdT* X = (const IdT*)m->pred_ids;
         if (d % 4 == 0)
-            hipLaunchKernelGGL((ll_gather_rows<IdT, 4>), dim3(grid_for(toks * d / 4, 256, 1 << 20)), dim3(256), 0, m->stream, X, m->rw, dG, toks, d);
+            launch((ll_gather_rows<IdT, 4>), dim3(grid_for(toks * d / 4, 256, 1 << 20)), dim3(256), 0, m->stream, X, m->rw, dG, toks, d);
         else
-            hipLaunchKernelGGL((ll_gather_rows<IdT, 1>), dim3(grid_for(toks * d, 256, 1 << 20)), dim3(256), 0, m->stream, X, m->rw, dG, toks, d);
+            launch((ll_gather_rows<IdT, 1>), dim3(grid_for(toks * d, 256, 1 << 20)), dim3(256), 0, m->stream, X, m->rw, dG, toks, d);
     });
     launch_gemm<false, false, EPI_BIAS>(m->stream, dG, m->W, dZ, m->b, (int)toks, V, d, d, V, V);
-    hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(toks, 4)), dim3(256), 0, m->stream, dZ, toks, V);
+    launch(ll_softmax_rows, dim3(cdiv(toks, 4)), dim3(256), 0, m->stream, dZ, toks, V);
     SERT_HIP(hipMemcpyAsync(out, dZ, (size_t)toks * V * sizeof(float), hipMemcpyDeviceToHost, m->stream));
     SERT_HIP(hipStreamSynchronize(m->stream));
     return 0;

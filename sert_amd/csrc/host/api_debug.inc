@@ -92,7 +92,7 @@ int sert_debug_scorer_select(int device, int mode, const float* S, int64_t Q, in
         if (mode == 0) {
             SERT_TRY(dmalloc(&dS, (size_t)Q * V));
             SERT_HIP(hipMemcpy(dS, S, (size_t)Q * V * sizeof(float), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(topk_rows<false>, dim3((unsigned)Q), dim3(256), 0, 0, dS, (int)V, (int)k, didx, dval, (float*)nullptr);
+            launch(topk_rows<false>, dim3((unsigned)Q), dim3(256), 0, 0, dS, (int)V, (int)k, didx, dval, (float*)nullptr);
         } else {
             // the lists as the fp32 filter epilogue leaves them: per (row, 64-entity group) the elements with S >= thr in
             // ascending entity order, keyed by plain desc_key (a NaN fails the compare there as here)
@@ -114,8 +114,8 @@ int sert_debug_scorer_select(int device, int mode, const float* S, int64_t Q, in
             SERT_HIP(hipMemcpy(dcand, cand.data(), cand.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
             SERT_HIP(hipMemcpy(dcnt, cnt.data(), cnt.size(), hipMemcpyHostToDevice));
             SERT_HIP(hipMemset(dflag, 0, ((size_t)Q + 1) * sizeof(int)));
-            hipLaunchKernelGGL(topk_from_groups, dim3((unsigned)Q), dim3(256), (size_t)ccap * sizeof(unsigned long long), 0,
-                               dcand, dcnt, ngroups, gcap, (int)k, didx, dval, 0, dflag, dflag + 1, ccap, (int*)nullptr);
+            launch(topk_from_groups, dim3((unsigned)Q), dim3(256), (size_t)ccap * sizeof(unsigned long long), 0,
+                   dcand, dcnt, ngroups, gcap, (int)k, didx, dval, 0, dflag, dflag + 1, ccap, (int*)nullptr);
         }
         SERT_HIP(hipGetLastError());
         SERT_HIP(hipDeviceSynchronize());
@@ -538,12 +538,12 @@ int sert_bench_memory(int device, int kind, size_t bytes, size_t table_bytes, in
     if (kind == SERT_MEMBENCH_COPY || kind == SERT_MEMBENCH_READ) {
         float *a = nullptr, *b = nullptr;
         if ((rc = alloc(n * 4, (void**)&a)) || (rc = alloc(kind == SERT_MEMBENCH_COPY ? n * 4 : 65536 * 4, (void**)&b))) { cleanup(); return rc; }
-        hipLaunchKernelGGL(mb_fill_f32, dim3(2048), dim3(256), 0, s, a, n, 1.0f);
+        launch(mb_fill_f32, dim3(2048), dim3(256), 0, s, a, n, 1.0f);
         const int nb = blocks > 0 ? blocks : 4096;
         if (kind == SERT_MEMBENCH_COPY)
-            run = [=]() { hipLaunchKernelGGL(mb_stream_copy, dim3(nb), dim3(256), 0, s, (const float4*)a, (float4*)b, n / 4); };
+            run = [=]() { launch(mb_stream_copy, dim3(nb), dim3(256), 0, s, (const float4*)a, (float4*)b, n / 4); };
         else
-            run = [=]() { hipLaunchKernelGGL(mb_stream_read, dim3(nb), dim3(256), 0, s, (const float4*)a, n / 4, b); };
+            run = [=]() { launch(mb_stream_read, dim3(nb), dim3(256), 0, s, (const float4*)a, n / 4, b); };
     } else if (kind == SERT_MEMBENCH_GATHER) {
         if (row_bytes < 16 || row_bytes % 16 || window < 1 || table_bytes < (size_t)row_bytes) { cleanup(); SERT_FAIL("bad gather shape"); }
         const int d = row_bytes / 4;
@@ -553,10 +553,10 @@ int sert_bench_memory(int device, int kind, size_t bytes, size_t table_bytes, in
         float *tab = nullptr, *out = nullptr; uint32_t* ids = nullptr;
         if ((rc = alloc(rows * row_bytes, (void**)&tab)) || (rc = alloc(B * row_bytes, (void**)&out)) ||
             (rc = alloc(B * window * 4, (void**)&ids))) { cleanup(); return rc; }
-        hipLaunchKernelGGL(mb_fill_f32, dim3(2048), dim3(256), 0, s, tab, rows * d, 1.0f);
-        hipLaunchKernelGGL(mb_fill_ids, dim3(2048), dim3(256), 0, s, ids, B * window, (uint32_t)rows, 17u);
+        launch(mb_fill_f32, dim3(2048), dim3(256), 0, s, tab, rows * d, 1.0f);
+        launch(mb_fill_ids, dim3(2048), dim3(256), 0, s, ids, B * window, (uint32_t)rows, 17u);
         const int grid = grid_for((int64_t)B * d / 4, 256, 1 << 20);
-        run = [=]() { hipLaunchKernelGGL((vs_gather_mean<uint32_t, 4>), dim3(grid), dim3(256), 0, s, (const uint32_t*)ids, (const float*)tab, out, (int)B, window, d); };
+        run = [=]() { launch((vs_gather_mean<uint32_t, 4>), dim3(grid), dim3(256), 0, s, (const uint32_t*)ids, (const float*)tab, out, (int)B, window, d); };
     } else if (kind == SERT_MEMBENCH_OPTIMIZER) {
         float* arr[4] = {nullptr, nullptr, nullptr, nullptr};
         if (gap_bytes == (size_t)-1) {   // four allocations of their own, as the model holds them
@@ -569,14 +569,14 @@ int sert_bench_memory(int device, int kind, size_t bytes, size_t table_bytes, in
         }
         float* sq = nullptr;
         if ((rc = alloc((size_t)8 * kOptBlocks * 4, (void**)&sq))) { cleanup(); return rc; }
-        hipLaunchKernelGGL(mb_fill_f32, dim3(2048), dim3(256), 0, s, arr[0], n, 0.01f);
-        hipLaunchKernelGGL(mb_fill_f32, dim3(2048), dim3(256), 0, s, arr[1], n, 1e-4f);
+        launch(mb_fill_f32, dim3(2048), dim3(256), 0, s, arr[0], n, 0.01f);
+        launch(mb_fill_f32, dim3(2048), dim3(256), 0, s, arr[1], n, 1e-4f);
         SERT_HIP(hipMemsetAsync(arr[2], 0, n * 4, s));
         SERT_HIP(hipMemsetAsync(arr[3], 0, n * 4, s));
         const int nb = blocks > 0 ? std::min(blocks, 8 * kOptBlocks) : 2 * kOptBlocks;
         const AdamArgs aa{1e-7f, 1e-3f, 0.9f, 0.999f, 1e-8f};
         float *p = arr[0], *g = arr[1], *m1 = arr[2], *v1 = arr[3];
-        run = [=]() { hipLaunchKernelGGL((adam_l2<false>), dim3(nb), dim3(256), 0, s, p, g, m1, v1, n, aa, sq, (const uint32_t*)nullptr, 1u, (int)kRowsAll); };
+        run = [=]() { launch((adam_l2<false>), dim3(nb), dim3(256), 0, s, p, g, m1, v1, n, aa, sq, (const uint32_t*)nullptr, 1u, (int)kRowsAll, nullptr); };
     } else {
         cleanup();
         SERT_FAIL("unknown membench kind");

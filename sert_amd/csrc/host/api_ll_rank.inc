@@ -64,10 +64,10 @@ static float ll_log2v_f(int V) { return (float)(log((double)V) / log(2.0)); }
 // P holds the chunk's per-token distributions (rows indexed by w.tok_row), w.offs its Qc + 1 query offsets: joint rows,
 // entropies, status and the ranking (w.idx / w.val, Qc x kk) on stream s
 static int ll_rank_chunk(hipStream_t s, LLRankScratch& w, const float* P, int Qc, int V, int kk, int mode) {
-    hipLaunchKernelGGL(ll_query_aggregate, dim3(Qc), dim3(256), 0, s, P, w.tok_row, w.offs, V, ll_ln2_f(), ll_log2v_f(V),
-                       w.J, w.joint_h, w.status);
+    launch(ll_query_aggregate, dim3(Qc), dim3(256), 0, s, P, w.tok_row, w.offs, V, ll_ln2_f(), ll_log2v_f(V),
+           w.J, w.joint_h, w.status);
     if (mode == RANK_TOPK) {
-        hipLaunchKernelGGL(topk_rows<true>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val, (float*)nullptr);
+        launch(topk_rows<true>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val, (float*)nullptr);
         SERT_HIP(hipGetLastError());
         return 0;
     }
@@ -174,13 +174,13 @@ static int64_t ll_rank_chunk_inputs(const int32_t* tokens, const int64_t* offset
 static int ll_rank_chunk_device(sert_model* m, hipStream_t s, LLRankScratch& w, int64_t Dc, int64_t rows, int Qc, int kk, int mode) {
     const int V = m->cfg.num_entities, d = m->cfg.word_dim;
     if (d % 4 == 0)
-        hipLaunchKernelGGL((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+        launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
     else
-        hipLaunchKernelGGL((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+        launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
     for (int64_t r0 = 0; r0 < rows; r0 += kLLRankRows)
         launch_gemm<false, false, EPI_BIAS>(s, w.G + (size_t)r0 * d, m->W, w.P + (size_t)r0 * V, m->b, kLLRankRows, V, d, d, V, V);
-    hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);
-    hipLaunchKernelGGL(ll_row_entropy, dim3((unsigned)Dc), dim3(256), 0, s, w.P, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
+    launch(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);
+    launch(ll_row_entropy, dim3((unsigned)Dc), dim3(256), 0, s, w.P, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
     return ll_rank_chunk(s, w, w.P, Qc, V, kk, mode);
 }
 
@@ -260,7 +260,7 @@ int sert_debug_ll_rank_distributions(int device, const float* P, const int64_t* 
             SERT_HIP(hipMemcpyAsync(dP, P, (size_t)T * V * sizeof(float), hipMemcpyHostToDevice, s));
             SERT_HIP(hipMemcpyAsync(w.tok_row, rows.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, s));
             SERT_HIP(hipMemcpyAsync(w.offs, offsets, (num_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(ll_row_entropy, dim3((unsigned)T), dim3(256), 0, s, dP, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
+            launch(ll_row_entropy, dim3((unsigned)T), dim3(256), 0, s, dP, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
             SERT_TRY(ll_rank_chunk(s, w, dP, (int)num_queries, V, kk, mode));
             SERT_TRY(ll_rank_copy_out(s, w, 0, (int)num_queries, kk, idx_out, score_out, joint_entropy_out, status_out));
             SERT_HIP(hipMemcpyAsync(token_entropy_out, w.tok_h, T * sizeof(float), hipMemcpyDeviceToHost, s));

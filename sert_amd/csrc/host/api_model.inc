@@ -520,9 +520,9 @@ int sert_negatives_of_step(sert_model* m, int64_t position, int evaluation, int6
     // a stream of its own: nothing of the model's state or schedule is touched
     hipStream_t st = nullptr;
     if (hipStreamCreate(&st) != hipSuccess) { (void)hipFree(tmp); SERT_FAIL("hipStreamCreate failed"); }
-    hipLaunchKernelGGL(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count,
-                       (int64_t)m->rank * count, (uint32_t)m->cfg.num_entities, m->cfg.seed,
-                       (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
+    launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count,
+           (int64_t)m->rank * count, (uint32_t)m->cfg.num_entities, m->cfg.seed,
+           (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
     std::vector<int32_t> host((size_t)count);
     const hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     const hipError_t e2 = hipStreamSynchronize(st);

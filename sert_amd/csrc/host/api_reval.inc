@@ -195,17 +195,17 @@ static void reval_launch_count(hipStream_t s, const float* S, int rows, int64_t 
     const dim3 grid((unsigned)rows, (unsigned)splits);
     const bool vec = V % 4 == 0;
     if (max_judged <= 8) {
-        if (vec) hipLaunchKernelGGL((reval_count_ranks<8, true>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
-        else hipLaunchKernelGGL((reval_count_ranks<8, false>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
+        if (vec) launch((reval_count_ranks<8, true>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
+        else launch((reval_count_ranks<8, false>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
     } else {
-        if (vec) hipLaunchKernelGGL((reval_count_ranks<32, true>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
-        else hipLaunchKernelGGL((reval_count_ranks<32, false>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
+        if (vec) launch((reval_count_ranks<32, true>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
+        else launch((reval_count_ranks<32, false>), grid, dim3(256), 0, s, S, (int)V, q0, rel_indptr, rel_ent, ranks);
     }
 }
 
 static void reval_launch_metrics(sert_reval* r, hipStream_t s, const int32_t* idx, int Qc, int64_t q0) {
-    hipLaunchKernelGGL(reval_metrics, dim3(cdiv(Qc, 4)), dim3(256), 0, s, idx, r->kk, Qc, q0, r->rel_indptr, r->rel_ent,
-                       r->rel_gain, r->log2tab, r->idcg, r->num_rel, r->metrics);
+    launch(reval_metrics, dim3(cdiv(Qc, 4)), dim3(256), 0, s, idx, r->kk, Qc, q0, r->rel_indptr, r->rel_ent,
+           r->rel_gain, r->log2tab, r->idcg, r->num_rel, r->metrics);
 }
 
 int sert_reval_run(sert_reval* r, double* metrics_out, int32_t* status_out, int32_t* idx_out, float* score_out) {
@@ -234,12 +234,12 @@ int sert_reval_run(sert_reval* r, double* metrics_out, int32_t* status_out, int3
         const int64_t V = c.num_entities;
         r->ranks_valid = false;
         if (dw % 4 == 0)
-            hipLaunchKernelGGL(reval_gather_mean<4>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
+            launch(reval_gather_mean<4>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
         else
-            hipLaunchKernelGGL(reval_gather_mean<1>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
+            launch(reval_gather_mean<1>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
         launch_gemm<false, false, EPI_BIAS_TANH>(s, r->avg, m->W, r->proj, m->b, (int)Q, de, dw, dw, de, de);
         SERT_TRY(scorer_load_table(r->sc, m->re, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->proj, Q, de);     // (as sert_scorer_rank normalises its copy)
+        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->proj, Q, de);     // (as sert_scorer_rank normalises its copy)
         if (r->R) SERT_HIP(hipMemsetAsync(r->ranks, 0, (size_t)r->R * sizeof(int32_t), s));
         // sert_scorer_rank's slab call, in launches of at most kScoreRankRows rows (a row's cosines do not depend on the
         // rows launched with it): a judged entity's rank is its position in that call's ranking.  Everything on the model's
@@ -248,16 +248,16 @@ int sert_reval_run(sert_reval* r, double* metrics_out, int32_t* status_out, int3
             const int qn = (int)std::min<int64_t>(kScoreRankRows, Q - q0);
             scorer_cosine_slab(r->sc, s, r->proj + q0 * de, qn, r->slab, r->sc->bf16);
             reval_launch_count(s, r->slab, qn, V, q0, r->rel_indptr, r->rel_ent, r->ranks, r->max_judged);
-            hipLaunchKernelGGL(reval_metrics_from_ranks, dim3(cdiv(qn, 4)), dim3(256), 0, s, r->ranks, kk, qn, q0, r->rel_indptr,
-                               r->rel_gain, r->log2tab, r->idcg, r->num_rel, r->metrics);
+            launch(reval_metrics_from_ranks, dim3(cdiv(qn, 4)), dim3(256), 0, s, r->ranks, kk, qn, q0, r->rel_indptr,
+                   r->rel_gain, r->log2tab, r->idcg, r->num_rel, r->metrics);
         }
         SERT_HIP(hipGetLastError());
     } else if (is_vs(m)) {
         const int dw = c.word_dim, de = c.entity_dim;
         if (dw % 4 == 0)
-            hipLaunchKernelGGL(reval_gather_mean<4>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
+            launch(reval_gather_mean<4>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
         else
-            hipLaunchKernelGGL(reval_gather_mean<1>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
+            launch(reval_gather_mean<1>, dim3(cdiv(Q, 4)), dim3(256), 0, s, r->tokens, r->offsets, m->rw, (int)Q, dw, r->avg);
         // sert_predict_project's launch on the resident block
         launch_gemm<false, false, EPI_BIAS_TANH>(s, r->avg, m->W, r->proj, m->b, (int)Q, de, dw, dw, de, de);
         SERT_TRY(scorer_load_table(r->sc, m->re, hipMemcpyDeviceToDevice, s));

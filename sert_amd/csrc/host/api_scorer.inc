@@ -29,10 +29,10 @@ static int scorer_load_table(sert_scorer* sc, const float* entities, hipMemcpyKi
     const int64_t V = sc->V;
     const int dim = sc->dim;
     SERT_HIP(hipMemcpyAsync(sc->E, entities, (size_t)V * dim * sizeof(float), kind, s));
-    hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(V, 4)), dim3(256), 0, s, sc->E, V, dim);
+    launch(l2_normalize_rows, dim3(cdiv(V, 4)), dim3(256), 0, s, sc->E, V, dim);
     if (sc->bf16)
-        hipLaunchKernelGGL(to_bf16_rows, dim3(grid_for(V * sc->kp)), dim3(256), 0, s, sc->E, V, dim,
-                           sc->kp, sc->E16);
+        launch(to_bf16_rows, dim3(grid_for(V * sc->kp)), dim3(256), 0, s, sc->E, V, dim,
+               sc->kp, sc->E16);
     sc->bf16_demoted = false;     // (a verdict on the previous table's rows)
     return 0;
 }
@@ -131,13 +131,13 @@ static int scorer_topk_materialised(sert_scorer* sc, const float* P, int64_t Q, 
 #endif
             launch_gemm<false, true, EPI_STORE>(st, P + q0 * dim, sc->E, S, nullptr, (int)qn, (int)V, dim,
                                                 dim, dim, (int)V);
-        hipLaunchKernelGGL(topk_rows<false>, dim3((unsigned)qn), dim3(256), 0, st, S, (int)V, k, idx + q0 * k,
-                           val + q0 * k, (float*)nullptr);
+        launch(topk_rows<false>, dim3((unsigned)qn), dim3(256), 0, st, S, (int)V, k, idx + q0 * k,
+               val + q0 * k, (float*)nullptr);
         if (sc->bf16) {   // same exact_dot scores and order as the bf16-prefiltered path reports
             int sn = 2;
             while (sn < k) sn <<= 1;
-            hipLaunchKernelGGL(rescore_topk_rows, dim3((unsigned)qn), dim3(256), (size_t)sn * sizeof(unsigned long long),
-                               st, P + q0 * dim, sc->E, dim, k, idx + q0 * k, val + q0 * k);
+            launch(rescore_topk_rows, dim3((unsigned)qn), dim3(256), (size_t)sn * sizeof(unsigned long long),
+                   st, P + q0 * dim, sc->E, dim, k, idx + q0 * k, val + q0 * k, nullptr);
         }
     }
     SERT_HIP(hipEventRecord(sc->ev_done, sc->stream2));
@@ -219,7 +219,7 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         hipStream_t st = set ? sc->stream2 : s;
         float* Pw = sc->P + q0 * dim;
         SERT_HIP(hipMemcpyAsync(Pw, proj + q0 * dim, (size_t)qn * dim * sizeof(float), kind_in, st));
-        hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(qn, 4)), dim3(256), 0, st, Pw, qn, dim);
+        launch(l2_normalize_rows, dim3(cdiv(qn, 4)), dim3(256), 0, st, Pw, qn, dim);
         const float* P = Pw;
         float* Ss = sc->Ss + (size_t)set * QT * Vs;
         float* thr = sc->thr + (size_t)set * QT;
@@ -230,15 +230,15 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         // 1. cosines against every kScoreStride-th entity; threshold = rs-th best of the sample
         // (bf16 scorer: approximate sample scores are as good for choosing a threshold)
         if (use_bf16) {
-            hipLaunchKernelGGL(to_bf16_rows, dim3(grid_for(qn * sc->kp)), dim3(256), 0, st, P, qn, dim, sc->kp, P16);
+            launch(to_bf16_rows, dim3(grid_for(qn * sc->kp)), dim3(256), 0, st, P, qn, dim, sc->kp, P16);
             launch_score_sample_bf16(st, P16, sc->E16, Ss, (int)qn, (int)Vs, sc->kp, kScoreStride);
         } else
             launch_gemm<false, true, EPI_STORE>(st, P, sc->E, Ss, nullptr, (int)qn, (int)Vs, dim, dim,
                                                 dim * kScoreStride, (int)Vs);
         if (rs <= 64 && Vs >= 2048)
-            hipLaunchKernelGGL(approx_kth_rows, dim3((unsigned)qn), dim3(256), 0, st, Ss, (int)Vs, rs, thr);
+            launch(approx_kth_rows, dim3((unsigned)qn), dim3(256), 0, st, Ss, (int)Vs, rs, thr);
         else
-            hipLaunchKernelGGL(kth_largest_rows, dim3((unsigned)qn), dim3(256), 0, st, Ss, (int)Vs, rs, thr);
+            launch(kth_largest_rows, dim3((unsigned)qn), dim3(256), 0, st, Ss, (int)Vs, rs, thr);
         // 2. full GEMM, filtering epilogue
         if (use_bf16) {
             launch_score_filter_bf16(st, P16, sc->E16, thr, (uint32_t*)cand, cnt, ngroups, gcap, (int)qn, (int)V, sc->kp);
@@ -256,18 +256,18 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         int ccap = 1024;
         while (ccap < 2 * k + 400 + 6 * 16 * (int)ceilf(sqrtf((float)rs)) && ccap < kCandCap) ccap <<= 1;
         if (use_bf16)
-            hipLaunchKernelGGL(topk_from_groups_rescore, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
-                               (const uint32_t*)cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
-                               sc->nflag, sc->flag_list, ccap, P, sc->E, dim, thr, bf16_delta(dim));
+            launch(topk_from_groups_rescore, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
+                   (const uint32_t*)cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
+                   sc->nflag, sc->flag_list, ccap, P, sc->E, dim, thr, bf16_delta(dim));
         else {
-            hipLaunchKernelGGL(topk_from_groups, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
-                               cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
-                               sc->nflag, sc->flag_list, ccap, sc->flag_list + sc->cap_flag);
+            launch(topk_from_groups, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
+                   cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
+                   sc->nflag, sc->flag_list, ccap, sc->flag_list + sc->cap_flag);
             if (sc->bf16) {   // demoted table: its scores stay the exact_dot ones every other path of this scorer reports
                 int sn = 2;
                 while (sn < k) sn <<= 1;
-                hipLaunchKernelGGL(rescore_topk_rows, dim3((unsigned)qn), dim3(256), (size_t)sn * sizeof(unsigned long long),
-                                   st, P, sc->E, dim, k, sc->idx + q0 * k, sc->val + q0 * k, sc->flag_list + sc->cap_flag + q0);
+                launch(rescore_topk_rows, dim3((unsigned)qn), dim3(256), (size_t)sn * sizeof(unsigned long long),
+                       st, P, sc->E, dim, k, sc->idx + q0 * k, sc->val + q0 * k, sc->flag_list + sc->cap_flag + q0);
             }
         }
         // results of the previous chunk (other stream) travel while this one computes
@@ -302,11 +302,11 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         SERT_TRY(dmalloc(&sc->val_c, (size_t)nf * k));
         sc->cap_ck = (int64_t)nf * k;
     }
-    hipLaunchKernelGGL(gather_rows_f32, dim3(grid_for((int64_t)nf * dim)), dim3(256), 0, s, sc->P,
-                       sc->flag_list, nf, dim, sc->Pc);
+    launch(gather_rows_f32, dim3(grid_for((int64_t)nf * dim)), dim3(256), 0, s, sc->P,
+           sc->flag_list, nf, dim, sc->Pc);
     SERT_TRY(scorer_topk_materialised(sc, sc->Pc, nf, k, sc->idx_c, sc->val_c));
-    hipLaunchKernelGGL(scatter_topk_rows, dim3(grid_for((int64_t)nf * k)), dim3(256), 0, s, sc->idx_c,
-                       sc->val_c, sc->flag_list, nf, k, sc->idx, sc->val);
+    launch(scatter_topk_rows, dim3(grid_for((int64_t)nf * k)), dim3(256), 0, s, sc->idx_c,
+           sc->val_c, sc->flag_list, nf, k, sc->idx, sc->val);
     return 0;
 }
 
@@ -347,7 +347,7 @@ static int scorer_topk_io(sert_scorer* sc, const float* proj, int64_t Q, int32_t
     if (fused) SERT_TRY(scorer_topk_fused(sc, proj, Q, k, rs, idx_out, score_out, &copied, dev));
     else {
         SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
+        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
         SERT_TRY(scorer_topk_materialised(sc, sc->P, Q, k, sc->idx, sc->val));
         sc->path_counts[4] += Q;
     }
@@ -371,8 +371,8 @@ static void scorer_cosine_slab(sert_scorer* sc, hipStream_t st, const float* P, 
     const int64_t V = sc->V;
     const int dim = sc->dim;
     if (exact)
-        hipLaunchKernelGGL(exact_cosine_rows, dim3((unsigned)std::min<int64_t>(cdiv(V, 8), 1024), (unsigned)qn), dim3(256), 0, st,
-                           P, sc->E, V, dim, S);
+        launch(exact_cosine_rows, dim3((unsigned)std::min<int64_t>(cdiv(V, 8), 1024), (unsigned)qn), dim3(256), 0, st,
+               P, sc->E, V, dim, S);
     else
         launch_gemm<false, true, EPI_STORE>(st, P, sc->E, S, nullptr, (int)qn, (int)V, dim, dim, dim, (int)V);
 }
@@ -398,11 +398,11 @@ static int scorer_all(sert_scorer* sc, const float* proj, int64_t Q, float* scor
         sc->cap_s = QT * V;
     }
     SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
+    launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
     for (int64_t q0 = 0; q0 < Q; q0 += QT) {
         const int64_t qn = std::min(QT, Q - q0);
         scorer_cosine_slab(sc, s, sc->P + q0 * dim, qn, sc->S, raw && sc->bf16);
-        if (!raw) hipLaunchKernelGGL(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S, (size_t)(qn * V));
+        if (!raw) launch(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S, (size_t)(qn * V));
         SERT_HIP(hipMemcpyAsync(score_out + q0 * V, sc->S, (size_t)qn * V * sizeof(float), hipMemcpyDeviceToHost, s));
         SERT_HIP(hipStreamSynchronize(s));
     }

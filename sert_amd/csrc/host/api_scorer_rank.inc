@@ -129,7 +129,7 @@ int sert_scorer_rank(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
     };
     auto body = [&]() -> int {
         SERT_HIP(hipMemcpyAsync(sc->rP, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->rP, Q, dim);
+        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->rP, Q, dim);
         for (int64_t c = 0; c < nchunks; ++c) {
             const int b = (int)(c & 1);
             const int64_t q0 = c * Qc, qn = std::min(Qc, Q - q0);

@@ -176,12 +176,12 @@ static int xr_fetch_params(sert_model* m, int64_t b) {
     ScopedTimer tm(m, TG_ALLGATHER);
     if (async) SERT_HIP(hipStreamWaitEvent(st, m->ev_word_updated, 0));   // (the owners' rows are final)
     if (xb.serve_total)
-        hipLaunchKernelGGL(xchg_pack_rows, dim3(grid_for((int64_t)xb.serve_total * d4)), dim3(256), 0, st, (const float*)m->rw,
-                           (const int32_t*)m->xr_serve + xb.serve_off, xb.serve_total, d4, reinterpret_cast<float4*>(m->xr_send));
+        launch(xchg_pack_rows, dim3(grid_for((int64_t)xb.serve_total * d4)), dim3(256), 0, st, (const float*)m->rw,
+               (const int32_t*)m->xr_serve + xb.serve_off, xb.serve_total, d4, reinterpret_cast<float4*>(m->xr_send));
     SERT_TRY(xr_alltoall(m, xb.serve_cnt, xb.fetch_cnt, st));
     if (xb.fetch_total)
-        hipLaunchKernelGGL(xchg_unpack_rows, dim3(grid_for((int64_t)xb.fetch_total * d4)), dim3(256), 0, st, m->rw,
-                           (const int32_t*)m->xr_fetch + xb.fetch_off, xb.fetch_total, d4, reinterpret_cast<const float4*>(m->xr_recv));
+        launch(xchg_unpack_rows, dim3(grid_for((int64_t)xb.fetch_total * d4)), dim3(256), 0, st, m->rw,
+               (const int32_t*)m->xr_fetch + xb.fetch_off, xb.fetch_total, d4, reinterpret_cast<const float4*>(m->xr_recv));
     if (async) {
         SERT_HIP(hipEventRecord(m->ev_params_ready, st));
         SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_params_ready, 0));
@@ -203,13 +203,13 @@ static int xr_return_grads(sert_model* m, int64_t b) {
         SERT_HIP(hipStreamWaitEvent(st, m->ev_grad_ready[0], 0));
     }
     if (xb.fetch_total)
-        hipLaunchKernelGGL(xchg_pack_rows, dim3(grid_for((int64_t)xb.fetch_total * d4)), dim3(256), 0, st, (const float*)m->g_rw,
-                           (const int32_t*)m->xr_fetch + xb.fetch_off, xb.fetch_total, d4, reinterpret_cast<float4*>(m->xr_send));
+        launch(xchg_pack_rows, dim3(grid_for((int64_t)xb.fetch_total * d4)), dim3(256), 0, st, (const float*)m->g_rw,
+               (const int32_t*)m->xr_fetch + xb.fetch_off, xb.fetch_total, d4, reinterpret_cast<float4*>(m->xr_send));
     SERT_TRY(xr_alltoall(m, xb.fetch_cnt, xb.serve_cnt, st));
     if (xb.nunion)
-        hipLaunchKernelGGL(xchg_reduce_rows, dim3(grid_for((int64_t)xb.nunion * d4)), dim3(256), 0, st,
-                           reinterpret_cast<const float4*>(m->xr_recv), (const int32_t*)m->xr_ptr + xb.ptr_off,
-                           (const int32_t*)m->xr_ent + xb.ent_off, (const int32_t*)m->xr_union + xb.union_off, xb.nunion, d4, m->g_rw);
+        launch(xchg_reduce_rows, dim3(grid_for((int64_t)xb.nunion * d4)), dim3(256), 0, st,
+               reinterpret_cast<const float4*>(m->xr_recv), (const int32_t*)m->xr_ptr + xb.ptr_off,
+               (const int32_t*)m->xr_ent + xb.ent_off, (const int32_t*)m->xr_union + xb.union_off, xb.nunion, d4, m->g_rw);
     if (async) {
         SERT_HIP(hipEventRecord(m->ev_rs_done[0][0], st));
         m->rs_issued[0] = true;
@@ -410,10 +410,10 @@ static int owned_sum_of_squares(sert_model* m, hipStream_t st) {
         const ParamTensor t = param_tensor(m, i);
         const size_t owned = m->pt_sc[i] * (size_t)m->ar_chunks;
         const int nb = (int)std::min<size_t>(kOptBlocks / 2, std::max<size_t>(1, owned / 1024));
-        hipLaunchKernelGGL(sumsq_pieces, dim3(nb), dim3(256), 0, st, (const float*)t.p + (size_t)m->rank * m->pt_sc[i],
-                           m->pt_sc[i], slab_elems(m, i), m->ar_chunks, m->sq_scratch + 4 * kOptBlocks + nparts);
+        launch(sumsq_pieces, dim3(nb), dim3(256), 0, st, (const float*)t.p + (size_t)m->rank * m->pt_sc[i],
+               m->pt_sc[i], slab_elems(m, i), m->ar_chunks, m->sq_scratch + 4 * kOptBlocks + nparts);
         nparts += nb;
     }
-    if (nparts) hipLaunchKernelGGL(partials_to_scalar, dim3(1), dim3(256), 0, st, m->sq_scratch + 4 * kOptBlocks, nparts, m->g_sq);
+    if (nparts) launch(partials_to_scalar, dim3(1), dim3(256), 0, st, m->sq_scratch + 4 * kOptBlocks, nparts, m->g_sq);
     return 0;
 }

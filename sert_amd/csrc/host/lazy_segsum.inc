@@ -33,11 +33,11 @@ static int ensure_rw_current(sert_model* m, int64_t batch, int64_t t_applied) {
     const int64_t max_nb = m->n_rw >= ((size_t)1 << 24) ? 2 * kOptBlocks : kOptBlocks;
     const int nb = (int)std::min<int64_t>(max_nb, cdiv(cdiv(m->n_rw, 4), 256));
     if (is_vs(m))
-        hipLaunchKernelGGL((dense_update_lazy<true>), dim3(nb), dim3(256), 0, m->stream, m->rw, (const float*)m->g_rw, m->s0_rw, m->s1_rw,
-                           m->n_rw, aa, da, m->sq_scratch, (const uint32_t*)nullptr, (unsigned)m->cfg.word_dim, lz);
+        launch((dense_update_lazy<true>), dim3(nb), dim3(256), 0, m->stream, m->rw, (const float*)m->g_rw, m->s0_rw, m->s1_rw,
+               m->n_rw, aa, da, m->sq_scratch, (const uint32_t*)nullptr, (unsigned)m->cfg.word_dim, lz);
     else
-        hipLaunchKernelGGL((dense_update_lazy<false>), dim3(nb), dim3(256), 0, m->stream, m->rw, (const float*)m->g_rw, m->s0_rw, m->s1_rw,
-                           m->n_rw, aa, da, m->sq_scratch, (const uint32_t*)nullptr, (unsigned)m->cfg.word_dim, lz);
+        launch((dense_update_lazy<false>), dim3(nb), dim3(256), 0, m->stream, m->rw, (const float*)m->g_rw, m->s0_rw, m->s1_rw,
+               m->n_rw, aa, da, m->sq_scratch, (const uint32_t*)nullptr, (unsigned)m->cfg.word_dim, lz);
     m->rw_last_cur ^= 1;
     m->rw_stale = false;
     m->rw_ready_batch = -1;
@@ -135,10 +135,10 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
         const int nblk = cdiv(B, kHeavyRowsPerBlock);
         wp[4] = SERT_WGRAD_HEAVY_TWO_LAUNCHES; wp[5] = kHeavyRowsPerBlock; wp[6] = nblk;
         const size_t lds = (size_t)4 * kHeavyMax * 32 * sizeof(float4);   // 32 KB
-        hipLaunchKernelGGL(segsum_heavy, dim3(nblk * cdiv(d4, 32)), dim3(1024), lds, m->stream, src, cnt, B, d, m->hpart);
-        hipLaunchKernelGGL(segsum_heavy_combine, dim3(bx.dense_cnt, cdiv(d4, 32)), dim3(256), 0, m->stream,
-                           (const float*)m->hpart, nblk, d, (const int32_t*)ds.idx_dense_words + (size_t)batch_index * kHeavyMax,
-                           bx.dense_cnt, m->g_rw, divisor);
+        launch(segsum_heavy, dim3(nblk * cdiv(d4, 32)), dim3(1024), lds, m->stream, src, cnt, B, d, m->hpart);
+        launch(segsum_heavy_combine, dim3(bx.dense_cnt, cdiv(d4, 32)), dim3(256), 0, m->stream,
+               (const float*)m->hpart, nblk, d, (const int32_t*)ds.idx_dense_words + (size_t)batch_index * kHeavyMax,
+               bx.dense_cnt, m->g_rw, divisor);
         }
     }
     auto heavy_combine_job = [&]() { PlusJob j = hjob; j.kind = 2; j.extra = bx.dense_cnt; j.src = m->hpart; return j; };
@@ -148,9 +148,9 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
         if (fused_upper && l == 1) {
             // levels 1 and 2 in one launch (kernels_seg.h: segsum_upper_fused)
             const int nb_normal = cdiv(nitems, 32);
-            hipLaunchKernelGGL(segsum_upper_fused, dim3(nb_normal + bx.heavy_cnt, cdiv(d / 4, 32)), dim3(1024), 0, m->stream,
-                               m->wpart + (size_t)bx.part_off[0] * d, ds.idx_items + bx.item_off[1], nitems, nb_normal,
-                               ds.idx_heavy + bx.heavy_off, m->g_rw, d, divisor);
+            launch(segsum_upper_fused, dim3(nb_normal + bx.heavy_cnt, cdiv(d / 4, 32)), dim3(1024), 0, m->stream,
+                   m->wpart + (size_t)bx.part_off[0] * d, ds.idx_items + bx.item_off[1], nitems, nb_normal,
+                   ds.idx_heavy + bx.heavy_off, m->g_rw, d, divisor);
             wp_launch(SERT_WGRAD_FORM_UPPER_FUSED, cdiv(d / 4, 32));
             break;
         }
@@ -162,8 +162,8 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             // level 0 + the heavy words' partial sums / level 1 + their combine: one launch each
             PlusJob j = l == 0 ? hjob : heavy_combine_job();
             j.slot_is_row = (l == 0 && bx.slot_is_row) ? 1 : 0;
-            hipLaunchKernelGGL(segsum_rows_plus, dim3(j.extra + cdiv(nitems, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows, items,
-                               nitems, m->g_rw, pout, d, divisor, j);
+            launch(segsum_rows_plus, dim3(j.extra + cdiv(nitems, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows, items,
+                   nitems, m->g_rw, pout, d, divisor, j);
             wp_launch(SERT_WGRAD_FORM_ROWS_PLUS, cdiv(d / 4, 32));
             if (l == 1) heavy_combined = true;
             continue;
@@ -172,8 +172,8 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
         // same sums bit for bit as one item per lane group, tests/test_gpu_parity.py::test_word_gradient_bundled_level0)
 #ifdef SERT_VARIANTS
         if (l == 0 && d % 4 == 0 && bx.bundle_cnt > 0 && ds.idx_bundles && bx.row_groups == 1) {
-            hipLaunchKernelGGL(segsum_rows_bundled, dim3(cdiv(bx.bundle_cnt, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows,
-                               items, (const int32_t*)ds.idx_bundles + bx.bundle_off, (int)bx.bundle_cnt, m->g_rw, pout, d, divisor);
+            launch(segsum_rows_bundled, dim3(cdiv(bx.bundle_cnt, 8), cdiv(d / 4, 32)), dim3(256), 0, m->stream, in, rows,
+                   items, (const int32_t*)ds.idx_bundles + bx.bundle_off, (int)bx.bundle_cnt, m->g_rw, pout, d, divisor);
             wp_launch(SERT_WGRAD_FORM_BUNDLED, cdiv(d / 4, 32));
             continue;
         }
@@ -194,28 +194,28 @@ static int word_grad_segsum(sert_model* m, const DataSplit& ds, int64_t batch_in
             const int ipb = (d / 4 <= 32 || seg32y) ? 8 : 4;
             const int gx = xl.on ? 8 * cdiv(longest, ipb) : cdiv(nitems, ipb);
             if (d / 4 <= 32) {
-                hipLaunchKernelGGL((segsum_rows<32>), dim3(gx), dim3(256), 0, m->stream,
-                                   in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
+                launch((segsum_rows<32>), dim3(gx), dim3(256), 0, m->stream,
+                       in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
                 wp_launch(SERT_WGRAD_FORM_ROWS32, 1);
             } else if (seg32y) {
-                hipLaunchKernelGGL((segsum_rows<32>), dim3(gx, cdiv(d / 4, 32)), dim3(256), 0, m->stream,
-                                   in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
+                launch((segsum_rows<32>), dim3(gx, cdiv(d / 4, 32)), dim3(256), 0, m->stream,
+                       in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
                 wp_launch(SERT_WGRAD_FORM_ROWS32, cdiv(d / 4, 32));
             } else {   // rows wider than 64 float4 chunks (d = 300: 75): the rest goes to further column groups
-                hipLaunchKernelGGL((segsum_rows<64>), dim3(gx, cdiv(d / 4, 64)), dim3(256), 0, m->stream,
-                                   in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
+                launch((segsum_rows<64>), dim3(gx, cdiv(d / 4, 64)), dim3(256), 0, m->stream,
+                       in, rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, DenseSlots(), xl);
                 wp_launch(SERT_WGRAD_FORM_ROWS64, cdiv(d / 4, 64));
             }
         } else {
-            hipLaunchKernelGGL((segsum_rows_scalar<false>), dim3(cdiv(nitems, 4), cdiv(d, 64)), dim3(256), 0, m->stream, in,
-                               rows, items, nitems, m->g_rw, pout, d, divisor, touched);
+            launch((segsum_rows_scalar<false>), dim3(cdiv(nitems, 4), cdiv(d, 64)), dim3(256), 0, m->stream, in,
+                   rows, items, nitems, m->g_rw, pout, d, divisor, touched, 1, nullptr, nullptr, nullptr, nullptr, nullptr);
             wp_launch(SERT_WGRAD_FORM_SCALAR, cdiv(d, 64));
         }
     }
     if (heavy_fused && !heavy_combined) {   // (no level 1, or the fused upper levels took it: the combine alone)
         const PlusJob j = heavy_combine_job();
-        hipLaunchKernelGGL(segsum_rows_plus, dim3(j.extra, cdiv(d / 4, 32)), dim3(256), 0, m->stream, (const float*)nullptr,
-                           (const int32_t*)nullptr, (const int4*)nullptr, 0, m->g_rw, (float*)nullptr, d, divisor, j);
+        launch(segsum_rows_plus, dim3(j.extra, cdiv(d / 4, 32)), dim3(256), 0, m->stream, (const float*)nullptr,
+               (const int32_t*)nullptr, (const int4*)nullptr, 0, m->g_rw, (float*)nullptr, d, divisor, j);
         wp[7] = 1;
     }
     return 0;
@@ -245,8 +245,8 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         const int4* items = ds.idx_items + bx.item_off[l];
         const float* in = (l == 0) ? m->ll_r : m->ll_rpart + (size_t)bx.part_off[l - 1];
         float* pout = m->ll_rpart + (size_t)bx.part_off[l];
-        hipLaunchKernelGGL(segsum_scalar_wave, dim3(cdiv(nitems, 4)), dim3(256), 0, m->stream, in, rows, items, nitems,
-                           m->ll_rsum, pout);
+        launch(segsum_scalar_wave, dim3(cdiv(nitems, 4)), dim3(256), 0, m->stream, in, rows, items, nitems,
+               m->ll_rsum, pout);
     }
     // the dense heavy words inside the tree's launches (round 5; SERT_HEAVY_NO_FUSE in a variants build: the two launches behind the tree)
     static const bool ll_no_fuse = variant_knob("SERT_HEAVY_NO_FUSE") != nullptr;
@@ -279,32 +279,32 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
                 PlusJobLL j = ll_job;
                 j.dense = dsl;
                 if (l == 1) { j.j.kind = 2; j.j.extra = bx.dense_cnt; j.j.src = m->hpart; ll_heavy_combined = true; }
-                hipLaunchKernelGGL(segsum_rows_plus_ll, dim3(j.j.extra + cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0, m->stream, in,
-                                   rows, items, nitems, m->dZu, pout, V, dsl, j);
+                launch(segsum_rows_plus_ll, dim3(j.j.extra + cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0, m->stream, in,
+                       rows, items, nitems, m->dZu, pout, V, dsl, j);
                 wp_launch(SERT_WGRAD_FORM_ROWS_PLUS_LL, cdiv(V / 4, 64));
                 continue;
             }
-            hipLaunchKernelGGL((segsum_rows<64, true, true, true>), dim3(cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0,
-                               m->stream, in, rows, items, nitems, m->dZu, pout, V, 1.0f,
-                               (unsigned char*)nullptr, 1, (const float*)m->Zu,
-                               (const float*)m->ll_rsum, dsl);
+            launch((segsum_rows<64, true, true, true>), dim3(cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0,
+                   m->stream, in, rows, items, nitems, m->dZu, pout, V, 1.0f,
+                   (unsigned char*)nullptr, 1, (const float*)m->Zu,
+                   (const float*)m->ll_rsum, dsl, XcdLists());
             wp_launch(SERT_WGRAD_FORM_ROWS64, cdiv(V / 4, 64));
         } else if (V % 4 == 0) {
-            hipLaunchKernelGGL((segsum_rows<64, true, true>), dim3(cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0,
-                               m->stream, in, rows, items, nitems, m->dZu, pout, V, 1.0f,
-                               (unsigned char*)nullptr, 1, (const float*)m->Zu,
-                               (const float*)m->ll_rsum);
+            launch((segsum_rows<64, true, true>), dim3(cdiv(nitems, 4), cdiv(V / 4, 64)), dim3(256), 0,
+                   m->stream, in, rows, items, nitems, m->dZu, pout, V, 1.0f,
+                   (unsigned char*)nullptr, 1, (const float*)m->Zu,
+                   (const float*)m->ll_rsum, DenseSlots(), XcdLists());
             wp_launch(SERT_WGRAD_FORM_ROWS64, cdiv(V / 4, 64));
         } else if (fused_odd) {
-            hipLaunchKernelGGL((segsum_rows_scalar<true, true>), dim3(cdiv(nitems, 4), cdiv(V, 64)), dim3(256), 0, m->stream, in,
-                               rows, items, nitems, m->dZu, pout, V, 1.0f, (unsigned char*)nullptr, 1, (const float*)m->Zu,
-                               (const float*)((l == 0) ? m->ll_r : m->ll_rpart + (size_t)bx.part_off[l - 1]),
-                               (l == 0) ? (const int32_t*)(ds.idx_rows + bx.rows_off) : (const int32_t*)nullptr,
-                               m->ll_rsum, m->ll_rpart + (size_t)bx.part_off[l]);
+            launch((segsum_rows_scalar<true, true>), dim3(cdiv(nitems, 4), cdiv(V, 64)), dim3(256), 0, m->stream, in,
+                   rows, items, nitems, m->dZu, pout, V, 1.0f, (unsigned char*)nullptr, 1, (const float*)m->Zu,
+                   (const float*)((l == 0) ? m->ll_r : m->ll_rpart + (size_t)bx.part_off[l - 1]),
+                   (l == 0) ? (const int32_t*)(ds.idx_rows + bx.rows_off) : (const int32_t*)nullptr,
+                   m->ll_rsum, m->ll_rpart + (size_t)bx.part_off[l]);
             wp_launch(SERT_WGRAD_FORM_SCALAR_LL, cdiv(V, 64));
         } else {
-            hipLaunchKernelGGL((segsum_rows_scalar<true>), dim3(cdiv(nitems, 4), cdiv(V, 64)), dim3(256), 0, m->stream, in,
-                               rows, items, nitems, m->dZu, pout, V, 1.0f, (unsigned char*)nullptr, 1);
+            launch((segsum_rows_scalar<true>), dim3(cdiv(nitems, 4), cdiv(V, 64)), dim3(256), 0, m->stream, in,
+                   rows, items, nitems, m->dZu, pout, V, 1.0f, (unsigned char*)nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr);
             wp_launch(SERT_WGRAD_FORM_SCALAR, cdiv(V, 64));
         }
     }
@@ -313,8 +313,8 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         j.dense.n = bx.dense_cnt;
         for (int h = 0; h < kHeavyMax; ++h) j.dense.slot[h] = h < bx.dense_cnt ? bx.dense_slot[h] : -2;
         j.j.kind = 2; j.j.extra = bx.dense_cnt; j.j.src = m->hpart;
-        hipLaunchKernelGGL(segsum_rows_plus_ll, dim3(j.j.extra, cdiv(V / 4, 64)), dim3(256), 0, m->stream, (const float*)nullptr,
-                           (const int32_t*)nullptr, (const int4*)nullptr, 0, m->dZu, (float*)nullptr, V, j.dense, j);
+        launch(segsum_rows_plus_ll, dim3(j.j.extra, cdiv(V / 4, 64)), dim3(256), 0, m->stream, (const float*)nullptr,
+               (const int32_t*)nullptr, (const int4*)nullptr, 0, m->dZu, (float*)nullptr, V, j.dense, j);
         wp[7] = 1;
     }
     if (V % 4 == 0 && bx.dense_cnt > 0 && !ll_heavy_fused) {
@@ -327,17 +327,17 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         static const bool attr_set = hipFuncSetAttribute((const void*)segsum_heavy_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          2 * kHeavyMax * 128 * (int)sizeof(float4)) == hipSuccess;
         if (!attr_set) SERT_FAIL("cannot reserve the LDS of segsum_heavy_wide");
-        hipLaunchKernelGGL(segsum_heavy_wide, dim3(nblk * cdiv(d4, 128)), dim3(512), (size_t)2 * kHeavyMax * 128 * sizeof(float4), m->stream,
-                           (const float*)m->J, cnt, B, V, m->hpart);
+        launch(segsum_heavy_wide, dim3(nblk * cdiv(d4, 128)), dim3(512), (size_t)2 * kHeavyMax * 128 * sizeof(float4), m->stream,
+               (const float*)m->J, cnt, B, V, m->hpart);
         DenseSlots dsl;
         dsl.n = bx.dense_cnt;
         for (int h = 0; h < kHeavyMax; ++h) dsl.slot[h] = h < bx.dense_cnt ? bx.dense_slot[h] : -2;
-        hipLaunchKernelGGL(segsum_heavy_combine_ll, dim3(bx.dense_cnt, cdiv(d4, 32)), dim3(256), 0, m->stream,
-                           (const float*)m->hpart, nblk, V, dsl, m->dZu, (const float*)m->Zu, (const float*)m->ll_rsum);
+        launch(segsum_heavy_combine_ll, dim3(bx.dense_cnt, cdiv(d4, 32)), dim3(256), 0, m->stream,
+               (const float*)m->hpart, nblk, V, dsl, m->dZu, (const float*)m->Zu, (const float*)m->ll_rsum);
     }
     if (V % 4 != 0 && !fused_odd)   // (odd V_e, split form: separate finishing pass)
-        hipLaunchKernelGGL(ll_dzu_combine, dim3(grid_for((int64_t)m->ll_U * V)), dim3(256), 0, m->stream, m->dZu,
-                           (const float*)m->Zu, (const float*)m->ll_rsum, (int64_t)m->ll_U, V);
+        launch(ll_dzu_combine, dim3(grid_for((int64_t)m->ll_U * V)), dim3(256), 0, m->stream, m->dZu,
+               (const float*)m->Zu, (const float*)m->ll_rsum, (int64_t)m->ll_U, V);
     return 0;
 }
 

@@ -13,9 +13,9 @@ static int reduce_rowloss(sert_model* m, hipStream_t st) {
         // few rows: the finalisation sums them itself (fp64, fixed order) -- one 4 us launch less on a small step's chain
         m->loss_from_rows = true;
         nb = B;
-    } else hipLaunchKernelGGL(sum_partial, dim3(nb), dim3(256), 0, st, m->rowloss, (size_t)B, m->red_loss);
+    } else launch(sum_partial, dim3(nb), dim3(256), 0, st, m->rowloss, (size_t)B, m->red_loss);
     if (is_dp(m))
-        hipLaunchKernelGGL(partials_to_scalar, dim3(1), dim3(256), 0, st, m->red_loss, nb, m->g_loss);
+        launch(partials_to_scalar, dim3(1), dim3(256), 0, st, m->red_loss, nb, m->g_loss);
     m->n_loss_partials = nb;
     return 0;
 }
@@ -27,11 +27,11 @@ static void launch_stream_opt(sert_model* m, hipStream_t st, float* p, float* g,
     const bool keep = m->cfg.keep_grads != 0;
     const int rows_mode = kRowsAll;   // (kernels_opt.h keeps the rows_mode parameter of its kernels; the host always passes kRowsAll)
     if (is_vs(m)) {
-        if (keep) hipLaunchKernelGGL((adam_l2<true>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, aa, sq, bits, row_len, rows_mode, sq_new);
-        else      hipLaunchKernelGGL((adam_l2<false>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, aa, sq, bits, row_len, rows_mode, sq_new);
+        if (keep) launch((adam_l2<true>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, aa, sq, bits, row_len, rows_mode, sq_new);
+        else      launch((adam_l2<false>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, aa, sq, bits, row_len, rows_mode, sq_new);
     } else {
-        if (keep) hipLaunchKernelGGL((adadelta_l2<true>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, da, sq, bits, row_len, rows_mode);
-        else      hipLaunchKernelGGL((adadelta_l2<false>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, da, sq, bits, row_len, rows_mode);
+        if (keep) launch((adadelta_l2<true>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, da, sq, bits, row_len, rows_mode);
+        else      launch((adadelta_l2<false>), dim3(nb), dim3(256), 0, st, p, g, s0, s1, count, da, sq, bits, row_len, rows_mode);
     }
 }
 
@@ -87,7 +87,7 @@ static int launch_lazy_word_update(sert_model* m, const ParamTensor& t, const ui
                                                  (int)cdiv(nrows, 8u)));
         nb_skip = nb;
 #define SERT_SKIP_LAUNCH(ADAM, LPR, CPL)                                                                                   \
-    hipLaunchKernelGGL((dense_update_skip<ADAM, LPR, CPL>), dim3(nb), dim3(256), 0, m->stream, t.p, (const float*)t.g, t.s0, \
+    launch((dense_update_skip<ADAM, LPR, CPL>), dim3(nb), dim3(256), 0, m->stream, t.p, (const float*)t.g, t.s0,             \
            t.s1, nrows, aa, da, sq, tf, (unsigned)c.word_dim, lz, sk)
         // d_w = 300: 75 float4 per row are 3 x 32 lanes at 78 % or 2 x 64 at 59 % of the lanes, and eight rows per
         // workgroup instead of four.  Measured (tools/experiments/r05_skip_32x3.sh, three rounds, 64 x 2 -> 32 x 3):
@@ -113,11 +113,11 @@ static int launch_lazy_word_update(sert_model* m, const ParamTensor& t, const ui
     } else {
     ++m->upd_counts[1];
     if (is_vs(m))
-        hipLaunchKernelGGL((dense_update_lazy<true>), dim3(nb), dim3(256), 0, m->stream, t.p, (const float*)t.g, t.s0, t.s1, t.n,
-                           aa, da, sq, tf, (unsigned)c.word_dim, lz);
+        launch((dense_update_lazy<true>), dim3(nb), dim3(256), 0, m->stream, t.p, (const float*)t.g, t.s0, t.s1, t.n,
+               aa, da, sq, tf, (unsigned)c.word_dim, lz);
     else
-        hipLaunchKernelGGL((dense_update_lazy<false>), dim3(nb), dim3(256), 0, m->stream, t.p, (const float*)t.g, t.s0, t.s1, t.n,
-                           aa, da, sq, tf, (unsigned)c.word_dim, lz);
+        launch((dense_update_lazy<false>), dim3(nb), dim3(256), 0, m->stream, t.p, (const float*)t.g, t.s0, t.s1, t.n,
+               aa, da, sq, tf, (unsigned)c.word_dim, lz);
     }
     m->rw_last_cur ^= 1;
     m->rw_stale = !lz.write_all;
@@ -278,8 +278,8 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         // here on the side stream unless the step's forward already drew them in front of its fork:
         // ev_small below orders them before anything of the next step
         const int64_t count = (int64_t)c.batch_size * c.num_negatives;
-        hipLaunchKernelGGL(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, ss, m->neg_alt, count,
-                           (int64_t)m->rank * count, (uint32_t)c.num_entities, c.seed, (uint64_t)m->step * 2);
+        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, ss, m->neg_alt, count,
+               (int64_t)m->rank * count, (uint32_t)c.num_entities, c.seed, (uint64_t)m->step * 2, nullptr, 0, nullptr, 0);
         m->neg_alt_step = m->step;
     }
     auto small_tensors = [&](hipStream_t ss, unsigned mask) {
@@ -312,8 +312,8 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
             if (m->re_sq_for[re_cur] != m->step) {
                 // no previous launch left this step's sums (first step, another schedule in between, the host replaced
                 // the table): the same partials from a read-only pass IN FRONT of the update, and the tail joins once
-                hipLaunchKernelGGL(sumsq_like_small, dim3(blocks), dim3(256), 0, ss, (const float*)m->re, m->n_re, l2k,
-                                   m->re_sq + re_cur * re_cap);
+                launch(sumsq_like_small, dim3(blocks), dim3(256), 0, ss, (const float*)m->re, m->n_re, l2k,
+                       m->re_sq + re_cur * re_cap);
                 m->re_sq_for[re_cur] = m->step;
                 small_needs_join = true;
             }
@@ -321,13 +321,13 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
         if (blocks > 0) {
             const bool keep = c.keep_grads != 0;
             if (is_vs(m) && sq_new) {
-                hipLaunchKernelGGL((optimizer_small<true, false>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq, sq_new);
+                launch((optimizer_small<true, false>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq, sq_new);
             } else if (is_vs(m)) {
-                if (keep) hipLaunchKernelGGL((optimizer_small<true, true>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq);
-                else      hipLaunchKernelGGL((optimizer_small<true, false>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq);
+                if (keep) launch((optimizer_small<true, true>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq, nullptr);
+                else      launch((optimizer_small<true, false>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq, nullptr);
             } else {
-                if (keep) hipLaunchKernelGGL((optimizer_small<false, true>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq);
-                else      hipLaunchKernelGGL((optimizer_small<false, false>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq);
+                if (keep) launch((optimizer_small<false, true>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq, nullptr);
+                else      launch((optimizer_small<false, false>), dim3(blocks), dim3(256), 0, ss, st, aa, da, sq, nullptr);
             }
         }
         n_sq += blocks;
@@ -345,7 +345,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     if (P.defer_re && m->re_sq_for[re_cur] != m->step) {
         // no previous deferred launch left this step's sums (first step, another schedule in between, the
         // host replaced the table): the same partials from a read-only pass, in front of the join
-        hipLaunchKernelGGL(sumsq_like_adam, dim3(re_nb), dim3(256), 0, ss, (const float*)m->re, m->n_re, m->re_sq + re_cur * re_cap);
+        launch(sumsq_like_adam, dim3(re_nb), dim3(256), 0, ss, (const float*)m->re, m->n_re, m->re_sq + re_cur * re_cap);
         m->re_sq_for[re_cur] = m->step;
     }
     if (side_small && small_needs_join) {
@@ -407,13 +407,13 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
                 m->tail_pending = true;
             } else {
                 ++m->tail_counts[0];
-                if (c.keep_grads) hipLaunchKernelGGL((vs_tail<true>), dim3(nb), dim3(1024), 0, m->stream, ta);
-                else              hipLaunchKernelGGL((vs_tail<false>), dim3(nb), dim3(1024), 0, m->stream, ta);
+                if (c.keep_grads) launch((vs_tail<true>), dim3(nb), dim3(1024), 0, m->stream, ta);
+                else              launch((vs_tail<false>), dim3(nb), dim3(1024), 0, m->stream, ta);
             }
         } else
-        hipLaunchKernelGGL(finalize_loss, dim3(1), dim3(256), 0, m->stream, lp, nl, m->red_sq,
-                           n_sq, inv_batch, reg_scale, loss_dst, flag, publish ? ++m->loss_seq : 0u,
-                           is_dp(m) ? (const float*)m->g_sq : (const float*)nullptr);
+        launch(finalize_loss, dim3(1), dim3(256), 0, m->stream, lp, nl, m->red_sq,
+               n_sq, inv_batch, reg_scale, loss_dst, flag, publish ? ++m->loss_seq : 0u,
+               is_dp(m) ? (const float*)m->g_sq : (const float*)nullptr);
     }
     if (any_ag) {
         // the loss leaves first; the next kernel that reads a parameter waits for the last slab
@@ -446,10 +446,10 @@ static bool fused_prologue_applies(const sert_model* m) { return fused_prologue_
 // sampler of optimiser step m->step + zeroing of the small gradient buffers
 static void launch_fused_prologue(sert_model* m) {
     const int64_t count = (int64_t)m->cfg.batch_size * m->cfg.num_negatives;
-    hipLaunchKernelGGL(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, m->stream, m->neg,
-                       count, (int64_t)m->rank * count, (uint32_t)m->cfg.num_entities, m->cfg.seed,
-                       (uint64_t)m->step * 2, reinterpret_cast<float4*>(m->gflat + zero_from(m)),
-                       (m->gflat_alloc - zero_from(m)) / 4, (uint4*)nullptr, (size_t)0);
+    launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, m->stream, m->neg,
+           count, (int64_t)m->rank * count, (uint32_t)m->cfg.num_entities, m->cfg.seed,
+           (uint64_t)m->step * 2, reinterpret_cast<float4*>(m->gflat + zero_from(m)),
+           (m->gflat_alloc - zero_from(m)) / 4, (uint4*)nullptr, (size_t)0);
 }
 
 static bool use_touched_now(const sert_model* m) {

@@ -24,10 +24,10 @@ template <bool RAW>
 static void rank_rows_launch(hipStream_t s, int mode, const float* S, int Qc, int V, int kk, const RankSortScratch& r, int32_t* idx,
                              float* val) {
     if (mode == RANK_LDS) {
-        if (V <= 1024)      hipLaunchKernelGGL((rank_rows_lds<1024, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-        else if (V <= 2048) hipLaunchKernelGGL((rank_rows_lds<2048, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-        else if (V <= 4096) hipLaunchKernelGGL((rank_rows_lds<4096, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
-        else                hipLaunchKernelGGL((rank_rows_lds<kRankLdsMax, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        if (V <= 1024)      launch((rank_rows_lds<1024, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        else if (V <= 2048) launch((rank_rows_lds<2048, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        else if (V <= 4096) launch((rank_rows_lds<4096, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
+        else                launch((rank_rows_lds<kRankLdsMax, RAW>), dim3(Qc), dim3(256), 0, s, S, V, kk, idx, val);
         return;
     }
     // key in 11 + 11 + 10-bit digits over iota values, then the query index: stability keeps, inside a query, the key order
@@ -35,15 +35,15 @@ static void rank_rows_launch(hipStream_t s, int mode, const float* S, int Qc, in
     const int n = Qc * V;
     int32_t *ka = r.keys, *va = r.keys + (size_t)n, *kb = r.keys + (size_t)2 * n, *vb = r.keys + (size_t)3 * n;
     int32_t* bin_total = r.hist + (size_t)kSortMaxBins * cdiv(n, kSortTile);
-    hipLaunchKernelGGL(rank_keys<RAW>, dim3(grid_for(n)), dim3(256), 0, s, S, n, ka);
+    launch(rank_keys<RAW>, dim3(grid_for(n)), dim3(256), 0, s, S, n, ka);
     csort_pass(s, ka, nullptr, kb, vb, n, 0, 11, r.hist, bin_total);
     csort_pass(s, kb, vb, ka, va, n, 11, 11, r.hist, bin_total);
     csort_pass(s, ka, va, kb, vb, n, 22, 10, r.hist, bin_total);
     int qbits = 1;
     while ((1 << qbits) < Qc) ++qbits;
-    hipLaunchKernelGGL(rank_query_keys, dim3(grid_for(n)), dim3(256), 0, s, vb, n, V, kb);
+    launch(rank_query_keys, dim3(grid_for(n)), dim3(256), 0, s, vb, n, V, kb);
     csort_pass(s, kb, vb, ka, va, n, 0, qbits, r.hist, bin_total);
-    hipLaunchKernelGGL(rank_emit<RAW>, dim3(grid_for((int64_t)Qc * kk)), dim3(256), 0, s, va, S, Qc, V, kk, idx, val);
+    launch(rank_emit<RAW>, dim3(grid_for((int64_t)Qc * kk)), dim3(256), 0, s, va, S, Qc, V, kk, idx, val);
 }
 
 // The ranking kernels on the rows of S (Qc, V), stream s: the first kk of every row into idx / val (Qc, kk), ordered and

@@ -11,19 +11,19 @@ static int fs_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         SERT_ID_DISPATCH(c.id_bytes, {
             const IdT* X = (const IdT*)ds.x + row0 * n;
             if (dw % 4 == 0)
-                hipLaunchKernelGGL((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+                launch((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
             else
-                hipLaunchKernelGGL((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+                launch((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
         });
     }
     {
         ScopedTimer t(m, TG_GEMM_FWD);
         launch_gemm<false, false, EPI_BIAS_TANH>(m->stream, m->H, m->W, m->T, m->b, B, de, dw, dw, de, de);
         // p = clip(t) ; logits = p.R_e^T   (B, V)
-        hipLaunchKernelGGL(vs_clip, dim3(grid_for((int64_t)B * de)), dim3(256), 0, m->stream, m->T, m->DH2,
-                           (size_t)B * de);
+        launch(vs_clip, dim3(grid_for((int64_t)B * de)), dim3(256), 0, m->stream, m->T, m->DH2,
+               (size_t)B * de);
     }
     const float inv_batch = 1.0f / (float)c.global_batch_size;
     const int tile = m->fs_tile > 0 ? m->fs_tile : B;
@@ -37,8 +37,8 @@ static int fs_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             ScopedTimer t(m, TG_LOSS);
             // rows up to 2048 entities stay in registers (one read, one write)
 #define SERT_FS_CE(EPL)                                                                                   \
-    hipLaunchKernelGGL((fs_softmax_ce<TRAIN, EPL>), dim3(cdiv(rows, 4)), dim3(256), 0, m->stream, m->Z, \
-                       ds.y + row0 + r0, TRAIN ? ds.w + row0 + r0 : nullptr, m->rowloss + r0, rows, V, inv_batch)
+    launch((fs_softmax_ce<TRAIN, EPL>), dim3(cdiv(rows, 4)), dim3(256), 0, m->stream, m->Z,             \
+           ds.y + row0 + r0, TRAIN ? ds.w + row0 + r0 : nullptr, m->rowloss + r0, rows, V, inv_batch)
             if (V <= 64 * 16)      SERT_FS_CE(16);
             else if (V <= 64 * 32) SERT_FS_CE(32);
             else                   SERT_FS_CE(0);
@@ -84,8 +84,8 @@ static int fs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         // dp = dZ.R_e (B, d_e) ; da = dp * clip'(t) * tanh'(a)
         ScopedTimer t(m, TG_GEMM_DX);
         if (!tiled) SERT_TRY((gemm_long_k<false, false>(m, m->stream, m->Z, m->re, m->DA, B, de, V, V, de)));
-        hipLaunchKernelGGL(vs_tanh_backward, dim3(grid_for((int64_t)B * de)), dim3(256), 0, m->stream, m->DA,
-                           m->T, (size_t)B * de);
+        launch(vs_tanh_backward, dim3(grid_for((int64_t)B * de)), dim3(256), 0, m->stream, m->DA,
+               m->T, (size_t)B * de);
     }
     {
         static const int want_splits = [] { const char* e = variant_knob("SERT_DW_SPLITS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }();
@@ -130,27 +130,27 @@ static int ll_stream_loss(sert_model* m, const DataSplit& ds, size_t row0, const
     // is then a per-WORD quantity, and dL/dZ of every token goes to Z
     const float* logits = slot ? m->Zu : m->Z;
     const int64_t lrows = slot ? m->ll_U : rows;
-    hipLaunchKernelGGL((ll_s_tokstat<V4>), dim3((unsigned)(lrows * nseg)), dim3(256), 0, s, logits, V, nseg, m->ll_tokstat);
-    hipLaunchKernelGGL(ll_s_lse, dim3(cdiv(lrows, 4)), dim3(256), 0, s, m->ll_tokstat, lrows, nseg, m->ll_lse);
-    hipLaunchKernelGGL((ll_s_window<V4>), dim3((unsigned)((int64_t)B * nseg)), dim3(256), 0, s, logits, m->ll_lse, n, V,
-                       nseg, m->J, m->ll_jstat, slot);
-    hipLaunchKernelGGL((ll_s_rowloss<TRAIN>), dim3(B), dim3(256), 0, s, m->J, m->ll_jstat, y, indptr,
-                       ds.csr_indices, ds.csr_data, w, m->rowloss, m->ll_rowinfo, labfix, V, nseg, inv_batch);
+    launch((ll_s_tokstat<V4>), dim3((unsigned)(lrows * nseg)), dim3(256), 0, s, logits, V, nseg, m->ll_tokstat);
+    launch(ll_s_lse, dim3(cdiv(lrows, 4)), dim3(256), 0, s, m->ll_tokstat, lrows, nseg, m->ll_lse);
+    launch((ll_s_window<V4>), dim3((unsigned)((int64_t)B * nseg)), dim3(256), 0, s, logits, m->ll_lse, n, V,
+           nseg, m->J, m->ll_jstat, slot);
+    launch((ll_s_rowloss<TRAIN>), dim3(B), dim3(256), 0, s, m->J, m->ll_jstat, y, indptr,
+           ds.csr_indices, ds.csr_data, w, m->rowloss, m->ll_rowinfo, labfix, V, nseg, inv_batch);
     if (!TRAIN) return 0;
-    hipLaunchKernelGGL((ll_s_dj<V4>), dim3((unsigned)((int64_t)B * nseg)), dim3(256), 0, s, m->J, m->ll_rowinfo, V, nseg);
-    hipLaunchKernelGGL(ll_s_labfix, dim3(B), dim3(256), 0, s, m->J, y, indptr, ds.csr_indices, labfix, V);
-    hipLaunchKernelGGL((ll_s_tokr<V4>), dim3((unsigned)(rows * nseg)), dim3(256), 0, s, logits, m->ll_lse, m->J, n, V,
-                       nseg, m->ll_rpart, slot);
-    hipLaunchKernelGGL(ll_s_rsum, dim3(cdiv(rows, 4)), dim3(256), 0, s, m->ll_rpart, rows, nseg, m->ll_r);
+    launch((ll_s_dj<V4>), dim3((unsigned)((int64_t)B * nseg)), dim3(256), 0, s, m->J, m->ll_rowinfo, V, nseg);
+    launch(ll_s_labfix, dim3(B), dim3(256), 0, s, m->J, y, indptr, ds.csr_indices, labfix, V);
+    launch((ll_s_tokr<V4>), dim3((unsigned)(rows * nseg)), dim3(256), 0, s, logits, m->ll_lse, m->J, n, V,
+           nseg, m->ll_rpart, slot);
+    launch(ll_s_rsum, dim3(cdiv(rows, 4)), dim3(256), 0, s, m->ll_rpart, rows, nseg, m->ll_r);
     if (slot) {
         // distinct-word mode: stop here -- dJ (in J) and r_ik are all the per-word backward
         // needs (dzu_from_dj); the per-token dL/dZ pass and its 2 x B*n*V_e floats are skipped.
         // The word rows must hold LOG-probabilities for the finishing transform:
-        hipLaunchKernelGGL(ll_s_logp_rows, dim3((unsigned)(lrows * nseg)), dim3(256), 0, s, m->Zu, m->ll_lse, V, nseg);
+        launch(ll_s_logp_rows, dim3((unsigned)(lrows * nseg)), dim3(256), 0, s, m->Zu, m->ll_lse, V, nseg);
         return 0;
     }
-    hipLaunchKernelGGL((ll_s_dz<V4>), dim3((unsigned)(rows * nseg)), dim3(256), 0, s, m->Z, m->ll_lse, m->J, m->ll_r, n,
-                       V, nseg);
+    launch((ll_s_dz<V4>), dim3((unsigned)(rows * nseg)), dim3(256), 0, s, m->Z, m->ll_lse, m->J, m->ll_r, n,
+           V, nseg);
     return 0;
 }
 
@@ -183,20 +183,20 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         if (m->ll_dedup) {
             const uint32_t* U = reinterpret_cast<const uint32_t*>(ds.idx_uwords + bx->uw_off);
             if (d % 4 == 0)
-                hipLaunchKernelGGL((ll_gather_rows<uint32_t, 4>), dim3(grid_for(grows * d / 4, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, U, m->rw, m->G, grows, d);
+                launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(grows * d / 4, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, U, m->rw, m->G, grows, d);
             else
-                hipLaunchKernelGGL((ll_gather_rows<uint32_t, 1>), dim3(grid_for(grows * d, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, U, m->rw, m->G, grows, d);
+                launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(grows * d, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, U, m->rw, m->G, grows, d);
         } else {
             SERT_ID_DISPATCH(c.id_bytes, {
                 const IdT* X = (const IdT*)ds.x + row0 * n;
                 if (d % 4 == 0)
-                    hipLaunchKernelGGL((ll_gather_rows<IdT, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)),
-                                       dim3(256), 0, m->stream, X, m->rw, m->G, rows, d);
+                    launch((ll_gather_rows<IdT, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)),
+                           dim3(256), 0, m->stream, X, m->rw, m->G, rows, d);
                 else
-                    hipLaunchKernelGGL((ll_gather_rows<IdT, 1>), dim3(grid_for(rows * d, 256, 1 << 20)),
-                                       dim3(256), 0, m->stream, X, m->rw, m->G, rows, d);
+                    launch((ll_gather_rows<IdT, 1>), dim3(grid_for(rows * d, 256, 1 << 20)),
+                           dim3(256), 0, m->stream, X, m->rw, m->G, rows, d);
             });
         }
     }
@@ -217,9 +217,9 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         ScopedTimer t(m, TG_LOSS);
         if (m->ll_dedup)   // the per-token log-softmax, once per distinct word
         {
-            if (V <= 64 * 16)      hipLaunchKernelGGL((ll_logsoftmax_rows<16>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
-            else if (V <= 64 * 32) hipLaunchKernelGGL((ll_logsoftmax_rows<32>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
-            else                   hipLaunchKernelGGL((ll_logsoftmax_rows<0>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
+            if (V <= 64 * 16)      launch((ll_logsoftmax_rows<16>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
+            else if (V <= 64 * 32) launch((ll_logsoftmax_rows<32>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
+            else                   launch((ll_logsoftmax_rows<0>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
         }
         // 512 threads per row: 302 us at 256 (too few waves to hide the slab load), 228 at
         // 512, 320 at 640 (one wave per token, but only two workgroups fit a CU)
@@ -236,8 +236,8 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             static const bool no_wave = variant_knob("SERT_LL_NO_ROW_WAVE") != nullptr;   // cross-check knob
 #define SERT_LL_WAVE(E)                                                                                        \
     m->ll_form[0] = SERT_LL_FORM_WAVE; m->ll_form[1] = E;                                                       \
-    hipLaunchKernelGGL((ll_row_wave<E>), dim3(cdiv(B, 4)), dim3(256), 0, m->stream, (const float*)m->Zu, slot, y, \
-                       indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, B, n, V, inv_batch, m->J, m->ll_r)
+    launch((ll_row_wave<E>), dim3(cdiv(B, 4)), dim3(256), 0, m->stream, (const float*)m->Zu, slot, y,             \
+           indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, B, n, V, inv_batch, m->J, m->ll_r)
             // (its row fetches are buffer loads off one descriptor of the table: 32-bit byte offsets)
             if (!no_wave && V % 4 == 0 && V <= 2048 && (size_t)m->ll_U * V * sizeof(float) < ((size_t)1 << 32)) {
                 const int e4 = cdiv(V / 4, 64);
@@ -249,29 +249,29 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
 #undef SERT_LL_WAVE
             if (V <= nt128_below) {
                 m->ll_form[0] = SERT_LL_FORM_TABLE; m->ll_form[1] = 128;
-                hipLaunchKernelGGL((ll_row_from_table<128>), dim3(B), dim3(128), lds, m->stream, (const float*)m->Zu,
-                                   slot, y, indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch,
-                                   m->J, m->ll_r);
+                launch((ll_row_from_table<128>), dim3(B), dim3(128), lds, m->stream, (const float*)m->Zu,
+                       slot, y, indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch,
+                       m->J, m->ll_r);
             } else {
                 m->ll_form[0] = SERT_LL_FORM_TABLE; m->ll_form[1] = 512;
-                hipLaunchKernelGGL((ll_row_from_table<512>), dim3(B), dim3(512), lds, m->stream, (const float*)m->Zu,
-                                   slot, y, indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch,
-                                   m->J, m->ll_r);
+                launch((ll_row_from_table<512>), dim3(B), dim3(512), lds, m->stream, (const float*)m->Zu,
+                       slot, y, indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch,
+                       m->J, m->ll_r);
             }
         } else {
             m->ll_form[0] = SERT_LL_FORM_FUSED_ROW; m->ll_form[1] = 512;
-            hipLaunchKernelGGL((ll_fused_row<TRAIN, 512>), dim3(B), dim3(512), fused_lds, m->stream,
-                               m->ll_dedup ? m->J : m->Z, (const float*)m->Zu, slot, y, indptr, ds.csr_indices,
-                               ds.csr_data, w, m->rowloss, n, V, inv_batch, m->ll_r);
+            launch((ll_fused_row<TRAIN, 512>), dim3(B), dim3(512), fused_lds, m->stream,
+                   m->ll_dedup ? m->J : m->Z, (const float*)m->Zu, slot, y, indptr, ds.csr_indices,
+                   ds.csr_data, w, m->rowloss, n, V, inv_batch, m->ll_r);
         }
     } else if (rowwise) {
         // the plain row-per-workgroup kernels (kept as a cross-check of the streaming path)
         ScopedTimer t(m, TG_LOSS);
         m->ll_form[0] = SERT_LL_FORM_ROWWISE;
-        hipLaunchKernelGGL(ll_softmax_rows, dim3(cdiv(rows, 4)), dim3(256), 0, m->stream, m->Z, rows,
-                           V);
-        hipLaunchKernelGGL((ll_window<TRAIN>), dim3(B), dim3(256), 0, m->stream, m->Z, m->J, y,
-                           indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch);
+        launch(ll_softmax_rows, dim3(cdiv(rows, 4)), dim3(256), 0, m->stream, m->Z, rows,
+               V);
+        launch((ll_window<TRAIN>), dim3(B), dim3(256), 0, m->stream, m->Z, m->J, y,
+               indptr, ds.csr_indices, ds.csr_data, w, m->rowloss, n, V, inv_batch);
     } else {
         ScopedTimer t(m, TG_LOSS);
         m->ll_form[0] = SERT_LL_FORM_STREAM; m->ll_form[1] = V % 4 == 0 ? 1 : 0;
@@ -342,9 +342,9 @@ static int ll_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
         if (m->ll_dedup) {
             // dG already holds one row per distinct word: dR_w[word_u, :] = dG[u, :]
             const BatchIndex& bx = ds.idx_batches[(size_t)batch_index];
-            hipLaunchKernelGGL(ll_scatter_rows, dim3(grid_for(rows * d)), dim3(256), 0, m->stream, m->DG,
-                               ds.idx_uwords + bx.uw_off, rows, d, m->g_rw,
-                               (unsigned char*)nullptr);
+            launch(ll_scatter_rows, dim3(grid_for(rows * d)), dim3(256), 0, m->stream, m->DG,
+                   ds.idx_uwords + bx.uw_off, rows, d, m->g_rw,
+                   (unsigned char*)nullptr);
         } else {
             // dR_w[X[r],:] += dG[r,:]
             SERT_TRY(word_grad_segsum(m, ds, batch_index, m->DG, 1.0f));

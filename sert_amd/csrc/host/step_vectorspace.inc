@@ -14,15 +14,15 @@ static int vs_negatives(sert_model* m, const int64_t* negatives, uint64_t stream
             if (negatives[i] < 0 || negatives[i] >= Ve) SERT_FAIL("negative sample out of range [0, num_entities)");
         SERT_HIP(hipMemcpyAsync(m->neg_stage, negatives, count * sizeof(int64_t),
                                 hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(convert_i64_to_i32, dim3(grid_for(count)), dim3(256), 0, st,
-                           m->neg_stage, m->neg, count);
+        launch(convert_i64_to_i32, dim3(grid_for(count)), dim3(256), 0, st,
+               m->neg_stage, m->neg, count);
     } else {
         const int64_t global_offset = (int64_t)m->rank * count;
         // Philox stream position: even = training draws, odd = evaluation draws
         // (the reference keeps two independent RandomStreams, models.py:745-752).
-        hipLaunchKernelGGL(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0,
-                           st, m->neg, count, global_offset, (uint32_t)c.num_entities,
-                           c.seed, stream_pos);
+        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0,
+               st, m->neg, count, global_offset, (uint32_t)c.num_entities,
+               c.seed, stream_pos, nullptr, 0, nullptr, 0);
     }
     return 0;
 }
@@ -34,7 +34,7 @@ static void flush_pending_tail(sert_model* m) {
     m->tail_pending = false;
     ScopedTimer t(m, TG_FINALIZE);
     ++m->tail_counts[0];
-    hipLaunchKernelGGL((vs_tail<false>), dim3(m->tail_nb), dim3(1024), 0, m->stream, m->tail_args);
+    launch((vs_tail<false>), dim3(m->tail_nb), dim3(1024), 0, m->stream, m->tail_args);
 }
 
 // gather + mean-pool + projection: needs neither the negatives nor the gradient buffers
@@ -53,8 +53,8 @@ static int vs_project(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         ScopedTimer t(m, TG_GATHER);
         SERT_ID_DISPATCH(c.id_bytes, {
             const IdT* X = (const IdT*)ds.x + row0 * n;
-            hipLaunchKernelGGL((vs_project_x3<IdT>), dim3(vs_project_grid(B, m->num_cus)), dim3(PJ_THREADS), 0, m->stream, X, (const float*)m->rw,
-                               (const float*)m->W, (const float*)m->b, m->H, m->T, B, n, dw, de);
+            launch((vs_project_x3<IdT>), dim3(vs_project_grid(B, m->num_cus)), dim3(PJ_THREADS), 0, m->stream, X, (const float*)m->rw,
+                   (const float*)m->W, (const float*)m->b, m->H, m->T, B, n, dw, de);
         });
         return 0;
     }
@@ -70,24 +70,24 @@ static int vs_project(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             const int nhot = (ds.idx_tok_slot && (size_t)batch_index < ds.dense_cnt_of.size()) ? ds.dense_cnt_of[(size_t)batch_index] : 0;
             if (dw % 4 == 0 && nhot > 0 && (size_t)nhot * dw * sizeof(float) <= 48 * 1024) {
                 flush_pending_tail(m);
-                hipLaunchKernelGGL((vs_gather_mean_hot<IdT>), dim3(std::min<int64_t>(grid_for((int64_t)B * dw / 4, 256, 1 << 20), 8 * m->num_cus)),
-                                   dim3(256), (size_t)nhot * dw * sizeof(float), m->stream, X, (const uint8_t*)ds.idx_tok_slot + row0 * n,
-                                   (const int32_t*)ds.idx_dense_words + (size_t)batch_index * kHeavyMax, nhot, (const float*)m->rw, m->H, B, n, dw);
+                launch((vs_gather_mean_hot<IdT>), dim3(std::min<int64_t>(grid_for((int64_t)B * dw / 4, 256, 1 << 20), 8 * m->num_cus)),
+                       dim3(256), (size_t)nhot * dw * sizeof(float), m->stream, X, (const uint8_t*)ds.idx_tok_slot + row0 * n,
+                       (const int32_t*)ds.idx_dense_words + (size_t)batch_index * kHeavyMax, nhot, (const float*)m->rw, m->H, B, n, dw);
             } else
 #endif
             if (dw % 4 == 0 && m->tail_pending) {
                 // the previous step's tail: the leading workgroups of this launch (kernels_vs.h: vs_gather_mean_tail)
                 m->tail_pending = false;
                 ++m->tail_counts[1];
-                hipLaunchKernelGGL((vs_gather_mean_tail<IdT>), dim3(m->tail_nb + grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw, m->tail_args, (unsigned)m->tail_nb);
+                launch((vs_gather_mean_tail<IdT>), dim3(m->tail_nb + grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw, m->tail_args, (unsigned)m->tail_nb);
             } else if (dw % 4 == 0) {
-                hipLaunchKernelGGL((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+                launch((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
             } else {
                 flush_pending_tail(m);
-                hipLaunchKernelGGL((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
-                                   dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+                launch((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
+                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
             }
         });
     }
@@ -178,23 +178,23 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         const float* w = TRAIN ? ds.w + row0 : nullptr;
         const float inv_batch = 1.0f / (float)c.global_batch_size;
         dim3 block(256);
+        if (de > 512) SERT_FAIL("entity_dim > 512 is not supported");
         // training with a side stream: the fork event of the backward pass is this kernel's own
-        // completion signal (common.h: SERT_LAUNCH)
-        if (de > 512) SERT_FAIL("entity_dim > 512 is not supported");   // (before an event is armed)
-        if (TRAIN && m->plan.fork_at == SERT_VS_FORK_LOSS && m->plan.fork_carried) set_stop_event(m->ev_fork);
+        // completion signal (launch.h)
+        CarriedEvent carry(TRAIN && m->plan.fork_at == SERT_VS_FORK_LOSS && m->plan.fork_carried ? m->ev_fork : nullptr);
         if (de % 4 == 0) {
             const int nch = cdiv(de / 4, 16);
             dim3 grid(cdiv(B, 16));
 #define SERT_NCE_CASE(N)                                                                     \
     case N:                                                                                  \
-        SERT_LAUNCH((vs_nce<N, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y,          \
-                           m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,               \
-                           c.num_negatives, de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr); \
+        launch((vs_nce<N, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y,                \
+               m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,                            \
+               c.num_negatives, de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);       \
         break;
 #define SERT_NCE_REGS(N, C)                                                                  \
-    SERT_LAUNCH((vs_nce_regs<N, TRAIN, C>), grid, block, 0, m->stream, m->T, m->re, y,       \
-                       m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B, c.num_negatives,   \
-                       de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr)
+    launch((vs_nce_regs<N, TRAIN, C>), grid, block, 0, m->stream, m->T, m->re, y,            \
+           m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B, c.num_negatives,               \
+           de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr)
             static const bool no_regs = variant_knob("SERT_NCE_PER_CANDIDATE") != nullptr;
             const int nc = c.num_negatives + 1;
             // (d_e = 300, five float4 per lane and candidate: 256 VGPRs + AGPR spills, one wave per SIMD --
@@ -220,7 +220,6 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             }
 #undef SERT_NCE_REGS
 #undef SERT_NCE_CASE
-            set_stop_event(nullptr);   // (never leave an armed event behind a launch that did not happen)
             // (training: the kernel left one loss partial per workgroup in red_loss)
             m->nce_loss_partials = TRAIN ? cdiv(B, 16) : 0;
         } else {
@@ -229,9 +228,9 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             dim3 grid(cdiv(B, 4));
 #define SERT_NCE_CASE(N)                                                                     \
     case N:                                                                                  \
-        hipLaunchKernelGGL((vs_nce_scalar<N, TRAIN>), grid, block, 0, m->stream, m->T,      \
-                           m->re, y, m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,     \
-                           c.num_negatives, de, inv_batch);                                  \
+        launch((vs_nce_scalar<N, TRAIN>), grid, block, 0, m->stream, m->T,                  \
+               m->re, y, m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,                 \
+               c.num_negatives, de, inv_batch);                                              \
         break;
             switch (npl) {
                 SERT_NCE_CASE(1) SERT_NCE_CASE(2) SERT_NCE_CASE(3) SERT_NCE_CASE(4)
@@ -277,9 +276,9 @@ static int vs_bwd_fused_grid(int B) {
 static int vs_early_bucket(sert_model* m, const DataSplit& ds, size_t row0) {
     const auto& c = m->cfg;
     ScopedTimer t(m, TG_SORT, m->stream2);
-    hipLaunchKernelGGL(egrad_bucket, dim3(m->eg_num_sub), dim3(512), 0, m->stream2, (const int32_t*)nullptr, c.batch_size, c.num_negatives + 1,
-                       m->eg_sub_rows, m->eg_er_shift, m->eg_ranges, m->eg_entries, m->eg_offs,
-                       (const int32_t*)ds.y + row0, (const int32_t*)m->neg);
+    launch(egrad_bucket, dim3(m->eg_num_sub), dim3(512), 0, m->stream2, (const int32_t*)nullptr, c.batch_size, c.num_negatives + 1,
+           m->eg_sub_rows, m->eg_er_shift, m->eg_ranges, m->eg_entries, m->eg_offs,
+           (const int32_t*)ds.y + row0, (const int32_t*)m->neg);
     return 0;
 }
 // ... and the stable counting sort of the (entity, pair) keys of the SORTED chain (plan.sort_early); behind the fork that chain is
@@ -289,8 +288,8 @@ static int vs_early_sort(sert_model* m, const DataSplit& ds, size_t row0) {
     const auto& c = m->cfg;
     const int total = c.batch_size * (c.num_negatives + 1);
     ScopedTimer t(m, TG_SORT, m->stream2);
-    hipLaunchKernelGGL(vs_build_cand, dim3(grid_for(total)), dim3(256), 0, m->stream2, (const int32_t*)ds.y + row0, (const int32_t*)m->neg,
-                       c.batch_size, c.num_negatives, m->cand_early);
+    launch(vs_build_cand, dim3(grid_for(total)), dim3(256), 0, m->stream2, (const int32_t*)ds.y + row0, (const int32_t*)m->neg,
+           c.batch_size, c.num_negatives, m->cand_early);
     return entity_key_sort(m, total, m->stream2, m->cand_early);
 }
 
@@ -312,15 +311,15 @@ static int vs_entity_grad(sert_model* m, const VsStepPlan& P) {
         const int grid = 8 * cdiv(m->eg_groups, 8) * m->eg_ranges;
         if (!P.bucket_early) {     // (else: the partition ran beside the forward, vs_early_bucket)
             ScopedTimer t(m, TG_SORT, st);
-            hipLaunchKernelGGL(egrad_bucket, dim3(m->eg_num_sub), dim3(512), 0, st, m->cand, B, c1, m->eg_sub_rows,
-                               m->eg_er_shift, m->eg_ranges, m->eg_entries, m->eg_offs, (const int32_t*)nullptr,
-                               (const int32_t*)nullptr);
+            launch(egrad_bucket, dim3(m->eg_num_sub), dim3(512), 0, st, m->cand, B, c1, m->eg_sub_rows,
+                   m->eg_er_shift, m->eg_ranges, m->eg_entries, m->eg_offs, (const int32_t*)nullptr,
+                   (const int32_t*)nullptr);
         }
         {
             ScopedTimer t(m, TG_EGRAD, st);
 #define SERT_EL_ARGS m->eg_entries, m->eg_offs, m->coef, m->T, c1, de, V, m->eg_sub_rows, m->eg_num_sub, \
                  m->eg_subs_per_group, m->eg_groups, m->eg_ranges, m->epart
-            hipLaunchKernelGGL((egrad_acc<2>), dim3(grid), dim3(256), lds, st, SERT_EL_ARGS);
+            launch((egrad_acc<2>), dim3(grid), dim3(256), lds, st, SERT_EL_ARGS);
             m->eg_plan[0] = SERT_EGRAD_PATH_BUCKET;
             m->eg_plan[1] = m->eg_sub_rows; m->eg_plan[2] = m->eg_num_sub; m->eg_plan[3] = m->eg_subs_per_group;
             m->eg_plan[4] = m->eg_groups; m->eg_plan[5] = m->eg_ranges;
@@ -332,16 +331,16 @@ static int vs_entity_grad(sert_model* m, const VsStepPlan& P) {
         if (!P.re_in_parts) {
             ScopedTimer t(m, TG_EFIX, st);
             const size_t table4 = (size_t)V * de4;
-            hipLaunchKernelGGL(egrad_group_sum, dim3(grid_for((int64_t)table4)), dim3(256), 0, st, m->epart, m->eg_groups,
-                               table4, m->g_re);
+            launch(egrad_group_sum, dim3(grid_for((int64_t)table4)), dim3(256), 0, st, m->epart, m->eg_groups,
+                   table4, m->g_re);
             m->eg_plan[6] = 1;
         }
 #ifdef SERT_VARIANTS
     } else if (egrad_ranges_ok(m, total)) {
         // few pairs over a mid-size table: one workgroup per range of 32 entities, no sort (variants/kernels_egrad_ranges.h)
         ScopedTimer t(m, TG_EGRAD, st);
-        hipLaunchKernelGGL(egrad_ranges, dim3(cdiv(V, kERange)), dim3(256), 0, st, (const int32_t*)m->cand, (const float*)m->coef,
-                           (const float*)m->T, total, c.num_negatives + 1, de, V, m->g_re);
+        launch(egrad_ranges, dim3(cdiv(V, kERange)), dim3(256), 0, st, (const int32_t*)m->cand, (const float*)m->coef,
+               (const float*)m->T, total, c.num_negatives + 1, de, V, m->g_re);
 #endif
     } else {
     // dR_e: stable sort of the (entity, pair) keys, chunked reduce, carry fix-up
@@ -358,12 +357,12 @@ static int vs_entity_grad(sert_model* m, const VsStepPlan& P) {
         ScopedTimer t(m, TG_EGRAD, st);
         if (de % 4 == 0) {
             const int nch = cdiv(de / 4, 16);
-            if (nch <= 1)      { hipLaunchKernelGGL((egrad_chunk_reduce<4, 1>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 1; }
-            else if (nch <= 2) { hipLaunchKernelGGL((egrad_chunk_reduce<4, 2>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 2; }
-            else if (nch <= 5) { hipLaunchKernelGGL((egrad_chunk_reduce<4, 5>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 5; }
-            else               { hipLaunchKernelGGL((egrad_chunk_reduce<4, 8>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 8; }
+            if (nch <= 1)      { launch((egrad_chunk_reduce<4, 1>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 1; }
+            else if (nch <= 2) { launch((egrad_chunk_reduce<4, 2>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 2; }
+            else if (nch <= 5) { launch((egrad_chunk_reduce<4, 5>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 5; }
+            else               { launch((egrad_chunk_reduce<4, 8>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 8; }
         } else {
-            hipLaunchKernelGGL((egrad_chunk_reduce<1, 4>), cgrid, blk, 0, st, SERT_EG_ARGS);
+            launch((egrad_chunk_reduce<1, 4>), cgrid, blk, 0, st, SERT_EG_ARGS);
             m->eg_plan[9] = 1; m->eg_plan[10] = 4;
         }
     }
@@ -372,21 +371,21 @@ static int vs_entity_grad(sert_model* m, const VsStepPlan& P) {
         const bool few = V < 256 && de <= 512;   // few entities: one workgroup per entity (long runs)
         if (de % 4 == 0) {
             if (few) {
-                hipLaunchKernelGGL((egrad_fixup_wg<4>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
-                                   m->ehead, m->etail, m->g_re);
+                launch((egrad_fixup_wg<4>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
+                       m->ehead, m->etail, m->g_re);
                 m->eg_plan[11] = SERT_EGRAD_FIXUP_WORKGROUP;
             } else {
-                hipLaunchKernelGGL((egrad_fixup<4>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
-                                   m->ehead, m->etail, m->g_re);
+                launch((egrad_fixup<4>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
+                       m->ehead, m->etail, m->g_re);
                 m->eg_plan[11] = SERT_EGRAD_FIXUP_WAVE;
             }
         } else if (few) {
-            hipLaunchKernelGGL((egrad_fixup_wg<1>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
-                               m->ehead, m->etail, m->g_re);
+            launch((egrad_fixup_wg<1>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
+                   m->ehead, m->etail, m->g_re);
             m->eg_plan[11] = SERT_EGRAD_FIXUP_WORKGROUP;
         } else {
-            hipLaunchKernelGGL((egrad_fixup<1>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
-                               m->ehead, m->etail, m->g_re);
+            launch((egrad_fixup<1>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
+                   m->ehead, m->etail, m->g_re);
             m->eg_plan[11] = SERT_EGRAD_FIXUP_WAVE;
         }
     }
@@ -402,17 +401,17 @@ static int vs_dh_gemm(sert_model* m, const VsStepPlan& P) {
         // dh = da.W^T
         ScopedTimer t(m, TG_GEMM_DX);
         // (the event of its end: the completion signal of this GEMM, not a barrier packet behind it)
-        if (P.dh_carried) set_stop_event(vs_event(m, P.dh_event));
+        CarriedEvent carry(P.dh_carried ? vs_event(m, P.dh_event) : nullptr);
 #ifdef SERT_VARIANTS
         if (P.bwd_fused) {
             // dh, the per-workgroup partial slabs of dW and their column sums (db): one launch
             static const bool attr_set = hipFuncSetAttribute((const void*)vs_bwd_fused, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                              (int)vs_bwd_fused_lds_bytes()) == hipSuccess;
-            if (!attr_set) { set_stop_event(nullptr); SERT_FAIL("cannot reserve the LDS of vs_bwd_fused"); }
+            if (!attr_set) SERT_FAIL("cannot reserve the LDS of vs_bwd_fused");
             BwdFusedArgs fa;
             fa.DA = m->DA; fa.H = m->H; fa.W = m->W; fa.DH = m->DH; fa.part = m->part; fa.B = B;
             fa.stride = (size_t)FB_D * FB_D + FB_D;
-            SERT_LAUNCH(vs_bwd_fused, dim3(vs_bwd_fused_grid(B)), dim3(FB_THREADS), vs_bwd_fused_lds_bytes(), m->stream, fa);
+            launch(vs_bwd_fused, dim3(vs_bwd_fused_grid(B)), dim3(FB_THREADS), vs_bwd_fused_lds_bytes(), m->stream, fa);
         } else
         if (gemm_strip_ok(B, dw, de, de, de, true, m->DA, m->W))
             launch_gemm_strip<true, EPI_STORE>(m->stream, m->DA, m->W, m->DH, nullptr, B, dw, de, de, de, dw);
@@ -420,7 +419,6 @@ static int vs_dh_gemm(sert_model* m, const VsStepPlan& P) {
 #endif
             launch_gemm<false, true, EPI_STORE>(m->stream, m->DA, m->W, m->DH, nullptr, B, dw, de, de,
                                                 de, dw);
-        set_stop_event(nullptr);
     }
     // From here on the main stream has produced dW, db and the loss partials AND is done
     // READING W (the dh GEMM): the side stream may update the small tensors.
@@ -434,8 +432,8 @@ static int vs_dh_gemm(sert_model* m, const VsStepPlan& P) {
         // were swapped into `neg` at its start.  Ordered before the next step's loss kernel by this stream's
         // order and the end-of-step join (ev_small).
         const int64_t count = (int64_t)c.batch_size * c.num_negatives;
-        hipLaunchKernelGGL(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, m->stream2, m->neg_alt, count,
-                           (int64_t)m->rank * count, (uint32_t)c.num_entities, c.seed, (uint64_t)(m->step + 1) * 2);
+        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, m->stream2, m->neg_alt, count,
+               (int64_t)m->rank * count, (uint32_t)c.num_entities, c.seed, (uint64_t)(m->step + 1) * 2, nullptr, 0, nullptr, 0);
         m->neg_alt_step = m->step + 1;
     }
     if (P.fork_at == SERT_VS_FORK_DH) SERT_HIP(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
@@ -488,8 +486,8 @@ static int vs_dense_grad(sert_model* m, const VsStepPlan& P) {
         const int strips = cdiv(B, SG_ROWS);
         const int spw = std::max(1, cdiv(strips, std::min(want_wgs, 1024)));
         splits = cdiv(strips, spw);
-        hipLaunchKernelGGL(gemm_strip_tn, dim3(splits), dim3(256), 0, sd, (const float*)m->H, (const float*)m->DA, B,
-                           dw, de, dw, de, spw, m->part, stride);
+        launch(gemm_strip_tn, dim3(splits), dim3(256), 0, sd, (const float*)m->H, (const float*)m->DA, B,
+               dw, de, dw, de, spw, m->part, stride);
     } else
 #endif
     {

@@ -263,8 +263,8 @@ __device__ __forceinline__ float4 clip4(float4 t) {
 // loss kernel writes (kernels_vs.h) -- so that the partition can run BEFORE the loss kernel, beside the forward (round 6).
 __global__ __launch_bounds__(512) void egrad_bucket(const int32_t* __restrict__ cand, int B, int c1, int sub_rows,
                                                     int er_shift, int num_ranges, int32_t* __restrict__ entries,
-                                                    int32_t* __restrict__ offs, const int32_t* __restrict__ y = nullptr,
-                                                    const int32_t* __restrict__ neg = nullptr) {
+                                                    int32_t* __restrict__ offs, const int32_t* __restrict__ y,
+                                                    const int32_t* __restrict__ neg) {
     constexpr int NW = 8;                        // waves per workgroup
     __shared__ int32_t wh[NW][kElMaxRanges];    // per-wave range counts -> start positions
     __shared__ int32_t base[kElMaxRanges + 1];

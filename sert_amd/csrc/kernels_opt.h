@@ -83,9 +83,9 @@ __global__ __launch_bounds__(256) void adam_l2(float* __restrict__ p, float* __r
                                                float* __restrict__ m, float* __restrict__ v,
                                                size_t count, AdamArgs a,
                                                float* __restrict__ sumsq_partial,
-                                               const uint32_t* __restrict__ bits = nullptr,
-                                               unsigned row_len = 1, int rows_mode = kRowsAll,
-                                               float* __restrict__ sumsq_new_partial = nullptr) {
+                                               const uint32_t* __restrict__ bits,
+                                               unsigned row_len, int rows_mode,
+                                               float* __restrict__ sumsq_new_partial) {
     // sumsq_new_partial: also leave the sums of squares of the UPDATED values, partitioned exactly as
     // sumsq_partial is -- what the next step's launch over the same tensor would compute as its pre-update
     // sums, bit for bit (the deferred entity-table update of the side-heavy schedule, sert_hip.hip)
@@ -211,8 +211,8 @@ __global__ __launch_bounds__(256) void adadelta_l2(float* __restrict__ p, float*
                                                    float* __restrict__ delta, size_t count,
                                                    AdadeltaArgs a,
                                                    float* __restrict__ sumsq_partial,
-                                                   const uint32_t* __restrict__ bits = nullptr,
-                                                   unsigned row_len = 1, int rows_mode = kRowsAll) {
+                                                   const uint32_t* __restrict__ bits,
+                                                   unsigned row_len, int rows_mode) {
     __shared__ float red[4];
     float ss = 0.f;
     const float omr = 1.0f - a.rho;
@@ -611,7 +611,7 @@ struct SmallTensors {
 template <bool ADAM, bool STORE_G>
 __global__ __launch_bounds__(256) void optimizer_small(SmallTensors t, AdamArgs aa, AdadeltaArgs da,
                                                        float* __restrict__ sumsq_partial,
-                                                       float* __restrict__ sumsq_new_partial = nullptr) {
+                                                       float* __restrict__ sumsq_new_partial) {
     __shared__ float red[4];
     int i = 0;
     if ((int)blockIdx.x >= t.first_block[1]) i = 1;
@@ -717,9 +717,9 @@ __global__ __launch_bounds__(256) void finalize_loss(const float* __restrict__ l
                                                      const float* __restrict__ sq_partials,
                                                      int n_sq, float inv_batch, float reg_scale,
                                                      float* __restrict__ out,
-                                                     unsigned* __restrict__ host_flag = nullptr,
-                                                     unsigned seq = 0,
-                                                     const float* __restrict__ extra_sq = nullptr) {
+                                                     unsigned* __restrict__ host_flag,
+                                                     unsigned seq,
+                                                     const float* __restrict__ extra_sq) {
     // eight partials per thread and trip in flight (the loop used to be one dependent load per
     // partial: 16 + 9 round trips in series at C2), both sums reduced together: lanes by shuffle,
     // the four waves through LDS -- one barrier instead of eighteen.  Fixed order throughout.

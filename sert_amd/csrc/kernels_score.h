@@ -77,7 +77,7 @@ template <bool RAW>
 __global__ __launch_bounds__(256) void topk_rows(const float* __restrict__ S, int V, int k,
                                                  int32_t* __restrict__ idx_out,
                                                  float* __restrict__ val_out,
-                                                 float* __restrict__ thr_out = nullptr) {
+                                                 float* __restrict__ thr_out) {
     __shared__ uint32_t hist[2048];
     __shared__ unsigned long long keys[kTopKMax];
     __shared__ unsigned long long cand[kTopKCand];
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256) void topk_from_groups(const unsigned long long
                                                         int gcap, int k, int32_t* __restrict__ idx_out,
                                                         float* __restrict__ val_out, int q_base,
                                                         int* __restrict__ nflag, int* __restrict__ flag_list,
-                                                        int ccap, int* __restrict__ row_flag = nullptr) {
+                                                        int ccap, int* __restrict__ row_flag) {
     // ccap (a power of two <= kCandCap) keys of dynamic LDS: sized by the host for the expected
     // candidate count, so that 8 workgroups fit a CU instead of the 4 a 32 KB array allows
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];

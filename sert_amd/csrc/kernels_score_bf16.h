@@ -20,6 +20,7 @@
 // So the result is exactly the fp32 ranking; bf16 only decides where fp32 is spent.
 #pragma once
 #include "common.h"
+#include "launch.h"
 #include "kernels_score.h"
 
 namespace sert {
@@ -122,7 +123,7 @@ __device__ __forceinline__ void rescore_sort_emit(unsigned long long* keys, int 
 // get the same exact_dot scores and ordering as the fused path's.
 __global__ __launch_bounds__(256) void rescore_topk_rows(const float* __restrict__ P, const float* __restrict__ E,
                                                          int d, int k, int32_t* __restrict__ idx,
-                                                         float* __restrict__ val, const int* __restrict__ row_flag = nullptr) {
+                                                         float* __restrict__ val, const int* __restrict__ row_flag) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     const int q = blockIdx.x;
     if (row_flag && row_flag[q]) return;    // a row topk_from_groups flagged: the materialising path fills it (workgroup-uniform)
@@ -504,7 +505,7 @@ inline void launch_score_filter_bf16(hipStream_t s, const uint16_t* P16, const u
     if (kp == 128 && ring) {
         const int parts = std::max(1, std::min(g.tiles_n, cdiv(2 * 256, g.tiles_m)));
         const int per = cdiv(g.tiles_n, parts);
-        hipLaunchKernelGGL(score_filter_bf16_ring, dim3(g.tiles_m * cdiv(g.tiles_n, per)), dim3(512), 0, s, g, per);
+        launch(score_filter_bf16_ring, dim3(g.tiles_m * cdiv(g.tiles_n, per)), dim3(512), 0, s, g, per);
         return;
     }
 #endif
@@ -512,8 +513,8 @@ inline void launch_score_filter_bf16(hipStream_t s, const uint16_t* P16, const u
     //  queries against 1.235 / 1.210, identical results -- so the kernel is not bound by its epilogue's instruction count
     //  after all; variants build only, SERT_SCORE_EPI=atomic; profiles/r05_experiments.txt)
     static const bool atomic_epi = variant_knob("SERT_SCORE_EPI") && !strcmp(variant_knob("SERT_SCORE_EPI"), "atomic");
-    if (atomic_epi) hipLaunchKernelGGL((score_filter_bf16<false, true>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL((score_filter_bf16<false, false>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
+    if (atomic_epi) launch((score_filter_bf16<false, true>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
+    else launch((score_filter_bf16<false, false>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
 }
 
 // C (M, N) = P16 . E16[::stride]^T in fp32 (approximate scores of every stride-th entity)
@@ -523,7 +524,7 @@ inline void launch_score_sample_bf16(hipStream_t s, const uint16_t* P16, const u
     g.P16 = P16; g.E16 = E16; g.M = M; g.N = N; g.kp = kp; g.estride = (size_t)kp * stride;
     g.tiles_m = cdiv(M, SB_T); g.tiles_n = cdiv(N, SB_T);
     g.C = C; g.ldc = N;
-    hipLaunchKernelGGL((score_filter_bf16<true, false>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
+    launch((score_filter_bf16<true, false>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
 }
 
 }  // namespace sert

@@ -174,11 +174,11 @@ __global__ __launch_bounds__(256) void segsum_rows(const float* __restrict__ src
                                                    float* __restrict__ partial_dst, int d,
                                                    float divisor,
                                                    unsigned char* __restrict__ touched,
-                                                   int rdiv = 1,
-                                                   const float* __restrict__ logp = nullptr,
-                                                   const float* __restrict__ rsum = nullptr,
-                                                   const DenseSlots dense = DenseSlots(),
-                                                   const XcdLists xl = XcdLists()) {
+                                                   int rdiv,
+                                                   const float* __restrict__ logp,
+                                                   const float* __restrict__ rsum,
+                                                   const DenseSlots dense,
+                                                   const XcdLists xl) {
     segsum_rows_body<LPI, DST_SLOT, LL_FINAL, SKIP_DENSE>((int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y, src, rows, items, nitems,
                                                           final_dst, partial_dst, d, divisor, touched, rdiv, logp, rsum, dense, xl);
 }
@@ -200,12 +200,12 @@ __global__ __launch_bounds__(256) void segsum_rows_scalar(const float* __restric
                                                           float* __restrict__ partial_dst, int d,
                                                           float divisor,
                                                           unsigned char* __restrict__ touched,
-                                                          int rdiv = 1,
-                                                          const float* __restrict__ logp = nullptr,
-                                                          const float* __restrict__ rsrc = nullptr,
-                                                          const int32_t* __restrict__ rrows = nullptr,
-                                                          float* __restrict__ rsum = nullptr,
-                                                          float* __restrict__ rpart = nullptr) {
+                                                          int rdiv,
+                                                          const float* __restrict__ logp,
+                                                          const float* __restrict__ rsrc,
+                                                          const int32_t* __restrict__ rrows,
+                                                          float* __restrict__ rsum,
+                                                          float* __restrict__ rpart) {
     const int lane = threadIdx.x & 63;
     const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= nitems) return;

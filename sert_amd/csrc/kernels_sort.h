@@ -14,6 +14,7 @@
 //                   and deterministic.
 #pragma once
 #include "common.h"
+#include "launch.h"
 
 namespace sert {
 
@@ -28,7 +29,7 @@ constexpr int kSortMaxBins = 1 << kSortMaxBits;
 __global__ __launch_bounds__(256) void csort_hist(const int32_t* __restrict__ keys, int n,
                                                   int shift, int nbins, int tiles,
                                                   int32_t* __restrict__ hist,
-                                                  int32_t* __restrict__ zero = nullptr, int zero_n = 0) {
+                                                  int32_t* __restrict__ zero, int zero_n) {
     __shared__ int32_t h[kSortMaxBins];
     const int tile = blockIdx.x;
     // the caller's per-entity run bounds, cleared ahead of the reduce that follows the sort on this stream
@@ -162,9 +163,9 @@ __global__ __launch_bounds__(256) void csort_scatter(const int32_t* __restrict__
 static inline void csort_pass(hipStream_t s, const int32_t* kin, const int32_t* vin, int32_t* kout, int32_t* vout, int n, int shift,
                               int nbits, int32_t* hist, int32_t* bin_total, int32_t* zero = nullptr, int zero_n = 0) {
     const int tiles = cdiv(n, kSortTile);
-    hipLaunchKernelGGL(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nbits, tiles, hist, zero, zero_n);
-    hipLaunchKernelGGL(csort_scan_bins, dim3(cdiv(1 << nbits, 4)), dim3(256), 0, s, hist, 1 << nbits, tiles, bin_total);
-    hipLaunchKernelGGL(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nbits, tiles, hist, bin_total);
+    launch(csort_hist, dim3(tiles), dim3(256), 0, s, kin, n, shift, 1 << nbits, tiles, hist, zero, zero_n);
+    launch(csort_scan_bins, dim3(cdiv(1 << nbits, 4)), dim3(256), 0, s, hist, 1 << nbits, tiles, bin_total);
+    launch(csort_scatter, dim3(tiles), dim3(256), 0, s, kin, vin, kout, vout, n, shift, nbits, tiles, hist, bin_total);
 }
 
 }  // namespace sert

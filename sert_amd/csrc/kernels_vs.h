@@ -136,8 +136,8 @@ __global__ __launch_bounds__(256) void vs_build_cand(const int32_t* __restrict__
 // a sampler on a side stream plus a cross-queue wait (7-11 us of idle GPU).
 __global__ void vs_sample_negatives(int32_t* __restrict__ neg, int64_t count, int64_t global_offset,
                                     uint32_t num_entities, uint64_t seed, uint64_t step,
-                                    float4* __restrict__ zero_f = nullptr, size_t nzf4 = 0,
-                                    uint4* __restrict__ zero_b = nullptr, size_t nzb16 = 0) {
+                                    float4* __restrict__ zero_f, size_t nzf4,
+                                    uint4* __restrict__ zero_b, size_t nzb16) {
     {
         const size_t t0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
         const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
                                               const float* __restrict__ w, float* __restrict__ DA,
                                               float* __restrict__ coef, int32_t* __restrict__ cand,
                                               float* __restrict__ rowloss, int B, int z, int de,
-                                              float inv_batch, float* __restrict__ wg_loss = nullptr) {
+                                              float inv_batch, float* __restrict__ wg_loss) {
     // wg_loss (optional): wg_loss[blockIdx.x] = sum of this workgroup's sixteen (weighted) row
     // losses, added in row order -- the first level of the loss reduction rides along instead of
     // being a launch of its own on the step's critical path
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
                                                    const float* __restrict__ w, float* __restrict__ DA,
                                                    float* __restrict__ coef, int32_t* __restrict__ cand,
                                                    float* __restrict__ rowloss, int B, int z, int de,
-                                                   float inv_batch, float* __restrict__ wg_loss = nullptr) {
+                                                   float inv_batch, float* __restrict__ wg_loss) {
     __shared__ float wg_red[16];
     const int l = threadIdx.x & 15;
     const int lane = threadIdx.x & 63;

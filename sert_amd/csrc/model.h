@@ -71,7 +71,7 @@ struct Timing {
     int64_t samples[TG_COUNT] = {};
 };
 
-// sert_timing_enable(m, 2) (common.h: InStepHook): event pairs of the launches in flight, harvested when the ring is full
+// sert_timing_enable(m, 2) (launch.h: InStepHook; host/timing.inc): event pairs of the launches in flight, harvested when the ring is full
 // and when the averages are read
 struct InStep {
     static constexpr int kRing = 1024;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "launch.h"
 #include "gemm.h"
 #include "gemm_x3.h"
 #ifdef SERT_VARIANTS   // opt-in variants that lost their A/B (csrc/variants/; tools/build_variant.sh -DSERT_VARIANTS)
@@ -45,114 +46,6 @@
 
 namespace sert {
 thread_local std::string g_last_error;
-
-static const char* kTimingNames[TG_COUNT] = {
-    "gather",        "gemm_fwd", "loss",      "entity_sort",          "entity_grad_reduce",
-    "entity_grad_fixup", "gemm_dW", "splitk_combine", "gemm_dX",      "word_grad_segsum",
-    "allreduce",     "reduce_scatter", "all_gather", "optimizer_word_table",  "optimizer_other",      "finalize"};
-
-// ---- roctx ranges (sert_profile_range_push / pop) ------------------------------------
-// Loaded lazily from the ROCm tools library; SERT_ROCTX=1 additionally wraps every kernel group of a step
-// (the timing groups below) in a range, so that a rocprofv3 --marker-trace shows the step's structure on
-// the host timeline.  Without the library the calls are no-ops.
-struct Roctx {
-    bool tried = false;
-    int (*push)(const char*) = nullptr;
-    int (*pop)() = nullptr;
-};
-static Roctx g_roctx;
-static void roctx_load() {
-    if (g_roctx.tried) return;
-    g_roctx.tried = true;
-    for (const char* n : {"libroctx64.so.4", "libroctx64.so", "librocprofiler-sdk-roctx.so.1", "/opt/rocm/lib/libroctx64.so"}) {
-        void* lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) continue;
-        g_roctx.push = (decltype(g_roctx.push))dlsym(lib, "roctxRangePushA");
-        g_roctx.pop = (decltype(g_roctx.pop))dlsym(lib, "roctxRangePop");
-        if (g_roctx.push && g_roctx.pop) return;
-        g_roctx.push = nullptr; g_roctx.pop = nullptr;
-    }
-}
-static bool roctx_groups() {
-    static const bool on = [] {
-        const bool want = knob("SERT_ROCTX") && atoi(knob("SERT_ROCTX")) != 0;
-        if (want) roctx_load();
-        return want && g_roctx.push != nullptr;
-    }();
-    return on;
-}
-
-// ---- timing ----------------------------------------------------------------
-// in-step mode (sert_timing_enable(m, 2); common.h: InStepHook): a (start, stop) pair for the next launch of the group the
-// launching thread is inside
-static void instep_harvest(sert_model* m, bool all) {
-    InStep& t = m->instep;
-    while (t.head < t.tail && (all || t.tail - t.head >= InStep::kRing)) {
-        const int i = (int)(t.head % InStep::kRing);
-        float ms = 0.f;
-        if (hipEventSynchronize(t.ev[i][1]) == hipSuccess && hipEventElapsedTime(&ms, t.ev[i][0], t.ev[i][1]) == hipSuccess) {
-            t.total_us[t.group[i]] += 1000.0 * ms;
-            t.launches[t.group[i]] += 1;
-        }
-        ++t.head;
-    }
-}
-static void instep_next(void* ctx, hipEvent_t* a, hipEvent_t* b) {
-    sert_model* m = (sert_model*)ctx;
-    InStep& t = m->instep;
-    if (!t.on || t.cur_group < 0) return;
-    instep_harvest(m, false);
-    const int i = (int)(t.tail % InStep::kRing);
-    t.group[i] = t.cur_group;
-    *a = t.ev[i][0];
-    *b = t.ev[i][1];
-    ++t.tail;
-}
-
-struct ScopedTimer {
-    sert_model* m;
-    int g;
-    hipStream_t s;
-    int instep_prev = -1;
-    InStepHook hook_prev = {nullptr, nullptr};
-    ScopedTimer(sert_model* m_, int g_, hipStream_t s_ = nullptr) : m(m_), g(g_), s(s_ ? s_ : m_->stream) {
-        if (m->instep.on) {
-            instep_prev = m->instep.cur_group;
-            hook_prev = instep_hook();
-            m->instep.cur_group = g;
-            instep_hook() = InStepHook{instep_next, m};
-        }
-        if (roctx_groups()) (void)g_roctx.push(kTimingNames[g]);
-        // a group bracketed several times in one step spans first start .. last end
-        if (m->timing.enabled && !m->timing.used[g]) {
-            (void)hipEventRecord(m->timing.ev[g][0], s);
-        }
-    }
-    ~ScopedTimer() {
-        if (m->timing.enabled) {
-            (void)hipEventRecord(m->timing.ev[g][1], s);
-            m->timing.used[g] = true;
-        }
-        if (roctx_groups()) (void)g_roctx.pop();
-        if (m->instep.on) {
-            m->instep.cur_group = instep_prev;
-            instep_hook() = hook_prev;
-        }
-    }
-};
-
-static void timing_collect(sert_model* m) {
-    if (!m->timing.enabled) return;
-    for (int g = 0; g < TG_COUNT; ++g) {
-        if (!m->timing.used[g]) continue;
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, m->timing.ev[g][0], m->timing.ev[g][1]) == hipSuccess) {
-            m->timing.total_us[g] += 1000.0 * ms;
-            m->timing.samples[g] += 1;
-        }
-        m->timing.used[g] = false;
-    }
-}
 
 // ---- RCCL, loaded lazily (single-GPU runs never touch it) --------------------
 struct UniqueId {
@@ -262,6 +155,8 @@ static void invalidate_speculation(sert_model* m) {
     m->neg_alt_step = -1;      // (step counter, seed-relevant state or data may change)
     m->rw_pred_ok = false;     // (the rows' predicted shares of sum(p^2) are trajectories of THESE parameters and THIS step counter)
 }
+
+#include "host/timing.inc"
 
 #include "host/lazy_segsum.inc"
 

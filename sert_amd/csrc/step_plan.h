@@ -58,7 +58,7 @@ static_assert(sizeof(VsStepFacts) == SERT_VS_FACT_COUNT * sizeof(int32_t), "VsSt
 struct VsStepPlan {
     // ---- the fork
     int32_t fork_at = SERT_VS_FORK_NONE;   // the kernel behind which the side queue starts its chain
-    int32_t fork_carried = 0;     // that kernel's own completion signal is ev_fork (set_stop_event) ...
+    int32_t fork_carried = 0;     // that kernel's own completion signal is ev_fork (CarriedEvent) ...
     int32_t fork_recorded = 0;    // ... or, behind the loss kernel, hipEventRecord(ev_fork) on the main queue: where the side queue meets
                                   // the fork in front of the pieces (side_meets_fork), else at the head of the entity chain
     int32_t dh_event = SERT_VS_EVENT_NONE;   // what the end of the dh GEMM marks: ev_fork, ev_dense or nothing
@@ -201,7 +201,7 @@ inline VsStepPlan vs_plan_step(const VsStepFacts& f) {
 
     // ---- the fork and the event of the dh GEMM
     // (the loss kernel carries ev_fork wherever the fork is not the late one, data parallel and three queues included;
-    //  entity_dim % 4: the kernels launched through SERT_LAUNCH)
+    //  entity_dim % 4: the kernels that have always carried it)
     const bool nce_carries = ext && (!fork_late || fork_nce) && two && f.entity_dim % 4 == 0;
     // (the end of the dh GEMM: from there on the main stream has produced dW, db and the loss partials AND is done
     //  READING W -- the side stream may update the small tensors)

@@ -14,6 +14,7 @@
 //   MFMA step j of the slab contracts the k's {4g + j}: any partition of k is a valid order
 #pragma once
 #include "../common.h"
+#include "../launch.h"
 
 namespace sert {
 
@@ -244,8 +245,8 @@ inline void launch_gemm_big_nt(hipStream_t s, const float* A, const float* B, fl
     BigGemmArgs g = {};
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.tiles_m = cdiv(M, BM); g.tiles_n = cdiv(N, mid ? 128 : 256);
-    if (mid) hipLaunchKernelGGL(gemm_mid_nt<false>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(gemm_big_nt<false>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
+    if (mid) launch(gemm_mid_nt<false>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
+    else launch(gemm_big_nt<false>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
 }
 
 // rows of A that reach thr[row] -> (row, 64-column group) candidate lists; ngr groups per row
@@ -256,8 +257,8 @@ inline void launch_gemm_big_filter(hipStream_t s, const float* A, const float* B
     g.A = A; g.B = B; g.C = nullptr; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = 0;
     g.tiles_m = cdiv(M, BM); g.tiles_n = cdiv(N, mid ? 128 : 256);
     g.thr = thr; g.cand = cand; g.cnt = cnt; g.ngr = ngr; g.cap = cap;
-    if (mid) hipLaunchKernelGGL(gemm_mid_nt<true>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(gemm_big_nt<true>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
+    if (mid) launch(gemm_mid_nt<true>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
+    else launch(gemm_big_nt<true>, dim3(g.tiles_m * g.tiles_n), dim3(256), 0, s, g);
 }
 
 }  // namespace sert

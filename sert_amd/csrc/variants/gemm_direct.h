@@ -28,6 +28,7 @@
 // operands with K >= k to it.
 #pragma once
 #include "../common.h"
+#include "../launch.h"
 #include "../gemm.h"
 
 namespace sert {
@@ -241,12 +242,12 @@ inline bool launch_gemm_direct(hipStream_t s, const float* A, const float* B, fl
         auto kern = gemm_f32_direct<BRC, E, 2>;
         static const bool ok = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
         if (!ok) return false;
-        SERT_LAUNCH(kern, dim3(cdiv(M, 256) * g.tiles_n), dim3(64 * DG_WAVES), lds, s, g);
+        launch(kern, dim3(cdiv(M, 256) * g.tiles_n), dim3(64 * DG_WAVES), lds, s, g);
     } else {
         auto kern = gemm_f32_direct<BRC, E, 1>;
         static const bool ok = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
         if (!ok) return false;
-        SERT_LAUNCH(kern, dim3(cdiv(M, 128) * g.tiles_n), dim3(64 * DG_WAVES), lds, s, g);
+        launch(kern, dim3(cdiv(M, 128) * g.tiles_n), dim3(64 * DG_WAVES), lds, s, g);
     }
     return true;
 }

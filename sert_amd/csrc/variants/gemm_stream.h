@@ -35,6 +35,7 @@
 // Compiled with -DSERT_VARIANTS only; SERT_GEMM_STREAM=1 routes the shape to it.
 #pragma once
 #include "../common.h"
+#include "../launch.h"
 #include "../gemm.h"
 
 namespace sert {
@@ -214,7 +215,7 @@ inline bool launch_gemm_stream(hipStream_t s, const float* A, const float* B, fl
     static const bool attr_ok = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
     if (!attr_ok) return false;
     const int grid = std::min(256 * (8 / kStreamWaves), cdiv(g.nstrips, kStreamWaves));
-    SERT_LAUNCH(kern, dim3(grid), dim3(64 * kStreamWaves), lds, s, g);
+    launch(kern, dim3(grid), dim3(64 * kStreamWaves), lds, s, g);
     return true;
 }
 

@@ -558,7 +558,7 @@ inline void launch_gemm_strip(hipStream_t s, const float* A, const float* B, flo
         // role-specialised variant: one persistent workgroup per CU
         const int grid2 = std::min(strips, 256 * std::max(1, per_cu));
         switch (K / 8) {
-#define SG_CASE(K8) case K8: SERT_LAUNCH((gemm_roles_nn<TB, EPI, K8>), dim3(grid2), dim3(512), 0, s, g); break;
+#define SG_CASE(K8) case K8: launch((gemm_roles_nn<TB, EPI, K8>), dim3(grid2), dim3(512), 0, s, g); break;
             SG_CASE(4) SG_CASE(8) SG_CASE(12) SG_CASE(16)
 #undef SG_CASE
             default: break;
@@ -566,7 +566,7 @@ inline void launch_gemm_strip(hipStream_t s, const float* A, const float* B, flo
         return;
     }
     switch (K / 8) {
-#define SG_CASE(K8) case K8: SERT_LAUNCH((gemm_strip_nn<TB, EPI, K8>), dim3(grid), dim3(512), 0, s, g); break;
+#define SG_CASE(K8) case K8: launch((gemm_strip_nn<TB, EPI, K8>), dim3(grid), dim3(512), 0, s, g); break;
         SG_CASE(4) SG_CASE(8) SG_CASE(12) SG_CASE(16)
 #undef SG_CASE
         default: break;   // (gemm_strip_ok admits K in {32, 64, 96, 128} only)

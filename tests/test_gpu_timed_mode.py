@@ -218,3 +218,54 @@ def test_in_step_timing_changes_nothing_and_times_the_update(hip_lib, kind):
         del model
     assert outs[0][0] == outs[1][0]
     assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][2], outs[1][2])
+
+
+# One batch trained six times, no announcement: nothing runs ahead, every step issues the same launches.  `env`: set before
+# the engine is created.
+COUNT_CASES = {
+    # d_w = 30 is no multiple of 4: every level of the word gradient's tree is segsum_rows_scalar
+    'tree_scalar': dict(B=256, n=4, Vw=2000, Ve=40, dw=30, de=32, z=4, env={}),
+    # the sorted entity chain: key sort, egrad_chunk_reduce, egrad_fixup
+    'sorted_chain': dict(B=256, n=4, Vw=2000, Ve=3000, dw=32, de=32, z=4, env={'SERT_EGRAD_SORT': '1'}),
+}
+
+
+@pytest.mark.parametrize('case', sorted(COUNT_CASES))
+def test_in_step_timing_counts_every_launch(hip_lib, monkeypatch, case):
+    """sert_timing_enable(m, 2) times EVERY plain launch of a group, however its call site is spelled: the counts per step are
+    those of the engine's own recorders (wgrad_plan, egrad_plan) and of the groups' structure (model.h: TimingGroup), and the
+    steps' results are those of untimed steps bit for bit."""
+    c = COUNT_CASES[case]
+    B, n, Vw, Ve, dw, de, z, steps = c['B'], c['n'], c['Vw'], c['Ve'], c['dw'], c['de'], c['z'], 6
+    for k, v in c['env'].items():
+        monkeypatch.setenv(k, v)
+    p = U.make_vs_problem(31, B, n, z, Vw, Ve, dw, de)
+    outs = []
+    for mode in (0, 2):
+        eng = U.vs_engine(p, B, n, z, 0.01, keep_grads=0, seed=4321)
+        eng.upload_dataset(C.SPLIT_TRAIN, p['X'], y_int=p['y'], w=p['w'])
+        eng.timing_reset()
+        eng.timing_enable(mode)
+        losses = [eng.train_batch(0, None) for _ in range(steps)]
+        eng.synchronize()
+        if mode == 2:
+            us, launches = eng.timings(), eng.timing_launches()      # (timings() harvests what is still in flight)
+            print(case, 'launches per step', {k: v for k, v in sorted(launches.items()) if v}, 'us', {k: round(v, 2) for k, v in sorted(us.items()) if v})
+            if case == 'tree_scalar':
+                plan = eng.wgrad_plan()
+                assert plan['path'] == 'word_grad' and plan['dense_cnt'] == 0 and plan['heavy'] == 'none' and not plan['combine_alone'], plan
+                assert plan['launches'] and all(form == 'scalar' for form, _ in plan['launches']), plan
+                # (word_grad_segsum without dense words: the tree's launches and nothing else inside the group)
+                assert launches['word_grad_segsum'] == len(plan['launches']), (launches, plan)
+                assert us['word_grad_segsum'] > 0, us
+            else:
+                assert eng.egrad_plan()['path'] == 'sorted', eng.egrad_plan()
+                # (model.h: one egrad_chunk_reduce and one egrad_fixup per step)
+                assert launches['entity_grad_reduce'] == 1 and launches['entity_grad_fixup'] == 1, launches
+                assert us['entity_grad_reduce'] > 0 and us['entity_grad_fixup'] > 0, us
+        eng.timing_enable(0)
+        outs.append((losses, eng.get_tensor(C.T_RW).copy(), eng.get_tensor(C.T_RE).copy(), eng.get_tensor(C.T_W).copy()))
+        eng.close()
+    assert outs[0][0] == outs[1][0]
+    for a, b in zip(outs[0][1:], outs[1][1:]):
+        assert np.array_equal(a, b)
