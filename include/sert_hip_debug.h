@@ -63,6 +63,22 @@ enum {
 };
 int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n);
 
+/* The NCE score / loss / gradient kernel the LAST vectorspace forward of this model launched (vs_loss in
+ * csrc/host/step_vectorspace.inc, kernels in csrc/kernels_vs.h; sert_train_batch, sert_eval_batch, ...) -- host record written
+ * where the launch is made, test hook, no device is touched: out[0] one of SERT_NCE_FORM_*, out[1] the float4 chunks per lane NCH
+ * (REGS, PER_CANDIDATE) or the columns per lane NPL (SCALAR), out[2] MAXC of vs_nce_regs<NCH, ., MAXC> (0 for the other forms),
+ * out[3] 1 for the training instance and 0 for the evaluating one, out[4] workgroups of the launch, out[5] the per-workgroup loss
+ * partials the kernel left for the loss reduction (0: the reduction starts from the row losses).  n <= 6; all zero before the
+ * first forward and for a model that has no NCE loss.  tests/test_gpu_nce_forms.py asserts through this that every case of
+ * tests/nce_cases.py reaches the template instance it is there for. */
+enum {
+    SERT_NCE_FORM_NONE = 0,
+    SERT_NCE_FORM_REGS = 1,           /* vs_nce_regs<NCH, TRAIN, MAXC>: every candidate row of a batch row in registers */
+    SERT_NCE_FORM_PER_CANDIDATE = 2,  /* vs_nce<NCH, TRAIN>: one candidate after the other */
+    SERT_NCE_FORM_SCALAR = 3          /* vs_nce_scalar<NPL, TRAIN>: d_e % 4 != 0, one wave per row */
+};
+int sert_debug_nce_form(sert_model* m, int32_t* out, int n);
+
 /* What the LAST backward of this model launched for the per-word sums -- the word-table gradient of the vectorspace models
  * (word_grad_segsum) or dZu of the loglinear model (dzu_from_dj), both in csrc/host/lazy_segsum.inc over the tree of
  * csrc/word_index.h -- host record written where the launches are made, test hook, no device is touched:

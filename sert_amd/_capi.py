@@ -30,6 +30,7 @@ LL_FORMS = ('none', 'wave', 'table', 'fused_row', 'stream', 'rowwise')
 # SERT_EGRAD_PATH_* / SERT_EGRAD_FIXUP_*, by value
 EGRAD_PATHS = ('none', 'bucket', 'sorted')
 EGRAD_FIXUPS = ('none', 'wave', 'workgroup')
+NCE_FORMS = ('none', 'regs', 'per_candidate', 'scalar')                  # SERT_NCE_FORM_*
 WGRAD_PATHS = ('none', 'word_grad', 'dzu')                               # SERT_WGRAD_PATH_*
 WGRAD_HEAVY = ('none', 'fused', 'two_launches', 'wide')                  # SERT_WGRAD_HEAVY_*
 WGRAD_FORMS = ('none', 'rows32', 'rows64', 'scalar', 'rows_plus', 'rows_plus_ll', 'upper_fused', 'scalar_ll', 'bundled')   # SERT_WGRAD_FORM_*
@@ -66,7 +67,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
     'sert_debug_count_ranks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -467,6 +468,17 @@ class Engine(object):
             return {'path': path, 'sort_bits': v[7], 'passes': v[8], 'vec': v[9], 'nch': v[10], 'fixup': EGRAD_FIXUPS[v[11]]}
         assert not any(v), v
         return {'path': path}
+
+    def nce_form(self):
+        """sert_debug_nce_form (test hook): the NCE loss kernel the last vectorspace forward launched -- 'form' (none / regs /
+        per_candidate / scalar), 'param' (NCH or NPL), 'maxc' (regs only, else 0), 'train', 'workgroups' and 'loss_partials'.
+        All zero before the first forward and for a model without an NCE loss."""
+        v = (ctypes.c_int32 * 6)()
+        self._lib.sert_debug_nce_form.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_nce_form(self._h, v, 6))
+        v = [int(x) for x in v]
+        return {'form': NCE_FORMS[v[0]], 'param': v[1], 'maxc': v[2], 'train': bool(v[3]), 'workgroups': v[4],
+                'loss_partials': v[5]}
 
     def wgrad_plan(self):
         """sert_debug_wgrad_plan (test hook): what the last backward launched for the per-word sums (the word-table gradient of a

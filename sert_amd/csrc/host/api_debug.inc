@@ -43,6 +43,12 @@ int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n) {
     return 0;
 }
 
+int sert_debug_nce_form(sert_model* m, int32_t* out, int n) {
+    if (!m || !out || n < 1 || n > 6) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = m->nce_form[i];
+    return 0;
+}
+
 int sert_debug_wgrad_plan(sert_model* m, int32_t* out, int n) {
     if (!m || !out || n < 1 || n > 24) SERT_FAIL("bad argument");
     for (int i = 0; i < n; ++i) out[i] = m->wg_plan[i];

@@ -178,6 +178,7 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         const float* w = TRAIN ? ds.w + row0 : nullptr;
         const float inv_batch = 1.0f / (float)c.global_batch_size;
         dim3 block(256);
+        for (int32_t& v : m->nce_form) v = 0;   // (the instance launched below: sert_debug_nce_form, sert_hip_debug.h)
         if (de > 512) SERT_FAIL("entity_dim > 512 is not supported");
         // training with a side stream: the fork event of the backward pass is this kernel's own
         // completion signal (launch.h)
@@ -190,11 +191,13 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         launch((vs_nce<N, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y,                \
                m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,                            \
                c.num_negatives, de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);       \
+        m->nce_form[0] = SERT_NCE_FORM_PER_CANDIDATE; m->nce_form[1] = N;                    \
         break;
 #define SERT_NCE_REGS(N, C)                                                                  \
     launch((vs_nce_regs<N, TRAIN, C>), grid, block, 0, m->stream, m->T, m->re, y,            \
            m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B, c.num_negatives,               \
-           de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr)
+           de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);                            \
+    m->nce_form[0] = SERT_NCE_FORM_REGS; m->nce_form[1] = N; m->nce_form[2] = C
             static const bool no_regs = variant_knob("SERT_NCE_PER_CANDIDATE") != nullptr;
             const int nc = c.num_negatives + 1;
             // (d_e = 300, five float4 per lane and candidate: 256 VGPRs + AGPR spills, one wave per SIMD --
@@ -222,6 +225,7 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
 #undef SERT_NCE_CASE
             // (training: the kernel left one loss partial per workgroup in red_loss)
             m->nce_loss_partials = TRAIN ? cdiv(B, 16) : 0;
+            m->nce_form[4] = (int32_t)grid.x;
         } else {
             m->nce_loss_partials = 0;
             const int npl = cdiv(de, 64);
@@ -231,6 +235,7 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         launch((vs_nce_scalar<N, TRAIN>), grid, block, 0, m->stream, m->T,                  \
                m->re, y, m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,                 \
                c.num_negatives, de, inv_batch);                                              \
+        m->nce_form[0] = SERT_NCE_FORM_SCALAR; m->nce_form[1] = N;                           \
         break;
             switch (npl) {
                 SERT_NCE_CASE(1) SERT_NCE_CASE(2) SERT_NCE_CASE(3) SERT_NCE_CASE(4)
@@ -238,7 +243,10 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
                 default: SERT_FAIL("entity_dim > 512 is not supported");
             }
 #undef SERT_NCE_CASE
+            m->nce_form[4] = (int32_t)grid.x;
         }
+        m->nce_form[3] = TRAIN ? 1 : 0;
+        m->nce_form[5] = m->nce_loss_partials;
     }
     return 0;
 }

@@ -126,6 +126,8 @@ struct sert_model {
     int n_loss_partials = 0;
     bool loss_from_rows = false;     // this step: the loss finalisation reads the per-row losses directly (few rows)
     int nce_loss_partials = 0;       // > 0: vs_nce wrote this many per-workgroup loss partials into red_loss
+    // the NCE loss kernel vs_loss launched last, recorded where the launch is made: sert_debug_nce_form (sert_hip_debug.h)
+    int32_t nce_form[6] = {0, 0, 0, 0, 0, 0};
     // SERT_STREAMS: 1 = everything on the main stream (0.423 ms/step at C2), 2 = + the entity
     // chain, the step prologue and the small-tensor optimiser on a side stream (0.396),
     // 3 = + dW on a third (0.403: every cross-queue dependency costs 15-25 us of idle GPU)

@@ -75,6 +75,19 @@ def test_egrad_plan_hook_refuses_bad_arguments(hip_lib):
         assert re.search(r'\bSERT_EGRAD_FIXUP_%s = %d\b' % (name, k), src), name
 
 
+def test_nce_form_hook_refuses_bad_arguments(hip_lib):
+    """sert_debug_nce_form (include/sert_hip_debug.h) touches no device: without a model it fails with a message, and the
+    binding knows the values of its enum by name."""
+    v = (ctypes.c_int32 * 6)()
+    hip_lib.sert_debug_nce_form.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    assert hip_lib.sert_debug_nce_form(None, v, 6) != 0
+    assert b'bad argument' in hip_lib.sert_last_error()
+    src = open(os.path.join(ROOT, 'include', 'sert_hip_debug.h')).read()
+    assert _capi.NCE_FORMS == ('none', 'regs', 'per_candidate', 'scalar')
+    for k, name in enumerate(_capi.NCE_FORMS):
+        assert re.search(r'\bSERT_NCE_FORM_%s = %d\b' % (name.upper(), k), src), name
+
+
 def test_wgrad_plan_hook_refuses_bad_arguments(hip_lib):
     """sert_debug_wgrad_plan (include/sert_hip_debug.h) touches no device: without a model it fails with a message, and the
     binding knows the values of its three enums by name."""
