@@ -10,7 +10,9 @@ Writes ``<run_out>_debug``, ``<run_out>_ep`` (topics per entity) and
 ``<run_out>_ef`` (entities per topic) (query.py:94, :149-156).
 
 Additive flags: --no_batch (score one query at a time like the reference
-instead of all queries in one device call), --device.  Both model kinds take
+instead of all queries in one device call), --device, --candidates FILE [FILE ...]
+(TREC run files of a first stage: each topic's entities there, not every entity, are ranked -- re-ranking; a topic without
+candidates is skipped, as a topic of only OOV terms is).  Both model kinds take
 the batched path by default: vectorspace through VectorSpaceCallback.process_batch,
 loglinear through LogLinearPredictFn.rank_queries + LogLinearCallback.process_batch
 (the per-token distributions stay on the device; every entity is ranked and --top
@@ -23,6 +25,8 @@ import logging
 import os
 import pickle
 import sys
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -43,6 +47,7 @@ def build_parser():
     parser.add_argument('--run_out', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--no_batch', action='store_true', default=False)
     parser.add_argument('--device', type=int, default=0)
+    parser.add_argument('--candidates', type=au.existing_file_path, nargs='+', default=None)
     return parser
 
 
@@ -66,6 +71,28 @@ def load_meta(path):
     """Five pickles written by bin/prepare.py:373-376."""
     with open(path, 'rb') as f:
         return tuple(pickle.load(f) for _ in range(5))
+
+
+def load_candidates(paths, entity_indices_inv):
+    """The candidate lists of TREC run files (trec_utils.parse_run; several files are merged): dict topic id -> sorted
+    unique int32 array of internal entity indices.  Entity ids the model does not know are dropped and their number is
+    logged once; a topic with none left is absent."""
+    internal = dict((str(entity_id), index) for index, entity_id in
+                    (entity_indices_inv.items() if hasattr(entity_indices_inv, 'items') else enumerate(entity_indices_inv)))
+    lists = collections.defaultdict(list)
+    unknown = 0
+    for path in paths:
+        with io.open(path, 'r', encoding='utf8') as f:
+            for topic_id, entries in trec_utils.parse_run(f).items():
+                for _, entity_id in entries:
+                    index = internal.get(entity_id)
+                    if index is None:
+                        unknown += 1
+                    else:
+                        lists[topic_id].append(index)
+    if unknown:
+        logging.warning('Dropped %d candidates whose entity the model does not know.', unknown)
+    return dict((topic_id, np.unique(np.asarray(indices, dtype=np.int32))) for topic_id, indices in lists.items() if indices)
 
 
 def topic_tokens(text, words):
@@ -97,6 +124,8 @@ def main(argv=None):
         for handle in handles:
             handle.close()
 
+    candidates = None if args.candidates is None else load_candidates(args.candidates, entity_indices_inv)
+
     by_entity = collections.defaultdict(list)   # entity profiling: topics per entity
     by_topic = collections.defaultdict(list)    # entity finding: entities per topic
 
@@ -108,10 +137,10 @@ def main(argv=None):
 
     with open(args.run_out + '_debug', 'w') as debug_out:
         if model_args.type is models.LanguageModel:
-            callback = scoring.LogLinearCallback(args, model_args, tokens, debug_out, collect)
+            callback = scoring.LogLinearCallback(args, model_args, tokens, debug_out, collect, candidates=candidates)
         elif model_args.type in VECTORSPACE_TYPES:
             callback = scoring.VectorSpaceCallback(entity_representations, args, model_args, tokens,
-                                                   debug_out, collect, device=args.device)
+                                                   debug_out, collect, device=args.device, candidates=candidates)
         else:
             raise RuntimeError('Unknown model type %s.' % model_args.type)
 
@@ -123,7 +152,9 @@ def main(argv=None):
         for position, (topic_id, text) in enumerate(topics.items(), 1):
             ids = topic_tokens(text, words)
             logging.debug('Query (%d/%d) %s: %s', position, len(topics), topic_id, text)
-            if ids:
+            if candidates is not None and topic_id not in candidates:
+                logging.warning('Skipping query "%s": no candidates.', topic_id)
+            elif ids:
                 batcher.submit(ids, topic_id=topic_id)
             else:
                 logging.warning('Skipping query with terms "%s".', text)

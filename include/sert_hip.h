@@ -355,6 +355,42 @@ int sert_scorer_scores(sert_scorer* s, const float* proj, int64_t num_queries, f
  * An all-zero entity row or query has no direction: its cosines are NaN. */
 int sert_scorer_cosines(sert_scorer* s, const float* proj, int64_t num_queries, float* cos_out);
 
+/* Re-ranking: score and order the candidates a first stage found for each query, instead of every entity (no reference
+ * counterpart: the reference ranks all of V_e and leaves the restriction to whoever reads the run file).  The candidates are
+ * CSR: cand_indptr (Q + 1) int64 starts at 0 and never decreases, cand_entities int32 in [0, V_e); query q owns
+ * cand_entities[cand_indptr[q] .. cand_indptr[q + 1]), which may be empty.  All arrays on the host.
+ * ONE ARITHMETIC: the projections are L2-normalised as for every other call of the scorer, and a pair's cosine is exact_dot32
+ * (csrc/kernels_score_bf16.h) of the normalised query row and the normalised table row -- whatever the table size, whichever
+ * kernel ranks the list.  For d % 4 != 0, which exact_dot32's 16-byte loads cannot take, the same lanes own the same columns
+ * and run the same fmaf chain and the same shuffle tree on scalar loads.  So
+ *   - for a bf16-prefiltered table (V_e >= 32768, d % 4 == 0, no SERT_SCORE_FP32) the pair cosines are sert_scorer_cosines'
+ *     values bit for bit, and the ranking of a list is sert_scorer_rank(-1)'s ranking restricted to the list;
+ *   - for smaller tables sert_scorer_cosines / _scores / _rank / _topk report the fp32 GEMM's cosines, which differ from
+ *     exact_dot32's within fp32 rounding: the two calls below can then differ from them in the last bits of a value, and in the
+ *     order of two entities whose cosines lie within a rounding of each other.  Small tables are not routed through the GEMM to
+ *     hide this: the work would again be V_e per query.
+ * A failed argument check (null pointer, cand_indptr[0] != 0, a decreasing cand_indptr, an entity out of range, and for the
+ * ranker an unsorted or duplicated list or a bad k) returns before anything is launched; sert_last_error names the fault.
+ *
+ * sert_scorer_pairs: out[j] for every j in [0, cand_indptr[Q]), in the caller's order, = the cosine of the pair (raw = 1) or
+ * (cos + 1)/2 (raw = 0).  Any order and duplicates are allowed inside a list.  One half-wave per pair, the work cut by pairs
+ * and not by queries (csrc/kernels_rerank.h); chunks of SERT_SCORE_RANK_BUDGET / 8 pairs. */
+int sert_scorer_pairs(sert_scorer* s, const float* proj, int64_t num_queries, const int64_t* cand_indptr,
+                      const int32_t* cand_entities, int raw, float* out);
+
+/* sert_scorer_rank_candidates: every list STRICTLY ASCENDING (hence free of duplicates).  k = -1 ranks the whole list, k >= 1
+ * its best min(k, length) -- the ranked depth kk_q; k = 0 and k < -1 are refused.  The results are compact: query q's kk_q
+ * entries start at sum_{p < q} kk_p of idx_out / score_out (the caller sizes both from cand_indptr and k).  The order is the
+ * scorer's one order (sert_scorer_rank) on the cosines sert_scorer_pairs(raw = 1) returns for the list: cosine descending
+ * (-0 equal to +0), a NaN of either sign after every number, ties and the NaNs among themselves by lowest entity index; score
+ * = (cos + 1)/2, applied after the ordering.  The kernel goes by the query's own list length: up to 8192 candidates are
+ * scored, sorted and emitted by one workgroup in LDS; longer lists have their cosines written to a NaN-padded slab, ordered
+ * by the counting-sort passes of sert_scorer_rank and mapped back to entities.  Queries are cut into chunks of consecutive
+ * queries whose device footprint fits SERT_SCORE_RANK_BUDGET (at least one query; at most 2048 long lists and fewer than 2^31
+ * slab elements); a query's result depends neither on the chunking nor on the other queries of the call. */
+int sert_scorer_rank_candidates(sert_scorer* s, const float* proj, int64_t num_queries, const int64_t* cand_indptr,
+                                const int32_t* cand_entities, int32_t k, int32_t* idx_out, float* score_out);
+
 /* Page-locked host memory for the arrays that cross this boundary on every query call (the
  * (Q, d) projections in, the (Q, k) indices and scores out).  The reference hands numpy arrays
  * to sklearn (query.py:304-318); a caller that builds its query block in such a buffer and reads

@@ -201,6 +201,12 @@ int sert_debug_scorer_rank_counts(sert_scorer* s, int64_t* out, int n);
 int sert_debug_scorer_rank_select(int device, const float* S, int64_t num_queries, int32_t V, int32_t k, int32_t* idx_out,
                                   float* score_out);
 
+/* What a scorer's sert_scorer_pairs and sert_scorer_rank_candidates calls did since sert_scorer_create -- host counters, test
+ * hook: out[0] calls of the two that passed their argument checks, out[1] their chunks (SERT_SCORE_RANK_BUDGET), queries
+ * ranked by out[2] the LDS kernel (1 .. 8192 candidates), out[3] the slab and the counting-sort passes (more), out[4] pairs
+ * scored (a pair of sert_scorer_rank_candidates is scored once, whichever kernel ranks it), out[5] empty lists. */
+int sert_debug_scorer_rerank_counts(sert_scorer* s, int64_t out[6]);
+
 /* Test hook: overwrite the step's gradient scratch -- the flat buffer [g_Rw | g_Re | g_W | g_b | loss, sum of squares] with
  * quiet NaNs, the per-entity sorted-run bounds behind it with the wrong run [0, 1) -- after waiting for the device.  A step
  * whose negatives were drawn ahead launches NO prologue (nothing is zeroed): it relies on every value it reads having been

@@ -63,11 +63,12 @@ EXPORTS = [
     'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_score_topk',
     'sert_reval_create', 'sert_reval_run', 'sert_reval_destroy',
     'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_rank', 'sert_scorer_scores', 'sert_scorer_cosines',
+    'sert_scorer_pairs', 'sert_scorer_rank_candidates',
     'sert_host_alloc', 'sert_host_free',
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -164,6 +165,8 @@ def load():
     lib.sert_scorer_rank.argtypes = [vp, fp, i64, i32, fp, fp]
     lib.sert_scorer_scores.argtypes = [vp, fp, i64, fp]
     lib.sert_scorer_cosines.argtypes = [vp, fp, i64, fp]
+    lib.sert_scorer_pairs.argtypes = [vp, fp, i64, fp, fp, ctypes.c_int, fp]
+    lib.sert_scorer_rank_candidates.argtypes = [vp, fp, i64, fp, fp, i32, fp, fp]
     lib.sert_host_alloc.argtypes = [ctypes.POINTER(vp), sz]
     lib.sert_host_free.argtypes = [vp]
     lib.sert_comm_unique_id.argtypes = [ctypes.c_char_p]
@@ -690,6 +693,39 @@ def debug_count_ranks(cosines, judged, device=0):
     return [ranks[indptr[q]:indptr[q + 1]] for q in range(s.shape[0])]
 
 
+def candidates_csr(candidates, unique=False):
+    """Per-query candidate lists (a sequence of integer arrays) as the CSR sert_scorer_pairs / sert_scorer_rank_candidates
+    take: (indptr (Q + 1) int64, entities int32).  unique: every list sorted ascending and de-duplicated (np.unique), what
+    the ranker requires; otherwise order and duplicates are kept."""
+    lists = [np.asarray(c).reshape(-1) for c in candidates]
+    for c in lists:
+        if c.size and not np.issubdtype(c.dtype, np.integer):
+            raise SertError('candidate lists hold integer entity indices')
+    def flatten(lists):
+        indptr = np.zeros(len(lists) + 1, dtype=np.int64)
+        np.cumsum([c.size for c in lists], out=indptr[1:])
+        return indptr, (np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64))
+
+    indptr, flat = flatten(lists)
+    if unique and flat.size > 1:
+        # (lists that arrive clean -- a run file's, a previous call's -- are recognised in one pass over the flat array)
+        rising = flat[1:] > flat[:-1]
+        rising[indptr[1:-1][(indptr[1:-1] > 0) & (indptr[1:-1] < flat.size)] - 1] = True      # (across a list boundary: anything goes)
+        if not rising.all():
+            indptr, flat = flatten([np.unique(c) for c in lists])
+    if flat.size and (flat.min() < -2 ** 31 or flat.max() >= 2 ** 31):
+        raise SertError('candidate entity index does not fit int32')
+    return indptr, np.ascontiguousarray(flat, dtype=np.int32)
+
+
+def ranked_indptr(indptr, k=None):
+    """Where sert_scorer_rank_candidates writes each query's results: the prefix sum of min(k, length) (k None: length)."""
+    lengths = np.diff(np.asarray(indptr, dtype=np.int64))
+    out = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(lengths if k is None else np.minimum(lengths, int(k)), out=out[1:])
+    return out
+
+
 class Scorer(object):
     """Persistent device copy of the (L2-normalised) entity table + top-k scoring
     (sert_scorer_* in include/sert_hip.h).
@@ -804,6 +840,52 @@ class Scorer(object):
             idx[lo:lo + step] = order
             val[lo:lo + step] = (np.take_along_axis(cos, order, axis=1) + np.float32(1)) / np.float32(2)
         return idx, val
+
+    def _queries(self, projections, count):
+        p = np.ascontiguousarray(projections, dtype=np.float32)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        assert p.shape == (count, self.dim), (p.shape, count, self.dim)
+        return p
+
+    def score_pairs(self, projections, candidates, raw=False):
+        """(indptr, values): the value of every (query, candidate) pair, candidates[q] the integer entity indices of query q
+        -- in the caller's order, duplicates kept; query q's values are values[indptr[q]:indptr[q + 1]].  raw: the cosine
+        itself, else (cos + 1) / 2 (sert_scorer_pairs)."""
+        indptr, ents = candidates_csr(candidates)
+        p = self._queries(projections, len(indptr) - 1)
+        out = np.empty(len(ents), dtype=np.float32)
+        # (the library refuses a null pointer: an empty array still has an address to give)
+        e, o = (ents, out) if len(ents) else (np.zeros(1, np.int32), np.zeros(1, np.float32))
+        check(self._lib.sert_scorer_pairs(self._h, p.ctypes.data, p.shape[0], indptr.ctypes.data, e.ctypes.data,
+                                          1 if raw else 0, o.ctypes.data))
+        return indptr, out
+
+    def rank_candidates(self, projections, candidates, k=None):
+        """(out_indptr, idx, score): each query's candidates ranked, best first, under the scorer's one order; k=None ranks
+        the whole list, else its best min(k, length).  Query q's result is idx / score[out_indptr[q]:out_indptr[q + 1]].
+        The lists may come in any order and with duplicates: they are sorted and de-duplicated here, as
+        sert_scorer_rank_candidates requires."""
+        if k is not None and k <= 0:
+            raise SertError('Scorer.rank_candidates: k must be None (the whole list) or positive')
+        indptr, ents = candidates_csr(candidates, unique=True)
+        p = self._queries(projections, len(indptr) - 1)
+        out_indptr = ranked_indptr(indptr, k)
+        n = int(out_indptr[-1])
+        idx = np.empty(max(n, 1), dtype=np.int32)
+        val = np.empty(max(n, 1), dtype=np.float32)
+        e = ents if len(ents) else np.zeros(1, np.int32)
+        check(self._lib.sert_scorer_rank_candidates(self._h, p.ctypes.data, p.shape[0], indptr.ctypes.data, e.ctypes.data,
+                                                    -1 if k is None else min(int(k), 2 ** 31 - 1), idx.ctypes.data, val.ctypes.data))
+        return out_indptr, idx[:n], val[:n]
+
+    def debug_rerank_counts(self):
+        """sert_debug_scorer_rerank_counts (test hook): [score_pairs / rank_candidates calls, their chunks, queries ranked by
+        the LDS kernel, by the slab and the counting-sort passes, pairs scored, empty lists]."""
+        v = (ctypes.c_int64 * 6)()
+        self._lib.sert_debug_scorer_rerank_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        check(self._lib.sert_debug_scorer_rerank_counts(self._h, v))
+        return [int(x) for x in v]
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:

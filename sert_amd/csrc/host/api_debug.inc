@@ -140,6 +140,12 @@ int sert_debug_scorer_rank_counts(sert_scorer* sc, int64_t* out, int n) {
     return 0;
 }
 
+int sert_debug_scorer_rerank_counts(sert_scorer* sc, int64_t out[6]) {
+    if (!sc || !out) SERT_FAIL("bad argument");
+    for (int i = 0; i < 6; ++i) out[i] = sc->rerank_counts[i];
+    return 0;
+}
+
 int sert_debug_scorer_rank_select(int device, const float* S, int64_t Q, int32_t V, int32_t k, int32_t* idx_out, float* score_out) {
     if (!S || !idx_out || !score_out || Q <= 0 || V <= 0 || k == 0 || k < -1) SERT_FAIL("bad argument");
     const int kk = (k < 0 || k >= V) ? V : k;

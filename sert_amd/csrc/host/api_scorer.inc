@@ -66,6 +66,8 @@ int sert_scorer_destroy(sert_scorer* sc) {
     (void)hipFree(sc->nflag); (void)hipFree(sc->flag_list); (void)hipFree(sc->Pc); (void)hipFree(sc->idx_c);
     (void)hipFree(sc->val_c); (void)hipFree(sc->E16); (void)hipFree(sc->P16);
     (void)hipFree(sc->rP); (void)hipFree(sc->rS); rank_scratch_free(sc->rsort);
+    (void)hipFree(sc->cptr); (void)hipFree(sc->cents); (void)hipFree(sc->cq); (void)hipFree(sc->csptr);
+    (void)hipFree(sc->cidx); (void)hipFree(sc->cval); (void)hipFree(sc->cpos); (void)hipFree(sc->cpval);
     for (int b = 0; b < 2; ++b) {
         (void)hipFree(sc->ridx[b]); (void)hipFree(sc->rval[b]);
         if (sc->ev_rsorted[b]) (void)hipEventDestroy(sc->ev_rsorted[b]);

@@ -60,8 +60,27 @@ __device__ __forceinline__ float exact_dot32(const float* __restrict__ p, const 
     return a;
 }
 
+// exact_dot32 for any d.  d % 4 == 0 IS exact_dot32.  Otherwise rows are not 16-byte aligned and the last chunk is short: the
+// same lane ownership (lane l: columns 4 l .. 4 l + 3, then + 128, ...), the same fmaf chain and the same tree, on scalar
+// loads; a column at or beyond d contributes nothing.  Only the candidate re-ranker (kernels_rerank.h) scores such tables
+// with it: no bf16-prefiltered table has d % 4 != 0.
+__device__ __forceinline__ float exact_dot32_any(const float* __restrict__ p, const float* __restrict__ e, int d, int l) {
+    if ((d & 3) == 0) return exact_dot32(p, e, d, l);
+    float a = 0.f;
+    for (int c = 4 * l; c < d; c += 128) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (c + i < d) a = fmaf(p[c + i], e[c + i], a);
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+    return a;
+}
+
 // keys[0, m): (anything << 32 | entity).  Replace the high words by the exact fp32 score keys,
 // sort (score desc, entity asc) and emit the k best.  sort_n = power of two >= m, <= LDS size.
+// ANY_DIM (the candidate re-ranker): d % 4 != 0 is allowed, through exact_dot32_any.
+template <bool ANY_DIM = false>
 __device__ __forceinline__ void rescore_sort_emit(unsigned long long* keys, int m, int sort_n,
                                                   const float* __restrict__ prow, const float* __restrict__ E,
                                                   int d, int k, int32_t* __restrict__ idx_out,
@@ -90,7 +109,8 @@ __device__ __forceinline__ void rescore_sort_emit(unsigned long long* keys, int 
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) sc[j] = exact_dot32(prow, E + (size_t)e[j] * d, d, l);
+            for (int j = 0; j < 4; ++j)
+                sc[j] = ANY_DIM ? exact_dot32_any(prow, E + (size_t)e[j] * d, d, l) : exact_dot32(prow, E + (size_t)e[j] * d, d, l);
         }
         if (l == 0) {
 #pragma unroll

@@ -374,4 +374,14 @@ struct sert_scorer {
     // [0] sert_scorer_rank calls, [1] their query chunks, rows ranked by [2] the top-k path, [3] the LDS sort, [4] the LSD
     // passes, [5] microseconds the copies of [3] and [4]'s results took on the second stream (sert_debug_scorer_rank_counts)
     int64_t rank_counts[6] = {0, 0, 0, 0, 0, 0};
+    // sert_scorer_pairs / sert_scorer_rank_candidates (host/api_scorer_rerank.inc), grown on demand; they also use rP, rS and
+    // rsort above.  cptr (2 (Q + 1)) the call's indptr and behind it its output offsets; per chunk: cents its candidates, cq its
+    // queries grouped by kernel, csptr the prefix of the slab rows' lengths, cidx / cval its ragged results, cpos / cpval
+    // the slab rows' (rows, kkc) list positions and scores
+    int64_t* cptr = nullptr; int32_t* cents = nullptr; int32_t* cq = nullptr; int64_t* csptr = nullptr;
+    int32_t* cidx = nullptr; float* cval = nullptr; int32_t* cpos = nullptr; float* cpval = nullptr;
+    int64_t cap_cptr = 0, cap_cents = 0, cap_cq = 0, cap_csptr = 0, cap_cidx = 0, cap_cval = 0, cap_cpos = 0, cap_cpval = 0;
+    // [0] calls of the two, [1] their chunks, queries ranked by [2] the LDS kernel, [3] the slab and the counting-sort passes,
+    // [4] pairs scored, [5] empty lists (sert_debug_scorer_rerank_counts)
+    int64_t rerank_counts[6] = {0, 0, 0, 0, 0, 0};
 };

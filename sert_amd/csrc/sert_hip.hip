@@ -31,6 +31,7 @@
 #include "kernels_membench.h"
 #include "kernels_opt.h"
 #include "kernels_rank.h"
+#include "kernels_rerank.h"
 #include "kernels_reval.h"
 #include "kernels_score.h"
 #include "kernels_seg.h"
@@ -186,6 +187,8 @@ extern "C" {
 #include "host/api_ll_rank.inc"
 
 #include "host/api_scorer_rank.inc"
+
+#include "host/api_scorer_rerank.inc"
 
 #include "host/api_reval.inc"
 

@@ -59,10 +59,28 @@ class Callback(object):
         raise NotImplementedError()
 
 
+def _candidate_array(candidates, topic_id):
+    """The candidate entity indices of a topic; none at all for a topic without a list."""
+    return np.asarray(candidates.get(topic_id, ()), dtype=np.int64).reshape(-1)
+
+
 class LogLinearCallback(Callback):
+    """``candidates`` (optional): topic id -> array of internal entity indices.  When given, the ranking of a topic is
+    filtered to its candidates before ``rank_callback``: same order, same scores.  The scores stay normalised over ALL
+    entities (the model's distribution is over the whole collection), so those of a filtered ranking do not sum to one."""
+
+    def __init__(self, *args, **kwargs):
+        self.candidates = kwargs.pop('candidates', None)
+        super(LogLinearCallback, self).__init__(*args, **kwargs)
 
     def should_average_input(self):
         return False
+
+    def _report(self, topic_id, idx, score):
+        if self.candidates is not None:
+            keep = np.isin(idx, _candidate_array(self.candidates, topic_id))
+            idx, score = idx[keep], score[keep]
+        self.rank_callback(topic_id, idx, score)
 
     def process(self, payload, distribution, topic_id):
         per_token_entropy = compute_normalised_entropy(distribution, base=2)
@@ -83,7 +101,7 @@ class LogLinearCallback(Callback):
 
         # ascending argsort read backwards = best first; all V_e entities are ranked
         order = np.argsort(joint)[::-1]
-        self.rank_callback(topic_id, order, joint[order])
+        self._report(topic_id, order, joint[order])
 
     def process_batch(self, payloads, ranking, kwargs_list):
         """Additive: the queries of a run ranked on the device (inference.QueryRanking, from
@@ -117,13 +135,17 @@ class LogLinearCallback(Callback):
                 self.f_debug_out.write('Topic {0} {1}: {2}\n'.format(
                     topic_id, etype(ranking.joint_entropy[q]),
                     list(zip(words, [etype(h) for h in ranking.token_entropy[q]]))))
-            self.rank_callback(topic_id, idx, score)
+            self._report(topic_id, idx, score)
 
 
 class VectorSpaceCallback(Callback):
+    """``candidates`` (optional): topic id -> array of internal entity indices.  When given, each topic's candidates -- not
+    every entity -- are scored and ranked on the device (Scorer.rank_candidates; --top is its k), ``process_batch`` in one
+    call for all topics; a topic without a list gets an empty ranking.  ``rank_callback`` is called as without."""
 
     def __init__(self, entity_representations, *args, **kwargs):
         self.device = kwargs.pop('device', 0)
+        self.candidates = kwargs.pop('candidates', None)
         super(VectorSpaceCallback, self).__init__(*args, **kwargs)
 
         num_entities = entity_representations.shape[0]
@@ -158,6 +180,11 @@ class VectorSpaceCallback(Callback):
         identity = inference.aggregate_distribution(result, mode='identity', axis=0)
         rows = 1 if identity.ndim == 1 else identity.shape[0]
         assert rows == 1, 'one centroid per query'
+        if self.candidates is not None:
+            _, idx, score = self.scorer.rank_candidates(self._as_queries(identity, 1),
+                                                        [_candidate_array(self.candidates, topic_id)], self.n_neighbors)
+            self.rank_callback(topic_id, idx.astype(np.int64), score)
+            return
         idx, score = self.scorer.rank(self._as_queries(identity, 1), self.n_neighbors)
         self.rank_callback(topic_id, idx[0].astype(np.int64), score[0])
 
@@ -169,6 +196,12 @@ class VectorSpaceCallback(Callback):
         for kw, q in zip(kwargs_list, queries):
             # (a copy: `queries` is the scorer's reusable page-locked block, overwritten by the next call)
             self._remember(kw['topic_id'], q.copy())
+        if self.candidates is not None:
+            at, idx, score = self.scorer.rank_candidates(
+                queries, [_candidate_array(self.candidates, kw['topic_id']) for kw in kwargs_list], self.n_neighbors)
+            for row, kw in enumerate(kwargs_list):
+                self.rank_callback(kw['topic_id'], idx[at[row]:at[row + 1]].astype(np.int64), score[at[row]:at[row + 1]])
+            return
         idx, score = self.scorer.rank(queries, self.n_neighbors)
         for row, kw in enumerate(kwargs_list):
             self.rank_callback(kw['topic_id'], idx[row].astype(np.int64), score[row])
