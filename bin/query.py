@@ -16,7 +16,10 @@ candidates is skipped, as a topic of only OOV terms is).  Both model kinds take
 the batched path by default: vectorspace through VectorSpaceCallback.process_batch,
 loglinear through LogLinearPredictFn.rank_queries + LogLinearCallback.process_batch
 (the per-token distributions stay on the device; every entity is ranked and --top
-is ignored, as in the reference, query.py:199-236).
+is ignored, as in the reference, query.py:199-236).  With --candidates the batched
+loglinear path ranks each topic's whole list on the device (sert_ll_rank_candidates:
+scores normalised over all entities, --top still ignored) instead of ranking every
+entity and filtering on the host; the three files come out the same.
 """
 import argparse
 import collections

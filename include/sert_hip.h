@@ -241,6 +241,26 @@ int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* of
                          int32_t* idx_out, float* score_out, float* joint_entropy_out, float* token_entropy_out,
                          int32_t* status_out);
 
+/* Re-ranking with the loglinear model: sert_ll_rank_queries restricted to per-query candidate lists.  tokens / offsets,
+ * joint_entropy_out, token_entropy_out and status_out are exactly those of sert_ll_rank_queries (the entropies are over ALL
+ * entities).  cand_indptr (Q + 1) / cand_entities: the CSR of sert_scorer_rank_candidates -- cand_indptr starts at 0 and never
+ * decreases, a list may be empty, entities lie in [0, V_e) and are STRICTLY ASCENDING inside a list.  k = -1 ranks the whole
+ * list, k >= 1 its best kk_q = min(k, length); query q writes at out_ptr[q] = sum_{p < q} kk_p of idx_out / score_out (the
+ * ragged layout of sert_scorer_rank_candidates).
+ *   For a query with status DEVICE the result is sert_ll_rank_queries(k = -1)'s ranking of that query restricted to its list,
+ *   cut to its head: the same entities in the same order (score descending, ties by lowest entity index) and the same score
+ *   BITS -- the scores stay normalised over all entities, the partition function is not restricted.  A query with status HOST
+ *   has a zeroed joint row: its list comes back in entity order with score 0, not meaningful; the caller takes the host path.
+ * A query's result does not depend on the other queries of the call, on their lists, or on how the call is cut into chunks
+ * (SERT_LL_RANK_BUDGET; a chunk holds joint rows but neither a V_e-wide sort scratch nor V_e-wide outputs, so far more queries
+ * than one of sert_ll_rank_queries).  Every argument fault -- a null pointer, cand_indptr[0] != 0, a decreasing cand_indptr, an
+ * entity out of range, an unsorted or duplicated list, k == 0 or k < -1, a vectorspace model, a bad token or offset -- returns
+ * before anything is launched; a failed call leaves nothing queued.  COLLECTIVE in data parallel, as sert_ll_rank_queries. */
+int sert_ll_rank_candidates(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries,
+                            const int64_t* cand_indptr, const int32_t* cand_entities, int32_t k,
+                            int32_t* idx_out, float* score_out, float* joint_entropy_out,
+                            float* token_entropy_out, int32_t* status_out);
+
 /* ---- retrieval evaluation on the live model (product-search.sh:136-170, W3C-expert-finding.sh:108-124) ---- */
 
 typedef struct sert_reval sert_reval;

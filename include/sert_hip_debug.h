@@ -247,6 +247,20 @@ int sert_debug_ll_rank_distributions(int device, const float* P, const int64_t* 
                                      int32_t k, int32_t* idx_out, float* score_out, float* joint_entropy_out,
                                      float* token_entropy_out, int32_t* status_out);
 
+/* Test hook: sert_debug_ll_rank_distributions plus the candidate CSR and the ragged outputs of sert_ll_rank_candidates -- the
+ * aggregate and the candidate-ranking kernels (csrc/kernels_ll_rerank.h) on per-token distributions the caller provides, all
+ * queries as one chunk. */
+int sert_debug_ll_rank_candidates_distributions(int device, const float* P, const int64_t* offsets, int64_t num_queries,
+                                                int32_t V, const int64_t* cand_indptr, const int32_t* cand_entities, int32_t k,
+                                                int32_t* idx_out, float* score_out, float* joint_entropy_out,
+                                                float* token_entropy_out, int32_t* status_out);
+
+/* What the sert_ll_rank_candidates and sert_debug_ll_rank_candidates_distributions calls of this PROCESS did -- host counters,
+ * test hook: out[0] calls that passed their argument checks, out[1] their chunks (SERT_LL_RANK_BUDGET), lists ranked by out[2]
+ * the LDS kernel (1 .. 8192 candidates), out[3] the slab and the counting-sort passes (more), out[4] empty lists.  One
+ * process-wide set for both calls (the debug call has no model to keep them in): compare two readings. */
+int sert_debug_ll_rerank_counts(int64_t out[5]);
+
 /* Micro-benchmark of the fp32 MFMA GEMM on device-resident random operands:
  * C (M,N) = op(A).op(B); ta/tb as in gemm.h; epi 0 = store, 1 = +bias, 2 = tanh(+bias);
  * splits > 1 = split-K partial slabs.  Returns the average launch time in *avg_us

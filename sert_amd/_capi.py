@@ -60,7 +60,7 @@ EXPORTS = [
     'sert_set_eval_draws', 'sert_get_eval_draws', 'sert_negatives_of_step',
     'sert_upload_dataset', 'sert_train_batch', 'sert_hint_next_batch', 'sert_train_batches',
     'sert_eval_batch', 'sert_eval_batches',
-    'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_score_topk',
+    'sert_predict_project', 'sert_predict_tokens', 'sert_ll_rank_queries', 'sert_ll_rank_candidates', 'sert_score_topk',
     'sert_reval_create', 'sert_reval_run', 'sert_reval_destroy',
     'sert_scorer_create', 'sert_scorer_destroy', 'sert_scorer_topk', 'sert_scorer_rank', 'sert_scorer_scores', 'sert_scorer_cosines',
     'sert_scorer_pairs', 'sert_scorer_rank_candidates',
@@ -69,7 +69,7 @@ EXPORTS = [
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
     'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
-    'sert_debug_count_ranks',
+    'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
 # ... and include/sert_hip_reval_counted.h, which sert_hip.h includes (the evaluator by rank counting)
@@ -153,6 +153,9 @@ def load():
     lib.sert_predict_project.argtypes = [vp, fp, i64, fp]
     lib.sert_predict_tokens.argtypes = [vp, fp, i64, fp]
     lib.sert_ll_rank_queries.argtypes = [vp, fp, fp, i64, i32, fp, fp, fp, fp, fp]
+    lib.sert_ll_rank_candidates.argtypes = [vp, fp, fp, i64, fp, fp, i32, fp, fp, fp, fp, fp]
+    lib.sert_debug_ll_rank_candidates_distributions.argtypes = [ctypes.c_int, fp, fp, i64, i32, fp, fp, i32, fp, fp, fp, fp, fp]
+    lib.sert_debug_ll_rerank_counts.argtypes = [ctypes.POINTER(i64)]
     lib.sert_reval_create.argtypes = [vp, fp, fp, i64, fp, fp, fp, fp, fp, i32, ctypes.POINTER(vp)]
     lib.sert_reval_create_counted.argtypes = lib.sert_reval_create.argtypes
     lib.sert_reval_judged_ranks.argtypes = [vp, fp]
@@ -374,6 +377,18 @@ class Engine(object):
         return _ll_rank_call(self.cfg.num_entities, offsets, k, lambda kk, outs: self._lib.sert_ll_rank_queries(
             self._h, tokens.ctypes.data, offsets.ctypes.data, offsets.size - 1, kk, *outs), tokens.size)
 
+    def ll_rank_candidates(self, token_lists, candidates, k=None):
+        """sert_ll_rank_candidates: every query's candidate list (one integer array per query; any order, duplicates allowed:
+        sorted and de-duplicated here, as Scorer.rank_candidates does) ranked under the loglinear model, scores normalised
+        over all entities.  (out_indptr (Q + 1,) int64, idx int32, score f32 -- query q's result is
+        idx / score[out_indptr[q]:out_indptr[q + 1]], its best min(k, length), k None: the whole list --, joint_entropy (Q,),
+        token_entropy (T,), status (Q,) int32, offsets (Q + 1,) int64)."""
+        tokens, offsets = _concat_queries(token_lists)
+        return _ll_rank_candidates_call(self.cfg.num_entities, offsets, candidates, k, tokens.size,
+                                        lambda indptr, ents, kk, outs: self._lib.sert_ll_rank_candidates(
+                                            self._h, tokens.ctypes.data, offsets.ctypes.data, offsets.size - 1,
+                                            indptr.ctypes.data, ents.ctypes.data, kk, *outs))
+
     # data parallel
     def comm_init(self, unique_id, rank, world):
         assert len(unique_id) == COMM_ID_BYTES
@@ -588,6 +603,49 @@ def debug_ll_rank_distributions(distributions, offsets, k=None, device=0):
                                                      ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 5
     return _ll_rank_call(P.shape[1], offsets, k, lambda kk, outs: lib.sert_debug_ll_rank_distributions(
         device, P.ctypes.data, offsets.ctypes.data, offsets.size - 1, P.shape[1], kk, *outs), P.shape[0])
+
+
+def _ll_rank_candidates_call(num_entities, offsets, candidates, k, num_tokens, call):
+    q = offsets.size - 1
+    if k is not None and k <= 0:
+        raise SertError('ll_rank_candidates: k must be None (the whole list) or positive')
+    if len(candidates) != q:
+        raise SertError('ll_rank_candidates: %d candidate lists for %d queries' % (len(candidates), q))
+    indptr, ents = candidates_csr(candidates, unique=True)
+    out_indptr = ranked_indptr(indptr, k)
+    n = int(out_indptr[-1])
+    idx = np.empty(max(n, 1), dtype=np.int32)
+    score = np.empty(max(n, 1), dtype=np.float32)
+    joint_h = np.empty(q, dtype=np.float32)
+    token_h = np.empty(max(num_tokens, 1), dtype=np.float32)
+    status = np.empty(q, dtype=np.int32)
+    # (the library refuses a null pointer: an empty array still has an address to give)
+    e = ents if len(ents) else np.zeros(1, np.int32)
+    outs = [a.ctypes.data for a in (idx, score, joint_h, token_h, status)]
+    check(call(indptr, e, -1 if k is None else min(int(k), 2 ** 31 - 1), outs))
+    return out_indptr, idx[:n], score[:n], joint_h, token_h[:num_tokens], status, offsets
+
+
+def debug_ll_rank_candidates_distributions(distributions, offsets, candidates, k=None, device=0):
+    """sert_debug_ll_rank_candidates_distributions: the aggregate and the candidate-ranking kernels of
+    sert_ll_rank_candidates on per-token distributions (offsets[-1], V_e) given here; same outputs as
+    Engine.ll_rank_candidates."""
+    lib = load()
+    P = np.ascontiguousarray(distributions, dtype=np.float32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    assert P.ndim == 2 and P.shape[0] == offsets[-1]
+    return _ll_rank_candidates_call(P.shape[1], offsets, candidates, k, P.shape[0],
+                                    lambda indptr, ents, kk, outs: lib.sert_debug_ll_rank_candidates_distributions(
+                                        device, P.ctypes.data, offsets.ctypes.data, offsets.size - 1, P.shape[1],
+                                        indptr.ctypes.data, ents.ctypes.data, kk, *outs))
+
+
+def debug_ll_rerank_counts():
+    """sert_debug_ll_rerank_counts (test hook): what the loglinear candidate calls of this process did so far -- [calls, their
+    chunks, lists ranked by the LDS kernel, by the slab and the counting-sort passes, empty lists]."""
+    v = (ctypes.c_int64 * 5)()
+    check(load().sert_debug_ll_rerank_counts(v))
+    return [int(x) for x in v]
 
 
 def score_topk(entities, projections, k, device=0):

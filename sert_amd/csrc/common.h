@@ -15,7 +15,7 @@
 //   SERT_SCORE_MATERIALISE  SERT_SCORE_FP32  SERT_LL_NODEDUP  SERT_LL_DW_SIDE  SERT_DENSE_HEAVY  SERT_FS_TILE_ROWS
 //   SERT_EGRAD_SORT  SERT_ROCTX  SERT_EVENT_FENCE  SERT_LAZY_SKIP (0: dense_update_lazy instead of dense_update_skip)
 //   SERT_LAZY_MAX (largest touched fraction of a batch whose word-table update is lazy; default 0.5 behind an announced
-//   next batch, min(that, 0.35) without one)  SERT_LL_RANK_BUDGET (device bytes per chunk of sert_ll_rank_queries)
+//   next batch, min(that, 0.35) without one)  SERT_LL_RANK_BUDGET (device bytes per chunk of sert_ll_rank_queries / _candidates)
 //   SERT_SCORE_RANK_BUDGET (device bytes per query chunk of sert_scorer_rank)
 // Round 6 moved the measured-and-lost opt-ins of round 5 behind variant_knob() and their kernels into csrc/variants/:
 // SERT_PROJ_FUSED, SERT_GATHER_HOT, SERT_EGRAD_RANGES, SERT_SEG_BUNDLE (and SERT_BWD_FUSED's kernel).

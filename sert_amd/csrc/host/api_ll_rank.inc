@@ -62,10 +62,14 @@ static float ll_ln2_f() { return (float)log(2.0); }
 static float ll_log2v_f(int V) { return (float)(log((double)V) / log(2.0)); }
 
 // P holds the chunk's per-token distributions (rows indexed by w.tok_row), w.offs its Qc + 1 query offsets: joint rows,
-// entropies, status and the ranking (w.idx / w.val, Qc x kk) on stream s
-static int ll_rank_chunk(hipStream_t s, LLRankScratch& w, const float* P, int Qc, int V, int kk, int mode) {
+// joint entropies and status on stream s (ll_rank_aggregate: all sert_ll_rank_candidates takes, host/api_ll_rerank.inc), then
+// the ranking of the whole rows (w.idx / w.val, Qc x kk)
+static void ll_rank_aggregate(hipStream_t s, LLRankScratch& w, const float* P, int Qc, int V) {
     launch(ll_query_aggregate, dim3(Qc), dim3(256), 0, s, P, w.tok_row, w.offs, V, ll_ln2_f(), ll_log2v_f(V),
            w.J, w.joint_h, w.status);
+}
+static int ll_rank_chunk(hipStream_t s, LLRankScratch& w, const float* P, int Qc, int V, int kk, int mode) {
+    ll_rank_aggregate(s, w, P, Qc, V);
     if (mode == RANK_TOPK) {
         launch(topk_rows<true>, dim3(Qc), dim3(256), 0, s, w.J, V, kk, w.idx, w.val, (float*)nullptr);
         SERT_HIP(hipGetLastError());
@@ -104,25 +108,14 @@ static int ll_rank_check_tokens(const sert_model* m, const int32_t* tokens, int6
     return 0;
 }
 
-static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
-                         LLRankPlan& plan) {
-    const auto& c = m->cfg;
-    const int V = c.num_entities, d = c.word_dim;
+// The cut itself: a chunk takes the next query q while over(q0, q, D) is false -- q0 the chunk's first query, D its distinct
+// tokens with q's -- and its first query always.  Fills bounds and the max_* of plan.
+static void ll_rank_cut(const sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries,
+                        const std::function<bool(int64_t, int64_t, int64_t)>& over, LLRankPlan& plan) {
     const int64_t T = offsets[num_queries];
-    const int kk = (k < 0 || k >= V) ? V : k;
-    const int mode = ll_rank_mode(V, kk);
-    plan.kk = kk; plan.mode = mode;
-    const size_t budget = ll_rank_budget();
-    auto bytes = [&](int64_t D, int64_t Qc) -> size_t {
-        const size_t rows = (size_t)cdiv(D, kLLRankRows) * kLLRankRows;
-        // (the sort scratch without the 8 KiB of its bin totals: they have never been counted, and counting them would move
-        //  the chunk bounds of a given budget)
-        const size_t sort = mode == RANK_CSORT ? rank_scratch_bytes(Qc * (int64_t)V) - (size_t)kSortMaxBins * 4 : 0;
-        return rows * ((size_t)d + V + 2) * 4 + (size_t)Qc * ((size_t)V * 4 + (size_t)kk * 8) + sort;
-    };
     std::vector<int64_t>& bounds = plan.bounds;
     bounds.assign(1, 0);
-    std::vector<int64_t> chunk_of(c.vocab_size, -1);
+    std::vector<int64_t> chunk_of(m->cfg.vocab_size, -1);
     std::vector<int32_t> qtok;
     int64_t D = 0, q0 = 0, maxD = 0, maxT = 0, maxQ = 0;
     for (int64_t q = 0; q < num_queries; ++q) {
@@ -132,7 +125,7 @@ static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64
         const int64_t chunk = (int64_t)bounds.size() - 1;
         int64_t fresh = 0;
         for (int32_t w : qtok) fresh += chunk_of[w] != chunk;
-        if (q > q0 && ((mode == RANK_CSORT && !rank_chunk_fits(q - q0 + 1, V)) || bytes(D + fresh, q - q0 + 1) > budget)) {
+        if (q > q0 && over(q0, q, D + fresh)) {
             maxD = std::max(maxD, D); maxQ = std::max(maxQ, q - q0); maxT = std::max(maxT, offsets[q] - offsets[q0]);
             bounds.push_back(q);
             q0 = q; D = 0;
@@ -147,6 +140,30 @@ static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64
     plan.max_rows = (int64_t)cdiv(maxD, kLLRankRows) * kLLRankRows;
     plan.max_tokens = maxT;
     plan.max_queries = maxQ;
+}
+
+// bytes of the chain in front of the ranking for D distinct tokens: gathered rows, distributions, token entropies (and ids)
+static size_t ll_rank_front_bytes(int64_t D, int d, int V) {
+    return (size_t)cdiv(D, kLLRankRows) * kLLRankRows * ((size_t)d + V + 2) * 4;
+}
+
+static void ll_rank_plan(const sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,
+                         LLRankPlan& plan) {
+    const auto& c = m->cfg;
+    const int V = c.num_entities, d = c.word_dim;
+    const int kk = (k < 0 || k >= V) ? V : k;
+    const int mode = ll_rank_mode(V, kk);
+    plan.kk = kk; plan.mode = mode;
+    const size_t budget = ll_rank_budget();
+    auto bytes = [&](int64_t D, int64_t Qc) -> size_t {
+        // (the sort scratch without the 8 KiB of its bin totals: they have never been counted, and counting them would move
+        //  the chunk bounds of a given budget)
+        const size_t sort = mode == RANK_CSORT ? rank_scratch_bytes(Qc * (int64_t)V) - (size_t)kSortMaxBins * 4 : 0;
+        return ll_rank_front_bytes(D, d, V) + (size_t)Qc * ((size_t)V * 4 + (size_t)kk * 8) + sort;
+    };
+    ll_rank_cut(m, tokens, offsets, num_queries, [&](int64_t q0, int64_t q, int64_t D) {
+        return (mode == RANK_CSORT && !rank_chunk_fits(q - q0 + 1, V)) || bytes(D, q - q0 + 1) > budget;
+    }, plan);
 }
 
 // the device inputs of one chunk (queries a .. b): its distinct token ids in order of first appearance, padded to whole
@@ -168,10 +185,9 @@ static int64_t ll_rank_chunk_inputs(const int32_t* tokens, const int64_t* offset
     return Dc;
 }
 
-// One chunk on the device, inputs in w.ids / w.tok_row / w.offs: the predict_fn chain of sert_predict_tokens on the Dc
-// distinct tokens (`rows` with the padding), their entropies, then ll_rank_chunk.  Both sert_ll_rank_queries and
-// sert_reval_run rank through here, so a query's ranking does not depend on the caller.
-static int ll_rank_chunk_device(sert_model* m, hipStream_t s, LLRankScratch& w, int64_t Dc, int64_t rows, int Qc, int kk, int mode) {
+// The distributions of one chunk, inputs in w.ids / w.tok_row / w.offs: the predict_fn chain of sert_predict_tokens on the Dc
+// distinct tokens (`rows` with the padding) into w.P, and their entropies
+static void ll_rank_chunk_distributions(sert_model* m, hipStream_t s, LLRankScratch& w, int64_t Dc, int64_t rows) {
     const int V = m->cfg.num_entities, d = m->cfg.word_dim;
     if (d % 4 == 0)
         launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
@@ -181,7 +197,13 @@ static int ll_rank_chunk_device(sert_model* m, hipStream_t s, LLRankScratch& w, 
         launch_gemm<false, false, EPI_BIAS>(s, w.G + (size_t)r0 * d, m->W, w.P + (size_t)r0 * V, m->b, kLLRankRows, V, d, d, V, V);
     launch(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);
     launch(ll_row_entropy, dim3((unsigned)Dc), dim3(256), 0, s, w.P, V, ll_ln2_f(), ll_log2v_f(V), w.tok_h);
-    return ll_rank_chunk(s, w, w.P, Qc, V, kk, mode);
+}
+// One chunk on the device: its distributions, then ll_rank_chunk.  sert_ll_rank_queries and sert_reval_run rank through here,
+// and sert_ll_rank_candidates takes its joint rows from the same two steps (ll_rank_chunk_distributions, ll_rank_aggregate), so
+// a query's scores do not depend on the caller.
+static int ll_rank_chunk_device(sert_model* m, hipStream_t s, LLRankScratch& w, int64_t Dc, int64_t rows, int Qc, int kk, int mode) {
+    ll_rank_chunk_distributions(m, s, w, Dc, rows);
+    return ll_rank_chunk(s, w, w.P, Qc, m->cfg.num_entities, kk, mode);
 }
 
 int sert_ll_rank_queries(sert_model* m, const int32_t* tokens, const int64_t* offsets, int64_t num_queries, int32_t k,

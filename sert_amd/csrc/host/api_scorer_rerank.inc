@@ -15,23 +15,26 @@ static int rerank_reserve(T** p, int64_t* cap, int64_t n) {
 }
 }
 
-// The faults of a candidate CSR, found before anything is launched.  ascending: the ranker's lists (strictly ascending, hence
-// free of duplicates).
-static int rerank_check(const sert_scorer* sc, const float* proj, int64_t Q, const int64_t* indptr, const int32_t* ents,
-                        const void* out_a, const void* out_b, bool ascending) {
-    if (!sc || !proj || !indptr || !ents || !out_a || !out_b) SERT_FAIL("null argument");
+// The faults of a candidate CSR over V entities, found before anything is launched.  ascending: the rankers' lists (strictly
+// ascending, hence free of duplicates).  Also sert_ll_rank_candidates' check (api_ll_rerank.inc).
+static int rerank_check_csr(int64_t V, int64_t Q, const int64_t* indptr, const int32_t* ents, bool ascending) {
     if (Q < 0 || Q >= ((int64_t)1 << 31) - 1) SERT_FAIL("bad sizes");
     if (indptr[0] != 0) SERT_FAIL("cand_indptr[0] must be 0");
     for (int64_t q = 0; q < Q; ++q)
         if (indptr[q + 1] < indptr[q]) SERT_FAIL("cand_indptr decreases at query " + std::to_string(q));
     for (int64_t q = 0; q < Q; ++q)
         for (int64_t j = indptr[q]; j < indptr[q + 1]; ++j) {
-            if (ents[j] < 0 || ents[j] >= sc->V)
+            if (ents[j] < 0 || ents[j] >= V)
                 SERT_FAIL("candidate entity out of range: " + std::to_string(ents[j]) + " in the list of query " + std::to_string(q));
             if (ascending && j > indptr[q] && ents[j] <= ents[j - 1])
                 SERT_FAIL("candidate list not strictly ascending (unsorted or duplicated) at query " + std::to_string(q));
         }
     return 0;
+}
+static int rerank_check(const sert_scorer* sc, const float* proj, int64_t Q, const int64_t* indptr, const int32_t* ents,
+                        const void* out_a, const void* out_b, bool ascending) {
+    if (!sc || !proj || !indptr || !ents || !out_a || !out_b) SERT_FAIL("null argument");
+    return rerank_check_csr(sc->V, Q, indptr, ents, ascending);
 }
 
 // the call's projections, normalised, in rP; its indptr (and, ranker, the output offsets behind it) in cptr
@@ -53,11 +56,11 @@ static int rerank_upload_queries(sert_scorer* sc, hipStream_t s, const float* pr
 // workgroups of the pair kernel: eight per CU's worth at most, and at least four trips per half-wave behind its one bisection
 static unsigned rerank_pair_grid(int64_t items) { return (unsigned)std::min<int64_t>(cdiv(items, 4 * kRerankTile), 2048); }
 
-// nothing of a failed call stays queued (sert_scorer_rank's rule)
-static int rerank_finish(sert_scorer* sc, int rc) {
+// nothing of a failed call stays queued on its stream s (sert_scorer_rank's rule; also sert_ll_rank_candidates')
+static int rerank_finish(hipStream_t s, int rc) {
     if (rc == 0) return 0;
     const std::string keep = g_last_error;
-    (void)hipStreamSynchronize(sc->stream);
+    (void)hipStreamSynchronize(s);
     g_last_error = keep;
     return rc;
 }
@@ -90,7 +93,7 @@ int sert_scorer_pairs(sert_scorer* sc, const float* proj, int64_t Q, const int64
         }
         return 0;
     };
-    return rerank_finish(sc, body());
+    return rerank_finish(s, body());
 }
 
 // the LDS size a list of len candidates is sorted in (rank_rows_lds' sizes), as an index 0 .. 3
@@ -204,5 +207,5 @@ int sert_scorer_rank_candidates(sert_scorer* sc, const float* proj, int64_t Q, c
         }
         return 0;
     };
-    return rerank_finish(sc, body());
+    return rerank_finish(s, body());
 }

@@ -15,6 +15,24 @@ namespace sert {
 
 constexpr int kRankLdsMax = 8192;               // V up to this: the whole ranking sorted in one workgroup's LDS
 
+// Ascending bitonic sort of keys[0, sort_n) in LDS by a 256-thread workgroup: sort_n a power of two >= 2, the words already
+// written and a barrier behind them.  (The sort of rank_rows_lds; ll_rerank_lds, kernels_ll_rerank.h, sorts through it too.)
+__device__ __forceinline__ void bitonic_sort_lds(unsigned long long* keys, int sort_n) {
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= sort_n; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < sort_n / 2; i += 256) {
+                const int lo = 2 * i - (i & (stride - 1));
+                const int hi = lo + stride;
+                const bool up = ((lo & size) == 0);
+                const unsigned long long a = keys[lo], b = keys[hi];
+                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // Full ranking of one row of S (V <= N) in LDS: N 64-bit words (rank_key(x) << 32 | entity), bitonic sort, the first kk
 // written.  The ~0 padding sorts after a NaN's word, whose low half is an entity index.  N = 8192 is 64 KiB of LDS (two
 // workgroups per CU).  RAW gives the score back from the key (desc_key is a bijection on bit patterns).
@@ -29,18 +47,7 @@ __global__ __launch_bounds__(256) void rank_rows_lds(const float* __restrict__ S
     for (int i = tid; i < sort_n; i += 256)
         keys[i] = i < V ? ((unsigned long long)rank_key<RAW>(row[i]) << 32) | (uint32_t)i : ~0ull;
     __syncthreads();
-    for (int size = 2; size <= sort_n; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < sort_n / 2; i += 256) {
-                const int lo = 2 * i - (i & (stride - 1));
-                const int hi = lo + stride;
-                const bool up = ((lo & size) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_lds(keys, sort_n);
     for (int i = tid; i < kk; i += 256) {
         const unsigned long long kv = keys[i];
         const uint32_t e = (uint32_t)kv;

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <string>
@@ -28,6 +29,7 @@
 #include "kernels_egrad.h"
 #include "kernels_ll.h"
 #include "kernels_ll_rank.h"
+#include "kernels_ll_rerank.h"
 #include "kernels_membench.h"
 #include "kernels_opt.h"
 #include "kernels_rank.h"
@@ -189,6 +191,8 @@ extern "C" {
 #include "host/api_scorer_rank.inc"
 
 #include "host/api_scorer_rerank.inc"
+
+#include "host/api_ll_rerank.inc"
 
 #include "host/api_reval.inc"
 

@@ -106,13 +106,17 @@ class QueryRanking(object):
     """What ``rank_queries`` returns for Q queries (sert_ll_rank_queries): ``idx`` / ``score`` (Q, kk) best first,
     ``joint_entropy`` (Q,), ``token_entropy[q]`` the per-token entropies of query q, ``status`` (Q,) (``HOST``: the
     joint's sum is 0 or not finite, the query must take the host path), ``k`` as asked.  ``distributions_of(q)``,
-    set by the front end, returns the (T, V_e) per-token distributions of query q as the unbatched path computes them."""
+    set by the front end, returns the (T, V_e) per-token distributions of query q as the unbatched path computes them.
+
+    ``candidates`` True (rank_queries(candidates=...), sert_ll_rank_candidates): ``idx[q]`` / ``score[q]`` are per-query
+    arrays of differing length -- query q's candidate list ranked, its best min(k, length) -- and not rows of a matrix."""
 
     DEVICE, HOST = 0, 1
 
-    def __init__(self, idx, score, joint_entropy, token_entropy, status, k=None):
+    def __init__(self, idx, score, joint_entropy, token_entropy, status, k=None, candidates=False):
         self.idx, self.score, self.joint_entropy = idx, score, joint_entropy
         self.token_entropy, self.status, self.k = token_entropy, status, k
+        self.candidates = candidates
         self.distributions_of = None
 
     def __len__(self):
@@ -121,7 +125,8 @@ class QueryRanking(object):
 
 class BatchedWordRanker(object):
     """All loglinear queries at once (additive): ``submit`` queues, ``process`` ranks every queued query with ONE
-    ``predict_fn.rank_queries`` call and hands the ranking to ``callback.process_batch``.  A query that the device
+    ``predict_fn.rank_queries`` call -- of the callback's candidate lists, when it has some (``callback.candidate_lists``) --
+    and hands the ranking to ``callback.process_batch``.  A query that the device
     cannot rank (status HOST) gets its distributions from a one-query WordBatcher of the same (batch_size, window_size)
     shape, so that predict_fn runs at the shape the unbatched path uses and the query's output is that path's."""
 
@@ -150,7 +155,13 @@ class BatchedWordRanker(object):
         if not self.pending:
             return
         payloads = [p for p, _ in self.pending]
-        ranking = self.predict_fn.rank_queries(payloads, k=self.k)
+        # a callback that re-ranks candidate lists (LogLinearCallback(candidates=...)) names the pending queries' lists: only
+        # they are ranked and copied out
+        lists = self.callback.candidate_lists([kw for _, kw in self.pending]) if hasattr(self.callback, 'candidate_lists') else None
+        if lists is None:
+            ranking = self.predict_fn.rank_queries(payloads, k=self.k)
+        else:
+            ranking = self.predict_fn.rank_queries(payloads, k=self.k, candidates=lists)
         ranking.distributions_of = lambda q: self._distributions(payloads[q])
         self.callback.process_batch(payloads, ranking, [kw for _, kw in self.pending])
         self.pending = []

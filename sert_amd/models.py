@@ -511,19 +511,30 @@ class LogLinearPredictFn(object):
             self._engine.set_tensor(_capi.T_B, self.b)
         return self._engine
 
-    def rank_queries(self, token_lists, k=None):
+    def rank_queries(self, token_lists, k=None, candidates=None):
         """Additive: rank the entities for every query of ``token_lists`` (lists of word ids) in one device call
         (sert_ll_rank_queries) -- what __call__ + scoring.LogLinearCallback.process give one query at a time, without
-        the (T, V_e) distributions leaving the device.  k None ranks every entity.  Returns an inference.QueryRanking."""
+        the (T, V_e) distributions leaving the device.  k None ranks every entity.  Returns an inference.QueryRanking.
+
+        ``candidates`` (one integer array of entity indices per query; any order, duplicates allowed): only each query's
+        listed entities are ranked (sert_ll_rank_candidates) -- the full ranking restricted to the list, same order and
+        score bits, the scores still normalised over all entities; k None ranks the whole list.  The ranking's ``idx[q]`` /
+        ``score[q]`` are then per-query arrays of differing length and its ``candidates`` flag is set."""
         if self._model is not None:
             eng = self._model._engine
         elif self._engine is not None:
             eng = self._engine
         else:       # (the id width WordBatcher's batches will have: the host path reuses this engine)
             eng = self._get_engine(np.min_scalar_type(self.R_w.shape[0] - 1).itemsize)
-        idx, score, joint_h, token_h, status, offsets = eng.ll_rank_queries(token_lists, k)
+        if candidates is not None:
+            at, idx, score, joint_h, token_h, status, offsets = eng.ll_rank_candidates(token_lists, candidates, k)
+            idx = idx.astype(np.int64)
+            idx, score = [[a[at[q]:at[q + 1]] for q in range(len(token_lists))] for a in (idx, score)]
+        else:
+            idx, score, joint_h, token_h, status, offsets = eng.ll_rank_queries(token_lists, k)
+            idx = idx.astype(np.int64)
         token_entropy = [token_h[offsets[q]:offsets[q + 1]] for q in range(len(token_lists))]
-        return inference.QueryRanking(idx.astype(np.int64), score, joint_h, token_entropy, status, k=k)
+        return inference.QueryRanking(idx, score, joint_h, token_entropy, status, k=k, candidates=candidates is not None)
 
     def __call__(self, batch, mask=None):
         batch = _as_id_array(batch)

@@ -8,7 +8,9 @@ topic_id=...)`` -- and reports a ranking through
                        Score = product over the tokens (zeros skipped),
                        renormalised; EVERY entity is ranked (query.py:199-236).
                        ``process_batch`` takes the ranking of all queries of a
-                       run from ONE device call (sert_ll_rank_queries).
+                       run from ONE device call (sert_ll_rank_queries; with
+                       candidate lists sert_ll_rank_candidates, which ranks
+                       and copies out the listed entities only).
   VectorSpaceCallback  result = (1, d_e) query projection.  Score of an entity =
                        (cosine + 1) / 2 against the L2-normalised entity table;
                        the best --top entities (or all) are ranked
@@ -67,7 +69,9 @@ def _candidate_array(candidates, topic_id):
 class LogLinearCallback(Callback):
     """``candidates`` (optional): topic id -> array of internal entity indices.  When given, the ranking of a topic is
     filtered to its candidates before ``rank_callback``: same order, same scores.  The scores stay normalised over ALL
-    entities (the model's distribution is over the whole collection), so those of a filtered ranking do not sum to one."""
+    entities (the model's distribution is over the whole collection), so those of a filtered ranking do not sum to one.
+    The batched front end asks ``candidate_lists`` for the lists and has the device rank only them
+    (sert_ll_rank_candidates): the same rank_callback calls, without the (Q, V_e) ranking crossing to the host."""
 
     def __init__(self, *args, **kwargs):
         self.candidates = kwargs.pop('candidates', None)
@@ -75,6 +79,13 @@ class LogLinearCallback(Callback):
 
     def should_average_input(self):
         return False
+
+    def candidate_lists(self, kwargs_list):
+        """The candidate list of every query of ``kwargs_list`` (their submit() keywords), None without candidates; a topic
+        without a list has an empty one."""
+        if self.candidates is None:
+            return None
+        return [_candidate_array(self.candidates, kw['topic_id']) for kw in kwargs_list]
 
     def _report(self, topic_id, idx, score):
         if self.candidates is not None:
@@ -110,9 +121,13 @@ class LogLinearCallback(Callback):
         HOST (joint sum 0 or not finite) goes through ``process`` itself, on the distributions
         ``ranking.distributions_of`` computes for it.
 
+        A candidate ranking (``ranking.candidates``: each query's list ranked by the device) is reported as it is, without
+        a second filter; its HOST queries take ``process`` and its filter as before.
+
         ``topic_projections`` holds, for a device-ranked query, its normalised joint in entity order when
         ``ranking.k`` is None, else the scores of its ranked k best in rank order (``process`` stores the
-        raveled per-token distributions)."""
+        raveled per-token distributions); for a device-ranked candidate query, whatever k, the ranked scores of its list in
+        rank order -- the joint of the unlisted entities never leaves the device."""
         etype = type(math_utils.entropy(np.full(2, 0.5, np.float32), base=2, normalize=True))
         for q, (payload, kw) in enumerate(zip(payloads, kwargs_list)):
             topic_id = kw['topic_id']
@@ -120,7 +135,8 @@ class LogLinearCallback(Callback):
                 self(payload, ranking.distributions_of(q), **kw)
                 continue
             idx, score = ranking.idx[q], ranking.score[q]
-            if ranking.k is None:
+            listed = getattr(ranking, 'candidates', False)
+            if ranking.k is None and not listed:
                 joint = np.empty(score.shape[0], dtype=score.dtype)
                 joint[idx] = score
                 self._remember(topic_id, joint)
@@ -135,7 +151,10 @@ class LogLinearCallback(Callback):
                 self.f_debug_out.write('Topic {0} {1}: {2}\n'.format(
                     topic_id, etype(ranking.joint_entropy[q]),
                     list(zip(words, [etype(h) for h in ranking.token_entropy[q]]))))
-            self._report(topic_id, idx, score)
+            if listed:
+                self.rank_callback(topic_id, idx, score)
+            else:
+                self._report(topic_id, idx, score)
 
 
 class VectorSpaceCallback(Callback):
