@@ -31,6 +31,17 @@ int sert_debug_update_counts(sert_model* m, int64_t* out, int n);
  * batch's gather (vs_gather_mean_tail: hinted steps, sert_hint_next_batch).  n <= 2.  (tests/test_gpu_tail_in_gather.py) */
 int sert_debug_tail_counts(sert_model* m, int64_t* out, int n);
 
+/* Transitions of the state one training step leaves for the next call (a run-ahead step, rows of the lazy word table that are
+ * behind, a deferred entity-table update, the sums of squares of R_e handed from step to step) since sert_create -- host
+ * counters incremented where the transition is made, test hook, no device is touched and nothing that is launched depends on
+ * them: out[0] run-ahead steps discarded (a wrong hint, explicit negatives, any call that invalidates the speculation),
+ * out[1] run-ahead steps consumed by the step they were issued for, out[2] flushes of the lazy word table (every row brought
+ * to the step counter), out[3] deferred entity-table updates a later reader of R_e waited for, and the deferring steps whose
+ * sums of squares of R_e out[4] were left by the previous step's launch, out[5] came from a read-only pass over a small table
+ * (sumsq_like_small), out[6] from one over a big table (sumsq_like_adam).  n <= 7.  tests/test_gpu_op_sequences.py asserts
+ * through this that the calls it puts between two steps met the state they are there to break. */
+int sert_debug_state_counts(sert_model* m, int64_t* out, int n);
+
 /* The loss form the LAST loglinear forward of this model launched (sert_train_batch, sert_eval_batch, ...) -- host record, test
  * hook, no device is touched: out[0] one of SERT_LL_FORM_*, out[1] its template parameter (WAVE: float4 chunks per lane 1 / 2 /
  * 4 / 8; TABLE and FUSED_ROW: threads per row 128 / 512; STREAM: 1 = 16-byte rows (V_e % 4 == 0), 0 = scalar rows), out[2] 1 for

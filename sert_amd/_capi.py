@@ -26,6 +26,9 @@ T_ACT_H, T_ACT_T, T_ACT_DA, T_ACT_DH, T_ACT_ROWLOSS = 16, 17, 18, 19, 20
 
 COMM_ID_BYTES = 128
 # SERT_LL_FORM_* of include/sert_hip_debug.h, by value
+# sert_debug_state_counts, by position
+STATE_COUNTS = ('run_ahead_discarded', 'run_ahead_consumed', 'lazy_flushes', 're_settled', 're_sq_handed', 're_sq_small',
+                're_sq_adam')
 LL_FORMS = ('none', 'wave', 'table', 'fused_row', 'stream', 'rowwise')
 # SERT_EGRAD_PATH_* / SERT_EGRAD_FIXUP_*, by value
 EGRAD_PATHS = ('none', 'bucket', 'sorted')
@@ -68,7 +71,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -463,6 +466,13 @@ class Engine(object):
         self._lib.sert_debug_tail_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
         check(self._lib.sert_debug_tail_counts(self._h, v, 2))
         return {'alone': int(v[0]), 'in_gather': int(v[1])}
+
+    def state_counts(self):
+        """sert_debug_state_counts (test hook): transitions of the state a step leaves for the next call, since creation."""
+        v = (ctypes.c_int64 * len(STATE_COUNTS))()
+        self._lib.sert_debug_state_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+        check(self._lib.sert_debug_state_counts(self._h, v, len(STATE_COUNTS)))
+        return dict(zip(STATE_COUNTS, (int(x) for x in v)))
 
     def ll_loss_form(self):
         """sert_debug_ll_loss_form (test hook): the loss form the last loglinear forward launched."""

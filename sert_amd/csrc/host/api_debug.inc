@@ -29,6 +29,12 @@ int sert_debug_tail_counts(sert_model* m, int64_t* out, int n) {
     return 0;
 }
 
+int sert_debug_state_counts(sert_model* m, int64_t* out, int n) {
+    if (!m || !out || n < 1 || n > 7) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = m->state_counts[i];
+    return 0;
+}
+
 int sert_debug_ll_loss_form(sert_model* m, int32_t* out, int n) {
     if (!m || !out || n < 1 || n > 5) SERT_FAIL("bad argument");
     if (is_vs(m)) SERT_FAIL("not a loglinear model");

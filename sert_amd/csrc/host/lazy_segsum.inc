@@ -27,6 +27,7 @@ static int ensure_rw_current(sert_model* m, int64_t batch, int64_t t_applied) {
     if (!m->rw_stale) return 0;
     if (batch >= 0 && batch == m->rw_ready_batch) return 0;
     if (t_applied < 0) t_applied = m->step;
+    ++m->state_counts[2];
     AdamArgs aa; AdadeltaArgs da;
     optimizer_args(m, std::max<int64_t>(1, t_applied), &aa, &da);
     const LazyArgs lz = lazy_args(m, t_applied, /*update=*/0);
@@ -50,6 +51,7 @@ static int settle_entity_update(sert_model* m) {
     if (m->re_pending) {
         SERT_HIP(hipStreamWaitEvent(m->stream, m->ev_re, 0));
         m->re_pending = false;
+        ++m->state_counts[3];
     }
     return 0;
 }

@@ -316,6 +316,9 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
                        m->re_sq + re_cur * re_cap);
                 m->re_sq_for[re_cur] = m->step;
                 small_needs_join = true;
+                ++m->state_counts[5];
+            } else {
+                ++m->state_counts[4];
             }
         }
         if (blocks > 0) {
@@ -342,6 +345,7 @@ static int optimizer_and_loss(sert_model* m, float* loss_dst, bool publish = fal
     } else {
         small_tensors(ss, 0xEu);
     }
+    if (P.defer_re) ++m->state_counts[m->re_sq_for[re_cur] != m->step ? 6 : 4];
     if (P.defer_re && m->re_sq_for[re_cur] != m->step) {
         // no previous deferred launch left this step's sums (first step, another schedule in between, the
         // host replaced the table): the same partials from a read-only pass, in front of the join
@@ -594,7 +598,7 @@ static int train_step_async(sert_model* m, int64_t batch_index, const int64_t* n
     const bool have_fb = negatives == nullptr && m->spec_fb_batch == batch_index && m->spec_fb_step == m->step &&
                          can_speculate_step(m);
     bool fused_pre = true;   // (a speculated step always ran its prologue on the main stream)
-    if (have_fb) m->spec_fb_batch = -1;     // consumed
+    if (have_fb) { m->spec_fb_batch = -1; ++m->state_counts[1]; }   // consumed
     else discard_run_ahead(m);              // a run-ahead for something else: discard it cleanly
     const uint32_t* bits = ds.idx_touched_bits ? ds.idx_touched_bits + (size_t)batch_index * ds.bit_words : nullptr;
     if (!have_fb) SERT_TRY(step_forward_backward(m, ds, batch_index, negatives, &fused_pre));

@@ -253,6 +253,11 @@ struct sert_model {
     sert::TailArgs tail_args;
     int tail_nb = 0;
     int64_t tail_counts[2] = {0, 0};   // tails launched [0] alone (vs_tail), [1] inside a gather: sert_debug_tail_counts
+    // transitions of the state a step hands to the next call, counted where they happen (host counters, read by
+    // sert_debug_state_counts): [0] run-aheads discarded, [1] run-aheads consumed, [2] flushes of the lazy word table,
+    // [3] deferred entity-table updates settled, [4] sums of squares of R_e handed over from the previous step's launch,
+    // [5] recomputed by sumsq_like_small, [6] recomputed by sumsq_like_adam
+    int64_t state_counts[7] = {0, 0, 0, 0, 0, 0, 0};
     float* red_loss = nullptr;    // loss partials [kOptBlocks]
     float* red_sq = nullptr;      // sumsq partials [3 * kOptBlocks]
     float* d_loss = nullptr;      // [3] loss, data term, reg term (device)

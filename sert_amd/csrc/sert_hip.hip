@@ -135,6 +135,7 @@ static bool is_vs(const sert_model* m) { return m->cfg.kind != SERT_KIND_LOGLINE
 static bool is_fs(const sert_model* m) { return m->cfg.kind == SERT_KIND_VECTORSPACE_SOFTMAX; }
 // drop whatever a previous training call ran ahead for the next one (sert_hint_next_batch)
 static void discard_run_ahead(sert_model* m) {
+    if (m->spec_fb_batch >= 0) ++m->state_counts[0];
     if (m->spec_fb_batch >= 0 && m->stream2 && m->ev_join) {
         // a discarded run-ahead may still be busy on the side stream (its entity chain is only
         // joined by the update that will now never come): order the main stream behind it
@@ -152,6 +153,7 @@ static void invalidate_speculation(sert_model* m) {
     if (m->re_pending) {       // (a deferred entity-table update: see settle_entity_update)
         (void)hipStreamWaitEvent(m->stream, m->ev_re, 0);
         m->re_pending = false;
+        ++m->state_counts[3];
     }
     m->re_sq_for[0] = m->re_sq_for[1] = -1;
     m->projected_batch = -1;
