@@ -1,0 +1,115 @@
+#!/usr/bin/env python
+"""Fold unseen entities into a trained vectorspace model, on the device, without retraining it.
+
+    python bin/prepare.py --seed 1 new_docs/*.trectext --assoc_path new_assocs --vocabulary_from meta \\
+        --window_size 4 --meta_output new_meta --data_output new.npz
+    python bin/fold_in.py --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
+        --model_output model_15_ext.bin --meta_output meta_ext
+    python bin/query.py --meta meta_ext --model model_15_ext.bin --topics topics --top 100 --run_out run
+
+The word table, the projection and the trained entity rows stay as they are; only the rows of the new entities learn
+(sert_amd.foldin.EntityFoldIn), with the NCE objective of training, on the instances of ``--data``: the ``x_train`` /
+``y_train`` / ``w_train`` of a bin/prepare.py run with ``--vocabulary_from META`` over the new entities' documents.
+``--model_output`` is a model dump with R_e extended by the new rows, ``--meta_output`` the meta with the entity index
+and the associations extended (new entity e of ``--new_meta`` gets internal index V_e + e); bin/query.py serves the pair
+unchanged.  A new entity id that ``--meta`` already knows is refused.
+"""
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from sert_amd import foldin, models, training  # noqa: E402
+from sert_amd.utils import argparse_utils as au  # noqa: E402
+from sert_amd.utils import logging_utils  # noqa: E402
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    parser.add_argument('--loglevel', type=str, default='INFO')
+    parser.add_argument('--meta', type=au.existing_file_path, required=True)
+    parser.add_argument('--model', type=au.existing_file_path, required=True)
+    parser.add_argument('--new_meta', type=au.existing_file_path, required=True)
+    parser.add_argument('--data', type=au.existing_file_path, required=True)
+    parser.add_argument('--iterations', type=au.positive_int, required=True)
+    parser.add_argument('--batch_size', type=au.positive_int, default=1024)
+    parser.add_argument('--num_negative_samples', type=au.positive_int, default=10)
+    parser.add_argument('--regularization_lambda', type=float, default=0.01)
+    parser.add_argument('--seed', type=int, default=None)
+    parser.add_argument('--device', type=int, default=0)
+    parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
+    parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
+    return parser
+
+
+def load_model(path):
+    """The pickle stream of bin/train.py, as bin/query.py reads it: namespace, predict_fn, R_w, R_e (an optimiser-state
+    trailer is not carried over: the trained rows do not move)."""
+    dump = training.read_checkpoint(path)
+    if len(dump['tables']) < 2:
+        raise RuntimeError('%s holds no entity representations: a fold-in needs a vectorspace model.' % path)
+    return [dump['args'], dump['predict_fn']] + dump['tables'][:2]
+
+
+def one_hot_training_set(path):
+    """(x, y int, w) of a bin/prepare.py npz, label distributions expanded as bin/train.py --one_hot_classes does."""
+    training_set, validation_set = training.load_data_sets(path)
+    (x, y, w), _ = training.to_one_hot(training_set, validation_set)
+    return x, np.asarray(y), w
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    try:
+        logging_utils.configure_logging(args)
+    except IOError:
+        return -1
+    if args.seed is not None:
+        np.random.seed(args.seed)
+
+    model_args, predict_fn, R_w, R_e = load_model(args.model)
+    if getattr(model_args, 'type', None) is not models.VectorSpaceLanguageModel:
+        raise RuntimeError('a fold-in needs a model trained as vectorspace (found %r).' % (getattr(model_args, 'type', None),))
+    meta = foldin.read_meta(args.meta)
+    new_meta = foldin.read_meta(args.new_meta)
+    if new_meta[1] != meta[1]:
+        raise RuntimeError('%s was not prepared with --vocabulary_from %s: the token ids differ.' % (args.new_meta, args.meta))
+    new_index = new_meta[3]
+    new_entity_ids = [new_index[e] for e in range(len(new_index))]
+    # (refuses a known entity id before anything is computed)
+    extended_meta = foldin.extend_meta(meta, new_entity_ids, dict((e, new_meta[4].get(e, [])) for e in new_entity_ids))
+
+    x, y, w = one_hot_training_set(args.data)
+    assert y.size == 0 or int(y.max()) < len(new_entity_ids)
+    window_size = meta[0].window_size
+    new_rows = models._glorot_uniform((len(new_entity_ids), R_e.shape[1]))      # as bin/train.py initialises R_e
+    fold = foldin.EntityFoldIn(
+        R_w, R_e, predict_fn.W, predict_fn.b, new_rows, (x, y, w), batch_size=args.batch_size,
+        num_negative_samples=args.num_negative_samples, regularization_lambda=args.regularization_lambda,
+        window_size=window_size, seed=args.seed, device=args.device)
+
+    mean, stddev = fold.train_error()
+    logging.info('Epoch 0: fold-in error %.6f (stddev %.6f).', mean, stddev)
+    for epoch in range(1, args.iterations + 1):
+        num_batches, loss = fold.train()
+        mean, stddev = fold.train_error()
+        logging.info('Epoch %d: %d batches, mean training loss %.6f; fold-in error %.6f (stddev %.6f).',
+                     epoch, num_batches, loss, mean, stddev)
+
+    for path in (args.model_output, args.meta_output):
+        directory = os.path.dirname(path)
+        if directory and not os.path.exists(directory):
+            os.makedirs(directory)
+    foldin.write_dump(args.model_output, foldin.extend_dump(model_args, predict_fn, R_w, R_e, fold.get_new_representations()))
+    foldin.write_meta(args.meta_output, extended_meta)
+    logging.info('Saved the extended model "%s" (%d + %d entities) and its meta "%s".', args.model_output, R_e.shape[0],
+                 len(new_entity_ids), args.meta_output)
+    fold.close()
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -44,6 +44,10 @@ def build_parser():
     p.add_argument('--no_instance_weights', action='store_true', default=False)
     p.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     p.add_argument('--data_output', type=au.nonexisting_file_path, required=True)
+    # additive (bin/fold_in.py); absent from the namespace (which is pickled into the meta) unless given
+    p.add_argument('--vocabulary_from', type=au.existing_file_path, default=argparse.SUPPRESS, metavar='META',
+                   help='take the vocabulary (token ids) of a trained model\'s meta file instead of extracting one: '
+                        'for documents of entities that are folded into that model; out-of-vocabulary tokens are dropped')
     return p
 
 

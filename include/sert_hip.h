@@ -424,6 +424,13 @@ int sert_score_topk(int device, const float* entities, int64_t num_entities, int
                     const float* proj, int64_t num_queries, int32_t k,
                     int32_t* idx_out, float* score_out);
 
+/* ---- folding unseen entities into a trained vectorspace model ----------- */
+
+/* Entities that arrive after training get rows of their own without retraining: the word table, the projection and the
+ * trained entity rows stay fixed and only the new rows learn, with the same NCE objective.  The handle and its calls are
+ * declared in sert_hip_foldin.h, which is part of this boundary. */
+#include "sert_hip_foldin.h"
+
 /* ---- data parallel (new: the reference is single-device) ---- */
 
 #define SERT_COMM_ID_BYTES 128

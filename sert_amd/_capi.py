@@ -77,6 +77,14 @@ EXPORTS = [
 ]
 # ... and include/sert_hip_reval_counted.h, which sert_hip.h includes (the evaluator by rank counting)
 EXPORTS_REVAL_COUNTED = ['sert_reval_create_counted', 'sert_reval_judged_ranks']
+# ... and include/sert_hip_foldin.h, which sert_hip.h includes too (folding unseen entities into a trained model)
+EXPORTS_FOLDIN = [
+    'sert_foldin_create', 'sert_foldin_destroy', 'sert_foldin_upload', 'sert_foldin_num_batches',
+    'sert_foldin_train_batch', 'sert_foldin_train_batches', 'sert_foldin_eval_batch', 'sert_foldin_negatives_of_step',
+    'sert_foldin_get_rows', 'sert_foldin_set_rows', 'sert_foldin_set_step', 'sert_foldin_get_step',
+    'sert_foldin_set_eval_draws', 'sert_foldin_get_eval_draws',
+]
+FOLDIN_ROWS, FOLDIN_M, FOLDIN_V = 0, 1, 2
 
 
 # int (*sert_alltoall_fn)(void* user, const float* send, const int64_t* send_offsets, const int64_t* send_counts,
@@ -102,6 +110,21 @@ class SertConfig(ctypes.Structure):
         ('keep_grads', ctypes.c_int32),
         ('deterministic', ctypes.c_int32),
         ('inference_only', ctypes.c_int32),
+        ('lambda_', ctypes.c_float),
+        ('lr', ctypes.c_float),
+        ('beta1', ctypes.c_float),
+        ('beta2', ctypes.c_float),
+        ('eps', ctypes.c_float),
+        ('seed', ctypes.c_uint64),
+    ]
+
+
+class SertFoldInConfig(ctypes.Structure):
+    """sert_foldin_config (include/sert_hip_foldin.h)."""
+    _fields_ = [
+        ('struct_size', ctypes.c_uint32),
+        ('batch_size', ctypes.c_int32),
+        ('num_negatives', ctypes.c_int32),
         ('lambda_', ctypes.c_float),
         ('lr', ctypes.c_float),
         ('beta1', ctypes.c_float),
@@ -164,6 +187,23 @@ def load():
     lib.sert_reval_judged_ranks.argtypes = [vp, fp]
     lib.sert_reval_run.argtypes = [vp, fp, fp, fp, fp]
     lib.sert_reval_destroy.argtypes = [vp]
+    lib.sert_foldin_create.argtypes = [vp, i32, fp, ctypes.POINTER(SertFoldInConfig), ctypes.POINTER(vp)]
+    lib.sert_foldin_destroy.argtypes = [vp]
+    lib.sert_foldin_upload.argtypes = [vp, fp, fp, fp, i64]
+    lib.sert_foldin_num_batches.argtypes = [vp]
+    lib.sert_foldin_num_batches.restype = i64
+    lib.sert_foldin_train_batch.argtypes = [vp, i64, fp, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_foldin_train_batches.argtypes = [vp, fp, i64, fp]
+    lib.sert_foldin_eval_batch.argtypes = [vp, i64, fp, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_foldin_negatives_of_step.argtypes = [vp, i64, ctypes.c_int, fp]
+    lib.sert_foldin_get_rows.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_foldin_set_rows.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_foldin_set_step.argtypes = [vp, i64]
+    lib.sert_foldin_get_step.argtypes = [vp]
+    lib.sert_foldin_get_step.restype = i64
+    lib.sert_foldin_set_eval_draws.argtypes = [vp, i64]
+    lib.sert_foldin_get_eval_draws.argtypes = [vp]
+    lib.sert_foldin_get_eval_draws.restype = i64
     lib.sert_score_topk.argtypes = [ctypes.c_int, fp, i64, i32, fp, i64, i32, fp, fp]
     lib.sert_scorer_create.argtypes = [ctypes.c_int, fp, i64, i32, ctypes.POINTER(vp)]
     lib.sert_scorer_destroy.argtypes = [vp]
@@ -1034,6 +1074,107 @@ class RetrievalEval(object):
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
             self._lib.sert_reval_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FoldIn(object):
+    """Owner of one sert_foldin handle (include/sert_hip_foldin.h): ``num_new`` entity rows learnt on top of the frozen
+    parameters of ``engine`` (a vectorspace Engine), which are copied at construction -- the engine may train on or be
+    closed afterwards."""
+
+    def __init__(self, engine, new_rows_init, batch_size, num_negatives, lambda_, lr=1e-3, beta1=0.9, beta2=0.999,
+                 eps=1e-8, seed=0):
+        self._lib = load()
+        self._h = None
+        rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != engine.cfg.entity_dim:
+            raise SertError('new_rows_init must be (num_new, entity_dim)')
+        c = SertFoldInConfig()
+        c.struct_size = ctypes.sizeof(SertFoldInConfig)
+        c.batch_size, c.num_negatives, c.lambda_ = int(batch_size), int(num_negatives), float(lambda_)
+        c.lr, c.beta1, c.beta2, c.eps, c.seed = float(lr), float(beta1), float(beta2), float(eps), int(seed)
+        self.cfg = c
+        self.num_new, self.entity_dim = int(rows.shape[0]), int(rows.shape[1])
+        self.num_entities = int(engine.cfg.num_entities)
+        self.window_size = int(engine.cfg.window_size)
+        h = ctypes.c_void_p()
+        check(self._lib.sert_foldin_create(engine._h, self.num_new, rows.ctypes.data if rows.size else None,
+                                           ctypes.byref(c), ctypes.byref(h)))
+        self._h = h
+
+    def upload(self, x, y, w=None):
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if x.ndim != 2 or x.shape[1] != self.window_size or y.shape != (x.shape[0],):
+            raise SertError('x must be (M, window_size) and y (M,)')
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != y.shape:
+                raise SertError('w must be (M,)')
+        check(self._lib.sert_foldin_upload(self._h, x.ctypes.data, y.ctypes.data, _addr(w), x.shape[0]))
+
+    def num_batches(self):
+        return int(self._lib.sert_foldin_num_batches(self._h))
+
+    def train_batch(self, batch_index, negatives=None):
+        loss = ctypes.c_float()
+        if negatives is not None:
+            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
+            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
+        check(self._lib.sert_foldin_train_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
+        return np.float32(loss.value)
+
+    def train_batches(self, batch_indices):
+        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
+        out = np.empty(idx.size, dtype=np.float32)
+        check(self._lib.sert_foldin_train_batches(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
+        return out
+
+    def eval_batch(self, batch_index, negatives=None):
+        loss = ctypes.c_float()
+        if negatives is not None:
+            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
+            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
+        check(self._lib.sert_foldin_eval_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
+        return np.float32(loss.value)
+
+    def negatives_of_step(self, position, evaluation=False):
+        """(B, z) int64 in [0, num_entities + num_new): what the device sampler draws at training position `position`
+        (= get_step() before the step) or for the `position`-th evaluation draw."""
+        out = np.empty((self.cfg.batch_size, self.cfg.num_negatives), dtype=np.int64)
+        check(self._lib.sert_foldin_negatives_of_step(self._h, int(position), int(bool(evaluation)), out.ctypes.data))
+        return out
+
+    def get_rows(self, which=FOLDIN_ROWS):
+        out = np.empty((self.num_new, self.entity_dim), dtype=np.float32)
+        check(self._lib.sert_foldin_get_rows(self._h, int(which), out.ctypes.data, out.size))
+        return out
+
+    def set_rows(self, which, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        check(self._lib.sert_foldin_set_rows(self._h, int(which), a.ctypes.data, a.size))
+
+    def set_step(self, t):
+        check(self._lib.sert_foldin_set_step(self._h, int(t)))
+
+    def get_step(self):
+        return int(self._lib.sert_foldin_get_step(self._h))
+
+    def set_eval_draws(self, n):
+        check(self._lib.sert_foldin_set_eval_draws(self._h, int(n)))
+
+    def get_eval_draws(self):
+        return int(self._lib.sert_foldin_get_eval_draws(self._h))
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sert_foldin_destroy(self._h)
             self._h = None
 
     def __del__(self):

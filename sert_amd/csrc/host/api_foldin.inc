@@ -1,0 +1,457 @@
+// Part of sert_hip.hip (one translation unit; included there, inside its extern "C" block): C ABI: folding unseen entities
+// into a trained vectorspace model (include/sert_hip_foldin.h: sert_foldin_*; kernels_foldin.h).  The handle copies the
+// model's parameters when it is created and runs on a stream of its own: it shares nothing with the model's step schedule.
+
+struct sert_foldin {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    sert_foldin_config cfg;
+    int Vw = 0, Ve = 0, N = 0, dw = 0, de = 0, n = 0;
+    // the frozen snapshot
+    float *rw = nullptr, *W = nullptr, *b = nullptr, *re = nullptr;
+    // the new rows, Adam's moments, the gradient
+    float *E = nullptr, *m1 = nullptr, *m2 = nullptr, *G = nullptr;
+    // the uploaded instances and their projections
+    int64_t M = 0;
+    int32_t* y = nullptr;
+    float* w = nullptr;
+    float* T = nullptr;              // (M, d_e)
+    // per-step scratch
+    int32_t* neg = nullptr;          // (B, z)
+    int64_t* neg_stage = nullptr;    // (B, z) host-supplied negatives
+    float* coef = nullptr;           // (B, 1 + z)
+    int32_t *key = nullptr, *key_sorted = nullptr, *pair_sorted = nullptr, *k_tmp = nullptr, *v_tmp = nullptr;
+    int32_t *sort_hist = nullptr, *sort_bin_total = nullptr;
+    int sort_bits = 1;
+    int32_t* run_bounds = nullptr;   // run_start (round_up(N, 4)) then run_end (the same)
+    float *ehead = nullptr, *etail = nullptr;   // (chunks, d_e) carries
+    float* rowloss = nullptr;        // (B)
+    float* red_loss = nullptr;       // per-workgroup loss partials of foldin_nce
+    float* red_sq = nullptr;         // [kOptBlocks] sums of squares of E
+    float* d_loss = nullptr;         // [3]
+    float* d_losses = nullptr;       // multi-step loss ring
+    int64_t d_losses_cap = 0;
+    int64_t step = 0, eval_draws = 0;
+};
+
+int sert_foldin_destroy(sert_foldin* f) {
+    if (!f) return 0;
+    if (f->device >= 0) {
+        (void)hipSetDevice(f->device);
+        if (f->stream) (void)hipStreamSynchronize(f->stream);
+    }
+    for (void* p : {(void*)f->rw, (void*)f->W, (void*)f->b, (void*)f->re, (void*)f->E, (void*)f->m1, (void*)f->m2, (void*)f->G,
+                    (void*)f->y, (void*)f->w, (void*)f->T, (void*)f->neg, (void*)f->neg_stage, (void*)f->coef, (void*)f->key,
+                    (void*)f->key_sorted, (void*)f->pair_sorted, (void*)f->k_tmp, (void*)f->v_tmp, (void*)f->sort_hist,
+                    (void*)f->sort_bin_total, (void*)f->run_bounds, (void*)f->ehead, (void*)f->etail, (void*)f->rowloss,
+                    (void*)f->red_loss, (void*)f->red_sq, (void*)f->d_loss, (void*)f->d_losses})
+        (void)hipFree(p);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+    return 0;
+}
+
+static int foldin_create(sert_foldin* f, sert_model* m, int32_t num_new, const float* init_rows, const sert_foldin_config* cfg) {
+    const auto& c = m->cfg;
+    // ---- validation: everything the kernels index with is checked here ----
+    if (c.kind == SERT_KIND_LOGLINEAR) SERT_FAIL("a fold-in needs a vectorspace model: a loglinear model has no entity rows to add");
+    if (c.kind != SERT_KIND_VECTORSPACE)
+        SERT_FAIL("a fold-in needs the NCE vectorspace model: the full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX) is not supported");
+    if (m->comm || m->host_ar || m->world > 1)
+        SERT_FAIL("a fold-in of a data-parallel model (a communicator is attached) is not supported");
+    if (num_new < 1) SERT_FAIL("a fold-in needs at least one new entity (num_new >= 1)");
+    if (!init_rows) SERT_FAIL("null argument");
+    if (cfg->batch_size < 1 || cfg->num_negatives < 1) SERT_FAIL("a fold-in needs batch_size >= 1 and num_negatives >= 1");
+    if (!(cfg->lambda_ >= 0.f)) SERT_FAIL("regularization lambda must be >= 0");
+    if (c.entity_dim > 512) SERT_FAIL("entity_dim > 512 is not supported");
+    if ((int64_t)c.num_entities + num_new > INT32_MAX) SERT_FAIL("more than 2^31 - 1 rows in the extended entity table");
+    if ((int64_t)cfg->batch_size * (cfg->num_negatives + 1) > ((int64_t)1 << 30)) SERT_FAIL("batch_size * (num_negatives + 1) > 2^30");
+    SERT_HIP(hipSetDevice(c.device));
+    f->device = c.device; f->cfg = *cfg;
+    f->Vw = c.vocab_size; f->Ve = c.num_entities; f->N = num_new; f->dw = c.word_dim; f->de = c.entity_dim; f->n = c.window_size;
+    const int B = cfg->batch_size, z = cfg->num_negatives, de = f->de, N = f->N;
+    const size_t n_e = (size_t)N * de;
+    // the parameters as a reader must see them (sert_get_tensor, sert_reval_run): every lazily updated word-table row brought
+    // to the model's step, a deferred entity-table update landed
+    SERT_TRY(ensure_full_rw(m));
+    SERT_TRY(ensure_rw_current(m, -1));
+    if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
+    if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
+    SERT_TRY(settle_entity_update(m));
+    flush_pending_tail(m);
+    SERT_TRY(dmalloc(&f->rw, m->n_rw));
+    SERT_TRY(dmalloc(&f->W, m->n_w));
+    SERT_TRY(dmalloc(&f->b, m->n_b));
+    SERT_TRY(dmalloc(&f->re, std::max<size_t>(m->n_re, 4)));
+    SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    if (m->n_re) SERT_HIP(hipMemcpyAsync(f->re, m->re, m->n_re * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipStreamCreate(&f->stream));
+    hipStream_t s = f->stream;
+    SERT_TRY(dmalloc(&f->E, n_e));
+    SERT_TRY(dzalloc(&f->m1, n_e, s));
+    SERT_TRY(dzalloc(&f->m2, n_e, s));
+    SERT_TRY(dmalloc(&f->G, n_e));
+    SERT_HIP(hipMemcpyAsync(f->E, init_rows, n_e * sizeof(float), hipMemcpyHostToDevice, s));
+    const size_t total = (size_t)B * (z + 1);
+    SERT_TRY(dmalloc(&f->neg, (size_t)B * z));
+    SERT_TRY(dmalloc(&f->neg_stage, (size_t)B * z));
+    SERT_TRY(dmalloc(&f->coef, total));
+    SERT_TRY(dmalloc(&f->key, total));
+    SERT_TRY(dmalloc(&f->key_sorted, total));
+    SERT_TRY(dmalloc(&f->pair_sorted, total));
+    // keys lie in [0, N] (N: the sentinel of a pair on a frozen row)
+    f->sort_bits = 1;
+    while (((int64_t)1 << f->sort_bits) <= (int64_t)N) ++f->sort_bits;
+    if (f->sort_bits > kSortMaxBits) {
+        SERT_TRY(dmalloc(&f->k_tmp, total));
+        SERT_TRY(dmalloc(&f->v_tmp, total));
+    }
+    SERT_TRY(dmalloc(&f->sort_hist, (size_t)kSortMaxBins * cdiv((int64_t)total, kSortTile)));
+    SERT_TRY(dmalloc(&f->sort_bin_total, (size_t)kSortMaxBins));
+    SERT_TRY(dzalloc(&f->run_bounds, 2 * round_up((size_t)N, 4), s));
+    const size_t chunks = (size_t)cdiv((int64_t)total, kEChunk);
+    SERT_TRY(dmalloc(&f->ehead, chunks * de));
+    SERT_TRY(dmalloc(&f->etail, chunks * de));
+    SERT_TRY(dmalloc(&f->rowloss, (size_t)B));
+    SERT_TRY(dmalloc(&f->red_loss, (size_t)cdiv(B, 16)));
+    SERT_TRY(dmalloc(&f->red_sq, (size_t)kOptBlocks));
+    SERT_TRY(dmalloc(&f->d_loss, (size_t)3));
+    SERT_HIP(hipStreamSynchronize(s));             // (init_rows is borrowed for the call only)
+    SERT_HIP(hipStreamSynchronize(m->stream));     // (the snapshot is complete: the model may train or go away)
+    return 0;
+}
+
+int sert_foldin_create(sert_model* m, int32_t num_new, const float* init_rows, const sert_foldin_config* cfg, sert_foldin** out) {
+    refresh_gemm_choice();
+    if (!m || !cfg || !out) SERT_FAIL("null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(sert_foldin_config)) SERT_FAIL("sert_foldin_config size mismatch (ABI)");
+    sert_foldin* f = new sert_foldin();
+    const int rc = foldin_create(f, m, num_new, init_rows, cfg);
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        sert_foldin_destroy(f);
+        g_last_error = keep;
+        return rc;
+    }
+    *out = f;
+    return 0;
+}
+
+int sert_foldin_upload(sert_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
+    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+    const int n = f->n, dw = f->dw, de = f->de;
+    // host-side validation: no kernel is launched on bad ids
+    for (int64_t i = 0; i < M; ++i)
+        if (y[i] < 0 || y[i] >= f->N) SERT_FAIL("fold-in label out of range [0, num_new)");
+    for (int64_t i = 0; i < M * n; ++i)
+        if (x[i] < 0 || x[i] >= f->Vw) SERT_FAIL("token id out of range [0, vocab_size)");
+    SERT_HIP(hipSetDevice(f->device));
+    hipStream_t s = f->stream;
+    SERT_HIP(hipStreamSynchronize(s));
+    (void)hipFree(f->y); (void)hipFree(f->w); (void)hipFree(f->T);
+    f->y = nullptr; f->w = nullptr; f->T = nullptr; f->M = 0;
+    if (M == 0) return 0;
+    SERT_TRY(dmalloc(&f->y, (size_t)M));
+    SERT_TRY(dmalloc(&f->w, (size_t)M));
+    SERT_TRY(dmalloc(&f->T, (size_t)M * de));
+    SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (w) {
+        SERT_HIP(hipMemcpyAsync(f->w, w, (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
+    } else {
+        const std::vector<float> ones((size_t)M, 1.0f);
+        SERT_HIP(hipMemcpyAsync(f->w, ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipStreamSynchronize(s));
+    }
+    // T = tanh(h W + b) once, by the model's forward (vs_project: vs_gather_mean, the projection GEMM), a slab of rows at a time
+    const int64_t slab = std::min<int64_t>(M, 65536);
+    uint32_t* dx = nullptr;
+    float* H = nullptr;
+    auto body = [&]() -> int {
+        SERT_TRY(dmalloc(&dx, (size_t)slab * n));
+        SERT_TRY(dmalloc(&H, (size_t)slab * dw));
+        for (int64_t r0 = 0; r0 < M; r0 += slab) {
+            const int rows = (int)std::min<int64_t>(slab, M - r0);
+            SERT_HIP(hipMemcpyAsync(dx, x + (size_t)r0 * n, (size_t)rows * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            if (dw % 4 == 0)
+                launch((vs_gather_mean<uint32_t, 4>), dim3(grid_for((int64_t)rows * dw / 4, 256, 1 << 20)), dim3(256), 0, s,
+                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
+            else
+                launch((vs_gather_mean<uint32_t, 1>), dim3(grid_for((int64_t)rows * dw, 256, 1 << 20)), dim3(256), 0, s,
+                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
+            launch_gemm<false, false, EPI_BIAS_TANH>(s, H, f->W, f->T + (size_t)r0 * de, f->b, rows, de, dw, dw, de, de);
+        }
+        SERT_HIP(hipGetLastError());
+        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w are borrowed for the call only)
+        return 0;
+    };
+    const int rc = body();
+    (void)hipFree(dx); (void)hipFree(H);
+    if (rc != 0) return rc;
+    f->M = M;
+    return 0;
+}
+
+int64_t sert_foldin_num_batches(sert_foldin* f) { return f ? f->M / f->cfg.batch_size : -1; }
+
+// the step's negatives into f->neg: the caller's (validated before anything is launched) or the Philox sampler's
+static int foldin_negatives(sert_foldin* f, const int64_t* negatives, uint64_t stream_pos) {
+    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
+    const int64_t ext = (int64_t)f->Ve + f->N;
+    if (negatives) {
+        for (int64_t i = 0; i < count; ++i)
+            if (negatives[i] < 0 || negatives[i] >= ext) SERT_FAIL("negative sample out of range [0, num_entities + num_new)");
+        SERT_HIP(hipMemcpyAsync(f->neg_stage, negatives, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+        launch(convert_i64_to_i32, dim3(grid_for(count)), dim3(256), 0, f->stream, (const int64_t*)f->neg_stage, f->neg, count);
+    } else {
+        // (even = training draws, odd = evaluation draws, as the model's sampler)
+        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, f->stream, f->neg, count, (int64_t)0,
+               (uint32_t)ext, f->cfg.seed, stream_pos, (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
+    }
+    return 0;
+}
+
+// the loss kernel on batch `batch` (train: weighted, coef and keys written); *parts / *n_parts: the loss partials it left
+static int foldin_loss(sert_foldin* f, int64_t batch, bool train, const float** parts, int* n_parts) {
+    const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de;
+    const size_t row0 = (size_t)batch * B;
+    const float* T = f->T + row0 * de;
+    const int32_t* y = f->y + row0;
+    const float* w = train ? f->w + row0 : (const float*)nullptr;
+    const float inv_batch = 1.0f / (float)B;
+    hipStream_t s = f->stream;
+#define SERT_FI_ARGS T, (const float*)f->re, (const float*)f->E, y, (const int32_t*)f->neg, w, f->coef, f->key, f->rowloss, B, z, de, f->Ve, f->N, inv_batch
+    if (de % 4 == 0) {
+        const dim3 grid(cdiv(B, 16)), block(256);
+#define SERT_FI_CASE(K)                                                                                   \
+    case K:                                                                                               \
+        if (train) launch((foldin_nce<K, true>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);           \
+        else launch((foldin_nce<K, false>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);                \
+        break;
+        switch (cdiv(de / 4, 16)) {
+            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
+            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
+            default: SERT_FAIL("entity_dim > 512 is not supported");
+        }
+#undef SERT_FI_CASE
+        *parts = f->red_loss; *n_parts = cdiv(B, 16);
+    } else {
+        const dim3 grid(cdiv(B, 4)), block(256);
+#define SERT_FI_CASE(K)                                                                                   \
+    case K:                                                                                               \
+        if (train) launch((foldin_nce_scalar<K, true>), grid, block, 0, s, SERT_FI_ARGS);                 \
+        else launch((foldin_nce_scalar<K, false>), grid, block, 0, s, SERT_FI_ARGS);                      \
+        break;
+        switch (cdiv(de, 64)) {
+            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
+            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
+            default: SERT_FAIL("entity_dim > 512 is not supported");
+        }
+#undef SERT_FI_CASE
+        *parts = f->rowloss; *n_parts = B;     // (no workgroup partials on this path: the rows' losses themselves)
+    }
+#undef SERT_FI_ARGS
+    return 0;
+}
+
+// dE (data term) into f->G: stable sort of the (key, pair) entries, chunked reduce that stops at the sentinel, carry fix-up
+static int foldin_grad(sert_foldin* f, int64_t batch) {
+    const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de, N = f->N;
+    const int total = B * (z + 1);
+    hipStream_t s = f->stream;
+    const float* T = f->T + (size_t)batch * B * de;
+    const int bits = f->sort_bits;
+    const int passes = cdiv(bits, kSortMaxBits);
+    const int width = cdiv(bits, passes);
+    const int nbound = (int)round_up((size_t)N, 4);
+    int32_t* run_start = f->run_bounds;
+    int32_t* run_end = f->run_bounds + nbound;
+    const int32_t* kin = f->key;
+    const int32_t* vin = nullptr;      // value of element i is i
+    for (int p = 0; p < passes; ++p) {
+        const int shift = p * width;
+        const int nb = std::min(width, bits - shift);
+        const bool to_final = ((passes - 1 - p) % 2) == 0;
+        int32_t* kout = to_final ? f->key_sorted : f->k_tmp;
+        int32_t* vout = to_final ? f->pair_sorted : f->v_tmp;
+        // (first digit: also clears the run bounds, which the reduce writes only for the rows it meets)
+        csort_pass(s, kin, vin, kout, vout, total, shift, nb, f->sort_hist, f->sort_bin_total,
+                   p == 0 ? run_start : (int32_t*)nullptr, p == 0 ? 2 * nbound : 0);
+        kin = kout;
+        vin = vout;
+    }
+    const int chunks = cdiv(total, kEChunk);
+    const dim3 cgrid(cdiv(chunks, 16)), blk(256);
+#define SERT_FI_ARGS (const int32_t*)f->key_sorted, (const int32_t*)f->pair_sorted, (const float*)f->coef, T, total, z + 1, de, N, \
+                 f->G, f->ehead, f->etail, run_start, run_end
+    if (de % 4 == 0) {
+        const int nch = cdiv(de / 4, 16);
+        if (nch <= 1)      launch((foldin_chunk_reduce<4, 1>), cgrid, blk, 0, s, SERT_FI_ARGS);
+        else if (nch <= 2) launch((foldin_chunk_reduce<4, 2>), cgrid, blk, 0, s, SERT_FI_ARGS);
+        else if (nch <= 5) launch((foldin_chunk_reduce<4, 5>), cgrid, blk, 0, s, SERT_FI_ARGS);
+        else               launch((foldin_chunk_reduce<4, 8>), cgrid, blk, 0, s, SERT_FI_ARGS);
+    } else {
+        launch((foldin_chunk_reduce<1, 4>), cgrid, blk, 0, s, SERT_FI_ARGS);
+    }
+#undef SERT_FI_ARGS
+    // the fix-up over the N new rows only (kernels_egrad.h, as it is): rows no pair hit get a zero gradient row, runs that
+    // cross chunks their carries in chunk order.  Few rows: one workgroup per row (long runs).
+    const bool few = N < 256;
+    if (de % 4 == 0) {
+        if (few) launch((egrad_fixup_wg<4>), dim3(N), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
+        else launch((egrad_fixup<4>), dim3(cdiv(N, 4)), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
+    } else {
+        if (few) launch((egrad_fixup_wg<1>), dim3(N), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
+        else launch((egrad_fixup<1>), dim3(cdiv(N, 4)), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
+    }
+    return 0;
+}
+
+static int foldin_check_batch(sert_foldin* f, int64_t batch) {
+    if (!f) SERT_FAIL("null argument");
+    if (!f->T) SERT_FAIL("no fold-in instances uploaded (sert_foldin_upload)");
+    if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
+    return 0;
+}
+
+// one step enqueued on the handle's stream; dst: 3 floats on the device (finalize_loss: loss, data term, regulariser)
+static int foldin_step_async(sert_foldin* f, int64_t batch, const int64_t* negatives, float* dst) {
+    const auto& c = f->cfg;
+    const int B = c.batch_size;
+    hipStream_t s = f->stream;
+    SERT_TRY(foldin_negatives(f, negatives, (uint64_t)f->step * 2));
+    const float* parts = nullptr;
+    int n_parts = 0;
+    SERT_TRY(foldin_loss(f, batch, true, &parts, &n_parts));
+    SERT_TRY(foldin_grad(f, batch));
+    // Adam over E with the model's arithmetic (adam_l2: L2 folded into the gradient, sum of squares of the values BEFORE
+    // the update from the same pass); a_t on the host in fp32 (optimizer_args)
+    f->step += 1;
+    const float tf = (float)f->step;
+    AdamArgs aa{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr * sqrtf(1.0f - powf(c.beta2, tf)) / (1.0f - powf(c.beta1, tf)),
+                c.beta1, c.beta2, c.eps};
+    const size_t n_e = (size_t)f->N * f->de;
+    const int nb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)n_e, 4), 256)));
+    launch((adam_l2<false>), dim3(nb), dim3(256), 0, s, f->E, f->G, f->m1, f->m2, n_e, aa, f->red_sq, (const uint32_t*)nullptr,
+           1u, (int)kRowsAll, (float*)nullptr);
+    launch(finalize_loss, dim3(1), dim3(256), 0, s, parts, n_parts, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0,
+           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    return 0;
+}
+
+int sert_foldin_train_batch(sert_foldin* f, int64_t batch, const int64_t* negatives, float* loss_out) {
+    SERT_TRY(foldin_check_batch(f, batch));
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_TRY(foldin_step_async(f, batch, negatives, f->d_loss));
+    float host[3] = {0.f, 0.f, 0.f};
+    SERT_HIP(hipGetLastError());
+    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (loss_out) *loss_out = host[0];
+    return 0;
+}
+
+int sert_foldin_train_batches(sert_foldin* f, const int64_t* batches, int64_t count, float* losses_out) {
+    if (!f || count < 0 || (count > 0 && !batches)) SERT_FAIL("bad argument");
+    for (int64_t i = 0; i < count; ++i) SERT_TRY(foldin_check_batch(f, batches[i]));    // (before anything is enqueued)
+    if (count == 0) return 0;
+    SERT_HIP(hipSetDevice(f->device));
+    if (count > f->d_losses_cap) {
+        SERT_HIP(hipStreamSynchronize(f->stream));
+        (void)hipFree(f->d_losses);
+        f->d_losses = nullptr; f->d_losses_cap = 0;
+        SERT_TRY(dmalloc(&f->d_losses, (size_t)count * 3));
+        f->d_losses_cap = count;
+    }
+    for (int64_t i = 0; i < count; ++i) SERT_TRY(foldin_step_async(f, batches[i], nullptr, f->d_losses + 3 * i));
+    SERT_HIP(hipGetLastError());
+    std::vector<float> tmp((size_t)count * 3);
+    SERT_HIP(hipMemcpyAsync(tmp.data(), f->d_losses, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (losses_out)
+        for (int64_t i = 0; i < count; ++i) losses_out[i] = tmp[(size_t)3 * i];
+    return 0;
+}
+
+int sert_foldin_eval_batch(sert_foldin* f, int64_t batch, const int64_t* negatives, float* loss_out) {
+    SERT_TRY(foldin_check_batch(f, batch));
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_TRY(foldin_negatives(f, negatives, (uint64_t)f->eval_draws * 2 + 1));
+    if (!negatives) ++f->eval_draws;
+    const float* parts = nullptr;
+    int n_parts = 0;
+    SERT_TRY(foldin_loss(f, batch, false, &parts, &n_parts));
+    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, parts, n_parts, parts, 0, 1.0f / (float)f->cfg.batch_size, 0.0f,
+           f->d_loss, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    float host[3] = {0.f, 0.f, 0.f};
+    SERT_HIP(hipGetLastError());
+    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (loss_out) *loss_out = host[0];
+    return 0;
+}
+
+int sert_foldin_negatives_of_step(sert_foldin* f, int64_t position, int evaluation, int64_t* out) {
+    if (!f || !out || position < 0) SERT_FAIL("bad argument");
+    SERT_HIP(hipSetDevice(f->device));
+    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
+    int32_t* tmp = nullptr;
+    SERT_HIP(hipMalloc((void**)&tmp, (size_t)count * sizeof(int32_t)));
+    // a stream of its own: nothing of the handle's state is touched
+    hipStream_t st = nullptr;
+    if (hipStreamCreate(&st) != hipSuccess) { (void)hipFree(tmp); SERT_FAIL("hipStreamCreate failed"); }
+    launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count, (int64_t)0,
+           (uint32_t)((int64_t)f->Ve + f->N), f->cfg.seed, (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0,
+           (uint4*)nullptr, (size_t)0);
+    std::vector<int32_t> host((size_t)count);
+    const hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    (void)hipFree(tmp);
+    if (e != hipSuccess || e2 != hipSuccess) SERT_FAIL("reading the negatives back failed");
+    for (int64_t i = 0; i < count; ++i) out[i] = host[(size_t)i];
+    return 0;
+}
+
+static float* foldin_rows_ref(sert_foldin* f, int which) {
+    return which == SERT_FOLDIN_ROWS ? f->E : which == SERT_FOLDIN_M ? f->m1 : which == SERT_FOLDIN_V ? f->m2 : nullptr;
+}
+
+int sert_foldin_get_rows(sert_foldin* f, int which, float* host, size_t count) {
+    if (!f || !host) SERT_FAIL("null argument");
+    float* p = foldin_rows_ref(f, which);
+    if (!p) SERT_FAIL("which must be SERT_FOLDIN_ROWS, SERT_FOLDIN_M or SERT_FOLDIN_V");
+    if (count != (size_t)f->N * f->de) SERT_FAIL("element count mismatch");
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_HIP(hipMemcpyAsync(host, p, count * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int sert_foldin_set_rows(sert_foldin* f, int which, const float* host, size_t count) {
+    if (!f || !host) SERT_FAIL("null argument");
+    float* p = foldin_rows_ref(f, which);
+    if (!p) SERT_FAIL("which must be SERT_FOLDIN_ROWS, SERT_FOLDIN_M or SERT_FOLDIN_V");
+    if (count != (size_t)f->N * f->de) SERT_FAIL("element count mismatch");
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int sert_foldin_set_step(sert_foldin* f, int64_t t) {
+    if (!f || t < 0) SERT_FAIL("bad argument");
+    f->step = t;
+    return 0;
+}
+int64_t sert_foldin_get_step(sert_foldin* f) { return f ? f->step : -1; }
+int sert_foldin_set_eval_draws(sert_foldin* f, int64_t n) {
+    if (!f || n < 0) SERT_FAIL("bad argument");
+    f->eval_draws = n;
+    return 0;
+}
+int64_t sert_foldin_get_eval_draws(sert_foldin* f) { return f ? f->eval_draws : -1; }

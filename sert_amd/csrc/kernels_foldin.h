@@ -1,0 +1,265 @@
+// Folding unseen entities into a trained vectorspace model (host/api_foldin.inc; DESIGN.md, "Folding in unseen
+// entities"), gfx950.
+//
+// The word table, the projection and the V_e trained entity rows are FROZEN; only the N new rows E learn, with the NCE
+// objective of the vectorspace step over the extended table Ext = concat(R_e, E) (new entity e is row V_e + e).  The
+// projections T = tanh(h W + b) of the fold-in instances therefore never change: they are computed once, at upload, by the
+// model's own forward (vs_gather_mean + the projection GEMM).  A step is
+//   foldin_nce            the loss kernel of kernels_vs.h (vs_nce / vs_nce_scalar) on a two-part table, WITHOUT the da it
+//                         writes for the layers below (nothing below the projection learns); TRAIN leaves coef[i, j] and a
+//                         KEY per pair: cand - V_e for a pair that hits a new row, the sentinel N for one that hits a frozen row
+//   csort_pass            stable sort of the B (1 + z) (key, pair) entries (kernels_sort.h, as it is)
+//   foldin_chunk_reduce   egrad_chunk_reduce (kernels_egrad.h) that stops at the sentinel: the sentinel run -- most of the
+//                         pairs -- is the END of the sorted order, so a chunk that starts inside it leaves after one load
+//   egrad_fixup(_wg)      the carries of the runs that cross chunks, over the N new rows only (kernels_egrad.h, as it is)
+//   adam_l2               Adam + L2 + sum of squares over E (kernels_opt.h, as it is), finalize_loss
+// Order-fixed throughout, no floating-point atomic: a fold-in is bit-reproducible.
+#pragma once
+#include "common.h"
+#include "kernels_egrad.h"
+#include "kernels_vs.h"
+
+namespace sert {
+
+// the row of Ext a candidate id names: frozen rows first, the new rows behind them
+__device__ __forceinline__ const float* foldin_row(const float* __restrict__ Re, const float* __restrict__ E, int Ve, int e,
+                                                   int de) {
+    return e < Ve ? Re + (size_t)e * de : E + (size_t)(e - Ve) * de;
+}
+
+// vs_nce's row layout: 16 lanes per instance, lane l owns the float4 column chunks l, l + 16, ...; one candidate after
+// the other, so any z >= 1.  T: the (B, d_e) projections of THIS batch (the host passes the batch's first row).
+//   u_j = <Ext[c_j], clip(t)>, s_j = clip(sigmoid(u_j)), loss = -(log s_0 + sum_{j>0} log(1 - s_j))
+//   TRAIN: coef[i, j] = d loss / d u_j * w_i / B (inclusive clip mask), key[i, j] = c_j >= V_e ? c_j - V_e : N
+//   rowloss[i] = (TRAIN ? w_i : 1) * loss; wg_loss[blockIdx.x] = the workgroup's sixteen row losses added in row order
+template <int NCH, bool TRAIN>
+__global__ __launch_bounds__(256) void foldin_nce(const float* __restrict__ T, const float* __restrict__ Re,
+                                                  const float* __restrict__ E, const int32_t* __restrict__ y,
+                                                  const int32_t* __restrict__ neg, const float* __restrict__ w,
+                                                  float* __restrict__ coef, int32_t* __restrict__ key,
+                                                  float* __restrict__ rowloss, int B, int z, int de, int Ve, int N,
+                                                  float inv_batch, float* __restrict__ wg_loss) {
+    __shared__ float wg_red[16];
+    const int l = threadIdx.x & 15;
+    // (rows past the end of a ragged last workgroup: computed on a clamped row, never stored -- no return in front of the
+    //  barrier below)
+    const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool valid = i_raw < B;
+    const int i = valid ? i_raw : B - 1;
+    const int chunks = de >> 2;  // de % 4 == 0 on this path
+    float4 t[NCH], p[NCH];
+#pragma unroll
+    for (int q = 0; q < NCH; ++q) {
+        const int c = l + 16 * q;
+        t[q] = (c < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * c)
+                            : make_float4(0.f, 0.f, 0.f, 0.f);
+        p[q].x = fminf(fmaxf(t[q].x, -SERT_CLIP_HI), SERT_CLIP_HI);
+        p[q].y = fminf(fmaxf(t[q].y, -SERT_CLIP_HI), SERT_CLIP_HI);
+        p[q].z = fminf(fmaxf(t[q].z, -SERT_CLIP_HI), SERT_CLIP_HI);
+        p[q].w = fminf(fmaxf(t[q].w, -SERT_CLIP_HI), SERT_CLIP_HI);
+    }
+    const float wi = TRAIN ? w[i] : 1.f;
+    const float g = wi * inv_batch;
+    float loss = 0.f;
+    for (int j = 0; j <= z; ++j) {
+        const int e = (j == 0) ? Ve + y[i] : neg[(size_t)i * z + (j - 1)];
+        const float* __restrict__ row = foldin_row(Re, E, Ve, e, de);
+        float part = 0.f;
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) {
+            const int c = l + 16 * q;
+            const float4 er = (c < chunks) ? *reinterpret_cast<const float4*>(row + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            part += er.x * p[q].x + er.y * p[q].y + er.z * p[q].z + er.w * p[q].w;
+        }
+        const float u = row16_sum(part);
+        const float sig = theano_sigmoid(u);
+        const float s = clip_prob(sig);
+        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
+        if (TRAIN) {
+            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
+            float du = 0.f;
+            if (inside) {
+                const float ds = sig * (1.0f - sig);
+                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
+            }
+            if (l == 0 && valid) {
+                coef[(size_t)i * (z + 1) + j] = du;
+                key[(size_t)i * (z + 1) + j] = e >= Ve ? e - Ve : N;
+            }
+        }
+    }
+    loss += row_nan(t);
+    if (l == 0 && valid) rowloss[i] = wi * loss;
+    if (l == 0) wg_red[threadIdx.x >> 4] = valid ? wi * loss : 0.f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s += wg_red[r];
+        wg_loss[blockIdx.x] = s;
+    }
+}
+
+// Any d_e (d_e % 4 != 0), the way vs_nce_scalar covers it: one wave per instance, scalar columns.  No barrier, no
+// workgroup partial: the loss is finalised from rowloss.
+template <int NPL, bool TRAIN>
+__global__ __launch_bounds__(256) void foldin_nce_scalar(const float* __restrict__ T, const float* __restrict__ Re,
+                                                         const float* __restrict__ E, const int32_t* __restrict__ y,
+                                                         const int32_t* __restrict__ neg, const float* __restrict__ w,
+                                                         float* __restrict__ coef, int32_t* __restrict__ key,
+                                                         float* __restrict__ rowloss, int B, int z, int de, int Ve, int N,
+                                                         float inv_batch) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= B) return;
+    float t[NPL], p[NPL];
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int c = lane + 64 * q;
+        t[q] = (c < de) ? T[(size_t)i * de + c] : 0.f;
+        p[q] = fminf(fmaxf(t[q], -SERT_CLIP_HI), SERT_CLIP_HI);
+    }
+    const float wi = TRAIN ? w[i] : 1.f;
+    const float g = wi * inv_batch;
+    float loss = 0.f;
+    for (int j = 0; j <= z; ++j) {
+        const int e = (j == 0) ? Ve + y[i] : neg[(size_t)i * z + (j - 1)];
+        const float* __restrict__ row = foldin_row(Re, E, Ve, e, de);
+        float part = 0.f;
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) {
+            const int c = lane + 64 * q;
+            part += ((c < de) ? row[c] : 0.f) * p[q];
+        }
+        const float u = wave_sum(part);
+        const float sig = theano_sigmoid(u);
+        const float s = clip_prob(sig);
+        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
+        if (TRAIN) {
+            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
+            float du = 0.f;
+            if (inside) {
+                const float ds = sig * (1.0f - sig);
+                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
+            }
+            if (lane == 0) {
+                coef[(size_t)i * (z + 1) + j] = du;
+                key[(size_t)i * (z + 1) + j] = e >= Ve ? e - Ve : N;
+            }
+        }
+    }
+    // (a NaN unit of the row: see row_nan)
+    float tsum = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) tsum += t[q];
+    loss += wave_sum(tsum) * 0.0f;
+    if (lane == 0) rowloss[i] = wi * loss;
+}
+
+// egrad_chunk_reduce over keys sorted ascending whose LAST run is the sentinel (key == sentinel: a pair on a frozen row).
+// 16 lanes per chunk of 16 consecutive sorted pairs.  A chunk whose first key is the sentinel lies wholly inside that run and
+// leaves after that one load; the chunk the run begins in reduces its leading live pairs only and ends its last live run
+// there (no carry into the sentinel).  So the sentinel run is neither accumulated nor fixed up, and the work is proportional
+// to the pairs that hit new rows.  Same association as egrad_chunk_reduce for the live runs; head / tail / run_start /
+// run_end as there, for keys < sentinel (egrad_fixup over `sentinel` rows finishes).  T: this batch's projections.
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void foldin_chunk_reduce(
+    const int32_t* __restrict__ keys, const int32_t* __restrict__ pairs,
+    const float* __restrict__ coef, const float* __restrict__ T, int total, int zp1, int de, int sentinel,
+    float* __restrict__ G, float* __restrict__ head, float* __restrict__ tail,
+    int32_t* __restrict__ run_start, int32_t* __restrict__ run_end) {
+    const int l = threadIdx.x & 15;
+    const int gbase = (threadIdx.x & 63) & ~15;  // first lane of this group inside the wave
+    const int chunk = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int cb = chunk * kEChunk;
+    if (cb >= total) return;
+    const int first_key = keys[cb];              // (the same address for the group's sixteen lanes)
+    if (first_key >= sentinel) return;
+    const int ce = min(total, cb + kEChunk);
+    const int pieces = de / VEC;
+    int my_key = sentinel, my_row = 0;
+    float my_coef = 0.f;
+    if (l < ce - cb) {
+        my_key = keys[cb + l];
+        if (my_key < sentinel) {
+            const int pr = pairs[cb + l];
+            my_coef = coef[pr];
+            my_row = pr / zp1;
+        }
+    }
+    // live pairs of the chunk: sorted, so they are its leading lanes (every lane of the group is active here: the two
+    // returns above are uniform over a group)
+    const unsigned long long live = __ballot(my_key < sentinel);
+    const int cnt = __popc((unsigned)(live >> gbase) & 0xffffu);
+    const int prev_key = (cb > 0) ? keys[cb - 1] : -1;
+    // the key behind the chunk's live pairs: a sentinel inside the chunk, or behind it, continues no live run
+    const int next_key = (cnt < ce - cb) ? -1 : ((ce < total) ? keys[ce] : -1);
+
+    for (int p0 = 0; p0 < pieces; p0 += 16 * NCH) {
+        float acc[NCH][VEC];
+#pragma unroll
+        for (int q = 0; q < NCH; ++q)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[q][v] = 0.f;
+        int cur = first_key;
+        bool at_begin = true;
+        int jb = 0;
+
+        auto flush = [&](int e, bool touches_begin, bool touches_end, int jb, int je) {
+            if (p0 == 0 && l == 0) {
+                if (!touches_begin) run_start[e] = cb + jb;
+                if (!touches_end) run_end[e] = cb + je;
+            }
+            float* dst;
+            if (!touches_begin && !touches_end) dst = G + (size_t)e * de;   // sole owner
+            else if (touches_end) dst = tail + (size_t)chunk * de;
+            else dst = head + (size_t)chunk * de;
+#pragma unroll
+            for (int q = 0; q < NCH; ++q) {
+                const int c = p0 + l + 16 * q;
+                if (c < pieces) {
+                    if (VEC == 4)
+                        *reinterpret_cast<float4*>(dst + 4 * c) =
+                            make_float4(acc[q][0], acc[q][1 % VEC], acc[q][2 % VEC], acc[q][3 % VEC]);
+                    else
+                        dst[c] = acc[q][0];
+                }
+            }
+        };
+
+        for (int j = 0; j < cnt; ++j) {
+            const int k = __shfl(my_key, gbase + j, kWave);
+            const int row = __shfl(my_row, gbase + j, kWave);
+            const float cf = __shfl(my_coef, gbase + j, kWave);
+            if (k != cur) {
+                flush(cur, at_begin && prev_key == cur, false, jb, j);
+                jb = j;
+#pragma unroll
+                for (int q = 0; q < NCH; ++q)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[q][v] = 0.f;
+                cur = k;
+                at_begin = false;
+            }
+#pragma unroll
+            for (int q = 0; q < NCH; ++q) {
+                const int c = p0 + l + 16 * q;
+                if (c < pieces) {
+                    float tv[VEC];
+                    if (VEC == 4) {
+                        const float4 t4 = *reinterpret_cast<const float4*>(T + (size_t)row * de + 4 * c);
+                        tv[0] = t4.x; tv[1 % VEC] = t4.y; tv[2 % VEC] = t4.z; tv[3 % VEC] = t4.w;
+                    } else {
+                        tv[0] = T[(size_t)row * de + c];
+                    }
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v)
+                        acc[q][v] += cf * fminf(fmaxf(tv[v], -SERT_CLIP_HI), SERT_CLIP_HI);
+                }
+            }
+        }
+        flush(cur, at_begin && prev_key == cur, next_key == cur, jb, cnt);
+    }
+}
+
+}  // namespace sert

@@ -39,6 +39,7 @@
 #include "kernels_seg.h"
 #include "kernels_sort.h"
 #include "kernels_vs.h"
+#include "kernels_foldin.h"
 #ifdef SERT_VARIANTS
 #include "variants/kernels_gather_hot.h"
 #include "variants/kernels_seg_bundled.h"
@@ -197,6 +198,8 @@ extern "C" {
 #include "host/api_ll_rerank.inc"
 
 #include "host/api_reval.inc"
+
+#include "host/api_foldin.inc"
 
 #include "host/api_comm.inc"
 

@@ -1,0 +1,197 @@
+"""Folding unseen entities into a trained vectorspace model (include/sert_hip_foldin.h).
+
+A catalogue gains entities after training.  The LSE paper's answer is to fold them in: keep the word table, the
+projection and the trained entity rows fixed and learn only the new rows, with the same NCE objective, on the new
+entities' instances.  ``EntityFoldIn`` is that, on the device; ``bin/fold_in.py`` is its command line.
+"""
+import logging
+import pickle
+
+import numpy as np
+
+from sert_amd import _capi
+from sert_amd import models
+
+
+class EntityFoldIn(models.ModelInterface):
+    """N new entity rows learnt on top of a trained vectorspace model (R_w, R_e, W, b: host arrays, never written).
+
+    training_set: (x (M, window_size) token ids of the TRAINED vocabulary, y (M,) in [0, N), w (M,) weights or None).
+    New entity e becomes row V_e + e of the extended table.  ``new_rows_init`` None: N = y.max() + 1 rows drawn with
+    ``_glorot_uniform((N, d_e))``, as bin/train.py initialises R_e.  The batch size, the number of negatives, lambda and the
+    learning rate are the fold-in's own."""
+
+    #: callable batch_index -> (B, z) int64 negatives in [0, V_e + N), or None (device sampler)
+    negative_sampler = None
+    #: same, for train_error()
+    eval_negative_sampler = None
+    #: batches issued to the device before their losses are read back (device-drawn negatives only)
+    steps_per_sync = 1
+
+    def __init__(self, R_w, R_e, W, b, new_rows_init, training_set, batch_size, num_negative_samples,
+                 regularization_lambda, window_size, seed=None, lr=1e-3, device=0, _engine=None):
+        super(EntityFoldIn, self).__init__(batch_size)
+        x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
+        w = training_set[2] if len(training_set) > 2 else None
+        assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        if new_rows_init is None:
+            if not y.size:
+                raise RuntimeError('no fold-in instances and no initial rows: nothing says how many entities are new')
+            new_rows_init = models._glorot_uniform((int(y.max()) + 1, np.shape(R_e)[1]))
+        new_rows_init = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        if seed is None:
+            seed = int(np.random.randint(low=0, high=(1 << 30)))
+        self.window_size = int(window_size)
+        self.num_new = int(new_rows_init.shape[0])
+        self.num_entities = int(np.shape(R_e)[0])
+        self.training_num_instances = int(y.shape[0])
+        _capi.require_gpu()
+        engine, owned = _engine, False
+        if engine is None:
+            # a parameters-only model on the device holds the frozen tensors for the moment of the copy
+            R_w, R_e = np.asarray(R_w, dtype=np.float32), np.asarray(R_e, dtype=np.float32)
+            W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
+            assert W.shape == (R_w.shape[1], R_e.shape[1]) and b.shape == (R_e.shape[1],)
+            engine = _capi.Engine(
+                kind=_capi.KIND_VECTORSPACE, batch_size=1, global_batch_size=1, window_size=self.window_size,
+                vocab_size=R_w.shape[0], num_entities=R_e.shape[0], word_dim=R_w.shape[1], entity_dim=R_e.shape[1],
+                num_negatives=0, id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0,
+                lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0)
+            owned = True
+            for which, value in ((_capi.T_RW, R_w), (_capi.T_RE, R_e), (_capi.T_W, W), (_capi.T_B, b)):
+                engine.set_tensor(which, value)
+        try:
+            self._foldin = _capi.FoldIn(engine, new_rows_init, batch_size, num_negative_samples, regularization_lambda,
+                                        lr=lr, seed=seed)
+        finally:
+            if owned:
+                engine.close()      # (the handle copied what it needs)
+        self._foldin.upload(x, y, w)
+        logging.info('Folding in %d new entities (rows %d .. %d) on %d instances.', self.num_new, self.num_entities,
+                     self.num_entities + self.num_new - 1, self.training_num_instances)
+
+    @classmethod
+    def from_model(cls, model, new_rows_init, training_set, batch_size, num_negative_samples, regularization_lambda,
+                   seed=None, lr=1e-3):
+        """From a live ``models.VectorSpaceLanguageModel``: its parameters as they are now are copied on the device (the
+        model may train on or be dropped afterwards)."""
+        if not isinstance(model, models.VectorSpaceLanguageModel):
+            raise RuntimeError('a fold-in needs a VectorSpaceLanguageModel')
+        shape = (model.num_entities, model.entity_representation_size)
+        return cls(None, _Shape(shape), None, None, new_rows_init, training_set, batch_size, num_negative_samples,
+                   regularization_lambda, model.window_size, seed=seed, lr=lr, _engine=model._engine)
+
+    # -- the step functions ---------------------------------------------------------------------------------------
+    def train_fn(self, batch_index):
+        sampler = self.negative_sampler
+        return self._foldin.train_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
+
+    def test_fn(self, batch_index):
+        sampler = self.eval_negative_sampler
+        return self._foldin.eval_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
+
+    def train(self):
+        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
+        count = self.training_num_instances
+        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
+        if self.steps_per_sync > 1 and self.negative_sampler is None:
+            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
+                                                       report_interval=1000, shuffle=True)
+        else:
+            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
+        return num_batches, np.mean(losses)
+
+    def train_error(self):
+        """(mean, std) of the per-batch evaluation losses on the extended table: unweighted, unregularised."""
+        count = self.training_num_instances
+        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
+        _, losses = self._iterate_batches(self.test_fn, count)
+        return np.mean(losses), np.std(losses)
+
+    # -- results and state --------------------------------------------------------------------------------------------
+    def get_new_representations(self):
+        """(N, d_e): the new rows as they are now."""
+        return self._foldin.get_rows(_capi.FOLDIN_ROWS)
+
+    def get_extended_representations(self, R_e):
+        """(V_e + N, d_e): the trained rows ``R_e`` (the caller's: the fold-in never changes them) with the new rows behind."""
+        R_e = np.asarray(R_e, dtype=np.float32)
+        assert R_e.shape[0] == self.num_entities
+        return np.concatenate([R_e, self.get_new_representations()], axis=0)
+
+    def get_optimizer_state(self):
+        return {'step': self._foldin.get_step(), 'm_E': self._foldin.get_rows(_capi.FOLDIN_M),
+                'v_E': self._foldin.get_rows(_capi.FOLDIN_V)}
+
+    def set_optimizer_state(self, st):
+        self._foldin.set_step(st['step'])
+        self._foldin.set_rows(_capi.FOLDIN_M, st['m_E'])
+        self._foldin.set_rows(_capi.FOLDIN_V, st['v_E'])
+
+    def get_sampler_state(self):
+        return {'seed': int(self._foldin.cfg.seed), 'eval_draws': self._foldin.get_eval_draws()}
+
+    def set_sampler_state(self, st):
+        if int(st['seed']) != int(self._foldin.cfg.seed):
+            raise RuntimeError('the sampler seed is fixed at construction')
+        self._foldin.set_eval_draws(st['eval_draws'])
+
+    def close(self):
+        self._foldin.close()
+
+
+class _Shape(object):
+    """Stands in for a table the constructor only asks the shape of (from_model: the table itself stays on the device)."""
+
+    def __init__(self, shape):
+        self.shape = shape
+
+
+# ---- the model dump and the meta of the extended model (bin/fold_in.py) -------------------------------------------------
+
+def extend_dump(args, predict_fn, R_w, R_e, new_rows):
+    """The objects of a model dump (training.EpochDriver.dump: args, predict_fn, R_w, R_e) with R_e extended by the new rows."""
+    R_e = np.asarray(R_e)
+    new_rows = np.asarray(new_rows, dtype=R_e.dtype)
+    assert new_rows.ndim == 2 and new_rows.shape[1] == R_e.shape[1]
+    return [args, predict_fn, R_w, np.concatenate([R_e, new_rows], axis=0)]
+
+
+def write_dump(path, objects):
+    with open(path, 'wb') as f:
+        for obj in objects:
+            pickle.dump(obj, f, protocol=pickle.HIGHEST_PROTOCOL)
+
+
+def extend_meta(meta, new_entity_ids, new_associations=None):
+    """The five pickles of a meta file (args, words, tokens, entity_indices_inv, documents_per_entity) for the extended
+    model: ``new_entity_ids[e]`` gets internal index V_e + e, ``new_associations`` (entity id -> document ids) are added.
+    An id the meta already knows is refused; ``words`` / ``tokens`` are the trained model's, untouched."""
+    args, words, tokens, entity_indices_inv, assocs = meta
+    new_entity_ids = list(new_entity_ids)
+    known = set(entity_indices_inv.values())
+    clash = [e for e in new_entity_ids if e in known]
+    if clash:
+        raise RuntimeError('entity ids already in the trained model: %r' % (clash[:5],))
+    if len(set(new_entity_ids)) != len(new_entity_ids):
+        raise RuntimeError('duplicate new entity ids')
+    V_e = len(entity_indices_inv)
+    assert sorted(entity_indices_inv) == list(range(V_e)), 'internal entity indices must be 0 .. V_e - 1'
+    extended = dict(entity_indices_inv)
+    for e, entity_id in enumerate(new_entity_ids):
+        extended[V_e + e] = entity_id
+    merged = dict(assocs)
+    for entity_id, documents in (new_associations or {}).items():
+        merged[entity_id] = list(merged.get(entity_id, [])) + list(documents)
+    return [args, words, tokens, extended, merged]
+
+
+def read_meta(path):
+    with open(path, 'rb') as f:
+        return [pickle.load(f) for _ in range(5)]
+
+
+def write_meta(path, meta):
+    with open(path, 'wb') as f:
+        for obj in meta:
+            pickle.dump(obj, f, protocol=pickle.HIGHEST_PROTOCOL)

@@ -98,6 +98,13 @@ def extract_vocabulary(documents, min_count=2, max_size=65536, min_word_size=2,
     return words, tokens
 
 
+def vocabulary_of_meta(path):
+    """(words, tokens) of a meta file: the second and third of its five pickles."""
+    with open(path, 'rb') as f:
+        _, words, tokens = (pickle.load(f) for _ in range(3))
+    return words, tokens
+
+
 def read_associations(f, known_documents=None):
     """Lines ``entity_id document_id [1]`` -> (entities_per_document,
     documents_per_entity); associations to unknown documents are dropped."""
@@ -169,10 +176,19 @@ def prepare(args):
     logging.info('Generating instances with stride %d.', stride)
 
     documents = list(iter_trec_documents(args.document_paths, args.encoding))
-    words, tokens = extract_vocabulary(
-        documents, min_count=args.vocabulary_min_count, max_size=args.vocabulary_max_size,
-        min_word_size=args.vocabulary_min_word_size, ignore=ignore,
-        with_padding=not args.no_padding)
+    vocabulary_from = getattr(args, 'vocabulary_from', None)
+    if vocabulary_from:
+        # documents of entities that arrive after training (bin/fold_in.py): the TRAINED model's vocabulary, so that the
+        # instances carry its token ids; tokens outside it are dropped below, as at query time
+        words, tokens = vocabulary_of_meta(vocabulary_from)
+        if not args.no_padding and PADDING_TOKEN not in words:
+            raise ValueError('The vocabulary of %s has no padding token; pass --no_padding.' % vocabulary_from)
+        logging.info('Took the vocabulary of %s (%d words).', vocabulary_from, len(words))
+    else:
+        words, tokens = extract_vocabulary(
+            documents, min_count=args.vocabulary_min_count, max_size=args.vocabulary_max_size,
+            min_word_size=args.vocabulary_min_word_size, ignore=ignore,
+            with_padding=not args.no_padding)
     padding_id = None if args.no_padding else words[PADDING_TOKEN].id
 
     with open(args.assoc_path, 'r') as f:
