@@ -1,5 +1,5 @@
 // Shared by the gfx950 kernels of libsert_hip.so and their host code: the environment switches (knob / variant_knob), the
-// error plumbing (SERT_FAIL / SERT_HIP / SERT_TRY), and the device helpers -- wave and workgroup reductions, ranking keys,
+// error plumbing (SERT_FAIL / SERT_HIP / SERT_TRY), device allocation (dmalloc, DevBuf), and the device helpers -- wave and workgroup reductions, ranking keys,
 // the reference's clips and sigmoid, the write-through stores.  How a kernel is started is launch.h; how it is timed,
 // host/timing.inc.
 #pragma once
@@ -63,6 +63,37 @@ inline int fail(const char* file, int line, const std::string& msg) {
         int _rc = (expr);         \
         if (_rc != 0) return _rc; \
     } while (0)
+
+// ---- device memory (host side) ---------------------------------------------
+template <typename T>
+inline int dmalloc(T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) return 0;
+    SERT_HIP(hipMalloc((void**)p, count * sizeof(T)));
+    return 0;
+}
+// A grow-only device array: room for `cap` elements at `p`.  reserve(n) keeps the array when it is large enough; otherwise
+// the old one is freed first, and what it held is gone.  It does not synchronise: the caller has nothing queued that still
+// reads the old array.  After a reserve that FAILED the array is {nullptr, 0} -- never a freed pointer, never a capacity
+// without memory behind it -- so the owner stays usable: the next reserve simply allocates again.  No destructor: the owner
+// frees with release(), on the device it chose (sert_scorer_destroy).
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;               // elements
+    int reserve(int64_t n) {
+        if (cap >= n) return 0;
+        release();
+        SERT_TRY(dmalloc(&p, (size_t)n));
+        cap = n;
+        return 0;
+    }
+    void release() {
+        (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
 
 // ---- wave-level reductions -------------------------------------------------
 // DPP row operations (pure VALU, ~1 issue each) reduce each 16-lane row, four

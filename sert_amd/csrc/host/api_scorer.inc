@@ -61,15 +61,13 @@ int sert_scorer_create(int device, const float* entities, int64_t V, int32_t dim
 int sert_scorer_destroy(sert_scorer* sc) {
     if (!sc) return 0;
     (void)hipSetDevice(sc->device);
-    (void)hipFree(sc->E); (void)hipFree(sc->P); (void)hipFree(sc->S); (void)hipFree(sc->val); (void)hipFree(sc->idx);
-    (void)hipFree(sc->Ss); (void)hipFree(sc->thr); (void)hipFree(sc->cand); (void)hipFree(sc->cnt);
-    (void)hipFree(sc->nflag); (void)hipFree(sc->flag_list); (void)hipFree(sc->Pc); (void)hipFree(sc->idx_c);
-    (void)hipFree(sc->val_c); (void)hipFree(sc->E16); (void)hipFree(sc->P16);
-    (void)hipFree(sc->rP); (void)hipFree(sc->rS); rank_scratch_free(sc->rsort);
-    (void)hipFree(sc->cptr); (void)hipFree(sc->cents); (void)hipFree(sc->cq); (void)hipFree(sc->csptr);
-    (void)hipFree(sc->cidx); (void)hipFree(sc->cval); (void)hipFree(sc->cpos); (void)hipFree(sc->cpval);
+    (void)hipFree(sc->E); (void)hipFree(sc->E16);
+    sc->P.release(); sc->S.release(); sc->val.release(); sc->idx.release();
+    sc->Ss.release(); sc->thr.release(); sc->cand.release(); sc->cnt.release(); sc->nflag.release(); sc->flag_list.release();
+    sc->Pc.release(); sc->idx_c.release(); sc->val_c.release(); sc->P16.release();
+    sc->rP.release(); sc->lists.release(); sc->csptr.release();
     for (int b = 0; b < 2; ++b) {
-        (void)hipFree(sc->ridx[b]); (void)hipFree(sc->rval[b]);
+        sc->ridx[b].release(); sc->rval[b].release();
         if (sc->ev_rsorted[b]) (void)hipEventDestroy(sc->ev_rsorted[b]);
         if (sc->ev_rcopy0[b]) (void)hipEventDestroy(sc->ev_rcopy0[b]);
         if (sc->ev_rcopied[b]) (void)hipEventDestroy(sc->ev_rcopied[b]);
@@ -110,20 +108,15 @@ static int scorer_topk_materialised(sert_scorer* sc, const float* P, int64_t Q, 
     }();
     // query tile: bounds one materialised score slab to ~0.5 GiB (two slabs alternate)
     const int64_t QT = std::min<int64_t>(Q, std::max<int64_t>(128, slab_elems / V / 128 * 128));
-    if (sc->cap_s < 2 * QT * V) {
-        SERT_HIP(hipStreamSynchronize(s));
-        (void)hipFree(sc->S);
-        sc->S = nullptr; sc->cap_s = 0;
-        SERT_TRY(dmalloc(&sc->S, (size_t)2 * QT * V));
-        sc->cap_s = 2 * QT * V;
-    }
+    if (sc->S.cap < 2 * QT * V) SERT_HIP(hipStreamSynchronize(s));      // (reserve does not synchronise)
+    SERT_TRY(sc->S.reserve(2 * QT * V));
     SERT_HIP(hipEventRecord(sc->ev_ready, s));
     SERT_HIP(hipStreamWaitEvent(sc->stream2, sc->ev_ready, 0));
     int t = 0;
     for (int64_t q0 = 0; q0 < Q; q0 += QT, ++t) {
         const int64_t qn = std::min(QT, Q - q0);
         hipStream_t st = (t & 1) ? sc->stream2 : s;
-        float* S = sc->S + (size_t)(t & 1) * QT * V;
+        float* S = sc->S.p + (size_t)(t & 1) * QT * V;
         // S = P.E^T  (cosines), then per-row selection
         // (same kernel family as the fused path, so a row's scores do not depend on the path)
 #ifdef SERT_VARIANTS
@@ -168,50 +161,29 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
     static const int64_t chunk_rows = variant_knob("SERT_SCORE_CHUNK") ? atoll(variant_knob("SERT_SCORE_CHUNK")) : 8192;   // tuning knob
     const int64_t nchunks = Q <= 1024 ? 1 : 2 * cdiv(Q, 2 * chunk_rows);
     const int64_t QT = std::min<int64_t>(Q, round_up(cdiv(Q, nchunks), 128));
-    if (sc->cap_ss < 2 * QT * Vs) {
-        (void)hipFree(sc->Ss); sc->Ss = nullptr; sc->cap_ss = 0;
-        SERT_TRY(dmalloc(&sc->Ss, (size_t)(2 * QT * Vs)));
-        sc->cap_ss = 2 * QT * Vs;
-    }
+    SERT_TRY(sc->Ss.reserve(2 * QT * Vs));
     // per-(row, 64-entity group) candidate lists: 8 slots for ~0.5 expected entries per
     // group (k <= 128), 16 beyond
     const int ngroups = 2 * cdiv((int)V, GN);
     const int gcap = k <= 128 ? 8 : 16;
-    if (sc->cap_ft < 2 * QT) {
-        (void)hipFree(sc->thr); sc->thr = nullptr; sc->cap_ft = 0;
-        SERT_TRY(dmalloc(&sc->thr, (size_t)(2 * QT)));
-        sc->cap_ft = 2 * QT;
-    }
+    SERT_TRY(sc->thr.reserve(2 * QT));
     const int64_t cand_set = QT * ngroups * gcap, cnt_set = QT * ngroups;
-    if (sc->cap_cand < 2 * cand_set) {
-        (void)hipFree(sc->cand); (void)hipFree(sc->cnt);
-        sc->cand = nullptr; sc->cnt = nullptr; sc->cap_cand = 0;
-        SERT_TRY(dmalloc(&sc->cand, (size_t)(2 * cand_set)));
-        SERT_TRY(dmalloc(&sc->cnt, (size_t)(2 * QT * ngroups * 16 / 8)));   // sized for either gcap
-        sc->cap_cand = 2 * cand_set;
-    }
-    if (sc->cap_flag < Q) {
-        (void)hipFree(sc->flag_list); (void)hipFree(sc->nflag);
-        sc->flag_list = nullptr; sc->nflag = nullptr; sc->cap_flag = 0;
-        SERT_TRY(dmalloc(&sc->flag_list, (size_t)(2 * Q)));   // the list, and behind it one flag per row (topk_from_groups)
-        SERT_TRY(dmalloc(&sc->nflag, (size_t)1));
-        sc->cap_flag = Q;
-    }
+    SERT_TRY(sc->cand.reserve(2 * cand_set));
+    SERT_TRY(sc->cnt.reserve(2 * QT * ngroups * 16 / 8));   // sized for either gcap
+    SERT_TRY(sc->flag_list.reserve(2 * Q));   // the list, and behind it (at Q) one flag per row (topk_from_groups)
+    SERT_TRY(sc->nflag.reserve(1));
+    int* const row_flags = sc->flag_list.p + Q;
     // the bf16 prefilter needs a gap of 2 delta between the k-th score and the filter threshold;
     // a table whose rows mostly lack it (very high d_e, heavy ties) is scored in fp32 from then on
     const bool use_bf16 = sc->bf16 && !sc->bf16_demoted;
-    if (use_bf16 && sc->cap_p16 < 2 * QT * sc->kp) {
-        (void)hipFree(sc->P16); sc->P16 = nullptr; sc->cap_p16 = 0;
-        SERT_TRY(dmalloc(&sc->P16, (size_t)(2 * QT * sc->kp)));
-        sc->cap_p16 = 2 * QT * sc->kp;
-    }
-    SERT_HIP(hipMemsetAsync(sc->nflag, 0, sizeof(int), s));
+    if (use_bf16) SERT_TRY(sc->P16.reserve(2 * QT * sc->kp));
+    SERT_HIP(hipMemsetAsync(sc->nflag.p, 0, sizeof(int), s));
     SERT_HIP(hipEventRecord(sc->ev_ready, s));           // nflag zeroed, earlier work on s done
     SERT_HIP(hipStreamWaitEvent(sc->stream2, sc->ev_ready, 0));
     auto copy_out = [&](int64_t q0, int64_t qn, hipStream_t st) {   // (host, pageable: returns when done; device: asynchronous on st -- ev_done and the synchronisation of s below join both streams before this function returns)
-        hipError_t e = hipMemcpyAsync(idx_out + q0 * k, sc->idx + q0 * k, (size_t)qn * k * sizeof(int32_t), kind_out, st);
+        hipError_t e = hipMemcpyAsync(idx_out + q0 * k, sc->idx.p + q0 * k, (size_t)qn * k * sizeof(int32_t), kind_out, st);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(score_out + q0 * k, sc->val + q0 * k, (size_t)qn * k * sizeof(float), kind_out, st);
+            e = hipMemcpyAsync(score_out + q0 * k, sc->val.p + q0 * k, (size_t)qn * k * sizeof(float), kind_out, st);
         return e;
     };
     int64_t t = 0;
@@ -219,15 +191,15 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         const int64_t qn = std::min(QT, Q - q0);
         const int set = (int)(t & 1);
         hipStream_t st = set ? sc->stream2 : s;
-        float* Pw = sc->P + q0 * dim;
+        float* Pw = sc->P.p + q0 * dim;
         SERT_HIP(hipMemcpyAsync(Pw, proj + q0 * dim, (size_t)qn * dim * sizeof(float), kind_in, st));
         launch(l2_normalize_rows, dim3(cdiv(qn, 4)), dim3(256), 0, st, Pw, qn, dim);
         const float* P = Pw;
-        float* Ss = sc->Ss + (size_t)set * QT * Vs;
-        float* thr = sc->thr + (size_t)set * QT;
-        unsigned long long* cand = sc->cand + (size_t)set * cand_set;
-        unsigned char* cnt = sc->cnt + (size_t)set * cnt_set;
-        uint16_t* P16 = use_bf16 ? sc->P16 + (size_t)set * QT * sc->kp : nullptr;
+        float* Ss = sc->Ss.p + (size_t)set * QT * Vs;
+        float* thr = sc->thr.p + (size_t)set * QT;
+        unsigned long long* cand = sc->cand.p + (size_t)set * cand_set;
+        unsigned char* cnt = sc->cnt.p + (size_t)set * cnt_set;
+        uint16_t* P16 = use_bf16 ? sc->P16.p + (size_t)set * QT * sc->kp : nullptr;
         SERT_HIP(hipMemsetAsync(cnt, 0, (size_t)qn * ngroups, st));
         // 1. cosines against every kScoreStride-th entity; threshold = rs-th best of the sample
         // (bf16 scorer: approximate sample scores are as good for choosing a threshold)
@@ -259,17 +231,17 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
         while (ccap < 2 * k + 400 + 6 * 16 * (int)ceilf(sqrtf((float)rs)) && ccap < kCandCap) ccap <<= 1;
         if (use_bf16)
             launch(topk_from_groups_rescore, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
-                   (const uint32_t*)cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
-                   sc->nflag, sc->flag_list, ccap, P, sc->E, dim, thr, bf16_delta(dim));
+                   (const uint32_t*)cand, cnt, ngroups, gcap, k, sc->idx.p + q0 * k, sc->val.p + q0 * k, (int)q0,
+                   sc->nflag.p, sc->flag_list.p, ccap, P, sc->E, dim, thr, bf16_delta(dim));
         else {
             launch(topk_from_groups, dim3((unsigned)qn), dim3(256), (size_t)ccap * sizeof(unsigned long long), st,
-                   cand, cnt, ngroups, gcap, k, sc->idx + q0 * k, sc->val + q0 * k, (int)q0,
-                   sc->nflag, sc->flag_list, ccap, sc->flag_list + sc->cap_flag);
+                   cand, cnt, ngroups, gcap, k, sc->idx.p + q0 * k, sc->val.p + q0 * k, (int)q0,
+                   sc->nflag.p, sc->flag_list.p, ccap, row_flags);
             if (sc->bf16) {   // demoted table: its scores stay the exact_dot ones every other path of this scorer reports
                 int sn = 2;
                 while (sn < k) sn <<= 1;
                 launch(rescore_topk_rows, dim3((unsigned)qn), dim3(256), (size_t)sn * sizeof(unsigned long long),
-                       st, P, sc->E, dim, k, sc->idx + q0 * k, sc->val + q0 * k, sc->flag_list + sc->cap_flag + q0);
+                       st, P, sc->E, dim, k, sc->idx.p + q0 * k, sc->val.p + q0 * k, row_flags + q0);
             }
         }
         // results of the previous chunk (other stream) travel while this one computes
@@ -282,33 +254,24 @@ static int scorer_topk_fused(sert_scorer* sc, const float* proj, int64_t Q, int 
     SERT_HIP(hipEventRecord(sc->ev_done, sc->stream2));
     SERT_HIP(hipStreamWaitEvent(s, sc->ev_done, 0));
     int nf = 0;
-    SERT_HIP(hipMemcpyAsync(&nf, sc->nflag, sizeof(int), hipMemcpyDeviceToHost, s));
+    SERT_HIP(hipMemcpyAsync(&nf, sc->nflag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     SERT_HIP(hipStreamSynchronize(s));
     sc->path_counts[0] += 1; sc->path_counts[1] += use_bf16 ? 1 : 0; sc->path_counts[2] += t; sc->path_counts[3] += nf;
     if (nf == 0) { *copied_out = true; return 0; }
     if (use_bf16 && (int64_t)nf * 4 > Q && Q >= 64) sc->bf16_demoted = true;
     // rows the sample misjudged: recompute exactly (ascending order, for reproducibility)
     std::vector<int> list((size_t)nf);
-    SERT_HIP(hipMemcpy(list.data(), sc->flag_list, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost));
+    SERT_HIP(hipMemcpy(list.data(), sc->flag_list.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost));
     std::sort(list.begin(), list.end());
-    SERT_HIP(hipMemcpyAsync(sc->flag_list, list.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice, s));
-    if (sc->cap_c < nf) {
-        (void)hipFree(sc->Pc); sc->Pc = nullptr; sc->cap_c = 0;
-        SERT_TRY(dmalloc(&sc->Pc, (size_t)nf * dim));
-        sc->cap_c = nf;
-    }
-    if (sc->cap_ck < (int64_t)nf * k) {
-        (void)hipFree(sc->idx_c); (void)hipFree(sc->val_c);
-        sc->idx_c = nullptr; sc->val_c = nullptr; sc->cap_ck = 0;
-        SERT_TRY(dmalloc(&sc->idx_c, (size_t)nf * k));
-        SERT_TRY(dmalloc(&sc->val_c, (size_t)nf * k));
-        sc->cap_ck = (int64_t)nf * k;
-    }
-    launch(gather_rows_f32, dim3(grid_for((int64_t)nf * dim)), dim3(256), 0, s, sc->P,
-           sc->flag_list, nf, dim, sc->Pc);
-    SERT_TRY(scorer_topk_materialised(sc, sc->Pc, nf, k, sc->idx_c, sc->val_c));
-    launch(scatter_topk_rows, dim3(grid_for((int64_t)nf * k)), dim3(256), 0, s, sc->idx_c,
-           sc->val_c, sc->flag_list, nf, k, sc->idx, sc->val);
+    SERT_HIP(hipMemcpyAsync(sc->flag_list.p, list.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice, s));
+    SERT_TRY(sc->Pc.reserve((int64_t)nf * dim));
+    SERT_TRY(sc->idx_c.reserve((int64_t)nf * k));
+    SERT_TRY(sc->val_c.reserve((int64_t)nf * k));
+    launch(gather_rows_f32, dim3(grid_for((int64_t)nf * dim)), dim3(256), 0, s, sc->P.p,
+           sc->flag_list.p, nf, dim, sc->Pc.p);
+    SERT_TRY(scorer_topk_materialised(sc, sc->Pc.p, nf, k, sc->idx_c.p, sc->val_c.p));
+    launch(scatter_topk_rows, dim3(grid_for((int64_t)nf * k)), dim3(256), 0, s, sc->idx_c.p,
+           sc->val_c.p, sc->flag_list.p, nf, k, sc->idx.p, sc->val.p);
     return 0;
 }
 
@@ -324,20 +287,9 @@ static int scorer_topk_io(sert_scorer* sc, const float* proj, int64_t Q, int32_t
     hipStream_t s = sc->stream;
     const int64_t V = sc->V;
     const int dim = sc->dim;
-    if (sc->cap_q < Q) {
-        (void)hipFree(sc->P); (void)hipFree(sc->val); (void)hipFree(sc->idx);
-        sc->P = nullptr; sc->val = nullptr; sc->idx = nullptr;
-        sc->cap_q = 0; sc->cap_qk = 0;
-        SERT_TRY(dmalloc(&sc->P, (size_t)Q * dim));
-        sc->cap_q = Q;
-    }
-    if (sc->cap_qk < Q * k) {
-        (void)hipFree(sc->val); (void)hipFree(sc->idx);
-        sc->val = nullptr; sc->idx = nullptr; sc->cap_qk = 0;
-        SERT_TRY(dmalloc(&sc->val, (size_t)Q * k));
-        SERT_TRY(dmalloc(&sc->idx, (size_t)Q * k));
-        sc->cap_qk = Q * k;
-    }
+    SERT_TRY(sc->P.reserve(Q * dim));
+    SERT_TRY(sc->val.reserve(Q * k));
+    SERT_TRY(sc->idx.reserve(Q * k));
     // fused path for large entity tables: the sample must be big enough for a stable
     // threshold: rank rs among the V/16 sampled entities, i.e. an expected 2k+400 (std ~
     // sqrt(rs)*16) candidates of V -- at k=100: 608 +- 99, >= k at 5 sigma, <= 1024 at 4
@@ -348,16 +300,16 @@ static int scorer_topk_io(sert_scorer* sc, const float* proj, int64_t Q, int32_t
     bool copied = false;
     if (fused) SERT_TRY(scorer_topk_fused(sc, proj, Q, k, rs, idx_out, score_out, &copied, dev));
     else {
-        SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
-        SERT_TRY(scorer_topk_materialised(sc, sc->P, Q, k, sc->idx, sc->val));
+        SERT_HIP(hipMemcpyAsync(sc->P.p, proj, (size_t)Q * dim * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P.p, Q, dim);
+        SERT_TRY(scorer_topk_materialised(sc, sc->P.p, Q, k, sc->idx.p, sc->val.p));
         sc->path_counts[4] += Q;
     }
     SERT_HIP(hipGetLastError());
     if (copied) return 0;
     const hipMemcpyKind kind_out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    SERT_HIP(hipMemcpyAsync(idx_out, sc->idx, (size_t)Q * k * sizeof(int32_t), kind_out, s));
-    SERT_HIP(hipMemcpyAsync(score_out, sc->val, (size_t)Q * k * sizeof(float), kind_out, s));
+    SERT_HIP(hipMemcpyAsync(idx_out, sc->idx.p, (size_t)Q * k * sizeof(int32_t), kind_out, s));
+    SERT_HIP(hipMemcpyAsync(score_out, sc->val.p, (size_t)Q * k * sizeof(float), kind_out, s));
     SERT_HIP(hipStreamSynchronize(s));
     return 0;
 }
@@ -389,23 +341,15 @@ static int scorer_all(sert_scorer* sc, const float* proj, int64_t Q, float* scor
     const int64_t V = sc->V;
     const int dim = sc->dim;
     const int64_t QT = std::min<int64_t>(Q, std::max<int64_t>(128, ((int64_t)1 << 28) / V / 128 * 128));
-    if (sc->cap_q < Q) {
-        (void)hipFree(sc->P); (void)hipFree(sc->val); (void)hipFree(sc->idx);
-        SERT_TRY(dmalloc(&sc->P, (size_t)Q * dim));
-        sc->cap_q = Q; sc->cap_qk = 0; sc->val = nullptr; sc->idx = nullptr;
-    }
-    if (sc->cap_s < QT * V) {
-        (void)hipFree(sc->S);
-        SERT_TRY(dmalloc(&sc->S, (size_t)QT * V));
-        sc->cap_s = QT * V;
-    }
-    SERT_HIP(hipMemcpyAsync(sc->P, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P, Q, dim);
+    SERT_TRY(sc->P.reserve(Q * dim));
+    SERT_TRY(sc->S.reserve(QT * V));
+    SERT_HIP(hipMemcpyAsync(sc->P.p, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->P.p, Q, dim);
     for (int64_t q0 = 0; q0 < Q; q0 += QT) {
         const int64_t qn = std::min(QT, Q - q0);
-        scorer_cosine_slab(sc, s, sc->P + q0 * dim, qn, sc->S, raw && sc->bf16);
-        if (!raw) launch(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S, (size_t)(qn * V));
-        SERT_HIP(hipMemcpyAsync(score_out + q0 * V, sc->S, (size_t)qn * V * sizeof(float), hipMemcpyDeviceToHost, s));
+        scorer_cosine_slab(sc, s, sc->P.p + q0 * dim, qn, sc->S.p, raw && sc->bf16);
+        if (!raw) launch(cos_to_score, dim3(grid_for(qn * V)), dim3(256), 0, s, sc->S.p, (size_t)(qn * V));
+        SERT_HIP(hipMemcpyAsync(score_out + q0 * V, sc->S.p, (size_t)qn * V * sizeof(float), hipMemcpyDeviceToHost, s));
         SERT_HIP(hipStreamSynchronize(s));
     }
     return 0;

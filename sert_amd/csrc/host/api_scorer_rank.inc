@@ -41,7 +41,8 @@ static int64_t score_rank_chunk_queries(int mode, int64_t Q, int64_t V, int kk) 
     return lo;
 }
 
-// the scratch of a call whose largest chunk holds Qc queries (sert_scorer members r*: nothing the other calls use)
+// the scratch of a call whose largest chunk holds Qc queries (sert_scorer members r* and, shared with the candidate calls,
+// lists.slab / lists.sort: nothing the top-k and score calls use)
 static int score_rank_scratch(sert_scorer* sc, int mode, int64_t Q, int64_t Qc, int kk) {
     const int64_t V = sc->V;
     for (int b = 0; b < 2; ++b) {
@@ -49,29 +50,13 @@ static int score_rank_scratch(sert_scorer* sc, int mode, int64_t Q, int64_t Qc, 
         if (!sc->ev_rcopy0[b]) SERT_HIP(hipEventCreate(&sc->ev_rcopy0[b]));      // (timed: the pair brackets a chunk's copies)
         if (!sc->ev_rcopied[b]) SERT_HIP(hipEventCreate(&sc->ev_rcopied[b]));
     }
-    if (sc->cap_rp < Q) {
-        (void)hipFree(sc->rP); sc->rP = nullptr; sc->cap_rp = 0;
-        SERT_TRY(dmalloc(&sc->rP, (size_t)Q * sc->dim));
-        sc->cap_rp = Q;
+    SERT_TRY(sc->rP.reserve(Q * sc->dim));
+    SERT_TRY(sc->lists.slab.reserve(Qc * V));
+    for (int b = 0; b < 2; ++b) {
+        SERT_TRY(sc->ridx[b].reserve(Qc * kk));
+        SERT_TRY(sc->rval[b].reserve(Qc * kk));
     }
-    if (sc->cap_rs < Qc * V) {
-        (void)hipFree(sc->rS); sc->rS = nullptr; sc->cap_rs = 0;
-        SERT_TRY(dmalloc(&sc->rS, (size_t)(Qc * V)));
-        sc->cap_rs = Qc * V;
-    }
-    if (sc->cap_rout < Qc * kk) {
-        for (int b = 0; b < 2; ++b) {
-            (void)hipFree(sc->ridx[b]); (void)hipFree(sc->rval[b]);
-            sc->ridx[b] = nullptr; sc->rval[b] = nullptr;
-        }
-        sc->cap_rout = 0;
-        for (int b = 0; b < 2; ++b) {
-            SERT_TRY(dmalloc(&sc->ridx[b], (size_t)(Qc * kk)));
-            SERT_TRY(dmalloc(&sc->rval[b], (size_t)(Qc * kk)));
-        }
-        sc->cap_rout = Qc * kk;
-    }
-    if (mode == RANK_CSORT) SERT_TRY(rank_scratch_reserve(sc->rsort, Qc * V));
+    if (mode == RANK_CSORT) SERT_TRY(rank_scratch_reserve(sc->lists.sort, Qc * V));
     return 0;
 }
 
@@ -121,22 +106,22 @@ int sert_scorer_rank(sert_scorer* sc, const float* proj, int64_t Q, int32_t k, i
         SERT_TRY(harvest(b));                                     // (chunk c - 2's copies: long done)
         SERT_HIP(hipStreamWaitEvent(s2, sc->ev_rsorted[b], 0));
         SERT_HIP(hipEventRecord(sc->ev_rcopy0[b], s2));
-        SERT_HIP(hipMemcpyAsync(idx_out + q0 * kk, sc->ridx[b], (size_t)qn * kk * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
-        SERT_HIP(hipMemcpyAsync(score_out + q0 * kk, sc->rval[b], (size_t)qn * kk * sizeof(float), hipMemcpyDeviceToHost, s2));
+        SERT_HIP(hipMemcpyAsync(idx_out + q0 * kk, sc->ridx[b].p, (size_t)qn * kk * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
+        SERT_HIP(hipMemcpyAsync(score_out + q0 * kk, sc->rval[b].p, (size_t)qn * kk * sizeof(float), hipMemcpyDeviceToHost, s2));
         SERT_HIP(hipEventRecord(sc->ev_rcopied[b], s2));
         timed[b] = true;
         return 0;
     };
     auto body = [&]() -> int {
-        SERT_HIP(hipMemcpyAsync(sc->rP, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
-        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->rP, Q, dim);
+        SERT_HIP(hipMemcpyAsync(sc->rP.p, proj, (size_t)Q * dim * sizeof(float), hipMemcpyHostToDevice, s));
+        launch(l2_normalize_rows, dim3(cdiv(Q, 4)), dim3(256), 0, s, sc->rP.p, Q, dim);
         for (int64_t c = 0; c < nchunks; ++c) {
             const int b = (int)(c & 1);
             const int64_t q0 = c * Qc, qn = std::min(Qc, Q - q0);
             if (c >= 2) SERT_HIP(hipStreamWaitEvent(s, sc->ev_rcopied[b], 0));      // (chunk c - 2 has left this result set)
             for (int64_t r0 = 0; r0 < qn; r0 += kScoreRankRows)
-                scorer_cosine_slab(sc, s, sc->rP + (q0 + r0) * dim, std::min<int64_t>(kScoreRankRows, qn - r0), sc->rS + (size_t)r0 * V, sc->bf16);
-            SERT_TRY(rank_rows_full(s, mode, /*raw=*/false, sc->rS, (int)qn, (int)V, kk, sc->rsort, sc->ridx[b], sc->rval[b]));
+                scorer_cosine_slab(sc, s, sc->rP.p + (q0 + r0) * dim, std::min<int64_t>(kScoreRankRows, qn - r0), sc->lists.slab.p + (size_t)r0 * V, sc->bf16);
+            SERT_TRY(rank_rows_full(s, mode, /*raw=*/false, sc->lists.slab.p, (int)qn, (int)V, kk, sc->lists.sort, sc->ridx[b].p, sc->rval[b].p));
             SERT_HIP(hipEventRecord(sc->ev_rsorted[b], s));
             if (c >= 1) SERT_TRY(copy_out(c - 1));
             sc->rank_counts[1] += 1; sc->rank_counts[mode == RANK_LDS ? 3 : 4] += qn;

@@ -15,10 +15,6 @@ static int rank_scratch_reserve(RankSortScratch& r, int64_t n) {
     r.cap = n;
     return 0;
 }
-static void rank_scratch_free(RankSortScratch& r) {
-    (void)hipFree(r.keys); (void)hipFree(r.hist);
-    r = RankSortScratch();
-}
 
 template <bool RAW>
 static void rank_rows_launch(hipStream_t s, int mode, const float* S, int Qc, int V, int kk, const RankSortScratch& r, int32_t* idx,

@@ -94,6 +94,10 @@ struct RankSortScratch {
     int32_t* hist = nullptr;
     int64_t cap = 0;               // elements both hold room for
 };
+inline void rank_scratch_free(RankSortScratch& r) {      // (rank_scratch_reserve: host/rank_rows.inc)
+    (void)hipFree(r.keys); (void)hipFree(r.hist);
+    r = RankSortScratch();
+}
 inline int64_t rank_hist_ints(int64_t n) { return (int64_t)kSortMaxBins * cdiv(n, kSortTile) + kSortMaxBins; }
 inline size_t rank_scratch_bytes(int64_t n) { return (size_t)n * 16 + (size_t)rank_hist_ints(n) * 4; }
 

@@ -1,6 +1,7 @@
 // Re-ranking: cosines and rankings of per-query candidate lists, gfx950 (include/sert_hip.h: sert_scorer_pairs,
-// sert_scorer_rank_candidates; host/api_scorer_rerank.inc).  The candidates are CSR: query q owns
-// cand_entities[indptr[q] .. indptr[q + 1]).
+// sert_scorer_rank_candidates; host/api_scorer_rerank.inc, and for the rankings the host chain of host/rank_lists.inc).  The
+// candidates are CSR: query q owns cand_entities[indptr[q] .. indptr[q + 1]).  The ranker's arrays are chunk-relative: its
+// kernels see the queries, the candidates and the output offsets of one chunk, counted from that chunk's first query.
 //
 // One arithmetic: every pair's cosine is exact_dot32_any (kernels_score_bf16.h) of the normalised query row and the normalised
 // table row -- whatever the table size, whichever kernel below computes it.
@@ -12,6 +13,11 @@
 //                         ascending, so the entity in the low word breaks ties as the position in the list would.
 //   rerank_compact        longer lists: the slab's rows ordered by the counting-sort passes of kernels_rank.h (positions in the
 //                         list), mapped back to entities and packed into the ragged output.
+//
+// The loglinear re-ranker (kernels_ll_rerank.h) runs through the same host chain and shares rerank_compact, but keeps its own
+// score-producing kernels, ll_rerank_lds<N> and ll_rerank_gather_slab, beside rerank_lds<N> and rerank_pair_cosines<true>:
+// these compute exact dot products with half-waves, those gather from a joint row that already exists.  That difference is
+// real; one kernel for both would be a switch around two bodies.
 //
 // The pair -> query map is a search in indptr, not an uploaded int32 per pair: the map would double the bytes a call sends to
 // the device (the candidates themselves are 4 bytes per pair), and at 10 000 x 1 000 pairs that upload costs more than the
@@ -29,7 +35,8 @@ constexpr int kRerankTile = 8 * kRerankPairsPerTrip;          // pairs per workg
 
 // Work items [j0, j1) of rows r = 0 .. R - 1, row r owning the items [wptr[r], wptr[r + 1]) (wptr[0] <= j0, j1 <= wptr[R]).
 // Item j of row r is the pair (query, cand_entities[indptr[query] + j - wptr[r]]), query = row_query ? row_query[r] : r;
-// `ents` holds the caller's cand_entities from element ent_base on.
+// `ents` holds the caller's cand_entities from element ent_base on (sert_scorer_pairs cuts its chunks inside a list; the
+// slab form's arrays are chunk-relative and its ent_base is 0).
 //   !SLAB  out[j - j0] = the cosine (raw) or (cos + 1) / 2          (sert_scorer_pairs: wptr == indptr)
 //    SLAB  out[r * stride + j - wptr[r]] = the cosine              (the padding behind a row's list is the caller's)
 template <bool SLAB>
@@ -98,40 +105,39 @@ __global__ __launch_bounds__(256) void rerank_pair_cosines(const float* __restri
 }
 
 // One workgroup per query of qlist, each with 1 .. N candidates: the kk = out_ptr[q + 1] - out_ptr[q] best of the list to
-// idx_out / val_out at out_ptr[q] - out_base.  N = 8192 is rank_rows_lds<8192>'s 64 KiB of LDS.
+// idx_out / val_out at out_ptr[q].  N = 8192 is rank_rows_lds<8192>'s 64 KiB of LDS.
 template <int N>
 __global__ __launch_bounds__(256) void rerank_lds(const float* __restrict__ P, const float* __restrict__ E, int d,
-                                                  const int32_t* __restrict__ ents, int64_t ent_base,
-                                                  const int64_t* __restrict__ indptr, const int64_t* __restrict__ out_ptr,
-                                                  int64_t out_base, const int32_t* __restrict__ qlist,
+                                                  const int32_t* __restrict__ ents, const int64_t* __restrict__ indptr,
+                                                  const int64_t* __restrict__ out_ptr, const int32_t* __restrict__ qlist,
                                                   int32_t* __restrict__ idx_out, float* __restrict__ val_out) {
     __shared__ unsigned long long keys[N];
     const int q = qlist[blockIdx.x];
     const int64_t b = indptr[q];
     const int m = (int)(indptr[q + 1] - b);
     const int kk = (int)(out_ptr[q + 1] - out_ptr[q]);
-    for (int i = threadIdx.x; i < m; i += 256) keys[i] = (uint32_t)ents[b - ent_base + i];
+    for (int i = threadIdx.x; i < m; i += 256) keys[i] = (uint32_t)ents[b + i];
     __syncthreads();
     int sort_n = 2;
     while (sort_n < m) sort_n <<= 1;
-    const int64_t o = out_ptr[q] - out_base;
+    const int64_t o = out_ptr[q];
     rescore_sort_emit<true>(keys, m, sort_n, P + (size_t)q * d, E, d, kk, idx_out + o, val_out + o);
 }
 
 // Rows of the slab path after rank_rows_full: pos / val (rows, kkc) = each row's list positions in ranking order and their
-// scores.  The first kk of row r, as entities, to the ragged output of its query.
+// scores.  The first kk of row r, as entities, to the ragged output of its query.  Both re-rankers end their slab path here.
 __global__ void rerank_compact(const int32_t* __restrict__ pos, const float* __restrict__ val, int rows, int kkc,
-                               const int32_t* __restrict__ row_query, const int32_t* __restrict__ ents, int64_t ent_base,
-                               const int64_t* __restrict__ indptr, const int64_t* __restrict__ out_ptr, int64_t out_base,
+                               const int32_t* __restrict__ row_query, const int32_t* __restrict__ ents,
+                               const int64_t* __restrict__ indptr, const int64_t* __restrict__ out_ptr,
                                int32_t* __restrict__ idx_out, float* __restrict__ val_out) {
     const size_t total = (size_t)rows * kkc;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         const size_t r = t / kkc, i = t - r * kkc;
         const int q = row_query[r];
-        const int64_t o = out_ptr[q];
-        if ((int64_t)i >= out_ptr[q + 1] - o) continue;      // (beyond this query's ranked depth: padding, or a shorter list)
-        idx_out[o - out_base + i] = ents[indptr[q] - ent_base + pos[t]];
-        val_out[o - out_base + i] = val[t];
+        const int64_t o = out_ptr[q] + (int64_t)i;
+        if (o >= out_ptr[q + 1]) continue;      // (beyond this query's ranked depth: padding, or a shorter list)
+        idx_out[o] = ents[indptr[q] + pos[t]];
+        val_out[o] = val[t];
     }
 }
 

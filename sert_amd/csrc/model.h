@@ -338,54 +338,78 @@ struct sert_model {
     sert::InStep instep;
 };
 
+namespace sert {
+// Device scratch of the candidate-list chain (host/rank_lists.inc: rank_lists_chunk), every array grown per chunk to that
+// chunk's sizes.  The cosine scorer keeps one for its lifetime; sert_ll_rank_candidates makes one per call.
+struct ListScratch {
+    DevBuf<int64_t> cptr;          // chunk-relative cand_indptr (Qc + 1), then the chunk-relative output offsets (Qc + 1)
+    DevBuf<int32_t> ents, qlist;   // the chunk's candidates; its queries (chunk-local) grouped by kernel
+    DevBuf<int32_t> idx;           // the chunk's ragged results
+    DevBuf<float> val;
+    DevBuf<float> slab;            // (rows, lmax) scores of the lists beyond LDS, padded
+    RankSortScratch sort;          // the counting-sort passes over the slab (kernels_rank.h)
+    DevBuf<int32_t> pos;           // (rows, kkc) the slab rows' list positions in ranking order, and their scores
+    DevBuf<float> pval;
+    std::vector<int64_t> h_cptr;   // host staging of cptr / qlist: read by the uploads until the caller has synchronised
+    std::vector<int32_t> h_qlist;
+    void release() {
+        cptr.release(); ents.release(); qlist.release(); idx.release(); val.release(); slab.release(); pos.release();
+        pval.release(); rank_scratch_free(sort);
+    }
+    ~ListScratch() { release(); }
+};
+}  // namespace sert
+
+// The device scratch of a scorer is grow-only arrays (DevBuf, common.h), one capacity each, reserved where they are used and
+// released in sert_scorer_destroy.  An allocation that fails leaves its array {nullptr, 0}: the call returns an error and the
+// scorer serves the next one.
 struct sert_scorer {
     int device = 0;
     hipStream_t stream = nullptr;
     int64_t V = 0;
     int dim = 0;
-    float* E = nullptr;      // (V, dim) L2-normalised entity table
-    float* P = nullptr;      // (Q, dim) query projections
-    float* S = nullptr;      // 2 x (QT, V) cosine slabs: query tiles alternate between two
-                             // streams so the GEMM of tile t+1 overlaps the top-k of tile t
+    float* E = nullptr;            // (V, dim) L2-normalised entity table (allocated once, by sert_scorer_create)
+    sert::DevBuf<float> P;         // (Q, dim) query projections
+    sert::DevBuf<float> S;         // 2 x (QT, V) cosine slabs: query tiles alternate between two
+                                   // streams so the GEMM of tile t+1 overlaps the top-k of tile t
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_ready = nullptr, ev_done = nullptr;
-    float* val = nullptr;    // (Q, k)
-    int32_t* idx = nullptr;  // (Q, k)
-    int64_t cap_q = 0, cap_qk = 0, cap_s = 0;
+    sert::DevBuf<float> val;       // (Q, k)
+    sert::DevBuf<int32_t> idx;     // (Q, k)
     // fused path (GEMM with filtering epilogue): sample cosines, thresholds, candidate lists
-    float* Ss = nullptr; float* thr = nullptr;
-    unsigned long long* cand = nullptr; unsigned char* cnt = nullptr;
-    int* nflag = nullptr; int* flag_list = nullptr;
-    float* Pc = nullptr; int32_t* idx_c = nullptr; float* val_c = nullptr;
-    int64_t cap_ss = 0, cap_ft = 0, cap_cand = 0, cap_flag = 0, cap_c = 0, cap_ck = 0;
+    sert::DevBuf<float> Ss, thr;
+    sert::DevBuf<unsigned long long> cand;
+    sert::DevBuf<unsigned char> cnt;
+    sert::DevBuf<int> nflag, flag_list;
+    sert::DevBuf<float> Pc, val_c;
+    sert::DevBuf<int32_t> idx_c;
     // bf16 prefilter (kernels_score_bf16.h): bf16 copies of E and of the current query tile,
     // rows zero-padded to kp columns
     bool bf16 = false, bf16_demoted = false;
     int kp = 0;
-    uint16_t* E16 = nullptr; uint16_t* P16 = nullptr;
-    int64_t cap_p16 = 0;
+    uint16_t* E16 = nullptr;       // (allocated once, like E)
+    sert::DevBuf<uint16_t> P16;
     // which path the rows took since sert_scorer_create (host counters, read by sert_debug_scorer_counts): [0] fused calls,
     // [1] those that filtered in bf16, [2] query chunks of the fused calls, [3] rows the fused path flagged and handed to the
     // materialising path, [4] rows of calls that went to the materialising path directly
     int64_t path_counts[5] = {0, 0, 0, 0, 0};
-    // sert_scorer_rank (host/api_scorer_rank.inc): scratch of its own, grown on demand, so that the cap_* bookkeeping of the
-    // other calls is not disturbed.  rP (Q, dim) normalised projections; rS (Qc, V) the cosine slab of one query chunk; rsort
-    // the scratch of the LSD passes (kernels_rank.h); ridx / rval two sets of (Qc, kk) results: chunk i's set travels to the host on stream2 while chunk i + 1 is sorted into the other
-    float* rP = nullptr; float* rS = nullptr;
-    sert::RankSortScratch rsort;
-    int32_t* ridx[2] = {nullptr, nullptr}; float* rval[2] = {nullptr, nullptr};
-    int64_t cap_rp = 0, cap_rs = 0, cap_rout = 0;
+    // sert_scorer_rank (host/api_scorer_rank.inc): scratch of its own, so that the arrays of the other calls are not
+    // disturbed.  rP (Q, dim) normalised projections; ridx / rval two sets of (Qc, kk) results: chunk i's set travels to the
+    // host on stream2 while chunk i + 1 is sorted into the other.  Its (Qc, V) cosine slab and the scratch of its LSD passes
+    // are lists.slab and lists.sort: the candidate calls below use the same two for their long lists, and every call of a
+    // scorer returns with nothing queued, so the two never hold them at once.
+    sert::DevBuf<float> rP;
+    sert::DevBuf<int32_t> ridx[2];
+    sert::DevBuf<float> rval[2];
     hipEvent_t ev_rsorted[2] = {nullptr, nullptr}, ev_rcopy0[2] = {nullptr, nullptr}, ev_rcopied[2] = {nullptr, nullptr};
     // [0] sert_scorer_rank calls, [1] their query chunks, rows ranked by [2] the top-k path, [3] the LDS sort, [4] the LSD
     // passes, [5] microseconds the copies of [3] and [4]'s results took on the second stream (sert_debug_scorer_rank_counts)
     int64_t rank_counts[6] = {0, 0, 0, 0, 0, 0};
-    // sert_scorer_pairs / sert_scorer_rank_candidates (host/api_scorer_rerank.inc), grown on demand; they also use rP, rS and
-    // rsort above.  cptr (2 (Q + 1)) the call's indptr and behind it its output offsets; per chunk: cents its candidates, cq its
-    // queries grouped by kernel, csptr the prefix of the slab rows' lengths, cidx / cval its ragged results, cpos / cpval
-    // the slab rows' (rows, kkc) list positions and scores
-    int64_t* cptr = nullptr; int32_t* cents = nullptr; int32_t* cq = nullptr; int64_t* csptr = nullptr;
-    int32_t* cidx = nullptr; float* cval = nullptr; int32_t* cpos = nullptr; float* cpval = nullptr;
-    int64_t cap_cptr = 0, cap_cents = 0, cap_cq = 0, cap_csptr = 0, cap_cidx = 0, cap_cval = 0, cap_cpos = 0, cap_cpval = 0;
+    // sert_scorer_pairs / sert_scorer_rank_candidates (host/api_scorer_rerank.inc): rP above and the list chain's scratch
+    // (the pair call keeps its indptr in lists.cptr, a chunk's candidates in lists.ents and their values in lists.val);
+    // csptr is the cosine ranker's own: the prefix of the slab rows' lengths its pair kernel walks
+    sert::ListScratch lists;
+    sert::DevBuf<int64_t> csptr;
     // [0] calls of the two, [1] their chunks, queries ranked by [2] the LDS kernel, [3] the slab and the counting-sort passes,
     // [4] pairs scored, [5] empty lists (sert_debug_scorer_rerank_counts)
     int64_t rerank_counts[6] = {0, 0, 0, 0, 0, 0};

@@ -109,13 +109,7 @@ static int rccl_load() {
     } while (0)
 
 // ---- small helpers -----------------------------------------------------------
-template <typename T>
-static int dmalloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) return 0;
-    SERT_HIP(hipMalloc((void**)p, count * sizeof(T)));
-    return 0;
-}
+// (dmalloc and the grow-only DevBuf: common.h)
 template <typename T>
 static int dzalloc(T** p, size_t count, hipStream_t s) {
     SERT_TRY(dmalloc(p, count));
@@ -175,6 +169,8 @@ static void invalidate_speculation(sert_model* m) {
 #include "host/optimizer_and_loss.inc"
 
 #include "host/rank_rows.inc"
+
+#include "host/rank_lists.inc"   // (behind rank_rows.inc, in front of its two callers api_scorer_rerank.inc / api_ll_rerank.inc)
 
 }  // namespace sert
 

@@ -16,6 +16,13 @@ WIDTHS = (4, 18, 128, 300)
 K_LENGTHS = (0, 1, 3, 40, 1500, 2000, 8500, 0, 5)
 K_VALUES = (1, 5, 1500, 20000)
 
+# two chunks of several queries each: the second starts at query 4, behind non-zero candidate and output offsets, and holds two
+# slab rows of unequal length (a padded slab), lists in two LDS classes and an empty list
+CHUNK_LENGTHS = (8200, 300, 8300, 5, 8250, 1100, 0, 8193, 2000)
+CHUNK_BOUNDS = [0, 4, 9]
+CHUNK_BUDGETS = {None: 1000000, 7: 600000}       # k -> SERT_SCORE_RANK_BUDGET under which the planner cuts at CHUNK_BOUNDS
+SORT_MAX_BINS, SORT_TILE = 2048, 2048            # csrc/kernels_sort.h kSortMaxBins, kSortTile
+
 
 def ladder(V):
     """The list lengths of an exact problem over V entities."""
@@ -70,6 +77,43 @@ def form_case():
     E, P = U.gaussian_score_problem(FORM_V, 16, len(FORM_LENGTHS), seed=43)
     rng = np.random.RandomState(4301)
     return E, P, [draw_list(rng, FORM_V, n) for n in FORM_LENGTHS]
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_case():
+    """Lists of CHUNK_LENGTHS over a table of FORM_V entities: (E, P, lists)."""
+    E, P = U.gaussian_score_problem(FORM_V, 16, len(CHUNK_LENGTHS), seed=59)
+    rng = np.random.RandomState(5901)
+    return E, P, [draw_list(rng, FORM_V, n) for n in CHUNK_LENGTHS]
+
+
+def plan_chunks(lengths, k, budget):
+    """sert_scorer_rank_candidates' planner restated (host/api_scorer_rerank.inc, ListShape::bytes of host/rank_lists.inc): the
+    query bounds of its chunks.  A chunk takes the next query while its footprint stays within `budget` bytes -- 4 a candidate,
+    8 a ranked entry and, for its lists beyond LDS_MAX, the (rows, lmax) slab, the sort scratch over it (16 bytes an element
+    and the histograms) and the (rows, min(k, lmax)) positions and scores -- and its slab fits one sorted chunk; its first
+    query always."""
+    def footprint(pairs, outs, rows, lmax):
+        b = pairs * 4 + outs * 8
+        if rows:
+            n = rows * lmax
+            b += n * 4 + n * 16 + (SORT_MAX_BINS * -(-n // SORT_TILE) + SORT_MAX_BINS) * 4 + rows * (lmax if k is None else min(k, lmax)) * 8
+        return b
+
+    bounds, q = [0], 0
+    while q < len(lengths):
+        pairs = outs = rows = lmax = 0
+        q0 = q
+        while q < len(lengths):
+            n = lengths[q]
+            t = (pairs + n, outs + (n if k is None else min(k, n)), rows + (n > LDS_MAX), max(lmax, n) if n > LDS_MAX else lmax)
+            fits = not t[2] or (t[2] <= SORT_MAX_BINS and t[2] * t[3] <= 2 ** 31 - 2 ** 20)
+            if q > q0 and (not fits or footprint(*t) > budget):
+                break
+            pairs, outs, rows, lmax = t
+            q += 1
+        bounds.append(q)
+    return bounds
 
 
 @functools.lru_cache(maxsize=None)

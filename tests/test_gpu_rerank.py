@@ -168,6 +168,25 @@ def test_a_query_does_not_depend_on_the_call(hip_lib, monkeypatch):
     sc.close()
 
 
+@pytest.mark.parametrize('k', [None, 7])
+def test_chunks_of_several_queries_are_ranked_chunk_relative(hip_lib, monkeypatch, k):
+    """Two chunks, [0, 4) and [4, 9) (tests/test_rerank_inputs_cpu.py proves the plan): the second one's kernels see its
+    queries, candidates and output offsets counted from query 4, a padded slab of two rows, LDS lists and an empty list."""
+    E, P, lists = R.chunk_case()
+    sc = C.Scorer(E)
+    want, added = _counted(sc, lambda: _ranked(sc, P, lists, k))
+    assert added[CHUNKS] == 1, added
+    monkeypatch.setenv('SERT_SCORE_RANK_BUDGET', str(R.CHUNK_BUDGETS[k]))
+    got, added = _counted(sc, lambda: _ranked(sc, P, lists, k))
+    monkeypatch.delenv('SERT_SCORE_RANK_BUDGET')
+    assert added[CHUNKS] == len(R.CHUNK_BOUNDS) - 1 == 2, added
+    assert added[LDS_QUERIES] == 4 and added[SLAB_QUERIES] == 4 and added[EMPTY] == 1, added
+    _same_lists(got, want, ('two chunks against one', k))
+    cos = _pair_cosines(sc, P, lists)
+    _same_lists(got, [R.expected_ranking(c, lst, k) for c, lst in zip(cos, lists)], ('two chunks against the pair cosines', k))
+    sc.close()
+
+
 # ---- 8. reuse --------------------------------------------------------------------------------------------------------------
 
 def test_a_reused_scorer_answers_as_a_fresh_one(hip_lib):

@@ -77,6 +77,33 @@ def test_form_prefilter_width_and_k_cases():
         assert np.all(np.diff(lst) > 0)
 
 
+def test_chunk_case_is_cut_into_two_chunks_of_several_queries():
+    """The planner's arithmetic restated with kRankLdsMax = 8192, kSortMaxBins = 2048 and kSortTile = 2048: the budgets of
+    CHUNK_BUDGETS cut CHUNK_LENGTHS at queries [0, 4) and [4, 9) -- and so does every budget from 800 000 to 1 100 000 for the
+    whole lists, so that 1 000 000 sits mid-range.  tests/test_gpu_rerank.py asserts the device's chunk count against this."""
+    assert (R.LDS_MAX, R.SORT_MAX_BINS, R.SORT_TILE) == (8192, 2048, 2048)
+    E, P, lists = R.chunk_case()
+    assert E.shape == (9000, 16) and P.shape == (9, 16)
+    assert tuple(len(x) for x in lists) == R.CHUNK_LENGTHS == (8200, 300, 8300, 5, 8250, 1100, 0, 8193, 2000)
+    for lst in lists:
+        assert lst.dtype == np.int32 and np.all(np.diff(lst) > 0)
+    assert R.CHUNK_BUDGETS == {None: 1000000, 7: 600000} and R.CHUNK_BOUNDS == [0, 4, 9]
+    for k, budget in R.CHUNK_BUDGETS.items():
+        assert R.plan_chunks(R.CHUNK_LENGTHS, k, budget) == R.CHUNK_BOUNDS, (k, budget)
+    for budget in range(800000, 1100001, 10000):
+        assert R.plan_chunks(R.CHUNK_LENGTHS, None, budget) == R.CHUNK_BOUNDS, budget
+    # the plan's other ends: everything in one chunk, one query per chunk
+    assert R.plan_chunks(R.CHUNK_LENGTHS, None, 2 << 30) == [0, 9]
+    assert R.plan_chunks(R.CHUNK_LENGTHS, None, 1) == list(range(10))
+    # what the second chunk holds: two slab rows of unequal length, two lists of the 2048-entry LDS kernel (the first chunk's
+    # two are of the 1024-entry one), an empty list
+    second = R.CHUNK_LENGTHS[4:]
+    slab = [n for n in second if n > R.LDS_MAX]
+    assert len(slab) == 2 and slab[0] != slab[1] and 0 in second
+    assert sorted(n for n in second if 0 < n <= R.LDS_MAX) == [1100, 2000] and sorted(n for n in R.CHUNK_LENGTHS[:4] if n <= R.LDS_MAX) == [5, 300]
+    assert sum(0 < n <= R.LDS_MAX for n in R.CHUNK_LENGTHS) == 4 and sum(n > R.LDS_MAX for n in R.CHUNK_LENGTHS) == 4
+
+
 @pytest.mark.parametrize('V', [1100, 8300])
 def test_special_expectations_put_nans_last_by_entity(V):
     E, P, lists = R.special_case(V)
