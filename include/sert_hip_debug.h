@@ -90,6 +90,22 @@ enum {
 };
 int sert_debug_nce_form(sert_model* m, int32_t* out, int n);
 
+/* What the LAST step of a fold-in handle launched (include/sert_hip_foldin.h; kernels in csrc/kernels_foldin.h, dispatch in
+ * csrc/host/api_foldin.inc: foldin_loss, foldin_grad) -- host record written where the launches are made, test hook, no device is
+ * touched: out[0] one of SERT_FOLDIN_LOSS_*, out[1] its template parameter (VECTOR: float4 chunks per lane; SCALAR: columns per
+ * lane), out[2] 1 for the training instance and 0 for the evaluating one, out[3] key bits of the counting sort (the smallest b
+ * with 2^b > num_new: the sentinel key is num_new itself), out[4] its digit passes, out[5] / out[6] VEC and NCH of
+ * foldin_chunk_reduce<VEC, NCH>, out[7] its column passes, out[8] one of SERT_EGRAD_FIXUP_*, out[9] the tiles of 2048 keys of the
+ * sort.  n <= 10; all zero before the first step.  An evaluation launches the loss kernel alone: it rewrites out[0..2] and leaves
+ * out[3..9] as the last training step left them.  tests/test_gpu_foldin_keys.py asserts through this that every key structure of
+ * tests/foldin_key_cases.py reaches the kernels it is there for. */
+enum {
+    SERT_FOLDIN_LOSS_NONE = 0,
+    SERT_FOLDIN_LOSS_VECTOR = 1,   /* foldin_nce<K, TRAIN>: d_e % 4 == 0, sixteen lanes per instance */
+    SERT_FOLDIN_LOSS_SCALAR = 2    /* foldin_nce_scalar<K, TRAIN>: any other d_e, one wave per instance */
+};
+int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n);
+
 /* What the LAST backward of this model launched for the per-word sums -- the word-table gradient of the vectorspace models
  * (word_grad_segsum) or dZu of the loglinear model (dzu_from_dj), both in csrc/host/lazy_segsum.inc over the tree of
  * csrc/word_index.h -- host record written where the launches are made, test hook, no device is touched:

@@ -71,7 +71,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -85,6 +85,7 @@ EXPORTS_FOLDIN = [
     'sert_foldin_set_eval_draws', 'sert_foldin_get_eval_draws',
 ]
 FOLDIN_ROWS, FOLDIN_M, FOLDIN_V = 0, 1, 2
+FOLDIN_LOSS_FORMS = ('none', 'vector', 'scalar')       # SERT_FOLDIN_LOSS_* (include/sert_hip_debug.h)
 
 
 # int (*sert_alltoall_fn)(void* user, const float* send, const int64_t* send_offsets, const int64_t* send_counts,
@@ -1171,6 +1172,18 @@ class FoldIn(object):
 
     def get_eval_draws(self):
         return int(self._lib.sert_foldin_get_eval_draws(self._h))
+
+    def plan(self):
+        """sert_debug_foldin_plan (test hook): what the last step of this handle launched -- 'loss' (none / vector / scalar),
+        'k' (its template parameter), 'train', 'sort_bits', 'passes', 'vec', 'nch' and 'col_passes' of foldin_chunk_reduce,
+        'fixup' (none / wave / workgroup), 'tiles' of the sort.  All zero before the first step; an evaluation rewrites the
+        first three entries only."""
+        v = (ctypes.c_int32 * 10)()
+        self._lib.sert_debug_foldin_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_foldin_plan(self._h, v, 10))
+        v = [int(x) for x in v]
+        return {'loss': FOLDIN_LOSS_FORMS[v[0]], 'k': v[1], 'train': bool(v[2]), 'sort_bits': v[3], 'passes': v[4], 'vec': v[5],
+                'nch': v[6], 'col_passes': v[7], 'fixup': EGRAD_FIXUPS[v[8]], 'tiles': v[9]}
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:

@@ -32,6 +32,8 @@ struct sert_foldin {
     float* d_losses = nullptr;       // multi-step loss ring
     int64_t d_losses_cap = 0;
     int64_t step = 0, eval_draws = 0;
+    // what the last step launched, recorded where the launches are made: sert_debug_foldin_plan (sert_hip_debug.h)
+    int32_t plan[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 int sert_foldin_destroy(sert_foldin* f) {
@@ -239,6 +241,7 @@ static int foldin_loss(sert_foldin* f, int64_t batch, bool train, const float** 
         }
 #undef SERT_FI_CASE
         *parts = f->red_loss; *n_parts = cdiv(B, 16);
+        f->plan[0] = SERT_FOLDIN_LOSS_VECTOR; f->plan[1] = cdiv(de / 4, 16);
     } else {
         const dim3 grid(cdiv(B, 4)), block(256);
 #define SERT_FI_CASE(K)                                                                                   \
@@ -253,8 +256,10 @@ static int foldin_loss(sert_foldin* f, int64_t batch, bool train, const float** 
         }
 #undef SERT_FI_CASE
         *parts = f->rowloss; *n_parts = B;     // (no workgroup partials on this path: the rows' losses themselves)
+        f->plan[0] = SERT_FOLDIN_LOSS_SCALAR; f->plan[1] = cdiv(de, 64);
     }
 #undef SERT_FI_ARGS
+    f->plan[2] = train ? 1 : 0;
     return 0;
 }
 
@@ -284,23 +289,27 @@ static int foldin_grad(sert_foldin* f, int64_t batch) {
         kin = kout;
         vin = vout;
     }
+    f->plan[3] = bits; f->plan[4] = passes; f->plan[9] = (int32_t)cdiv((int64_t)total, kSortTile);
     const int chunks = cdiv(total, kEChunk);
     const dim3 cgrid(cdiv(chunks, 16)), blk(256);
 #define SERT_FI_ARGS (const int32_t*)f->key_sorted, (const int32_t*)f->pair_sorted, (const float*)f->coef, T, total, z + 1, de, N, \
                  f->G, f->ehead, f->etail, run_start, run_end
     if (de % 4 == 0) {
         const int nch = cdiv(de / 4, 16);
-        if (nch <= 1)      launch((foldin_chunk_reduce<4, 1>), cgrid, blk, 0, s, SERT_FI_ARGS);
-        else if (nch <= 2) launch((foldin_chunk_reduce<4, 2>), cgrid, blk, 0, s, SERT_FI_ARGS);
-        else if (nch <= 5) launch((foldin_chunk_reduce<4, 5>), cgrid, blk, 0, s, SERT_FI_ARGS);
-        else               launch((foldin_chunk_reduce<4, 8>), cgrid, blk, 0, s, SERT_FI_ARGS);
+        if (nch <= 1)      { launch((foldin_chunk_reduce<4, 1>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 1; }
+        else if (nch <= 2) { launch((foldin_chunk_reduce<4, 2>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 2; }
+        else if (nch <= 5) { launch((foldin_chunk_reduce<4, 5>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 5; }
+        else               { launch((foldin_chunk_reduce<4, 8>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 8; }
+        f->plan[5] = 4; f->plan[7] = cdiv(de / 4, 16 * f->plan[6]);
     } else {
         launch((foldin_chunk_reduce<1, 4>), cgrid, blk, 0, s, SERT_FI_ARGS);
+        f->plan[5] = 1; f->plan[6] = 4; f->plan[7] = cdiv(de, 16 * 4);
     }
 #undef SERT_FI_ARGS
     // the fix-up over the N new rows only (kernels_egrad.h, as it is): rows no pair hit get a zero gradient row, runs that
     // cross chunks their carries in chunk order.  Few rows: one workgroup per row (long runs).
     const bool few = N < 256;
+    f->plan[8] = few ? SERT_EGRAD_FIXUP_WORKGROUP : SERT_EGRAD_FIXUP_WAVE;
     if (de % 4 == 0) {
         if (few) launch((egrad_fixup_wg<4>), dim3(N), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
         else launch((egrad_fixup<4>), dim3(cdiv(N, 4)), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
@@ -455,3 +464,9 @@ int sert_foldin_set_eval_draws(sert_foldin* f, int64_t n) {
     return 0;
 }
 int64_t sert_foldin_get_eval_draws(sert_foldin* f) { return f ? f->eval_draws : -1; }
+
+int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n) {
+    if (!f || !out || n < 1 || n > 10) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = f->plan[i];
+    return 0;
+}
