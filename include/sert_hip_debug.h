@@ -77,7 +77,8 @@ int sert_debug_egrad_plan(sert_model* m, int32_t* out, int n);
 /* The NCE score / loss / gradient kernel the LAST vectorspace forward of this model launched (vs_loss in
  * csrc/host/step_vectorspace.inc, kernels in csrc/kernels_vs.h; sert_train_batch, sert_eval_batch, ...) -- host record written
  * where the launch is made, test hook, no device is touched: out[0] one of SERT_NCE_FORM_*, out[1] the float4 chunks per lane NCH
- * (REGS, PER_CANDIDATE) or the columns per lane NPL (SCALAR), out[2] MAXC of vs_nce_regs<NCH, ., MAXC> (0 for the other forms),
+ * (REGS, PER_CANDIDATE) or the columns per lane NPL (SCALAR), out[2] MAXC of vs_nce_regs<NCH, ., MAXC> (0 for the other forms;
+ * 6 for z + 1 <= 6, 11 for z + 1 == 11 exactly, 12 for every other z + 1 <= 12),
  * out[3] 1 for the training instance and 0 for the evaluating one, out[4] workgroups of the launch, out[5] the per-workgroup loss
  * partials the kernel left for the loss reduction (0: the reduction starts from the row losses).  n <= 6; all zero before the
  * first forward and for a model that has no NCE loss.  tests/test_gpu_nce_forms.py asserts through this that every case of

@@ -540,7 +540,7 @@ class Engine(object):
 
     def nce_form(self):
         """sert_debug_nce_form (test hook): the NCE loss kernel the last vectorspace forward launched -- 'form' (none / regs /
-        per_candidate / scalar), 'param' (NCH or NPL), 'maxc' (regs only, else 0), 'train', 'workgroups' and 'loss_partials'.
+        per_candidate / scalar), 'param' (NCH or NPL), 'maxc' (regs only, else 0: 6 for z + 1 <= 6, 11 for z + 1 == 11, else 12), 'train', 'workgroups' and 'loss_partials'.
         All zero before the first forward and for a model without an NCE loss."""
         v = (ctypes.c_int32 * 6)()
         self._lib.sert_debug_nce_form.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]

@@ -112,6 +112,19 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += dpp_mov<0x128>(v);   // row_ror:8
     return v;
 }
+// lane u of each aligned group of sixteen lanes, to all sixteen of the group (DPP row_newbcast: one VALU issue; u a constant
+// after unrolling)
+__device__ __forceinline__ int row16_bcast(int v, int u) {
+    switch (u & 15) {
+#define SERT_ROW_BCAST(U) case U: return __builtin_amdgcn_update_dpp(0, v, 0x150 + U, 0xF, 0xF, true);
+        SERT_ROW_BCAST(0) SERT_ROW_BCAST(1) SERT_ROW_BCAST(2) SERT_ROW_BCAST(3) SERT_ROW_BCAST(4) SERT_ROW_BCAST(5)
+        SERT_ROW_BCAST(6) SERT_ROW_BCAST(7) SERT_ROW_BCAST(8) SERT_ROW_BCAST(9) SERT_ROW_BCAST(10) SERT_ROW_BCAST(11)
+        SERT_ROW_BCAST(12) SERT_ROW_BCAST(13) SERT_ROW_BCAST(14)
+        default: return __builtin_amdgcn_update_dpp(0, v, 0x15F, 0xF, 0xF, true);
+#undef SERT_ROW_BCAST
+    }
+}
+__device__ __forceinline__ float row16_bcast(float v, int u) { return __int_as_float(row16_bcast(__float_as_int(v), u)); }
 __device__ __forceinline__ float row16_max(float v) {
     v = fmaxf(v, dpp_mov<0xB1>(v));
     v = fmaxf(v, dpp_mov<0x4E>(v));

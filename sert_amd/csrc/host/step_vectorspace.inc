@@ -194,25 +194,37 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         m->nce_form[0] = SERT_NCE_FORM_PER_CANDIDATE; m->nce_form[1] = N;                    \
         break;
 #define SERT_NCE_REGS(N, C)                                                                  \
-    launch((vs_nce_regs<N, TRAIN, C>), grid, block, 0, m->stream, m->T, m->re, y,            \
-           m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B, c.num_negatives,               \
-           de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);                            \
+    /* a training step at d_e == 64 N, every lane full: the instance without chunk masks */  \
+    if (TRAIN && de == 64 * N)                                                               \
+        launch((vs_nce_regs<N, TRAIN, C, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y, \
+               m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B, c.num_negatives,           \
+               de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);                        \
+    else                                                                                     \
+        launch((vs_nce_regs<N, TRAIN, C, false>), grid, block, 0, m->stream, m->T, m->re, y, \
+               m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B, c.num_negatives,           \
+               de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);                        \
     m->nce_form[0] = SERT_NCE_FORM_REGS; m->nce_form[1] = N; m->nce_form[2] = C
             static const bool no_regs = variant_knob("SERT_NCE_PER_CANDIDATE") != nullptr;
             const int nc = c.num_negatives + 1;
             // (d_e = 300, five float4 per lane and candidate: 256 VGPRs + AGPR spills, one wave per SIMD --
             //  191 us against 169 us for the per-candidate kernel at C4: the limit stays at four)
             if (!no_regs && nch <= 4 && nc <= 12) {
-                // every candidate row of a row in registers (kernels_vs.h: vs_nce_regs)
-                const int key = nch * 2 + (nc > 6 ? 1 : 0);
+                // every candidate row of a row in registers (kernels_vs.h: vs_nce_regs).  MAXC: 6 for z + 1 <= 6; 11 for
+                // z + 1 == 11 exactly (z = 10, the reference's default: no twelfth row fetched for nothing, and d_e = 128 fits
+                // four waves per SIMD); 12 for every other z + 1 <= 12
+                const int key = nch * 3 + (nc <= 6 ? 0 : nc == 11 ? 1 : 2);
                 switch (key) {
-                    case 2: SERT_NCE_REGS(1, 6); break;
-                    case 3: SERT_NCE_REGS(1, 12); break;
-                    case 4: SERT_NCE_REGS(2, 6); break;
-                    case 5: SERT_NCE_REGS(2, 12); break;
-                    case 6: SERT_NCE_REGS(3, 6); break;
-                    case 7: SERT_NCE_REGS(3, 12); break;
-                    case 8: SERT_NCE_REGS(4, 6); break;
+                    case 3: SERT_NCE_REGS(1, 6); break;
+                    case 4: SERT_NCE_REGS(1, 11); break;
+                    case 5: SERT_NCE_REGS(1, 12); break;
+                    case 6: SERT_NCE_REGS(2, 6); break;
+                    case 7: SERT_NCE_REGS(2, 11); break;
+                    case 8: SERT_NCE_REGS(2, 12); break;
+                    case 9: SERT_NCE_REGS(3, 6); break;
+                    case 10: SERT_NCE_REGS(3, 11); break;
+                    case 11: SERT_NCE_REGS(3, 12); break;
+                    case 12: SERT_NCE_REGS(4, 6); break;
+                    case 13: SERT_NCE_REGS(4, 11); break;
                     default: SERT_NCE_REGS(4, 12); break;
                 }
             } else

@@ -317,7 +317,13 @@ __global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
 // on all sixteen lanes.  The per-candidate kernel above walks id -> row -> dot -> sigmoid z + 1 times
 // in series with two waves per SIMD in flight (B = 8192 is 2048 waves), which is what its 40 us
 // were; here a wave has two dependent memory round trips in all.
-template <int NCH, bool TRAIN, int MAXC>
+// MAXC is 6, 11 or 12 (vs_loss): 11 is the exact count of z = 10, where a twelfth slot would fetch, dot and scale by 0 one
+// more row per pair.  Candidate u's id and du reach the row's sixteen lanes by a DPP row broadcast, not through the LDS
+// crossbar.  FULL (training steps at d_e == 64 NCH): every lane holds NCH whole chunks, so there is no `c < chunks` mask,
+// which costs every load a branch of its own and a zero fill -- about 280 of the 1000 instructions of <2, true, 11>, 2 of its
+// 31 us at batch 65536.  <2, true, 11, true> -- d_e = 128, z = 10 -- has 127 VGPRs: four waves per SIMD for three.  The
+// evaluating instances have no such form: <2, false, 6> and <2, false, 12> would lose waves by it.
+template <int NCH, bool TRAIN, int MAXC, bool FULL>
 __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
                                                    const float* __restrict__ Re,
                                                    const int32_t* __restrict__ y,
@@ -328,7 +334,6 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
                                                    float inv_batch, float* __restrict__ wg_loss) {
     __shared__ float wg_red[16];
     const int l = threadIdx.x & 15;
-    const int lane = threadIdx.x & 63;
     const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool valid = i_raw < B;
     const int i = valid ? i_raw : B - 1;
@@ -340,17 +345,17 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
 #pragma unroll
     for (int q = 0; q < NCH; ++q) {
         const int c = l + 16 * q;
-        t[q] = (c < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * c)
+        t[q] = (FULL || c < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * c)
                             : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     float4 er[MAXC][NCH];
 #pragma unroll
     for (int u = 0; u < MAXC; ++u) {
-        const int e = __shfl(my_e, (lane & 48) | u);
+        const int e = row16_bcast(my_e, u);
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
             const int c = l + 16 * q;
-            er[u][q] = (c < chunks) ? *reinterpret_cast<const float4*>(Re + (size_t)e * de + 4 * c)
+            er[u][q] = (FULL || c < chunks) ? *reinterpret_cast<const float4*>(Re + (size_t)e * de + 4 * c)
                                     : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
@@ -395,7 +400,7 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
         for (int q = 0; q < NCH; ++q) dp[q] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int u = 0; u < MAXC; ++u) {
-            const float du_u = __shfl(du, (lane & 48) | u);   // 0 for candidates past z
+            const float du_u = row16_bcast(du, u);   // 0 for candidates past z
 #pragma unroll
             for (int q = 0; q < NCH; ++q) {
                 dp[q].x += du_u * er[u][q].x; dp[q].y += du_u * er[u][q].y;
@@ -405,7 +410,7 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
             const int c = l + 16 * q;
-            if (c >= chunks || !valid) continue;
+            if ((!FULL && c >= chunks) || !valid) continue;
             float4 o;
             o.x = (t[q].x >= -SERT_CLIP_HI && t[q].x <= SERT_CLIP_HI) ? dp[q].x * (1.0f - t[q].x * t[q].x) : 0.f;
             o.y = (t[q].y >= -SERT_CLIP_HI && t[q].y <= SERT_CLIP_HI) ? dp[q].y * (1.0f - t[q].y * t[q].y) : 0.f;
