@@ -13,6 +13,15 @@ The word table, the projection and the trained entity rows stay as they are; onl
 ``--model_output`` is a model dump with R_e extended by the new rows, ``--meta_output`` the meta with the entity index
 and the associations extended (new entity e of ``--new_meta`` gets internal index V_e + e); bin/query.py serves the pair
 unchanged.  A new entity id that ``--meta`` already knows is refused.
+
+With ``--refresh`` such an id is not refused: the entity GAINED documents (new reviews of a known product), and its trained
+row learns too, in place -- it keeps its internal index, the output dump has its row replaced and the rows of the really
+new entities appended (V_e is unchanged when nothing is new), the output meta has its associations merged
+(sert_amd.foldin.merge_meta).  A refreshed row starts from its trained value and learns from the instances given: to keep
+its old evidence, pass the entity's old documents along with the new ones.
+
+    python bin/fold_in.py --refresh --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
+        --model_output model_15_ref.bin --meta_output meta_ref
 """
 import argparse
 import logging
@@ -41,6 +50,11 @@ def build_parser():
     parser.add_argument('--regularization_lambda', type=float, default=0.01)
     parser.add_argument('--seed', type=int, default=None)
     parser.add_argument('--device', type=int, default=0)
+    parser.add_argument('--refresh', action='store_true', default=False,
+                        help='entity ids of --new_meta that --meta knows are refreshed (their trained rows learn from the '
+                             'instances given, in place) instead of refused; the rest are new.  A refreshed row learns from '
+                             'the instances given: to keep its old evidence, pass the entity\'s old documents along with '
+                             'the new ones.')
     parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     return parser
@@ -80,17 +94,25 @@ def main(argv=None):
         raise RuntimeError('%s was not prepared with --vocabulary_from %s: the token ids differ.' % (args.new_meta, args.meta))
     new_index = new_meta[3]
     new_entity_ids = [new_index[e] for e in range(len(new_index))]
-    # (refuses a known entity id before anything is computed)
-    extended_meta = foldin.extend_meta(meta, new_entity_ids, dict((e, new_meta[4].get(e, [])) for e in new_entity_ids))
+    associations = dict((e, new_meta[4].get(e, [])) for e in new_entity_ids)
+    refresh = None
+    if args.refresh:
+        extended_meta, refresh, added_ids, slots = foldin.merge_meta(meta, new_entity_ids, associations)
+    else:
+        # (refuses a known entity id before anything is computed)
+        extended_meta = foldin.extend_meta(meta, new_entity_ids, associations)
+        added_ids = new_entity_ids
 
     x, y, w = one_hot_training_set(args.data)
     assert y.size == 0 or int(y.max()) < len(new_entity_ids)
+    if args.refresh:
+        y = slots[y] if y.size else y           # (entity index of --new_meta -> slot)
     window_size = meta[0].window_size
-    new_rows = models._glorot_uniform((len(new_entity_ids), R_e.shape[1]))      # as bin/train.py initialises R_e
+    new_rows = models._glorot_uniform((len(added_ids), R_e.shape[1]))      # as bin/train.py initialises R_e
     fold = foldin.EntityFoldIn(
         R_w, R_e, predict_fn.W, predict_fn.b, new_rows, (x, y, w), batch_size=args.batch_size,
         num_negative_samples=args.num_negative_samples, regularization_lambda=args.regularization_lambda,
-        window_size=window_size, seed=args.seed, device=args.device)
+        window_size=window_size, seed=args.seed, device=args.device, refresh=refresh)
 
     mean, stddev = fold.train_error()
     logging.info('Epoch 0: fold-in error %.6f (stddev %.6f).', mean, stddev)
@@ -104,10 +126,15 @@ def main(argv=None):
         directory = os.path.dirname(path)
         if directory and not os.path.exists(directory):
             os.makedirs(directory)
-    foldin.write_dump(args.model_output, foldin.extend_dump(model_args, predict_fn, R_w, R_e, fold.get_new_representations()))
+    if args.refresh:
+        objects = foldin.refresh_dump(model_args, predict_fn, R_w, R_e, refresh, fold.get_refreshed_representations(),
+                                      fold.get_new_representations())
+    else:
+        objects = foldin.extend_dump(model_args, predict_fn, R_w, R_e, fold.get_new_representations())
+    foldin.write_dump(args.model_output, objects)
     foldin.write_meta(args.meta_output, extended_meta)
-    logging.info('Saved the extended model "%s" (%d + %d entities) and its meta "%s".', args.model_output, R_e.shape[0],
-                 len(new_entity_ids), args.meta_output)
+    logging.info('Saved the extended model "%s" (%d + %d entities, %d refreshed) and its meta "%s".', args.model_output,
+                 R_e.shape[0], len(added_ids), 0 if refresh is None else len(refresh), args.meta_output)
     fold.close()
 
 

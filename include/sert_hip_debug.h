@@ -107,6 +107,12 @@ enum {
 };
 int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n);
 
+/* How a fold-in handle addresses its trainable rows -- host record, test hook, no device is touched: out[0] 1 for the map form
+ * (sert_foldin_create_refresh: foldin_nce_map* look every negative up in slot_of) and 0 for sert_foldin_create, out[1]
+ * num_refresh, out[2] num_new, out[3] Nt = the rows of E.  n <= 4.  sert_debug_foldin_plan keeps its ten entries and their
+ * meaning for a refresh handle (num_new there reads Nt). */
+int sert_debug_foldin_table(sert_foldin* f, int32_t* out, int n);
+
 /* What the LAST backward of this model launched for the per-word sums -- the word-table gradient of the vectorspace models
  * (word_grad_segsum) or dZu of the loglinear model (dzu_from_dj), both in csrc/host/lazy_segsum.inc over the tree of
  * csrc/word_index.h -- host record written where the launches are made, test hook, no device is touched:

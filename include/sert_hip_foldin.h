@@ -50,7 +50,35 @@ enum { SERT_FOLDIN_ROWS = 0, SERT_FOLDIN_M = 1, SERT_FOLDIN_V = 2 };
 int sert_foldin_create(sert_model* m, int32_t num_new, const float* init_rows, const sert_foldin_config* cfg, sert_foldin** out);
 int sert_foldin_destroy(sert_foldin* f);
 
-/* The fold-in instances: x (M, n) int32 token ids in [0, V_w), y (M,) int32 in [0, num_new), w (M,) float32 instance
+/* REFRESH: a fold-in whose trainable table E is any set of rows of the extended table -- trained rows that gained documents
+ * (new reviews of a known product) and new entities, in one handle.  E has Nt = num_refresh + num_new rows, the SLOTS:
+ *     slot s < num_refresh      trained row refresh_ids[s]; its initial value is copied on the device from the model's R_e, after
+ *                               the preamble of sert_foldin_create
+ *     slot num_refresh + e      new entity e = row V_e + e of Ext; its initial value is init_new_rows[e]
+ * With ext_of_slot the row of Ext a slot stands for and Ext = concat(R_e, new rows) in which EVERY slot's current value is
+ * written to its row, a step on batch i is, against oracle/sert_oracle.py,
+ *     loss, grads, _ = VectorSpaceOracle(B, n, z, R_w, Ext, W, b, lambda).loss_and_grads(X, ext_of_slot[y], w, neg)
+ *     gradient       grads[0][ext_of_slot], the Nt rows in slot order, plus lambda / B * E
+ *     returned loss  sum(loss_i * w_i) / B + lambda / (2B) * sum(E * E) over the Nt trainable rows only
+ *     update         oracle.Adam over the single tensor E: zero moments, a step counter of the handle's own, dense over all
+ *                    Nt rows
+ * y at upload is a SLOT in [0, Nt): every instance's positive is a trainable row.  Negatives are ids of the extended table in
+ * [0, V_e + num_new), explicit or from the unchanged Philox sampler over V_e + num_new; a negative that names a refreshed row
+ * moves it, as in the oracle.  sert_foldin_get_rows / sert_foldin_set_rows take Nt * d_e values in slot order.  R_w, W, b and
+ * every trained row not in refresh_ids are never written; the snapshot's stale copy of a refreshed row is never read.  Upload,
+ * the projection slabs, train_batches, eval_batch, negatives_of_step and the step and sampler state work as on a handle of
+ * sert_foldin_create.  A refreshed row learns from the instances given: to keep its old evidence, upload the entity's old
+ * documents along with the new ones.
+ * refresh_ids: distinct, each in [0, V_e), any order; may be NULL iff num_refresh == 0.  init_new_rows: (num_new, d_e); may be
+ * NULL iff num_new == 0.  Refused with a message before any launch: num_refresh < 0 or num_new < 0; Nt < 1; a null array with
+ * a positive count; an id outside [0, V_e); a duplicate id; and everything sert_foldin_create refuses (loglinear, the
+ * full-softmax variant, a communicator, the config, d_e > 512, the size limits).  With num_refresh == 0 the handle holds the
+ * bits of sert_foldin_create(num_new) on the same inputs and seed. */
+int sert_foldin_create_refresh(sert_model* m, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
+                               const float* init_new_rows, const sert_foldin_config* cfg, sert_foldin** out);
+
+/* The fold-in instances: x (M, n) int32 token ids in [0, V_w), y (M,) int32 in [0, num_new) (a refresh handle: a slot in
+ * [0, Nt)), w (M,) float32 instance
  * weights or NULL (all 1).  Validated on the host (no kernel is launched on bad ids), then the projections
  * T = VectorSpaceOracle.forward(x, ..)['t'] = tanh(h W + b) of all M instances are computed and kept (the model's
  * forward: window mean, projection GEMM).  Batch i is rows [iB, (i + 1)B); a trailing M mod B instances are never
@@ -76,7 +104,8 @@ int sert_foldin_eval_batch(sert_foldin* f, int64_t batch, const int64_t* negativ
  * evaluation != 0, for the position-th evaluation draw.  A pure function of (seed, position, evaluation). */
 int sert_foldin_negatives_of_step(sert_foldin* f, int64_t position, int evaluation, int64_t* out);
 
-/* which = SERT_FOLDIN_ROWS: E; SERT_FOLDIN_M / SERT_FOLDIN_V: Adam's moments of E.  count must be num_new * d_e. */
+/* which = SERT_FOLDIN_ROWS: E; SERT_FOLDIN_M / SERT_FOLDIN_V: Adam's moments of E.  count must be num_new * d_e (a refresh
+ * handle: Nt * d_e, slot order). */
 int sert_foldin_get_rows(sert_foldin* f, int which, float* host, size_t count);
 int sert_foldin_set_rows(sert_foldin* f, int which, const float* host, size_t count);
 

@@ -71,7 +71,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -79,7 +79,7 @@ EXPORTS = [
 EXPORTS_REVAL_COUNTED = ['sert_reval_create_counted', 'sert_reval_judged_ranks']
 # ... and include/sert_hip_foldin.h, which sert_hip.h includes too (folding unseen entities into a trained model)
 EXPORTS_FOLDIN = [
-    'sert_foldin_create', 'sert_foldin_destroy', 'sert_foldin_upload', 'sert_foldin_num_batches',
+    'sert_foldin_create', 'sert_foldin_create_refresh', 'sert_foldin_destroy', 'sert_foldin_upload', 'sert_foldin_num_batches',
     'sert_foldin_train_batch', 'sert_foldin_train_batches', 'sert_foldin_eval_batch', 'sert_foldin_negatives_of_step',
     'sert_foldin_get_rows', 'sert_foldin_set_rows', 'sert_foldin_set_step', 'sert_foldin_get_step',
     'sert_foldin_set_eval_draws', 'sert_foldin_get_eval_draws',
@@ -189,6 +189,7 @@ def load():
     lib.sert_reval_run.argtypes = [vp, fp, fp, fp, fp]
     lib.sert_reval_destroy.argtypes = [vp]
     lib.sert_foldin_create.argtypes = [vp, i32, fp, ctypes.POINTER(SertFoldInConfig), ctypes.POINTER(vp)]
+    lib.sert_foldin_create_refresh.argtypes = [vp, fp, i32, i32, fp, ctypes.POINTER(SertFoldInConfig), ctypes.POINTER(vp)]
     lib.sert_foldin_destroy.argtypes = [vp]
     lib.sert_foldin_upload.argtypes = [vp, fp, fp, fp, i64]
     lib.sert_foldin_num_batches.argtypes = [vp]
@@ -1087,12 +1088,19 @@ class RetrievalEval(object):
 class FoldIn(object):
     """Owner of one sert_foldin handle (include/sert_hip_foldin.h): ``num_new`` entity rows learnt on top of the frozen
     parameters of ``engine`` (a vectorspace Engine), which are copied at construction -- the engine may train on or be
-    closed afterwards."""
+    closed afterwards.
+
+    ``refresh_ids`` (an array of trained internal indices, possibly empty; None: sert_foldin_create as ever): a REFRESH
+    handle (sert_foldin_create_refresh) whose ``num_rows = len(refresh_ids) + num_new`` trainable rows are slots -- the
+    refreshed trained rows in the order given, then the new rows; ``new_rows_init`` may then be None (no new entity), y at
+    upload is a slot, and get_rows / set_rows are in slot order."""
 
     def __init__(self, engine, new_rows_init, batch_size, num_negatives, lambda_, lr=1e-3, beta1=0.9, beta2=0.999,
-                 eps=1e-8, seed=0):
+                 eps=1e-8, seed=0, refresh_ids=None):
         self._lib = load()
         self._h = None
+        if new_rows_init is None and refresh_ids is not None:
+            new_rows_init = np.zeros((0, engine.cfg.entity_dim), dtype=np.float32)
         rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
         if rows.ndim != 2 or rows.shape[1] != engine.cfg.entity_dim:
             raise SertError('new_rows_init must be (num_new, entity_dim)')
@@ -1105,8 +1113,20 @@ class FoldIn(object):
         self.num_entities = int(engine.cfg.num_entities)
         self.window_size = int(engine.cfg.window_size)
         h = ctypes.c_void_p()
-        check(self._lib.sert_foldin_create(engine._h, self.num_new, rows.ctypes.data if rows.size else None,
-                                           ctypes.byref(c), ctypes.byref(h)))
+        if refresh_ids is None:
+            self.num_refresh = 0
+            check(self._lib.sert_foldin_create(engine._h, self.num_new, rows.ctypes.data if rows.size else None,
+                                               ctypes.byref(c), ctypes.byref(h)))
+        else:
+            given = np.asarray(refresh_ids)
+            ids = np.ascontiguousarray(given, dtype=np.int32)
+            if ids.ndim != 1 or not np.array_equal(ids, given):
+                raise SertError('refresh_ids must be a 1-d array of int32 entity indices')
+            self.num_refresh = int(ids.size)
+            check(self._lib.sert_foldin_create_refresh(engine._h, ids.ctypes.data if ids.size else None, self.num_refresh,
+                                                       self.num_new, rows.ctypes.data if rows.size else None,
+                                                       ctypes.byref(c), ctypes.byref(h)))
+        self.num_rows = self.num_refresh + self.num_new         # the trainable rows E
         self._h = h
 
     def upload(self, x, y, w=None):
@@ -1153,7 +1173,7 @@ class FoldIn(object):
         return out
 
     def get_rows(self, which=FOLDIN_ROWS):
-        out = np.empty((self.num_new, self.entity_dim), dtype=np.float32)
+        out = np.empty((self.num_rows, self.entity_dim), dtype=np.float32)
         check(self._lib.sert_foldin_get_rows(self._h, int(which), out.ctypes.data, out.size))
         return out
 
@@ -1184,6 +1204,14 @@ class FoldIn(object):
         v = [int(x) for x in v]
         return {'loss': FOLDIN_LOSS_FORMS[v[0]], 'k': v[1], 'train': bool(v[2]), 'sort_bits': v[3], 'passes': v[4], 'vec': v[5],
                 'nch': v[6], 'col_passes': v[7], 'fixup': EGRAD_FIXUPS[v[8]], 'tiles': v[9]}
+
+    def table(self):
+        """sert_debug_foldin_table (test hook): how this handle addresses its trainable rows -- 'map' (True: the loss kernels
+        that look a negative up in slot_of, sert_foldin_create_refresh), 'num_refresh', 'num_new', 'rows' (= Nt)."""
+        v = (ctypes.c_int32 * 4)()
+        self._lib.sert_debug_foldin_table.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+        check(self._lib.sert_debug_foldin_table(self._h, v, 4))
+        return {'map': bool(v[0]), 'num_refresh': int(v[1]), 'num_new': int(v[2]), 'rows': int(v[3])}
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:

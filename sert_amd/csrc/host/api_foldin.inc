@@ -6,7 +6,13 @@ struct sert_foldin {
     int device = -1;
     hipStream_t stream = nullptr;
     sert_foldin_config cfg;
-    int Vw = 0, Ve = 0, N = 0, dw = 0, de = 0, n = 0;
+    int Vw = 0, Ve = 0, N = 0, dw = 0, de = 0, n = 0;     // N: the trainable rows E (sert_foldin_create: the new rows)
+    // sert_foldin_create_refresh: E is num_refresh trained rows, then num_new new rows; slot_of (Ve + num_new): the slot of a
+    // row of the extended table or -1 (frozen); refresh_ids (num_refresh): the trained row of a slot.  map: the loss kernels
+    // that look a candidate up in slot_of (foldin_nce_map*); sert_foldin_create leaves it false and both arrays null.
+    int num_new = 0, num_refresh = 0;
+    bool map = false;
+    int32_t *slot_of = nullptr, *refresh_ids = nullptr;
     // the frozen snapshot
     float *rw = nullptr, *W = nullptr, *b = nullptr, *re = nullptr;
     // the new rows, Adam's moments, the gradient
@@ -46,14 +52,17 @@ int sert_foldin_destroy(sert_foldin* f) {
                     (void*)f->y, (void*)f->w, (void*)f->T, (void*)f->neg, (void*)f->neg_stage, (void*)f->coef, (void*)f->key,
                     (void*)f->key_sorted, (void*)f->pair_sorted, (void*)f->k_tmp, (void*)f->v_tmp, (void*)f->sort_hist,
                     (void*)f->sort_bin_total, (void*)f->run_bounds, (void*)f->ehead, (void*)f->etail, (void*)f->rowloss,
-                    (void*)f->red_loss, (void*)f->red_sq, (void*)f->d_loss, (void*)f->d_losses})
+                    (void*)f->red_loss, (void*)f->red_sq, (void*)f->d_loss, (void*)f->d_losses, (void*)f->slot_of,
+                    (void*)f->refresh_ids})
         (void)hipFree(p);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
     return 0;
 }
 
-static int foldin_create(sert_foldin* f, sert_model* m, int32_t num_new, const float* init_rows, const sert_foldin_config* cfg) {
+// map == false: sert_foldin_create (refresh_ids null, num_refresh 0).  map == true: sert_foldin_create_refresh.
+static int foldin_create(sert_foldin* f, sert_model* m, bool map, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
+                         const float* init_rows, const sert_foldin_config* cfg) {
     const auto& c = m->cfg;
     // ---- validation: everything the kernels index with is checked here ----
     if (c.kind == SERT_KIND_LOGLINEAR) SERT_FAIL("a fold-in needs a vectorspace model: a loglinear model has no entity rows to add");
@@ -61,16 +70,36 @@ static int foldin_create(sert_foldin* f, sert_model* m, int32_t num_new, const f
         SERT_FAIL("a fold-in needs the NCE vectorspace model: the full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX) is not supported");
     if (m->comm || m->host_ar || m->world > 1)
         SERT_FAIL("a fold-in of a data-parallel model (a communicator is attached) is not supported");
-    if (num_new < 1) SERT_FAIL("a fold-in needs at least one new entity (num_new >= 1)");
-    if (!init_rows) SERT_FAIL("null argument");
+    if (!map) {
+        if (num_new < 1) SERT_FAIL("a fold-in needs at least one new entity (num_new >= 1)");
+        if (!init_rows) SERT_FAIL("null argument");
+    } else {
+        if (num_refresh < 0 || num_new < 0) SERT_FAIL("a refresh needs num_refresh >= 0 and num_new >= 0");
+        if ((int64_t)num_refresh + num_new < 1) SERT_FAIL("a refresh needs at least one trainable row (num_refresh + num_new >= 1)");
+        if (num_refresh > 0 && !refresh_ids) SERT_FAIL("null refresh_ids with num_refresh > 0");
+        if (num_new > 0 && !init_rows) SERT_FAIL("null init_new_rows with num_new > 0");
+    }
     if (cfg->batch_size < 1 || cfg->num_negatives < 1) SERT_FAIL("a fold-in needs batch_size >= 1 and num_negatives >= 1");
     if (!(cfg->lambda_ >= 0.f)) SERT_FAIL("regularization lambda must be >= 0");
     if (c.entity_dim > 512) SERT_FAIL("entity_dim > 512 is not supported");
     if ((int64_t)c.num_entities + num_new > INT32_MAX) SERT_FAIL("more than 2^31 - 1 rows in the extended entity table");
     if ((int64_t)cfg->batch_size * (cfg->num_negatives + 1) > ((int64_t)1 << 30)) SERT_FAIL("batch_size * (num_negatives + 1) > 2^30");
+    // the slot of every row of the extended table (host; uploaded below): also what finds an id out of range or given twice
+    std::vector<int32_t> slot_of;
+    if (map) {
+        slot_of.assign((size_t)c.num_entities + (size_t)num_new, -1);
+        for (int32_t s = 0; s < num_refresh; ++s) {
+            const int32_t e = refresh_ids[s];
+            if (e < 0 || e >= c.num_entities) SERT_FAIL("refresh id out of range [0, num_entities)");
+            if (slot_of[(size_t)e] >= 0) SERT_FAIL("duplicate refresh id");
+            slot_of[(size_t)e] = s;
+        }
+        for (int32_t e = 0; e < num_new; ++e) slot_of[(size_t)c.num_entities + e] = num_refresh + e;
+    }
     SERT_HIP(hipSetDevice(c.device));
     f->device = c.device; f->cfg = *cfg;
-    f->Vw = c.vocab_size; f->Ve = c.num_entities; f->N = num_new; f->dw = c.word_dim; f->de = c.entity_dim; f->n = c.window_size;
+    f->map = map; f->num_new = num_new; f->num_refresh = num_refresh;
+    f->Vw = c.vocab_size; f->Ve = c.num_entities; f->N = num_refresh + num_new; f->dw = c.word_dim; f->de = c.entity_dim; f->n = c.window_size;
     const int B = cfg->batch_size, z = cfg->num_negatives, de = f->de, N = f->N;
     const size_t n_e = (size_t)N * de;
     // the parameters as a reader must see them (sert_get_tensor, sert_reval_run): every lazily updated word-table row brought
@@ -95,7 +124,24 @@ static int foldin_create(sert_foldin* f, sert_model* m, int32_t num_new, const f
     SERT_TRY(dzalloc(&f->m1, n_e, s));
     SERT_TRY(dzalloc(&f->m2, n_e, s));
     SERT_TRY(dmalloc(&f->G, n_e));
-    SERT_HIP(hipMemcpyAsync(f->E, init_rows, n_e * sizeof(float), hipMemcpyHostToDevice, s));
+    if (!map) {
+        SERT_HIP(hipMemcpyAsync(f->E, init_rows, n_e * sizeof(float), hipMemcpyHostToDevice, s));
+    } else {
+        const size_t n_r = (size_t)num_refresh * de;
+        if (num_new > 0)
+            SERT_HIP(hipMemcpyAsync(f->E + n_r, init_rows, (n_e - n_r) * sizeof(float), hipMemcpyHostToDevice, s));
+        SERT_TRY(dmalloc(&f->slot_of, slot_of.size()));
+        SERT_HIP(hipMemcpyAsync(f->slot_of, slot_of.data(), slot_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (num_refresh > 0) {
+            // the refreshed slots start from the model's rows as they are now: taken on the model's stream, behind the
+            // preamble above (and from the model's table, not from the snapshot: the two hold the same bits)
+            SERT_TRY(dmalloc(&f->refresh_ids, (size_t)num_refresh));
+            SERT_HIP(hipMemcpyAsync(f->refresh_ids, refresh_ids, (size_t)num_refresh * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+            launch(foldin_take_rows, dim3(grid_for((int64_t)n_r, 256, 1 << 16)), dim3(256), 0, m->stream, (const float*)m->re,
+                   (const int32_t*)f->refresh_ids, f->E, (int64_t)num_refresh, de);
+            SERT_HIP(hipGetLastError());
+        }
+    }
     const size_t total = (size_t)B * (z + 1);
     SERT_TRY(dmalloc(&f->neg, (size_t)B * z));
     SERT_TRY(dmalloc(&f->neg_stage, (size_t)B * z));
@@ -131,7 +177,25 @@ int sert_foldin_create(sert_model* m, int32_t num_new, const float* init_rows, c
     *out = nullptr;
     if (cfg->struct_size != sizeof(sert_foldin_config)) SERT_FAIL("sert_foldin_config size mismatch (ABI)");
     sert_foldin* f = new sert_foldin();
-    const int rc = foldin_create(f, m, num_new, init_rows, cfg);
+    const int rc = foldin_create(f, m, false, nullptr, 0, num_new, init_rows, cfg);
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        sert_foldin_destroy(f);
+        g_last_error = keep;
+        return rc;
+    }
+    *out = f;
+    return 0;
+}
+
+int sert_foldin_create_refresh(sert_model* m, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
+                               const float* init_new_rows, const sert_foldin_config* cfg, sert_foldin** out) {
+    refresh_gemm_choice();
+    if (!m || !cfg || !out) SERT_FAIL("null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(sert_foldin_config)) SERT_FAIL("sert_foldin_config size mismatch (ABI)");
+    sert_foldin* f = new sert_foldin();
+    const int rc = foldin_create(f, m, true, refresh_ids, num_refresh, num_new, init_new_rows, cfg);
     if (rc != 0) {
         const std::string keep = g_last_error;
         sert_foldin_destroy(f);
@@ -149,7 +213,9 @@ int sert_foldin_upload(sert_foldin* f, const int32_t* x, const int32_t* y, const
     const int n = f->n, dw = f->dw, de = f->de;
     // host-side validation: no kernel is launched on bad ids
     for (int64_t i = 0; i < M; ++i)
-        if (y[i] < 0 || y[i] >= f->N) SERT_FAIL("fold-in label out of range [0, num_new)");
+        if (y[i] < 0 || y[i] >= f->N)
+            SERT_FAIL(f->map ? "fold-in label out of range [0, num_refresh + num_new): y is a slot"
+                             : "fold-in label out of range [0, num_new)");
     for (int64_t i = 0; i < M * n; ++i)
         if (x[i] < 0 || x[i] >= f->Vw) SERT_FAIL("token id out of range [0, vocab_size)");
     SERT_HIP(hipSetDevice(f->device));
@@ -203,7 +269,7 @@ int64_t sert_foldin_num_batches(sert_foldin* f) { return f ? f->M / f->cfg.batch
 // the step's negatives into f->neg: the caller's (validated before anything is launched) or the Philox sampler's
 static int foldin_negatives(sert_foldin* f, const int64_t* negatives, uint64_t stream_pos) {
     const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
-    const int64_t ext = (int64_t)f->Ve + f->N;
+    const int64_t ext = (int64_t)f->Ve + f->num_new;
     if (negatives) {
         for (int64_t i = 0; i < count; ++i)
             if (negatives[i] < 0 || negatives[i] >= ext) SERT_FAIL("negative sample out of range [0, num_entities + num_new)");
@@ -217,8 +283,55 @@ static int foldin_negatives(sert_foldin* f, const int64_t* negatives, uint64_t s
     return 0;
 }
 
+// foldin_loss of a handle made by sert_foldin_create_refresh: the same dispatch over foldin_nce_map / foldin_nce_map_scalar
+static int foldin_loss_map(sert_foldin* f, int64_t batch, bool train, const float** parts, int* n_parts) {
+    const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de;
+    const size_t row0 = (size_t)batch * B;
+    const float* T = f->T + row0 * de;
+    const int32_t* y = f->y + row0;
+    const float* w = train ? f->w + row0 : (const float*)nullptr;
+    const float inv_batch = 1.0f / (float)B;
+    hipStream_t s = f->stream;
+#define SERT_FI_ARGS T, (const float*)f->re, (const float*)f->E, (const int32_t*)f->slot_of, y, (const int32_t*)f->neg, w, f->coef, f->key, f->rowloss, B, z, de, f->N, inv_batch
+    if (de % 4 == 0) {
+        const dim3 grid(cdiv(B, 16)), block(256);
+#define SERT_FI_CASE(K)                                                                                   \
+    case K:                                                                                               \
+        if (train) launch((foldin_nce_map<K, true>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);       \
+        else launch((foldin_nce_map<K, false>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);            \
+        break;
+        switch (cdiv(de / 4, 16)) {
+            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
+            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
+            default: SERT_FAIL("entity_dim > 512 is not supported");
+        }
+#undef SERT_FI_CASE
+        *parts = f->red_loss; *n_parts = cdiv(B, 16);
+        f->plan[0] = SERT_FOLDIN_LOSS_VECTOR; f->plan[1] = cdiv(de / 4, 16);
+    } else {
+        const dim3 grid(cdiv(B, 4)), block(256);
+#define SERT_FI_CASE(K)                                                                                   \
+    case K:                                                                                               \
+        if (train) launch((foldin_nce_map_scalar<K, true>), grid, block, 0, s, SERT_FI_ARGS);             \
+        else launch((foldin_nce_map_scalar<K, false>), grid, block, 0, s, SERT_FI_ARGS);                  \
+        break;
+        switch (cdiv(de, 64)) {
+            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
+            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
+            default: SERT_FAIL("entity_dim > 512 is not supported");
+        }
+#undef SERT_FI_CASE
+        *parts = f->rowloss; *n_parts = B;     // (no workgroup partials on this path: the rows' losses themselves)
+        f->plan[0] = SERT_FOLDIN_LOSS_SCALAR; f->plan[1] = cdiv(de, 64);
+    }
+#undef SERT_FI_ARGS
+    f->plan[2] = train ? 1 : 0;
+    return 0;
+}
+
 // the loss kernel on batch `batch` (train: weighted, coef and keys written); *parts / *n_parts: the loss partials it left
 static int foldin_loss(sert_foldin* f, int64_t batch, bool train, const float** parts, int* n_parts) {
+    if (f->map) return foldin_loss_map(f, batch, train, parts, n_parts);
     const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de;
     const size_t row0 = (size_t)batch * B;
     const float* T = f->T + row0 * de;
@@ -414,7 +527,7 @@ int sert_foldin_negatives_of_step(sert_foldin* f, int64_t position, int evaluati
     hipStream_t st = nullptr;
     if (hipStreamCreate(&st) != hipSuccess) { (void)hipFree(tmp); SERT_FAIL("hipStreamCreate failed"); }
     launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count, (int64_t)0,
-           (uint32_t)((int64_t)f->Ve + f->N), f->cfg.seed, (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0,
+           (uint32_t)((int64_t)f->Ve + f->num_new), f->cfg.seed, (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0,
            (uint4*)nullptr, (size_t)0);
     std::vector<int32_t> host((size_t)count);
     const hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
@@ -468,5 +581,12 @@ int64_t sert_foldin_get_eval_draws(sert_foldin* f) { return f ? f->eval_draws : 
 int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n) {
     if (!f || !out || n < 1 || n > 10) SERT_FAIL("bad argument");
     for (int i = 0; i < n; ++i) out[i] = f->plan[i];
+    return 0;
+}
+
+int sert_debug_foldin_table(sert_foldin* f, int32_t* out, int n) {
+    if (!f || !out || n < 1 || n > 4) SERT_FAIL("bad argument");
+    const int32_t v[4] = {f->map ? 1 : 0, f->num_refresh, f->num_new, f->N};
+    for (int i = 0; i < n; ++i) out[i] = v[i];
     return 0;
 }

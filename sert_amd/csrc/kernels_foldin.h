@@ -14,6 +14,9 @@
 //   egrad_fixup(_wg)      the carries of the runs that cross chunks, over the N new rows only (kernels_egrad.h, as it is)
 //   adam_l2               Adam + L2 + sum of squares over E (kernels_opt.h, as it is), finalize_loss
 // Order-fixed throughout, no floating-point atomic: a fold-in is bit-reproducible.
+// A REFRESH handle (sert_foldin_create_refresh: trained rows that gained documents learn too) runs the same step with
+// foldin_nce_map / foldin_nce_map_scalar in place of the loss kernel -- the trainable rows are slots found through a table --
+// and N := the number of slots; see below.
 #pragma once
 #include "common.h"
 #include "kernels_egrad.h"
@@ -147,6 +150,179 @@ __global__ __launch_bounds__(256) void foldin_nce_scalar(const float* __restrict
                 key[(size_t)i * (z + 1) + j] = e >= Ve ? e - Ve : N;
             }
         }
+    }
+    // (a NaN unit of the row: see row_nan)
+    float tsum = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) tsum += t[q];
+    loss += wave_sum(tsum) * 0.0f;
+    if (lane == 0) rowloss[i] = wi * loss;
+}
+
+// ---- a trainable table that is any subset of the extended table (sert_foldin_create_refresh) ----
+// The N trainable rows E are SLOTS: refreshed trained rows first, new rows behind.  slot_of (V_e + num_new int32, built once
+// at create) holds the slot of a row of the extended table, or -1 for a frozen one.  foldin_nce_map / foldin_nce_map_scalar are
+// foldin_nce / foldin_nce_scalar, changed only in how a candidate finds its row and key:
+//   negative e:  s = slot_of[e]; row = s >= 0 ? E + s d_e : Re + e d_e; key = s >= 0 ? s : N
+//   positive:    y[i] IS a slot: row = E + y[i] d_e, key = y[i] -- no lookup
+// so the snapshot's stale copy of a refreshed row is never read.  The lookup is a dependent 4-byte load in front of the row
+// fetch; z is a run-time value, so the lookups cannot all sit in registers ahead of the loop.  They run one candidate ahead
+// instead: while candidate j's row is fetched, the slot of candidate j + 1 and the id of candidate j + 2 are already in
+// flight (FoldinAhead; the reads past the last candidate are clamped onto it).  Same arithmetic in the same order as the
+// originals: with no refreshed row the two forms hold the same bits.
+
+// the rows of E that are trained rows: E[s] = Re[ids[s]] (create only)
+__global__ __launch_bounds__(256) void foldin_take_rows(const float* __restrict__ Re, const int32_t* __restrict__ ids,
+                                                        float* __restrict__ E, int64_t rows, int de) {
+    const int64_t total = rows * de;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = k / de;
+        E[k] = Re[(size_t)ids[s] * de + (k - s * de)];
+    }
+}
+
+// the candidates of one instance, looked up ahead of their use.  At the top of iteration j: s = the slot of candidate j (the
+// positive's y for j = 0), e = its id (unused for j = 0), (e1, s1) = candidate j + 1, e2 = the id of candidate j + 2.
+struct FoldinAhead {
+    const int32_t* __restrict__ nrow;
+    const int32_t* __restrict__ slot_of;
+    int z, e, s, e1, s1, e2;
+    __device__ __forceinline__ FoldinAhead(const int32_t* __restrict__ nrow_, const int32_t* __restrict__ slot_of_, int z_, int yi)
+        : nrow(nrow_), slot_of(slot_of_), z(z_), e(0), s(yi) {
+        e1 = nrow[0];                    // (z >= 1)
+        e2 = nrow[min(1, z - 1)];
+        s1 = slot_of[e1];
+    }
+    // issued in front of candidate j's row fetch; `commit` after the candidate's arithmetic
+    int e3, s2;
+    __device__ __forceinline__ void issue(int j) {
+        e3 = nrow[min(j + 2, z - 1)];
+        s2 = slot_of[e2];
+    }
+    __device__ __forceinline__ void commit() { e = e1; s = s1; e1 = e2; s1 = s2; e2 = e3; }
+    __device__ __forceinline__ const float* row(const float* __restrict__ Re, const float* __restrict__ E, int de) const {
+        return s >= 0 ? E + (size_t)s * de : Re + (size_t)e * de;
+    }
+    __device__ __forceinline__ int key(int N) const { return s >= 0 ? s : N; }
+};
+
+template <int NCH, bool TRAIN>
+__global__ __launch_bounds__(256) void foldin_nce_map(const float* __restrict__ T, const float* __restrict__ Re,
+                                                      const float* __restrict__ E, const int32_t* __restrict__ slot_of,
+                                                      const int32_t* __restrict__ y, const int32_t* __restrict__ neg,
+                                                      const float* __restrict__ w, float* __restrict__ coef,
+                                                      int32_t* __restrict__ key, float* __restrict__ rowloss, int B, int z,
+                                                      int de, int N, float inv_batch, float* __restrict__ wg_loss) {
+    __shared__ float wg_red[16];
+    const int l = threadIdx.x & 15;
+    // (rows past the end of a ragged last workgroup: computed on a clamped row, never stored -- no return in front of the
+    //  barrier below)
+    const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool valid = i_raw < B;
+    const int i = valid ? i_raw : B - 1;
+    const int chunks = de >> 2;  // de % 4 == 0 on this path
+    FoldinAhead c(neg + (size_t)i * z, slot_of, z, y[i]);
+    float4 t[NCH], p[NCH];
+#pragma unroll
+    for (int q = 0; q < NCH; ++q) {
+        const int cc = l + 16 * q;
+        t[q] = (cc < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * cc)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        p[q].x = fminf(fmaxf(t[q].x, -SERT_CLIP_HI), SERT_CLIP_HI);
+        p[q].y = fminf(fmaxf(t[q].y, -SERT_CLIP_HI), SERT_CLIP_HI);
+        p[q].z = fminf(fmaxf(t[q].z, -SERT_CLIP_HI), SERT_CLIP_HI);
+        p[q].w = fminf(fmaxf(t[q].w, -SERT_CLIP_HI), SERT_CLIP_HI);
+    }
+    const float wi = TRAIN ? w[i] : 1.f;
+    const float g = wi * inv_batch;
+    float loss = 0.f;
+    for (int j = 0; j <= z; ++j) {
+        c.issue(j);
+        const float* __restrict__ row = c.row(Re, E, de);
+        float part = 0.f;
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) {
+            const int cc = l + 16 * q;
+            const float4 er = (cc < chunks) ? *reinterpret_cast<const float4*>(row + 4 * cc) : make_float4(0.f, 0.f, 0.f, 0.f);
+            part += er.x * p[q].x + er.y * p[q].y + er.z * p[q].z + er.w * p[q].w;
+        }
+        const float u = row16_sum(part);
+        const float sig = theano_sigmoid(u);
+        const float s = clip_prob(sig);
+        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
+        if (TRAIN) {
+            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
+            float du = 0.f;
+            if (inside) {
+                const float ds = sig * (1.0f - sig);
+                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
+            }
+            if (l == 0 && valid) {
+                coef[(size_t)i * (z + 1) + j] = du;
+                key[(size_t)i * (z + 1) + j] = c.key(N);
+            }
+        }
+        c.commit();
+    }
+    loss += row_nan(t);
+    if (l == 0 && valid) rowloss[i] = wi * loss;
+    if (l == 0) wg_red[threadIdx.x >> 4] = valid ? wi * loss : 0.f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s += wg_red[r];
+        wg_loss[blockIdx.x] = s;
+    }
+}
+
+template <int NPL, bool TRAIN>
+__global__ __launch_bounds__(256) void foldin_nce_map_scalar(const float* __restrict__ T, const float* __restrict__ Re,
+                                                             const float* __restrict__ E, const int32_t* __restrict__ slot_of,
+                                                             const int32_t* __restrict__ y, const int32_t* __restrict__ neg,
+                                                             const float* __restrict__ w, float* __restrict__ coef,
+                                                             int32_t* __restrict__ key, float* __restrict__ rowloss, int B,
+                                                             int z, int de, int N, float inv_batch) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= B) return;
+    FoldinAhead c(neg + (size_t)i * z, slot_of, z, y[i]);
+    float t[NPL], p[NPL];
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int cc = lane + 64 * q;
+        t[q] = (cc < de) ? T[(size_t)i * de + cc] : 0.f;
+        p[q] = fminf(fmaxf(t[q], -SERT_CLIP_HI), SERT_CLIP_HI);
+    }
+    const float wi = TRAIN ? w[i] : 1.f;
+    const float g = wi * inv_batch;
+    float loss = 0.f;
+    for (int j = 0; j <= z; ++j) {
+        c.issue(j);
+        const float* __restrict__ row = c.row(Re, E, de);
+        float part = 0.f;
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) {
+            const int cc = lane + 64 * q;
+            part += ((cc < de) ? row[cc] : 0.f) * p[q];
+        }
+        const float u = wave_sum(part);
+        const float sig = theano_sigmoid(u);
+        const float s = clip_prob(sig);
+        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
+        if (TRAIN) {
+            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
+            float du = 0.f;
+            if (inside) {
+                const float ds = sig * (1.0f - sig);
+                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
+            }
+            if (lane == 0) {
+                coef[(size_t)i * (z + 1) + j] = du;
+                key[(size_t)i * (z + 1) + j] = c.key(N);
+            }
+        }
+        c.commit();
     }
     // (a NaN unit of the row: see row_nan)
     float tsum = 0.f;

@@ -19,7 +19,13 @@ class EntityFoldIn(models.ModelInterface):
     training_set: (x (M, window_size) token ids of the TRAINED vocabulary, y (M,) in [0, N), w (M,) weights or None).
     New entity e becomes row V_e + e of the extended table.  ``new_rows_init`` None: N = y.max() + 1 rows drawn with
     ``_glorot_uniform((N, d_e))``, as bin/train.py initialises R_e.  The batch size, the number of negatives, lambda and the
-    learning rate are the fold-in's own."""
+    learning rate are the fold-in's own.
+
+    ``refresh`` (an array of distinct trained internal indices): these trained rows learn too -- entities that gained
+    documents.  The trainable rows are then SLOTS, the refreshed rows first, in the order of ``refresh``, the new rows
+    behind them: y is a slot in [0, len(refresh) + N), and ``new_rows_init`` may be None or empty (nothing is new).
+    Negatives stay ids of the extended table.  A refreshed row starts from its trained value and learns from the
+    instances given: to keep its old evidence, pass the entity's old documents along with the new ones."""
 
     #: callable batch_index -> (B, z) int64 negatives in [0, V_e + N), or None (device sampler)
     negative_sampler = None
@@ -29,11 +35,15 @@ class EntityFoldIn(models.ModelInterface):
     steps_per_sync = 1
 
     def __init__(self, R_w, R_e, W, b, new_rows_init, training_set, batch_size, num_negative_samples,
-                 regularization_lambda, window_size, seed=None, lr=1e-3, device=0, _engine=None):
+                 regularization_lambda, window_size, seed=None, lr=1e-3, device=0, _engine=None, refresh=None):
         super(EntityFoldIn, self).__init__(batch_size)
         x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
         w = training_set[2] if len(training_set) > 2 else None
         assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        if refresh is not None:
+            refresh = np.asarray(refresh, dtype=np.int64).reshape(-1)
+            if new_rows_init is None:
+                new_rows_init = np.zeros((0, np.shape(R_e)[1]), dtype=np.float32)
         if new_rows_init is None:
             if not y.size:
                 raise RuntimeError('no fold-in instances and no initial rows: nothing says how many entities are new')
@@ -43,6 +53,8 @@ class EntityFoldIn(models.ModelInterface):
             seed = int(np.random.randint(low=0, high=(1 << 30)))
         self.window_size = int(window_size)
         self.num_new = int(new_rows_init.shape[0])
+        self.refresh = None if refresh is None else refresh.copy()
+        self.num_refresh = 0 if refresh is None else int(refresh.size)
         self.num_entities = int(np.shape(R_e)[0])
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
@@ -62,24 +74,28 @@ class EntityFoldIn(models.ModelInterface):
                 engine.set_tensor(which, value)
         try:
             self._foldin = _capi.FoldIn(engine, new_rows_init, batch_size, num_negative_samples, regularization_lambda,
-                                        lr=lr, seed=seed)
+                                        lr=lr, seed=seed, refresh_ids=refresh)
         finally:
             if owned:
                 engine.close()      # (the handle copied what it needs)
         self._foldin.upload(x, y, w)
-        logging.info('Folding in %d new entities (rows %d .. %d) on %d instances.', self.num_new, self.num_entities,
-                     self.num_entities + self.num_new - 1, self.training_num_instances)
+        if refresh is None:
+            logging.info('Folding in %d new entities (rows %d .. %d) on %d instances.', self.num_new, self.num_entities,
+                         self.num_entities + self.num_new - 1, self.training_num_instances)
+        else:
+            logging.info('Refreshing %d trained entities and folding in %d new ones on %d instances.', self.num_refresh,
+                         self.num_new, self.training_num_instances)
 
     @classmethod
     def from_model(cls, model, new_rows_init, training_set, batch_size, num_negative_samples, regularization_lambda,
-                   seed=None, lr=1e-3):
+                   seed=None, lr=1e-3, refresh=None):
         """From a live ``models.VectorSpaceLanguageModel``: its parameters as they are now are copied on the device (the
         model may train on or be dropped afterwards)."""
         if not isinstance(model, models.VectorSpaceLanguageModel):
             raise RuntimeError('a fold-in needs a VectorSpaceLanguageModel')
         shape = (model.num_entities, model.entity_representation_size)
         return cls(None, _Shape(shape), None, None, new_rows_init, training_set, batch_size, num_negative_samples,
-                   regularization_lambda, model.window_size, seed=seed, lr=lr, _engine=model._engine)
+                   regularization_lambda, model.window_size, seed=seed, lr=lr, _engine=model._engine, refresh=refresh)
 
     # -- the step functions ---------------------------------------------------------------------------------------
     def train_fn(self, batch_index):
@@ -111,13 +127,22 @@ class EntityFoldIn(models.ModelInterface):
     # -- results and state --------------------------------------------------------------------------------------------
     def get_new_representations(self):
         """(N, d_e): the new rows as they are now."""
-        return self._foldin.get_rows(_capi.FOLDIN_ROWS)
+        return self._foldin.get_rows(_capi.FOLDIN_ROWS)[self.num_refresh:]
+
+    def get_refreshed_representations(self):
+        """(len(refresh), d_e): the refreshed trained rows as they are now, in the order of ``refresh``."""
+        return self._foldin.get_rows(_capi.FOLDIN_ROWS)[:self.num_refresh]
 
     def get_extended_representations(self, R_e):
-        """(V_e + N, d_e): the trained rows ``R_e`` (the caller's: the fold-in never changes them) with the new rows behind."""
+        """(V_e + N, d_e): the trained rows ``R_e`` (the caller's: never modified) with the rows of ``refresh`` replaced by
+        their slots and the new rows behind."""
         R_e = np.asarray(R_e, dtype=np.float32)
         assert R_e.shape[0] == self.num_entities
-        return np.concatenate([R_e, self.get_new_representations()], axis=0)
+        rows = self._foldin.get_rows(_capi.FOLDIN_ROWS)
+        ext = np.concatenate([R_e, rows[self.num_refresh:]], axis=0)
+        if self.num_refresh:
+            ext[self.refresh] = rows[:self.num_refresh]
+        return ext
 
     def get_optimizer_state(self):
         return {'step': self._foldin.get_step(), 'm_E': self._foldin.get_rows(_capi.FOLDIN_M),
@@ -184,6 +209,44 @@ def extend_meta(meta, new_entity_ids, new_associations=None):
     for entity_id, documents in (new_associations or {}).items():
         merged[entity_id] = list(merged.get(entity_id, [])) + list(documents)
     return [args, words, tokens, extended, merged]
+
+
+def merge_meta(meta, entity_ids, associations=None):
+    """The meta of a model in which entities GAIN documents (bin/fold_in.py --refresh).  ``entity_ids[k]`` is entity k of the
+    new documents' meta: an id the trained meta knows keeps its internal index and is refreshed, an unknown one gets
+    V_e + e in order of first appearance; ``associations`` (entity id -> document ids) are added to either kind.
+    -> (the five pickles, the refreshed internal indices in order of first appearance, the new ids, slots): ``slots[k]`` is
+    the slot of entity k in a fold-in with ``refresh`` = the refreshed indices -- refreshed slots first, new ones behind."""
+    args, words, tokens, entity_indices_inv, assocs = meta
+    entity_ids = list(entity_ids)
+    if len(set(entity_ids)) != len(entity_ids):
+        raise RuntimeError('duplicate entity ids')
+    V_e = len(entity_indices_inv)
+    assert sorted(entity_indices_inv) == list(range(V_e)), 'internal entity indices must be 0 .. V_e - 1'
+    index_of = dict((entity_id, index) for index, entity_id in entity_indices_inv.items())
+    refreshed = [index_of[e] for e in entity_ids if e in index_of]
+    new_ids = [e for e in entity_ids if e not in index_of]
+    extended = dict(entity_indices_inv)
+    for e, entity_id in enumerate(new_ids):
+        extended[V_e + e] = entity_id
+    slot_of_index = dict((index, s) for s, index in enumerate(refreshed))
+    slot_of_new = dict((entity_id, len(refreshed) + e) for e, entity_id in enumerate(new_ids))
+    slots = np.array([slot_of_index[index_of[e]] if e in index_of else slot_of_new[e] for e in entity_ids], dtype=np.int32)
+    merged = dict(assocs)
+    for entity_id, documents in (associations or {}).items():
+        merged[entity_id] = list(merged.get(entity_id, [])) + list(documents)
+    return [args, words, tokens, extended, merged], np.array(refreshed, dtype=np.int32), new_ids, slots
+
+
+def refresh_dump(args, predict_fn, R_w, R_e, refresh, refreshed_rows, new_rows):
+    """The objects of a model dump with the rows ``refresh`` of R_e replaced by ``refreshed_rows`` and ``new_rows`` appended;
+    the caller's R_e is not modified."""
+    R_e = np.array(R_e, copy=True)
+    refresh = np.asarray(refresh, dtype=np.int64)
+    refreshed_rows = np.asarray(refreshed_rows, dtype=R_e.dtype)
+    assert refreshed_rows.shape == (refresh.size, R_e.shape[1])
+    R_e[refresh] = refreshed_rows
+    return extend_dump(args, predict_fn, R_w, R_e, np.asarray(new_rows, dtype=R_e.dtype).reshape(-1, R_e.shape[1]))
 
 
 def read_meta(path):

@@ -9,6 +9,11 @@ window, device-drawn negatives both.  One warm-up pass of each, then --repeats a
 host clock around a call that ends in its one host synchronisation.  The one-time projection of the fold-in instances
 (sert_foldin_upload: host validation, copy, window mean, GEMM) is timed apart.
 
+--refresh R (`python tools/foldin_bench.py --refresh 1024 --out profiles/r14_refresh.json`): per setting, in place of the
+two-way alternation and the end-to-end figure, the REFRESH step -- sert_foldin_create_refresh with R trained rows refreshed and no new entity, whose
+loss kernel looks every negative up in a slot table -- alternating in the same process with the fold-in step of
+sert_foldin_create with N new rows and with the full step; the ratio reported is refresh / fold-in.
+
 The end-to-end figure (--e2e_epochs K > 0): K epochs of fold-in of N entities x --e2e_instances instances against K
 epochs of training on the union set ((V_e + N) x --e2e_instances instances), uploads included, at the first setting.
 """
@@ -83,6 +88,43 @@ def step_setting(name, B, Vw, Ve, N, dw, de, n, z, steps, repeats, num_batches):
     return rec
 
 
+def refresh_setting(name, B, Vw, Ve, N, dw, de, n, z, steps, repeats, num_batches, R):
+    """The refresh step (R refreshed trained rows, num_new = 0), the fold-in step of sert_foldin_create (N new rows) and the
+    full step (V_e + N entities), alternating."""
+    rng = np.random.RandomState(0)
+    R = min(R, Ve)          # (a setting with fewer trained rows than R: every one of them is refreshed)
+    M = B * num_batches
+    X = zipf_tokens(rng, Vw, (M, n))
+    full = engine(rng, B, Vw, Ve + N, dw, de, n, z)
+    full.upload_dataset(C.SPLIT_TRAIN, X, y_int=rng.randint(0, Ve + N, M).astype(np.int32), w=np.ones(M, np.float32))
+    frozen = engine(rng, 1, Vw, Ve, dw, de, n, 0, inference_only=1)
+    fold = C.FoldIn(frozen, glorot(rng, (N, de)), B, z, 0.01, lr=1e-3, seed=7)
+    refresh = C.FoldIn(frozen, None, B, z, 0.01, lr=1e-3, seed=7,
+                       refresh_ids=rng.permutation(Ve)[:R].astype(np.int32))
+    frozen.close()
+    assert refresh.table() == dict(map=True, num_refresh=R, num_new=0, rows=R) and not fold.table()['map']
+    fold.upload(X.astype(np.int32), rng.randint(0, N, M).astype(np.int32), None)
+    refresh.upload(X.astype(np.int32), rng.randint(0, R, M).astype(np.int32), None)
+    order = np.arange(steps, dtype=np.int64) % num_batches
+    handles = (('refresh', refresh), ('foldin', fold), ('full', full))
+    for _, h in handles:
+        h.train_batches(order)
+    times = dict((k, []) for k, _ in handles)
+    for _ in range(repeats):
+        for k, h in handles:
+            times[k].append(timed(lambda: h.train_batches(order))[0] / steps)
+    plans = dict(refresh=refresh.plan(), foldin=fold.plan())
+    for _, h in handles:
+        h.close()
+    rec = dict(setting=name, B=B, V_w=Vw, V_e=Ve, R=R, N=N, d_w=dw, d_e=de, window=n, z=z, steps=steps, instances=M, plans=plans)
+    for k in times:
+        rec[k + '_step_ms'] = [1e3 * t for t in times[k]]
+        rec[k + '_step_ms_median'] = 1e3 * float(np.median(times[k]))
+    rec['refresh_over_foldin_median'] = rec['refresh_step_ms_median'] / rec['foldin_step_ms_median']
+    rec['full_over_refresh_median'] = rec['full_step_ms_median'] / rec['refresh_step_ms_median']
+    return rec
+
+
 def end_to_end(name, B, Vw, Ve, N, dw, de, n, z, epochs, per_entity):
     rng = np.random.RandomState(1)
 
@@ -134,18 +176,26 @@ def main(argv=None):
     ap.add_argument('--num_batches', type=int, default=8)
     ap.add_argument('--e2e_epochs', type=int, default=2)
     ap.add_argument('--e2e_instances', type=int, default=256)
+    ap.add_argument('--refresh', type=int, default=0, metavar='R',
+                    help='also time the refresh step with R refreshed trained rows and no new entity (0: not)')
     ap.add_argument('--settings', nargs='+', default=[s[0] for s in SETTINGS])
     args = ap.parse_args(argv)
     C.require_gpu()
     out = dict(device=C.device_info(0), steps=[], end_to_end=None)
+    if args.refresh > 0:
+        out['refresh'] = []
     for s in SETTINGS:
-        if s[0] in args.settings:
+        if s[0] in args.settings and args.refresh > 0:
+            rec = refresh_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches, R=args.refresh)
+            print(json.dumps(rec))
+            out['refresh'].append(rec)
+        elif s[0] in args.settings:
             rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches)
             print(json.dumps(rec))
             out['steps'].append(rec)
             with open(args.out, 'w') as f:
                 json.dump(out, f, indent=1, sort_keys=True)
-    if args.e2e_epochs > 0 and SETTINGS[0][0] in args.settings:
+    if args.e2e_epochs > 0 and args.refresh == 0 and SETTINGS[0][0] in args.settings:
         out['end_to_end'] = end_to_end(*SETTINGS[0], epochs=args.e2e_epochs, per_entity=args.e2e_instances)
         print(json.dumps(out['end_to_end']))
     with open(args.out, 'w') as f:
