@@ -228,6 +228,14 @@ __device__ __forceinline__ float clip_unit(float t) {
 __device__ __forceinline__ float clip_prob(float s) {
     return s > SERT_CLIP_HI ? SERT_CLIP_HI : (s < SERT_CLIP_LO ? SERT_CLIP_LO : s);
 }
+// The same clip of a LOG-probability, clip(log p, log eps, log(1-eps)) = log clip(p, eps, 1-eps) (sert/models.py:200): the
+// loglinear loss kernels (kernels_ll.h) keep the token distributions in the log domain.  A NaN stays a NaN here too -- as
+// fminf(fmaxf(..)) it became log(1e-7), the row's J, Q and loss stayed finite while the backward filled W and b with NaN,
+// and the epoch loop's non-finite check never fired.  For every other input the result is lo, hi or x itself, the bits the
+// min/max form gave (-inf, the log of a zero probability, clips to lo).
+__device__ __forceinline__ float clip_logp(float lp, float lo, float hi) {
+    return lp > hi ? hi : (lp < lo ? lo : lp);
+}
 
 // T.nnet.sigmoid, float32 C implementation of Theano 0.8.2 [upstream]:
 // x < -88 -> 0 ; x > 15 -> 1 ; else 1/(1+exp(-x))

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
     for (int e = tid; e < V; e += 256) {
         float a = 0.f;
         for (int k = 0; k < n; ++k) {
-            const float pc = fminf(fmaxf(Pi[(size_t)k * V + e], SERT_CLIP_LO), SERT_CLIP_HI);
+            const float pc = clip_prob(Pi[(size_t)k * V + e]);
             a += logf(pc);
         }
         Ji[e] = a;
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
         const int e = y_int ? y_int[i] : indices[l];
         const float yv = y_int ? 1.f : data[l];
         const float q = expf(Ji[e] - mx) / se;
-        const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float qc = clip_prob(q);
         loss -= yv * logf(qc);
         if (TRAIN) {
             const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
@@ -120,11 +120,11 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
         // recover Q_e from the stored -Q_e*s is ill-conditioned; recompute from P
         float a = 0.f;
         for (int k = 0; k < n; ++k) {
-            const float pc = fminf(fmaxf(Pi[(size_t)k * V + e], SERT_CLIP_LO), SERT_CLIP_HI);
+            const float pc = clip_prob(Pi[(size_t)k * V + e]);
             a += logf(pc);
         }
         const float q = expf(a - mx) / se;
-        const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float qc = clip_prob(q);
         const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
         const float dq = inside ? -(g * yv) / qc : 0.f;
         Ji[e] += q * dq;
@@ -292,11 +292,11 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
         if (n > kLlTableWindow) {
             double a64 = 0.0;
 #pragma unroll 5
-            for (int k = 0; k < n; ++k) a64 += (double)fminf(fmaxf(S[(size_t)k * V + e], LOGLO), LOGHI);
+            for (int k = 0; k < n; ++k) a64 += (double)clip_logp(S[(size_t)k * V + e], LOGLO, LOGHI);
             a = (float)a64;
         } else {
 #pragma unroll 5
-            for (int k = 0; k < n; ++k) a += fminf(fmaxf(S[(size_t)k * V + e], LOGLO), LOGHI);
+            for (int k = 0; k < n; ++k) a += clip_logp(S[(size_t)k * V + e], LOGLO, LOGHI);
         }
         Jl[e] = a;
         mx = fmaxf(mx, a);
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
         const int e = y_int ? y_int[i] : indices[l];
         const float yv = y_int ? 1.f : data[l];
         const float q = expf(Jl[e] - mx) / se;
-        const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float qc = clip_prob(q);
         loss -= yv * logf(qc);
         if (TRAIN) {
             const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
             const int e = y_int ? y_int[i] : indices[l];
             const float yv = y_int ? 1.f : data[l];
             const float q = expf(Jl[e] - mx) / se;
-            const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+            const float qc = clip_prob(q);
             const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
             fix_e[f] = e;
             fix_val[f] = q * (inside ? -(g * yv) / qc : 0.f);
@@ -455,10 +455,10 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
 #pragma unroll
                     for (int c = 0; c < 8; ++c) bad = bad || (!(x[c] >= LOGLO && x[c] <= LOGHI) && (c < 4 || two));
                     if (bad) oob |= 1ull << (k0 + q);
-                    a0.x += fminf(fmaxf(x[0], LOGLO), LOGHI); a0.y += fminf(fmaxf(x[1], LOGLO), LOGHI);
-                    a0.z += fminf(fmaxf(x[2], LOGLO), LOGHI); a0.w += fminf(fmaxf(x[3], LOGLO), LOGHI);
-                    a1.x += fminf(fmaxf(x[4], LOGLO), LOGHI); a1.y += fminf(fmaxf(x[5], LOGLO), LOGHI);
-                    a1.z += fminf(fmaxf(x[6], LOGLO), LOGHI); a1.w += fminf(fmaxf(x[7], LOGLO), LOGHI);
+                    a0.x += clip_logp(x[0], LOGLO, LOGHI); a0.y += clip_logp(x[1], LOGLO, LOGHI);
+                    a0.z += clip_logp(x[2], LOGLO, LOGHI); a0.w += clip_logp(x[3], LOGLO, LOGHI);
+                    a1.x += clip_logp(x[4], LOGLO, LOGHI); a1.y += clip_logp(x[5], LOGLO, LOGHI);
+                    a1.z += clip_logp(x[6], LOGLO, LOGHI); a1.w += clip_logp(x[7], LOGLO, LOGHI);
                 }
             }
             reinterpret_cast<float4*>(Jl)[e0] = a0;
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
         for (int k = 0; k < n; ++k) {
             const float lp = Zu[(size_t)s_slot[k] * V + e];
             if (!(lp >= LOGLO && lp <= LOGHI)) oob |= 1ull << k;
-            a += fminf(fmaxf(lp, LOGLO), LOGHI);
+            a += clip_logp(lp, LOGLO, LOGHI);
         }
         Jl[e] = a;
         mx = fmaxf(mx, a);
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
             const int e = y_int ? y_int[i] : indices[l];
             const float yv = y_int ? 1.f : data[l];
             const float q = expf(Jl[e] - mx) / se;
-            const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+            const float qc = clip_prob(q);
             loss -= yv * logf(qc);
             const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
             const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
@@ -623,8 +623,8 @@ __global__ __launch_bounds__(256) void ll_row_wave(const float* __restrict__ Zu,
                 const float x[4] = {v[q][j].x, v[q][j].y, v[q][j].z, v[q][j].w};
 #pragma unroll
                 for (int cc = 0; cc < 4; ++cc) bad = bad || (in && !(x[cc] >= LOGLO && x[cc] <= LOGHI));
-                J[j].x += fminf(fmaxf(x[0], LOGLO), LOGHI); J[j].y += fminf(fmaxf(x[1], LOGLO), LOGHI);
-                J[j].z += fminf(fmaxf(x[2], LOGLO), LOGHI); J[j].w += fminf(fmaxf(x[3], LOGLO), LOGHI);
+                J[j].x += clip_logp(x[0], LOGLO, LOGHI); J[j].y += clip_logp(x[1], LOGLO, LOGHI);
+                J[j].z += clip_logp(x[2], LOGLO, LOGHI); J[j].w += clip_logp(x[3], LOGLO, LOGHI);
             }
             if (bad) oob |= 1ull << (k0 + q);
         }
@@ -666,7 +666,7 @@ __global__ __launch_bounds__(256) void ll_row_wave(const float* __restrict__ Zu,
             for (int jj = 0; jj < E4PL; ++jj)
                 if (jj == j) ev = comp == 0 ? E[jj].x : comp == 1 ? E[jj].y : comp == 2 ? E[jj].z : E[jj].w;
             const float q = ev / se;
-            const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+            const float qc = clip_prob(q);
             loss -= yv * logf(qc);
             const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
             const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
@@ -916,7 +916,7 @@ __global__ __launch_bounds__(256) void ll_s_window(const float* __restrict__ Z, 
         float x[16];
         seg_load<V4>(Z + (size_t)row * V, V, seg, x, 0.f);
 #pragma unroll
-        for (int u = 0; u < 16; ++u) acc[u] += fminf(fmaxf(x[u] - l, LOGLO), LOGHI);
+        for (int u = 0; u < 16; ++u) acc[u] += clip_logp(x[u] - l, LOGLO, LOGHI);
     }
     seg_store<V4>(J + (size_t)i * V, V, seg, acc);
     float mx = -INFINITY;
@@ -960,7 +960,7 @@ __global__ __launch_bounds__(256) void ll_s_rowloss(const float* __restrict__ J,
         const int e = y_int ? y_int[i] : indices[l];
         const float yv = y_int ? 1.f : data[l];
         const float q = expf(Ji[e] - mx) / se;
-        const float qc = fminf(fmaxf(q, SERT_CLIP_LO), SERT_CLIP_HI);
+        const float qc = clip_prob(q);
         loss -= yv * logf(qc);
         if (TRAIN) {
             const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);

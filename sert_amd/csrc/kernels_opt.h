@@ -184,7 +184,10 @@ __device__ __forceinline__ void adadelta_elem(float& p, float& g, float& accu, f
                                               const AdadeltaArgs& a, float omr, float& ss) {
 #pragma clang fp contract(off)
     const float pv = p;
-    const float l2 = a.l2k * pv;
+    // l2k == 0 (lambda = 0, and always for the unregularised bias): NO L2 term, as in the reference's graph -- not 0 * p, which
+    // is NaN for an infinite p: a bias of -inf (an entity switched off) has gradient 0 and must stay -inf.  The signed zero is
+    // what 0 * p gives for every finite p: same bits.
+    const float l2 = a.l2k != 0.f ? a.l2k * pv : copysignf(0.f, pv);
     const float gv = g + l2;
     ss = sq_acc(ss, pv);
     const float a1 = a.rho * accu, a2 = (omr * gv) * gv;
