@@ -9,6 +9,7 @@
 // is deterministic, and no address is ever contended.
 #pragma once
 #include "common.h"
+#include "loss_terms.h"
 
 namespace sert {
 
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void egrad_chunk_reduce(
                     }
 #pragma unroll
                     for (int v = 0; v < VEC; ++v)
-                        acc[q][v] += cf * fminf(fmaxf(tv[v], -SERT_CLIP_HI), SERT_CLIP_HI);
+                        acc[q][v] += cf * clip_proj(tv[v]);
                 }
             }
         }
@@ -248,14 +249,6 @@ __global__ __launch_bounds__(256) void egrad_fixup_wg(const int32_t* __restrict_
 constexpr int kElBatch = SERT_EL_BATCH;   // pairs (T rows) in flight per wave
 constexpr int kElSubPairs = 4096;  // pair capacity of one sub-group (16 per thread)
 constexpr int kElMaxRanges = 128;
-
-__device__ __forceinline__ float4 clip4(float4 t) {
-    t.x = fminf(fmaxf(t.x, -SERT_CLIP_HI), SERT_CLIP_HI);
-    t.y = fminf(fmaxf(t.y, -SERT_CLIP_HI), SERT_CLIP_HI);
-    t.z = fminf(fmaxf(t.z, -SERT_CLIP_HI), SERT_CLIP_HI);
-    t.w = fminf(fmaxf(t.w, -SERT_CLIP_HI), SERT_CLIP_HI);
-    return t;
-}
 
 // er_shift: er = 1 << er_shift entities per range (<= 16).  sub_rows rows per sub-group,
 // sub_rows * c1 <= kElSubPairs.  entries: (B*c1) ints, offs: (num_sub, num_ranges + 1) ints.
@@ -414,7 +407,7 @@ __global__ __launch_bounds__(256) void egrad_acc(const int32_t* __restrict__ ent
                 const float cf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cfv), b0 + q));
 #pragma unroll
                 for (int v = 0; v < VPL; ++v)
-                    acc[el][v] += cf * fminf(fmaxf(tv[q][v], -SERT_CLIP_HI), SERT_CLIP_HI);
+                    acc[el][v] += cf * clip_proj(tv[q][v]);
             }
         }
     };

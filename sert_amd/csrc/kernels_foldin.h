@@ -5,9 +5,10 @@
 // objective of the vectorspace step over the extended table Ext = concat(R_e, E) (new entity e is row V_e + e).  The
 // projections T = tanh(h W + b) of the fold-in instances therefore never change: they are computed once, at upload, by the
 // model's own forward (vs_gather_mean + the projection GEMM).  A step is
-//   foldin_nce            the loss kernel of kernels_vs.h (vs_nce / vs_nce_scalar) on a two-part table, WITHOUT the da it
-//                         writes for the layers below (nothing below the projection learns); TRAIN leaves coef[i, j] and a
-//                         KEY per pair: cand - V_e for a pair that hits a new row, the sentinel N for one that hits a frozen row
+//   foldin_nce            the loss kernel's row body (kernels_vs.h: nce_rows16 / nce_rows_wave, the body of vs_nce /
+//                         vs_nce_scalar) over a two-part table, WITHOUT the da it writes for the layers below (nothing
+//                         below the projection learns); TRAIN leaves coef[i, j] and a KEY per pair: cand - V_e for a pair
+//                         that hits a new row, the sentinel N for one that hits a frozen row
 //   csort_pass            stable sort of the B (1 + z) (key, pair) entries (kernels_sort.h, as it is)
 //   foldin_chunk_reduce   egrad_chunk_reduce (kernels_egrad.h) that stops at the sentinel: the sentinel run -- most of the
 //                         pairs -- is the END of the sorted order, so a chunk that starts inside it leaves after one load
@@ -30,8 +31,24 @@ __device__ __forceinline__ const float* foldin_row(const float* __restrict__ Re,
     return e < Ve ? Re + (size_t)e * de : E + (size_t)(e - Ve) * de;
 }
 
-// vs_nce's row layout: 16 lanes per instance, lane l owns the float4 column chunks l, l + 16, ...; one candidate after
-// the other, so any z >= 1.  T: the (B, d_e) projections of THIS batch (the host passes the batch's first row).
+// The candidate policy (kernels_vs.h, nce_rows16) of the two-part table: the positive is new row y[i], a negative any row of
+// Ext; the key of a pair is its new row, or the sentinel N for a frozen one.
+struct FoldinTwoPart {
+    const int32_t* __restrict__ yi;
+    const int32_t* __restrict__ nrow;
+    int Ve, e;
+    __device__ __forceinline__ FoldinTwoPart(const int32_t* __restrict__ y, const int32_t* __restrict__ neg, int i, int z, int Ve_)
+        : yi(y + i), nrow(neg + (size_t)i * z), Ve(Ve_), e(0) {}
+    __device__ __forceinline__ void issue(int j) { e = (j == 0) ? Ve + *yi : nrow[j - 1]; }
+    __device__ __forceinline__ void commit() {}
+    __device__ __forceinline__ const float* row(const float* __restrict__ Re, const float* __restrict__ E, int de) const {
+        return foldin_row(Re, E, Ve, e, de);
+    }
+    __device__ __forceinline__ int key(int N) const { return e >= Ve ? e - Ve : N; }
+};
+
+// vs_nce's row layout (nce_rows16): 16 lanes per instance, lane l owns the float4 column chunks l, l + 16, ...; one candidate
+// after the other, so any z >= 1.  T: the (B, d_e) projections of THIS batch (the host passes the batch's first row).
 //   u_j = <Ext[c_j], clip(t)>, s_j = clip(sigmoid(u_j)), loss = -(log s_0 + sum_{j>0} log(1 - s_j))
 //   TRAIN: coef[i, j] = d loss / d u_j * w_i / B (inclusive clip mask), key[i, j] = c_j >= V_e ? c_j - V_e : N
 //   rowloss[i] = (TRAIN ? w_i : 1) * loss; wg_loss[blockIdx.x] = the workgroup's sixteen row losses added in row order
@@ -42,69 +59,14 @@ __global__ __launch_bounds__(256) void foldin_nce(const float* __restrict__ T, c
                                                   float* __restrict__ coef, int32_t* __restrict__ key,
                                                   float* __restrict__ rowloss, int B, int z, int de, int Ve, int N,
                                                   float inv_batch, float* __restrict__ wg_loss) {
-    __shared__ float wg_red[16];
-    const int l = threadIdx.x & 15;
-    // (rows past the end of a ragged last workgroup: computed on a clamped row, never stored -- no return in front of the
-    //  barrier below)
     const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool valid = i_raw < B;
     const int i = valid ? i_raw : B - 1;
-    const int chunks = de >> 2;  // de % 4 == 0 on this path
-    float4 t[NCH], p[NCH];
-#pragma unroll
-    for (int q = 0; q < NCH; ++q) {
-        const int c = l + 16 * q;
-        t[q] = (c < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * c)
-                            : make_float4(0.f, 0.f, 0.f, 0.f);
-        p[q].x = fminf(fmaxf(t[q].x, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].y = fminf(fmaxf(t[q].y, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].z = fminf(fmaxf(t[q].z, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].w = fminf(fmaxf(t[q].w, -SERT_CLIP_HI), SERT_CLIP_HI);
-    }
-    const float wi = TRAIN ? w[i] : 1.f;
-    const float g = wi * inv_batch;
-    float loss = 0.f;
-    for (int j = 0; j <= z; ++j) {
-        const int e = (j == 0) ? Ve + y[i] : neg[(size_t)i * z + (j - 1)];
-        const float* __restrict__ row = foldin_row(Re, E, Ve, e, de);
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < NCH; ++q) {
-            const int c = l + 16 * q;
-            const float4 er = (c < chunks) ? *reinterpret_cast<const float4*>(row + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            part += er.x * p[q].x + er.y * p[q].y + er.z * p[q].z + er.w * p[q].w;
-        }
-        const float u = row16_sum(part);
-        const float sig = theano_sigmoid(u);
-        const float s = clip_prob(sig);
-        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
-        if (TRAIN) {
-            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-            float du = 0.f;
-            if (inside) {
-                const float ds = sig * (1.0f - sig);
-                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-            }
-            if (l == 0 && valid) {
-                coef[(size_t)i * (z + 1) + j] = du;
-                key[(size_t)i * (z + 1) + j] = e >= Ve ? e - Ve : N;
-            }
-        }
-    }
-    loss += row_nan(t);
-    if (l == 0 && valid) rowloss[i] = wi * loss;
-    if (l == 0) wg_red[threadIdx.x >> 4] = valid ? wi * loss : 0.f;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += wg_red[r];
-        wg_loss[blockIdx.x] = s;
-    }
+    nce_rows16<NCH, TRAIN, false>(T, Re, E, FoldinTwoPart(y, neg, i, z, Ve), w, nullptr, coef, key, rowloss, i, valid, z, de, N,
+                                  inv_batch, wg_loss);
 }
 
-// Any d_e (d_e % 4 != 0), the way vs_nce_scalar covers it: one wave per instance, scalar columns.  No barrier, no
-// workgroup partial: the loss is finalised from rowloss.
+// Any d_e (d_e % 4 != 0), the way vs_nce_scalar covers it (nce_rows_wave): one wave per instance, scalar columns.
 template <int NPL, bool TRAIN>
 __global__ __launch_bounds__(256) void foldin_nce_scalar(const float* __restrict__ T, const float* __restrict__ Re,
                                                          const float* __restrict__ E, const int32_t* __restrict__ y,
@@ -112,64 +74,23 @@ __global__ __launch_bounds__(256) void foldin_nce_scalar(const float* __restrict
                                                          float* __restrict__ coef, int32_t* __restrict__ key,
                                                          float* __restrict__ rowloss, int B, int z, int de, int Ve, int N,
                                                          float inv_batch) {
-    const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= B) return;
-    float t[NPL], p[NPL];
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) {
-        const int c = lane + 64 * q;
-        t[q] = (c < de) ? T[(size_t)i * de + c] : 0.f;
-        p[q] = fminf(fmaxf(t[q], -SERT_CLIP_HI), SERT_CLIP_HI);
-    }
-    const float wi = TRAIN ? w[i] : 1.f;
-    const float g = wi * inv_batch;
-    float loss = 0.f;
-    for (int j = 0; j <= z; ++j) {
-        const int e = (j == 0) ? Ve + y[i] : neg[(size_t)i * z + (j - 1)];
-        const float* __restrict__ row = foldin_row(Re, E, Ve, e, de);
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) {
-            const int c = lane + 64 * q;
-            part += ((c < de) ? row[c] : 0.f) * p[q];
-        }
-        const float u = wave_sum(part);
-        const float sig = theano_sigmoid(u);
-        const float s = clip_prob(sig);
-        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
-        if (TRAIN) {
-            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-            float du = 0.f;
-            if (inside) {
-                const float ds = sig * (1.0f - sig);
-                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-            }
-            if (lane == 0) {
-                coef[(size_t)i * (z + 1) + j] = du;
-                key[(size_t)i * (z + 1) + j] = e >= Ve ? e - Ve : N;
-            }
-        }
-    }
-    // (a NaN unit of the row: see row_nan)
-    float tsum = 0.f;
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) tsum += t[q];
-    loss += wave_sum(tsum) * 0.0f;
-    if (lane == 0) rowloss[i] = wi * loss;
+    nce_rows_wave<NPL, TRAIN, false>(T, Re, E, FoldinTwoPart(y, neg, i, z, Ve), w, nullptr, coef, key, rowloss, i, z, de, N,
+                                     inv_batch);
 }
 
 // ---- a trainable table that is any subset of the extended table (sert_foldin_create_refresh) ----
 // The N trainable rows E are SLOTS: refreshed trained rows first, new rows behind.  slot_of (V_e + num_new int32, built once
 // at create) holds the slot of a row of the extended table, or -1 for a frozen one.  foldin_nce_map / foldin_nce_map_scalar are
-// foldin_nce / foldin_nce_scalar, changed only in how a candidate finds its row and key:
+// foldin_nce / foldin_nce_scalar with another candidate policy (FoldinAhead) -- how a candidate finds its row and key:
 //   negative e:  s = slot_of[e]; row = s >= 0 ? E + s d_e : Re + e d_e; key = s >= 0 ? s : N
 //   positive:    y[i] IS a slot: row = E + y[i] d_e, key = y[i] -- no lookup
 // so the snapshot's stale copy of a refreshed row is never read.  The lookup is a dependent 4-byte load in front of the row
 // fetch; z is a run-time value, so the lookups cannot all sit in registers ahead of the loop.  They run one candidate ahead
 // instead: while candidate j's row is fetched, the slot of candidate j + 1 and the id of candidate j + 2 are already in
-// flight (FoldinAhead; the reads past the last candidate are clamped onto it).  Same arithmetic in the same order as the
-// originals: with no refreshed row the two forms hold the same bits.
+// flight (FoldinAhead; the reads past the last candidate are clamped onto it).  The arithmetic is the one row body's: with no
+// refreshed row the two forms hold the same bits.
 
 // the rows of E that are trained rows: E[s] = Re[ids[s]] (create only)
 __global__ __launch_bounds__(256) void foldin_take_rows(const float* __restrict__ Re, const int32_t* __restrict__ ids,
@@ -213,67 +134,11 @@ __global__ __launch_bounds__(256) void foldin_nce_map(const float* __restrict__ 
                                                       const float* __restrict__ w, float* __restrict__ coef,
                                                       int32_t* __restrict__ key, float* __restrict__ rowloss, int B, int z,
                                                       int de, int N, float inv_batch, float* __restrict__ wg_loss) {
-    __shared__ float wg_red[16];
-    const int l = threadIdx.x & 15;
-    // (rows past the end of a ragged last workgroup: computed on a clamped row, never stored -- no return in front of the
-    //  barrier below)
     const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool valid = i_raw < B;
     const int i = valid ? i_raw : B - 1;
-    const int chunks = de >> 2;  // de % 4 == 0 on this path
-    FoldinAhead c(neg + (size_t)i * z, slot_of, z, y[i]);
-    float4 t[NCH], p[NCH];
-#pragma unroll
-    for (int q = 0; q < NCH; ++q) {
-        const int cc = l + 16 * q;
-        t[q] = (cc < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * cc)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        p[q].x = fminf(fmaxf(t[q].x, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].y = fminf(fmaxf(t[q].y, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].z = fminf(fmaxf(t[q].z, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].w = fminf(fmaxf(t[q].w, -SERT_CLIP_HI), SERT_CLIP_HI);
-    }
-    const float wi = TRAIN ? w[i] : 1.f;
-    const float g = wi * inv_batch;
-    float loss = 0.f;
-    for (int j = 0; j <= z; ++j) {
-        c.issue(j);
-        const float* __restrict__ row = c.row(Re, E, de);
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < NCH; ++q) {
-            const int cc = l + 16 * q;
-            const float4 er = (cc < chunks) ? *reinterpret_cast<const float4*>(row + 4 * cc) : make_float4(0.f, 0.f, 0.f, 0.f);
-            part += er.x * p[q].x + er.y * p[q].y + er.z * p[q].z + er.w * p[q].w;
-        }
-        const float u = row16_sum(part);
-        const float sig = theano_sigmoid(u);
-        const float s = clip_prob(sig);
-        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
-        if (TRAIN) {
-            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-            float du = 0.f;
-            if (inside) {
-                const float ds = sig * (1.0f - sig);
-                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-            }
-            if (l == 0 && valid) {
-                coef[(size_t)i * (z + 1) + j] = du;
-                key[(size_t)i * (z + 1) + j] = c.key(N);
-            }
-        }
-        c.commit();
-    }
-    loss += row_nan(t);
-    if (l == 0 && valid) rowloss[i] = wi * loss;
-    if (l == 0) wg_red[threadIdx.x >> 4] = valid ? wi * loss : 0.f;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += wg_red[r];
-        wg_loss[blockIdx.x] = s;
-    }
+    nce_rows16<NCH, TRAIN, false>(T, Re, E, FoldinAhead(neg + (size_t)i * z, slot_of, z, y[i]), w, nullptr, coef, key, rowloss, i,
+                                  valid, z, de, N, inv_batch, wg_loss);
 }
 
 template <int NPL, bool TRAIN>
@@ -283,53 +148,10 @@ __global__ __launch_bounds__(256) void foldin_nce_map_scalar(const float* __rest
                                                              const float* __restrict__ w, float* __restrict__ coef,
                                                              int32_t* __restrict__ key, float* __restrict__ rowloss, int B,
                                                              int z, int de, int N, float inv_batch) {
-    const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= B) return;
-    FoldinAhead c(neg + (size_t)i * z, slot_of, z, y[i]);
-    float t[NPL], p[NPL];
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) {
-        const int cc = lane + 64 * q;
-        t[q] = (cc < de) ? T[(size_t)i * de + cc] : 0.f;
-        p[q] = fminf(fmaxf(t[q], -SERT_CLIP_HI), SERT_CLIP_HI);
-    }
-    const float wi = TRAIN ? w[i] : 1.f;
-    const float g = wi * inv_batch;
-    float loss = 0.f;
-    for (int j = 0; j <= z; ++j) {
-        c.issue(j);
-        const float* __restrict__ row = c.row(Re, E, de);
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) {
-            const int cc = lane + 64 * q;
-            part += ((cc < de) ? row[cc] : 0.f) * p[q];
-        }
-        const float u = wave_sum(part);
-        const float sig = theano_sigmoid(u);
-        const float s = clip_prob(sig);
-        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
-        if (TRAIN) {
-            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-            float du = 0.f;
-            if (inside) {
-                const float ds = sig * (1.0f - sig);
-                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-            }
-            if (lane == 0) {
-                coef[(size_t)i * (z + 1) + j] = du;
-                key[(size_t)i * (z + 1) + j] = c.key(N);
-            }
-        }
-        c.commit();
-    }
-    // (a NaN unit of the row: see row_nan)
-    float tsum = 0.f;
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) tsum += t[q];
-    loss += wave_sum(tsum) * 0.0f;
-    if (lane == 0) rowloss[i] = wi * loss;
+    nce_rows_wave<NPL, TRAIN, false>(T, Re, E, FoldinAhead(neg + (size_t)i * z, slot_of, z, y[i]), w, nullptr, coef, key, rowloss,
+                                     i, z, de, N, inv_batch);
 }
 
 // egrad_chunk_reduce over keys sorted ascending whose LAST run is the sentinel (key == sentinel: a pair on a frozen row).
@@ -430,7 +252,7 @@ __global__ __launch_bounds__(256) void foldin_chunk_reduce(
                     }
 #pragma unroll
                     for (int v = 0; v < VEC; ++v)
-                        acc[q][v] += cf * fminf(fmaxf(tv[v], -SERT_CLIP_HI), SERT_CLIP_HI);
+                        acc[q][v] += cf * clip_proj(tv[v]);
                 }
             }
         }

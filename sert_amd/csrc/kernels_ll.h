@@ -1,6 +1,11 @@
 // loglinear kernels (sert/models.py:804-890), gfx950.
+// The loss terms are stated in loss_terms.h and only CALLED here: a row's label entries (LlLabels), an entry's -y log clip(q)
+// and Q_e dQ_e (ll_label_term), the clip mask of a log-probability and dZ = mask dJ - P r (logp_inside / ll_masked / ll_dz;
+// the same in the word-gradient tree, kernels_seg.h); clip_logp is common.h's.  Each kernel keeps its own passes; what the
+// passes compute per element is shared.  ll_window alone works on probabilities (prob_inside, clip_prob in ll_window_logprod).
 #pragma once
 #include "common.h"
+#include "loss_terms.h"
 
 namespace sert {
 
@@ -53,6 +58,16 @@ __global__ __launch_bounds__(256) void ll_softmax_rows(float* __restrict__ Z, in
 //   dZ_ke = P_ke (dP_ke - sum_e dP_ke P_ke)
 // Labels: y_int (one-hot, --one_hot_classes) or CSR rows (densified per batch
 // by the reference, models.py:66-89).
+// J_e of ll_window, from the probabilities: sum_k log clip(P_ke)
+__device__ __forceinline__ float ll_window_logprod(const float* __restrict__ Pi, int n, int V, int e) {
+    float a = 0.f;
+    for (int k = 0; k < n; ++k) {
+        const float pc = clip_prob(Pi[(size_t)k * V + e]);
+        a += logf(pc);
+    }
+    return a;
+}
+
 template <bool TRAIN>
 __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* __restrict__ J,
                                                  const int32_t* __restrict__ y_int,
@@ -71,11 +86,7 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
     // pass A: J and its max
     float mx = -INFINITY;
     for (int e = tid; e < V; e += 256) {
-        float a = 0.f;
-        for (int k = 0; k < n; ++k) {
-            const float pc = clip_prob(Pi[(size_t)k * V + e]);
-            a += logf(pc);
-        }
+        const float a = ll_window_logprod(Pi, n, V, e);
         Ji[e] = a;
         mx = fmaxf(mx, a);
     }
@@ -89,19 +100,15 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
     const float wi = TRAIN ? w[i] : 1.f;
     const float g = wi * inv_batch;
     float loss = 0.f, sdq = 0.f;
-    int64_t l0 = 0, l1 = 1;
-    if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
-    for (int64_t l = l0 + tid; l < l1; l += 256) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
+    const LlLabels lab(y_int, indptr, indices, data, i);
+    for (int64_t l = lab.l0 + tid; l < lab.l1; l += 256) {
+        const int e = lab.entity(l);
+        const float yv = lab.value(l);
         const float q = expf(Ji[e] - mx) / se;
-        const float qc = clip_prob(q);
-        loss -= yv * logf(qc);
-        if (TRAIN) {
-            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-            const float dq = inside ? -(g * yv) / qc : 0.f;
-            sdq += dq * q;
-        }
+        float ylog, qdq;
+        ll_label_term<TRAIN>(q, yv, g, ylog, qdq);
+        loss -= ylog;
+        sdq += qdq;
     }
     loss = block_sum_256(loss, red);
     if (tid == 0) rowloss[i] = wi * loss;
@@ -114,20 +121,14 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
         Ji[e] = -q * sdq;
     }
     __syncthreads();
-    for (int64_t l = l0 + tid; l < l1; l += 256) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
+    for (int64_t l = lab.l0 + tid; l < lab.l1; l += 256) {
+        const int e = lab.entity(l);
+        const float yv = lab.value(l);
         // recover Q_e from the stored -Q_e*s is ill-conditioned; recompute from P
-        float a = 0.f;
-        for (int k = 0; k < n; ++k) {
-            const float pc = clip_prob(Pi[(size_t)k * V + e]);
-            a += logf(pc);
-        }
-        const float q = expf(a - mx) / se;
-        const float qc = clip_prob(q);
-        const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-        const float dq = inside ? -(g * yv) / qc : 0.f;
-        Ji[e] += q * dq;
+        const float q = expf(ll_window_logprod(Pi, n, V, e) - mx) / se;
+        float ylog, qdq;
+        ll_label_term<true>(q, yv, g, ylog, qdq);
+        Ji[e] += qdq;
     }
     __syncthreads();
 
@@ -137,14 +138,12 @@ __global__ __launch_bounds__(256) void ll_window(float* __restrict__ P, float* _
         float r = 0.f;
         for (int e = tid; e < V; e += 256) {
             const float p = Pk[e];
-            const bool inside = (p >= SERT_CLIP_LO) && (p <= SERT_CLIP_HI);
-            if (inside) r += (Ji[e] / p) * p;
+            if (prob_inside(p)) r += (Ji[e] / p) * p;
         }
         r = block_sum_256(r, red);
         for (int e = tid; e < V; e += 256) {
             const float p = Pk[e];
-            const bool inside = (p >= SERT_CLIP_LO) && (p <= SERT_CLIP_HI);
-            const float dp = inside ? Ji[e] / p : 0.f;
+            const float dp = prob_inside(p) ? Ji[e] / p : 0.f;
             Pk[e] = p * (dp - r);
         }
     }
@@ -309,18 +308,15 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
     const float wi = TRAIN ? w[i] : 1.f;
     const float g = wi * inv_batch;
     float loss = 0.f, sdq = 0.f;
-    int64_t l0 = 0, l1 = 1;
-    if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
-    for (int64_t l = l0 + tid; l < l1; l += NT) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
+    const LlLabels lab(y_int, indptr, indices, data, i);
+    for (int64_t l = lab.l0 + tid; l < lab.l1; l += NT) {
+        const int e = lab.entity(l);
+        const float yv = lab.value(l);
         const float q = expf(Jl[e] - mx) / se;
-        const float qc = clip_prob(q);
-        loss -= yv * logf(qc);
-        if (TRAIN) {
-            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-            sdq += (inside ? -(g * yv) / qc : 0.f) * q;
-        }
+        float ylog, qdq;
+        ll_label_term<TRAIN>(q, yv, g, ylog, qdq);
+        loss -= ylog;
+        sdq += qdq;
     }
     loss = block_sum_n<NW>(loss, red);
     if (tid == 0) rowloss[i] = wi * loss;
@@ -334,17 +330,16 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
     int fix_e[NFIX];
 #pragma unroll
     for (int f = 0; f < NFIX; ++f) {
-        const int64_t l = l0 + tid + (int64_t)f * NT;
+        const int64_t l = lab.l0 + tid + (int64_t)f * NT;
         fix_e[f] = -1;
         fix_val[f] = 0.f;
-        if (l < l1) {
-            const int e = y_int ? y_int[i] : indices[l];
-            const float yv = y_int ? 1.f : data[l];
+        if (l < lab.l1) {
+            const int e = lab.entity(l);
+            const float yv = lab.value(l);
             const float q = expf(Jl[e] - mx) / se;
-            const float qc = clip_prob(q);
-            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
+            float ylog;
             fix_e[f] = e;
-            fix_val[f] = q * (inside ? -(g * yv) / qc : 0.f);
+            ll_label_term<true>(q, yv, g, ylog, fix_val[f]);
         }
     }
     __syncthreads();
@@ -366,7 +361,7 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
 #pragma unroll 8
             for (int e = lane; e < V; e += 64) {
                 const float lp = lk[e];
-                r += (lp >= LOGLO && lp <= LOGHI) ? Jl[e] : 0.f;
+                r += ll_masked(lp, Jl[e], LOGLO, LOGHI);
             }
             r = wave_sum(r);
             if (lane == 0) r_out[(size_t)i * n + k] = r;
@@ -379,15 +374,13 @@ __global__ __launch_bounds__(NT) void ll_fused_row(float* __restrict__ Z,
 #pragma unroll 8
         for (int e = lane; e < V; e += 64) {
             const float lp = lk[e];
-            r += (lp >= LOGLO && lp <= LOGHI) ? Jl[e] : 0.f;
+            r += ll_masked(lp, Jl[e], LOGLO, LOGHI);
         }
         r = wave_sum(r);
         float* out = Zi + (size_t)k * V;
 #pragma unroll 8
         for (int e = lane; e < V; e += 64) {
-            const float lp = lk[e];
-            const float dj = (lp >= LOGLO && lp <= LOGHI) ? Jl[e] : 0.f;
-            out[e] = dj - __expf(lp) * r;
+            out[e] = ll_dz(lk[e], Jl[e], r, LOGLO, LOGHI);
         }
     }
 }
@@ -453,7 +446,7 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
                     const float x[8] = {v0[q].x, v0[q].y, v0[q].z, v0[q].w, v1[q].x, v1[q].y, v1[q].z, v1[q].w};
                     bool bad = false;
 #pragma unroll
-                    for (int c = 0; c < 8; ++c) bad = bad || (!(x[c] >= LOGLO && x[c] <= LOGHI) && (c < 4 || two));
+                    for (int c = 0; c < 8; ++c) bad = bad || (!logp_inside(x[c], LOGLO, LOGHI) && (c < 4 || two));
                     if (bad) oob |= 1ull << (k0 + q);
                     a0.x += clip_logp(x[0], LOGLO, LOGHI); a0.y += clip_logp(x[1], LOGLO, LOGHI);
                     a0.z += clip_logp(x[2], LOGLO, LOGHI); a0.w += clip_logp(x[3], LOGLO, LOGHI);
@@ -474,7 +467,7 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
         float a = 0.f;
         for (int k = 0; k < n; ++k) {
             const float lp = Zu[(size_t)s_slot[k] * V + e];
-            if (!(lp >= LOGLO && lp <= LOGHI)) oob |= 1ull << k;
+            if (!logp_inside(lp, LOGLO, LOGHI)) oob |= 1ull << k;
             a += clip_logp(lp, LOGLO, LOGHI);
         }
         Jl[e] = a;
@@ -489,8 +482,7 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
     const float wi = w[i];
     const float g = wi * inv_batch;
     float loss = 0.f, sdq = 0.f;
-    int64_t l0 = 0, l1 = 1;
-    if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
+    const LlLabels lab(y_int, indptr, indices, data, i);
     // (trip f of the label loop is entry f of the thread's fix-up list: kPerThread trips cover every row the host sends
     //  here, LlLabelFix -- 8 at NT = 128, 2 at NT = 512)
     constexpr int NFIX = LlLabelFix<NT>::kPerThread;
@@ -498,17 +490,16 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
     int fix_e[NFIX];
 #pragma unroll
     for (int f = 0; f < NFIX; ++f) {
-        const int64_t l = l0 + tid + (int64_t)f * NT;
+        const int64_t l = lab.l0 + tid + (int64_t)f * NT;
         fix_e[f] = -1;
         fix_val[f] = 0.f;
-        if (l < l1) {
-            const int e = y_int ? y_int[i] : indices[l];
-            const float yv = y_int ? 1.f : data[l];
+        if (l < lab.l1) {
+            const int e = lab.entity(l);
+            const float yv = lab.value(l);
             const float q = expf(Jl[e] - mx) / se;
-            const float qc = clip_prob(q);
-            loss -= yv * logf(qc);
-            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-            const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
+            float ylog, qdq;
+            ll_label_term<true>(q, yv, g, ylog, qdq);
+            loss -= ylog;
             sdq += qdq;
             fix_e[f] = e;
             fix_val[f] = qdq;
@@ -550,7 +541,7 @@ __global__ __launch_bounds__(NT) void ll_row_from_table(const float* __restrict_
             r = 0.f;
             for (int e = lane; e < V; e += 64) {
                 const float lp = lk[e];
-                r += (lp >= LOGLO && lp <= LOGHI) ? Jl[e] : 0.f;
+                r += ll_masked(lp, Jl[e], LOGLO, LOGHI);
             }
             r = wave_sum(r);
         }
@@ -622,7 +613,7 @@ __global__ __launch_bounds__(256) void ll_row_wave(const float* __restrict__ Zu,
                 const bool in = lane + 64 * j < V4;
                 const float x[4] = {v[q][j].x, v[q][j].y, v[q][j].z, v[q][j].w};
 #pragma unroll
-                for (int cc = 0; cc < 4; ++cc) bad = bad || (in && !(x[cc] >= LOGLO && x[cc] <= LOGHI));
+                for (int cc = 0; cc < 4; ++cc) bad = bad || (in && !logp_inside(x[cc], LOGLO, LOGHI));
                 J[j].x += clip_logp(x[0], LOGLO, LOGHI); J[j].y += clip_logp(x[1], LOGLO, LOGHI);
                 J[j].z += clip_logp(x[2], LOGLO, LOGHI); J[j].w += clip_logp(x[3], LOGLO, LOGHI);
             }
@@ -653,11 +644,10 @@ __global__ __launch_bounds__(256) void ll_row_wave(const float* __restrict__ Zu,
     float4 fix[E4PL];
 #pragma unroll
     for (int j = 0; j < E4PL; ++j) fix[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    int64_t l0 = 0, l1 = 1;
-    if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
-    for (int64_t l = l0; l < l1; ++l) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
+    const LlLabels lab(y_int, indptr, indices, data, i);
+    for (int64_t l = lab.l0; l < lab.l1; ++l) {
+        const int e = lab.entity(l);
+        const float yv = lab.value(l);
         const int c = e >> 2, comp = e & 3;
         if ((c & 63) == lane) {                  // (one lane per entry: the sums below are wave sums of one term)
             const int j = c >> 6;
@@ -665,11 +655,9 @@ __global__ __launch_bounds__(256) void ll_row_wave(const float* __restrict__ Zu,
 #pragma unroll
             for (int jj = 0; jj < E4PL; ++jj)
                 if (jj == j) ev = comp == 0 ? E[jj].x : comp == 1 ? E[jj].y : comp == 2 ? E[jj].z : E[jj].w;
-            const float q = ev / se;
-            const float qc = clip_prob(q);
-            loss -= yv * logf(qc);
-            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-            const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
+            float ylog, qdq;
+            ll_label_term<true>(ev / se, yv, g, ylog, qdq);
+            loss -= ylog;
             sdq += qdq;
 #pragma unroll
             for (int jj = 0; jj < E4PL; ++jj)
@@ -714,8 +702,8 @@ __global__ __launch_bounds__(256) void ll_row_wave(const float* __restrict__ Zu,
                 const int c = lane + 64 * j;
                 if (c >= V4) continue;
                 const float4 lp = row[c];
-                r += ((lp.x >= LOGLO && lp.x <= LOGHI) ? J[j].x : 0.f) + ((lp.y >= LOGLO && lp.y <= LOGHI) ? J[j].y : 0.f) +
-                     ((lp.z >= LOGLO && lp.z <= LOGHI) ? J[j].z : 0.f) + ((lp.w >= LOGLO && lp.w <= LOGHI) ? J[j].w : 0.f);
+                r += ll_masked(lp.x, J[j].x, LOGLO, LOGHI) + ll_masked(lp.y, J[j].y, LOGLO, LOGHI) +
+                     ll_masked(lp.z, J[j].z, LOGLO, LOGHI) + ll_masked(lp.w, J[j].w, LOGLO, LOGHI);
             }
             r = wave_sum(r);
             if (lane == k) my_r = r;
@@ -733,9 +721,7 @@ __global__ __launch_bounds__(256) void ll_dzu_combine(float* __restrict__ dZu, c
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t u = t / V;
-        const float lp = logp[t];
-        const float dj = (lp >= LOGLO && lp <= LOGHI) ? dZu[t] : 0.f;
-        dZu[t] = dj - __expf(lp) * rsum[u];
+        dZu[t] = ll_dz(logp[t], dZu[t], rsum[u], LOGLO, LOGHI);
     }
 }
 
@@ -954,19 +940,17 @@ __global__ __launch_bounds__(256) void ll_s_rowloss(const float* __restrict__ J,
     const float wi = TRAIN ? w[i] : 1.f;
     const float g = wi * inv_batch;
     float loss = 0.f, sdq = 0.f;
-    int64_t l0 = 0, l1 = 1;
-    if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
-    for (int64_t l = l0 + tid; l < l1; l += 256) {
-        const int e = y_int ? y_int[i] : indices[l];
-        const float yv = y_int ? 1.f : data[l];
+    const LlLabels lab(y_int, indptr, indices, data, i);
+    for (int64_t l = lab.l0 + tid; l < lab.l1; l += 256) {
+        const int e = lab.entity(l);
+        const float yv = lab.value(l);
         const float q = expf(Ji[e] - mx) / se;
-        const float qc = clip_prob(q);
-        loss -= yv * logf(qc);
+        float ylog, qdq;
+        ll_label_term<TRAIN>(q, yv, g, ylog, qdq);
+        loss -= ylog;
         if (TRAIN) {
-            const bool inside = (q >= SERT_CLIP_LO) && (q <= SERT_CLIP_HI);
-            const float qdq = q * (inside ? -(g * yv) / qc : 0.f);
             sdq += qdq;
-            labfix[y_int ? (int64_t)i : l] = qdq;
+            labfix[lab.slot(l)] = qdq;
         }
     }
     loss = block_sum_256(loss, red);
@@ -1006,12 +990,8 @@ __global__ __launch_bounds__(256) void ll_s_labfix(float* __restrict__ J, const 
                                                    const int32_t* __restrict__ indices,
                                                    const float* __restrict__ labfix, int V) {
     const int i = blockIdx.x;
-    int64_t l0 = 0, l1 = 1;
-    if (y_int == nullptr) { l0 = indptr[i]; l1 = indptr[i + 1]; }
-    for (int64_t l = l0 + threadIdx.x; l < l1; l += 256) {
-        const int e = y_int ? y_int[i] : indices[l];
-        J[(size_t)i * V + e] += labfix[y_int ? (int64_t)i : l];
-    }
+    const LlLabels lab(y_int, indptr, indices, nullptr, i);
+    for (int64_t l = lab.l0 + threadIdx.x; l < lab.l1; l += 256) J[(size_t)i * V + lab.entity(l)] += labfix[lab.slot(l)];
 }
 
 // r_k partials: sum over the segment of mask_ke dJ_e, mask = eps <= P_ke <= 1-eps
@@ -1033,8 +1013,7 @@ __global__ __launch_bounds__(256) void ll_s_tokr(const float* __restrict__ Z, co
     float r = 0.f;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-        const float lp = x[u] - l;
-        r += (lp >= LOGLO && lp <= LOGHI) ? dj[u] : 0.f;
+        r += ll_masked(x[u] - l, dj[u], LOGLO, LOGHI);
     }
     r = block_sum_256(r, red);
     if (threadIdx.x == 0) rpart[blockIdx.x] = r;
@@ -1066,8 +1045,7 @@ __global__ __launch_bounds__(256) void ll_s_dz(float* __restrict__ Z, const floa
     seg_load<V4>(dJ + (size_t)i * V, V, seg, dj, 0.f);
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-        const float lp = x[u] - l;
-        x[u] = ((lp >= LOGLO && lp <= LOGHI) ? dj[u] : 0.f) - __expf(lp) * rk;
+        x[u] = ll_dz(x[u] - l, dj[u], rk, LOGLO, LOGHI);
     }
     seg_store<V4>(Z + (size_t)row * V, V, seg, x);
 }

@@ -1,6 +1,7 @@
 // Order-fixed segmented gather-reduce (replaces fp32 atomic scatter-add), gfx950.
 #pragma once
 #include "common.h"
+#include "loss_terms.h"
 #include "word_index.h"
 
 namespace sert {
@@ -152,10 +153,7 @@ __device__ __forceinline__ void segsum_rows_body(const int bx_, const int by_, c
             const size_t o = (size_t)it.w * d + 4 * c;
             const float4 lp = lp_pre;
             const float rs = rs_pre;
-            a.x = ((lp.x >= LOGLO && lp.x <= LOGHI) ? a.x : 0.f) - __expf(lp.x) * rs;
-            a.y = ((lp.y >= LOGLO && lp.y <= LOGHI) ? a.y : 0.f) - __expf(lp.y) * rs;
-            a.z = ((lp.z >= LOGLO && lp.z <= LOGHI) ? a.z : 0.f) - __expf(lp.z) * rs;
-            a.w = ((lp.w >= LOGLO && lp.w <= LOGHI) ? a.w : 0.f) - __expf(lp.w) * rs;
+            a = ll_dz(lp, a, rs, LOGLO, LOGHI);
             store16<kWtSeg>(final_dst, o, a);
         } else if (it.z >= 0) {
             a.x /= divisor; a.y /= divisor; a.z /= divisor; a.w /= divisor;
@@ -244,9 +242,7 @@ __global__ __launch_bounds__(256) void segsum_rows_scalar(const float* __restric
         if (it.z >= 0) {
             const size_t t = (size_t)(DST_SLOT ? it.w : it.z) * d + c;
             if (LL) {
-                const float lp = logp[t];
-                const float dj = (lp >= LOGLO && lp <= LOGHI) ? a : 0.f;
-                final_dst[t] = dj - __expf(lp) * rs;
+                final_dst[t] = ll_dz(logp[t], a, rs, LOGLO, LOGHI);
             } else {
                 final_dst[t] = a / divisor;
             }
@@ -760,10 +756,7 @@ __device__ __forceinline__ void heavy_combine_ll_body64(const int h, const int s
         const float LOGLO = logf(SERT_CLIP_LO), LOGHI = logf(SERT_CLIP_HI);
         const size_t o = (size_t)slot * d + 4 * ch;
         const float4 lp = *reinterpret_cast<const float4*>(job.logp + o);
-        a.x = ((lp.x >= LOGLO && lp.x <= LOGHI) ? a.x : 0.f) - __expf(lp.x) * rs;
-        a.y = ((lp.y >= LOGLO && lp.y <= LOGHI) ? a.y : 0.f) - __expf(lp.y) * rs;
-        a.z = ((lp.z >= LOGLO && lp.z <= LOGHI) ? a.z : 0.f) - __expf(lp.z) * rs;
-        a.w = ((lp.w >= LOGLO && lp.w <= LOGHI) ? a.w : 0.f) - __expf(lp.w) * rs;
+        a = ll_dz(lp, a, rs, LOGLO, LOGHI);
         store16<kWtSeg>(final_dst, o, a);
     }
 }
@@ -813,10 +806,7 @@ __global__ __launch_bounds__(256) void segsum_heavy_combine_ll(const float* __re
         for (int q = 1; q < 8; ++q) { const float4 v = hc_lds[q][l]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
         const size_t o = (size_t)slot * d + 4 * ch;
         const float4 lp = *reinterpret_cast<const float4*>(logp + o);
-        a.x = ((lp.x >= LOGLO && lp.x <= LOGHI) ? a.x : 0.f) - __expf(lp.x) * rs;
-        a.y = ((lp.y >= LOGLO && lp.y <= LOGHI) ? a.y : 0.f) - __expf(lp.y) * rs;
-        a.z = ((lp.z >= LOGLO && lp.z <= LOGHI) ? a.z : 0.f) - __expf(lp.z) * rs;
-        a.w = ((lp.w >= LOGLO && lp.w <= LOGHI) ? a.w : 0.f) - __expf(lp.w) * rs;
+        a = ll_dz(lp, a, rs, LOGLO, LOGHI);
         store16<kWtSeg>(final_dst, o, a);
     }
 }

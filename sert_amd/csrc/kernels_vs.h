@@ -1,6 +1,10 @@
 // vectorspace / LSE kernels (sert/models.py:1024-1118), gfx950.
+// The loss terms are stated in loss_terms.h and only CALLED here (nce_term, clip_proj / clip_proj_bwd, fs_label_term).  The NCE
+// row has one body per lane layout, nce_rows16 and nce_rows_wave, shared with the fold-in (kernels_foldin.h) through a
+// candidate policy; vs_nce and vs_nce_scalar are their launches over the plain table, vs_nce_regs keeps a body of its own.
 #pragma once
 #include "common.h"
+#include "loss_terms.h"
 #include "kernels_opt.h"   // (TailArgs, vs_tail_body: vs_gather_mean_tail)
 
 namespace sert {
@@ -171,7 +175,7 @@ __global__ void convert_i64_to_i32(const int64_t* __restrict__ in, int32_t* __re
 }
 
 // A NaN projection must reach the loss (numpy and Theano clip a NaN to a NaN; the batch loop stops on a non-finite loss,
-// models.py:372-379), but p = fminf(fmaxf(t, -hi), hi) turns it into the unit -hi and the row's loss stays finite.  Replacing
+// models.py:372-379), but p = clip_proj(t) (loss_terms.h: a min/max) turns it into the unit -hi and the row's loss stays finite.  Replacing
 // that clip with NaN-keeping selects is value-identical for every finite t yet changes how the compiler contracts the dot
 // products behind it (measured: parameters one ulp apart after 110 steps).  So the clip stays as it is and the NaN travels
 // beside it: +-0 when every unit of the row (sixteen lanes, NCH float4 each; |t| <= 1) is finite -- adding it changes no
@@ -189,112 +193,115 @@ __device__ __forceinline__ float row_nan(const float4 (&t)[NCH]) {
 // float4 column chunks l, l+16, ... of the d_e-wide vectors, so one candidate's
 // entity row is a single coalesced 16-lane x 16-byte read and the dot product
 // closes with a 4-step DPP row reduction (no LDS).  With p = clip(t)
-// (models.py:1065-1068):
+// (models.py:1065-1068; clip_proj):
 //   u_j   = <R_e[c_j], p>                 c_0 = y_i, c_1..z = negatives (:990, :897)
 //   s_j   = clip(sigmoid(u_j), eps, 1-eps)                                (:896-900)
 //   loss  = -(log s_0 + sum_{j>0} log(1 - s_j))                           (:1091-1098)
 // TRAIN additionally produces, with g = w_i / B (models.py:278-282):
-//   du_j  = d loss/d u_j (clip gradient mask inclusive, [upstream Clip.grad])
+//   du_j  = d loss/d u_j (nce_term, loss_terms.h)
 //   coef[i,j] = du_j, cand[i,j] = c_j   -> dR_e[c_j] += du_j * p is done by the
 //           order-fixed sorted reduction in kernels_egrad.h (no atomics)
-//   da    = (sum_j du_j R_e[c_j]) * [|t| <= 1-eps] * (1 - t^2)
+//   da    = (sum_j du_j R_e[c_j]) * [|t| <= 1-eps] * (1 - t^2)            (clip_proj_bwd)
 // rowloss[i] = (TRAIN ? w_i : 1) * loss.
-template <int NCH, bool TRAIN>
-__global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
-                                              const float* __restrict__ Re,
-                                              const int32_t* __restrict__ y,
-                                              const int32_t* __restrict__ neg,
-                                              const float* __restrict__ w, float* __restrict__ DA,
-                                              float* __restrict__ coef, int32_t* __restrict__ cand,
-                                              float* __restrict__ rowloss, int B, int z, int de,
-                                              float inv_batch, float* __restrict__ wg_loss) {
-    // wg_loss (optional): wg_loss[blockIdx.x] = sum of this workgroup's sixteen (weighted) row
-    // losses, added in row order -- the first level of the loss reduction rides along instead of
-    // being a launch of its own on the step's critical path
+//
+// The row is walked by ONE body per lane layout -- nce_rows16 here, nce_rows_wave below (any d_e) -- that the vectorspace
+// step and the fold-in (kernels_foldin.h) share.  What differs between them is a CANDIDATE POLICY, Cand:
+//   issue(j)          in front of candidate j's row fetch: whatever the policy loads ahead
+//   row(Re, E, de)    candidate j's row
+//   key(N)            what is recorded beside coef[i, j]: the entity id, or the fold-in's sort key
+//   commit()          behind candidate j's arithmetic
+// and WITH_DA: keep the candidates' rows and produce da (the step), or not (the fold-in: nothing below the projection learns).
+
+// the plain table: row R_e[e], records the id
+struct NcePlainTable {
+    const int32_t* __restrict__ yi;     // the instance's label
+    const int32_t* __restrict__ nrow;   // its z negatives
+    int i, e;
+    __device__ __forceinline__ NcePlainTable(const int32_t* __restrict__ y, const int32_t* __restrict__ neg, int i_, int z)
+        : yi(y + i_), nrow(neg + (size_t)i_ * z), i(i_), e(0) {}
+    __device__ __forceinline__ void issue(int j) {
+#if defined(SERT_VARIANTS) && defined(KO_IDS)   // timing knock-out (wrong results), variants build only
+        e = (i * 7 + j * 13) & 2047;
+#else
+        e = (j == 0) ? *yi : nrow[j - 1];
+#endif
+    }
+    __device__ __forceinline__ void commit() {}
+    __device__ __forceinline__ const float* row(const float* __restrict__ Re, const float* __restrict__, int de) const {
+        return Re + (size_t)e * de;
+    }
+    __device__ __forceinline__ int key(int) const { return e; }
+};
+
+// i: the instance, clamped onto the last one for the rows past the end of a ragged last workgroup (valid = false): those are
+// computed and never stored -- no early return, so that every wave reaches the barrier below exactly once (a divergent
+// return would make a half-active wave hit it on both paths).
+// wg_loss (optional): wg_loss[blockIdx.x] = sum of this workgroup's sixteen (weighted) row losses, added in row order --
+// the first level of the loss reduction rides along instead of being a launch of its own on the step's critical path.
+template <int NCH, bool TRAIN, bool WITH_DA, typename Cand>
+__device__ __forceinline__ void nce_rows16(const float* __restrict__ T, const float* __restrict__ Re,
+                                           const float* __restrict__ E, Cand c, const float* __restrict__ w,
+                                           float* __restrict__ DA, float* __restrict__ coef, int32_t* __restrict__ key,
+                                           float* __restrict__ rowloss, int i, bool valid, int z, int de, int N,
+                                           float inv_batch, float* __restrict__ wg_loss) {
     __shared__ float wg_red[16];
     const int l = threadIdx.x & 15;
-    // Rows past the end (ragged last workgroup) are computed on a clamped row and never stored:
-    // no early return, so that every wave reaches the barrier below exactly once (a divergent
-    // return would make a half-active wave hit it on both paths).
-    const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const bool valid = i_raw < B;
-    const int i = valid ? i_raw : B - 1;
     const int chunks = de >> 2;  // de % 4 == 0 on this path
     float4 t[NCH], p[NCH], dp[NCH];
 #pragma unroll
     for (int q = 0; q < NCH; ++q) {
-        const int c = l + 16 * q;
-        t[q] = (c < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * c)
-                            : make_float4(0.f, 0.f, 0.f, 0.f);
-        p[q].x = fminf(fmaxf(t[q].x, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].y = fminf(fmaxf(t[q].y, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].z = fminf(fmaxf(t[q].z, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].w = fminf(fmaxf(t[q].w, -SERT_CLIP_HI), SERT_CLIP_HI);
+        const int cc = l + 16 * q;
+        t[q] = (cc < chunks) ? *reinterpret_cast<const float4*>(T + (size_t)i * de + 4 * cc)
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        p[q] = clip_proj(t[q]);
         dp[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     const float wi = TRAIN ? w[i] : 1.f;
     const float g = wi * inv_batch;
     float loss = 0.f;
     for (int j = 0; j <= z; ++j) {
-#if defined(SERT_VARIANTS) && defined(KO_IDS)   // timing knock-out (wrong results), variants build only
-        const int e = (i * 7 + j * 13) & 2047;
-#else
-        const int e = (j == 0) ? y[i] : neg[(size_t)i * z + (j - 1)];
-#endif
+        c.issue(j);
+        const float* __restrict__ row = c.row(Re, E, de);
         float4 er[NCH];
         float part = 0.f;
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
-            const int c = l + 16 * q;
+            const int cc = l + 16 * q;
 #if defined(SERT_VARIANTS) && defined(KO_ROWS)   // timing knock-out (wrong results), variants build only
-            er[q] = make_float4(1.f * e, 0.5f, 0.25f * j, 0.f);
-#else
-            er[q] = (c < chunks) ? *reinterpret_cast<const float4*>(Re + (size_t)e * de + 4 * c)
-                                 : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (WITH_DA) er[q] = make_float4(1.f * c.key(N), 0.5f, 0.25f * j, 0.f);
+            else
 #endif
+            er[q] = (cc < chunks) ? *reinterpret_cast<const float4*>(row + 4 * cc) : make_float4(0.f, 0.f, 0.f, 0.f);
             part += er[q].x * p[q].x + er[q].y * p[q].y + er[q].z * p[q].z + er[q].w * p[q].w;
         }
         const float u = row16_sum(part);
-#if defined(SERT_VARIANTS) && defined(KO_MATH)   // timing knock-out (wrong results), variants build only
-        const float sig = u * 0.01f + 0.5f;
-        const float s = clip_prob(sig);
-        loss -= s;
-#else
-        const float sig = theano_sigmoid(u);
-        const float s = clip_prob(sig);
-        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
-#endif
+        float logterm, du;
+        nce_term<TRAIN>(u, j == 0, g, logterm, du);
+        loss -= logterm;
         if (TRAIN) {
-            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-            float du = 0.f;
-            if (inside) {
-                const float ds = sig * (1.0f - sig);
-                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-            }
+            if (WITH_DA) {
 #pragma unroll
-            for (int q = 0; q < NCH; ++q) {
-                dp[q].x += du * er[q].x; dp[q].y += du * er[q].y;
-                dp[q].z += du * er[q].z; dp[q].w += du * er[q].w;
+                for (int q = 0; q < NCH; ++q) {
+                    dp[q].x += du * er[q].x; dp[q].y += du * er[q].y;
+                    dp[q].z += du * er[q].z; dp[q].w += du * er[q].w;
+                }
             }
-#if !(defined(SERT_VARIANTS) && defined(KO_COEF))   // (knock-out: variants build only)
+#if defined(SERT_VARIANTS) && defined(KO_COEF)   // timing knock-out (the step's kernels), variants build only
+            if (!WITH_DA)
+#endif
             if (l == 0 && valid) {
                 coef[(size_t)i * (z + 1) + j] = du;
-                cand[(size_t)i * (z + 1) + j] = e;
+                key[(size_t)i * (z + 1) + j] = c.key(N);
             }
-#endif
         }
+        c.commit();
     }
-    if (TRAIN) {
+    if (TRAIN && WITH_DA) {
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
-            const int c = l + 16 * q;
-            if (c >= chunks || !valid) continue;
-            float4 o;
-            o.x = (t[q].x >= -SERT_CLIP_HI && t[q].x <= SERT_CLIP_HI) ? dp[q].x * (1.0f - t[q].x * t[q].x) : 0.f;
-            o.y = (t[q].y >= -SERT_CLIP_HI && t[q].y <= SERT_CLIP_HI) ? dp[q].y * (1.0f - t[q].y * t[q].y) : 0.f;
-            o.z = (t[q].z >= -SERT_CLIP_HI && t[q].z <= SERT_CLIP_HI) ? dp[q].z * (1.0f - t[q].z * t[q].z) : 0.f;
-            o.w = (t[q].w >= -SERT_CLIP_HI && t[q].w <= SERT_CLIP_HI) ? dp[q].w * (1.0f - t[q].w * t[q].w) : 0.f;
-            store16<kWtNce>(DA, (size_t)i * de + 4 * c, o);
+            const int cc = l + 16 * q;
+            if (cc >= chunks || !valid) continue;
+            store16<kWtNce>(DA, (size_t)i * de + 4 * cc, clip_proj_bwd(t[q], dp[q]));
         }
     }
     loss += row_nan(t);
@@ -309,6 +316,22 @@ __global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
             wg_loss[blockIdx.x] = s;
         }
     }
+}
+
+template <int NCH, bool TRAIN>
+__global__ __launch_bounds__(256) void vs_nce(const float* __restrict__ T,
+                                              const float* __restrict__ Re,
+                                              const int32_t* __restrict__ y,
+                                              const int32_t* __restrict__ neg,
+                                              const float* __restrict__ w, float* __restrict__ DA,
+                                              float* __restrict__ coef, int32_t* __restrict__ cand,
+                                              float* __restrict__ rowloss, int B, int z, int de,
+                                              float inv_batch, float* __restrict__ wg_loss) {
+    const int i_raw = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool valid = i_raw < B;
+    const int i = valid ? i_raw : B - 1;
+    nce_rows16<NCH, TRAIN, true>(T, Re, nullptr, NcePlainTable(y, neg, i, z), w, DA, coef, cand, rowloss, i, valid, z, de, 0,
+                                 inv_batch, wg_loss);
 }
 
 // All candidates of a row in registers (z + 1 <= MAXC <= 16): the candidate ids arrive in one load
@@ -361,12 +384,7 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
     }
     float4 p[NCH];
 #pragma unroll
-    for (int q = 0; q < NCH; ++q) {
-        p[q].x = fminf(fmaxf(t[q].x, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].y = fminf(fmaxf(t[q].y, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].z = fminf(fmaxf(t[q].z, -SERT_CLIP_HI), SERT_CLIP_HI);
-        p[q].w = fminf(fmaxf(t[q].w, -SERT_CLIP_HI), SERT_CLIP_HI);
-    }
+    for (int q = 0; q < NCH; ++q) p[q] = clip_proj(t[q]);
     float my_u = 0.f;
 #pragma unroll
     for (int u = 0; u < MAXC; ++u) {
@@ -380,17 +398,11 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
     const float wi = TRAIN ? w[i] : 1.f;
     const float g = wi * inv_batch;
     const bool act = l <= z;
-    const float sig = theano_sigmoid(my_u);
-    const float s = clip_prob(sig);
-    const float term = (l == 0) ? logf(s) : logf(1.0f - s);
+    float term, du_l;
+    nce_term<TRAIN>(my_u, l == 0, g, term, du_l);
     const float loss = -row16_sum(act ? term : 0.f) + row_nan(t);
     if (TRAIN) {
-        const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-        float du = 0.f;
-        if (inside && act) {
-            const float ds = sig * (1.0f - sig);
-            du = (l == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-        }
+        const float du = act ? du_l : 0.f;
         if (act && valid) {
             coef[(size_t)i * (z + 1) + l] = du;
             cand[(size_t)i * (z + 1) + l] = my_e;
@@ -411,12 +423,7 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
         for (int q = 0; q < NCH; ++q) {
             const int c = l + 16 * q;
             if ((!FULL && c >= chunks) || !valid) continue;
-            float4 o;
-            o.x = (t[q].x >= -SERT_CLIP_HI && t[q].x <= SERT_CLIP_HI) ? dp[q].x * (1.0f - t[q].x * t[q].x) : 0.f;
-            o.y = (t[q].y >= -SERT_CLIP_HI && t[q].y <= SERT_CLIP_HI) ? dp[q].y * (1.0f - t[q].y * t[q].y) : 0.f;
-            o.z = (t[q].z >= -SERT_CLIP_HI && t[q].z <= SERT_CLIP_HI) ? dp[q].z * (1.0f - t[q].z * t[q].z) : 0.f;
-            o.w = (t[q].w >= -SERT_CLIP_HI && t[q].w <= SERT_CLIP_HI) ? dp[q].w * (1.0f - t[q].w * t[q].w) : 0.f;
-            store16<kWtNce>(DA, (size_t)i * de + 4 * c, o);
+            store16<kWtNce>(DA, (size_t)i * de + 4 * c, clip_proj_bwd(t[q], dp[q]));
         }
     }
     if (l == 0 && valid) rowloss[i] = wi * loss;
@@ -432,7 +439,68 @@ __global__ __launch_bounds__(256) void vs_nce_regs(const float* __restrict__ T,
     }
 }
 
-// Generic-width fallback (d_e % 4 != 0): one wave per row, scalar columns.
+// Generic-width fallback (d_e % 4 != 0): one wave per row, scalar columns -- the second lane layout of the shared row body
+// (Cand, WITH_DA: see nce_rows16).  i < B: the caller returned for the rows past the end.  No barrier, no workgroup
+// partial: the loss is finalised from rowloss.
+template <int NPL, bool TRAIN, bool WITH_DA, typename Cand>
+__device__ __forceinline__ void nce_rows_wave(const float* __restrict__ T, const float* __restrict__ Re,
+                                              const float* __restrict__ E, Cand c, const float* __restrict__ w,
+                                              float* __restrict__ DA, float* __restrict__ coef, int32_t* __restrict__ key,
+                                              float* __restrict__ rowloss, int i, int z, int de, int N, float inv_batch) {
+    const int lane = threadIdx.x & 63;
+    float t[NPL], p[NPL], dp[NPL];
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) {
+        const int cc = lane + 64 * q;
+        t[q] = (cc < de) ? T[(size_t)i * de + cc] : 0.f;
+        p[q] = clip_proj(t[q]);
+        dp[q] = 0.f;
+    }
+    const float wi = TRAIN ? w[i] : 1.f;
+    const float g = wi * inv_batch;
+    float loss = 0.f;
+    for (int j = 0; j <= z; ++j) {
+        c.issue(j);
+        const float* __restrict__ row = c.row(Re, E, de);
+        float er[NPL];
+        float part = 0.f;
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) {
+            const int cc = lane + 64 * q;
+            er[q] = (cc < de) ? row[cc] : 0.f;
+            part += er[q] * p[q];
+        }
+        const float u = wave_sum(part);
+        float logterm, du;
+        nce_term<TRAIN>(u, j == 0, g, logterm, du);
+        loss -= logterm;
+        if (TRAIN) {
+            if (WITH_DA) {
+#pragma unroll
+                for (int q = 0; q < NPL; ++q) dp[q] += du * er[q];
+            }
+            if (lane == 0) {
+                coef[(size_t)i * (z + 1) + j] = du;
+                key[(size_t)i * (z + 1) + j] = c.key(N);
+            }
+        }
+        c.commit();
+    }
+    if (TRAIN && WITH_DA) {
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) {
+            const int cc = lane + 64 * q;
+            if (cc < de) DA[(size_t)i * de + cc] = clip_proj_bwd(t[q], dp[q]);
+        }
+    }
+    // (a NaN unit of the row: see row_nan)
+    float tsum = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) tsum += t[q];
+    loss += wave_sum(tsum) * 0.0f;
+    if (lane == 0) rowloss[i] = wi * loss;
+}
+
 template <int NPL, bool TRAIN>
 __global__ __launch_bounds__(256) void vs_nce_scalar(const float* __restrict__ T,
                                                      const float* __restrict__ Re,
@@ -444,74 +512,15 @@ __global__ __launch_bounds__(256) void vs_nce_scalar(const float* __restrict__ T
                                                      int32_t* __restrict__ cand,
                                                      float* __restrict__ rowloss, int B, int z,
                                                      int de, float inv_batch) {
-    const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= B) return;
-    float t[NPL], p[NPL], dp[NPL];
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) {
-        const int c = lane + 64 * q;
-        t[q] = (c < de) ? T[(size_t)i * de + c] : 0.f;
-        p[q] = fminf(fmaxf(t[q], -SERT_CLIP_HI), SERT_CLIP_HI);
-        dp[q] = 0.f;
-    }
-    const float wi = TRAIN ? w[i] : 1.f;
-    const float g = wi * inv_batch;
-    float loss = 0.f;
-    for (int j = 0; j <= z; ++j) {
-        const int e = (j == 0) ? y[i] : neg[(size_t)i * z + (j - 1)];
-        float er[NPL];
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) {
-            const int c = lane + 64 * q;
-            er[q] = (c < de) ? Re[(size_t)e * de + c] : 0.f;
-            part += er[q] * p[q];
-        }
-        const float u = wave_sum(part);
-#if defined(SERT_VARIANTS) && defined(KO_MATH)   // timing knock-out (wrong results), variants build only
-        const float sig = u * 0.01f + 0.5f;
-        const float s = clip_prob(sig);
-        loss -= s;
-#else
-        const float sig = theano_sigmoid(u);
-        const float s = clip_prob(sig);
-        loss -= (j == 0) ? logf(s) : logf(1.0f - s);
-#endif
-        if (TRAIN) {
-            const bool inside = (sig >= SERT_CLIP_LO) && (sig <= SERT_CLIP_HI);
-            float du = 0.f;
-            if (inside) {
-                const float ds = sig * (1.0f - sig);
-                du = (j == 0) ? -(g / s) * ds : (g / (1.0f - s)) * ds;
-            }
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) dp[q] += du * er[q];
-            if (lane == 0) {
-                coef[(size_t)i * (z + 1) + j] = du;
-                cand[(size_t)i * (z + 1) + j] = e;
-            }
-        }
-    }
-    if (TRAIN) {
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) {
-            const int c = lane + 64 * q;
-            const bool inside = (t[q] >= -SERT_CLIP_HI) && (t[q] <= SERT_CLIP_HI);
-            if (c < de) DA[(size_t)i * de + c] = inside ? dp[q] * (1.0f - t[q] * t[q]) : 0.f;
-        }
-    }
-    // (a NaN unit of the row: see row_nan)
-    float tsum = 0.f;
-#pragma unroll
-    for (int q = 0; q < NPL; ++q) tsum += t[q];
-    loss += wave_sum(tsum) * 0.0f;
-    if (lane == 0) rowloss[i] = wi * loss;
+    nce_rows_wave<NPL, TRAIN, true>(T, Re, nullptr, NcePlainTable(y, neg, i, z), w, DA, coef, cand, rowloss, i, z, de, 0,
+                                    inv_batch);
 }
 
 // ---- full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX; additive) -----------
 // In place on the logits Z (B, V): P = softmax(Z_i);
-//   loss_i = -log clip(P[y_i], eps, 1-eps)      (same clipping as models.py:289-292)
+//   loss_i = -log clip(P[y_i], eps, 1-eps)      (same clipping as models.py:289-292; fs_label_term, loss_terms.h)
 //   TRAIN: Z_i <- dL/dZ_i = g_i * [eps <= P_y <= 1-eps] * (P - onehot(y_i)),  g_i = w_i / B
 // One wave per row.  EPL > 0: the row (V <= 64*EPL) stays in registers -- one read of Z,
 // one write of dZ (the 3-pass form below re-reads the row from cache twice and pays two
@@ -551,11 +560,10 @@ __global__ __launch_bounds__(256) void fs_softmax_ce(float* __restrict__ Z,
 #pragma unroll
         for (int u = 0; u < EPL; ++u) pyl = (lane + 64 * u == yi) ? x[u] : pyl;
         const float py = wave_sum(pyl) / sm;
-        const float pyc = clip_prob(py);
-        if (lane == 0) rowloss[i] = -wi * logf(pyc);
+        float loss, g;
+        fs_label_term<TRAIN>(py, wi, inv_batch, loss, g);
+        if (lane == 0) rowloss[i] = loss;
         if (TRAIN) {
-            const bool inside = (py >= SERT_CLIP_LO) && (py <= SERT_CLIP_HI);
-            const float g = inside ? wi * inv_batch : 0.f;
 #pragma unroll
             for (int u = 0; u < EPL; ++u) {
                 const int e = lane + 64 * u;
@@ -571,11 +579,10 @@ __global__ __launch_bounds__(256) void fs_softmax_ce(float* __restrict__ Z,
     for (int e = lane; e < V; e += 64) sm += __expf(z[e] - mx);
     sm = wave_sum(sm);
     const float py = __expf(z[yi] - mx) / sm;
-    const float pyc = clip_prob(py);
-    if (lane == 0) rowloss[i] = -wi * logf(pyc);
+    float loss, g;
+    fs_label_term<TRAIN>(py, wi, inv_batch, loss, g);
+    if (lane == 0) rowloss[i] = loss;
     if (TRAIN) {
-        const bool inside = (py >= SERT_CLIP_LO) && (py <= SERT_CLIP_HI);
-        const float g = inside ? wi * inv_batch : 0.f;
         for (int e = lane; e < V; e += 64) {
             const float p = __expf(z[e] - mx) / sm;
             z[e] = g * (p - (e == yi ? 1.f : 0.f));
@@ -587,9 +594,7 @@ __global__ __launch_bounds__(256) void fs_softmax_ce(float* __restrict__ Z,
 __global__ void vs_tanh_backward(float* __restrict__ DP, const float* __restrict__ T, size_t count) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count;
          i += (size_t)gridDim.x * blockDim.x) {
-        const float t = T[i];
-        const bool inside = (t >= -SERT_CLIP_HI) && (t <= SERT_CLIP_HI);
-        DP[i] = inside ? DP[i] * (1.0f - t * t) : 0.f;
+        DP[i] = clip_proj_bwd(T[i], DP[i]);
     }
 }
 

@@ -2,8 +2,9 @@
 instances were uploaded -- shared by the CPU proof of the inputs (test_foldin_keys_inputs_cpu.py) and the GPU test
 (test_gpu_foldin_keys.py).  Patterned on tests/egrad_key_cases.py.
 
-A fold-in step (csrc/kernels_foldin.h, dispatch in csrc/host/api_foldin.inc) runs copies of the vectorspace step's kernels,
-changed where it matters: foldin_nce<K> / foldin_nce_scalar<K> score a two-part table and write a KEY per pair (the new row,
+A fold-in step (csrc/kernels_foldin.h, dispatch in csrc/host/api_foldin.inc) runs the vectorspace step's kernels, changed
+where it matters: foldin_nce<K> / foldin_nce_scalar<K> -- the row body of the step's loss kernel (csrc/kernels_vs.h,
+nce_rows16 / nce_rows_wave) under another candidate policy -- score a two-part table and write a KEY per pair (the new row,
 or the sentinel N for a pair on a frozen row); csort_pass sorts the B (z + 1) keys over the smallest b bits with 2^b > N;
 foldin_chunk_reduce<VEC, NCH> reduces chunks of CHUNK = 16 sorted pairs and stops at the sentinel run, which is the END of the
 order; egrad_fixup<VEC> (N >= 256) or egrad_fixup_wg<VEC> adds the carries of the runs that cross chunks.  The sort is stable

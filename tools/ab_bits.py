@@ -1,0 +1,216 @@
+#!/usr/bin/env python
+"""Bit-for-bit A/B of two builds of the library over tiny problems that reach every loss kernel family.
+
+    python tools/ab_bits.py --lib sert_amd/variants/libsert_parent.so --out parent.npz
+    python tools/ab_bits.py --out change.npz --against parent.npz
+
+Each problem runs two training steps and both evaluations (a fold-in: two steps and one evaluation) and records the losses,
+the row losses, every parameter, gradient and optimiser moment, the fold-in rows, and the form the engine reports it
+took.  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.  The
+library is chosen by SERT_LIB, read at import, and SERT_LL_NODEDUP once per process: every (library, group) runs in a fresh
+child process started with subprocess, one at a time.  The run fails if the forms taken do not cover FAMILIES."""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+B = 37                       # a ragged last workgroup in both lane layouts (16 and 4 rows per workgroup)
+# loglinear: name -> (n, V_e); csrc/host/step_softmax_loglinear.inc, ll_forward
+LL = {'wave1': (7, 256), 'wave2': (7, 400), 'wave4': (7, 800), 'wave8': (7, 1028), 'table128': (7, 601),
+      'table512': (7, 2050), 'fusedrow': (65, 300), 'stream_v4': (3, 13000), 'stream_scalar': (3, 13001)}
+LL_PER_TOKEN = ('fusedrow', 'stream_v4', 'stream_scalar')            # the group under SERT_LL_NODEDUP: no slot table
+# vectorspace: name -> (z, d_e); csrc/host/step_vectorspace.inc, vs_loss
+VS = {'percand20': (12, 20), 'percand64': (12, 64), 'regs6': (5, 8), 'regs11': (10, 64), 'regs12': (11, 20), 'scalar': (3, 130)}
+FS = {'fs16': 200, 'fs32': 1500, 'fs0': 2100}                        # V_e -> fs_softmax_ce<.., EPL>: 16 to 1024, 32 to 2048
+FOLDIN = {'vector20': 20, 'vector64': 64, 'scalar130': 130}          # d_e; each with and without refreshed rows (the slot map)
+FAMILIES = (['ll %s %s %s' % (f, lab, m) for lab in ('int', 'csr') for f, m in
+             [('wave%d' % e, 'slots') for e in (1, 2, 4, 8)] + [('table128', 'slots'), ('table512', 'slots'),
+              ('fused_row512 train', 'slots'), ('fused_row512 train', 'tokens'), ('fused_row512 eval', 'slots'),
+              ('fused_row512 eval', 'tokens'), ('stream1', 'slots'), ('stream0', 'slots'), ('stream1', 'tokens'),
+              ('stream0', 'tokens')]] +
+            ['nce per_candidate train', 'nce per_candidate eval', 'nce scalar train', 'nce scalar eval'] +
+            ['nce regs%d %s' % (c, t) for c in (6, 11, 12) for t in ('train', 'eval')] + ['fs epl%d' % e for e in (16, 32, 0)] +
+            ['foldin %s %s %s' % (f, m, t) for f in ('vector', 'scalar') for m in ('two_part', 'map') for t in ('train', 'eval')])
+
+
+def run_engine(out, tag, eng, kind, uploads, form):
+    from sert_amd import _capi as C
+    from tests import util as U
+    for split, kw in uploads:
+        eng.upload_dataset(split, **kw)
+    forms = []
+    for step, call in enumerate([lambda: eng.train_batch(0), lambda: eng.train_batch(1),
+                                 lambda: eng.eval_batch(C.SPLIT_TRAIN, 0), lambda: eng.eval_batch(C.SPLIT_VALIDATE, 0)]):
+        out['%s/loss%d' % (tag, step)] = np.float32(call())
+        out['%s/rowloss%d' % (tag, step)] = eng.get_tensor(C.T_ACT_ROWLOSS)
+        forms.append(form(eng))
+    for k, v in U.engine_state(eng).items():
+        out['%s/%s' % (tag, k)] = v
+    for name, which in (('g.R_w', C.T_GRAD_RW), ('g.R_e', C.T_GRAD_RE), ('g.W', C.T_GRAD_W), ('g.b', C.T_GRAD_B),
+                        ('act.T', C.T_ACT_T), ('act.DA', C.T_ACT_DA)):
+        if kind != C.KIND_LOGLINEAR or name in ('g.R_w', 'g.W', 'g.b'):
+            out['%s/%s' % (tag, name)] = eng.get_tensor(which)
+    eng.close()
+    return forms
+
+
+def ll_form(eng):
+    f = eng.ll_loss_form()
+    name = f['form'] + str(f['param'])
+    if f['form'] == 'fused_row':
+        name += ' train' if f['train'] else ' eval'
+    return name, 'slots' if f['slots'] else 'tokens'
+
+
+def run_ll(out, tag, p, b, n, labels):
+    from sert_amd import _capi as C
+    from tests import util as U
+    eng = U.ll_engine(p, b, n, 0.0 if 'plant' in tag else 0.01)
+    lab = (lambda sl: dict(y_int=p['y'][sl])) if labels == 'int' else (lambda sl: dict(csr=p['y'][sl]))
+    tr, va = slice(0, 2 * b), slice(2 * b, 3 * b)
+    forms = run_engine(out, tag, eng, C.KIND_LOGLINEAR, [(C.SPLIT_TRAIN, dict(x=p['X'][tr], w=p['w'][tr], **lab(tr))),
+                                                        (C.SPLIT_VALIDATE, dict(x=p['X'][va], w=p['w'][va], **lab(va)))], ll_form)
+    return ['ll %s %s %s' % (name, labels, mode) for name, mode in forms]
+
+
+def run_vs(out, tag, p, z, kind=None):
+    from sert_amd import _capi as C
+    from tests import util as U
+    n = p['X'].shape[1]
+    if kind is None:
+        eng = U.vs_engine(p, B, n, z, 0.01)
+    else:
+        eng = C.Engine(kind=kind, batch_size=B, global_batch_size=B, window_size=n, vocab_size=p['Rw'].shape[0],
+                       num_entities=p['Re'].shape[0], word_dim=p['Rw'].shape[1], entity_dim=p['Re'].shape[1], num_negatives=0,
+                       id_bytes=p['X'].dtype.itemsize, device=0, keep_grads=1, deterministic=1, lambda_=0.01, lr=1e-3,
+                       beta1=0.9, beta2=0.999, eps=1e-8, seed=1)
+        for which, key in ((C.T_RW, 'Rw'), (C.T_RE, 'Re'), (C.T_W, 'W'), (C.T_B, 'b')):
+            eng.set_tensor(which, p[key])
+    tr, va = slice(0, 2 * B), slice(2 * B, 3 * B)
+
+    def form(e):
+        if kind is not None:
+            V = p['Re'].shape[0]
+            return 'fs epl%d' % (16 if V <= 1024 else 32 if V <= 2048 else 0)     # (no hook: the rule of fs_forward)
+        f = e.nce_form()
+        return 'nce %s%s %s' % (f['form'], f['maxc'] if f['form'] == 'regs' else '', 'train' if f['train'] else 'eval')
+    return run_engine(out, tag, eng, C.KIND_VECTORSPACE, [(C.SPLIT_TRAIN, dict(x=p['X'][tr], y_int=p['y'][tr], w=p['w'][tr])),
+                                                         (C.SPLIT_VALIDATE, dict(x=p['X'][va], y_int=p['y'][va], w=p['w'][va]))], form)
+
+
+def run_foldin(out, tag, p, z, refresh):
+    from sert_amd import _capi as C
+    from tests import util as U
+    n, (Ve, de) = p['X'].shape[1], p['Re'].shape
+    eng = U.vs_engine(p, 8, n, 2, 0.01, keep_grads=0)
+    rng = np.random.RandomState(7)
+    new = 5
+    f = C.FoldIn(eng, (0.1 * rng.randn(new, de)).astype(np.float32), B, z, 0.01, seed=3,
+                 refresh_ids=np.array([3, Ve - 1, 10], dtype=np.int32) if refresh else None)
+    f.upload(p['X'][:2 * B].astype(np.int32), rng.randint(0, f.num_rows, 2 * B).astype(np.int32), p['w'][:2 * B])
+    forms = []
+    for step, call in enumerate([lambda: f.train_batch(0), lambda: f.train_batch(1), lambda: f.eval_batch(0)]):
+        out['%s/loss%d' % (tag, step)] = np.float32(call())
+        pl = f.plan()
+        forms.append('foldin %s %s %s' % (pl['loss'], 'map' if f.table()['map'] else 'two_part', 'train' if pl['train'] else 'eval'))
+    for name, which in (('E', C.FOLDIN_ROWS), ('m', C.FOLDIN_M), ('v', C.FOLDIN_V)):
+        out['%s/%s' % (tag, name)] = f.get_rows(which)
+    f.close()
+    eng.close()
+    return forms
+
+
+def child(group, path):
+    from sert_amd import _capi as C
+    from tests import ll_nonfinite_cases as NF
+    from tests import util as U
+    out, forms = {}, []
+    for k, name in enumerate(sorted(LL if group == 'slots' else LL_PER_TOKEN)):
+        n, Ve = LL[name]
+        for labels in ('int', 'csr'):
+            p = U.make_ll_problem(500 + k, 3 * B, n, 150, Ve, 16, labels=labels)
+            forms += run_ll(out, 'll_%s_%s_%s' % (group, name, labels), p, B, n, labels)
+    if group == 'slots':
+        # one input that clips (a bias of -inf: the probability clips to 1e-7) and one planted NaN, loglinear ...
+        for plant in (NF.CONTROL, 'nan_word_mid'):
+            c, p = NF.case_problem('wave2')
+            Rw, W, b, _ = NF.planted('wave2', plant)
+            forms += run_ll(out, 'll_plant_%s' % plant, dict(p, Rw=Rw, W=W, b=b), NF.B, c['n'], 'int')
+        for k, name in enumerate(sorted(VS)):
+            z, de = VS[name]
+            forms += run_vs(out, 'vs_' + name, U.make_vs_problem(600 + k, 3 * B, 5, z, 150, 90, 12, de), z)
+        # ... and NCE: saturated sigmoids and tanh units (entity rows and W scaled up), a NaN in a word row of batch 0
+        for plant in ('clip', 'nan'):
+            p = U.make_vs_problem(650, 3 * B, 5, 12, 150, 90, 12, 20)
+            if plant == 'clip':
+                p['Re'], p['W'] = p['Re'] * np.float32(40), p['W'] * np.float32(30)
+            else:
+                p['Rw'][int(p['X'][3, 2]), 4] = np.nan
+            forms += run_vs(out, 'vs_plant_' + plant, p, 12)
+        for k, name in enumerate(sorted(FS)):
+            forms += run_vs(out, 'fs_' + name, U.make_vs_problem(700 + k, 3 * B, 5, 0, 150, FS[name], 12, 20), 0,
+                            kind=C.KIND_VECTORSPACE_SOFTMAX)
+        for k, name in enumerate(sorted(FOLDIN)):
+            for refresh in (False, True):
+                p = U.make_vs_problem(800 + k, 2 * B, 5, 6, 150, 90, 12, FOLDIN[name])
+                forms += run_foldin(out, 'foldin_%s_%d' % (name, refresh), p, 6, refresh)
+    out['forms'] = np.array(sorted(set(forms)))
+    np.savez_compressed(path, **out)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--lib', help='library to run (SERT_LIB); default: the tree\'s own')
+    ap.add_argument('--against', help='an .npz of an earlier run: every array must hold the same bits')
+    ap.add_argument('--child', help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.out)
+    merged = {}
+    for group in ('slots', 'tokens'):
+        env = dict(os.environ)
+        env.pop('SERT_LL_NODEDUP', None)
+        if a.lib:
+            env['SERT_LIB'] = os.path.abspath(a.lib)
+        if group == 'tokens':
+            env['SERT_LL_NODEDUP'] = '1'
+        with tempfile.TemporaryDirectory() as tmp:
+            part = os.path.join(tmp, group + '.npz')
+            subprocess.run([sys.executable, os.path.abspath(__file__), '--child', group, '--out', part], env=env, cwd=ROOT, check=True)
+            with np.load(part) as z:
+                forms = set(merged.get('forms', ())) | set(z['forms'].tolist())
+                merged.update({k: z[k] for k in z.files})
+                merged['forms'] = np.array(sorted(forms))
+    np.savez_compressed(a.out, **merged)
+    missing = [f for f in FAMILIES if f not in set(merged['forms'].tolist())]
+    print('%d arrays, %d forms' % (len(merged) - 1, len(merged['forms'])))
+    if missing:
+        print('forms taken:\n  ' + '\n  '.join(merged['forms'].tolist()))
+        sys.exit('families not reached: %s' % missing)
+    if a.against:
+        with np.load(a.against) as z:
+            other = {k: z[k] for k in z.files}
+        keys = sorted(set(merged) | set(other))
+        diff = [k for k in keys if k not in merged or k not in other or merged[k].shape != other[k].shape or
+                not np.array_equal(np.ascontiguousarray(merged[k]).view(np.uint8), np.ascontiguousarray(other[k]).view(np.uint8))]
+        for k in diff:
+            if k in merged and k in other and merged[k].shape == other[k].shape and merged[k].dtype == np.float32:
+                x, y = merged[k].ravel().view(np.uint32), other[k].ravel().view(np.uint32)
+                print('DIFFERENT %s: %d of %d elements' % (k, int((x != y).sum()), x.size))
+            else:
+                print('DIFFERENT %s (missing, or another shape)' % k)
+        nans = sum(int(np.isnan(v).any()) for k, v in merged.items() if v.dtype == np.float32)
+        print('%d arrays compared, %d differ; %d arrays hold a NaN' % (len(keys), len(diff), nans))
+        if diff:
+            sys.exit(1)
+
+
+if __name__ == '__main__':
+    main()
