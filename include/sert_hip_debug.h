@@ -60,7 +60,7 @@ enum {
 int sert_debug_ll_loss_form(sert_model* m, int32_t* out, int n);
 
 /* What the LAST vectorspace backward of this model launched for dR_e, the entity-table gradient (csrc/kernels_egrad.h, dispatch
- * in csrc/host/step_vectorspace.inc) -- host record written where the launches are made, test hook, no device is touched:
+ * in csrc/host/step_vectorspace.inc; the sorted chain's in csrc/host/lazy_segsum.inc: EntityChain) -- host record written where the launches are made, test hook, no device is touched:
  * out[0] one of SERT_EGRAD_PATH_*.  BUCKET: out[1] rows per sub-group, out[2] sub-groups, out[3] sub-groups per row group,
  * out[4] row groups, out[5] ranges of 16 entities, out[6] 1 when egrad_group_sum was launched and 0 when the sum of the group
  * tables was left to the optimiser.  SORTED: out[7] key bits of the counting sort, out[8] its digit passes, out[9] / out[10] VEC
@@ -92,7 +92,7 @@ enum {
 int sert_debug_nce_form(sert_model* m, int32_t* out, int n);
 
 /* What the LAST step of a fold-in handle launched (include/sert_hip_foldin.h; kernels in csrc/kernels_foldin.h, dispatch in
- * csrc/host/api_foldin.inc: foldin_loss, foldin_grad) -- host record written where the launches are made, test hook, no device is
+ * csrc/host/api_foldin.inc: foldin_loss, foldin_grad; lazy_segsum.inc: EntityChain, shared with the model) -- host record written where the launches are made, test hook, no device is
  * touched: out[0] one of SERT_FOLDIN_LOSS_*, out[1] its template parameter (VECTOR: float4 chunks per lane; SCALAR: columns per
  * lane), out[2] 1 for the training instance and 0 for the evaluating one, out[3] key bits of the counting sort (the smallest b
  * with 2^b > num_new: the sentinel key is num_new itself), out[4] its digit passes, out[5] / out[6] VEC and NCH of

@@ -283,153 +283,57 @@ static int foldin_negatives(sert_foldin* f, const int64_t* negatives, uint64_t s
     return 0;
 }
 
-// foldin_loss of a handle made by sert_foldin_create_refresh: the same dispatch over foldin_nce_map / foldin_nce_map_scalar
-static int foldin_loss_map(sert_foldin* f, int64_t batch, bool train, const float** parts, int* n_parts) {
-    const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de;
-    const size_t row0 = (size_t)batch * B;
-    const float* T = f->T + row0 * de;
-    const int32_t* y = f->y + row0;
-    const float* w = train ? f->w + row0 : (const float*)nullptr;
-    const float inv_batch = 1.0f / (float)B;
-    hipStream_t s = f->stream;
-#define SERT_FI_ARGS T, (const float*)f->re, (const float*)f->E, (const int32_t*)f->slot_of, y, (const int32_t*)f->neg, w, f->coef, f->key, f->rowloss, B, z, de, f->N, inv_batch
-    if (de % 4 == 0) {
-        const dim3 grid(cdiv(B, 16)), block(256);
-#define SERT_FI_CASE(K)                                                                                   \
-    case K:                                                                                               \
-        if (train) launch((foldin_nce_map<K, true>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);       \
-        else launch((foldin_nce_map<K, false>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);            \
-        break;
-        switch (cdiv(de / 4, 16)) {
-            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
-            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
-            default: SERT_FAIL("entity_dim > 512 is not supported");
-        }
-#undef SERT_FI_CASE
-        *parts = f->red_loss; *n_parts = cdiv(B, 16);
-        f->plan[0] = SERT_FOLDIN_LOSS_VECTOR; f->plan[1] = cdiv(de / 4, 16);
-    } else {
-        const dim3 grid(cdiv(B, 4)), block(256);
-#define SERT_FI_CASE(K)                                                                                   \
-    case K:                                                                                               \
-        if (train) launch((foldin_nce_map_scalar<K, true>), grid, block, 0, s, SERT_FI_ARGS);             \
-        else launch((foldin_nce_map_scalar<K, false>), grid, block, 0, s, SERT_FI_ARGS);                  \
-        break;
-        switch (cdiv(de, 64)) {
-            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
-            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
-            default: SERT_FAIL("entity_dim > 512 is not supported");
-        }
-#undef SERT_FI_CASE
-        *parts = f->rowloss; *n_parts = B;     // (no workgroup partials on this path: the rows' losses themselves)
-        f->plan[0] = SERT_FOLDIN_LOSS_SCALAR; f->plan[1] = cdiv(de, 64);
-    }
-#undef SERT_FI_ARGS
-    f->plan[2] = train ? 1 : 0;
-    return 0;
-}
-
-// the loss kernel on batch `batch` (train: weighted, coef and keys written); *parts / *n_parts: the loss partials it left
+// the loss kernel on batch `batch` (train: weighted, coef and keys written); *parts / *n_parts: the loss partials it left.
+// A handle made by sert_foldin_create_refresh (f->map) launches the instance of foldin_nce_map / foldin_nce_map_scalar.
 static int foldin_loss(sert_foldin* f, int64_t batch, bool train, const float** parts, int* n_parts) {
-    if (f->map) return foldin_loss_map(f, batch, train, parts, n_parts);
     const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de;
     const size_t row0 = (size_t)batch * B;
     const float* T = f->T + row0 * de;
     const int32_t* y = f->y + row0;
     const float* w = train ? f->w + row0 : (const float*)nullptr;
     const float inv_batch = 1.0f / (float)B;
-    hipStream_t s = f->stream;
-#define SERT_FI_ARGS T, (const float*)f->re, (const float*)f->E, y, (const int32_t*)f->neg, w, f->coef, f->key, f->rowloss, B, z, de, f->Ve, f->N, inv_batch
-    if (de % 4 == 0) {
-        const dim3 grid(cdiv(B, 16)), block(256);
-#define SERT_FI_CASE(K)                                                                                   \
-    case K:                                                                                               \
-        if (train) launch((foldin_nce<K, true>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);           \
-        else launch((foldin_nce<K, false>), grid, block, 0, s, SERT_FI_ARGS, f->red_loss);                \
-        break;
-        switch (cdiv(de / 4, 16)) {
-            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
-            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
-            default: SERT_FAIL("entity_dim > 512 is not supported");
-        }
-#undef SERT_FI_CASE
-        *parts = f->red_loss; *n_parts = cdiv(B, 16);
-        f->plan[0] = SERT_FOLDIN_LOSS_VECTOR; f->plan[1] = cdiv(de / 4, 16);
-    } else {
-        const dim3 grid(cdiv(B, 4)), block(256);
-#define SERT_FI_CASE(K)                                                                                   \
-    case K:                                                                                               \
-        if (train) launch((foldin_nce_scalar<K, true>), grid, block, 0, s, SERT_FI_ARGS);                 \
-        else launch((foldin_nce_scalar<K, false>), grid, block, 0, s, SERT_FI_ARGS);                      \
-        break;
-        switch (cdiv(de, 64)) {
-            SERT_FI_CASE(1) SERT_FI_CASE(2) SERT_FI_CASE(3) SERT_FI_CASE(4)
-            SERT_FI_CASE(5) SERT_FI_CASE(6) SERT_FI_CASE(7) SERT_FI_CASE(8)
-            default: SERT_FAIL("entity_dim > 512 is not supported");
-        }
-#undef SERT_FI_CASE
-        *parts = f->rowloss; *n_parts = B;     // (no workgroup partials on this path: the rows' losses themselves)
-        f->plan[0] = SERT_FOLDIN_LOSS_SCALAR; f->plan[1] = cdiv(de, 64);
-    }
-#undef SERT_FI_ARGS
-    f->plan[2] = train ? 1 : 0;
+    const bool vector = de % 4 == 0;      // 16 lanes per instance and float4 columns; else one wave per instance
+    const dim3 grid(cdiv(B, vector ? 16 : 4)), block(256);
+    // one instance of the two-part table's kernel or of the slot map's; tail: the arguments behind inv_batch
+    auto go = [&](auto two_part, auto map, auto... tail) {
+        if (f->map)
+            launch(map, grid, block, 0, f->stream, T, f->re, f->E, f->slot_of, y, f->neg, w, f->coef, f->key, f->rowloss, B, z, de,
+                   f->N, inv_batch, tail...);
+        else
+            launch(two_part, grid, block, 0, f->stream, T, f->re, f->E, y, f->neg, w, f->coef, f->key, f->rowloss, B, z, de, f->Ve,
+                   f->N, inv_batch, tail...);
+    };
+    const int k = vector ? cdiv(de / 4, 16) : cdiv(de, 64);
+    const bool launched = vector ? dispatch_int<1, 8>(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if (train) go(foldin_nce<K, true>, foldin_nce_map<K, true>, f->red_loss);
+        else go(foldin_nce<K, false>, foldin_nce_map<K, false>, f->red_loss);
+    }) : dispatch_int<1, 8>(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if (train) go(foldin_nce_scalar<K, true>, foldin_nce_map_scalar<K, true>);
+        else go(foldin_nce_scalar<K, false>, foldin_nce_map_scalar<K, false>);
+    });
+    if (!launched) SERT_FAIL("entity_dim > 512 is not supported");
+    // (the scalar layout leaves no workgroup partials: the rows' losses themselves)
+    *parts = vector ? f->red_loss : f->rowloss;
+    *n_parts = vector ? cdiv(B, 16) : B;
+    f->plan[0] = vector ? SERT_FOLDIN_LOSS_VECTOR : SERT_FOLDIN_LOSS_SCALAR; f->plan[1] = k; f->plan[2] = train ? 1 : 0;
     return 0;
 }
 
-// dE (data term) into f->G: stable sort of the (key, pair) entries, chunked reduce that stops at the sentinel, carry fix-up
+// dE (data term) into f->G: stable sort of the (key, pair) entries, chunked reduce that stops at the sentinel N, carry fix-up
+// over the N trainable rows -- the model's chain (lazy_segsum.inc: EntityChain) over this handle's buffers
 static int foldin_grad(sert_foldin* f, int64_t batch) {
     const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de, N = f->N;
     const int total = B * (z + 1);
-    hipStream_t s = f->stream;
-    const float* T = f->T + (size_t)batch * B * de;
-    const int bits = f->sort_bits;
-    const int passes = cdiv(bits, kSortMaxBits);
-    const int width = cdiv(bits, passes);
     const int nbound = (int)round_up((size_t)N, 4);
-    int32_t* run_start = f->run_bounds;
-    int32_t* run_end = f->run_bounds + nbound;
-    const int32_t* kin = f->key;
-    const int32_t* vin = nullptr;      // value of element i is i
-    for (int p = 0; p < passes; ++p) {
-        const int shift = p * width;
-        const int nb = std::min(width, bits - shift);
-        const bool to_final = ((passes - 1 - p) % 2) == 0;
-        int32_t* kout = to_final ? f->key_sorted : f->k_tmp;
-        int32_t* vout = to_final ? f->pair_sorted : f->v_tmp;
-        // (first digit: also clears the run bounds, which the reduce writes only for the rows it meets)
-        csort_pass(s, kin, vin, kout, vout, total, shift, nb, f->sort_hist, f->sort_bin_total,
-                   p == 0 ? run_start : (int32_t*)nullptr, p == 0 ? 2 * nbound : 0);
-        kin = kout;
-        vin = vout;
-    }
-    f->plan[3] = bits; f->plan[4] = passes; f->plan[9] = (int32_t)cdiv((int64_t)total, kSortTile);
-    const int chunks = cdiv(total, kEChunk);
-    const dim3 cgrid(cdiv(chunks, 16)), blk(256);
-#define SERT_FI_ARGS (const int32_t*)f->key_sorted, (const int32_t*)f->pair_sorted, (const float*)f->coef, T, total, z + 1, de, N, \
-                 f->G, f->ehead, f->etail, run_start, run_end
-    if (de % 4 == 0) {
-        const int nch = cdiv(de / 4, 16);
-        if (nch <= 1)      { launch((foldin_chunk_reduce<4, 1>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 1; }
-        else if (nch <= 2) { launch((foldin_chunk_reduce<4, 2>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 2; }
-        else if (nch <= 5) { launch((foldin_chunk_reduce<4, 5>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 5; }
-        else               { launch((foldin_chunk_reduce<4, 8>), cgrid, blk, 0, s, SERT_FI_ARGS); f->plan[6] = 8; }
-        f->plan[5] = 4; f->plan[7] = cdiv(de / 4, 16 * f->plan[6]);
-    } else {
-        launch((foldin_chunk_reduce<1, 4>), cgrid, blk, 0, s, SERT_FI_ARGS);
-        f->plan[5] = 1; f->plan[6] = 4; f->plan[7] = cdiv(de, 16 * 4);
-    }
-#undef SERT_FI_ARGS
-    // the fix-up over the N new rows only (kernels_egrad.h, as it is): rows no pair hit get a zero gradient row, runs that
-    // cross chunks their carries in chunk order.  Few rows: one workgroup per row (long runs).
-    const bool few = N < 256;
-    f->plan[8] = few ? SERT_EGRAD_FIXUP_WORKGROUP : SERT_EGRAD_FIXUP_WAVE;
-    if (de % 4 == 0) {
-        if (few) launch((egrad_fixup_wg<4>), dim3(N), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
-        else launch((egrad_fixup<4>), dim3(cdiv(N, 4)), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
-    } else {
-        if (few) launch((egrad_fixup_wg<1>), dim3(N), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
-        else launch((egrad_fixup<1>), dim3(cdiv(N, 4)), blk, 0, s, (const int32_t*)run_start, (const int32_t*)run_end, N, de, (const float*)f->ehead, (const float*)f->etail, f->G);
-    }
+    const EntityChain chain = {f->key_sorted, f->pair_sorted, f->k_tmp, f->v_tmp, f->sort_hist, f->sort_bin_total, f->run_bounds,
+                               f->run_bounds + nbound, 2 * nbound, f->ehead, f->etail, f->sort_bits, N, de, z + 1, total};
+    const ChainSorted sorted = entity_key_sort(chain, f->key, f->stream);
+    f->plan[3] = sorted.bits; f->plan[4] = sorted.passes; f->plan[9] = (int32_t)cdiv((int64_t)total, kSortTile);
+    const ChainReduced reduced = entity_chunk_reduce(chain, f->coef, f->T + (size_t)batch * B * de, f->G, f->stream, N);
+    f->plan[5] = reduced.vec; f->plan[6] = reduced.nch; f->plan[7] = cdiv(de / reduced.vec, 16 * reduced.nch);
+    f->plan[8] = entity_fixup(chain, f->G, f->stream);
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// Part of sert_hip.hip (one translation unit; included there, inside its namespace / extern "C" block): the lazy word-table update's host state, the tensor table, the word-gradient tree, the loglinear per-word sums, the entity key sort, long-K GEMMs.
+// Part of sert_hip.hip (one translation unit; included there, inside its namespace / extern "C" block): the lazy word-table update's host state, the tensor table, the word-gradient tree, the loglinear per-word sums, the sorted entity-gradient chain, long-K GEMMs.
 
 // ---- lazy dense update of the word table (kernels_opt.h: dense_update_lazy) ----------------------------------------
 static void optimizer_args(const sert_model* m, int64_t t, AdamArgs* aa, AdadeltaArgs* da);
@@ -343,29 +343,91 @@ static int dzu_from_dj(sert_model* m, const DataSplit& ds, int64_t batch_index) 
     return 0;
 }
 
-// Stable sort of the (entity id, pair index) keys of this step: cand -> cand_sorted,
-// iota -> pair_sorted (kernels_sort.h), LSD over ceil(bits/11) digits.
-static int entity_key_sort(sert_model* m, int total, hipStream_t st, const int32_t* keys = nullptr) {
-    const int bits = m->sort_bits;
+// ---- the sorted entity-gradient chain: stable key sort -> chunked reduce -> carry fix-up (kernels_sort.h, kernels_egrad.h) ----
+// One chain for the vectorspace step (vs_entity_grad, vs_early_sort: V_e rows) and the fold-in step (foldin_grad,
+// api_foldin.inc: N trainable rows behind a sentinel run).  EntityChain is a VIEW of the owner's buffers: pointers and sizes,
+// nothing is allocated or freed through it.  Each function returns what it launched; the owner records that in its own plan.
+struct EntityChain {
+    int32_t *keys_sorted, *pairs_sorted;      // (total) the sort's output: keys, and the pair index of each
+    int32_t *k_tmp, *v_tmp;                   // (total) ping-pong, only if sort_bits > kSortMaxBits
+    int32_t *sort_hist, *sort_bin_total;      // counting-sort scratch
+    int32_t *run_start, *run_end;             // per-row bounds of the sorted runs; run_end follows run_start in one array ...
+    int nbounds;                              // ... of nbounds ints, cleared by the sort's first pass
+    float *ehead, *etail;                     // (chunks, d_e) carries
+    int sort_bits, rows, de, zp1, total;      // rows of the gradient table (V_e / N); zp1 = z + 1; total = B (z + 1) keys
+};
+struct ChainSorted { int bits, passes; };
+struct ChainReduced { int vec, nch; };
+
+// Stable sort of the (key, pair index) entries: keys -> keys_sorted, iota -> pairs_sorted, LSD over ceil(bits/11) digits.
+static ChainSorted entity_key_sort(const EntityChain& c, const int32_t* keys, hipStream_t st) {
+    const int bits = c.sort_bits;
     const int passes = cdiv(bits, kSortMaxBits);
     const int width = cdiv(bits, passes);
-    const int32_t* kin = keys ? keys : m->cand;
+    const int32_t* kin = keys;
     const int32_t* vin = nullptr;  // value of element i is i
-    m->eg_plan[7] = bits; m->eg_plan[8] = passes;
     for (int p = 0; p < passes; ++p) {
         const int shift = p * width;
         const int nb = std::min(width, bits - shift);
         const bool to_final = ((passes - 1 - p) % 2) == 0;
-        int32_t* kout = to_final ? m->cand_sorted : m->sort_k_tmp;
-        int32_t* vout = to_final ? m->pair_sorted : m->sort_v_tmp;
-        // (first digit: also clears run_start / run_end, which the chunked reduce only writes for entities it meets --
+        int32_t* kout = to_final ? c.keys_sorted : c.k_tmp;
+        int32_t* vout = to_final ? c.pairs_sorted : c.v_tmp;
+        // (first digit: also clears run_start / run_end, which the chunked reduce only writes for the rows it meets --
         //  a step whose negatives were drawn ahead has no prologue launch to clear them)
-        csort_pass(st, kin, vin, kout, vout, total, shift, nb, m->sort_hist, m->sort_bin_total,
-                   p == 0 ? m->run_start : (int32_t*)nullptr, p == 0 ? (int)(2 * round_up(m->cfg.num_entities, 4)) : 0);
+        csort_pass(st, kin, vin, kout, vout, c.total, shift, nb, c.sort_hist, c.sort_bin_total,
+                   p == 0 ? c.run_start : (int32_t*)nullptr, p == 0 ? c.nbounds : 0);
         kin = kout;
         vin = vout;
     }
-    return 0;
+    return {bits, passes};
+}
+
+// The chunked reduce of the sorted pairs into G (rows, d_e) and the carries.  sentinel >= 0: the last run of the order, keys
+// == sentinel, is pairs that are not reduced (foldin_chunk_reduce); the model has none.
+static ChainReduced entity_chunk_reduce(const EntityChain& c, const float* coef, const float* T, float* G, hipStream_t st,
+                                        int sentinel = -1) {
+    const dim3 grid(cdiv(cdiv(c.total, kEChunk), 16)), blk(256);
+    auto go = [&](auto vec, auto nch) {
+        constexpr int VEC = decltype(vec)::value, NCH = decltype(nch)::value;
+        if (sentinel < 0)
+            launch((egrad_chunk_reduce<VEC, NCH>), grid, blk, 0, st, c.keys_sorted, c.pairs_sorted, coef, T, c.total, c.zp1, c.de,
+                   G, c.ehead, c.etail, c.run_start, c.run_end);
+        else
+            launch((foldin_chunk_reduce<VEC, NCH>), grid, blk, 0, st, c.keys_sorted, c.pairs_sorted, coef, T, c.total, c.zp1, c.de,
+                   sentinel, G, c.ehead, c.etail, c.run_start, c.run_end);
+        return ChainReduced{VEC, NCH};
+    };
+    using std::integral_constant;
+    if (c.de % 4 != 0) return go(integral_constant<int, 1>(), integral_constant<int, 4>());
+    const int nch = cdiv(c.de / 4, 16);
+    const integral_constant<int, 4> v4;
+    return nch <= 1 ? go(v4, integral_constant<int, 1>()) : nch <= 2 ? go(v4, integral_constant<int, 2>())
+         : nch <= 5 ? go(v4, integral_constant<int, 5>()) : go(v4, integral_constant<int, 8>());
+}
+
+// The fix-up over the table's rows: rows no pair hit get a zero gradient row, runs that cross chunks their carries in chunk
+// order.  Few rows: one workgroup per row (long runs).  -> SERT_EGRAD_FIXUP_WORKGROUP / SERT_EGRAD_FIXUP_WAVE
+static int entity_fixup(const EntityChain& c, float* G, hipStream_t st) {
+    const bool few = c.rows < 256 && c.de <= 512;
+    auto go = [&](auto vec) {
+        constexpr int VEC = decltype(vec)::value;
+        if (few)
+            launch((egrad_fixup_wg<VEC>), dim3(c.rows), dim3(256), 0, st, c.run_start, c.run_end, c.rows, c.de, c.ehead, c.etail, G);
+        else
+            launch((egrad_fixup<VEC>), dim3(cdiv(c.rows, 4)), dim3(256), 0, st, c.run_start, c.run_end, c.rows, c.de, c.ehead,
+                   c.etail, G);
+    };
+    if (c.de % 4 == 0) go(std::integral_constant<int, 4>());
+    else go(std::integral_constant<int, 1>());
+    return few ? SERT_EGRAD_FIXUP_WORKGROUP : SERT_EGRAD_FIXUP_WAVE;
+}
+
+// the model's chain (api_model.inc owns the buffers)
+static EntityChain vs_entity_chain(const sert_model* m) {
+    const auto& c = m->cfg;
+    return {m->cand_sorted, m->pair_sorted, m->sort_k_tmp, m->sort_v_tmp, m->sort_hist, m->sort_bin_total, m->run_start, m->run_end,
+            (int)(2 * round_up(c.num_entities, 4)), m->ehead, m->etail, m->sort_bits, c.num_entities, c.entity_dim,
+            c.num_negatives + 1, c.batch_size * (c.num_negatives + 1)};
 }
 
 // C (M,N, contiguous) = op(A).op(B) for a contraction over a LONG K (the entity

@@ -186,13 +186,6 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         if (de % 4 == 0) {
             const int nch = cdiv(de / 4, 16);
             dim3 grid(cdiv(B, 16));
-#define SERT_NCE_CASE(N)                                                                     \
-    case N:                                                                                  \
-        launch((vs_nce<N, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y,                \
-               m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,                            \
-               c.num_negatives, de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);       \
-        m->nce_form[0] = SERT_NCE_FORM_PER_CANDIDATE; m->nce_form[1] = N;                    \
-        break;
 #define SERT_NCE_REGS(N, C)                                                                  \
     /* a training step at d_e == 64 N, every lane full: the instance without chunk masks */  \
     if (TRAIN && de == 64 * N)                                                               \
@@ -227,14 +220,14 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
                     case 13: SERT_NCE_REGS(4, 11); break;
                     default: SERT_NCE_REGS(4, 12); break;
                 }
-            } else
-            switch (nch) {
-                SERT_NCE_CASE(1) SERT_NCE_CASE(2) SERT_NCE_CASE(3) SERT_NCE_CASE(4)
-                SERT_NCE_CASE(5) SERT_NCE_CASE(6) SERT_NCE_CASE(7) SERT_NCE_CASE(8)
-                default: SERT_FAIL("entity_dim > 512 is not supported");
-            }
+            } else if (!dispatch_int<1, 8>(nch, [&](auto k) {
+                           constexpr int K = decltype(k)::value;
+                           launch((vs_nce<K, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y, m->neg, w, m->DA, m->coef, m->cand,
+                                  m->rowloss, B, c.num_negatives, de, inv_batch, TRAIN ? m->red_loss : (float*)nullptr);
+                           m->nce_form[0] = SERT_NCE_FORM_PER_CANDIDATE; m->nce_form[1] = K;
+                       }))
+                SERT_FAIL("entity_dim > 512 is not supported");
 #undef SERT_NCE_REGS
-#undef SERT_NCE_CASE
             // (training: the kernel left one loss partial per workgroup in red_loss)
             m->nce_loss_partials = TRAIN ? cdiv(B, 16) : 0;
             m->nce_form[4] = (int32_t)grid.x;
@@ -242,19 +235,13 @@ static int vs_loss(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             m->nce_loss_partials = 0;
             const int npl = cdiv(de, 64);
             dim3 grid(cdiv(B, 4));
-#define SERT_NCE_CASE(N)                                                                     \
-    case N:                                                                                  \
-        launch((vs_nce_scalar<N, TRAIN>), grid, block, 0, m->stream, m->T,                  \
-               m->re, y, m->neg, w, m->DA, m->coef, m->cand, m->rowloss, B,                 \
-               c.num_negatives, de, inv_batch);                                              \
-        m->nce_form[0] = SERT_NCE_FORM_SCALAR; m->nce_form[1] = N;                           \
-        break;
-            switch (npl) {
-                SERT_NCE_CASE(1) SERT_NCE_CASE(2) SERT_NCE_CASE(3) SERT_NCE_CASE(4)
-                SERT_NCE_CASE(5) SERT_NCE_CASE(6) SERT_NCE_CASE(7) SERT_NCE_CASE(8)
-                default: SERT_FAIL("entity_dim > 512 is not supported");
-            }
-#undef SERT_NCE_CASE
+            if (!dispatch_int<1, 8>(npl, [&](auto k) {
+                    constexpr int K = decltype(k)::value;
+                    launch((vs_nce_scalar<K, TRAIN>), grid, block, 0, m->stream, m->T, m->re, y, m->neg, w, m->DA, m->coef, m->cand,
+                           m->rowloss, B, c.num_negatives, de, inv_batch);
+                    m->nce_form[0] = SERT_NCE_FORM_SCALAR; m->nce_form[1] = K;
+                }))
+                SERT_FAIL("entity_dim > 512 is not supported");
             m->nce_form[4] = (int32_t)grid.x;
         }
         m->nce_form[3] = TRAIN ? 1 : 0;
@@ -310,7 +297,9 @@ static int vs_early_sort(sert_model* m, const DataSplit& ds, size_t row0) {
     ScopedTimer t(m, TG_SORT, m->stream2);
     launch(vs_build_cand, dim3(grid_for(total)), dim3(256), 0, m->stream2, (const int32_t*)ds.y + row0, (const int32_t*)m->neg,
            c.batch_size, c.num_negatives, m->cand_early);
-    return entity_key_sort(m, total, m->stream2, m->cand_early);
+    const ChainSorted sorted = entity_key_sort(vs_entity_chain(m), m->cand_early, m->stream2);
+    m->eg_plan[7] = sorted.bits; m->eg_plan[8] = sorted.passes;
+    return 0;
 }
 
 // dR_e.  This chain only depends on the NCE kernel and is independent of the GEMMs / word-table reduction, so it runs on the
@@ -363,53 +352,23 @@ static int vs_entity_grad(sert_model* m, const VsStepPlan& P) {
                (const float*)m->T, total, c.num_negatives + 1, de, V, m->g_re);
 #endif
     } else {
-    // dR_e: stable sort of the (entity, pair) keys, chunked reduce, carry fix-up
+    // dR_e: stable sort of the (entity, pair) keys, chunked reduce, carry fix-up (lazy_segsum.inc: EntityChain)
+    const EntityChain chain = vs_entity_chain(m);
+    m->eg_plan[0] = SERT_EGRAD_PATH_SORTED;
     if (!P.sort_early) {       // (else: the keys were sorted beside the forward, vs_early_sort)
         ScopedTimer t(m, TG_SORT, st);
-        SERT_TRY(entity_key_sort(m, total, st));
+        const ChainSorted sorted = entity_key_sort(chain, m->cand, st);
+        m->eg_plan[7] = sorted.bits; m->eg_plan[8] = sorted.passes;
     }
-    const int chunks = cdiv(total, kEChunk);
-    m->eg_plan[0] = SERT_EGRAD_PATH_SORTED;
-    dim3 cgrid(cdiv(chunks, 16)), fgrid(cdiv(V, 4)), blk(256);
-#define SERT_EG_ARGS m->cand_sorted, m->pair_sorted, m->coef, m->T, total, c.num_negatives + 1, de, \
-                 m->g_re, m->ehead, m->etail, m->run_start, m->run_end
     {
         ScopedTimer t(m, TG_EGRAD, st);
-        if (de % 4 == 0) {
-            const int nch = cdiv(de / 4, 16);
-            if (nch <= 1)      { launch((egrad_chunk_reduce<4, 1>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 1; }
-            else if (nch <= 2) { launch((egrad_chunk_reduce<4, 2>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 2; }
-            else if (nch <= 5) { launch((egrad_chunk_reduce<4, 5>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 5; }
-            else               { launch((egrad_chunk_reduce<4, 8>), cgrid, blk, 0, st, SERT_EG_ARGS); m->eg_plan[9] = 4; m->eg_plan[10] = 8; }
-        } else {
-            launch((egrad_chunk_reduce<1, 4>), cgrid, blk, 0, st, SERT_EG_ARGS);
-            m->eg_plan[9] = 1; m->eg_plan[10] = 4;
-        }
+        const ChainReduced reduced = entity_chunk_reduce(chain, m->coef, m->T, m->g_re, st);
+        m->eg_plan[9] = reduced.vec; m->eg_plan[10] = reduced.nch;
     }
     {
         ScopedTimer t(m, TG_EFIX, st);
-        const bool few = V < 256 && de <= 512;   // few entities: one workgroup per entity (long runs)
-        if (de % 4 == 0) {
-            if (few) {
-                launch((egrad_fixup_wg<4>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
-                       m->ehead, m->etail, m->g_re);
-                m->eg_plan[11] = SERT_EGRAD_FIXUP_WORKGROUP;
-            } else {
-                launch((egrad_fixup<4>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
-                       m->ehead, m->etail, m->g_re);
-                m->eg_plan[11] = SERT_EGRAD_FIXUP_WAVE;
-            }
-        } else if (few) {
-            launch((egrad_fixup_wg<1>), dim3(V), blk, 0, st, m->run_start, m->run_end, V, de,
-                   m->ehead, m->etail, m->g_re);
-            m->eg_plan[11] = SERT_EGRAD_FIXUP_WORKGROUP;
-        } else {
-            launch((egrad_fixup<1>), fgrid, blk, 0, st, m->run_start, m->run_end, V, de,
-                   m->ehead, m->etail, m->g_re);
-            m->eg_plan[11] = SERT_EGRAD_FIXUP_WAVE;
-        }
+        m->eg_plan[11] = entity_fixup(chain, m->g_re, st);
     }
-#undef SERT_EG_ARGS
     }   // sorted path
     return 0;
 }

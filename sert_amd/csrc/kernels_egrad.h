@@ -20,10 +20,12 @@ constexpr int kEChunk = 16;   // pairs per chunk = lanes per chunk group
 // VEC-wide column pieces l, l+16, ... of the accumulated rows.  NCH pieces per
 // lane per pass; when the row is wider than 16*NCH pieces the chunk is walked
 // again for the next column block (only the scalar fallback needs that).
-template <int VEC, int NCH>
-__global__ __launch_bounds__(256) void egrad_chunk_reduce(
+// SENTINEL: the keys' LAST run is `sentinel`, pairs that are not reduced
+// (foldin_chunk_reduce, kernels_foldin.h); else `sentinel` is not read.
+template <int VEC, int NCH, bool SENTINEL>
+__device__ __forceinline__ void chunk_reduce_rows(
     const int32_t* __restrict__ keys, const int32_t* __restrict__ pairs,
-    const float* __restrict__ coef, const float* __restrict__ T, int total, int zp1, int de,
+    const float* __restrict__ coef, const float* __restrict__ T, int total, int zp1, int de, int sentinel,
     float* __restrict__ GRe, float* __restrict__ head, float* __restrict__ tail,
     int32_t* __restrict__ run_start, int32_t* __restrict__ run_end) {
     const int l = threadIdx.x & 15;
@@ -31,20 +33,37 @@ __global__ __launch_bounds__(256) void egrad_chunk_reduce(
     const int chunk = blockIdx.x * 16 + (threadIdx.x >> 4);
     const int cb = chunk * kEChunk;
     if (cb >= total) return;
+    int first_key = 0;
+    if constexpr (SENTINEL) {
+        first_key = keys[cb];                    // (the same address for the group's sixteen lanes)
+        if (first_key >= sentinel) return;       // the chunk lies wholly inside the sentinel run
+    }
     const int ce = min(total, cb + kEChunk);
-    const int cnt = ce - cb;
+    int cnt = ce - cb;
     const int pieces = de / VEC;
-    int my_key = -1, my_row = 0;
+    int my_key = SENTINEL ? sentinel : -1, my_row = 0;
     float my_coef = 0.f;
-    if (l < cnt) {
+    if (l < ce - cb) {
         my_key = keys[cb + l];
-        const int pr = pairs[cb + l];
-        my_coef = coef[pr];
-        my_row = pr / zp1;
+        if (!SENTINEL || my_key < sentinel) {
+            const int pr = pairs[cb + l];
+            my_coef = coef[pr];
+            my_row = pr / zp1;
+        }
     }
     const int prev_key = (cb > 0) ? keys[cb - 1] : -1;
-    const int next_key = (ce < total) ? keys[ce] : -1;
-    const int first_key = __shfl(my_key, gbase, kWave);
+    int next_key;
+    if constexpr (SENTINEL) {
+        // live pairs of the chunk: sorted, so they are its leading lanes (every lane of the group is active here: the
+        // two returns above are uniform over a group)
+        const unsigned long long live = __ballot(my_key < sentinel);
+        cnt = __popc((unsigned)(live >> gbase) & 0xffffu);
+        // the key behind the chunk's live pairs: a sentinel inside the chunk, or behind it, continues no live run
+        next_key = (cnt < ce - cb) ? -1 : ((ce < total) ? keys[ce] : -1);
+    } else {
+        next_key = (ce < total) ? keys[ce] : -1;
+        first_key = __shfl(my_key, gbase, kWave);
+    }
 
     for (int p0 = 0; p0 < pieces; p0 += 16 * NCH) {
         float acc[NCH][VEC];
@@ -73,7 +92,7 @@ __global__ __launch_bounds__(256) void egrad_chunk_reduce(
                 if (c < pieces) {
                     if (VEC == 4)
                         *reinterpret_cast<float4*>(dst + 4 * c) =
-                            make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]);
+                            make_float4(acc[q][0], acc[q][1 % VEC], acc[q][2 % VEC], acc[q][3 % VEC]);
                     else
                         dst[c] = acc[q][0];
                 }
@@ -113,6 +132,15 @@ __global__ __launch_bounds__(256) void egrad_chunk_reduce(
         }
         flush(cur, at_begin && prev_key == cur, next_key == cur, jb, cnt);
     }
+}
+
+template <int VEC, int NCH>
+__global__ __launch_bounds__(256) void egrad_chunk_reduce(
+    const int32_t* __restrict__ keys, const int32_t* __restrict__ pairs,
+    const float* __restrict__ coef, const float* __restrict__ T, int total, int zp1, int de,
+    float* __restrict__ GRe, float* __restrict__ head, float* __restrict__ tail,
+    int32_t* __restrict__ run_start, int32_t* __restrict__ run_end) {
+    chunk_reduce_rows<VEC, NCH, false>(keys, pairs, coef, T, total, zp1, de, 0, GRe, head, tail, run_start, run_end);
 }
 
 // One wave per entity: add the carries of the chunks its run [s,t) spans.  The

@@ -10,9 +10,12 @@
 //                         below the projection learns); TRAIN leaves coef[i, j] and a KEY per pair: cand - V_e for a pair
 //                         that hits a new row, the sentinel N for one that hits a frozen row
 //   csort_pass            stable sort of the B (1 + z) (key, pair) entries (kernels_sort.h, as it is)
-//   foldin_chunk_reduce   egrad_chunk_reduce (kernels_egrad.h) that stops at the sentinel: the sentinel run -- most of the
-//                         pairs -- is the END of the sorted order, so a chunk that starts inside it leaves after one load
+//   foldin_chunk_reduce   the body of egrad_chunk_reduce (kernels_egrad.h: chunk_reduce_rows) in the form that stops at the
+//                         sentinel: the sentinel run -- most of the pairs -- is the END of the sorted order, so a chunk that
+//                         starts inside it leaves after one load
 //   egrad_fixup(_wg)      the carries of the runs that cross chunks, over the N new rows only (kernels_egrad.h, as it is)
+// The three launches behind the loss kernel are the model's host chain (host/lazy_segsum.inc: EntityChain) over this
+// handle's buffers.
 //   adam_l2               Adam + L2 + sum of squares over E (kernels_opt.h, as it is), finalize_loss
 // Order-fixed throughout, no floating-point atomic: a fold-in is bit-reproducible.
 // A REFRESH handle (sert_foldin_create_refresh: trained rows that gained documents learn too) runs the same step with
@@ -154,110 +157,20 @@ __global__ __launch_bounds__(256) void foldin_nce_map_scalar(const float* __rest
                                      i, z, de, N, inv_batch);
 }
 
-// egrad_chunk_reduce over keys sorted ascending whose LAST run is the sentinel (key == sentinel: a pair on a frozen row).
-// 16 lanes per chunk of 16 consecutive sorted pairs.  A chunk whose first key is the sentinel lies wholly inside that run and
-// leaves after that one load; the chunk the run begins in reduces its leading live pairs only and ends its last live run
-// there (no carry into the sentinel).  So the sentinel run is neither accumulated nor fixed up, and the work is proportional
-// to the pairs that hit new rows.  Same association as egrad_chunk_reduce for the live runs; head / tail / run_start /
-// run_end as there, for keys < sentinel (egrad_fixup over `sentinel` rows finishes).  T: this batch's projections.
+// egrad_chunk_reduce over keys sorted ascending whose LAST run is the sentinel (key == sentinel: a pair on a frozen row): the
+// same body (kernels_egrad.h: chunk_reduce_rows, SENTINEL = true).  A chunk whose first key is the sentinel lies wholly inside
+// that run and leaves after that one load; the chunk the run begins in reduces its leading live pairs only and ends its last
+// live run there (no carry into the sentinel).  So the sentinel run is neither accumulated nor fixed up, and the work is
+// proportional to the pairs that hit new rows.  The live runs have the association of egrad_chunk_reduce by construction;
+// head / tail / run_start / run_end as there, for keys < sentinel (egrad_fixup over `sentinel` rows finishes).  T: this
+// batch's projections.
 template <int VEC, int NCH>
 __global__ __launch_bounds__(256) void foldin_chunk_reduce(
     const int32_t* __restrict__ keys, const int32_t* __restrict__ pairs,
     const float* __restrict__ coef, const float* __restrict__ T, int total, int zp1, int de, int sentinel,
     float* __restrict__ G, float* __restrict__ head, float* __restrict__ tail,
     int32_t* __restrict__ run_start, int32_t* __restrict__ run_end) {
-    const int l = threadIdx.x & 15;
-    const int gbase = (threadIdx.x & 63) & ~15;  // first lane of this group inside the wave
-    const int chunk = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int cb = chunk * kEChunk;
-    if (cb >= total) return;
-    const int first_key = keys[cb];              // (the same address for the group's sixteen lanes)
-    if (first_key >= sentinel) return;
-    const int ce = min(total, cb + kEChunk);
-    const int pieces = de / VEC;
-    int my_key = sentinel, my_row = 0;
-    float my_coef = 0.f;
-    if (l < ce - cb) {
-        my_key = keys[cb + l];
-        if (my_key < sentinel) {
-            const int pr = pairs[cb + l];
-            my_coef = coef[pr];
-            my_row = pr / zp1;
-        }
-    }
-    // live pairs of the chunk: sorted, so they are its leading lanes (every lane of the group is active here: the two
-    // returns above are uniform over a group)
-    const unsigned long long live = __ballot(my_key < sentinel);
-    const int cnt = __popc((unsigned)(live >> gbase) & 0xffffu);
-    const int prev_key = (cb > 0) ? keys[cb - 1] : -1;
-    // the key behind the chunk's live pairs: a sentinel inside the chunk, or behind it, continues no live run
-    const int next_key = (cnt < ce - cb) ? -1 : ((ce < total) ? keys[ce] : -1);
-
-    for (int p0 = 0; p0 < pieces; p0 += 16 * NCH) {
-        float acc[NCH][VEC];
-#pragma unroll
-        for (int q = 0; q < NCH; ++q)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[q][v] = 0.f;
-        int cur = first_key;
-        bool at_begin = true;
-        int jb = 0;
-
-        auto flush = [&](int e, bool touches_begin, bool touches_end, int jb, int je) {
-            if (p0 == 0 && l == 0) {
-                if (!touches_begin) run_start[e] = cb + jb;
-                if (!touches_end) run_end[e] = cb + je;
-            }
-            float* dst;
-            if (!touches_begin && !touches_end) dst = G + (size_t)e * de;   // sole owner
-            else if (touches_end) dst = tail + (size_t)chunk * de;
-            else dst = head + (size_t)chunk * de;
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) {
-                const int c = p0 + l + 16 * q;
-                if (c < pieces) {
-                    if (VEC == 4)
-                        *reinterpret_cast<float4*>(dst + 4 * c) =
-                            make_float4(acc[q][0], acc[q][1 % VEC], acc[q][2 % VEC], acc[q][3 % VEC]);
-                    else
-                        dst[c] = acc[q][0];
-                }
-            }
-        };
-
-        for (int j = 0; j < cnt; ++j) {
-            const int k = __shfl(my_key, gbase + j, kWave);
-            const int row = __shfl(my_row, gbase + j, kWave);
-            const float cf = __shfl(my_coef, gbase + j, kWave);
-            if (k != cur) {
-                flush(cur, at_begin && prev_key == cur, false, jb, j);
-                jb = j;
-#pragma unroll
-                for (int q = 0; q < NCH; ++q)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[q][v] = 0.f;
-                cur = k;
-                at_begin = false;
-            }
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) {
-                const int c = p0 + l + 16 * q;
-                if (c < pieces) {
-                    float tv[VEC];
-                    if (VEC == 4) {
-                        const float4 t4 = *reinterpret_cast<const float4*>(T + (size_t)row * de + 4 * c);
-                        tv[0] = t4.x; tv[1 % VEC] = t4.y; tv[2 % VEC] = t4.z; tv[3 % VEC] = t4.w;
-                    } else {
-                        tv[0] = T[(size_t)row * de + c];
-                    }
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v)
-                        acc[q][v] += cf * clip_proj(tv[v]);
-                }
-            }
-        }
-        flush(cur, at_begin && prev_key == cur, next_key == cur, jb, cnt);
-    }
+    chunk_reduce_rows<VEC, NCH, true>(keys, pairs, coef, T, total, zp1, de, sentinel, G, head, tail, run_start, run_end);
 }
 
 }  // namespace sert

@@ -77,4 +77,15 @@ inline void launch(void (*kernel)(Formal...), dim3 grid, dim3 block, size_t lds,
     kernel<<<grid, block, lds, stream>>>(static_cast<Formal>(std::forward<Actual>(args))...);
 }
 
+// A run-time k in LO..HI as a kernel's template argument: f(std::integral_constant<int, k>()), f a generic lambda that
+// launches the instance.  false: k lies outside, f was not called.
+template <int LO, int HI, typename F>
+inline bool dispatch_int(int k, F&& f) {
+    if constexpr (LO <= HI) {
+        if (k == LO) { f(std::integral_constant<int, LO>()); return true; }
+        return dispatch_int<LO + 1, HI>(k, f);
+    }
+    return false;
+}
+
 }  // namespace sert

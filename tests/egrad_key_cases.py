@@ -2,7 +2,8 @@
 inputs (test_egrad_keys_inputs_cpu.py) and the GPU test (test_gpu_egrad_keys.py).
 
 dR_e, the entity-table gradient of the NCE loss, is formed without atomics by one of two mechanisms (csrc/kernels_egrad.h,
-csrc/kernels_sort.h; dispatch in csrc/host/step_vectorspace.inc and api_model.inc):
+csrc/kernels_sort.h; the choice of path in csrc/host/step_vectorspace.inc and api_model.inc, the sorted chain's dispatch --
+shared with the fold-in step, tests/foldin_key_cases.py -- in csrc/host/lazy_segsum.inc: EntityChain):
 
   sorted   entity_key_sort -> egrad_chunk_reduce<VEC, NCH> -> egrad_fixup<VEC> / egrad_fixup_wg<VEC>: the keys counting-sorted
            by entity (stable), reduced in chunks of CHUNK = 16 sorted pairs; a run that crosses a chunk boundary leaves a tail

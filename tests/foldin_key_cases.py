@@ -2,7 +2,8 @@
 instances were uploaded -- shared by the CPU proof of the inputs (test_foldin_keys_inputs_cpu.py) and the GPU test
 (test_gpu_foldin_keys.py).  Patterned on tests/egrad_key_cases.py.
 
-A fold-in step (csrc/kernels_foldin.h, dispatch in csrc/host/api_foldin.inc) runs the vectorspace step's kernels, changed
+A fold-in step (csrc/kernels_foldin.h; the loss dispatch in csrc/host/api_foldin.inc, the sort / reduce / fix-up dispatch the
+model's own, csrc/host/lazy_segsum.inc: EntityChain) runs the vectorspace step's kernels, changed
 where it matters: foldin_nce<K> / foldin_nce_scalar<K> -- the row body of the step's loss kernel (csrc/kernels_vs.h,
 nce_rows16 / nce_rows_wave) under another candidate policy -- score a two-part table and write a KEY per pair (the new row,
 or the sentinel N for a pair on a frozen row); csort_pass sorts the B (z + 1) keys over the smallest b bits with 2^b > N;

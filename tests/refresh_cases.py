@@ -43,7 +43,7 @@ DEVICE_NEGATIVES_CASE, LAMBDA0_CASE = 'mixed', 'sparse'
 
 
 def expected_plan(c):
-    """FoldIn.plan() after a training step of the case: the fold-in's dispatch (csrc/host/api_foldin.inc) with N := Nt."""
+    """FoldIn.plan() after a training step of the case: the fold-in's dispatch (csrc/host/api_foldin.inc, lazy_segsum.inc) with N := Nt."""
     de, Nt, total = c['de'], c['Nt'], c['B'] * (c['z'] + 1)
     bits = 1
     while (1 << bits) <= Nt:

@@ -6,7 +6,9 @@
 
 Each problem runs two training steps and both evaluations (a fold-in: two steps and one evaluation) and records the losses,
 the row losses, every parameter, gradient and optimiser moment, the fold-in rows, and the form the engine reports it
-took.  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.  The
+took.  The entity-chain group runs two steps of every case of tests/egrad_key_cases.py (the sorted cases and, through the
+sort as well as on their own path, the bucket cases), tests/foldin_key_cases.py and tests/refresh_cases.py, and records dR_e
+after each step, or the fold-in's E, m and v, with the losses and the plan of the sorted chain (eg_plan, FoldIn.plan()).  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.  The
 library is chosen by SERT_LIB, read at import, and SERT_LL_NODEDUP once per process: every (library, group) runs in a fresh
 child process started with subprocess, one at a time.  The run fails if the forms taken do not cover FAMILIES."""
 import argparse
@@ -36,7 +38,14 @@ FAMILIES = (['ll %s %s %s' % (f, lab, m) for lab in ('int', 'csr') for f, m in
               ('stream0', 'tokens')]] +
             ['nce per_candidate train', 'nce per_candidate eval', 'nce scalar train', 'nce scalar eval'] +
             ['nce regs%d %s' % (c, t) for c in (6, 11, 12) for t in ('train', 'eval')] + ['fs epl%d' % e for e in (16, 32, 0)] +
-            ['foldin %s %s %s' % (f, m, t) for f in ('vector', 'scalar') for m in ('two_part', 'map') for t in ('train', 'eval')])
+            ['foldin %s %s %s' % (f, m, t) for f in ('vector', 'scalar') for m in ('two_part', 'map') for t in ('train', 'eval')] +
+            # the sorted entity-gradient chain: every <VEC, NCH> of the chunked reduce under either fix-up, as the cases state them
+            ['egrad %s %s' % (i, f) for i, f in [('1,4', 'wave'), ('1,4', 'workgroup'), ('4,1', 'wave'), ('4,1', 'workgroup'),
+                                                 ('4,2', 'wave'), ('4,2', 'workgroup'), ('4,5', 'wave'), ('4,8', 'wave'),
+                                                 ('4,8', 'workgroup')]] +
+            ['foldin reduce %s %s' % (i, f) for i, f in [('1,4', 'wave'), ('1,4', 'workgroup'), ('4,1', 'wave'), ('4,1', 'workgroup'),
+                                                         ('4,2', 'workgroup'), ('4,5', 'wave'), ('4,5', 'workgroup'), ('4,8', 'wave'),
+                                                         ('4,8', 'workgroup')]])
 
 
 def run_engine(out, tag, eng, kind, uploads, form):
@@ -126,11 +135,82 @@ def run_foldin(out, tag, p, z, refresh):
     return forms
 
 
+def run_egrad_case(out, name, sort):
+    """Two steps of a case of tests/egrad_key_cases.py with keep_grads = 1; sort: SERT_EGRAD_SORT=1 (read at sert_create)."""
+    from sert_amd import _capi as C
+    from tests import egrad_key_cases as K
+    from tests import util as U
+    c, p = K.case_problem(name)
+    os.environ.pop('SERT_EGRAD_SORT', None)
+    if sort:
+        os.environ['SERT_EGRAD_SORT'] = '1'
+    tag = 'egrad_%s_%s' % (name, 'sorted' if sort else 'bucket')
+    eng = U.vs_engine(p, c['B'], K.N, c['z'], K.LAM, keep_grads=1)
+    eng.upload_dataset(C.SPLIT_TRAIN, p['X'], y_int=p['y'], w=p['w'])
+    forms = []
+    for s in range(K.STEPS):
+        out['%s/loss%d' % (tag, s)] = np.float32(eng.train_batch(s, p['neg'][s] if p['neg'][s].shape[1] else None))
+        out['%s/g.R_e%d' % (tag, s)] = eng.get_tensor(C.T_GRAD_RE)
+        pl = eng.egrad_plan()
+        assert pl['path'] == ('sorted' if sort else 'bucket'), (name, pl)
+        if sort:
+            forms.append('egrad %d,%d %s' % (pl['vec'], pl['nch'], pl['fixup']))
+    out[tag + '/R_e'] = eng.get_tensor(C.T_RE)
+    eng.close()
+    return forms
+
+
+def run_foldin_case(out, tag, c, init_rows, seed, refresh_ids):
+    """Two steps of a case of tests/foldin_key_cases.py or tests/refresh_cases.py on the case's explicit negatives."""
+    from sert_amd import _capi as C
+    eng = C.Engine(kind=C.KIND_VECTORSPACE, batch_size=8, global_batch_size=8, window_size=c['n'], vocab_size=c['Vw'],
+                   num_entities=c['Ve'], word_dim=c['dw'], entity_dim=c['de'], num_negatives=2, id_bytes=4, device=0, keep_grads=0,
+                   deterministic=1, lambda_=0.01, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=99)
+    for which, key in ((C.T_RW, 'Rw'), (C.T_RE, 'Re'), (C.T_W, 'W'), (C.T_B, 'b')):
+        eng.set_tensor(which, c[key])
+    f = C.FoldIn(eng, init_rows, c['B'], c['z'], c['lam'], lr=c['lr'], seed=seed, refresh_ids=refresh_ids)
+    f.upload(c['X'], c['y'], c['w_upload'])
+    forms = []
+    for s, b in enumerate(c['batches']):
+        out['%s/loss%d' % (tag, s)] = np.float32(f.train_batch(b, c['neg'][s]))
+        pl = f.plan()
+        forms.append('foldin reduce %d,%d %s' % (pl['vec'], pl['nch'], pl['fixup']))
+        for name, which in (('E', C.FOLDIN_ROWS), ('m', C.FOLDIN_M), ('v', C.FOLDIN_V)):
+            out['%s/%s%d' % (tag, name, s)] = f.get_rows(which)
+    f.close()
+    eng.close()
+    return forms
+
+
+def chain_child(out):
+    from tests import egrad_key_cases as EK
+    from tests import foldin_cases as FC
+    from tests import foldin_key_cases as FK
+    from tests import refresh_cases as RC
+    forms = []
+    for name in EK.CASES:
+        forms += run_egrad_case(out, name, True)
+        if EK.is_bucket(name):
+            forms += run_egrad_case(out, name, False)
+    os.environ.pop('SERT_EGRAD_SORT', None)
+    for name in FK.CASES:
+        c = FK.case_problem(name)
+        forms += run_foldin_case(out, 'foldin_keys_' + name, c, c['E0'], FC.SEED, None)
+    for name in RC.CASES:
+        c = RC.make_case(name)
+        forms += run_foldin_case(out, 'refresh_' + name, c, c['New0'], RC.SEED, c['refresh'])
+    return forms
+
+
 def child(group, path):
     from sert_amd import _capi as C
     from tests import ll_nonfinite_cases as NF
     from tests import util as U
     out, forms = {}, []
+    if group == 'chain':
+        out['forms'] = np.array(sorted(set(chain_child(out))))
+        np.savez_compressed(path, **out)
+        return
     for k, name in enumerate(sorted(LL if group == 'slots' else LL_PER_TOKEN)):
         n, Ve = LL[name]
         for labels in ('int', 'csr'):
@@ -174,7 +254,7 @@ def main():
     if a.child:
         return child(a.child, a.out)
     merged = {}
-    for group in ('slots', 'tokens'):
+    for group in ('slots', 'tokens', 'chain'):
         env = dict(os.environ)
         env.pop('SERT_LL_NODEDUP', None)
         if a.lib:
