@@ -22,6 +22,12 @@ its old evidence, pass the entity's old documents along with the new ones.
 
     python bin/fold_in.py --refresh --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
         --model_output model_15_ref.bin --meta_output meta_ref
+
+A dump of a LOGLINEAR model (bin/train.py --type loglinear: expert finding) takes a path of its own, chosen by the dump's
+model type: the word table and the trained columns of the output layer stay as they are, each new entity gets a column of W
+and an entry of b (sert_amd.foldin.LogLinearFoldIn) that learn with the model's own loss over all V_e + N entities.  The same
+command line; ``--num_negative_samples`` is not read (there is nothing to sample), ``--refresh`` is refused.  The output dump's
+predict function holds W (d, V_e + N) and b (V_e + N).
 """
 import argparse
 import logging
@@ -76,6 +82,51 @@ def one_hot_training_set(path):
     return x, np.asarray(y), w
 
 
+def fold_in_loglinear(args):
+    """A loglinear dump (namespace, LogLinearPredictFn, R_w): the new entities get columns of the output layer and biases of
+    their own (sert_amd.foldin.LogLinearFoldIn) with the model's loss over all V_e + N entities; there are no negatives to
+    draw, so --num_negative_samples is not read.  --refresh is refused: trained columns do not learn here."""
+    if args.refresh:
+        raise RuntimeError('--refresh needs a vectorspace model: refreshing the trained columns of a loglinear model is not '
+                           'supported.')
+    dump = training.read_checkpoint(args.model)
+    model_args, predict_fn, R_w = dump['args'], dump['predict_fn'], dump['tables'][0]
+    meta = foldin.read_meta(args.meta)
+    new_meta = foldin.read_meta(args.new_meta)
+    if new_meta[1] != meta[1]:
+        raise RuntimeError('%s was not prepared with --vocabulary_from %s: the token ids differ.' % (args.new_meta, args.meta))
+    new_index = new_meta[3]
+    new_entity_ids = [new_index[e] for e in range(len(new_index))]
+    associations = dict((e, new_meta[4].get(e, [])) for e in new_entity_ids)
+    # (refuses a known entity id before anything is computed)
+    extended_meta = foldin.extend_meta(meta, new_entity_ids, associations)
+
+    x, y, w = one_hot_training_set(args.data)
+    assert y.size == 0 or int(y.max()) < len(new_entity_ids)
+    W, b = np.asarray(predict_fn.W), np.asarray(predict_fn.b)
+    new_W = models._glorot_uniform((W.shape[0], len(new_entity_ids)))       # as models.LanguageModel initialises W; b: zeros
+    fold = foldin.LogLinearFoldIn(R_w, W, b, new_W, None, (x, y, w), batch_size=args.batch_size,
+                                  regularization_lambda=args.regularization_lambda, window_size=meta[0].window_size,
+                                  device=args.device)
+    mean, stddev = fold.train_error()
+    logging.info('Epoch 0: fold-in error %.6f (stddev %.6f).', mean, stddev)
+    for epoch in range(1, args.iterations + 1):
+        num_batches, loss = fold.train()
+        mean, stddev = fold.train_error()
+        logging.info('Epoch %d: %d batches, mean training loss %.6f; fold-in error %.6f (stddev %.6f).',
+                     epoch, num_batches, loss, mean, stddev)
+    for path in (args.model_output, args.meta_output):
+        directory = os.path.dirname(path)
+        if directory and not os.path.exists(directory):
+            os.makedirs(directory)
+    Wn, bn = fold.get_new_dense()
+    foldin.write_dump(args.model_output, foldin.extend_ll_dump(model_args, predict_fn, R_w, Wn, bn))
+    foldin.write_meta(args.meta_output, extended_meta)
+    logging.info('Saved the extended model "%s" (%d + %d entities) and its meta "%s".', args.model_output, W.shape[1],
+                 len(new_entity_ids), args.meta_output)
+    fold.close()
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
@@ -84,6 +135,10 @@ def main(argv=None):
         return -1
     if args.seed is not None:
         np.random.seed(args.seed)
+
+    # the dump's model type decides: a loglinear dump takes the path of its own, anything else the vectorspace one below
+    if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:
+        return fold_in_loglinear(args)
 
     model_args, predict_fn, R_w, R_e = load_model(args.model)
     if getattr(model_args, 'type', None) is not models.VectorSpaceLanguageModel:

@@ -431,6 +431,13 @@ int sert_score_topk(int device, const float* entities, int64_t num_entities, int
  * declared in sert_hip_foldin.h, which is part of this boundary. */
 #include "sert_hip_foldin.h"
 
+/* ---- folding unseen entities into a trained loglinear model ------------- */
+
+/* The same for the expert-finding model: R_w, W and b stay fixed and N new columns of W and entries of b learn, with the
+ * model's own loss on the extended entity set.  The logits of the trained entities are cached per distinct word at upload.
+ * The handle and its calls are declared in sert_hip_ll_foldin.h, which is part of this boundary. */
+#include "sert_hip_ll_foldin.h"
+
 /* ---- data parallel (new: the reference is single-device) ---- */
 
 #define SERT_COMM_ID_BYTES 128

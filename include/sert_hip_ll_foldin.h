@@ -1,0 +1,88 @@
+/*
+ * sert_hip_ll_foldin.h -- folding unseen entities into a trained loglinear model.  Part of the boundary: included by
+ * sert_hip.h (include that), same conventions (0 = ok, sert_last_error()).
+ *
+ * The loglinear model is the expert-finding model, whose entity set changes most often: people join.  A fold-in keeps the word
+ * table R_w (V_w, d), the projection W (d, V_e) and the bias b (V_e) fixed and learns only N new columns Wn (d, N) and N new
+ * biases bn (N), on the new entities' instances; new entity e is column V_e + e.  Stated against oracle/sert_oracle.py, with
+ * Wx = concat(W, Wn, axis=1) and bx = concat(b, bn), a step on batch i -- rows [iB, (i + 1)B) of the uploaded instances -- is
+ *     loss, grads, _ = LogLinearOracle(B, n, R_w, Wx, bx, lambda).loss_and_grads(X, V_e + y, w)
+ * where only Wx[:, V_e:] and bx[V_e:] are parameters:
+ *     gradient       grads[1][:, V_e:], which includes lambda / B * Wn, and grads[2][V_e:] (the bias is not regularised)
+ *     returned loss  sum(loss_i * w_i) / B + lambda / (2B) * sum(Wn * Wn), evaluated before the update: the L2 term covers the
+ *                    trainable columns only
+ *     update         oracle.Adadelta over [Wn, bn], zero accumulators at creation, lr / rho / eps from the config
+ * The clips are part of the contract: log clip(P) per token, clip(Q) on the label and their inclusive gradient masks, exactly
+ * as in the model's step.  R_w, W and b are never written.  The logits of the V_e trained entities for a word cannot change, so
+ * they are computed once, at upload, for the upload's distinct words (the logit cache); a step runs an N-wide GEMM, one row
+ * kernel over the cached logits and Adadelta on d N + N numbers -- no V_e-wide GEMM, no word-table update.  Every reduction is
+ * order-fixed and there are no floating-point atomics: two handles with the same inputs hold the same bits.
+ *
+ * The handle is an object of its own, like sert_foldin: it COPIES what it needs from the model when it is created and shares
+ * no state with the model's step schedule.  Later training or destruction of the model does not change it.
+ * Out of scope: refreshing trained columns, CSR label rows, data-parallel handles, window sizes above 32, a logit cache that
+ * spills or is recomputed per step.
+ */
+#ifndef SERT_HIP_LL_FOLDIN_H
+#define SERT_HIP_LL_FOLDIN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct sert_model sert_model;
+typedef struct sert_ll_foldin sert_ll_foldin;
+
+typedef struct sert_ll_foldin_config {
+    uint32_t struct_size;      /* = sizeof(sert_ll_foldin_config), checked */
+    int32_t batch_size;        /* B of the fold-in (its own, not the model's): divisor of the loss mean and of lambda/(2B) */
+    float lambda_;             /* regularization_lambda of the new columns */
+    float lr, rho, eps;        /* Adadelta (oracle.Adadelta) */
+    uint64_t max_cache_bytes;  /* upper bound of the logit cache of an upload in bytes; 0 = no cap */
+} sert_ll_foldin_config;
+
+enum {
+    SERT_LL_FOLDIN_W = 0, SERT_LL_FOLDIN_B = 1, SERT_LL_FOLDIN_ACCU_W = 2, SERT_LL_FOLDIN_ACCU_B = 3,
+    SERT_LL_FOLDIN_DELTA_W = 4, SERT_LL_FOLDIN_DELTA_B = 5
+};
+
+/* A fold-in of num_new >= 1 entities into model m, with initial columns init_W (d, num_new) row-major and initial biases
+ * init_b (num_new) or NULL (zeros).  The model's parameters are first brought up to date, as for sert_get_tensor, then R_w, W
+ * and b are copied.  Refused with a message, before any launch: a vectorspace or SERT_KIND_VECTORSPACE_SOFTMAX model; a model
+ * with a communicator attached (data parallel); num_new < 1; a window size above 32; a bad config (struct_size, batch_size < 1,
+ * lambda < 0, rho outside [0, 1), eps <= 0); the size limits (V_e + num_new and B n num_new below 2^31). */
+int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
+                          const sert_ll_foldin_config* cfg, sert_ll_foldin** out);
+int sert_ll_foldin_destroy(sert_ll_foldin* f);
+
+/* The fold-in instances: x (M, n) int32 token ids in [0, V_w), y (M,) int32 in [0, num_new) -- one label per instance --, w (M,)
+ * float32 instance weights or NULL (all 1).  Validated on the host (no kernel is launched on bad ids).  Then, once per upload:
+ * the sorted distinct words D of x, the logit cache Zold = R_w[D] W + b of shape (|D|, V_e), and per word the (max, sum exp)
+ * of its row.  The cache takes |D| V_e 4 bytes; an upload whose cache exceeds max_cache_bytes or cannot be allocated is refused
+ * with a message that names the bytes needed, and the handle keeps what it held (a failed allocation: no upload).  Batch i is
+ * rows [iB, (i + 1)B); a trailing M mod B instances are never visited, as in training.  Replaces an earlier upload; the
+ * optimiser state is kept. */
+int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M);
+/* number of complete batches of the upload, floor(M / B); < 0 on a null handle */
+int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f);
+
+/* One step (see above) on batch `batch`; loss_out: the returned loss. */
+int sert_ll_foldin_train_batch(sert_ll_foldin* f, int64_t batch, float* loss_out);
+/* `count` steps with ONE host synchronisation: the bits of the sert_ll_foldin_train_batch loop. */
+int sert_ll_foldin_train_batches(sert_ll_foldin* f, const int64_t* batches, int64_t count, float* losses_out);
+
+/* LogLinearOracle.eval_loss(X, V_e + y) on the extended model for batch `batch`: unweighted, unregularised; no state changes. */
+int sert_ll_foldin_eval_batch(sert_ll_foldin* f, int64_t batch, float* loss_out);
+
+/* which = SERT_LL_FOLDIN_W / _B: Wn (d, num_new) row-major / bn (num_new); _ACCU_* / _DELTA_*: Adadelta's two accumulators of
+ * either.  count must be d * num_new or num_new. */
+int sert_ll_foldin_get_tensor(sert_ll_foldin* f, int which, float* host, size_t count);
+int sert_ll_foldin_set_tensor(sert_ll_foldin* f, int which, const float* host, size_t count);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SERT_HIP_LL_FOLDIN_H */

@@ -85,6 +85,13 @@ EXPORTS_FOLDIN = [
     'sert_foldin_set_eval_draws', 'sert_foldin_get_eval_draws',
 ]
 FOLDIN_ROWS, FOLDIN_M, FOLDIN_V = 0, 1, 2
+# ... and include/sert_hip_ll_foldin.h, which sert_hip.h includes as well (the same for a trained loglinear model)
+EXPORTS_LL_FOLDIN = [
+    'sert_ll_foldin_create', 'sert_ll_foldin_destroy', 'sert_ll_foldin_upload', 'sert_ll_foldin_num_batches',
+    'sert_ll_foldin_train_batch', 'sert_ll_foldin_train_batches', 'sert_ll_foldin_eval_batch',
+    'sert_ll_foldin_get_tensor', 'sert_ll_foldin_set_tensor',
+]
+LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B = 0, 1, 2, 3, 4, 5
 FOLDIN_LOSS_FORMS = ('none', 'vector', 'scalar')       # SERT_FOLDIN_LOSS_* (include/sert_hip_debug.h)
 
 
@@ -132,6 +139,19 @@ class SertFoldInConfig(ctypes.Structure):
         ('beta2', ctypes.c_float),
         ('eps', ctypes.c_float),
         ('seed', ctypes.c_uint64),
+    ]
+
+
+class SertLlFoldInConfig(ctypes.Structure):
+    """sert_ll_foldin_config (include/sert_hip_ll_foldin.h)."""
+    _fields_ = [
+        ('struct_size', ctypes.c_uint32),
+        ('batch_size', ctypes.c_int32),
+        ('lambda_', ctypes.c_float),
+        ('lr', ctypes.c_float),
+        ('rho', ctypes.c_float),
+        ('eps', ctypes.c_float),
+        ('max_cache_bytes', ctypes.c_uint64),
     ]
 
 
@@ -206,6 +226,16 @@ def load():
     lib.sert_foldin_set_eval_draws.argtypes = [vp, i64]
     lib.sert_foldin_get_eval_draws.argtypes = [vp]
     lib.sert_foldin_get_eval_draws.restype = i64
+    lib.sert_ll_foldin_create.argtypes = [vp, i32, fp, fp, ctypes.POINTER(SertLlFoldInConfig), ctypes.POINTER(vp)]
+    lib.sert_ll_foldin_destroy.argtypes = [vp]
+    lib.sert_ll_foldin_upload.argtypes = [vp, fp, fp, fp, i64]
+    lib.sert_ll_foldin_num_batches.argtypes = [vp]
+    lib.sert_ll_foldin_num_batches.restype = i64
+    lib.sert_ll_foldin_train_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_ll_foldin_train_batches.argtypes = [vp, fp, i64, fp]
+    lib.sert_ll_foldin_eval_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_ll_foldin_get_tensor.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_ll_foldin_set_tensor.argtypes = [vp, ctypes.c_int, fp, sz]
     lib.sert_score_topk.argtypes = [ctypes.c_int, fp, i64, i32, fp, i64, i32, fp, fp]
     lib.sert_scorer_create.argtypes = [ctypes.c_int, fp, i64, i32, ctypes.POINTER(vp)]
     lib.sert_scorer_destroy.argtypes = [vp]
@@ -1216,6 +1246,91 @@ class FoldIn(object):
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
             self._lib.sert_foldin_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LlFoldIn(object):
+    """Owner of one sert_ll_foldin handle (include/sert_hip_ll_foldin.h): ``num_new`` columns of W and entries of b learnt
+    on top of the frozen parameters of ``engine`` (a loglinear Engine), which are copied at construction -- the engine may
+    train on or be closed afterwards.  ``init_W``: (word_dim, num_new); ``init_b``: (num_new,) or None (zeros)."""
+
+    def __init__(self, engine, init_W, init_b, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0):
+        self._lib = load()
+        self._h = None
+        Wn = np.ascontiguousarray(init_W, dtype=np.float32)
+        if Wn.ndim != 2 or Wn.shape[0] != engine.cfg.word_dim:
+            raise SertError('init_W must be (word_dim, num_new)')
+        bn = None
+        if init_b is not None:
+            bn = np.ascontiguousarray(init_b, dtype=np.float32)
+            if bn.shape != (Wn.shape[1],):
+                raise SertError('init_b must be (num_new,)')
+        c = SertLlFoldInConfig()
+        c.struct_size = ctypes.sizeof(SertLlFoldInConfig)
+        c.batch_size, c.lambda_ = int(batch_size), float(lambda_)
+        c.lr, c.rho, c.eps, c.max_cache_bytes = float(lr), float(rho), float(eps), int(max_cache_bytes)
+        self.cfg = c
+        self.word_dim, self.num_new = int(Wn.shape[0]), int(Wn.shape[1])
+        self.num_entities = int(engine.cfg.num_entities)
+        self.window_size = int(engine.cfg.window_size)
+        h = ctypes.c_void_p()
+        check(self._lib.sert_ll_foldin_create(engine._h, self.num_new, Wn.ctypes.data if Wn.size else None, _addr(bn),
+                                              ctypes.byref(c), ctypes.byref(h)))
+        self._h = h
+
+    def upload(self, x, y, w=None):
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if x.ndim != 2 or x.shape[1] != self.window_size or y.shape != (x.shape[0],):
+            raise SertError('x must be (M, window_size) and y (M,)')
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != y.shape:
+                raise SertError('w must be (M,)')
+        check(self._lib.sert_ll_foldin_upload(self._h, x.ctypes.data, y.ctypes.data, _addr(w), x.shape[0]))
+
+    def num_batches(self):
+        return int(self._lib.sert_ll_foldin_num_batches(self._h))
+
+    def train_batch(self, batch_index):
+        loss = ctypes.c_float()
+        check(self._lib.sert_ll_foldin_train_batch(self._h, int(batch_index), ctypes.byref(loss)))
+        return np.float32(loss.value)
+
+    def train_batches(self, batch_indices):
+        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
+        out = np.empty(idx.size, dtype=np.float32)
+        check(self._lib.sert_ll_foldin_train_batches(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
+        return out
+
+    def eval_batch(self, batch_index):
+        loss = ctypes.c_float()
+        check(self._lib.sert_ll_foldin_eval_batch(self._h, int(batch_index), ctypes.byref(loss)))
+        return np.float32(loss.value)
+
+    def _shape(self, which):
+        if which not in (LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B):
+            raise SertError('which must be one of LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B')
+        return (self.num_new,) if which in (LL_FOLDIN_B, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_B) else (self.word_dim, self.num_new)
+
+    def get_tensor(self, which):
+        out = np.empty(self._shape(int(which)), dtype=np.float32)
+        check(self._lib.sert_ll_foldin_get_tensor(self._h, int(which), out.ctypes.data, out.size))
+        return out
+
+    def set_tensor(self, which, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        check(self._lib.sert_ll_foldin_set_tensor(self._h, int(which), a.ctypes.data, a.size))
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sert_ll_foldin_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,417 @@
+// Part of sert_hip.hip (one translation unit; included there, inside its extern "C" block): C ABI: folding unseen entities
+// into a trained loglinear model (include/sert_hip_ll_foldin.h: sert_ll_foldin_*; kernels_ll_foldin.h).  Like sert_foldin the
+// handle copies the model's parameters when it is created and runs on a stream of its own.
+
+struct sert_ll_foldin {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    sert_ll_foldin_config cfg;
+    int Vw = 0, Ve = 0, N = 0, d = 0, n = 0;
+    // the frozen snapshot
+    float *rw = nullptr, *W = nullptr, *b = nullptr;
+    // the new columns Wn (d, N) and biases bn (N), Adadelta's accumulators, the gradients
+    float *Wn = nullptr, *bn = nullptr, *accu_w = nullptr, *accu_b = nullptr, *delta_w = nullptr, *delta_b = nullptr;
+    float *g_w = nullptr, *g_b = nullptr;
+    // ---- the upload ----
+    int64_t M = 0, D = 0;                // instances; distinct words
+    int32_t* y = nullptr;
+    float* w = nullptr;
+    float* G = nullptr;                  // (D, d) = R_w[distinct words]
+    float* Zold = nullptr;               // (D, V_e) the logit cache
+    float2* stat = nullptr;              // (D) (max, sum exp) of a cache row
+    int32_t* Lb = nullptr;               // per batch: the sorted distinct words of the batch, as rows of the cache
+    int32_t* tok = nullptr;              // (batches, B, n): a token's slot in its batch's list
+    int32_t* wptr = nullptr;             // per batch: U + 1 offsets into wpos
+    int32_t* wpos = nullptr;             // (batches, B n): the token positions of each word of the batch, ascending
+    std::vector<int64_t> lb_off, ptr_off;    // where a batch's Lb / wptr start
+    std::vector<int32_t> U;                  // a batch's number of distinct words
+    // per-step scratch, sized by the upload's largest U
+    float *Gb = nullptr, *Zn = nullptr, *lse = nullptr, *dZ = nullptr, *dZu = nullptr, *part = nullptr;
+    float* rowloss = nullptr;            // (B)
+    float* red_sq = nullptr;             // [kOptBlocks] sums of squares of Wn, then [kOptBlocks] of bn (not in the loss)
+    float* d_loss = nullptr;             // [3]
+    float* d_losses = nullptr;           // multi-step loss ring
+    int64_t d_losses_cap = 0;
+};
+
+static void llf_free_upload(sert_ll_foldin* f) {
+    for (void* p : {(void*)f->y, (void*)f->w, (void*)f->G, (void*)f->Zold, (void*)f->stat, (void*)f->Lb, (void*)f->tok, (void*)f->wptr,
+                    (void*)f->wpos, (void*)f->Gb, (void*)f->Zn, (void*)f->lse, (void*)f->dZ, (void*)f->dZu, (void*)f->part})
+        (void)hipFree(p);
+    f->y = nullptr; f->w = nullptr; f->G = nullptr; f->Zold = nullptr; f->stat = nullptr; f->Lb = nullptr; f->tok = nullptr;
+    f->wptr = nullptr; f->wpos = nullptr; f->Gb = nullptr; f->Zn = nullptr; f->lse = nullptr; f->dZ = nullptr; f->dZu = nullptr;
+    f->part = nullptr;
+    f->lb_off.clear(); f->ptr_off.clear(); f->U.clear();
+    f->M = 0; f->D = 0;
+}
+
+int sert_ll_foldin_destroy(sert_ll_foldin* f) {
+    if (!f) return 0;
+    if (f->device >= 0) {
+        (void)hipSetDevice(f->device);
+        if (f->stream) (void)hipStreamSynchronize(f->stream);
+    }
+    llf_free_upload(f);
+    for (void* p : {(void*)f->rw, (void*)f->W, (void*)f->b, (void*)f->Wn, (void*)f->bn, (void*)f->accu_w, (void*)f->accu_b,
+                    (void*)f->delta_w, (void*)f->delta_b, (void*)f->g_w, (void*)f->g_b, (void*)f->rowloss, (void*)f->red_sq,
+                    (void*)f->d_loss, (void*)f->d_losses})
+        (void)hipFree(p);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+    return 0;
+}
+
+static int llf_create(sert_ll_foldin* f, sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
+                      const sert_ll_foldin_config* cfg) {
+    const auto& c = m->cfg;
+    // ---- validation: everything the kernels index with is checked here ----
+    if (c.kind == SERT_KIND_VECTORSPACE)
+        SERT_FAIL("a loglinear fold-in needs a loglinear model: a vectorspace model folds in through sert_foldin_create");
+    if (c.kind != SERT_KIND_LOGLINEAR)
+        SERT_FAIL("a loglinear fold-in needs a loglinear model: the full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX) is not supported");
+    if (m->comm || m->host_ar || m->world > 1)
+        SERT_FAIL("a fold-in of a data-parallel model (a communicator is attached) is not supported");
+    if (num_new < 1) SERT_FAIL("a fold-in needs at least one new entity (num_new >= 1)");
+    if (!init_W) SERT_FAIL("null argument");
+    if (c.window_size > 32) SERT_FAIL("a loglinear fold-in supports window sizes up to 32");
+    if (cfg->batch_size < 1) SERT_FAIL("a fold-in needs batch_size >= 1");
+    if (!(cfg->lambda_ >= 0.f)) SERT_FAIL("regularization lambda must be >= 0");
+    if (!(cfg->rho >= 0.f && cfg->rho < 1.f) || !(cfg->eps > 0.f)) SERT_FAIL("Adadelta needs 0 <= rho < 1 and eps > 0");
+    if ((int64_t)c.num_entities + num_new > INT32_MAX) SERT_FAIL("more than 2^31 - 1 columns in the extended model");
+    if ((int64_t)cfg->batch_size * c.window_size * num_new > INT32_MAX) SERT_FAIL("batch_size * window_size * num_new > 2^31 - 1");
+    if ((int64_t)c.word_dim * num_new > INT32_MAX) SERT_FAIL("word_dim * num_new > 2^31 - 1");
+    SERT_HIP(hipSetDevice(c.device));
+    f->device = c.device; f->cfg = *cfg;
+    f->Vw = c.vocab_size; f->Ve = c.num_entities; f->N = num_new; f->d = c.word_dim; f->n = c.window_size;
+    const size_t n_w = (size_t)f->d * f->N, n_b = (size_t)f->N;
+    // the parameters as a reader must see them (sert_get_tensor): every lazily updated word-table row brought to the model's
+    // step, the side queues drained
+    SERT_TRY(ensure_full_rw(m));
+    SERT_TRY(ensure_rw_current(m, -1));
+    if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
+    if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
+    SERT_TRY(dmalloc(&f->rw, m->n_rw));
+    SERT_TRY(dmalloc(&f->W, m->n_w));
+    SERT_TRY(dmalloc(&f->b, m->n_b));
+    SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipStreamCreate(&f->stream));
+    hipStream_t s = f->stream;
+    SERT_TRY(dmalloc(&f->Wn, n_w));
+    SERT_TRY(dzalloc(&f->bn, n_b, s));
+    SERT_TRY(dzalloc(&f->accu_w, n_w, s));
+    SERT_TRY(dzalloc(&f->accu_b, n_b, s));
+    SERT_TRY(dzalloc(&f->delta_w, n_w, s));
+    SERT_TRY(dzalloc(&f->delta_b, n_b, s));
+    SERT_TRY(dmalloc(&f->g_w, n_w));
+    SERT_TRY(dmalloc(&f->g_b, n_b));
+    SERT_HIP(hipMemcpyAsync(f->Wn, init_W, n_w * sizeof(float), hipMemcpyHostToDevice, s));
+    if (init_b) SERT_HIP(hipMemcpyAsync(f->bn, init_b, n_b * sizeof(float), hipMemcpyHostToDevice, s));
+    SERT_TRY(dmalloc(&f->rowloss, (size_t)cfg->batch_size));
+    SERT_TRY(dmalloc(&f->red_sq, (size_t)2 * kOptBlocks));
+    SERT_TRY(dmalloc(&f->d_loss, (size_t)3));
+    SERT_HIP(hipStreamSynchronize(s));             // (init_W, init_b are borrowed for the call only)
+    SERT_HIP(hipStreamSynchronize(m->stream));     // (the snapshot is complete: the model may train or go away)
+    return 0;
+}
+
+int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
+                          const sert_ll_foldin_config* cfg, sert_ll_foldin** out) {
+    refresh_gemm_choice();
+    if (!m || !cfg || !out) SERT_FAIL("null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(sert_ll_foldin_config)) SERT_FAIL("sert_ll_foldin_config size mismatch (ABI)");
+    sert_ll_foldin* f = new sert_ll_foldin();
+    const int rc = llf_create(f, m, num_new, init_W, init_b, cfg);
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        sert_ll_foldin_destroy(f);
+        g_last_error = keep;
+        return rc;
+    }
+    *out = f;
+    return 0;
+}
+
+// the split-K shape of dWn = Gb^T dZu over `rows` distinct words (the loglinear step's rule, step_softmax_loglinear.inc)
+static void llf_dw_splits(const sert_ll_foldin* f, int64_t rows, int* splits, int* kper) {
+    const int tiles = cdiv(f->N, GN) * cdiv(f->d, GM);
+    int sp = std::max(1, std::min(cdiv(rows, GK), cdiv(1024, tiles)));
+    const int kp = (int)round_up((size_t)cdiv(std::max<int64_t>(rows, 1), sp), GK);
+    sp = std::max(1, cdiv(rows, kp));
+    *splits = sp; *kper = kp;
+}
+
+int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
+    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+    const int n = f->n, d = f->d, Ve = f->Ve, N = f->N, B = f->cfg.batch_size;
+    if (M * n > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in tokens");
+    // host-side validation: no kernel is launched on bad ids
+    for (int64_t i = 0; i < M; ++i)
+        if (y[i] < 0 || y[i] >= N) SERT_FAIL("fold-in label out of range [0, num_new)");
+    for (int64_t i = 0; i < M * n; ++i)
+        if (x[i] < 0 || x[i] >= f->Vw) SERT_FAIL("token id out of range [0, vocab_size)");
+    // ---- the distinct words D of x (sorted) and the row of the cache of every token ----
+    std::vector<int32_t> row_of((size_t)f->Vw, -1), words;
+    for (int64_t i = 0; i < M * n; ++i) row_of[(size_t)x[i]] = 0;
+    for (int32_t v = 0; v < f->Vw; ++v)
+        if (row_of[(size_t)v] == 0) { row_of[(size_t)v] = (int32_t)words.size(); words.push_back(v); }
+    const int64_t D = (int64_t)words.size();
+    const unsigned long long need = (unsigned long long)D * (unsigned long long)Ve * sizeof(float);
+    if (f->cfg.max_cache_bytes != 0 && need > f->cfg.max_cache_bytes)
+        SERT_FAIL("the logit cache of this upload needs " + std::to_string(need) + " bytes (" + std::to_string(D) +
+                  " distinct words x " + std::to_string(Ve) + " entities), more than max_cache_bytes = " +
+                  std::to_string((unsigned long long)f->cfg.max_cache_bytes));
+    // ---- per batch: the sorted list of its distinct words, a slot per token, the token positions per word ----
+    const int64_t nb = M / B, bt = (int64_t)B * n;
+    std::vector<int32_t> Lb, tok((size_t)(nb * bt)), wptr, wpos((size_t)(nb * bt)), local((size_t)D, -1), fill;
+    std::vector<int64_t> lb_off((size_t)nb), ptr_off((size_t)nb);
+    std::vector<int32_t> Us((size_t)nb);
+    int Umax = 1;
+    for (int64_t bi = 0; bi < nb; ++bi) {
+        const int32_t* xb = x + (size_t)bi * bt;
+        const size_t l0 = Lb.size();
+        for (int64_t t = 0; t < bt; ++t) {
+            const int32_t r = row_of[(size_t)xb[t]];
+            if (local[(size_t)r] < 0) { local[(size_t)r] = 0; Lb.push_back(r); }
+        }
+        std::sort(Lb.begin() + (std::ptrdiff_t)l0, Lb.end());
+        const int U = (int)(Lb.size() - l0);
+        for (int u = 0; u < U; ++u) local[(size_t)Lb[l0 + u]] = u;
+        lb_off[(size_t)bi] = (int64_t)l0; ptr_off[(size_t)bi] = (int64_t)wptr.size(); Us[(size_t)bi] = U;
+        Umax = std::max(Umax, U);
+        std::vector<int32_t> cnt((size_t)U + 1, 0);
+        int32_t* tb = tok.data() + (size_t)bi * bt;
+        for (int64_t t = 0; t < bt; ++t) { tb[t] = local[(size_t)row_of[(size_t)xb[t]]]; ++cnt[(size_t)tb[t] + 1]; }
+        for (int u = 0; u < U; ++u) cnt[(size_t)u + 1] += cnt[(size_t)u];
+        wptr.insert(wptr.end(), cnt.begin(), cnt.end());
+        fill.assign(cnt.begin(), cnt.end() - 1);
+        int32_t* pb = wpos.data() + (size_t)bi * bt;
+        for (int64_t t = 0; t < bt; ++t) pb[fill[(size_t)tb[t]]++] = (int32_t)t;     // (ascending t within a word)
+        for (int u = 0; u < U; ++u) local[(size_t)Lb[l0 + u]] = -1;
+    }
+    SERT_HIP(hipSetDevice(f->device));
+    hipStream_t s = f->stream;
+    SERT_HIP(hipStreamSynchronize(s));
+    llf_free_upload(f);
+    if (M == 0) return 0;
+    uint32_t* dwords = nullptr;
+    auto body = [&]() -> int {
+        if (hipMalloc((void**)&f->Zold, (size_t)need) != hipSuccess) {
+            (void)hipGetLastError();
+            f->Zold = nullptr;
+            SERT_FAIL("the logit cache of this upload needs " + std::to_string(need) + " bytes, which cannot be allocated");
+        }
+        SERT_TRY(dmalloc(&f->y, (size_t)M));
+        SERT_TRY(dmalloc(&f->w, (size_t)M));
+        SERT_TRY(dmalloc(&f->G, (size_t)D * d));
+        SERT_TRY(dmalloc(&f->stat, (size_t)D));
+        SERT_TRY(dmalloc(&f->Lb, std::max<size_t>(Lb.size(), 1)));
+        SERT_TRY(dmalloc(&f->tok, std::max<size_t>(tok.size(), 1)));
+        SERT_TRY(dmalloc(&f->wptr, std::max<size_t>(wptr.size(), 1)));
+        SERT_TRY(dmalloc(&f->wpos, std::max<size_t>(wpos.size(), 1)));
+        SERT_TRY(dmalloc(&dwords, (size_t)D));
+        // (llf_dw_splits never gives a batch more slabs than its first guess for the largest one)
+        const int max_splits = std::max(1, std::min(cdiv(Umax, GK), cdiv(1024, cdiv(N, GN) * cdiv(d, GM)))) + 1;
+        SERT_TRY(dmalloc(&f->Gb, (size_t)Umax * d));
+        SERT_TRY(dmalloc(&f->Zn, (size_t)Umax * N));
+        SERT_TRY(dmalloc(&f->lse, (size_t)Umax));
+        SERT_TRY(dmalloc(&f->dZ, (size_t)bt * N));
+        SERT_TRY(dmalloc(&f->dZu, (size_t)Umax * N));
+        SERT_TRY(dmalloc(&f->part, (size_t)max_splits * ((size_t)d * N + N)));
+        const std::vector<float> ones(w ? 0 : (size_t)M, 1.0f);
+        SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipMemcpyAsync(dwords, words.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!Lb.empty()) SERT_HIP(hipMemcpyAsync(f->Lb, Lb.data(), Lb.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!tok.empty()) SERT_HIP(hipMemcpyAsync(f->tok, tok.data(), tok.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!wptr.empty()) SERT_HIP(hipMemcpyAsync(f->wptr, wptr.data(), wptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!wpos.empty()) SERT_HIP(hipMemcpyAsync(f->wpos, wpos.data(), wpos.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        // G = R_w[D]; Zold = G W + b, a slab of rows at a time so that no launch sees 2 GiB of either operand: the slabs'
+        // offsets into the cache are 64 bits wide
+        if (d % 4 == 0)
+            launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(D * d / 4, 256, 1 << 20)), dim3(256), 0, s, (const uint32_t*)dwords,
+                   (const float*)f->rw, f->G, D, d);
+        else
+            launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(D * d, 256, 1 << 20)), dim3(256), 0, s, (const uint32_t*)dwords,
+                   (const float*)f->rw, f->G, D, d);
+        const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(D, (((int64_t)1 << 29) - 1) / std::max(Ve, d)));
+        for (int64_t r0 = 0; r0 < D; r0 += slab) {
+            const int rows = (int)std::min<int64_t>(slab, D - r0);
+            launch_gemm<false, false, EPI_BIAS>(s, f->G + (size_t)r0 * d, f->W, f->Zold + (size_t)r0 * Ve, f->b, rows, Ve, d, d, Ve, Ve);
+        }
+        launch(llf_row_stat, dim3((unsigned)D), dim3(256), 0, s, (const float*)f->Zold, Ve, f->stat);
+        SERT_HIP(hipGetLastError());
+        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w and the host lists are borrowed for the call only)
+        return 0;
+    };
+    const int rc = body();
+    (void)hipFree(dwords);
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        (void)hipStreamSynchronize(s);
+        llf_free_upload(f);
+        g_last_error = keep;
+        return rc;
+    }
+    f->M = M; f->D = D;
+    f->lb_off.swap(lb_off); f->ptr_off.swap(ptr_off); f->U.swap(Us);
+    return 0;
+}
+
+int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f) { return f ? f->M / f->cfg.batch_size : -1; }
+
+static int llf_check_batch(sert_ll_foldin* f, int64_t batch) {
+    if (!f) SERT_FAIL("null argument");
+    if (!f->Zold) SERT_FAIL("no fold-in instances uploaded (sert_ll_foldin_upload)");
+    if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
+    return 0;
+}
+
+// the forward of batch `batch` on the handle's stream: the new logits, the tokens' log-sum-exp, the row kernel (TRAIN: dZ of
+// the new columns as well); the rows' losses are left in f->rowloss
+static int llf_forward(sert_ll_foldin* f, int64_t batch, bool train) {
+    const int B = f->cfg.batch_size, n = f->n, d = f->d, N = f->N, U = f->U[(size_t)batch];
+    hipStream_t s = f->stream;
+    const int32_t* Lb = f->Lb + f->lb_off[(size_t)batch];
+    const int32_t* tok = f->tok + (size_t)batch * B * n;
+    // Gb = G[L_b]; Zn = Gb Wn + bn
+    if (d % 4 == 0)
+        launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for((int64_t)U * d / 4, 256, 1 << 20)), dim3(256), 0, s,
+               reinterpret_cast<const uint32_t*>(Lb), (const float*)f->G, f->Gb, (int64_t)U, d);
+    else
+        launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for((int64_t)U * d, 256, 1 << 20)), dim3(256), 0, s,
+               reinterpret_cast<const uint32_t*>(Lb), (const float*)f->G, f->Gb, (int64_t)U, d);
+    launch_gemm<false, false, EPI_BIAS>(s, f->Gb, f->Wn, f->Zn, f->bn, U, N, d, d, N, N);
+    launch(llf_lse, dim3(cdiv(U, 4)), dim3(256), 0, s, f->Zn, (const float2*)f->stat, Lb, f->lse, U, N);
+    const size_t row0 = (size_t)batch * B;
+    auto go = [&](auto training, auto evaluation) {
+        if (train)
+            launch(training, dim3(B), dim3(256), 0, s, (const float*)f->Zold, (const float*)f->Zn, (const float*)f->lse, Lb, tok,
+                   (const int32_t*)(f->y + row0), (const float*)(f->w + row0), f->rowloss, f->dZ, n, f->Ve, N, 1.0f / (float)B);
+        else
+            launch(evaluation, dim3(B), dim3(256), 0, s, (const float*)f->Zold, (const float*)f->Zn, (const float*)f->lse, Lb, tok,
+                   (const int32_t*)(f->y + row0), (const float*)nullptr, f->rowloss, f->dZ, n, f->Ve, N, 1.0f / (float)B);
+    };
+    if (n <= 8) go(llf_row<true, 8>, llf_row<false, 8>);
+    else if (n <= 16) go(llf_row<true, 16>, llf_row<false, 16>);
+    else go(llf_row<true, 32>, llf_row<false, 32>);
+    return 0;
+}
+
+// one step enqueued on the handle's stream; dst: 3 floats on the device (finalize_loss: loss, data term, regulariser)
+static int llf_step_async(sert_ll_foldin* f, int64_t batch, float* dst) {
+    const auto& c = f->cfg;
+    const int B = c.batch_size, d = f->d, N = f->N, U = f->U[(size_t)batch];
+    hipStream_t s = f->stream;
+    SERT_TRY(llf_forward(f, batch, true));
+    // dZu = per-word sums of dZ; dWn = Gb^T dZu with db = the column sums of dZu, split-K with an order-fixed combine
+    launch(llf_word_sum, dim3(grid_for((int64_t)U * N)), dim3(256), 0, s, (const float*)f->dZ,
+           (const int32_t*)(f->wptr + f->ptr_off[(size_t)batch]), (const int32_t*)(f->wpos + (size_t)batch * B * f->n), f->dZu, U, N);
+    int splits = 1, kper = 0;
+    llf_dw_splits(f, U, &splits, &kper);
+    const size_t mn = (size_t)d * N, stride = mn + N;
+    launch_gemm<true, false, EPI_STORE, true>(s, f->Gb, f->dZu, f->part, nullptr, d, N, U, d, N, N, splits, kper, stride);
+    launch_reduce_partials(s, f->part, splits, stride, stride, f->g_w, mn, f->g_b);
+    // Adadelta with the model's arithmetic (adadelta_l2: L2 folded into the gradient of Wn, none for bn; the sum of squares of
+    // the values BEFORE the update from the same pass)
+    const AdadeltaArgs aw{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr, c.rho, c.eps};
+    const AdadeltaArgs ab{0.f, c.lr, c.rho, c.eps};
+    const int nbw = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)mn, 4), 256)));
+    const int nbb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)N, 4), 256)));
+    launch((adadelta_l2<false>), dim3(nbw), dim3(256), 0, s, f->Wn, f->g_w, f->accu_w, f->delta_w, mn, aw, f->red_sq,
+           (const uint32_t*)nullptr, 1u, (int)kRowsAll);
+    launch((adadelta_l2<false>), dim3(nbb), dim3(256), 0, s, f->bn, f->g_b, f->accu_b, f->delta_b, (size_t)N, ab,
+           f->red_sq + kOptBlocks, (const uint32_t*)nullptr, 1u, (int)kRowsAll);
+    launch(finalize_loss, dim3(1), dim3(256), 0, s, (const float*)f->rowloss, B, (const float*)f->red_sq, c.lambda_ > 0.f ? nbw : 0,
+           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    return 0;
+}
+
+int sert_ll_foldin_train_batch(sert_ll_foldin* f, int64_t batch, float* loss_out) {
+    SERT_TRY(llf_check_batch(f, batch));
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_TRY(llf_step_async(f, batch, f->d_loss));
+    float host[3] = {0.f, 0.f, 0.f};
+    SERT_HIP(hipGetLastError());
+    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (loss_out) *loss_out = host[0];
+    return 0;
+}
+
+int sert_ll_foldin_train_batches(sert_ll_foldin* f, const int64_t* batches, int64_t count, float* losses_out) {
+    if (!f || count < 0 || (count > 0 && !batches)) SERT_FAIL("bad argument");
+    for (int64_t i = 0; i < count; ++i) SERT_TRY(llf_check_batch(f, batches[i]));    // (before anything is enqueued)
+    if (count == 0) return 0;
+    SERT_HIP(hipSetDevice(f->device));
+    if (count > f->d_losses_cap) {
+        SERT_HIP(hipStreamSynchronize(f->stream));
+        (void)hipFree(f->d_losses);
+        f->d_losses = nullptr; f->d_losses_cap = 0;
+        SERT_TRY(dmalloc(&f->d_losses, (size_t)count * 3));
+        f->d_losses_cap = count;
+    }
+    for (int64_t i = 0; i < count; ++i) SERT_TRY(llf_step_async(f, batches[i], f->d_losses + 3 * i));
+    SERT_HIP(hipGetLastError());
+    std::vector<float> tmp((size_t)count * 3);
+    SERT_HIP(hipMemcpyAsync(tmp.data(), f->d_losses, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (losses_out)
+        for (int64_t i = 0; i < count; ++i) losses_out[i] = tmp[(size_t)3 * i];
+    return 0;
+}
+
+int sert_ll_foldin_eval_batch(sert_ll_foldin* f, int64_t batch, float* loss_out) {
+    SERT_TRY(llf_check_batch(f, batch));
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_TRY(llf_forward(f, batch, false));
+    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, (const float*)f->rowloss, f->cfg.batch_size, (const float*)f->rowloss, 0,
+           1.0f / (float)f->cfg.batch_size, 0.0f, f->d_loss, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    float host[3] = {0.f, 0.f, 0.f};
+    SERT_HIP(hipGetLastError());
+    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (loss_out) *loss_out = host[0];
+    return 0;
+}
+
+static float* llf_tensor_ref(sert_ll_foldin* f, int which, size_t* count) {
+    const size_t n_w = (size_t)f->d * f->N, n_b = (size_t)f->N;
+    switch (which) {
+        case SERT_LL_FOLDIN_W: *count = n_w; return f->Wn;
+        case SERT_LL_FOLDIN_B: *count = n_b; return f->bn;
+        case SERT_LL_FOLDIN_ACCU_W: *count = n_w; return f->accu_w;
+        case SERT_LL_FOLDIN_ACCU_B: *count = n_b; return f->accu_b;
+        case SERT_LL_FOLDIN_DELTA_W: *count = n_w; return f->delta_w;
+        case SERT_LL_FOLDIN_DELTA_B: *count = n_b; return f->delta_b;
+        default: return nullptr;
+    }
+}
+
+int sert_ll_foldin_get_tensor(sert_ll_foldin* f, int which, float* host, size_t count) {
+    if (!f || !host) SERT_FAIL("null argument");
+    size_t have = 0;
+    float* p = llf_tensor_ref(f, which, &have);
+    if (!p) SERT_FAIL("which must be one of SERT_LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B");
+    if (count != have) SERT_FAIL("element count mismatch");
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_HIP(hipMemcpyAsync(host, p, count * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int sert_ll_foldin_set_tensor(sert_ll_foldin* f, int which, const float* host, size_t count) {
+    if (!f || !host) SERT_FAIL("null argument");
+    size_t have = 0;
+    float* p = llf_tensor_ref(f, which, &have);
+    if (!p) SERT_FAIL("which must be one of SERT_LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B");
+    if (count != have) SERT_FAIL("element count mismatch");
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}

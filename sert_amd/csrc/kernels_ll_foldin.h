@@ -1,0 +1,155 @@
+// Folding unseen entities into a trained loglinear model (include/sert_hip_ll_foldin.h; host: host/api_ll_foldin.inc), gfx950.
+// The logits of the V_e trained entities for a word never change: Zold (|D|, V_e) holds them for the upload's distinct words,
+// and a step computes logits of the N new columns only.  The loss terms are stated in loss_terms.h and only CALLED here
+// (ll_label_term, logp_inside / ll_masked / ll_dz; clip_logp is common.h's).  Every sum has a fixed order: no atomics.
+#pragma once
+#include "common.h"
+#include "loss_terms.h"
+
+namespace sert {
+
+// Once per upload: stat[r] = (max_e Zold[r, e], sum_e exp(Zold[r, e] - max)) over the frozen entities.  One workgroup per row;
+// the maximum first, so that an entity switched off (a bias of -inf) adds exp(-inf) = 0 and no inf - inf is ever formed.
+__global__ __launch_bounds__(256) void llf_row_stat(const float* __restrict__ Zold, int V, float2* __restrict__ stat) {
+    __shared__ float red[4];
+    const float* row = Zold + (size_t)blockIdx.x * V;
+    float mx = -INFINITY;
+    for (int e = threadIdx.x; e < V; e += 256) mx = fmaxf(mx, row[e]);
+    mx = block_max_256(mx, red);
+    float se = 0.f;
+    for (int e = threadIdx.x; e < V; e += 256) se += expf(row[e] - mx);
+    se = block_sum_256(se, red);
+    if (threadIdx.x == 0) stat[blockIdx.x] = make_float2(mx, se);
+}
+
+// Per step, one wave per distinct word u of the batch: the word's frozen (max, sum) merged with its N new logits into
+// lse[u] = log sum over all V_e + N entities; Zn[u, :] becomes the LOG-probabilities of the new columns.
+__global__ __launch_bounds__(256) void llf_lse(float* __restrict__ Zn, const float2* __restrict__ stat,
+                                               const int32_t* __restrict__ Lb, float* __restrict__ lse, int U, int N) {
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (u >= U) return;        // (whole waves leave: the wave reductions below see 64 active lanes)
+    float* z = Zn + (size_t)u * N;
+    const float2 st = stat[Lb[u]];
+    float mx = st.x;
+    for (int j = lane; j < N; j += 64) mx = fmaxf(mx, z[j]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int j = lane; j < N; j += 64) se += expf(z[j] - mx);
+    se = wave_sum(se) + st.y * expf(st.x - mx);
+    const float l = mx + logf(se);
+    for (int j = lane; j < N; j += 64) z[j] -= l;
+    if (lane == 0) lse[u] = l;
+}
+
+// The row kernel: one workgroup per instance i of the batch.
+//   pass A  J_e = sum_t clip(log P_te) over the frozen entities (Zold rows of the window's words, lanes over e) and the new
+//           columns (logpn), an online (max, sum exp) of J per thread merged in a fixed tree, J_y, Q_y, the row's loss
+//   pass B  (TRAIN) the same rows again: dJ_e = Q_e (dQ_e - Q_y dQ_y), r_t = sum_e mask_te dJ_e in NMAX registers per
+//           thread, then dZ[token, j] = mask dJ_j - P_tj r_t for the N new columns only
+// tok: the (B, n) slots of the tokens in the batch's word list Lb; Lb[u]: the word's row of Zold.  n <= NMAX <= 32.
+template <bool TRAIN, int NMAX>
+__global__ __launch_bounds__(256) void llf_row(const float* __restrict__ Zold, const float* __restrict__ logpn,
+                                               const float* __restrict__ lse, const int32_t* __restrict__ Lb,
+                                               const int32_t* __restrict__ tok, const int32_t* __restrict__ y,
+                                               const float* __restrict__ w, float* __restrict__ rowloss,
+                                               float* __restrict__ dZ, int n, int Ve, int N, float inv_batch) {
+    __shared__ float red[4];
+    __shared__ unsigned long long s_off[32];    // element offset of token t's row of Zold (64 bits: the cache may pass 2 GiB)
+    __shared__ unsigned s_new[32];              // ... and of its row of logpn
+    __shared__ float s_lse[32], s_r[32];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const float LOGLO = logf(SERT_CLIP_LO), LOGHI = logf(SERT_CLIP_HI);
+    if (tid < n) {
+        const int u = tok[(size_t)i * n + tid];
+        s_off[tid] = (unsigned long long)Lb[u] * (unsigned long long)Ve;
+        s_new[tid] = (unsigned)u * (unsigned)N;
+        s_lse[tid] = lse[u];
+    }
+    __syncthreads();
+    const int yi = y[i];
+    // ---- pass A ----
+    float mx = -INFINITY, se = 0.f, jy = 0.f;
+    auto online = [&](float a) {
+        if (a > mx) { se = se * expf(mx - a) + 1.0f; mx = a; }
+        else se += expf(a - mx);
+    };
+    for (int e = tid; e < Ve; e += 256) {
+        float a = 0.f;
+        for (int t = 0; t < n; ++t) a += clip_logp(Zold[s_off[t] + e] - s_lse[t], LOGLO, LOGHI);
+        online(a);
+    }
+    for (int j = tid; j < N; j += 256) {
+        float a = 0.f;
+        for (int t = 0; t < n; ++t) a += clip_logp(logpn[s_new[t] + j], LOGLO, LOGHI);
+        online(a);
+        if (j == yi) jy = a;
+    }
+    const float M = block_max_256(mx, red);
+    const float S = block_sum_256(se * expf(mx - M), red);     // (a thread without an element: 0 * exp(-inf) = 0)
+    jy = block_sum_256(jy, red);
+    const float wi = w ? w[i] : 1.0f;
+    const float g = wi * inv_batch;
+    float ylog, qdq;
+    ll_label_term<TRAIN>(expf(jy - M) / S, 1.0f, g, ylog, qdq);
+    if (tid == 0) rowloss[i] = wi * -ylog;
+    if (!TRAIN) return;
+    // ---- pass B ----
+    float r[NMAX];
+#pragma unroll
+    for (int t = 0; t < NMAX; ++t) r[t] = 0.f;
+    for (int e = tid; e < Ve; e += 256) {
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) { lp[t] = Zold[s_off[t] + e] - s_lse[t]; a += clip_logp(lp[t], LOGLO, LOGHI); }
+        const float dj = -(expf(a - M) / S) * qdq;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) r[t] += ll_masked(lp[t], dj, LOGLO, LOGHI);
+    }
+    for (int j = tid; j < N; j += 256) {
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) { lp[t] = logpn[s_new[t] + j]; a += clip_logp(lp[t], LOGLO, LOGHI); }
+        float dj = -(expf(a - M) / S) * qdq;
+        if (j == yi) dj += qdq;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) r[t] += ll_masked(lp[t], dj, LOGLO, LOGHI);
+    }
+#pragma unroll
+    for (int t = 0; t < NMAX; ++t) {
+        if (t < n) {               // (n is uniform: every thread takes the same barriers)
+            const float rt = block_sum_256(r[t], red);
+            if (tid == 0) s_r[t] = rt;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < N; j += 256) {
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) { lp[t] = logpn[s_new[t] + j]; a += clip_logp(lp[t], LOGLO, LOGHI); }
+        float dj = -(expf(a - M) / S) * qdq;
+        if (j == yi) dj += qdq;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) dZ[((size_t)i * n + t) * N + j] = ll_dz(lp[t], dj, s_r[t], LOGLO, LOGHI);
+    }
+}
+
+// dZu[u, :] = the sum of the dZ rows of word u's tokens, in ascending token order (ptr / pos: the batch's CSR of token
+// positions per word, built on the host at upload).  One thread per (u, j).
+__global__ __launch_bounds__(256) void llf_word_sum(const float* __restrict__ dZ, const int32_t* __restrict__ ptr,
+                                                    const int32_t* __restrict__ pos, float* __restrict__ dZu, int U, int N) {
+    const int64_t total = (int64_t)U * N;
+    for (int64_t k = blockIdx.x * (int64_t)256 + threadIdx.x; k < total; k += (int64_t)gridDim.x * 256) {
+        const int u = (int)(k / N), j = (int)(k - (int64_t)u * N);
+        float a = 0.f;
+        for (int q = ptr[u]; q < ptr[u + 1]; ++q) a += dZ[(size_t)pos[q] * N + j];
+        dZu[k] = a;
+    }
+}
+
+}  // namespace sert

@@ -40,6 +40,7 @@
 #include "kernels_sort.h"
 #include "kernels_vs.h"
 #include "kernels_foldin.h"
+#include "kernels_ll_foldin.h"
 #ifdef SERT_VARIANTS
 #include "variants/kernels_gather_hot.h"
 #include "variants/kernels_seg_bundled.h"
@@ -196,6 +197,8 @@ extern "C" {
 #include "host/api_reval.inc"
 
 #include "host/api_foldin.inc"
+
+#include "host/api_ll_foldin.inc"
 
 #include "host/api_comm.inc"
 

@@ -3,6 +3,9 @@
 A catalogue gains entities after training.  The LSE paper's answer is to fold them in: keep the word table, the
 projection and the trained entity rows fixed and learn only the new rows, with the same NCE objective, on the new
 entities' instances.  ``EntityFoldIn`` is that, on the device; ``bin/fold_in.py`` is its command line.
+
+``LogLinearFoldIn`` is the same for a trained loglinear (expert-finding) model (include/sert_hip_ll_foldin.h): the word table
+and the trained columns of the output layer stay fixed and the new entities' columns and biases learn.
 """
 import logging
 import pickle
@@ -165,6 +168,120 @@ class EntityFoldIn(models.ModelInterface):
         self._foldin.close()
 
 
+class LogLinearFoldIn(models.ModelInterface):
+    """N new entities learnt on top of a trained loglinear model (R_w, W (d, V_e), b (V_e): host arrays, never written):
+    N new columns Wn (d, N) of the output layer and N new biases bn, with the model's own loss over the V_e + N entities
+    (include/sert_hip_ll_foldin.h).
+
+    training_set: (x (M, window_size) token ids of the TRAINED vocabulary, y (M,) in [0, N), w (M,) weights or None).
+    New entity e becomes column V_e + e.  ``new_W_init`` None: N = y.max() + 1 columns drawn with
+    ``_glorot_uniform((d, N))``; ``new_b_init`` None: zeros -- as models.LanguageModel initialises its output layer.  The
+    batch size and lambda are the fold-in's own.  ``max_cache_bytes``: a cap on the logit cache of the upload (0: none)."""
+
+    #: batches issued to the device before their losses are read back
+    steps_per_sync = 1
+
+    def __init__(self, R_w, W, b, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, window_size,
+                 device=0, max_cache_bytes=0, _engine=None):
+        super(LogLinearFoldIn, self).__init__(batch_size)
+        x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
+        w = training_set[2] if len(training_set) > 2 else None
+        assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        word_dim = int(np.shape(W)[0])
+        if new_W_init is None:
+            if not y.size:
+                raise RuntimeError('no fold-in instances and no initial columns: nothing says how many entities are new')
+            new_W_init = models._glorot_uniform((word_dim, int(y.max()) + 1))
+        new_W_init = np.ascontiguousarray(new_W_init, dtype=np.float32)
+        self.window_size = int(window_size)
+        self.num_new = int(new_W_init.shape[1])
+        self.num_entities = int(np.shape(W)[1])
+        self.training_num_instances = int(y.shape[0])
+        _capi.require_gpu()
+        engine, owned = _engine, False
+        if engine is None:
+            # a parameters-only model on the device holds the frozen tensors for the moment of the copy
+            R_w, W, b = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
+            assert W.shape[0] == R_w.shape[1] and b.shape == (W.shape[1],)
+            engine = _capi.Engine(
+                kind=_capi.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=self.window_size,
+                vocab_size=R_w.shape[0], num_entities=W.shape[1], word_dim=R_w.shape[1], entity_dim=0, num_negatives=0,
+                id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0, lr=1.0, beta1=0.95,
+                beta2=0.0, eps=1e-6, seed=0)
+            owned = True
+            for which, value in ((_capi.T_RW, R_w), (_capi.T_W, W), (_capi.T_B, b)):
+                engine.set_tensor(which, value)
+        try:
+            self._foldin = _capi.LlFoldIn(engine, new_W_init, new_b_init, batch_size, regularization_lambda,
+                                          max_cache_bytes=max_cache_bytes)
+        finally:
+            if owned:
+                engine.close()      # (the handle copied what it needs)
+        self._foldin.upload(x, y, w)
+        logging.info('Folding in %d new entities (columns %d .. %d) on %d instances.', self.num_new, self.num_entities,
+                     self.num_entities + self.num_new - 1, self.training_num_instances)
+
+    @classmethod
+    def from_model(cls, model, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, max_cache_bytes=0):
+        """From a live ``models.LanguageModel``: its parameters as they are now are copied on the device (the model may train
+        on or be dropped afterwards)."""
+        if not isinstance(model, models.LanguageModel):
+            raise RuntimeError('a loglinear fold-in needs a LanguageModel')
+        return cls(None, _Shape((model.representation_size, model.output_layer_size)), None, new_W_init, new_b_init,
+                   training_set, batch_size, regularization_lambda, model.window_size, max_cache_bytes=max_cache_bytes,
+                   _engine=model._engine)
+
+    # -- the step functions ---------------------------------------------------------------------------------------
+    def train_fn(self, batch_index):
+        return self._foldin.train_batch(batch_index)
+
+    def test_fn(self, batch_index):
+        return self._foldin.eval_batch(batch_index)
+
+    def train(self):
+        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
+        count = self.training_num_instances
+        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
+        if self.steps_per_sync > 1:
+            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
+                                                       report_interval=1000, shuffle=True)
+        else:
+            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
+        return num_batches, np.mean(losses)
+
+    def train_error(self):
+        """(mean, std) of the per-batch evaluation losses on the extended model: unweighted, unregularised."""
+        count = self.training_num_instances
+        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
+        _, losses = self._iterate_batches(self.test_fn, count)
+        return np.mean(losses), np.std(losses)
+
+    # -- results and state --------------------------------------------------------------------------------------------
+    def get_new_dense(self):
+        """(Wn (d, N), bn (N,)): the new columns and biases as they are now."""
+        return self._foldin.get_tensor(_capi.LL_FOLDIN_W), self._foldin.get_tensor(_capi.LL_FOLDIN_B)
+
+    def get_extended_dense(self, W, b):
+        """(W (d, V_e + N), b (V_e + N,)): the trained ``W`` / ``b`` (the caller's: never modified) with the new columns behind."""
+        W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
+        assert W.shape[1] == self.num_entities and b.shape == (self.num_entities,)
+        Wn, bn = self.get_new_dense()
+        return np.concatenate([W, Wn], axis=1), np.concatenate([b, bn])
+
+    def get_optimizer_state(self):
+        g = self._foldin.get_tensor
+        return {'accu_W': g(_capi.LL_FOLDIN_ACCU_W), 'accu_b': g(_capi.LL_FOLDIN_ACCU_B),
+                'delta_W': g(_capi.LL_FOLDIN_DELTA_W), 'delta_b': g(_capi.LL_FOLDIN_DELTA_B)}
+
+    def set_optimizer_state(self, st):
+        for name, which in (('accu_W', _capi.LL_FOLDIN_ACCU_W), ('accu_b', _capi.LL_FOLDIN_ACCU_B),
+                            ('delta_W', _capi.LL_FOLDIN_DELTA_W), ('delta_b', _capi.LL_FOLDIN_DELTA_B)):
+            self._foldin.set_tensor(which, st[name])
+
+    def close(self):
+        self._foldin.close()
+
+
 class _Shape(object):
     """Stands in for a table the constructor only asks the shape of (from_model: the table itself stays on the device)."""
 
@@ -180,6 +297,19 @@ def extend_dump(args, predict_fn, R_w, R_e, new_rows):
     new_rows = np.asarray(new_rows, dtype=R_e.dtype)
     assert new_rows.ndim == 2 and new_rows.shape[1] == R_e.shape[1]
     return [args, predict_fn, R_w, np.concatenate([R_e, new_rows], axis=0)]
+
+
+def extend_ll_dump(args, predict_fn, R_w, Wn, bn):
+    """The objects of a loglinear model dump (args, predict_fn, R_w) whose LogLinearPredictFn holds W (d, V_e + N) and
+    b (V_e + N): the trained output layer of ``predict_fn`` (never modified) with the new columns ``Wn`` (d, N) and biases
+    ``bn`` (N) behind.  bin/query.py and LogLinearPredictFn.rank_queries serve it unchanged."""
+    st = predict_fn.__getstate__()
+    W, b = np.asarray(st['W']), np.asarray(st['b'])
+    Wn, bn = np.asarray(Wn, dtype=W.dtype), np.asarray(bn, dtype=b.dtype)
+    assert Wn.ndim == 2 and Wn.shape[0] == W.shape[0] and bn.shape == (Wn.shape[1],)
+    extended = models.LogLinearPredictFn(R_w=np.asarray(st['R_w']), W=np.concatenate([W, Wn], axis=1),
+                                         b=np.concatenate([b, bn]), window_size=st['window_size'])
+    return [args, extended, R_w]
 
 
 def write_dump(path, objects):

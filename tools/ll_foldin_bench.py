@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""Folding new entities into a loglinear model (sert_ll_foldin_*) against the step it replaces: one process, alternating.
+
+    python tools/ll_foldin_bench.py --out profiles/r15_ll_foldin.json
+
+Per setting: the fold-in step through sert_ll_foldin_train_batches (N new columns on top of a frozen loglinear model with V_e
+entities) and the full loglinear step through sert_train_batches of a model with V_e + N entities, at the same B, window and
+d, on the same Zipfian tokens.  One warm-up pass of each, then --repeats alternations of --steps steps; a time is a host
+clock around a call that ends in its one host synchronisation.  The one-time cost of the fold-in's upload
+(sert_ll_foldin_upload: host validation and word lists, copies, the logit cache GEMM over the distinct words, the row pass) is
+timed apart, with the size of the cache.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from sert_amd import _capi as C  # noqa: E402
+
+# name, B, V_w, V_e, N, d, window
+SETTINGS = [('w3c', 1024, 100000, 715, 64, 300, 8),                  # bench.py's W3C loglinear settings
+            ('ve_100000', 1024, 100000, 100000, 64, 300, 8)]
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return time.perf_counter() - t0, out
+
+
+def glorot(rng, shape):
+    a = np.sqrt(6.0 / sum(shape))
+    return rng.uniform(-a, a, size=shape).astype(np.float32)
+
+
+def engine(rng, B, Vw, Ve, d, n, inference_only=0):
+    e = C.Engine(kind=C.KIND_LOGLINEAR, batch_size=B, global_batch_size=B, window_size=n, vocab_size=Vw, num_entities=Ve,
+                 word_dim=d, entity_dim=0, num_negatives=0, id_bytes=4, device=0, keep_grads=0, deterministic=1,
+                 inference_only=inference_only, lambda_=0.01, lr=1.0, beta1=0.95, beta2=0.0, eps=1e-6, seed=0)
+    e.set_tensor(C.T_RW, glorot(rng, (Vw, d)))
+    e.set_tensor(C.T_W, glorot(rng, (d, Ve)))
+    e.set_tensor(C.T_B, np.zeros(Ve, np.float32))
+    return e
+
+
+def zipf_tokens(rng, Vw, shape):
+    return rng.permutation(Vw)[np.minimum(rng.zipf(1.1, size=shape) - 1, Vw - 1)].astype(np.uint32)
+
+
+def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches):
+    rng = np.random.RandomState(0)
+    M = B * num_batches
+    X = zipf_tokens(rng, Vw, (M, n))
+    full = engine(rng, B, Vw, Ve + N, d, n)
+    full.upload_dataset(C.SPLIT_TRAIN, X, y_int=rng.randint(0, Ve + N, M).astype(np.int32), w=np.ones(M, np.float32))
+    frozen = engine(rng, 1, Vw, Ve, d, n, inference_only=1)
+    fold = C.LlFoldIn(frozen, glorot(rng, (d, N)), None, B, 0.01)
+    frozen.close()
+    t_upload, _ = timed(lambda: fold.upload(X.astype(np.int32), rng.randint(0, N, M).astype(np.int32), None))
+    distinct = int(np.unique(X).size)
+    order = np.arange(steps, dtype=np.int64) % num_batches
+    full.train_batches(order)
+    fold.train_batches(order)
+    t_fold, t_full = [], []
+    for _ in range(repeats):
+        t_fold.append(timed(lambda: fold.train_batches(order))[0] / steps)
+        t_full.append(timed(lambda: full.train_batches(order))[0] / steps)
+    full.close()
+    fold.close()
+    rec = dict(setting=name, B=B, V_w=Vw, V_e=Ve, N=N, d=d, window=n, steps=steps, instances=M,
+               foldin_step_ms=[1e3 * t for t in t_fold], full_step_ms=[1e3 * t for t in t_full],
+               foldin_step_ms_median=1e3 * float(np.median(t_fold)), full_step_ms_median=1e3 * float(np.median(t_full)),
+               foldin_faster_in_every_alternation=bool(all(a < b for a, b in zip(t_fold, t_full))),
+               upload_ms=1e3 * t_upload, upload_instances=M, distinct_words=distinct, logit_cache_bytes=distinct * Ve * 4)
+    rec['speedup_median'] = rec['full_step_ms_median'] / rec['foldin_step_ms_median']
+    return rec
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--num_batches', type=int, default=8)
+    ap.add_argument('--settings', nargs='+', default=[s[0] for s in SETTINGS])
+    args = ap.parse_args(argv)
+    C.require_gpu()
+    out = dict(device=C.device_info(0), steps=[])
+    for s in SETTINGS:
+        if s[0] in args.settings:
+            rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches)
+            print(json.dumps(rec))
+            out['steps'].append(rec)
+            with open(args.out, 'w') as f:
+                json.dump(out, f, indent=1, sort_keys=True)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+
+
+if __name__ == '__main__':
+    sys.exit(main())
