@@ -28,6 +28,18 @@ model type: the word table and the trained columns of the output layer stay as t
 and an entry of b (sert_amd.foldin.LogLinearFoldIn) that learn with the model's own loss over all V_e + N entities.  The same
 command line; ``--num_negative_samples`` is not read (there is nothing to sample), ``--refresh`` is refused.  The output dump's
 predict function holds W (d, V_e + N) and b (V_e + N).
+
+With ``--label_distributions`` (loglinear dumps only) the fold-in learns from the loss the expert-finding recipe trains with,
+bin/train.py --type loglinear WITHOUT --one_hot_classes: ``y_train`` of ``--data`` is used as the sparse matrix of label
+distributions it is -- one row per instance over the entities of ``--new_meta`` -- and ``w_train`` as bin/train.py uses it.
+An entity id of ``--new_meta`` that ``--meta`` knows is then a frozen co-label, not an error: a new person's documents are
+mostly co-authored with people the model knows.  Such an id keeps its internal index and its column of W / b, bit for bit; its
+share of a document's label mass enters the new columns' gradient; its associations gain the new documents.  The unknown ids
+become columns V_e .. in the order of ``--new_meta`` (sert_amd.foldin.label_columns); if none is unknown there is nothing to
+fold in and the run is refused.
+
+    python bin/fold_in.py --label_distributions --meta meta --model model_15.bin --new_meta new_meta --data new.npz \\
+        --iterations 10 --model_output model_15_ext.bin --meta_output meta_ext
 """
 import argparse
 import logging
@@ -61,6 +73,12 @@ def build_parser():
                              'instances given, in place) instead of refused; the rest are new.  A refreshed row learns from '
                              'the instances given: to keep its old evidence, pass the entity\'s old documents along with '
                              'the new ones.')
+    parser.add_argument('--label_distributions', action='store_true', default=False,
+                        help='loglinear dumps only: learn from the label distributions of --data (y_train as the sparse matrix '
+                             'it is, as bin/train.py does without --one_hot_classes) instead of one instance per label.  Entity '
+                             'ids of --new_meta that --meta knows are accepted as frozen co-labels: they keep their index and '
+                             'their trained column, and their associations gain the new documents; the unknown ids become the '
+                             'new columns.  Refused if no id is unknown.')
     parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     return parser
@@ -85,7 +103,8 @@ def one_hot_training_set(path):
 def fold_in_loglinear(args):
     """A loglinear dump (namespace, LogLinearPredictFn, R_w): the new entities get columns of the output layer and biases of
     their own (sert_amd.foldin.LogLinearFoldIn) with the model's loss over all V_e + N entities; there are no negatives to
-    draw, so --num_negative_samples is not read.  --refresh is refused: trained columns do not learn here."""
+    draw, so --num_negative_samples is not read.  --refresh is refused: trained columns do not learn here.
+    --label_distributions: the instances keep their label rows, and ids the trained meta knows are frozen co-labels."""
     if args.refresh:
         raise RuntimeError('--refresh needs a vectorspace model: refreshing the trained columns of a loglinear model is not '
                            'supported.')
@@ -98,13 +117,22 @@ def fold_in_loglinear(args):
     new_index = new_meta[3]
     new_entity_ids = [new_index[e] for e in range(len(new_index))]
     associations = dict((e, new_meta[4].get(e, [])) for e in new_entity_ids)
-    # (refuses a known entity id before anything is computed)
-    extended_meta = foldin.extend_meta(meta, new_entity_ids, associations)
-
-    x, y, w = one_hot_training_set(args.data)
-    assert y.size == 0 or int(y.max()) < len(new_entity_ids)
     W, b = np.asarray(predict_fn.W), np.asarray(predict_fn.b)
-    new_W = models._glorot_uniform((W.shape[0], len(new_entity_ids)))       # as models.LanguageModel initialises W; b: zeros
+    if args.label_distributions:
+        # known ids are frozen co-labels at their trained index, unknown ones the new columns V_e ..
+        extended_meta, columns, added_ids = foldin.label_columns(meta, new_entity_ids, associations)
+        if not added_ids:
+            raise RuntimeError('nothing to fold in: %s knows every entity id of %s.' % (args.meta, args.new_meta))
+        (x, y, w), _ = training.load_data_sets(args.data)
+        assert y.shape[1] <= len(new_entity_ids)
+        y = foldin.remap_label_columns(y, columns, W.shape[1] + len(added_ids))
+    else:
+        # (refuses a known entity id before anything is computed)
+        extended_meta = foldin.extend_meta(meta, new_entity_ids, associations)
+        added_ids = new_entity_ids
+        x, y, w = one_hot_training_set(args.data)
+        assert y.size == 0 or int(y.max()) < len(new_entity_ids)
+    new_W = models._glorot_uniform((W.shape[0], len(added_ids)))       # as models.LanguageModel initialises W; b: zeros
     fold = foldin.LogLinearFoldIn(R_w, W, b, new_W, None, (x, y, w), batch_size=args.batch_size,
                                   regularization_lambda=args.regularization_lambda, window_size=meta[0].window_size,
                                   device=args.device)
@@ -123,7 +151,7 @@ def fold_in_loglinear(args):
     foldin.write_dump(args.model_output, foldin.extend_ll_dump(model_args, predict_fn, R_w, Wn, bn))
     foldin.write_meta(args.meta_output, extended_meta)
     logging.info('Saved the extended model "%s" (%d + %d entities) and its meta "%s".', args.model_output, W.shape[1],
-                 len(new_entity_ids), args.meta_output)
+                 len(added_ids), args.meta_output)
     fold.close()
 
 
@@ -140,6 +168,9 @@ def main(argv=None):
     if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:
         return fold_in_loglinear(args)
 
+    if args.label_distributions:
+        raise RuntimeError('--label_distributions needs a loglinear model: a vectorspace model learns from one entity per '
+                           'instance (NCE), with or without it.')
     model_args, predict_fn, R_w, R_e = load_model(args.model)
     if getattr(model_args, 'type', None) is not models.VectorSpaceLanguageModel:
         raise RuntimeError('a fold-in needs a model trained as vectorspace (found %r).' % (getattr(model_args, 'type', None),))

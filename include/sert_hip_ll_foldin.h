@@ -18,9 +18,20 @@
  * kernel over the cached logits and Adadelta on d N + N numbers -- no V_e-wide GEMM, no word-table update.  Every reduction is
  * order-fixed and there are no floating-point atomics: two handles with the same inputs hold the same bits.
  *
+ *
+ * Label rows.  The expert-finding recipe trains on label DISTRIBUTIONS (bin/train.py without --one_hot_classes: one CSR row per
+ * instance, loss_i = -sum_e Y_ie log clip(Q_ie)), and a new person's documents are mostly co-authored with people the model
+ * knows.  sert_ll_foldin_upload_csr takes such rows over all V_e + N columns: column e < V_e is trained entity e -- a label
+ * only, its parameters stay frozen, but its share of the label mass enters the new columns' gradient through the joint's
+ * normaliser and through r_t --, column V_e + j is new entity j.  The step is then, with Ydense the batch's rows densified to
+ * (B, V_e + N),
+ *     loss, grads, _ = LogLinearOracle(B, n, R_w, Wx, bx, lambda).loss_and_grads(X, Ydense, w)
+ * with the gradient, the returned loss and the update as above.  A label on a trained column costs a gather from the logit
+ * cache; the cache itself is the same.
+ *
  * The handle is an object of its own, like sert_foldin: it COPIES what it needs from the model when it is created and shares
  * no state with the model's step schedule.  Later training or destruction of the model does not change it.
- * Out of scope: refreshing trained columns, CSR label rows, data-parallel handles, window sizes above 32, a logit cache that
+ * Out of scope: refreshing trained columns, data-parallel handles, window sizes above 32, a logit cache that
  * spills or is recomputed per step.
  */
 #ifndef SERT_HIP_LL_FOLDIN_H
@@ -66,6 +77,16 @@ int sert_ll_foldin_destroy(sert_ll_foldin* f);
  * rows [iB, (i + 1)B); a trailing M mod B instances are never visited, as in training.  Replaces an earlier upload; the
  * optimiser state is kept. */
 int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M);
+/* The same with label ROWS: x, w, M, the batches, the trailing M mod B, the logit cache and max_cache_bytes exactly as above;
+ * the labels are a canonical CSR matrix (M, V_e + num_new) -- indptr (M + 1) starts at 0 and does not decrease; the columns
+ * of a row (indices) lie in [0, V_e + num_new) and are STRICTLY INCREASING; a row holds any number of entries from none (loss
+ * 0, no gradient) to V_e + num_new; the values (data) are what sert_upload_dataset takes for csr_data: arbitrary finite
+ * floats, a stored 0, rows that do not sum to 1; fewer than 2^31 entries.  Column e < V_e is trained entity e (a label only),
+ * column V_e + j new entity j.  Every fault is found on the host before anything is launched, with sert_upload_dataset's
+ * wording for csr_*; a refused upload keeps the earlier one.  An upload of either form replaces an upload of either form;
+ * the optimiser state is kept. */
+int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t* indptr, const int32_t* indices,
+                              const float* data, const float* w, int64_t M);
 /* number of complete batches of the upload, floor(M / B); < 0 on a null handle */
 int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f);
 
@@ -74,7 +95,8 @@ int sert_ll_foldin_train_batch(sert_ll_foldin* f, int64_t batch, float* loss_out
 /* `count` steps with ONE host synchronisation: the bits of the sert_ll_foldin_train_batch loop. */
 int sert_ll_foldin_train_batches(sert_ll_foldin* f, const int64_t* batches, int64_t count, float* losses_out);
 
-/* LogLinearOracle.eval_loss(X, V_e + y) on the extended model for batch `batch`: unweighted, unregularised; no state changes. */
+/* LogLinearOracle.eval_loss(X, V_e + y) -- label rows: eval_loss(X, Ydense) -- on the extended model for batch `batch`:
+ * unweighted, unregularised; no state changes. */
 int sert_ll_foldin_eval_batch(sert_ll_foldin* f, int64_t batch, float* loss_out);
 
 /* which = SERT_LL_FOLDIN_W / _B: Wn (d, num_new) row-major / bn (num_new); _ACCU_* / _DELTA_*: Adadelta's two accumulators of

@@ -87,8 +87,8 @@ EXPORTS_FOLDIN = [
 FOLDIN_ROWS, FOLDIN_M, FOLDIN_V = 0, 1, 2
 # ... and include/sert_hip_ll_foldin.h, which sert_hip.h includes as well (the same for a trained loglinear model)
 EXPORTS_LL_FOLDIN = [
-    'sert_ll_foldin_create', 'sert_ll_foldin_destroy', 'sert_ll_foldin_upload', 'sert_ll_foldin_num_batches',
-    'sert_ll_foldin_train_batch', 'sert_ll_foldin_train_batches', 'sert_ll_foldin_eval_batch',
+    'sert_ll_foldin_create', 'sert_ll_foldin_destroy', 'sert_ll_foldin_upload', 'sert_ll_foldin_upload_csr',
+    'sert_ll_foldin_num_batches', 'sert_ll_foldin_train_batch', 'sert_ll_foldin_train_batches', 'sert_ll_foldin_eval_batch',
     'sert_ll_foldin_get_tensor', 'sert_ll_foldin_set_tensor',
 ]
 LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B = 0, 1, 2, 3, 4, 5
@@ -229,6 +229,7 @@ def load():
     lib.sert_ll_foldin_create.argtypes = [vp, i32, fp, fp, ctypes.POINTER(SertLlFoldInConfig), ctypes.POINTER(vp)]
     lib.sert_ll_foldin_destroy.argtypes = [vp]
     lib.sert_ll_foldin_upload.argtypes = [vp, fp, fp, fp, i64]
+    lib.sert_ll_foldin_upload_csr.argtypes = [vp, fp, fp, fp, fp, fp, i64]
     lib.sert_ll_foldin_num_batches.argtypes = [vp]
     lib.sert_ll_foldin_num_batches.restype = i64
     lib.sert_ll_foldin_train_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
@@ -1294,6 +1295,25 @@ class LlFoldIn(object):
             if w.shape != y.shape:
                 raise SertError('w must be (M,)')
         check(self._lib.sert_ll_foldin_upload(self._h, x.ctypes.data, y.ctypes.data, _addr(w), x.shape[0]))
+
+    def upload_csr(self, x, indptr, indices, data, w=None):
+        """Label ROWS: a canonical CSR matrix (M, num_entities + num_new) -- column e < num_entities is trained entity e (a
+        label only), column num_entities + j new entity j (sert_ll_foldin_upload_csr, which validates the rows)."""
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.window_size or indptr.shape != (x.shape[0] + 1,):
+            raise SertError('x must be (M, window_size) and indptr (M + 1,)')
+        # (what the library cannot see: the arrays must be as long as indptr says before it reads them)
+        if indices.ndim != 1 or data.shape != indices.shape or (indptr.size and indices.size < indptr.max()):
+            raise SertError('indices and data must be (nnz,) with nnz >= max(indptr)')
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (x.shape[0],):
+                raise SertError('w must be (M,)')
+        check(self._lib.sert_ll_foldin_upload_csr(self._h, x.ctypes.data, indptr.ctypes.data, _addr(indices), _addr(data),
+                                                  _addr(w), x.shape[0]))
 
     def num_batches(self):
         return int(self._lib.sert_ll_foldin_num_batches(self._h))

@@ -14,7 +14,11 @@ struct sert_ll_foldin {
     float *g_w = nullptr, *g_b = nullptr;
     // ---- the upload ----
     int64_t M = 0, D = 0;                // instances; distinct words
-    int32_t* y = nullptr;
+    int32_t* y = nullptr;                // one label per instance (sert_ll_foldin_upload), or ...
+    int64_t* indptr = nullptr;           // ... label rows (sert_ll_foldin_upload_csr): (M + 1) offsets, ...
+    int32_t* indices = nullptr;          // ... (nnz) columns in [0, V_e + N), strictly increasing per row, ...
+    float* data = nullptr;               // ... (nnz) values
+    float* labfix = nullptr;             // label rows: per entry Q_e dQ_e of the step (nnz)
     float* w = nullptr;
     float* G = nullptr;                  // (D, d) = R_w[distinct words]
     float* Zold = nullptr;               // (D, V_e) the logit cache
@@ -35,10 +39,11 @@ struct sert_ll_foldin {
 };
 
 static void llf_free_upload(sert_ll_foldin* f) {
-    for (void* p : {(void*)f->y, (void*)f->w, (void*)f->G, (void*)f->Zold, (void*)f->stat, (void*)f->Lb, (void*)f->tok, (void*)f->wptr,
-                    (void*)f->wpos, (void*)f->Gb, (void*)f->Zn, (void*)f->lse, (void*)f->dZ, (void*)f->dZu, (void*)f->part})
+    for (void* p : {(void*)f->y, (void*)f->indptr, (void*)f->indices, (void*)f->data, (void*)f->labfix, (void*)f->w, (void*)f->G,
+                    (void*)f->Zold, (void*)f->stat, (void*)f->Lb, (void*)f->tok, (void*)f->wptr, (void*)f->wpos, (void*)f->Gb, (void*)f->Zn, (void*)f->lse, (void*)f->dZ, (void*)f->dZu, (void*)f->part})
         (void)hipFree(p);
-    f->y = nullptr; f->w = nullptr; f->G = nullptr; f->Zold = nullptr; f->stat = nullptr; f->Lb = nullptr; f->tok = nullptr;
+    f->y = nullptr; f->indptr = nullptr; f->indices = nullptr; f->data = nullptr; f->labfix = nullptr;
+    f->w = nullptr; f->G = nullptr; f->Zold = nullptr; f->stat = nullptr; f->Lb = nullptr; f->tok = nullptr;
     f->wptr = nullptr; f->wpos = nullptr; f->Gb = nullptr; f->Zn = nullptr; f->lse = nullptr; f->dZ = nullptr; f->dZu = nullptr;
     f->part = nullptr;
     f->lb_off.clear(); f->ptr_off.clear(); f->U.clear();
@@ -143,15 +148,20 @@ static void llf_dw_splits(const sert_ll_foldin* f, int64_t rows, int* splits, in
     *splits = sp; *kper = kp;
 }
 
-int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
-    refresh_gemm_choice();
-    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
-    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+// The labels of an upload, already validated: y (one per instance), or the CSR rows (indptr, indices, data).
+struct LlfLabels {
+    const int32_t* y;
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float* data;
+};
+
+// What an upload of either label form does once its labels are known to be good: the tokens are validated; then the distinct
+// words, the per-batch word lists (Lb, tok, wptr / wpos), the logit cache with llf_row_stat, and the copies of those lists, of
+// the labels and of w.  Nothing of the handle is touched before every host-side check has passed.
+static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab, const float* w, int64_t M) {
     const int n = f->n, d = f->d, Ve = f->Ve, N = f->N, B = f->cfg.batch_size;
-    if (M * n > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in tokens");
-    // host-side validation: no kernel is launched on bad ids
-    for (int64_t i = 0; i < M; ++i)
-        if (y[i] < 0 || y[i] >= N) SERT_FAIL("fold-in label out of range [0, num_new)");
+    const int64_t nnz = (lab.y || M == 0) ? 0 : lab.indptr[M];      // (M == 0: an empty upload of either form)
     for (int64_t i = 0; i < M * n; ++i)
         if (x[i] < 0 || x[i] >= f->Vw) SERT_FAIL("token id out of range [0, vocab_size)");
     // ---- the distinct words D of x (sorted) and the row of the cache of every token ----
@@ -205,7 +215,20 @@ int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y,
             f->Zold = nullptr;
             SERT_FAIL("the logit cache of this upload needs " + std::to_string(need) + " bytes, which cannot be allocated");
         }
-        SERT_TRY(dmalloc(&f->y, (size_t)M));
+        if (lab.y) {
+            SERT_TRY(dmalloc(&f->y, (size_t)M));
+            SERT_HIP(hipMemcpyAsync(f->y, lab.y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        } else {
+            SERT_TRY(dmalloc(&f->indptr, (size_t)M + 1));
+            SERT_TRY(dmalloc(&f->indices, (size_t)std::max<int64_t>(1, nnz)));
+            SERT_TRY(dmalloc(&f->data, (size_t)std::max<int64_t>(1, nnz)));
+            SERT_TRY(dmalloc(&f->labfix, (size_t)std::max<int64_t>(1, nnz)));
+            SERT_HIP(hipMemcpyAsync(f->indptr, lab.indptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (nnz) {
+                SERT_HIP(hipMemcpyAsync(f->indices, lab.indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                SERT_HIP(hipMemcpyAsync(f->data, lab.data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, s));
+            }
+        }
         SERT_TRY(dmalloc(&f->w, (size_t)M));
         SERT_TRY(dmalloc(&f->G, (size_t)D * d));
         SERT_TRY(dmalloc(&f->stat, (size_t)D));
@@ -223,7 +246,6 @@ int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y,
         SERT_TRY(dmalloc(&f->dZu, (size_t)Umax * N));
         SERT_TRY(dmalloc(&f->part, (size_t)max_splits * ((size_t)d * N + N)));
         const std::vector<float> ones(w ? 0 : (size_t)M, 1.0f);
-        SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
         SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
         SERT_HIP(hipMemcpyAsync(dwords, words.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!Lb.empty()) SERT_HIP(hipMemcpyAsync(f->Lb, Lb.data(), Lb.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -245,7 +267,7 @@ int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y,
         }
         launch(llf_row_stat, dim3((unsigned)D), dim3(256), 0, s, (const float*)f->Zold, Ve, f->stat);
         SERT_HIP(hipGetLastError());
-        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w and the host lists are borrowed for the call only)
+        SERT_HIP(hipStreamSynchronize(s));     // (x, the labels, w and the host lists are borrowed for the call only)
         return 0;
     };
     const int rc = body();
@@ -260,6 +282,52 @@ int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y,
     f->M = M; f->D = D;
     f->lb_off.swap(lb_off); f->ptr_off.swap(ptr_off); f->U.swap(Us);
     return 0;
+}
+
+static int llf_upload_check_sizes(sert_ll_foldin* f, int64_t M) {
+    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+    if (M * f->n > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in tokens");
+    return 0;
+}
+
+int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
+    SERT_TRY(llf_upload_check_sizes(f, M));
+    // host-side validation: no kernel is launched on bad ids
+    for (int64_t i = 0; i < M; ++i)
+        if (y[i] < 0 || y[i] >= f->N) SERT_FAIL("fold-in label out of range [0, num_new)");
+    return llf_upload(f, x, LlfLabels{y, nullptr, nullptr, nullptr}, w, M);
+}
+
+int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t* indptr, const int32_t* indices,
+                              const float* data, const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !indptr))) SERT_FAIL("bad argument");
+    SERT_TRY(llf_upload_check_sizes(f, M));
+    // host-side validation, worded as sert_upload_dataset words it for csr_*: no kernel is launched on a bad row
+    if (M > 0) {
+        const int64_t cols = (int64_t)f->Ve + f->N;
+        if (indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
+        for (int64_t r = 0; r < M; ++r)
+            if (indptr[r + 1] < indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
+        const int64_t nnz = indptr[M];
+        if (nnz > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 label entries");
+        if (nnz > 0 && (!indices || !data)) SERT_FAIL("bad argument");
+        for (int64_t i = 0; i < nnz; ++i)
+            if (indices[i] < 0 || indices[i] >= cols) SERT_FAIL("label column out of range [0, V_e + num_new) in csr_indices");
+        // strictly increasing columns per row: llf_row_csr looks a new column's entry up by bisection and adds a row's entries
+        // from different threads without atomics
+        for (int64_t r = 0; r < M; ++r)
+            for (int64_t i = indptr[r] + 1; i < indptr[r + 1]; ++i)
+                if (indices[i] <= indices[i - 1]) {
+                    char msg[160];
+                    snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
+                             (long long)r, (int)indices[i]);
+                    SERT_FAIL(msg);
+                }
+    }
+    return llf_upload(f, x, LlfLabels{nullptr, indptr, indices, data}, w, M);
 }
 
 int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f) { return f ? f->M / f->cfg.batch_size : -1; }
@@ -296,7 +364,22 @@ static int llf_forward(sert_ll_foldin* f, int64_t batch, bool train) {
             launch(evaluation, dim3(B), dim3(256), 0, s, (const float*)f->Zold, (const float*)f->Zn, (const float*)f->lse, Lb, tok,
                    (const int32_t*)(f->y + row0), (const float*)nullptr, f->rowloss, f->dZ, n, f->Ve, N, 1.0f / (float)B);
     };
-    if (n <= 8) go(llf_row<true, 8>, llf_row<false, 8>);
+    // label rows (sert_ll_foldin_upload_csr): the same launch shape, the batch's slice of indptr
+    auto go_csr = [&](auto training, auto evaluation) {
+        if (train)
+            launch(training, dim3(B), dim3(256), 0, s, (const float*)f->Zold, (const float*)f->Zn, (const float*)f->lse, Lb, tok,
+                   (const int64_t*)(f->indptr + row0), (const int32_t*)f->indices, (const float*)f->data, (const float*)(f->w + row0),
+                   f->rowloss, f->labfix, f->dZ, n, f->Ve, N, 1.0f / (float)B);
+        else
+            launch(evaluation, dim3(B), dim3(256), 0, s, (const float*)f->Zold, (const float*)f->Zn, (const float*)f->lse, Lb, tok,
+                   (const int64_t*)(f->indptr + row0), (const int32_t*)f->indices, (const float*)f->data, (const float*)nullptr,
+                   f->rowloss, (float*)nullptr, f->dZ, n, f->Ve, N, 1.0f / (float)B);
+    };
+    if (f->indptr) {
+        if (n <= 8) go_csr(llf_row_csr<true, 8>, llf_row_csr<false, 8>);
+        else if (n <= 16) go_csr(llf_row_csr<true, 16>, llf_row_csr<false, 16>);
+        else go_csr(llf_row_csr<true, 32>, llf_row_csr<false, 32>);
+    } else if (n <= 8) go(llf_row<true, 8>, llf_row<false, 8>);
     else if (n <= 16) go(llf_row<true, 16>, llf_row<false, 16>);
     else go(llf_row<true, 32>, llf_row<false, 32>);
     return 0;

@@ -139,6 +139,142 @@ __global__ __launch_bounds__(256) void llf_row(const float* __restrict__ Zold, c
     }
 }
 
+// The row kernel for label ROWS (sert_ll_foldin_upload_csr): instance i's labels are the CSR row indptr[i] .. indptr[i + 1] of
+// (indices, data) over the V_e + N columns, strictly increasing; column e < V_e is frozen entity e -- a label only --, column
+// V_e + j new entity j.  The launch shape, the LDS tables and pass A are llf_row's; the label is no longer one column:
+//   pass A   (M, S) of the joint over all V_e + N columns
+//   labels   thread tid takes entries l0 + tid, l0 + tid + 256, ..: J_e gathered from the cache (e < V_e) or from logpn,
+//            q = exp(J_e - M) / S, ll_label_term; the row's loss and s = sum_l Q_l dQ_l in the fixed tree.  TRAIN: the entry's
+//            Q dQ goes to labfix[l] (per entry of the upload, as the model's: no cap on a row's labels) and its share
+//            mask_t Q dQ of r_t to the owning thread's registers -- frozen and new columns alike
+//   pass B   (TRAIN) the dense part dJ_e = -Q_e s of every column into r_t, then dZ[token, j] for the N new columns with
+//            dJ_j = -Q_j s + labfix of the row's entry at column V_e + j, where it has one: the columns are sorted, so the
+//            new-side entries are the row's tail [lt, l1), and the thread of column j looks its entry up by bisection --
+//            one writer per element, no order to fix
+// indptr is the batch's (indptr + row0); its values are offsets into the UPLOAD's indices / data / labfix.
+template <bool TRAIN, int NMAX>
+__global__ __launch_bounds__(256) void llf_row_csr(const float* __restrict__ Zold, const float* __restrict__ logpn,
+                                                   const float* __restrict__ lse, const int32_t* __restrict__ Lb,
+                                                   const int32_t* __restrict__ tok, const int64_t* __restrict__ indptr,
+                                                   const int32_t* __restrict__ indices, const float* __restrict__ data,
+                                                   const float* __restrict__ w, float* __restrict__ rowloss, float* labfix,
+                                                   float* __restrict__ dZ, int n, int Ve, int N, float inv_batch) {
+    __shared__ float red[4];
+    __shared__ unsigned long long s_off[32];
+    __shared__ unsigned s_new[32];
+    __shared__ float s_lse[32], s_r[32];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const float LOGLO = logf(SERT_CLIP_LO), LOGHI = logf(SERT_CLIP_HI);
+    if (tid < n) {
+        const int u = tok[(size_t)i * n + tid];
+        s_off[tid] = (unsigned long long)Lb[u] * (unsigned long long)Ve;
+        s_new[tid] = (unsigned)u * (unsigned)N;
+        s_lse[tid] = lse[u];
+    }
+    __syncthreads();
+    const int64_t l0 = indptr[i], l1 = indptr[i + 1];
+    // ---- pass A ----
+    float mx = -INFINITY, se = 0.f;
+    auto online = [&](float a) {
+        if (a > mx) { se = se * expf(mx - a) + 1.0f; mx = a; }
+        else se += expf(a - mx);
+    };
+    for (int e = tid; e < Ve; e += 256) {
+        float a = 0.f;
+        for (int t = 0; t < n; ++t) a += clip_logp(Zold[s_off[t] + e] - s_lse[t], LOGLO, LOGHI);
+        online(a);
+    }
+    for (int j = tid; j < N; j += 256) {
+        float a = 0.f;
+        for (int t = 0; t < n; ++t) a += clip_logp(logpn[s_new[t] + j], LOGLO, LOGHI);
+        online(a);
+    }
+    const float M = block_max_256(mx, red);
+    const float S = block_sum_256(se * expf(mx - M), red);
+    const float wi = w ? w[i] : 1.0f;
+    const float g = wi * inv_batch;
+    // ---- the label entries ----
+    float r[NMAX];
+#pragma unroll
+    for (int t = 0; t < NMAX; ++t) r[t] = 0.f;
+    float loss = 0.f, sdq = 0.f;
+    for (int64_t l = l0 + tid; l < l1; l += 256) {
+        const int e = indices[l];
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) {
+                lp[t] = e < Ve ? Zold[s_off[t] + e] - s_lse[t] : logpn[s_new[t] + (e - Ve)];
+                a += clip_logp(lp[t], LOGLO, LOGHI);
+            }
+        float ylog, qdq;
+        ll_label_term<TRAIN>(expf(a - M) / S, data[l], g, ylog, qdq);
+        loss -= ylog;
+        if (TRAIN) {
+            sdq += qdq;
+            labfix[l] = qdq;
+#pragma unroll
+            for (int t = 0; t < NMAX; ++t)
+                if (t < n) r[t] += ll_masked(lp[t], qdq, LOGLO, LOGHI);
+        }
+    }
+    loss = block_sum_256(loss, red);
+    if (tid == 0) rowloss[i] = wi * loss;
+    if (!TRAIN) return;
+    sdq = block_sum_256(sdq, red);
+    // ---- pass B ----
+    for (int e = tid; e < Ve; e += 256) {
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) { lp[t] = Zold[s_off[t] + e] - s_lse[t]; a += clip_logp(lp[t], LOGLO, LOGHI); }
+        const float dj = -(expf(a - M) / S) * sdq;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) r[t] += ll_masked(lp[t], dj, LOGLO, LOGHI);
+    }
+    for (int j = tid; j < N; j += 256) {
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) { lp[t] = logpn[s_new[t] + j]; a += clip_logp(lp[t], LOGLO, LOGHI); }
+        const float dj = -(expf(a - M) / S) * sdq;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) r[t] += ll_masked(lp[t], dj, LOGLO, LOGHI);
+    }
+#pragma unroll
+    for (int t = 0; t < NMAX; ++t) {
+        if (t < n) {               // (n is uniform: every thread takes the same barriers)
+            const float rt = block_sum_256(r[t], red);
+            if (tid == 0) s_r[t] = rt;
+        }
+    }
+    __syncthreads();               // (s_r; and every labfix entry of the row, written above by its owner, is visible)
+    // the row's tail: its first entry on a new column (the same bisection in every thread)
+    int64_t lt = l0;
+    for (int64_t hi = l1; lt < hi;) {
+        const int64_t mid = lt + ((hi - lt) >> 1);
+        if (indices[mid] < Ve) lt = mid + 1; else hi = mid;
+    }
+    for (int j = tid; j < N; j += 256) {
+        float lp[NMAX], a = 0.f;
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) { lp[t] = logpn[s_new[t] + j]; a += clip_logp(lp[t], LOGLO, LOGHI); }
+        float dj = -(expf(a - M) / S) * sdq;
+        int64_t lo = lt;
+        for (int64_t hi = l1; lo < hi;) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (indices[mid] < Ve + j) lo = mid + 1; else hi = mid;
+        }
+        if (lo < l1 && indices[lo] == Ve + j) dj += labfix[lo];
+#pragma unroll
+        for (int t = 0; t < NMAX; ++t)
+            if (t < n) dZ[((size_t)i * n + t) * N + j] = ll_dz(lp[t], dj, s_r[t], LOGLO, LOGHI);
+    }
+}
+
 // dZu[u, :] = the sum of the dZ rows of word u's tokens, in ascending token order (ptr / pos: the batch's CSR of token
 // positions per word, built on the host at upload).  One thread per (u, j).
 __global__ __launch_bounds__(256) void llf_word_sum(const float* __restrict__ dZ, const int32_t* __restrict__ ptr,

@@ -11,6 +11,7 @@ import logging
 import pickle
 
 import numpy as np
+import scipy.sparse
 
 from sert_amd import _capi
 from sert_amd import models
@@ -176,7 +177,12 @@ class LogLinearFoldIn(models.ModelInterface):
     training_set: (x (M, window_size) token ids of the TRAINED vocabulary, y (M,) in [0, N), w (M,) weights or None).
     New entity e becomes column V_e + e.  ``new_W_init`` None: N = y.max() + 1 columns drawn with
     ``_glorot_uniform((d, N))``; ``new_b_init`` None: zeros -- as models.LanguageModel initialises its output layer.  The
-    batch size and lambda are the fold-in's own.  ``max_cache_bytes``: a cap on the logit cache of the upload (0: none)."""
+    batch size and lambda are the fold-in's own.  ``max_cache_bytes``: a cap on the logit cache of the upload (0: none).
+
+    Label rows: y may be a ``scipy.sparse`` matrix (M, V_e + N) instead -- the label DISTRIBUTIONS the model was trained on
+    without --one_hot_classes.  Column e < V_e is trained entity e: a label only (a co-author the model knows), its column of
+    W stays frozen; column V_e + j is new entity j.  The matrix is brought to canonical CSR (``tocsr``, ``sum_duplicates``,
+    ``sort_indices``); with ``new_W_init`` None, N = y.shape[1] - V_e, which must be at least 1."""
 
     #: batches issued to the device before their losses are read back
     steps_per_sync = 1
@@ -184,15 +190,32 @@ class LogLinearFoldIn(models.ModelInterface):
     def __init__(self, R_w, W, b, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, window_size,
                  device=0, max_cache_bytes=0, _engine=None):
         super(LogLinearFoldIn, self).__init__(batch_size)
-        x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
+        x = np.asarray(training_set[0])
         w = training_set[2] if len(training_set) > 2 else None
-        assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
-        word_dim = int(np.shape(W)[0])
-        if new_W_init is None:
-            if not y.size:
-                raise RuntimeError('no fold-in instances and no initial columns: nothing says how many entities are new')
-            new_W_init = models._glorot_uniform((word_dim, int(y.max()) + 1))
+        word_dim, num_entities = int(np.shape(W)[0]), int(np.shape(W)[1])
+        rows = scipy.sparse.issparse(training_set[1])
+        if rows:
+            # label rows: canonical CSR over the V_e + N columns (a copy: the caller's matrix is not modified)
+            y = scipy.sparse.csr_matrix(training_set[1], dtype=np.float32, copy=True)
+            y.sum_duplicates()
+            y.sort_indices()
+            assert x.ndim == 2 and x.shape[1] == window_size and y.shape[0] == x.shape[0]
+            if new_W_init is None:
+                if y.shape[1] - num_entities < 1:
+                    raise RuntimeError('label rows of %d columns on a model of %d entities: no column is new'
+                                       % (y.shape[1], num_entities))
+                new_W_init = models._glorot_uniform((word_dim, y.shape[1] - num_entities))
+        else:
+            y = np.asarray(training_set[1])
+            assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+            if new_W_init is None:
+                if not y.size:
+                    raise RuntimeError('no fold-in instances and no initial columns: nothing says how many entities are new')
+                new_W_init = models._glorot_uniform((word_dim, int(y.max()) + 1))
         new_W_init = np.ascontiguousarray(new_W_init, dtype=np.float32)
+        if rows and y.shape[1] != num_entities + new_W_init.shape[1]:
+            raise RuntimeError('label rows must have V_e + N = %d + %d columns, not %d'
+                               % (num_entities, new_W_init.shape[1], y.shape[1]))
         self.window_size = int(window_size)
         self.num_new = int(new_W_init.shape[1])
         self.num_entities = int(np.shape(W)[1])
@@ -217,9 +240,13 @@ class LogLinearFoldIn(models.ModelInterface):
         finally:
             if owned:
                 engine.close()      # (the handle copied what it needs)
-        self._foldin.upload(x, y, w)
-        logging.info('Folding in %d new entities (columns %d .. %d) on %d instances.', self.num_new, self.num_entities,
-                     self.num_entities + self.num_new - 1, self.training_num_instances)
+        if rows:
+            self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
+        else:
+            self._foldin.upload(x, y, w)
+        logging.info('Folding in %d new entities (columns %d .. %d) on %d instances%s.', self.num_new, self.num_entities,
+                     self.num_entities + self.num_new - 1, self.training_num_instances,
+                     ' with %d label entries' % y.nnz if rows else '')
 
     @classmethod
     def from_model(cls, model, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, max_cache_bytes=0):
@@ -366,6 +393,29 @@ def merge_meta(meta, entity_ids, associations=None):
     for entity_id, documents in (associations or {}).items():
         merged[entity_id] = list(merged.get(entity_id, [])) + list(documents)
     return [args, words, tokens, extended, merged], np.array(refreshed, dtype=np.int32), new_ids, slots
+
+
+def label_columns(meta, entity_ids, associations=None):
+    """The columns of label rows over the entities of a new documents' meta (bin/fold_in.py --label_distributions).
+    ``entity_ids[k]`` is entity k of that meta: an id the trained meta knows maps to its trained internal index -- a frozen
+    co-label --, an unknown one to V_e + its position among the unknown ones.  ``associations`` (entity id -> document
+    ids) are added to either kind.  -> (the five pickles of the merged meta, columns (len(entity_ids),) int32, the new ids
+    in column order).  All of it is merge_meta's: a known id is what it calls refreshed."""
+    merged, known, new_ids, slots = merge_meta(meta, entity_ids, associations)
+    V_e = len(meta[3])
+    columns = np.concatenate([known, V_e + np.arange(len(new_ids), dtype=np.int32)]).astype(np.int32)[slots]
+    return merged, columns.reshape(-1), new_ids
+
+
+def remap_label_columns(y, columns, num_columns):
+    """The sparse label matrix ``y`` (M, len(columns)) with column k moved to ``columns[k]`` of ``num_columns``: canonical CSR."""
+    y = scipy.sparse.coo_matrix(y)
+    columns = np.asarray(columns, dtype=np.int64)
+    assert y.shape[1] <= columns.size and (columns.size == 0 or columns.max() < num_columns)
+    out = scipy.sparse.csr_matrix((y.data.astype(np.float32), (y.row, columns[y.col])), shape=(y.shape[0], num_columns))
+    out.sum_duplicates()
+    out.sort_indices()
+    return out
 
 
 def refresh_dump(args, predict_fn, R_w, R_e, refresh, refreshed_rows, new_rows):

@@ -9,6 +9,10 @@ d, on the same Zipfian tokens.  One warm-up pass of each, then --repeats alterna
 clock around a call that ends in its one host synchronisation.  The one-time cost of the fold-in's upload
 (sert_ll_foldin_upload: host validation and word lists, copies, the logit cache GEMM over the distinct words, the row pass) is
 timed apart, with the size of the cache.
+
+With --labels K the same process also times the fold-in step on label ROWS (sert_ll_foldin_upload_csr): K entries per
+instance, K // 2 of them on trained columns and the rest on new ones, values 1 / K, on a second handle over the same tokens --
+alternating with the other two, so that the row step stands beside the integer-label step of the same process.
 """
 import argparse
 import json
@@ -52,7 +56,18 @@ def zipf_tokens(rng, Vw, shape):
     return rng.permutation(Vw)[np.minimum(rng.zipf(1.1, size=shape) - 1, Vw - 1)].astype(np.uint32)
 
 
-def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches):
+def label_rows(rng, M, Ve, N, K):
+    """(indptr, indices, data) of M rows with K entries: K // 2 distinct trained columns, then K - K // 2 distinct new ones."""
+    kt = K // 2
+    kn = K - kt
+    assert 0 <= kt <= Ve and 1 <= kn <= N
+    # (k distinct sorted columns of V: sorted draws from [0, V - k] plus 0 .. k - 1)
+    draw = lambda V, k: np.sort(rng.randint(0, V - k + 1, (M, k)), axis=1) + np.arange(k)
+    cols = np.concatenate([draw(Ve, kt), Ve + draw(N, kn)], axis=1).astype(np.int32)
+    return np.arange(M + 1, dtype=np.int64) * K, cols.reshape(-1), np.full(M * K, 1.0 / K, np.float32)
+
+
+def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches, labels=0):
     rng = np.random.RandomState(0)
     M = B * num_batches
     X = zipf_tokens(rng, Vw, (M, n))
@@ -60,15 +75,22 @@ def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches):
     full.upload_dataset(C.SPLIT_TRAIN, X, y_int=rng.randint(0, Ve + N, M).astype(np.int32), w=np.ones(M, np.float32))
     frozen = engine(rng, 1, Vw, Ve, d, n, inference_only=1)
     fold = C.LlFoldIn(frozen, glorot(rng, (d, N)), None, B, 0.01)
+    rows = C.LlFoldIn(frozen, glorot(rng, (d, N)), None, B, 0.01) if labels else None
     frozen.close()
     t_upload, _ = timed(lambda: fold.upload(X.astype(np.int32), rng.randint(0, N, M).astype(np.int32), None))
     distinct = int(np.unique(X).size)
     order = np.arange(steps, dtype=np.int64) % num_batches
     full.train_batches(order)
     fold.train_batches(order)
-    t_fold, t_full = [], []
+    t_fold, t_full, t_rows = [], [], []
+    if rows is not None:
+        indptr, indices, data = label_rows(rng, M, Ve, N, labels)
+        t_upload_rows, _ = timed(lambda: rows.upload_csr(X.astype(np.int32), indptr, indices, data, None))
+        rows.train_batches(order)
     for _ in range(repeats):
         t_fold.append(timed(lambda: fold.train_batches(order))[0] / steps)
+        if rows is not None:
+            t_rows.append(timed(lambda: rows.train_batches(order))[0] / steps)
         t_full.append(timed(lambda: full.train_batches(order))[0] / steps)
     full.close()
     fold.close()
@@ -78,6 +100,11 @@ def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches):
                foldin_faster_in_every_alternation=bool(all(a < b for a, b in zip(t_fold, t_full))),
                upload_ms=1e3 * t_upload, upload_instances=M, distinct_words=distinct, logit_cache_bytes=distinct * Ve * 4)
     rec['speedup_median'] = rec['full_step_ms_median'] / rec['foldin_step_ms_median']
+    if rows is not None:
+        rows.close()
+        rec.update(labels_per_row=labels, trained_labels_per_row=labels // 2, rows_step_ms=[1e3 * t for t in t_rows],
+                   rows_step_ms_median=1e3 * float(np.median(t_rows)), rows_upload_ms=1e3 * t_upload_rows)
+        rec['rows_over_integer_median'] = rec['rows_step_ms_median'] / rec['foldin_step_ms_median']
     return rec
 
 
@@ -88,12 +115,14 @@ def main(argv=None):
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--num_batches', type=int, default=8)
     ap.add_argument('--settings', nargs='+', default=[s[0] for s in SETTINGS])
+    ap.add_argument('--labels', type=int, default=0,
+                    help='K > 0: also time the step on label rows of K entries, K // 2 of them trained (sert_ll_foldin_upload_csr)')
     args = ap.parse_args(argv)
     C.require_gpu()
     out = dict(device=C.device_info(0), steps=[])
     for s in SETTINGS:
         if s[0] in args.settings:
-            rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches)
+            rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches, labels=args.labels)
             print(json.dumps(rec))
             out['steps'].append(rec)
             with open(args.out, 'w') as f:
