@@ -26,8 +26,8 @@ its old evidence, pass the entity's old documents along with the new ones.
 A dump of a LOGLINEAR model (bin/train.py --type loglinear: expert finding) takes a path of its own, chosen by the dump's
 model type: the word table and the trained columns of the output layer stay as they are, each new entity gets a column of W
 and an entry of b (sert_amd.foldin.LogLinearFoldIn) that learn with the model's own loss over all V_e + N entities.  The same
-command line; ``--num_negative_samples`` is not read (there is nothing to sample), ``--refresh`` is refused.  The output dump's
-predict function holds W (d, V_e + N) and b (V_e + N).
+command line; ``--num_negative_samples`` is not read (there is nothing to sample), ``--refresh`` is refused (see
+``--unfreeze_known``).  The output dump's predict function holds W (d, V_e + N) and b (V_e + N).
 
 With ``--label_distributions`` (loglinear dumps only) the fold-in learns from the loss the expert-finding recipe trains with,
 bin/train.py --type loglinear WITHOUT --one_hot_classes: ``y_train`` of ``--data`` is used as the sparse matrix of label
@@ -40,6 +40,17 @@ fold in and the run is refused.
 
     python bin/fold_in.py --label_distributions --meta meta --model model_15.bin --new_meta new_meta --data new.npz \\
         --iterations 10 --model_output model_15_ext.bin --meta_output meta_ext
+
+With ``--unfreeze_known`` (loglinear dumps only) an entity id of ``--new_meta`` that ``--meta`` knows is neither refused nor
+frozen: the person GAINED documents, and their column of W and their bias learn too, in place -- they keep their internal
+index, the output dump has their column and bias replaced and the really new entities' appended (V_e is unchanged when nothing
+is new), every other column keeps its bits, and the output meta has the associations merged (sert_amd.foldin.merge_meta).
+Without ``--label_distributions`` the instances are one per label, as above; with it the label rows are used as they are and
+every known id among their columns learns.  A refreshed column starts from its trained value and learns from the instances
+given: to keep its old evidence, pass the entity's old documents along with the new ones.
+
+    python bin/fold_in.py --unfreeze_known --label_distributions --meta meta --model model_15.bin --new_meta new_meta \\
+        --data new.npz --iterations 10 --model_output model_15_ref.bin --meta_output meta_ref
 """
 import argparse
 import logging
@@ -79,6 +90,11 @@ def build_parser():
                              'ids of --new_meta that --meta knows are accepted as frozen co-labels: they keep their index and '
                              'their trained column, and their associations gain the new documents; the unknown ids become the '
                              'new columns.  Refused if no id is unknown.')
+    parser.add_argument('--unfreeze_known', action='store_true', default=False,
+                        help='loglinear dumps only: entity ids of --new_meta that --meta knows are neither refused nor frozen '
+                             'co-labels -- their trained columns of W and their biases learn from the instances given, in place; '
+                             'the rest are new (none need be).  A refreshed column learns from the instances given: to keep its '
+                             'old evidence, pass the entity\'s old documents along with the new ones.')
     parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     return parser
@@ -103,11 +119,12 @@ def one_hot_training_set(path):
 def fold_in_loglinear(args):
     """A loglinear dump (namespace, LogLinearPredictFn, R_w): the new entities get columns of the output layer and biases of
     their own (sert_amd.foldin.LogLinearFoldIn) with the model's loss over all V_e + N entities; there are no negatives to
-    draw, so --num_negative_samples is not read.  --refresh is refused: trained columns do not learn here.
-    --label_distributions: the instances keep their label rows, and ids the trained meta knows are frozen co-labels."""
+    draw, so --num_negative_samples is not read.  --refresh is refused: it is the vectorspace flag.
+    --label_distributions: the instances keep their label rows, and ids the trained meta knows are frozen co-labels.
+    --unfreeze_known: ids the trained meta knows are refreshed -- their columns and biases learn too."""
     if args.refresh:
-        raise RuntimeError('--refresh needs a vectorspace model: refreshing the trained columns of a loglinear model is not '
-                           'supported.')
+        raise RuntimeError('--refresh needs a vectorspace model: the trained columns of a loglinear model are refreshed with '
+                           '--unfreeze_known.')
     dump = training.read_checkpoint(args.model)
     model_args, predict_fn, R_w = dump['args'], dump['predict_fn'], dump['tables'][0]
     meta = foldin.read_meta(args.meta)
@@ -118,14 +135,25 @@ def fold_in_loglinear(args):
     new_entity_ids = [new_index[e] for e in range(len(new_index))]
     associations = dict((e, new_meta[4].get(e, [])) for e in new_entity_ids)
     W, b = np.asarray(predict_fn.W), np.asarray(predict_fn.b)
+    refresh = None
+    if args.unfreeze_known:
+        # known ids are refreshed in order of first appearance, unknown ones the new columns V_e ..
+        extended_meta, refresh, added_ids, slots = foldin.merge_meta(meta, new_entity_ids, associations)
+        if not len(refresh) and not added_ids:
+            raise RuntimeError('nothing to fold in: %s names no entity.' % args.new_meta)
     if args.label_distributions:
-        # known ids are frozen co-labels at their trained index, unknown ones the new columns V_e ..
+        # known ids keep their trained index -- frozen co-labels, or refreshed with --unfreeze_known --, unknown ones are the
+        # new columns V_e ..
         extended_meta, columns, added_ids = foldin.label_columns(meta, new_entity_ids, associations)
-        if not added_ids:
+        if not added_ids and not args.unfreeze_known:
             raise RuntimeError('nothing to fold in: %s knows every entity id of %s.' % (args.meta, args.new_meta))
         (x, y, w), _ = training.load_data_sets(args.data)
         assert y.shape[1] <= len(new_entity_ids)
         y = foldin.remap_label_columns(y, columns, W.shape[1] + len(added_ids))
+    elif args.unfreeze_known:
+        x, y, w = one_hot_training_set(args.data)
+        assert y.size == 0 or int(y.max()) < len(new_entity_ids)
+        y = slots[y] if y.size else y           # (entity index of --new_meta -> slot)
     else:
         # (refuses a known entity id before anything is computed)
         extended_meta = foldin.extend_meta(meta, new_entity_ids, associations)
@@ -135,7 +163,7 @@ def fold_in_loglinear(args):
     new_W = models._glorot_uniform((W.shape[0], len(added_ids)))       # as models.LanguageModel initialises W; b: zeros
     fold = foldin.LogLinearFoldIn(R_w, W, b, new_W, None, (x, y, w), batch_size=args.batch_size,
                                   regularization_lambda=args.regularization_lambda, window_size=meta[0].window_size,
-                                  device=args.device)
+                                  device=args.device, refresh=refresh)
     mean, stddev = fold.train_error()
     logging.info('Epoch 0: fold-in error %.6f (stddev %.6f).', mean, stddev)
     for epoch in range(1, args.iterations + 1):
@@ -148,10 +176,15 @@ def fold_in_loglinear(args):
         if directory and not os.path.exists(directory):
             os.makedirs(directory)
     Wn, bn = fold.get_new_dense()
-    foldin.write_dump(args.model_output, foldin.extend_ll_dump(model_args, predict_fn, R_w, Wn, bn))
+    if refresh is None:
+        objects = foldin.extend_ll_dump(model_args, predict_fn, R_w, Wn, bn)
+    else:
+        Wr, br = fold.get_refreshed_dense()
+        objects = foldin.refresh_ll_dump(model_args, predict_fn, R_w, refresh, Wr, br, Wn, bn)
+    foldin.write_dump(args.model_output, objects)
     foldin.write_meta(args.meta_output, extended_meta)
-    logging.info('Saved the extended model "%s" (%d + %d entities) and its meta "%s".', args.model_output, W.shape[1],
-                 len(added_ids), args.meta_output)
+    logging.info('Saved the extended model "%s" (%d + %d entities, %d refreshed) and its meta "%s".', args.model_output,
+                 W.shape[1], len(added_ids), 0 if refresh is None else len(refresh), args.meta_output)
     fold.close()
 
 
@@ -168,6 +201,9 @@ def main(argv=None):
     if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:
         return fold_in_loglinear(args)
 
+    if args.unfreeze_known:
+        raise RuntimeError('--unfreeze_known needs a loglinear model: the trained rows of a vectorspace model are refreshed '
+                           'with --refresh.')
     if args.label_distributions:
         raise RuntimeError('--label_distributions needs a loglinear model: a vectorspace model learns from one entity per '
                            'instance (NCE), with or without it.')

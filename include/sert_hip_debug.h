@@ -113,6 +113,14 @@ int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n);
  * meaning for a refresh handle (num_new there reads Nt). */
 int sert_debug_foldin_table(sert_foldin* f, int32_t* out, int n);
 
+/* The column layout of a loglinear fold-in handle (include/sert_hip_ll_foldin.h: sert_ll_foldin_create_refresh;
+ * csrc/ll_label_remap.h) -- host record, test hook, no device is touched: *V_f the frozen columns the step kernels see as
+ * V_e, *Nt the trainable ones they see as N (either may be NULL), internal_of_public[e] the internal column of public column e
+ * -- the frozen columns in ascending trained index, the refreshed slots in the order of refresh_ids behind them, the new
+ * columns last.  count must be V_e + num_new; for sert_ll_foldin_create the map is the identity.  Touches nothing else; fails
+ * with a message on a null handle. */
+int sert_debug_ll_foldin_layout(sert_ll_foldin* f, int32_t* V_f, int32_t* Nt, int32_t* internal_of_public, int64_t count);
+
 /* What the LAST backward of this model launched for the per-word sums -- the word-table gradient of the vectorspace models
  * (word_grad_segsum) or dZu of the loglinear model (dzu_from_dj), both in csrc/host/lazy_segsum.inc over the tree of
  * csrc/word_index.h -- host record written where the launches are made, test hook, no device is touched:

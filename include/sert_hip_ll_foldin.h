@@ -29,10 +29,29 @@
  * with the gradient, the returned loss and the update as above.  A label on a trained column costs a gather from the logit
  * cache; the cache itself is the same.
  *
+ * Refreshing trained columns.  The more common event in an expert-finding collection is that people the model KNOWS write new
+ * documents.  sert_ll_foldin_create_refresh makes the trainable columns SLOTS, as sert_foldin_create_refresh does for rows:
+ * R = num_refresh trained columns (the refreshed ones), then N = num_new new ones, Nt = R + N >= 1.  Slot s < R stands for
+ * trained column refresh_ids[s], slot R + j for column V_e + j; ext_of_slot names that column of the extended model.  With
+ * Wx (d, V_e + N) = concat(W, Wn_new) and bx = concat(b, bn_new) in which every slot's CURRENT value is written to its
+ * column, a step on batch i is, for integer labels -- y is a SLOT in [0, Nt) --,
+ *     loss, grads, _ = LogLinearOracle(B, n, R_w, Wx, bx, lambda).loss_and_grads(X, ext_of_slot[y], w)
+ * and for label rows loss_and_grads(X, Ydense, w): the CSR columns stay the PUBLIC ones, e < V_e trained entity e, V_e + j
+ * new entity j; a trained column that is refreshed is now a parameter, one that is not stays a frozen co-label.
+ *     gradient       columns ext_of_slot of grads[1] and of grads[2]
+ *     returned loss  sum(loss_i * w_i) / B + lambda / (2B) * the sum of squares of the Nt trainable columns (not of the bias)
+ *     update         oracle.Adadelta over the slot-ordered [Wt (d, Nt), bt (Nt)], zero accumulators at creation
+ * sert_ll_foldin_eval_batch is eval_loss on Wx, bx.  R_w and every trained column not in refresh_ids are never written.  A
+ * refreshed column starts from its trained value and bias, copied on the device from the model.  It learns from the instances
+ * given: to keep an entity's old evidence, upload its old documents along with the new ones.
+ * The step does not know about any of this: the handle keeps the V_f = V_e - R frozen columns compact, in ascending trained
+ * index, and runs the step above as a fold-in of Nt columns into a model of V_f entities -- the logit cache of an upload
+ * takes |D| V_f 4 bytes, and label rows are brought to that column order on the host at upload.  V_f = 0 (every trained
+ * column refreshed) is supported: there is no cache then.
+ *
  * The handle is an object of its own, like sert_foldin: it COPIES what it needs from the model when it is created and shares
  * no state with the model's step schedule.  Later training or destruction of the model does not change it.
- * Out of scope: refreshing trained columns, data-parallel handles, window sizes above 32, a logit cache that
- * spills or is recomputed per step.
+ * Out of scope: data-parallel handles, window sizes above 32, a logit cache that spills or is recomputed per step.
  */
 #ifndef SERT_HIP_LL_FOLDIN_H
 #define SERT_HIP_LL_FOLDIN_H
@@ -67,6 +86,19 @@ enum {
  * lambda < 0, rho outside [0, 1), eps <= 0); the size limits (V_e + num_new and B n num_new below 2^31). */
 int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
                           const sert_ll_foldin_config* cfg, sert_ll_foldin** out);
+/* The same with slots (see "Refreshing trained columns" above): refresh_ids (num_refresh) distinct trained columns in
+ * [0, V_e), any order -- NULL if and only if num_refresh == 0 --, then num_new new columns with init_new_W (d, num_new)
+ * row-major -- NULL if and only if num_new == 0 -- and init_new_b (num_new) or NULL (zeros).  A refreshed column starts from
+ * the model's own column and bias.  Refused with a message, before any launch: negative counts; num_refresh + num_new < 1;
+ * a null array with a positive count (and an array with a count of 0); an id out of range; a duplicate id; and everything
+ * sert_ll_foldin_create refuses, its size limits applied to Nt = num_refresh + num_new in the place of num_new.  With
+ * num_refresh == 0 the handle holds the bits of sert_ll_foldin_create(num_new) on the same inputs.
+ * On such a handle sert_ll_foldin_upload takes y in [0, Nt), a slot; sert_ll_foldin_upload_csr the public columns
+ * [0, V_e + num_new) it always takes; sert_ll_foldin_get_tensor / _set_tensor d * Nt or Nt values in slot order; the logit
+ * cache and max_cache_bytes count the V_f = V_e - num_refresh frozen columns. */
+int sert_ll_foldin_create_refresh(sert_model* m, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
+                                  const float* init_new_W, const float* init_new_b, const sert_ll_foldin_config* cfg,
+                                  sert_ll_foldin** out);
 int sert_ll_foldin_destroy(sert_ll_foldin* f);
 
 /* The fold-in instances: x (M, n) int32 token ids in [0, V_w), y (M,) int32 in [0, num_new) -- one label per instance --, w (M,)

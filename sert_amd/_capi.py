@@ -71,7 +71,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_ll_foldin_layout', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -87,7 +87,7 @@ EXPORTS_FOLDIN = [
 FOLDIN_ROWS, FOLDIN_M, FOLDIN_V = 0, 1, 2
 # ... and include/sert_hip_ll_foldin.h, which sert_hip.h includes as well (the same for a trained loglinear model)
 EXPORTS_LL_FOLDIN = [
-    'sert_ll_foldin_create', 'sert_ll_foldin_destroy', 'sert_ll_foldin_upload', 'sert_ll_foldin_upload_csr',
+    'sert_ll_foldin_create', 'sert_ll_foldin_create_refresh', 'sert_ll_foldin_destroy', 'sert_ll_foldin_upload', 'sert_ll_foldin_upload_csr',
     'sert_ll_foldin_num_batches', 'sert_ll_foldin_train_batch', 'sert_ll_foldin_train_batches', 'sert_ll_foldin_eval_batch',
     'sert_ll_foldin_get_tensor', 'sert_ll_foldin_set_tensor',
 ]
@@ -227,6 +227,7 @@ def load():
     lib.sert_foldin_get_eval_draws.argtypes = [vp]
     lib.sert_foldin_get_eval_draws.restype = i64
     lib.sert_ll_foldin_create.argtypes = [vp, i32, fp, fp, ctypes.POINTER(SertLlFoldInConfig), ctypes.POINTER(vp)]
+    lib.sert_ll_foldin_create_refresh.argtypes = [vp, fp, i32, i32, fp, fp, ctypes.POINTER(SertLlFoldInConfig), ctypes.POINTER(vp)]
     lib.sert_ll_foldin_destroy.argtypes = [vp]
     lib.sert_ll_foldin_upload.argtypes = [vp, fp, fp, fp, i64]
     lib.sert_ll_foldin_upload_csr.argtypes = [vp, fp, fp, fp, fp, fp, i64]
@@ -1259,11 +1260,19 @@ class FoldIn(object):
 class LlFoldIn(object):
     """Owner of one sert_ll_foldin handle (include/sert_hip_ll_foldin.h): ``num_new`` columns of W and entries of b learnt
     on top of the frozen parameters of ``engine`` (a loglinear Engine), which are copied at construction -- the engine may
-    train on or be closed afterwards.  ``init_W``: (word_dim, num_new); ``init_b``: (num_new,) or None (zeros)."""
+    train on or be closed afterwards.  ``init_W``: (word_dim, num_new); ``init_b``: (num_new,) or None (zeros).
 
-    def __init__(self, engine, init_W, init_b, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0):
+    ``refresh_ids`` (distinct trained columns, any order; sert_ll_foldin_create_refresh): these trained columns learn too.
+    The trainable columns are then ``num_slots`` = ``num_refresh`` + ``num_new`` SLOTS, the refreshed columns first in the
+    order given: integer labels are slots, the tensors are (word_dim, num_slots) / (num_slots,) in slot order, and ``init_W``
+    may be None or empty (nothing is new).  Label rows keep the public columns [0, num_entities + num_new)."""
+
+    def __init__(self, engine, init_W, init_b, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0,
+                 refresh_ids=None):
         self._lib = load()
         self._h = None
+        if init_W is None and refresh_ids is not None:
+            init_W = np.zeros((engine.cfg.word_dim, 0), dtype=np.float32)
         Wn = np.ascontiguousarray(init_W, dtype=np.float32)
         if Wn.ndim != 2 or Wn.shape[0] != engine.cfg.word_dim:
             raise SertError('init_W must be (word_dim, num_new)')
@@ -1281,8 +1290,20 @@ class LlFoldIn(object):
         self.num_entities = int(engine.cfg.num_entities)
         self.window_size = int(engine.cfg.window_size)
         h = ctypes.c_void_p()
-        check(self._lib.sert_ll_foldin_create(engine._h, self.num_new, Wn.ctypes.data if Wn.size else None, _addr(bn),
-                                              ctypes.byref(c), ctypes.byref(h)))
+        if refresh_ids is None:
+            self.num_refresh = 0
+            check(self._lib.sert_ll_foldin_create(engine._h, self.num_new, Wn.ctypes.data if Wn.size else None, _addr(bn),
+                                                  ctypes.byref(c), ctypes.byref(h)))
+        else:
+            given = np.asarray(refresh_ids)
+            ids = np.ascontiguousarray(given, dtype=np.int32)
+            if ids.ndim != 1 or not np.array_equal(ids, given):
+                raise SertError('refresh_ids must be a 1-d array of int32 entity indices')
+            self.num_refresh = int(ids.size)
+            check(self._lib.sert_ll_foldin_create_refresh(engine._h, ids.ctypes.data if ids.size else None, self.num_refresh,
+                                                          self.num_new, Wn.ctypes.data if Wn.size else None,
+                                                          _addr(bn) if Wn.size else None, ctypes.byref(c), ctypes.byref(h)))
+        self.num_slots = self.num_refresh + self.num_new        # the trainable columns
         self._h = h
 
     def upload(self, x, y, w=None):
@@ -1337,7 +1358,7 @@ class LlFoldIn(object):
     def _shape(self, which):
         if which not in (LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B):
             raise SertError('which must be one of LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B')
-        return (self.num_new,) if which in (LL_FOLDIN_B, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_B) else (self.word_dim, self.num_new)
+        return (self.num_slots,) if which in (LL_FOLDIN_B, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_B) else (self.word_dim, self.num_slots)
 
     def get_tensor(self, which):
         out = np.empty(self._shape(int(which)), dtype=np.float32)
@@ -1347,6 +1368,16 @@ class LlFoldIn(object):
     def set_tensor(self, which, array):
         a = np.ascontiguousarray(array, dtype=np.float32)
         check(self._lib.sert_ll_foldin_set_tensor(self._h, int(which), a.ctypes.data, a.size))
+
+    def layout(self):
+        """sert_debug_ll_foldin_layout (test hook): (V_f, Nt, internal_of) -- the frozen and the trainable columns the step
+        kernels see and the internal column of every public column [0, num_entities + num_new)."""
+        vf, nt = ctypes.c_int32(), ctypes.c_int32()
+        out = np.empty(self.num_entities + self.num_new, dtype=np.int32)
+        self._lib.sert_debug_ll_foldin_layout.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int64]
+        check(self._lib.sert_debug_ll_foldin_layout(self._h, ctypes.byref(vf), ctypes.byref(nt), out.ctypes.data, out.size))
+        return int(vf.value), int(nt.value), out
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:

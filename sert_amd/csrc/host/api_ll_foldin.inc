@@ -6,8 +6,12 @@ struct sert_ll_foldin {
     int device = -1;
     hipStream_t stream = nullptr;
     sert_ll_foldin_config cfg;
-    int Vw = 0, Ve = 0, N = 0, d = 0, n = 0;
-    // the frozen snapshot
+    int Vw = 0, Ve = 0, N = 0, d = 0, n = 0;     // Ve: the FROZEN columns V_f; N: the trainable ones Nt (the kernels' V_e and N)
+    // the public columns: Ve_pub trained entities of the model, of which R are refreshed (slots [0, R) of the N trainable
+    // columns), and N - R new ones; internal_of (Ve_pub + N - R): public column -> internal column (ll_label_remap.h)
+    int Ve_pub = 0, R = 0;
+    std::vector<int32_t> internal_of;
+    // the frozen snapshot (W (d, Ve), b (Ve): null when every trained column is refreshed)
     float *rw = nullptr, *W = nullptr, *b = nullptr;
     // the new columns Wn (d, N) and biases bn (N), Adadelta's accumulators, the gradients
     float *Wn = nullptr, *bn = nullptr, *accu_w = nullptr, *accu_b = nullptr, *delta_w = nullptr, *delta_b = nullptr;
@@ -66,8 +70,12 @@ int sert_ll_foldin_destroy(sert_ll_foldin* f) {
     return 0;
 }
 
-static int llf_create(sert_ll_foldin* f, sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
-                      const sert_ll_foldin_config* cfg) {
+// Both creators.  refresh == false: sert_ll_foldin_create, its arguments and its wording.  The trainable columns are SLOTS --
+// the num_refresh refreshed trained columns, then the new ones -- and the handle's Ve / N are V_f / Nt of the internal column
+// order (ll_label_remap.h).  num_refresh == 0: W and b are copied whole, as ever; otherwise llf_compact writes the frozen
+// columns and the refreshed slots in one pass over the model's W, b.
+static int llf_create(sert_ll_foldin* f, sert_model* m, bool refresh, const int32_t* refresh_ids, int32_t num_refresh,
+                      int32_t num_new, const float* init_W, const float* init_b, const sert_ll_foldin_config* cfg) {
     const auto& c = m->cfg;
     // ---- validation: everything the kernels index with is checked here ----
     if (c.kind == SERT_KIND_VECTORSPACE)
@@ -76,19 +84,38 @@ static int llf_create(sert_ll_foldin* f, sert_model* m, int32_t num_new, const f
         SERT_FAIL("a loglinear fold-in needs a loglinear model: the full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX) is not supported");
     if (m->comm || m->host_ar || m->world > 1)
         SERT_FAIL("a fold-in of a data-parallel model (a communicator is attached) is not supported");
-    if (num_new < 1) SERT_FAIL("a fold-in needs at least one new entity (num_new >= 1)");
-    if (!init_W) SERT_FAIL("null argument");
+    if (!refresh) {
+        if (num_new < 1) SERT_FAIL("a fold-in needs at least one new entity (num_new >= 1)");
+        if (!init_W) SERT_FAIL("null argument");
+    } else {
+        if (num_refresh < 0 || num_new < 0) SERT_FAIL("a refresh needs num_refresh >= 0 and num_new >= 0");
+        if ((int64_t)num_refresh + num_new < 1) SERT_FAIL("a refresh needs at least one trainable column (num_refresh + num_new >= 1)");
+        if ((num_refresh > 0) != (refresh_ids != nullptr))
+            SERT_FAIL(num_refresh > 0 ? "null refresh_ids with num_refresh > 0" : "refresh_ids must be NULL when num_refresh == 0");
+        if ((num_new > 0) != (init_W != nullptr))
+            SERT_FAIL(num_new > 0 ? "null init_new_W with num_new > 0" : "init_new_W must be NULL when num_new == 0");
+    }
+    const int64_t nt = (int64_t)num_refresh + num_new;
     if (c.window_size > 32) SERT_FAIL("a loglinear fold-in supports window sizes up to 32");
     if (cfg->batch_size < 1) SERT_FAIL("a fold-in needs batch_size >= 1");
     if (!(cfg->lambda_ >= 0.f)) SERT_FAIL("regularization lambda must be >= 0");
     if (!(cfg->rho >= 0.f && cfg->rho < 1.f) || !(cfg->eps > 0.f)) SERT_FAIL("Adadelta needs 0 <= rho < 1 and eps > 0");
     if ((int64_t)c.num_entities + num_new > INT32_MAX) SERT_FAIL("more than 2^31 - 1 columns in the extended model");
-    if ((int64_t)cfg->batch_size * c.window_size * num_new > INT32_MAX) SERT_FAIL("batch_size * window_size * num_new > 2^31 - 1");
-    if ((int64_t)c.word_dim * num_new > INT32_MAX) SERT_FAIL("word_dim * num_new > 2^31 - 1");
+    if ((int64_t)cfg->batch_size * c.window_size * nt > INT32_MAX)
+        SERT_FAIL(refresh ? "batch_size * window_size * (num_refresh + num_new) > 2^31 - 1" : "batch_size * window_size * num_new > 2^31 - 1");
+    if ((int64_t)c.word_dim * nt > INT32_MAX)
+        SERT_FAIL(refresh ? "word_dim * (num_refresh + num_new) > 2^31 - 1" : "word_dim * num_new > 2^31 - 1");
+    switch (ll_layout(c.num_entities, num_new, refresh_ids, num_refresh, f->internal_of)) {
+        case LL_LAYOUT_ID_RANGE: SERT_FAIL("refresh id out of range [0, num_entities)");
+        case LL_LAYOUT_ID_DUPLICATE: SERT_FAIL("duplicate refresh id");
+        default: break;
+    }
     SERT_HIP(hipSetDevice(c.device));
     f->device = c.device; f->cfg = *cfg;
-    f->Vw = c.vocab_size; f->Ve = c.num_entities; f->N = num_new; f->d = c.word_dim; f->n = c.window_size;
-    const size_t n_w = (size_t)f->d * f->N, n_b = (size_t)f->N;
+    f->Vw = c.vocab_size; f->Ve_pub = c.num_entities; f->R = num_refresh; f->d = c.word_dim; f->n = c.window_size;
+    f->Ve = c.num_entities - num_refresh; f->N = (int)nt;
+    const int R = f->R, Vf = f->Ve, Nt = f->N, d = f->d;
+    const size_t n_w = (size_t)d * Nt, n_b = (size_t)Nt;
     // the parameters as a reader must see them (sert_get_tensor): every lazily updated word-table row brought to the model's
     // step, the side queues drained
     SERT_TRY(ensure_full_rw(m));
@@ -96,11 +123,13 @@ static int llf_create(sert_ll_foldin* f, sert_model* m, int32_t num_new, const f
     if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
     if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
     SERT_TRY(dmalloc(&f->rw, m->n_rw));
-    SERT_TRY(dmalloc(&f->W, m->n_w));
-    SERT_TRY(dmalloc(&f->b, m->n_b));
+    SERT_TRY(dmalloc(&f->W, (size_t)d * Vf));          // (V_f == 0: no allocation, the pointers stay null and are never read)
+    SERT_TRY(dmalloc(&f->b, (size_t)Vf));
     SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    if (R == 0) {
+        SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+        SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    }
     SERT_HIP(hipStreamCreate(&f->stream));
     hipStream_t s = f->stream;
     SERT_TRY(dmalloc(&f->Wn, n_w));
@@ -111,24 +140,46 @@ static int llf_create(sert_ll_foldin* f, sert_model* m, int32_t num_new, const f
     SERT_TRY(dzalloc(&f->delta_b, n_b, s));
     SERT_TRY(dmalloc(&f->g_w, n_w));
     SERT_TRY(dmalloc(&f->g_b, n_b));
-    SERT_HIP(hipMemcpyAsync(f->Wn, init_W, n_w * sizeof(float), hipMemcpyHostToDevice, s));
-    if (init_b) SERT_HIP(hipMemcpyAsync(f->bn, init_b, n_b * sizeof(float), hipMemcpyHostToDevice, s));
+    // the new columns [R, Nt) of Wn (d, Nt) and of bn
+    if (num_new > 0) {
+        if (R == 0) SERT_HIP(hipMemcpyAsync(f->Wn, init_W, n_w * sizeof(float), hipMemcpyHostToDevice, s));
+        else
+            SERT_HIP(hipMemcpy2DAsync(f->Wn + R, (size_t)Nt * sizeof(float), init_W, (size_t)num_new * sizeof(float),
+                                      (size_t)num_new * sizeof(float), (size_t)d, hipMemcpyHostToDevice, s));
+        if (init_b) SERT_HIP(hipMemcpyAsync(f->bn + R, init_b, (size_t)num_new * sizeof(float), hipMemcpyHostToDevice, s));
+    }
     SERT_TRY(dmalloc(&f->rowloss, (size_t)cfg->batch_size));
     SERT_TRY(dmalloc(&f->red_sq, (size_t)2 * kOptBlocks));
     SERT_TRY(dmalloc(&f->d_loss, (size_t)3));
-    SERT_HIP(hipStreamSynchronize(s));             // (init_W, init_b are borrowed for the call only)
-    SERT_HIP(hipStreamSynchronize(m->stream));     // (the snapshot is complete: the model may train or go away)
+    int32_t* d_internal = nullptr;
+    if (R > 0) {
+        SERT_TRY(dmalloc(&d_internal, (size_t)f->Ve_pub));
+        if (hipMemcpyAsync(d_internal, f->internal_of.data(), (size_t)f->Ve_pub * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess) {
+            (void)hipFree(d_internal);
+            SERT_FAIL("copying the column layout to the device failed");
+        }
+    }
+    hipError_t e = hipStreamSynchronize(s);            // (init_W, init_b are borrowed for the call only; bn's zeros are in place)
+    if (e == hipSuccess && R > 0) {
+        // the frozen columns and the refreshed slots, from the model's own W and b: behind the preamble on the model's queue
+        launch(llf_compact, dim3(grid_for(((int64_t)d + 1) * f->Ve_pub)), dim3(256), 0, m->stream, (const float*)m->W,
+               (const float*)m->b, (const int32_t*)d_internal, f->W, f->b, f->Wn, f->bn, d, f->Ve_pub, Vf, Nt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);     // (the snapshot is complete: the model may train or go away)
+    (void)hipFree(d_internal);
+    SERT_HIP(e);
     return 0;
 }
 
-int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
-                          const sert_ll_foldin_config* cfg, sert_ll_foldin** out) {
+static int llf_create_checked(sert_model* m, bool refresh, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
+                              const float* init_W, const float* init_b, const sert_ll_foldin_config* cfg, sert_ll_foldin** out) {
     refresh_gemm_choice();
     if (!m || !cfg || !out) SERT_FAIL("null argument");
     *out = nullptr;
     if (cfg->struct_size != sizeof(sert_ll_foldin_config)) SERT_FAIL("sert_ll_foldin_config size mismatch (ABI)");
     sert_ll_foldin* f = new sert_ll_foldin();
-    const int rc = llf_create(f, m, num_new, init_W, init_b, cfg);
+    const int rc = llf_create(f, m, refresh, refresh_ids, num_refresh, num_new, init_W, init_b, cfg);
     if (rc != 0) {
         const std::string keep = g_last_error;
         sert_ll_foldin_destroy(f);
@@ -137,6 +188,17 @@ int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, c
     }
     *out = f;
     return 0;
+}
+
+int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
+                          const sert_ll_foldin_config* cfg, sert_ll_foldin** out) {
+    return llf_create_checked(m, false, nullptr, 0, num_new, init_W, init_b, cfg, out);
+}
+
+int sert_ll_foldin_create_refresh(sert_model* m, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
+                                  const float* init_new_W, const float* init_new_b, const sert_ll_foldin_config* cfg,
+                                  sert_ll_foldin** out) {
+    return llf_create_checked(m, true, refresh_ids, num_refresh, num_new, init_new_W, init_new_b, cfg, out);
 }
 
 // the split-K shape of dWn = Gb^T dZu over `rows` distinct words (the loglinear step's rule, step_softmax_loglinear.inc)
@@ -210,7 +272,8 @@ static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab,
     if (M == 0) return 0;
     uint32_t* dwords = nullptr;
     auto body = [&]() -> int {
-        if (hipMalloc((void**)&f->Zold, (size_t)need) != hipSuccess) {
+        // (V_f == 0, every trained column refreshed: no cache -- Zold stays null and no kernel reads a column of it)
+        if (need != 0 && hipMalloc((void**)&f->Zold, (size_t)need) != hipSuccess) {
             (void)hipGetLastError();
             f->Zold = nullptr;
             SERT_FAIL("the logit cache of this upload needs " + std::to_string(need) + " bytes, which cannot be allocated");
@@ -261,7 +324,7 @@ static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab,
             launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(D * d, 256, 1 << 20)), dim3(256), 0, s, (const uint32_t*)dwords,
                    (const float*)f->rw, f->G, D, d);
         const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(D, (((int64_t)1 << 29) - 1) / std::max(Ve, d)));
-        for (int64_t r0 = 0; r0 < D; r0 += slab) {
+        for (int64_t r0 = 0; Ve > 0 && r0 < D; r0 += slab) {
             const int rows = (int)std::min<int64_t>(slab, D - r0);
             launch_gemm<false, false, EPI_BIAS>(s, f->G + (size_t)r0 * d, f->W, f->Zold + (size_t)r0 * Ve, f->b, rows, Ve, d, d, Ve, Ve);
         }
@@ -296,7 +359,10 @@ int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y,
     SERT_TRY(llf_upload_check_sizes(f, M));
     // host-side validation: no kernel is launched on bad ids
     for (int64_t i = 0; i < M; ++i)
-        if (y[i] < 0 || y[i] >= f->N) SERT_FAIL("fold-in label out of range [0, num_new)");
+        if (y[i] < 0 || y[i] >= f->N)
+            SERT_FAIL(f->R > 0 ? "fold-in label out of range [0, num_refresh + num_new): y is a slot"
+                               : "fold-in label out of range [0, num_new)");
+    // (a slot is the label's trainable column as the step counts it, behind the V_f frozen ones: nothing to remap)
     return llf_upload(f, x, LlfLabels{y, nullptr, nullptr, nullptr}, w, M);
 }
 
@@ -307,7 +373,7 @@ int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t
     SERT_TRY(llf_upload_check_sizes(f, M));
     // host-side validation, worded as sert_upload_dataset words it for csr_*: no kernel is launched on a bad row
     if (M > 0) {
-        const int64_t cols = (int64_t)f->Ve + f->N;
+        const int64_t cols = (int64_t)f->internal_of.size();      // the PUBLIC columns V_e + num_new
         if (indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
         for (int64_t r = 0; r < M; ++r)
             if (indptr[r + 1] < indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
@@ -327,6 +393,14 @@ int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t
                     SERT_FAIL(msg);
                 }
     }
+    if (f->R > 0 && M > 0 && indptr[M] > 0) {
+        // public -> internal columns: a refreshed column leaves the frozen ones for the trainable tail, which llf_row_csr
+        // finds by bisection at V_f, so every row is brought back to strictly increasing columns (ll_label_remap.h)
+        std::vector<int32_t> cols((size_t)indptr[M]);
+        std::vector<float> vals((size_t)indptr[M]);
+        ll_remap_csr(indptr, indices, data, M, f->internal_of, f->Ve, cols.data(), vals.data());
+        return llf_upload(f, x, LlfLabels{nullptr, indptr, cols.data(), vals.data()}, w, M);
+    }
     return llf_upload(f, x, LlfLabels{nullptr, indptr, indices, data}, w, M);
 }
 
@@ -334,7 +408,7 @@ int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f) { return f ? f->M / f->cfg
 
 static int llf_check_batch(sert_ll_foldin* f, int64_t batch) {
     if (!f) SERT_FAIL("null argument");
-    if (!f->Zold) SERT_FAIL("no fold-in instances uploaded (sert_ll_foldin_upload)");
+    if (!f->G) SERT_FAIL("no fold-in instances uploaded (sert_ll_foldin_upload)");
     if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
     return 0;
 }
@@ -496,5 +570,15 @@ int sert_ll_foldin_set_tensor(sert_ll_foldin* f, int which, const float* host, s
     SERT_HIP(hipSetDevice(f->device));
     SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
     SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int sert_debug_ll_foldin_layout(sert_ll_foldin* f, int32_t* V_f, int32_t* Nt, int32_t* internal_of_public, int64_t count) {
+    if (!f) SERT_FAIL("null argument");
+    if (count != (int64_t)f->internal_of.size() || (count > 0 && !internal_of_public))
+        SERT_FAIL("count must be V_e + num_new, the public columns of the handle");
+    if (V_f) *V_f = f->Ve;
+    if (Nt) *Nt = f->N;
+    for (int64_t i = 0; i < count; ++i) internal_of_public[i] = f->internal_of[(size_t)i];
     return 0;
 }

@@ -8,6 +8,29 @@
 
 namespace sert {
 
+// Once per handle that refreshes trained columns (sert_ll_foldin_create_refresh): one pass over the model's W (d, V_e) and
+// b (V_e), row d of the pass being b.  Element (k, e) goes to internal column c = internal_of[e] (ll_label_remap.h): a frozen
+// column c < V_f to the compact Wf (d, V_f) / bf (V_f), a refreshed one to slot c - V_f of the trainable Wt (d, Nt) / bt (Nt).
+// Consecutive threads read consecutive e of one row; internal_of is a bijection of [0, V_e) onto [0, V_f + R), so every
+// output element has exactly one writer, and the new columns [R, Nt) of Wt / bt are not touched.  Wf / bf may be null when
+// V_f = 0: no column is below 0.
+__global__ __launch_bounds__(256) void llf_compact(const float* __restrict__ W, const float* __restrict__ b,
+                                                   const int32_t* __restrict__ internal_of, float* __restrict__ Wf,
+                                                   float* __restrict__ bf, float* __restrict__ Wt, float* __restrict__ bt,
+                                                   int d, int Ve, int Vf, int Nt) {
+    const int64_t total = ((int64_t)d + 1) * Ve;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int k = (int)(i / Ve), e = (int)(i - (int64_t)k * Ve);
+        const int c = internal_of[e];
+        const float v = k < d ? W[i] : b[e];
+        if (c < Vf) {
+            if (k < d) Wf[(size_t)k * Vf + c] = v; else bf[c] = v;
+        } else {
+            if (k < d) Wt[(size_t)k * Nt + (c - Vf)] = v; else bt[c - Vf] = v;
+        }
+    }
+}
+
 // Once per upload: stat[r] = (max_e Zold[r, e], sum_e exp(Zold[r, e] - max)) over the frozen entities.  One workgroup per row;
 // the maximum first, so that an entity switched off (a bias of -inf) adds exp(-inf) = 0 and no inf - inf is ever formed.
 __global__ __launch_bounds__(256) void llf_row_stat(const float* __restrict__ Zold, int V, float2* __restrict__ stat) {

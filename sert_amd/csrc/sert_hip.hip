@@ -41,6 +41,7 @@
 #include "kernels_vs.h"
 #include "kernels_foldin.h"
 #include "kernels_ll_foldin.h"
+#include "ll_label_remap.h"
 #ifdef SERT_VARIANTS
 #include "variants/kernels_gather_hot.h"
 #include "variants/kernels_seg_bundled.h"

@@ -5,7 +5,8 @@ projection and the trained entity rows fixed and learn only the new rows, with t
 entities' instances.  ``EntityFoldIn`` is that, on the device; ``bin/fold_in.py`` is its command line.
 
 ``LogLinearFoldIn`` is the same for a trained loglinear (expert-finding) model (include/sert_hip_ll_foldin.h): the word table
-and the trained columns of the output layer stay fixed and the new entities' columns and biases learn.
+and the trained columns of the output layer stay fixed and the new entities' columns and biases learn.  With ``refresh`` the
+columns and biases of trained entities that gained documents learn too (bin/fold_in.py --unfreeze_known).
 """
 import logging
 import pickle
@@ -182,14 +183,24 @@ class LogLinearFoldIn(models.ModelInterface):
     Label rows: y may be a ``scipy.sparse`` matrix (M, V_e + N) instead -- the label DISTRIBUTIONS the model was trained on
     without --one_hot_classes.  Column e < V_e is trained entity e: a label only (a co-author the model knows), its column of
     W stays frozen; column V_e + j is new entity j.  The matrix is brought to canonical CSR (``tocsr``, ``sum_duplicates``,
-    ``sort_indices``); with ``new_W_init`` None, N = y.shape[1] - V_e, which must be at least 1."""
+    ``sort_indices``); with ``new_W_init`` None, N = y.shape[1] - V_e, which must be at least 1.
+
+    ``refresh`` (an array of distinct trained internal indices): these trained columns and biases learn too -- people the
+    model knows who wrote new documents.  The trainable columns are then SLOTS, the refreshed columns first, in the order of
+    ``refresh``, the new columns behind them: an integer y is a slot in [0, len(refresh) + N), and ``new_W_init`` may be None
+    or empty (nothing is new; with label rows None still means N = y.shape[1] - V_e, which may then be 0).  Label rows keep
+    their columns: a trained column that is refreshed is a parameter, one that is not stays a frozen co-label.  A refreshed
+    column starts from its trained value and bias and learns from the instances given: to keep its old evidence, pass the
+    entity's old documents along with the new ones."""
 
     #: batches issued to the device before their losses are read back
     steps_per_sync = 1
 
     def __init__(self, R_w, W, b, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, window_size,
-                 device=0, max_cache_bytes=0, _engine=None):
+                 device=0, max_cache_bytes=0, _engine=None, refresh=None):
         super(LogLinearFoldIn, self).__init__(batch_size)
+        if refresh is not None:
+            refresh = np.asarray(refresh, dtype=np.int64).reshape(-1)
         x = np.asarray(training_set[0])
         w = training_set[2] if len(training_set) > 2 else None
         word_dim, num_entities = int(np.shape(W)[0]), int(np.shape(W)[1])
@@ -201,23 +212,28 @@ class LogLinearFoldIn(models.ModelInterface):
             y.sort_indices()
             assert x.ndim == 2 and x.shape[1] == window_size and y.shape[0] == x.shape[0]
             if new_W_init is None:
-                if y.shape[1] - num_entities < 1:
+                if y.shape[1] - num_entities < (1 if refresh is None else 0):
                     raise RuntimeError('label rows of %d columns on a model of %d entities: no column is new'
                                        % (y.shape[1], num_entities))
-                new_W_init = models._glorot_uniform((word_dim, y.shape[1] - num_entities))
+                new_W_init = (models._glorot_uniform((word_dim, y.shape[1] - num_entities)) if y.shape[1] > num_entities
+                              else np.zeros((word_dim, 0), dtype=np.float32))
         else:
             y = np.asarray(training_set[1])
             assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+            if new_W_init is None and refresh is not None:
+                new_W_init = np.zeros((word_dim, 0), dtype=np.float32)
             if new_W_init is None:
                 if not y.size:
                     raise RuntimeError('no fold-in instances and no initial columns: nothing says how many entities are new')
                 new_W_init = models._glorot_uniform((word_dim, int(y.max()) + 1))
-        new_W_init = np.ascontiguousarray(new_W_init, dtype=np.float32)
+        new_W_init = np.ascontiguousarray(new_W_init, dtype=np.float32).reshape(word_dim, -1)
         if rows and y.shape[1] != num_entities + new_W_init.shape[1]:
             raise RuntimeError('label rows must have V_e + N = %d + %d columns, not %d'
                                % (num_entities, new_W_init.shape[1], y.shape[1]))
         self.window_size = int(window_size)
         self.num_new = int(new_W_init.shape[1])
+        self.refresh = None if refresh is None else refresh.copy()
+        self.num_refresh = 0 if refresh is None else int(refresh.size)
         self.num_entities = int(np.shape(W)[1])
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
@@ -236,7 +252,7 @@ class LogLinearFoldIn(models.ModelInterface):
                 engine.set_tensor(which, value)
         try:
             self._foldin = _capi.LlFoldIn(engine, new_W_init, new_b_init, batch_size, regularization_lambda,
-                                          max_cache_bytes=max_cache_bytes)
+                                          max_cache_bytes=max_cache_bytes, refresh_ids=refresh)
         finally:
             if owned:
                 engine.close()      # (the handle copied what it needs)
@@ -244,19 +260,24 @@ class LogLinearFoldIn(models.ModelInterface):
             self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
         else:
             self._foldin.upload(x, y, w)
-        logging.info('Folding in %d new entities (columns %d .. %d) on %d instances%s.', self.num_new, self.num_entities,
-                     self.num_entities + self.num_new - 1, self.training_num_instances,
-                     ' with %d label entries' % y.nnz if rows else '')
+        if refresh is None:
+            logging.info('Folding in %d new entities (columns %d .. %d) on %d instances%s.', self.num_new, self.num_entities,
+                         self.num_entities + self.num_new - 1, self.training_num_instances,
+                         ' with %d label entries' % y.nnz if rows else '')
+        else:
+            logging.info('Refreshing %d trained entities and folding in %d new ones on %d instances%s.', self.num_refresh,
+                         self.num_new, self.training_num_instances, ' with %d label entries' % y.nnz if rows else '')
 
     @classmethod
-    def from_model(cls, model, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, max_cache_bytes=0):
+    def from_model(cls, model, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, max_cache_bytes=0,
+                   refresh=None):
         """From a live ``models.LanguageModel``: its parameters as they are now are copied on the device (the model may train
         on or be dropped afterwards)."""
         if not isinstance(model, models.LanguageModel):
             raise RuntimeError('a loglinear fold-in needs a LanguageModel')
         return cls(None, _Shape((model.representation_size, model.output_layer_size)), None, new_W_init, new_b_init,
                    training_set, batch_size, regularization_lambda, model.window_size, max_cache_bytes=max_cache_bytes,
-                   _engine=model._engine)
+                   _engine=model._engine, refresh=refresh)
 
     # -- the step functions ---------------------------------------------------------------------------------------
     def train_fn(self, batch_index):
@@ -286,14 +307,29 @@ class LogLinearFoldIn(models.ModelInterface):
     # -- results and state --------------------------------------------------------------------------------------------
     def get_new_dense(self):
         """(Wn (d, N), bn (N,)): the new columns and biases as they are now."""
-        return self._foldin.get_tensor(_capi.LL_FOLDIN_W), self._foldin.get_tensor(_capi.LL_FOLDIN_B)
+        R = self.num_refresh
+        return (np.ascontiguousarray(self._foldin.get_tensor(_capi.LL_FOLDIN_W)[:, R:]),
+                np.ascontiguousarray(self._foldin.get_tensor(_capi.LL_FOLDIN_B)[R:]))
+
+    def get_refreshed_dense(self):
+        """(W (d, len(refresh)), b (len(refresh),)): the refreshed trained columns and biases as they are now, in the order of
+        ``refresh``."""
+        R = self.num_refresh
+        return (np.ascontiguousarray(self._foldin.get_tensor(_capi.LL_FOLDIN_W)[:, :R]),
+                np.ascontiguousarray(self._foldin.get_tensor(_capi.LL_FOLDIN_B)[:R]))
 
     def get_extended_dense(self, W, b):
-        """(W (d, V_e + N), b (V_e + N,)): the trained ``W`` / ``b`` (the caller's: never modified) with the new columns behind."""
+        """(W (d, V_e + N), b (V_e + N,)): the trained ``W`` / ``b`` (the caller's: never modified) with the columns of
+        ``refresh`` replaced by their slots and the new columns behind."""
         W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
         assert W.shape[1] == self.num_entities and b.shape == (self.num_entities,)
-        Wn, bn = self.get_new_dense()
-        return np.concatenate([W, Wn], axis=1), np.concatenate([b, bn])
+        Wt, bt = self._foldin.get_tensor(_capi.LL_FOLDIN_W), self._foldin.get_tensor(_capi.LL_FOLDIN_B)
+        R = self.num_refresh
+        Wx, bx = np.concatenate([W, Wt[:, R:]], axis=1), np.concatenate([b, bt[R:]])
+        if R:
+            Wx[:, self.refresh] = Wt[:, :R]
+            bx[self.refresh] = bt[:R]
+        return Wx, bx
 
     def get_optimizer_state(self):
         g = self._foldin.get_tensor
@@ -339,6 +375,20 @@ def extend_ll_dump(args, predict_fn, R_w, Wn, bn):
     return [args, extended, R_w]
 
 
+def refresh_ll_dump(args, predict_fn, R_w, refresh, Wr, br, Wn, bn):
+    """extend_ll_dump with the columns ``refresh`` of the trained output layer replaced by ``Wr`` (d, len(refresh)) / ``br`` and
+    the new columns ``Wn`` / ``bn`` appended; ``predict_fn`` is not modified, every other column keeps its bits."""
+    st = predict_fn.__getstate__()
+    W, b = np.array(st['W'], copy=True), np.array(st['b'], copy=True)
+    refresh = np.asarray(refresh, dtype=np.int64).reshape(-1)
+    Wr, br = np.asarray(Wr, dtype=W.dtype).reshape(W.shape[0], -1), np.asarray(br, dtype=b.dtype).reshape(-1)
+    assert Wr.shape == (W.shape[0], refresh.size) and br.shape == (refresh.size,)
+    W[:, refresh] = Wr
+    b[refresh] = br
+    replaced = models.LogLinearPredictFn(R_w=np.asarray(st['R_w']), W=W, b=b, window_size=st['window_size'])
+    return extend_ll_dump(args, replaced, R_w, np.asarray(Wn, dtype=W.dtype).reshape(W.shape[0], -1), np.asarray(bn).reshape(-1))
+
+
 def write_dump(path, objects):
     with open(path, 'wb') as f:
         for obj in objects:
@@ -369,7 +419,7 @@ def extend_meta(meta, new_entity_ids, new_associations=None):
 
 
 def merge_meta(meta, entity_ids, associations=None):
-    """The meta of a model in which entities GAIN documents (bin/fold_in.py --refresh).  ``entity_ids[k]`` is entity k of the
+    """The meta of a model in which entities GAIN documents (bin/fold_in.py --refresh; --unfreeze_known for a loglinear dump).  ``entity_ids[k]`` is entity k of the
     new documents' meta: an id the trained meta knows keeps its internal index and is refreshed, an unknown one gets
     V_e + e in order of first appearance; ``associations`` (entity id -> document ids) are added to either kind.
     -> (the five pickles, the refreshed internal indices in order of first appearance, the new ids, slots): ``slots[k]`` is

@@ -13,6 +13,11 @@ timed apart, with the size of the cache.
 With --labels K the same process also times the fold-in step on label ROWS (sert_ll_foldin_upload_csr): K entries per
 instance, K // 2 of them on trained columns and the rest on new ones, values 1 / K, on a second handle over the same tokens --
 alternating with the other two, so that the row step stands beside the integer-label step of the same process.
+
+With --refresh R the same process also times a handle that REFRESHES R trained columns (sert_ll_foldin_create_refresh: R
+refreshed + N new slots) and the plain handle it should equal: sert_ll_foldin_create with R + N new columns on a model that
+holds the other V_e - R columns only, initialised with the refreshed columns' trained values.  Both launch the same kernels on
+the same shapes and the same numbers; the record says whether their losses came out equal bit for bit.
 """
 import argparse
 import json
@@ -67,7 +72,29 @@ def label_rows(rng, M, Ve, N, K):
     return np.arange(M + 1, dtype=np.int64) * K, cols.reshape(-1), np.full(M * K, 1.0 / K, np.float32)
 
 
-def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches, labels=0):
+def refresh_pair(rng, frozen, B, Vw, Ve, N, d, n, R, X, M):
+    """(the refresh handle, the plain handle on the column-deleted model), both with the same upload of slot labels"""
+    ids = rng.choice(Ve, R, replace=False).astype(np.int32)
+    W, b = frozen.get_tensor(C.T_W, (d, Ve)), frozen.get_tensor(C.T_B, (Ve,))
+    Wn = glorot(rng, (d, N))
+    keep = np.setdiff1d(np.arange(Ve), ids)
+    refresh = C.LlFoldIn(frozen, Wn, None, B, 0.01, refresh_ids=ids)
+    deleted = C.Engine(kind=C.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=n, vocab_size=Vw,
+                       num_entities=Ve - R, word_dim=d, entity_dim=0, num_negatives=0, id_bytes=4, device=0, keep_grads=0,
+                       deterministic=1, inference_only=1, lambda_=0.01, lr=1.0, beta1=0.95, beta2=0.0, eps=1e-6, seed=0)
+    deleted.set_tensor(C.T_RW, frozen.get_tensor(C.T_RW, (Vw, d)))
+    deleted.set_tensor(C.T_W, np.ascontiguousarray(W[:, keep]))
+    deleted.set_tensor(C.T_B, np.ascontiguousarray(b[keep]))
+    plain = C.LlFoldIn(deleted, np.ascontiguousarray(np.concatenate([W[:, ids], Wn], axis=1)),
+                       np.concatenate([b[ids], np.zeros(N, np.float32)]), B, 0.01)
+    deleted.close()
+    y = rng.randint(0, R + N, M).astype(np.int32)
+    t_upload, _ = timed(lambda: refresh.upload(X.astype(np.int32), y, None))
+    plain.upload(X.astype(np.int32), y, None)
+    return refresh, plain, t_upload
+
+
+def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches, labels=0, refresh=0):
     rng = np.random.RandomState(0)
     M = B * num_batches
     X = zipf_tokens(rng, Vw, (M, n))
@@ -76,13 +103,16 @@ def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches, labels=0
     frozen = engine(rng, 1, Vw, Ve, d, n, inference_only=1)
     fold = C.LlFoldIn(frozen, glorot(rng, (d, N)), None, B, 0.01)
     rows = C.LlFoldIn(frozen, glorot(rng, (d, N)), None, B, 0.01) if labels else None
+    pair = refresh_pair(rng, frozen, B, Vw, Ve, N, d, n, refresh, X, M) if refresh else None
     frozen.close()
     t_upload, _ = timed(lambda: fold.upload(X.astype(np.int32), rng.randint(0, N, M).astype(np.int32), None))
     distinct = int(np.unique(X).size)
     order = np.arange(steps, dtype=np.int64) % num_batches
     full.train_batches(order)
     fold.train_batches(order)
-    t_fold, t_full, t_rows = [], [], []
+    t_fold, t_full, t_rows, t_refresh, t_deleted = [], [], [], [], []
+    if pair is not None:
+        same_bits = bool(np.array_equal(pair[0].train_batches(order).view(np.uint32), pair[1].train_batches(order).view(np.uint32)))
     if rows is not None:
         indptr, indices, data = label_rows(rng, M, Ve, N, labels)
         t_upload_rows, _ = timed(lambda: rows.upload_csr(X.astype(np.int32), indptr, indices, data, None))
@@ -91,6 +121,9 @@ def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches, labels=0
         t_fold.append(timed(lambda: fold.train_batches(order))[0] / steps)
         if rows is not None:
             t_rows.append(timed(lambda: rows.train_batches(order))[0] / steps)
+        if pair is not None:
+            t_refresh.append(timed(lambda: pair[0].train_batches(order))[0] / steps)
+            t_deleted.append(timed(lambda: pair[1].train_batches(order))[0] / steps)
         t_full.append(timed(lambda: full.train_batches(order))[0] / steps)
     full.close()
     fold.close()
@@ -105,6 +138,15 @@ def step_setting(name, B, Vw, Ve, N, d, n, steps, repeats, num_batches, labels=0
         rec.update(labels_per_row=labels, trained_labels_per_row=labels // 2, rows_step_ms=[1e3 * t for t in t_rows],
                    rows_step_ms_median=1e3 * float(np.median(t_rows)), rows_upload_ms=1e3 * t_upload_rows)
         rec['rows_over_integer_median'] = rec['rows_step_ms_median'] / rec['foldin_step_ms_median']
+    if pair is not None:
+        pair[0].close()
+        pair[1].close()
+        rec.update(refreshed=refresh, refresh_slots=refresh + N, refresh_frozen_columns=Ve - refresh,
+                   refresh_step_ms=[1e3 * t for t in t_refresh], deleted_plain_step_ms=[1e3 * t for t in t_deleted],
+                   refresh_step_ms_median=1e3 * float(np.median(t_refresh)),
+                   deleted_plain_step_ms_median=1e3 * float(np.median(t_deleted)), refresh_upload_ms=1e3 * pair[2],
+                   refresh_logit_cache_bytes=distinct * (Ve - refresh) * 4, refresh_losses_equal_deleted_plain_bitwise=same_bits)
+        rec['refresh_over_deleted_plain_median'] = rec['refresh_step_ms_median'] / rec['deleted_plain_step_ms_median']
     return rec
 
 
@@ -117,12 +159,16 @@ def main(argv=None):
     ap.add_argument('--settings', nargs='+', default=[s[0] for s in SETTINGS])
     ap.add_argument('--labels', type=int, default=0,
                     help='K > 0: also time the step on label rows of K entries, K // 2 of them trained (sert_ll_foldin_upload_csr)')
+    ap.add_argument('--refresh', type=int, default=0,
+                    help='R > 0: also time a handle that refreshes R trained columns (R + N slots) and the plain handle with R + N '
+                         'new columns on the column-deleted model (sert_ll_foldin_create_refresh)')
     args = ap.parse_args(argv)
     C.require_gpu()
     out = dict(device=C.device_info(0), steps=[])
     for s in SETTINGS:
         if s[0] in args.settings:
-            rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches, labels=args.labels)
+            rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches, labels=args.labels,
+                               refresh=args.refresh)
             print(json.dumps(rec))
             out['steps'].append(rec)
             with open(args.out, 'w') as f:
