@@ -51,6 +51,19 @@ given: to keep its old evidence, pass the entity's old documents along with the 
 
     python bin/fold_in.py --unfreeze_known --label_distributions --meta meta --model model_15.bin --new_meta new_meta \\
         --data new.npz --iterations 10 --model_output model_15_ref.bin --meta_output meta_ref
+
+With ``--new_words`` (vectorspace dumps only) the VOCABULARY grows instead: ``--new_meta`` / ``--data`` come from a
+bin/prepare.py run with ``--vocabulary_from META --extend_vocabulary`` over new documents of trained entities, whose new words
+(brand names, model numbers) carry the token ids V_w ..  The trained word rows, the projection and the whole entity table stay
+as they are; only the rows of the new words learn (sert_amd.foldin.WordFoldIn), drawn at the scale bin/train.py drew the trained R_w, on
+the windows that hold a new word (the others cannot move a trainable row and are dropped).  Every entity of ``--new_meta`` must
+be known to ``--meta``: fold new entities in first and prepare against the extended meta.  ``--model_output`` is a dump with
+R_w extended by the new rows, ``--meta_output`` the meta with the extended vocabulary; bin/query.py serves the pair unchanged.
+
+    python bin/prepare.py --seed 1 new_docs/*.trectext --assoc_path new_assocs --vocabulary_from meta --extend_vocabulary \\
+        --window_size 4 --meta_output new_meta --data_output new.npz
+    python bin/fold_in.py --new_words --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
+        --model_output model_15_words.bin --meta_output meta_words
 """
 import argparse
 import logging
@@ -95,6 +108,10 @@ def build_parser():
                              'co-labels -- their trained columns of W and their biases learn from the instances given, in place; '
                              'the rest are new (none need be).  A refreshed column learns from the instances given: to keep its '
                              'old evidence, pass the entity\'s old documents along with the new ones.')
+    parser.add_argument('--new_words', action='store_true', default=False,
+                        help='vectorspace dumps only: fold in the new WORDS of --new_meta (bin/prepare.py --vocabulary_from META '
+                             '--extend_vocabulary) instead of entities: their rows of R_w learn, everything trained stays as it '
+                             'is.  Every entity of --new_meta must be known to --meta.')
     parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     return parser
@@ -188,6 +205,62 @@ def fold_in_loglinear(args):
     fold.close()
 
 
+def fold_in_words(args):
+    """--new_words on a vectorspace dump: the rows of the new words of --new_meta learn (sert_amd.foldin.WordFoldIn)."""
+    if args.refresh or args.unfreeze_known or args.label_distributions:
+        raise RuntimeError('--new_words folds in words, not entities: --refresh, --unfreeze_known and --label_distributions '
+                           'do not apply.')
+    model_args, predict_fn, R_w, R_e = load_model(args.model)
+    if getattr(model_args, 'type', None) is not models.VectorSpaceLanguageModel:
+        raise RuntimeError('--new_words needs a model trained as vectorspace (found %r).' % (getattr(model_args, 'type', None),))
+    meta = foldin.read_meta(args.meta)
+    new_meta = foldin.read_meta(args.new_meta)
+    # (refuses a vocabulary that does not extend the trained one and an entity the model does not know, before anything is computed)
+    extended_meta = foldin.extend_meta_words(meta, new_meta)
+    new_words = foldin.new_words_of(meta, new_meta)
+    if not new_words:
+        raise RuntimeError('nothing to fold in: %s holds no word that %s does not know.' % (args.new_meta, args.meta))
+    R_w = np.asarray(R_w)
+    V_w = R_w.shape[0]
+    if V_w != len(meta[1]):
+        raise RuntimeError('%s holds %d word rows but %s names %d words: they are not of the same model.'
+                           % (args.model, V_w, args.meta, len(meta[1])))
+    x, y, w = one_hot_training_set(args.data)
+    # labels: entity index of --new_meta -> trained index
+    index_of = dict((entity_id, index) for index, entity_id in meta[3].items())
+    trained = np.array([index_of[new_meta[3][e]] for e in range(len(new_meta[3]))], dtype=np.int32)
+    y = trained[y] if y.size else y.astype(np.int32)
+    # a window without a new word cannot move a trainable row
+    keep = (np.asarray(x) >= V_w).any(axis=1)
+    logging.info('Dropped %d of %d windows that hold no new word.', int((~keep).sum()), int(keep.size))
+    if not keep.any():
+        raise RuntimeError('nothing to fold in: no window of %s holds a new word.' % args.data)
+    x, y = np.asarray(x)[keep].astype(np.int32), y[keep]
+    w = None if w is None else np.asarray(w)[keep]
+    new_rows = foldin.new_word_rows(V_w, len(new_words), R_w.shape[1])
+    fold = foldin.WordFoldIn(
+        R_w, R_e, predict_fn.W, predict_fn.b, new_rows, (x, y, w), batch_size=args.batch_size,
+        num_negative_samples=args.num_negative_samples, regularization_lambda=args.regularization_lambda,
+        window_size=meta[0].window_size, seed=args.seed, device=args.device)
+    mean, stddev = fold.train_error()
+    logging.info('Epoch 0: fold-in error %.6f (stddev %.6f).', mean, stddev)
+    for epoch in range(1, args.iterations + 1):
+        num_batches, loss = fold.train()
+        mean, stddev = fold.train_error()
+        logging.info('Epoch %d: %d batches, mean training loss %.6f; fold-in error %.6f (stddev %.6f).',
+                     epoch, num_batches, loss, mean, stddev)
+    for path in (args.model_output, args.meta_output):
+        directory = os.path.dirname(path)
+        if directory and not os.path.exists(directory):
+            os.makedirs(directory)
+    foldin.write_dump(args.model_output, foldin.extend_words_dump(model_args, predict_fn, R_w, R_e,
+                                                                  fold.get_new_word_representations()))
+    foldin.write_meta(args.meta_output, extended_meta)
+    logging.info('Saved the extended model "%s" (%d + %d words) and its meta "%s".', args.model_output, V_w, len(new_words),
+                 args.meta_output)
+    fold.close()
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
@@ -196,6 +269,11 @@ def main(argv=None):
         return -1
     if args.seed is not None:
         np.random.seed(args.seed)
+
+    if args.new_words:
+        if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:
+            raise RuntimeError('--new_words needs a vectorspace model: a word fold-in of a loglinear model is not supported.')
+        return fold_in_words(args)
 
     # the dump's model type decides: a loglinear dump takes the path of its own, anything else the vectorspace one below
     if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:

@@ -48,6 +48,11 @@ def build_parser():
     p.add_argument('--vocabulary_from', type=au.existing_file_path, default=argparse.SUPPRESS, metavar='META',
                    help='take the vocabulary (token ids) of a trained model\'s meta file instead of extracting one: '
                         'for documents of entities that are folded into that model; out-of-vocabulary tokens are dropped')
+    p.add_argument('--extend_vocabulary', action='store_true', default=argparse.SUPPRESS,
+                   help='with --vocabulary_from META: tokens of the documents outside META\'s vocabulary that pass '
+                        '--vocabulary_min_count, --vocabulary_min_word_size and the stop list are appended as ids V_w, V_w + 1, ... '
+                        '(count descending, then word; at most --vocabulary_max_size words in all) instead of dropped: for '
+                        'bin/fold_in.py --new_words.  The trained ids do not move.')
     return p
 
 

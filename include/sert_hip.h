@@ -438,6 +438,13 @@ int sert_score_topk(int device, const float* entities, int64_t num_entities, int
  * The handle and its calls are declared in sert_hip_ll_foldin.h, which is part of this boundary. */
 #include "sert_hip_ll_foldin.h"
 
+/* ---- folding unseen words into a trained vectorspace model -------------- */
+
+/* The other half of a catalogue that changes after training: the vocabulary grows.  The trained word rows, the projection and
+ * the whole entity table stay fixed and only the rows of the new words learn, with the same NCE objective.  The handle and its
+ * calls are declared in sert_hip_wfold.h, which is part of this boundary. */
+#include "sert_hip_wfold.h"
+
 /* ---- data parallel (new: the reference is single-device) ---- */
 
 #define SERT_COMM_ID_BYTES 128

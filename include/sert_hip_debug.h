@@ -113,6 +113,31 @@ int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n);
  * meaning for a refresh handle (num_new there reads Nt). */
 int sert_debug_foldin_table(sert_foldin* f, int32_t* out, int n);
 
+/* What the LAST step of a word fold-in handle launched (include/sert_hip_wfold.h; kernels in csrc/kernels_wfold.h, dispatch in
+ * csrc/host/api_wfold.inc: wfold_forward_loss, wfold_segsum, wfold_step_async) -- host record written where the launches are
+ * made, test hook, no device is touched: out[0] one of SERT_WFOLD_PROJECT_* (the instance of wfold_project), out[1] the loss
+ * kernel's form (SERT_NCE_FORM_PER_CANDIDATE: vs_nce<K, TRAIN>; SERT_NCE_FORM_SCALAR: vs_nce_scalar<K, TRAIN>), out[2] its K,
+ * out[3] 1 for the training instance and 0 for the evaluating one, out[4] the levels of the batch's reduction (0: the batch
+ * holds no new word), out[5 + l] the items of level l < 6, out[11] the reduction kernel (SERT_WGRAD_FORM_ROWS32 / _ROWS64 /
+ * _SCALAR; 0 without a level), out[12] / out[13] the GEMM kernel chosen for P = Nv W and for G = S W^T (SERT_GEMM_ROUTE_*).
+ * n <= 16; all zero before the first step.  An evaluation runs the forward alone: out[4..11] and out[13] are zero after it. */
+enum {
+    SERT_WFOLD_PROJECT_NONE = 0,
+    SERT_WFOLD_PROJECT_VECTOR = 1,   /* wfold_project<4>: d_e % 4 == 0, float4 columns */
+    SERT_WFOLD_PROJECT_SCALAR = 2    /* wfold_project<1>: any other d_e */
+};
+typedef struct sert_wfold sert_wfold;
+int sert_debug_wfold_plan(sert_wfold* f, int32_t* out, int n);
+
+/* Host only, no device is touched: the inverted index of a word fold-in (csrc/wfold_index.h: build_wfold_index) for batch
+ * `batch` of tok (num_batches, B, n), the new word of every position or -1 -- levels[0] the levels, levels[1 + l] the items of
+ * level l < 6, levels[7 + l] the first partial row of level l's output (13 ints); rows_out the entries (batch rows), items_out
+ * the items {begin, end, dst, 0}, level after level; *num_rows / *num_items what the batch holds (nothing is copied when a
+ * capacity is too small). */
+int sert_debug_wfold_index(const int32_t* tok, int64_t num_batches, int B, int n, int num_words, int64_t batch, int32_t* levels,
+                           int32_t* rows_out, int64_t rows_cap, int32_t* items_out, int64_t items_cap, int64_t* num_rows,
+                           int64_t* num_items);
+
 /* The column layout of a loglinear fold-in handle (include/sert_hip_ll_foldin.h: sert_ll_foldin_create_refresh;
  * csrc/ll_label_remap.h) -- host record, test hook, no device is touched: *V_f the frozen columns the step kernels see as
  * V_e, *Nt the trainable ones they see as N (either may be NULL), internal_of_public[e] the internal column of public column e

@@ -71,7 +71,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_ll_foldin_layout', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_ll_foldin_layout', 'sert_debug_wfold_plan', 'sert_debug_wfold_index', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -92,6 +92,15 @@ EXPORTS_LL_FOLDIN = [
     'sert_ll_foldin_get_tensor', 'sert_ll_foldin_set_tensor',
 ]
 LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B = 0, 1, 2, 3, 4, 5
+# ... and include/sert_hip_wfold.h, which sert_hip.h includes as well (folding unseen WORDS into a trained vectorspace model)
+EXPORTS_WFOLD = [
+    'sert_wfold_create', 'sert_wfold_destroy', 'sert_wfold_upload', 'sert_wfold_num_batches',
+    'sert_wfold_train_batch', 'sert_wfold_train_batches', 'sert_wfold_eval_batch', 'sert_wfold_negatives_of_step',
+    'sert_wfold_get_rows', 'sert_wfold_set_rows', 'sert_wfold_set_step', 'sert_wfold_get_step',
+    'sert_wfold_set_eval_draws', 'sert_wfold_get_eval_draws',
+]
+WFOLD_ROWS, WFOLD_M, WFOLD_V = 0, 1, 2
+WFOLD_PROJECT_FORMS = ('none', 'vector', 'scalar')     # SERT_WFOLD_PROJECT_* (include/sert_hip_debug.h)
 FOLDIN_LOSS_FORMS = ('none', 'vector', 'scalar')       # SERT_FOLDIN_LOSS_* (include/sert_hip_debug.h)
 
 
@@ -140,6 +149,11 @@ class SertFoldInConfig(ctypes.Structure):
         ('eps', ctypes.c_float),
         ('seed', ctypes.c_uint64),
     ]
+
+
+class SertWFoldConfig(ctypes.Structure):
+    """sert_wfold_config (include/sert_hip_wfold.h)."""
+    _fields_ = list(SertFoldInConfig._fields_)
 
 
 class SertLlFoldInConfig(ctypes.Structure):
@@ -238,6 +252,26 @@ def load():
     lib.sert_ll_foldin_eval_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
     lib.sert_ll_foldin_get_tensor.argtypes = [vp, ctypes.c_int, fp, sz]
     lib.sert_ll_foldin_set_tensor.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_wfold_create.argtypes = [vp, i32, fp, ctypes.POINTER(SertWFoldConfig), ctypes.POINTER(vp)]
+    lib.sert_wfold_destroy.argtypes = [vp]
+    lib.sert_wfold_upload.argtypes = [vp, fp, fp, fp, i64]
+    lib.sert_wfold_num_batches.argtypes = [vp]
+    lib.sert_wfold_num_batches.restype = i64
+    lib.sert_wfold_train_batch.argtypes = [vp, i64, fp, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_wfold_train_batches.argtypes = [vp, fp, i64, fp]
+    lib.sert_wfold_eval_batch.argtypes = [vp, i64, fp, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_wfold_negatives_of_step.argtypes = [vp, i64, ctypes.c_int, fp]
+    lib.sert_wfold_get_rows.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_wfold_set_rows.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_wfold_set_step.argtypes = [vp, i64]
+    lib.sert_wfold_get_step.argtypes = [vp]
+    lib.sert_wfold_get_step.restype = i64
+    lib.sert_wfold_set_eval_draws.argtypes = [vp, i64]
+    lib.sert_wfold_get_eval_draws.argtypes = [vp]
+    lib.sert_wfold_get_eval_draws.restype = i64
+    lib.sert_debug_wfold_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    lib.sert_debug_wfold_index.argtypes = [fp, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, fp, fp, i64, fp, i64,
+                                           ctypes.POINTER(i64), ctypes.POINTER(i64)]
     lib.sert_score_topk.argtypes = [ctypes.c_int, fp, i64, i32, fp, i64, i32, fp, fp]
     lib.sert_scorer_create.argtypes = [ctypes.c_int, fp, i64, i32, ctypes.POINTER(vp)]
     lib.sert_scorer_destroy.argtypes = [vp]
@@ -1255,6 +1289,143 @@ class FoldIn(object):
             self.close()
         except Exception:
             pass
+
+
+class WordFoldIn(object):
+    """Owner of one sert_wfold handle (include/sert_hip_wfold.h): ``num_new_words`` word rows learnt on top of the frozen
+    parameters of ``engine`` (a vectorspace Engine), which are copied at construction -- the engine may train on or be
+    closed afterwards.  New word v is token id ``vocab_size + v``; labels and negatives are trained entities."""
+
+    def __init__(self, engine, new_rows_init, batch_size, num_negatives, lambda_, lr=1e-3, beta1=0.9, beta2=0.999,
+                 eps=1e-8, seed=0):
+        self._lib = load()
+        self._h = None
+        rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != engine.cfg.word_dim:
+            raise SertError('new_rows_init must be (num_new_words, word_dim)')
+        c = SertWFoldConfig()
+        c.struct_size = ctypes.sizeof(SertWFoldConfig)
+        c.batch_size, c.num_negatives, c.lambda_ = int(batch_size), int(num_negatives), float(lambda_)
+        c.lr, c.beta1, c.beta2, c.eps, c.seed = float(lr), float(beta1), float(beta2), float(eps), int(seed)
+        self.cfg = c
+        self.num_new_words, self.word_dim = int(rows.shape[0]), int(rows.shape[1])
+        self.vocab_size = int(engine.cfg.vocab_size)
+        self.num_entities = int(engine.cfg.num_entities)
+        self.window_size = int(engine.cfg.window_size)
+        h = ctypes.c_void_p()
+        check(self._lib.sert_wfold_create(engine._h, self.num_new_words, rows.ctypes.data if rows.size else None,
+                                          ctypes.byref(c), ctypes.byref(h)))
+        self._h = h
+
+    def upload(self, x, y, w=None):
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if x.ndim != 2 or x.shape[1] != self.window_size or y.shape != (x.shape[0],):
+            raise SertError('x must be (M, window_size) and y (M,)')
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != y.shape:
+                raise SertError('w must be (M,)')
+        check(self._lib.sert_wfold_upload(self._h, _addr(x), _addr(y), _addr(w), x.shape[0]))
+
+    def num_batches(self):
+        return int(self._lib.sert_wfold_num_batches(self._h))
+
+    def _negatives(self, negatives):
+        if negatives is not None:
+            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
+            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
+        return negatives
+
+    def train_batch(self, batch_index, negatives=None):
+        loss = ctypes.c_float()
+        negatives = self._negatives(negatives)
+        check(self._lib.sert_wfold_train_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
+        return np.float32(loss.value)
+
+    def train_batches(self, batch_indices):
+        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
+        out = np.empty(idx.size, dtype=np.float32)
+        check(self._lib.sert_wfold_train_batches(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
+        return out
+
+    def eval_batch(self, batch_index, negatives=None):
+        loss = ctypes.c_float()
+        negatives = self._negatives(negatives)
+        check(self._lib.sert_wfold_eval_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
+        return np.float32(loss.value)
+
+    def negatives_of_step(self, position, evaluation=False):
+        """(B, z) int64 in [0, num_entities): what the device sampler draws at training position `position` (= get_step()
+        before the step) or for the `position`-th evaluation draw."""
+        out = np.empty((self.cfg.batch_size, self.cfg.num_negatives), dtype=np.int64)
+        check(self._lib.sert_wfold_negatives_of_step(self._h, int(position), int(bool(evaluation)), out.ctypes.data))
+        return out
+
+    def get_rows(self, which=WFOLD_ROWS):
+        out = np.empty((self.num_new_words, self.word_dim), dtype=np.float32)
+        check(self._lib.sert_wfold_get_rows(self._h, int(which), out.ctypes.data, out.size))
+        return out
+
+    def set_rows(self, which, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        check(self._lib.sert_wfold_set_rows(self._h, int(which), a.ctypes.data, a.size))
+
+    def set_step(self, t):
+        check(self._lib.sert_wfold_set_step(self._h, int(t)))
+
+    def get_step(self):
+        return int(self._lib.sert_wfold_get_step(self._h))
+
+    def set_eval_draws(self, n):
+        check(self._lib.sert_wfold_set_eval_draws(self._h, int(n)))
+
+    def get_eval_draws(self):
+        return int(self._lib.sert_wfold_get_eval_draws(self._h))
+
+    def plan(self):
+        """sert_debug_wfold_plan (test hook): what the last step of this handle launched -- 'project' (none / vector / scalar:
+        the instance of wfold_project), 'loss' (per_candidate: vs_nce; scalar: vs_nce_scalar), 'k' (its template parameter),
+        'train', 'levels' of the batch's reduction and its 'items' per level, 'segsum' (rows32 / rows64 / scalar; none without
+        a level), 'gemm_p' / 'gemm_g' (GEMM_ROUTES; gemm_g is 'none' after an evaluation).  All zero before the first step."""
+        v = (ctypes.c_int32 * 16)()
+        check(self._lib.sert_debug_wfold_plan(self._h, v, 16))
+        v = [int(x) for x in v]
+        route = lambda code: GEMM_ROUTES[code - 1] if code >= 1 else 'none'
+        return {'project': WFOLD_PROJECT_FORMS[v[0]], 'loss': NCE_FORMS[v[1]], 'k': v[2], 'train': bool(v[3]), 'levels': v[4],
+                'items': v[5:5 + v[4]], 'segsum': WGRAD_FORMS[v[11]], 'gemm_p': route(v[12]), 'gemm_g': route(v[13])}
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._lib.sert_wfold_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_wfold_index(tok, num_words, batch=0):
+    """Host only (sert_debug_wfold_index): the inverted index a word fold-in builds for batch `batch` of tok
+    (num_batches, B, n) int32 -- the new word of every position, or -1.  Returns a dict: 'levels', 'item_counts' and 'part_off'
+    per level, 'rows' (the entries: batch rows) and 'items' (k, 4) int32 {begin, end, dst, 0}, level after level."""
+    lib = load()
+    tok = np.ascontiguousarray(tok, dtype=np.int32)
+    assert tok.ndim == 3, tok.shape
+    nb, B, n = tok.shape
+    levels = np.zeros(13, dtype=np.int32)
+    nr, ni = ctypes.c_int64(), ctypes.c_int64()
+    args = (_addr(tok), nb, B, n, int(num_words), int(batch), levels.ctypes.data)
+    check(lib.sert_debug_wfold_index(*(args + (None, 0, None, 0, ctypes.byref(nr), ctypes.byref(ni)))))
+    rows = np.zeros(max(1, nr.value), dtype=np.int32)
+    items = np.zeros((max(1, ni.value), 4), dtype=np.int32)
+    check(lib.sert_debug_wfold_index(*(args + (rows.ctypes.data, rows.size, items.ctypes.data, items.shape[0], ctypes.byref(nr),
+                                               ctypes.byref(ni)))))
+    L = int(levels[0])
+    return {'levels': L, 'item_counts': [int(x) for x in levels[1:1 + L]], 'part_off': [int(x) for x in levels[7:7 + L]],
+            'rows': rows[:nr.value].copy(), 'items': items[:ni.value].copy()}
 
 
 class LlFoldIn(object):

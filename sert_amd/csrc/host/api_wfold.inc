@@ -1,0 +1,520 @@
+// Part of sert_hip.hip (one translation unit; included there, inside its extern "C" block): C ABI: folding unseen WORDS into
+// a trained vectorspace model (include/sert_hip_wfold.h: sert_wfold_*; kernels_wfold.h; wfold_index.h).  Like sert_foldin the
+// handle copies the model's parameters when it is created and runs on a stream of its own: it shares nothing with the model's
+// step schedule.
+
+struct sert_wfold {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    sert_wfold_config cfg;
+    int Vw = 0, Ve = 0, Nw = 0, dw = 0, de = 0, n = 0;
+    // the frozen snapshot; rw holds V_w + 1 rows: the last one is zero, what a new position gathers at upload
+    float *rw = nullptr, *W = nullptr, *b = nullptr, *re = nullptr;
+    // the new word rows, Adam's moments, the gradient
+    float *Nv = nullptr, *m1 = nullptr, *m2 = nullptr, *G = nullptr;
+    // the uploaded instances
+    int64_t M = 0;
+    int32_t* y = nullptr;
+    float* w = nullptr;
+    float* A0 = nullptr;             // (M, d_e)  hf W + b
+    int32_t* tok = nullptr;          // (M, n)    the new word of a position, -1: frozen
+    // the inverted index new word -> batch rows (wfold_index.h)
+    std::vector<WfoldBatch> idx_batches;
+    int32_t* idx_rows = nullptr;
+    int4* idx_items = nullptr;
+    float* part = nullptr;           // (max_part_rows, d_e)
+    // per-step scratch
+    float* P = nullptr;              // (Nw, d_e)  Nv W
+    float* T = nullptr;              // (B, d_e)
+    float* DA = nullptr;             // (B, d_e)
+    float* S = nullptr;              // (Nw, d_e)
+    int32_t* neg = nullptr;          // (B, z)
+    int64_t* neg_stage = nullptr;    // (B, z) host-supplied negatives
+    float* coef = nullptr;           // (B, 1 + z): written by the loss kernel, read by nobody (the entity table is frozen)
+    int32_t* cand = nullptr;         // (B, 1 + z): the same
+    float* rowloss = nullptr;        // (B)
+    float* red_loss = nullptr;       // per-workgroup loss partials of vs_nce
+    float* red_sq = nullptr;         // [kOptBlocks] sums of squares of Nv
+    float* d_loss = nullptr;         // [3]
+    float* d_losses = nullptr;       // multi-step loss ring
+    int64_t d_losses_cap = 0;
+    int64_t step = 0, eval_draws = 0;
+    // what the last step launched, recorded where the launches are made: sert_debug_wfold_plan (sert_hip_debug.h)
+    int32_t plan[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+static void wfold_free_upload(sert_wfold* f) {
+    for (void* p : {(void*)f->y, (void*)f->w, (void*)f->A0, (void*)f->tok, (void*)f->idx_rows, (void*)f->idx_items, (void*)f->part})
+        (void)hipFree(p);
+    f->y = nullptr; f->w = nullptr; f->A0 = nullptr; f->tok = nullptr; f->idx_rows = nullptr; f->idx_items = nullptr; f->part = nullptr;
+    f->idx_batches.clear();
+    f->M = 0;
+}
+
+int sert_wfold_destroy(sert_wfold* f) {
+    if (!f) return 0;
+    if (f->device >= 0) {
+        (void)hipSetDevice(f->device);
+        if (f->stream) (void)hipStreamSynchronize(f->stream);
+    }
+    wfold_free_upload(f);
+    for (void* p : {(void*)f->rw, (void*)f->W, (void*)f->b, (void*)f->re, (void*)f->Nv, (void*)f->m1, (void*)f->m2, (void*)f->G,
+                    (void*)f->P, (void*)f->T, (void*)f->DA, (void*)f->S, (void*)f->neg, (void*)f->neg_stage, (void*)f->coef,
+                    (void*)f->cand, (void*)f->rowloss, (void*)f->red_loss, (void*)f->red_sq, (void*)f->d_loss, (void*)f->d_losses})
+        (void)hipFree(p);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+    return 0;
+}
+
+static int wfold_create(sert_wfold* f, sert_model* m, int32_t num_new_words, const float* init_rows, const sert_wfold_config* cfg) {
+    const auto& c = m->cfg;
+    // ---- validation: everything the kernels index with is checked here ----
+    if (c.kind == SERT_KIND_LOGLINEAR) SERT_FAIL("a word fold-in needs a vectorspace model: the loglinear model is not supported");
+    if (c.kind != SERT_KIND_VECTORSPACE)
+        SERT_FAIL("a word fold-in needs the NCE vectorspace model: the full-softmax variant (SERT_KIND_VECTORSPACE_SOFTMAX) is not supported");
+    if (m->comm || m->host_ar || m->world > 1)
+        SERT_FAIL("a word fold-in of a data-parallel model (a communicator is attached) is not supported");
+    if (num_new_words < 1) SERT_FAIL("a word fold-in needs at least one new word (num_new_words >= 1)");
+    if (!init_rows) SERT_FAIL("null argument");
+    if (cfg->batch_size < 1 || cfg->num_negatives < 1) SERT_FAIL("a word fold-in needs batch_size >= 1 and num_negatives >= 1");
+    if (!(cfg->lambda_ >= 0.f)) SERT_FAIL("regularization lambda must be >= 0");
+    if (c.entity_dim > 512) SERT_FAIL("entity_dim > 512 is not supported");
+    if ((int64_t)c.vocab_size + num_new_words > INT32_MAX) SERT_FAIL("more than 2^31 - 1 rows in the extended word table");
+    if ((int64_t)cfg->batch_size * (cfg->num_negatives + 1) > ((int64_t)1 << 30)) SERT_FAIL("batch_size * (num_negatives + 1) > 2^30");
+    if ((int64_t)cfg->batch_size * c.window_size > INT32_MAX) SERT_FAIL("batch_size * window_size > 2^31 - 1");
+    SERT_HIP(hipSetDevice(c.device));
+    f->device = c.device; f->cfg = *cfg;
+    f->Vw = c.vocab_size; f->Ve = c.num_entities; f->Nw = num_new_words; f->dw = c.word_dim; f->de = c.entity_dim; f->n = c.window_size;
+    const int B = cfg->batch_size, z = cfg->num_negatives, de = f->de, dw = f->dw, Nw = f->Nw;
+    const size_t n_v = (size_t)Nw * dw;
+    // the parameters as a reader must see them (sert_foldin_create)
+    SERT_TRY(ensure_full_rw(m));
+    SERT_TRY(ensure_rw_current(m, -1));
+    if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
+    if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
+    SERT_TRY(settle_entity_update(m));
+    flush_pending_tail(m);
+    SERT_TRY(dmalloc(&f->rw, round_up(m->n_rw + (size_t)dw, 4)));
+    SERT_TRY(dmalloc(&f->W, m->n_w));
+    SERT_TRY(dmalloc(&f->b, m->n_b));
+    SERT_TRY(dmalloc(&f->re, std::max<size_t>(m->n_re, 4)));
+    SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipMemsetAsync(f->rw + m->n_rw, 0, (round_up(m->n_rw + (size_t)dw, 4) - m->n_rw) * sizeof(float), m->stream));
+    SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    if (m->n_re) SERT_HIP(hipMemcpyAsync(f->re, m->re, m->n_re * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_HIP(hipStreamCreate(&f->stream));
+    hipStream_t s = f->stream;
+    SERT_TRY(dmalloc(&f->Nv, round_up(n_v, 4)));
+    SERT_TRY(dzalloc(&f->m1, round_up(n_v, 4), s));
+    SERT_TRY(dzalloc(&f->m2, round_up(n_v, 4), s));
+    SERT_TRY(dmalloc(&f->G, round_up(n_v, 4)));
+    SERT_HIP(hipMemcpyAsync(f->Nv, init_rows, n_v * sizeof(float), hipMemcpyHostToDevice, s));
+    const size_t total = (size_t)B * (z + 1);
+    SERT_TRY(dmalloc(&f->P, (size_t)Nw * de));
+    SERT_TRY(dmalloc(&f->S, (size_t)Nw * de));
+    SERT_TRY(dmalloc(&f->T, (size_t)B * de));
+    SERT_TRY(dmalloc(&f->DA, (size_t)B * de));
+    SERT_TRY(dmalloc(&f->neg, (size_t)B * z));
+    SERT_TRY(dmalloc(&f->neg_stage, (size_t)B * z));
+    SERT_TRY(dmalloc(&f->coef, total));
+    SERT_TRY(dmalloc(&f->cand, total));
+    SERT_TRY(dmalloc(&f->rowloss, (size_t)B));
+    SERT_TRY(dmalloc(&f->red_loss, (size_t)cdiv(B, 16)));
+    SERT_TRY(dmalloc(&f->red_sq, (size_t)kOptBlocks));
+    SERT_TRY(dmalloc(&f->d_loss, (size_t)3));
+    SERT_HIP(hipStreamSynchronize(s));             // (init_rows is borrowed for the call only)
+    SERT_HIP(hipStreamSynchronize(m->stream));     // (the snapshot is complete: the model may train or go away)
+    return 0;
+}
+
+int sert_wfold_create(sert_model* m, int32_t num_new_words, const float* init_rows, const sert_wfold_config* cfg, sert_wfold** out) {
+    refresh_gemm_choice();
+    if (!m || !cfg || !out) SERT_FAIL("null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(sert_wfold_config)) SERT_FAIL("sert_wfold_config size mismatch (ABI)");
+    sert_wfold* f = new sert_wfold();
+    const int rc = wfold_create(f, m, num_new_words, init_rows, cfg);
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        sert_wfold_destroy(f);
+        g_last_error = keep;
+        return rc;
+    }
+    *out = f;
+    return 0;
+}
+
+// launch_gemm, and the route it takes (gemm.h: GemmRoute) -- asked of the launcher's own predicates, for the plan
+extern "C++" {
+template <bool TA, bool TB, int EPI>
+static int wfold_gemm(hipStream_t s, const float* A, const float* Bm, float* C, const float* bias, int M, int N, int K, int lda,
+                      int ldb, int ldc) {
+    const int route = gemm_takes_x3(TA, TB, EPI, false, false, A, Bm, M, N, K, lda, ldb, 1, K)
+                          ? (TA ? x3_ta_route(M, N) : x3_route(TB, A, Bm, M, N, K, lda, ldb, 1))
+                          : gemm_f32_route(TA, TB, EPI, false, A, Bm, M, N, K, lda, ldb, 1, K);
+    launch_gemm<TA, TB, EPI>(s, A, Bm, C, bias, M, N, K, lda, ldb, ldc);
+    return route;
+}
+}  // extern "C++"
+
+int sert_wfold_upload(sert_wfold* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
+    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+    const int n = f->n, dw = f->dw, de = f->de, B = f->cfg.batch_size;
+    // host-side validation: no kernel is launched on bad ids
+    for (int64_t i = 0; i < M; ++i)
+        if (y[i] < 0 || y[i] >= f->Ve) SERT_FAIL("fold-in label out of range [0, num_entities)");
+    const int64_t ext = (int64_t)f->Vw + f->Nw;
+    for (int64_t i = 0; i < M * n; ++i)
+        if (x[i] < 0 || x[i] >= ext) SERT_FAIL("token id out of range [0, vocab_size + num_new_words)");
+    SERT_HIP(hipSetDevice(f->device));
+    hipStream_t s = f->stream;
+    SERT_HIP(hipStreamSynchronize(s));
+    wfold_free_upload(f);
+    if (M == 0) return 0;
+    // the inverted index of the complete batches (host; a function of the upload alone)
+    const int64_t nbatches = M / B;
+    WfoldIndex index;
+    {
+        std::vector<int32_t> tok((size_t)(nbatches * B) * n);
+        for (size_t k = 0; k < tok.size(); ++k) tok[k] = x[k] < f->Vw ? -1 : x[k] - f->Vw;
+        build_wfold_index(tok.data(), nbatches, B, n, f->Nw, index);
+    }
+    uint32_t* dx = nullptr;
+    int32_t* xs = nullptr;
+    float* H = nullptr;
+    const int64_t slab = std::min<int64_t>(M, 65536);
+    auto body = [&]() -> int {
+        SERT_TRY(dmalloc(&f->y, (size_t)M));
+        SERT_TRY(dmalloc(&f->w, (size_t)M));
+        SERT_TRY(dmalloc(&f->A0, (size_t)M * de));
+        SERT_TRY(dmalloc(&f->tok, (size_t)M * n));
+        SERT_TRY(dmalloc(&f->idx_rows, std::max<size_t>(index.rows.size(), 1)));
+        SERT_TRY(dmalloc(&f->idx_items, std::max<size_t>(index.items.size(), 1)));
+        SERT_TRY(dmalloc(&f->part, std::max<size_t>((size_t)index.max_part_rows * de, 4)));
+        SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        const std::vector<float> ones(w ? (size_t)0 : (size_t)M, 1.0f);
+        SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
+        if (!index.rows.empty())
+            SERT_HIP(hipMemcpyAsync(f->idx_rows, index.rows.data(), index.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!index.items.empty())
+            SERT_HIP(hipMemcpyAsync(f->idx_items, index.items.data(), index.items.size() * sizeof(SegItem), hipMemcpyHostToDevice, s));
+        // A0 = hf W + b once, by the model's forward (vs_gather_mean on the snapshot, the new positions pointed at its appended
+        // zero row; the projection GEMM), a slab of rows at a time
+        SERT_TRY(dmalloc(&xs, (size_t)slab * n));
+        SERT_TRY(dmalloc(&dx, (size_t)slab * n));
+        SERT_TRY(dmalloc(&H, (size_t)slab * dw));
+        for (int64_t r0 = 0; r0 < M; r0 += slab) {
+            const int rows = (int)std::min<int64_t>(slab, M - r0);
+            SERT_HIP(hipMemcpyAsync(xs, x + (size_t)r0 * n, (size_t)rows * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            launch(wfold_split_ids, dim3(grid_for((int64_t)rows * n)), dim3(256), 0, s, (const int32_t*)xs, dx, f->tok + (size_t)r0 * n,
+                   (int64_t)rows * n, f->Vw);
+            if (dw % 4 == 0)
+                launch((vs_gather_mean<uint32_t, 4>), dim3(grid_for((int64_t)rows * dw / 4, 256, 1 << 20)), dim3(256), 0, s,
+                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
+            else
+                launch((vs_gather_mean<uint32_t, 1>), dim3(grid_for((int64_t)rows * dw, 256, 1 << 20)), dim3(256), 0, s,
+                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
+            launch_gemm<false, false, EPI_BIAS>(s, H, f->W, f->A0 + (size_t)r0 * de, f->b, rows, de, dw, dw, de, de);
+        }
+        SERT_HIP(hipGetLastError());
+        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w and the host index are borrowed for the call only)
+        return 0;
+    };
+    const int rc = body();
+    (void)hipFree(dx); (void)hipFree(xs); (void)hipFree(H);
+    if (rc != 0) {
+        const std::string keep = g_last_error;
+        (void)hipStreamSynchronize(s);
+        wfold_free_upload(f);
+        g_last_error = keep;
+        return rc;
+    }
+    f->idx_batches.swap(index.batches);
+    f->M = M;
+    return 0;
+}
+
+int64_t sert_wfold_num_batches(sert_wfold* f) { return f ? f->M / f->cfg.batch_size : -1; }
+
+// the step's negatives into f->neg: the caller's (validated before anything is launched) or the Philox sampler's over V_e
+static int wfold_negatives(sert_wfold* f, const int64_t* negatives, uint64_t stream_pos) {
+    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
+    if (negatives) {
+        for (int64_t i = 0; i < count; ++i)
+            if (negatives[i] < 0 || negatives[i] >= f->Ve) SERT_FAIL("negative sample out of range [0, num_entities)");
+        SERT_HIP(hipMemcpyAsync(f->neg_stage, negatives, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
+        launch(convert_i64_to_i32, dim3(grid_for(count)), dim3(256), 0, f->stream, (const int64_t*)f->neg_stage, f->neg, count);
+    } else {
+        // (even = training draws, odd = evaluation draws, as the model's sampler)
+        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, f->stream, f->neg, count, (int64_t)0,
+               (uint32_t)f->Ve, f->cfg.seed, stream_pos, (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
+    }
+    return 0;
+}
+
+// steps 1 to 3 on batch `batch`: P = Nv W, T = tanh(A0 + sum P / n), the model's loss kernel on T (train: weighted, DA
+// written).  *parts / *n_parts: the loss partials it left.
+static int wfold_forward_loss(sert_wfold* f, int64_t batch, bool train, const float** parts, int* n_parts) {
+    const int B = f->cfg.batch_size, z = f->cfg.num_negatives, de = f->de, dw = f->dw, n = f->n;
+    hipStream_t s = f->stream;
+    const size_t row0 = (size_t)batch * B;
+    for (int32_t& v : f->plan) v = 0;
+    f->plan[12] = wfold_gemm<false, false, EPI_STORE>(s, f->Nv, f->W, f->P, nullptr, f->Nw, de, dw, dw, de, de);
+    const bool vector = de % 4 == 0;
+    if (vector)
+        launch((wfold_project<4>), dim3(grid_for((int64_t)B * de / 4, 256, 1 << 20)), dim3(256), 0, s, (const float*)(f->A0 + row0 * de),
+               (const int32_t*)(f->tok + row0 * n), (const float*)f->P, f->T, B, n, de);
+    else
+        launch((wfold_project<1>), dim3(grid_for((int64_t)B * de, 256, 1 << 20)), dim3(256), 0, s, (const float*)(f->A0 + row0 * de),
+               (const int32_t*)(f->tok + row0 * n), (const float*)f->P, f->T, B, n, de);
+    f->plan[0] = vector ? SERT_WFOLD_PROJECT_VECTOR : SERT_WFOLD_PROJECT_SCALAR;
+    const int32_t* y = f->y + row0;
+    const float* w = train ? f->w + row0 : (const float*)nullptr;
+    const float inv_batch = 1.0f / (float)B;
+    const int k = vector ? cdiv(de / 4, 16) : cdiv(de, 64);
+    const dim3 grid(cdiv(B, vector ? 16 : 4)), block(256);
+    const bool launched = dispatch_int<1, 8>(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if (vector) {
+            if (train) launch((vs_nce<K, true>), grid, block, 0, s, (const float*)f->T, (const float*)f->re, y, (const int32_t*)f->neg, w,
+                              f->DA, f->coef, f->cand, f->rowloss, B, z, de, inv_batch, f->red_loss);
+            else launch((vs_nce<K, false>), grid, block, 0, s, (const float*)f->T, (const float*)f->re, y, (const int32_t*)f->neg, w,
+                        f->DA, f->coef, f->cand, f->rowloss, B, z, de, inv_batch, f->red_loss);
+        } else {
+            if (train) launch((vs_nce_scalar<K, true>), grid, block, 0, s, (const float*)f->T, (const float*)f->re, y,
+                              (const int32_t*)f->neg, w, f->DA, f->coef, f->cand, f->rowloss, B, z, de, inv_batch);
+            else launch((vs_nce_scalar<K, false>), grid, block, 0, s, (const float*)f->T, (const float*)f->re, y,
+                        (const int32_t*)f->neg, w, f->DA, f->coef, f->cand, f->rowloss, B, z, de, inv_batch);
+        }
+    });
+    if (!launched) SERT_FAIL("entity_dim > 512 is not supported");
+    // (the scalar layout leaves no workgroup partials: the rows' losses themselves)
+    *parts = vector ? f->red_loss : f->rowloss;
+    *n_parts = vector ? cdiv(B, 16) : B;
+    f->plan[1] = vector ? SERT_NCE_FORM_PER_CANDIDATE : SERT_NCE_FORM_SCALAR; f->plan[2] = k; f->plan[3] = train ? 1 : 0;
+    return 0;
+}
+
+// step 4: S[v] = (sum of the DA rows of v's occurrences in the batch) / n over the batch's index, level after level -- the
+// kernels of the word-gradient tree (kernels_seg.h) as word_grad_segsum launches them; rows of absent words stay zero
+static int wfold_segsum(sert_wfold* f, int64_t batch) {
+    const int de = f->de;
+    hipStream_t s = f->stream;
+    const WfoldBatch& bx = f->idx_batches[(size_t)batch];
+    SERT_HIP(hipMemsetAsync(f->S, 0, (size_t)f->Nw * de * sizeof(float), s));
+    const float divisor = (float)f->n;
+    f->plan[4] = bx.nlevels;
+    for (int l = 0; l < bx.nlevels; ++l) {
+        const int nitems = bx.item_cnt[l];
+        f->plan[5 + l] = nitems;
+        if (nitems == 0) continue;
+        const float* in = (l == 0) ? f->DA : f->part + (size_t)bx.part_off[l - 1] * de;
+        const int32_t* rows = (l == 0) ? f->idx_rows + bx.rows_off : nullptr;
+        const int4* items = f->idx_items + bx.item_off[l];
+        float* pout = f->part + (size_t)bx.part_off[l] * de;
+        if (de % 4 == 0) {
+            const int ch = de / 4;
+            const bool seg32y = ch > 64 && 64 * cdiv(ch, 64) > 32 * cdiv(ch, 32);
+            if (ch <= 32 || seg32y) {
+                launch((segsum_rows<32>), dim3(cdiv(nitems, 8), ch <= 32 ? 1 : cdiv(ch, 32)), dim3(256), 0, s, in, rows, items, nitems,
+                       f->S, pout, de, divisor, (unsigned char*)nullptr, 1, nullptr, nullptr, DenseSlots(), XcdLists());
+                f->plan[11] = SERT_WGRAD_FORM_ROWS32;
+            } else {
+                launch((segsum_rows<64>), dim3(cdiv(nitems, 4), cdiv(ch, 64)), dim3(256), 0, s, in, rows, items, nitems, f->S, pout, de,
+                       divisor, (unsigned char*)nullptr, 1, nullptr, nullptr, DenseSlots(), XcdLists());
+                f->plan[11] = SERT_WGRAD_FORM_ROWS64;
+            }
+        } else {
+            launch((segsum_rows_scalar<false>), dim3(cdiv(nitems, 4), cdiv(de, 64)), dim3(256), 0, s, in, rows, items, nitems, f->S,
+                   pout, de, divisor, (unsigned char*)nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr);
+            f->plan[11] = SERT_WGRAD_FORM_SCALAR;
+        }
+    }
+    return 0;
+}
+
+static int wfold_check_batch(sert_wfold* f, int64_t batch) {
+    if (!f) SERT_FAIL("null argument");
+    if (!f->A0) SERT_FAIL("no fold-in instances uploaded (sert_wfold_upload)");
+    if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
+    return 0;
+}
+
+// one step enqueued on the handle's stream; dst: 3 floats on the device (finalize_loss: loss, data term, regulariser)
+static int wfold_step_async(sert_wfold* f, int64_t batch, const int64_t* negatives, float* dst) {
+    const auto& c = f->cfg;
+    const int B = c.batch_size;
+    hipStream_t s = f->stream;
+    SERT_TRY(wfold_negatives(f, negatives, (uint64_t)f->step * 2));
+    const float* parts = nullptr;
+    int n_parts = 0;
+    SERT_TRY(wfold_forward_loss(f, batch, true, &parts, &n_parts));
+    SERT_TRY(wfold_segsum(f, batch));
+    // G = S W^T: the form of the step's dh GEMM
+    f->plan[13] = wfold_gemm<false, true, EPI_STORE>(s, f->S, f->W, f->G, nullptr, f->Nw, f->dw, f->de, f->de, f->de, f->dw);
+    // Adam over Nv with the model's arithmetic, exactly as foldin_step_async runs it
+    f->step += 1;
+    const float tf = (float)f->step;
+    AdamArgs aa{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr * sqrtf(1.0f - powf(c.beta2, tf)) / (1.0f - powf(c.beta1, tf)),
+                c.beta1, c.beta2, c.eps};
+    const size_t n_v = (size_t)f->Nw * f->dw;
+    const int nb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)n_v, 4), 256)));
+    launch((adam_l2<false>), dim3(nb), dim3(256), 0, s, f->Nv, f->G, f->m1, f->m2, n_v, aa, f->red_sq, (const uint32_t*)nullptr,
+           1u, (int)kRowsAll, (float*)nullptr);
+    launch(finalize_loss, dim3(1), dim3(256), 0, s, parts, n_parts, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0,
+           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    return 0;
+}
+
+int sert_wfold_train_batch(sert_wfold* f, int64_t batch, const int64_t* negatives, float* loss_out) {
+    refresh_gemm_choice();
+    SERT_TRY(wfold_check_batch(f, batch));
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_TRY(wfold_step_async(f, batch, negatives, f->d_loss));
+    float host[3] = {0.f, 0.f, 0.f};
+    SERT_HIP(hipGetLastError());
+    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (loss_out) *loss_out = host[0];
+    return 0;
+}
+
+int sert_wfold_train_batches(sert_wfold* f, const int64_t* batches, int64_t count, float* losses_out) {
+    refresh_gemm_choice();
+    if (!f || count < 0 || (count > 0 && !batches)) SERT_FAIL("bad argument");
+    for (int64_t i = 0; i < count; ++i) SERT_TRY(wfold_check_batch(f, batches[i]));    // (before anything is enqueued)
+    if (count == 0) return 0;
+    SERT_HIP(hipSetDevice(f->device));
+    if (count > f->d_losses_cap) {
+        SERT_HIP(hipStreamSynchronize(f->stream));
+        (void)hipFree(f->d_losses);
+        f->d_losses = nullptr; f->d_losses_cap = 0;
+        SERT_TRY(dmalloc(&f->d_losses, (size_t)count * 3));
+        f->d_losses_cap = count;
+    }
+    for (int64_t i = 0; i < count; ++i) SERT_TRY(wfold_step_async(f, batches[i], nullptr, f->d_losses + 3 * i));
+    SERT_HIP(hipGetLastError());
+    std::vector<float> tmp((size_t)count * 3);
+    SERT_HIP(hipMemcpyAsync(tmp.data(), f->d_losses, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (losses_out)
+        for (int64_t i = 0; i < count; ++i) losses_out[i] = tmp[(size_t)3 * i];
+    return 0;
+}
+
+int sert_wfold_eval_batch(sert_wfold* f, int64_t batch, const int64_t* negatives, float* loss_out) {
+    refresh_gemm_choice();
+    SERT_TRY(wfold_check_batch(f, batch));
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_TRY(wfold_negatives(f, negatives, (uint64_t)f->eval_draws * 2 + 1));
+    if (!negatives) ++f->eval_draws;
+    const float* parts = nullptr;
+    int n_parts = 0;
+    SERT_TRY(wfold_forward_loss(f, batch, false, &parts, &n_parts));
+    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, parts, n_parts, parts, 0, 1.0f / (float)f->cfg.batch_size, 0.0f,
+           f->d_loss, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    float host[3] = {0.f, 0.f, 0.f};
+    SERT_HIP(hipGetLastError());
+    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    if (loss_out) *loss_out = host[0];
+    return 0;
+}
+
+int sert_wfold_negatives_of_step(sert_wfold* f, int64_t position, int evaluation, int64_t* out) {
+    if (!f || !out || position < 0) SERT_FAIL("bad argument");
+    SERT_HIP(hipSetDevice(f->device));
+    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
+    int32_t* tmp = nullptr;
+    SERT_HIP(hipMalloc((void**)&tmp, (size_t)count * sizeof(int32_t)));
+    // a stream of its own: nothing of the handle's state is touched
+    hipStream_t st = nullptr;
+    if (hipStreamCreate(&st) != hipSuccess) { (void)hipFree(tmp); SERT_FAIL("hipStreamCreate failed"); }
+    launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count, (int64_t)0, (uint32_t)f->Ve,
+           f->cfg.seed, (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
+    std::vector<int32_t> host((size_t)count);
+    const hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    (void)hipFree(tmp);
+    if (e != hipSuccess || e2 != hipSuccess) SERT_FAIL("reading the negatives back failed");
+    for (int64_t i = 0; i < count; ++i) out[i] = host[(size_t)i];
+    return 0;
+}
+
+static float* wfold_rows_ref(sert_wfold* f, int which) {
+    return which == SERT_WFOLD_ROWS ? f->Nv : which == SERT_WFOLD_M ? f->m1 : which == SERT_WFOLD_V ? f->m2 : nullptr;
+}
+
+int sert_wfold_get_rows(sert_wfold* f, int which, float* host, size_t count) {
+    if (!f || !host) SERT_FAIL("null argument");
+    float* p = wfold_rows_ref(f, which);
+    if (!p) SERT_FAIL("which must be SERT_WFOLD_ROWS, SERT_WFOLD_M or SERT_WFOLD_V");
+    if (count != (size_t)f->Nw * f->dw) SERT_FAIL("element count mismatch");
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_HIP(hipMemcpyAsync(host, p, count * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int sert_wfold_set_rows(sert_wfold* f, int which, const float* host, size_t count) {
+    if (!f || !host) SERT_FAIL("null argument");
+    float* p = wfold_rows_ref(f, which);
+    if (!p) SERT_FAIL("which must be SERT_WFOLD_ROWS, SERT_WFOLD_M or SERT_WFOLD_V");
+    if (count != (size_t)f->Nw * f->dw) SERT_FAIL("element count mismatch");
+    SERT_HIP(hipSetDevice(f->device));
+    SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int sert_wfold_set_step(sert_wfold* f, int64_t t) {
+    if (!f || t < 0) SERT_FAIL("bad argument");
+    f->step = t;
+    return 0;
+}
+int64_t sert_wfold_get_step(sert_wfold* f) { return f ? f->step : -1; }
+int sert_wfold_set_eval_draws(sert_wfold* f, int64_t n) {
+    if (!f || n < 0) SERT_FAIL("bad argument");
+    f->eval_draws = n;
+    return 0;
+}
+int64_t sert_wfold_get_eval_draws(sert_wfold* f) { return f ? f->eval_draws : -1; }
+
+int sert_debug_wfold_plan(sert_wfold* f, int32_t* out, int n) {
+    if (!f || !out || n < 1 || n > 16) SERT_FAIL("bad argument");
+    for (int i = 0; i < n; ++i) out[i] = f->plan[i];
+    return 0;
+}
+
+// Host only: the index build_wfold_index makes for batch `batch` of tok (num_batches, B, n) -- new word or -1 per position --
+// as flat arrays: levels[0] = the levels, levels[1 + l] = the items of level l, levels[7 + l] = the first partial row of level
+// l's output; rows_out (<= rows_cap) the entries; items_out (<= items_cap items of four ints) the items, level after level.
+// *num_rows / *num_items: what the batch holds (also when the caps are too small: nothing is copied then, and 0 is returned).
+int sert_debug_wfold_index(const int32_t* tok, int64_t num_batches, int B, int n, int num_words, int64_t batch, int32_t* levels,
+                           int32_t* rows_out, int64_t rows_cap, int32_t* items_out, int64_t items_cap, int64_t* num_rows,
+                           int64_t* num_items) {
+    if (!tok || !levels || !num_rows || !num_items || num_batches < 1 || B < 1 || n < 1 || num_words < 1 || batch < 0 ||
+        batch >= num_batches)
+        SERT_FAIL("bad argument");
+    for (int64_t k = 0; k < num_batches * B * n; ++k)
+        if (tok[k] >= num_words) SERT_FAIL("new word out of range [0, num_words)");
+    WfoldIndex index;
+    build_wfold_index(tok, num_batches, B, n, num_words, index);
+    const WfoldBatch& bx = index.batches[(size_t)batch];
+    for (int i = 0; i < 13; ++i) levels[i] = 0;
+    levels[0] = bx.nlevels;
+    int64_t items = 0;
+    for (int l = 0; l < bx.nlevels; ++l) { levels[1 + l] = bx.item_cnt[l]; levels[7 + l] = (int32_t)bx.part_off[l]; items += bx.item_cnt[l]; }
+    *num_rows = bx.num_entries;
+    *num_items = items;
+    if (rows_out && rows_cap >= bx.num_entries && items_out && items_cap >= items) {
+        std::copy(index.rows.begin() + bx.rows_off, index.rows.begin() + bx.rows_off + bx.num_entries, rows_out);
+        if (items) memcpy(items_out, index.items.data() + bx.item_off[0], (size_t)items * sizeof(SegItem));
+    }
+    return 0;
+}

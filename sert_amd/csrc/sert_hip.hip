@@ -41,6 +41,8 @@
 #include "kernels_vs.h"
 #include "kernels_foldin.h"
 #include "kernels_ll_foldin.h"
+#include "kernels_wfold.h"
+#include "wfold_index.h"
 #include "ll_label_remap.h"
 #ifdef SERT_VARIANTS
 #include "variants/kernels_gather_hot.h"
@@ -200,6 +202,8 @@ extern "C" {
 #include "host/api_foldin.inc"
 
 #include "host/api_ll_foldin.inc"
+
+#include "host/api_wfold.inc"
 
 #include "host/api_comm.inc"
 

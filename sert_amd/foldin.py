@@ -7,6 +7,10 @@ entities' instances.  ``EntityFoldIn`` is that, on the device; ``bin/fold_in.py`
 ``LogLinearFoldIn`` is the same for a trained loglinear (expert-finding) model (include/sert_hip_ll_foldin.h): the word table
 and the trained columns of the output layer stay fixed and the new entities' columns and biases learn.  With ``refresh`` the
 columns and biases of trained entities that gained documents learn too (bin/fold_in.py --unfreeze_known).
+
+``WordFoldIn`` is the other half of a catalogue that changes after training (include/sert_hip_wfold.h): the VOCABULARY grows.
+The trained word rows, the projection and the whole entity table stay fixed and only the rows of the new words learn
+(bin/prepare.py --extend_vocabulary, bin/fold_in.py --new_words).
 """
 import logging
 import pickle
@@ -345,6 +349,142 @@ class LogLinearFoldIn(models.ModelInterface):
         self._foldin.close()
 
 
+def new_word_rows(vocab_size, num_new_words, word_dim):
+    """(Nw, d_w) initial rows from the global np.random, uniform within the bound bin/train.py drew the trained R_w in:
+    Glorot's sqrt(6 / (V_w + d_w)), the fan of the trained table.  (Glorot on the (Nw, d_w) block alone would make a handful
+    of new rows several times larger than every trained one.)"""
+    a = np.sqrt(6.0 / (vocab_size + word_dim))
+    return np.random.uniform(low=-a, high=a, size=(num_new_words, word_dim)).astype(np.float32)
+
+
+class WordFoldIn(models.ModelInterface):
+    """Nw new word rows learnt on top of a trained vectorspace model (R_w, R_e, W, b: host arrays, never written).
+
+    training_set: (x (M, window_size) token ids in [0, V_w + Nw) -- new word v is id V_w + v --, y (M,) trained entity
+    indices in [0, V_e), w (M,) weights or None).  ``new_rows_init`` None: Nw = x.max() + 1 - V_w rows drawn by
+    ``new_word_rows``, at the scale bin/train.py drew the trained rows.  The batch size, the number of negatives, lambda and the
+    learning rate are the fold-in's own.  An instance without a new word is legal: it adds to the loss and moves nothing."""
+
+    #: callable batch_index -> (B, z) int64 negatives in [0, V_e), or None (device sampler)
+    negative_sampler = None
+    #: same, for train_error()
+    eval_negative_sampler = None
+    #: batches issued to the device before their losses are read back (device-drawn negatives only)
+    steps_per_sync = 1
+
+    def __init__(self, R_w, R_e, W, b, new_rows_init, training_set, batch_size, num_negative_samples,
+                 regularization_lambda, window_size, seed=None, lr=1e-3, device=0, _engine=None):
+        super(WordFoldIn, self).__init__(batch_size)
+        x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
+        w = training_set[2] if len(training_set) > 2 else None
+        assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        vocab_size, word_dim = int(np.shape(R_w)[0]), int(np.shape(R_w)[1])
+        if new_rows_init is None:
+            if not x.size or int(x.max()) < vocab_size:
+                raise RuntimeError('no token of a new word and no initial rows: nothing says how many words are new')
+            new_rows_init = new_word_rows(vocab_size, int(x.max()) + 1 - vocab_size, word_dim)
+        new_rows_init = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        if seed is None:
+            seed = int(np.random.randint(low=0, high=(1 << 30)))
+        self.window_size = int(window_size)
+        self.num_new_words = int(new_rows_init.shape[0])
+        self.vocab_size = vocab_size
+        self.training_num_instances = int(y.shape[0])
+        _capi.require_gpu()
+        engine, owned = _engine, False
+        if engine is None:
+            # a parameters-only model on the device holds the frozen tensors for the moment of the copy
+            R_w, R_e = np.asarray(R_w, dtype=np.float32), np.asarray(R_e, dtype=np.float32)
+            W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
+            assert W.shape == (R_w.shape[1], R_e.shape[1]) and b.shape == (R_e.shape[1],)
+            engine = _capi.Engine(
+                kind=_capi.KIND_VECTORSPACE, batch_size=1, global_batch_size=1, window_size=self.window_size,
+                vocab_size=R_w.shape[0], num_entities=R_e.shape[0], word_dim=R_w.shape[1], entity_dim=R_e.shape[1],
+                num_negatives=0, id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0,
+                lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0)
+            owned = True
+            for which, value in ((_capi.T_RW, R_w), (_capi.T_RE, R_e), (_capi.T_W, W), (_capi.T_B, b)):
+                engine.set_tensor(which, value)
+        try:
+            self._foldin = _capi.WordFoldIn(engine, new_rows_init, batch_size, num_negative_samples, regularization_lambda,
+                                            lr=lr, seed=seed)
+        finally:
+            if owned:
+                engine.close()      # (the handle copied what it needs)
+        self._foldin.upload(x, y, w)
+        logging.info('Folding in %d new words (token ids %d .. %d) on %d instances.', self.num_new_words, vocab_size,
+                     vocab_size + self.num_new_words - 1, self.training_num_instances)
+
+    @classmethod
+    def from_model(cls, model, new_rows_init, training_set, batch_size, num_negative_samples, regularization_lambda,
+                   seed=None, lr=1e-3):
+        """From a live ``models.VectorSpaceLanguageModel``: its parameters as they are now are copied on the device (the
+        model may train on or be dropped afterwards)."""
+        if not isinstance(model, models.VectorSpaceLanguageModel):
+            raise RuntimeError('a word fold-in needs a VectorSpaceLanguageModel')
+        cfg = model._engine.cfg
+        return cls(_Shape((int(cfg.vocab_size), int(cfg.word_dim))), None, None, None, new_rows_init, training_set, batch_size,
+                   num_negative_samples, regularization_lambda, model.window_size, seed=seed, lr=lr, _engine=model._engine)
+
+    # -- the step functions ---------------------------------------------------------------------------------------
+    def train_fn(self, batch_index):
+        sampler = self.negative_sampler
+        return self._foldin.train_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
+
+    def test_fn(self, batch_index):
+        sampler = self.eval_negative_sampler
+        return self._foldin.eval_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
+
+    def train(self):
+        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
+        count = self.training_num_instances
+        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
+        if self.steps_per_sync > 1 and self.negative_sampler is None:
+            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
+                                                       report_interval=1000, shuffle=True)
+        else:
+            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
+        return num_batches, np.mean(losses)
+
+    def train_error(self):
+        """(mean, std) of the per-batch evaluation losses with the extended word table: unweighted, unregularised."""
+        count = self.training_num_instances
+        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
+        _, losses = self._iterate_batches(self.test_fn, count)
+        return np.mean(losses), np.std(losses)
+
+    # -- results and state --------------------------------------------------------------------------------------------
+    def get_new_word_representations(self):
+        """(Nw, d_w): the new rows as they are now."""
+        return self._foldin.get_rows(_capi.WFOLD_ROWS)
+
+    def get_extended_word_representations(self, R_w):
+        """(V_w + Nw, d_w): the trained rows ``R_w`` (the caller's: never modified) with the new rows behind."""
+        R_w = np.asarray(R_w, dtype=np.float32)
+        assert R_w.shape[0] == self.vocab_size
+        return np.concatenate([R_w, self._foldin.get_rows(_capi.WFOLD_ROWS)], axis=0)
+
+    def get_optimizer_state(self):
+        return {'step': self._foldin.get_step(), 'm_Nv': self._foldin.get_rows(_capi.WFOLD_M),
+                'v_Nv': self._foldin.get_rows(_capi.WFOLD_V)}
+
+    def set_optimizer_state(self, st):
+        self._foldin.set_step(st['step'])
+        self._foldin.set_rows(_capi.WFOLD_M, st['m_Nv'])
+        self._foldin.set_rows(_capi.WFOLD_V, st['v_Nv'])
+
+    def get_sampler_state(self):
+        return {'seed': int(self._foldin.cfg.seed), 'eval_draws': self._foldin.get_eval_draws()}
+
+    def set_sampler_state(self, st):
+        if int(st['seed']) != int(self._foldin.cfg.seed):
+            raise RuntimeError('the sampler seed is fixed at construction')
+        self._foldin.set_eval_draws(st['eval_draws'])
+
+    def close(self):
+        self._foldin.close()
+
+
 class _Shape(object):
     """Stands in for a table the constructor only asks the shape of (from_model: the table itself stays on the device)."""
 
@@ -387,6 +527,54 @@ def refresh_ll_dump(args, predict_fn, R_w, refresh, Wr, br, Wn, bn):
     b[refresh] = br
     replaced = models.LogLinearPredictFn(R_w=np.asarray(st['R_w']), W=W, b=b, window_size=st['window_size'])
     return extend_ll_dump(args, replaced, R_w, np.asarray(Wn, dtype=W.dtype).reshape(W.shape[0], -1), np.asarray(bn).reshape(-1))
+
+
+def extend_words_dump(args, predict_fn, R_w, R_e, new_rows):
+    """The objects of a model dump (args, predict_fn, R_w, R_e) with R_w extended by the rows of the new words; the caller's
+    R_w is not modified, R_e and predict_fn (W, b) are the trained ones."""
+    R_w = np.asarray(R_w)
+    new_rows = np.asarray(new_rows, dtype=R_w.dtype)
+    assert new_rows.ndim == 2 and new_rows.shape[1] == R_w.shape[1]
+    return [args, predict_fn, np.concatenate([R_w, new_rows], axis=0), R_e]
+
+
+WORDS_FIRST_ADVICE = ('fold the entities in first (bin/fold_in.py without --new_words) and prepare the documents against the '
+                      'extended meta (bin/prepare.py --vocabulary_from META_EXT --extend_vocabulary)')
+
+
+def new_words_of(meta, new_meta):
+    """The words ``new_meta`` appends to the vocabulary of ``meta``, in id order (ids V_w, V_w + 1, ...).  Refused: a
+    ``new_meta`` whose vocabulary is not the trained one, every word at its trained id, with ids V_w .. appended
+    (bin/prepare.py --vocabulary_from META --extend_vocabulary)."""
+    words, tokens = meta[1], meta[2]
+    new_words, new_tokens = new_meta[1], new_meta[2]
+    V_w, V_x = len(words), len(new_words)
+    ok = (V_x >= V_w and len(new_tokens) == V_x and sorted(new_tokens) == list(range(V_x)) and
+          all(new_tokens[i] == tokens[i] for i in range(V_w)) and
+          all(new_words[w].id == entry.id for w, entry in words.items() if w in new_words) and
+          all(w in new_words for w in words) and all(new_words[new_tokens[i]].id == i for i in range(V_x)))
+    if not ok:
+        raise RuntimeError('the vocabulary of the new meta is not the trained one with new words appended behind it: prepare '
+                           'the documents with --vocabulary_from META --extend_vocabulary')
+    return [new_tokens[i] for i in range(V_w, V_x)]
+
+
+def extend_meta_words(meta, new_meta):
+    """The five pickles of a meta file for a model whose VOCABULARY grew: ``words`` and ``tokens`` are ``new_meta``'s (the
+    trained words at their trained ids, the new ones at V_w ..); the entity index is the trained one and the associations of
+    ``new_meta`` are added to it (merge_meta's rule for known ids).  Refused: a vocabulary that does not extend the trained
+    one (new_words_of), and an entity of ``new_meta`` that ``meta`` does not know."""
+    new_words_of(meta, new_meta)
+    new_index = new_meta[3]
+    entity_ids = [new_index[e] for e in range(len(new_index))]
+    known = set(meta[3].values())
+    unknown = [e for e in entity_ids if e not in known]
+    if unknown:
+        raise RuntimeError('entity ids the trained model does not know: %r; %s' % (unknown[:5], WORDS_FIRST_ADVICE))
+    associations = dict((e, new_meta[4].get(e, [])) for e in entity_ids)
+    merged, _, new_ids, _ = merge_meta(meta, entity_ids, associations)
+    assert not new_ids
+    return [merged[0], new_meta[1], new_meta[2], merged[3], merged[4]]
 
 
 def write_dump(path, objects):

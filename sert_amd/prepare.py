@@ -98,6 +98,27 @@ def extract_vocabulary(documents, min_count=2, max_size=65536, min_word_size=2,
     return words, tokens
 
 
+def extend_vocabulary(words, tokens, documents, min_count=2, max_size=65536, min_word_size=2, ignore=()):
+    """Append the tokens of ``documents`` that ``words`` does not hold -- those that pass ``min_count``, ``min_word_size`` and
+    the ignore list -- in extract_vocabulary's order (count descending, then word) as ids len(words), len(words) + 1, ...,
+    at most ``max_size - len(words)`` of them.  ``words`` / ``tokens`` are modified in place (no trained entry moves or
+    changes); -> the appended words in id order."""
+    ignore = set(ignore)
+    counts = collections.Counter()
+    for _, text in documents:
+        counts.update(tok for tok in tokenize(text)
+                      if tok not in words and tok not in ignore and len(tok) >= min_word_size)
+    kept = [(w, c) for w, c in counts.items() if c >= min_count]
+    kept.sort(key=lambda wc: (-wc[1], wc[0]))
+    kept = kept[:max(0, max_size - len(words))]
+    assert sorted(tokens) == list(range(len(words))), 'token ids must be 0 .. V_w - 1'
+    for w, c in kept:
+        idx = len(words)
+        words[w] = Word(idx, c)
+        tokens[idx] = w
+    return [w for w, _ in kept]
+
+
 def vocabulary_of_meta(path):
     """(words, tokens) of a meta file: the second and third of its five pickles."""
     with open(path, 'rb') as f:
@@ -184,6 +205,14 @@ def prepare(args):
         if not args.no_padding and PADDING_TOKEN not in words:
             raise ValueError('The vocabulary of %s has no padding token; pass --no_padding.' % vocabulary_from)
         logging.info('Took the vocabulary of %s (%d words).', vocabulary_from, len(words))
+        if getattr(args, 'extend_vocabulary', False):
+            # documents that bring new words (bin/fold_in.py --new_words): the trained ids stay, the new words follow them
+            appended = extend_vocabulary(words, tokens, documents, min_count=args.vocabulary_min_count,
+                                         max_size=args.vocabulary_max_size, min_word_size=args.vocabulary_min_word_size,
+                                         ignore=ignore)
+            logging.info('Appended %d new words (ids %d .. %d).', len(appended), len(words) - len(appended), len(words) - 1)
+    elif getattr(args, 'extend_vocabulary', False):
+        raise ValueError('Option --extend_vocabulary needs --vocabulary_from META.')
     else:
         words, tokens = extract_vocabulary(
             documents, min_count=args.vocabulary_min_count, max_size=args.vocabulary_max_size,
