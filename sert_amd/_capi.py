@@ -1151,7 +1151,134 @@ class RetrievalEval(object):
             pass
 
 
-class FoldIn(object):
+class _FoldHandle(object):
+    """What the owners of the three fold-in handles share: the handle ``_h``, the prefix of its library functions, the
+    (x, y, w) upload validation, the batch calls and the destruction."""
+
+    _prefix = None          # 'sert_foldin_', 'sert_wfold_', 'sert_ll_foldin_'
+
+    def _fn(self, name):
+        return getattr(self._lib, self._prefix + name)
+
+    def _x(self, x):
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        return x, x.ndim == 2 and x.shape[1] == self.window_size
+
+    @staticmethod
+    def _w(w, M):
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (M,):
+                raise SertError('w must be (M,)')
+        return w
+
+    def upload(self, x, y, w=None):
+        x, ok = self._x(x)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if not ok or y.shape != (x.shape[0],):
+            raise SertError('x must be (M, window_size) and y (M,)')
+        w = self._w(w, x.shape[0])
+        check(self._fn('upload')(self._h, x.ctypes.data, y.ctypes.data, _addr(w), x.shape[0]))
+
+    def num_batches(self):
+        return int(self._fn('num_batches')(self._h))
+
+    def _loss_of(self, name, batch_index, *args):
+        loss = ctypes.c_float()
+        check(self._fn(name)(self._h, int(batch_index), *(args + (ctypes.byref(loss),))))
+        return np.float32(loss.value)
+
+    def train_batch(self, batch_index):
+        return self._loss_of('train_batch', batch_index)
+
+    def train_batches(self, batch_indices):
+        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
+        out = np.empty(idx.size, dtype=np.float32)
+        check(self._fn('train_batches')(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
+        return out
+
+    def eval_batch(self, batch_index):
+        return self._loss_of('eval_batch', batch_index)
+
+    def close(self):
+        if getattr(self, '_h', None) is not None and self._h:
+            self._fn('destroy')(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _NceFoldHandle(_FoldHandle):
+    """The two handles of a vectorspace model on top of it: the NCE negatives, the rows and Adam's moments, the sampler's
+    counters and the config (sert_foldin_config and sert_wfold_config have the same fields)."""
+
+    _config = None          # SertFoldInConfig, SertWFoldConfig
+    _rows_shape = None      # of get_rows: set by the constructor
+
+    def _fill_config(self, batch_size, num_negatives, lambda_, lr, beta1, beta2, eps, seed):
+        c = self._config()
+        c.struct_size = ctypes.sizeof(self._config)
+        c.batch_size, c.num_negatives, c.lambda_ = int(batch_size), int(num_negatives), float(lambda_)
+        c.lr, c.beta1, c.beta2, c.eps, c.seed = float(lr), float(beta1), float(beta2), float(eps), int(seed)
+        self.cfg = c
+        return c
+
+    def _negatives(self, negatives):
+        if negatives is not None:
+            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
+            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
+        return negatives
+
+    def train_batch(self, batch_index, negatives=None):
+        return self._loss_of('train_batch', batch_index, _addr(self._negatives(negatives)))
+
+    def eval_batch(self, batch_index, negatives=None):
+        return self._loss_of('eval_batch', batch_index, _addr(self._negatives(negatives)))
+
+    def negatives_of_step(self, position, evaluation=False):
+        """(B, z) int64 in the range the handle draws from (FoldIn: [0, num_entities + num_new); WordFoldIn:
+        [0, num_entities)): what the device sampler draws at training position `position` (= get_step() before the step) or
+        for the `position`-th evaluation draw."""
+        out = np.empty((self.cfg.batch_size, self.cfg.num_negatives), dtype=np.int64)
+        check(self._fn('negatives_of_step')(self._h, int(position), int(bool(evaluation)), out.ctypes.data))
+        return out
+
+    def get_rows(self, which=0):
+        """``which``: FOLDIN_ROWS / _M / _V, or WFOLD_ROWS / _M / _V (the same three values)."""
+        out = np.empty(self._rows_shape, dtype=np.float32)
+        check(self._fn('get_rows')(self._h, int(which), out.ctypes.data, out.size))
+        return out
+
+    def set_rows(self, which, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        check(self._fn('set_rows')(self._h, int(which), a.ctypes.data, a.size))
+
+    def set_step(self, t):
+        check(self._fn('set_step')(self._h, int(t)))
+
+    def get_step(self):
+        return int(self._fn('get_step')(self._h))
+
+    def set_eval_draws(self, n):
+        check(self._fn('set_eval_draws')(self._h, int(n)))
+
+    def get_eval_draws(self):
+        return int(self._fn('get_eval_draws')(self._h))
+
+
+def _refresh_ids(refresh_ids):
+    given = np.asarray(refresh_ids)
+    ids = np.ascontiguousarray(given, dtype=np.int32)
+    if ids.ndim != 1 or not np.array_equal(ids, given):
+        raise SertError('refresh_ids must be a 1-d array of int32 entity indices')
+    return ids
+
+
+class FoldIn(_NceFoldHandle):
     """Owner of one sert_foldin handle (include/sert_hip_foldin.h): ``num_new`` entity rows learnt on top of the frozen
     parameters of ``engine`` (a vectorspace Engine), which are copied at construction -- the engine may train on or be
     closed afterwards.
@@ -1160,6 +1287,8 @@ class FoldIn(object):
     handle (sert_foldin_create_refresh) whose ``num_rows = len(refresh_ids) + num_new`` trainable rows are slots -- the
     refreshed trained rows in the order given, then the new rows; ``new_rows_init`` may then be None (no new entity), y at
     upload is a slot, and get_rows / set_rows are in slot order."""
+
+    _prefix, _config = 'sert_foldin_', SertFoldInConfig
 
     def __init__(self, engine, new_rows_init, batch_size, num_negatives, lambda_, lr=1e-3, beta1=0.9, beta2=0.999,
                  eps=1e-8, seed=0, refresh_ids=None):
@@ -1170,11 +1299,7 @@ class FoldIn(object):
         rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
         if rows.ndim != 2 or rows.shape[1] != engine.cfg.entity_dim:
             raise SertError('new_rows_init must be (num_new, entity_dim)')
-        c = SertFoldInConfig()
-        c.struct_size = ctypes.sizeof(SertFoldInConfig)
-        c.batch_size, c.num_negatives, c.lambda_ = int(batch_size), int(num_negatives), float(lambda_)
-        c.lr, c.beta1, c.beta2, c.eps, c.seed = float(lr), float(beta1), float(beta2), float(eps), int(seed)
-        self.cfg = c
+        c = self._fill_config(batch_size, num_negatives, lambda_, lr, beta1, beta2, eps, seed)
         self.num_new, self.entity_dim = int(rows.shape[0]), int(rows.shape[1])
         self.num_entities = int(engine.cfg.num_entities)
         self.window_size = int(engine.cfg.window_size)
@@ -1184,80 +1309,14 @@ class FoldIn(object):
             check(self._lib.sert_foldin_create(engine._h, self.num_new, rows.ctypes.data if rows.size else None,
                                                ctypes.byref(c), ctypes.byref(h)))
         else:
-            given = np.asarray(refresh_ids)
-            ids = np.ascontiguousarray(given, dtype=np.int32)
-            if ids.ndim != 1 or not np.array_equal(ids, given):
-                raise SertError('refresh_ids must be a 1-d array of int32 entity indices')
+            ids = _refresh_ids(refresh_ids)
             self.num_refresh = int(ids.size)
             check(self._lib.sert_foldin_create_refresh(engine._h, ids.ctypes.data if ids.size else None, self.num_refresh,
                                                        self.num_new, rows.ctypes.data if rows.size else None,
                                                        ctypes.byref(c), ctypes.byref(h)))
         self.num_rows = self.num_refresh + self.num_new         # the trainable rows E
+        self._rows_shape = (self.num_rows, self.entity_dim)
         self._h = h
-
-    def upload(self, x, y, w=None):
-        x = np.ascontiguousarray(x, dtype=np.int32)
-        y = np.ascontiguousarray(y, dtype=np.int32)
-        if x.ndim != 2 or x.shape[1] != self.window_size or y.shape != (x.shape[0],):
-            raise SertError('x must be (M, window_size) and y (M,)')
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            if w.shape != y.shape:
-                raise SertError('w must be (M,)')
-        check(self._lib.sert_foldin_upload(self._h, x.ctypes.data, y.ctypes.data, _addr(w), x.shape[0]))
-
-    def num_batches(self):
-        return int(self._lib.sert_foldin_num_batches(self._h))
-
-    def train_batch(self, batch_index, negatives=None):
-        loss = ctypes.c_float()
-        if negatives is not None:
-            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
-            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
-        check(self._lib.sert_foldin_train_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
-        return np.float32(loss.value)
-
-    def train_batches(self, batch_indices):
-        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
-        out = np.empty(idx.size, dtype=np.float32)
-        check(self._lib.sert_foldin_train_batches(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
-        return out
-
-    def eval_batch(self, batch_index, negatives=None):
-        loss = ctypes.c_float()
-        if negatives is not None:
-            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
-            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
-        check(self._lib.sert_foldin_eval_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
-        return np.float32(loss.value)
-
-    def negatives_of_step(self, position, evaluation=False):
-        """(B, z) int64 in [0, num_entities + num_new): what the device sampler draws at training position `position`
-        (= get_step() before the step) or for the `position`-th evaluation draw."""
-        out = np.empty((self.cfg.batch_size, self.cfg.num_negatives), dtype=np.int64)
-        check(self._lib.sert_foldin_negatives_of_step(self._h, int(position), int(bool(evaluation)), out.ctypes.data))
-        return out
-
-    def get_rows(self, which=FOLDIN_ROWS):
-        out = np.empty((self.num_rows, self.entity_dim), dtype=np.float32)
-        check(self._lib.sert_foldin_get_rows(self._h, int(which), out.ctypes.data, out.size))
-        return out
-
-    def set_rows(self, which, array):
-        a = np.ascontiguousarray(array, dtype=np.float32)
-        check(self._lib.sert_foldin_set_rows(self._h, int(which), a.ctypes.data, a.size))
-
-    def set_step(self, t):
-        check(self._lib.sert_foldin_set_step(self._h, int(t)))
-
-    def get_step(self):
-        return int(self._lib.sert_foldin_get_step(self._h))
-
-    def set_eval_draws(self, n):
-        check(self._lib.sert_foldin_set_eval_draws(self._h, int(n)))
-
-    def get_eval_draws(self):
-        return int(self._lib.sert_foldin_get_eval_draws(self._h))
 
     def plan(self):
         """sert_debug_foldin_plan (test hook): what the last step of this handle launched -- 'loss' (none / vector / scalar),
@@ -1279,22 +1338,13 @@ class FoldIn(object):
         check(self._lib.sert_debug_foldin_table(self._h, v, 4))
         return {'map': bool(v[0]), 'num_refresh': int(v[1]), 'num_new': int(v[2]), 'rows': int(v[3])}
 
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sert_foldin_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class WordFoldIn(object):
+class WordFoldIn(_NceFoldHandle):
     """Owner of one sert_wfold handle (include/sert_hip_wfold.h): ``num_new_words`` word rows learnt on top of the frozen
     parameters of ``engine`` (a vectorspace Engine), which are copied at construction -- the engine may train on or be
     closed afterwards.  New word v is token id ``vocab_size + v``; labels and negatives are trained entities."""
+
+    _prefix, _config = 'sert_wfold_', SertWFoldConfig
 
     def __init__(self, engine, new_rows_init, batch_size, num_negatives, lambda_, lr=1e-3, beta1=0.9, beta2=0.999,
                  eps=1e-8, seed=0):
@@ -1303,12 +1353,9 @@ class WordFoldIn(object):
         rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
         if rows.ndim != 2 or rows.shape[1] != engine.cfg.word_dim:
             raise SertError('new_rows_init must be (num_new_words, word_dim)')
-        c = SertWFoldConfig()
-        c.struct_size = ctypes.sizeof(SertWFoldConfig)
-        c.batch_size, c.num_negatives, c.lambda_ = int(batch_size), int(num_negatives), float(lambda_)
-        c.lr, c.beta1, c.beta2, c.eps, c.seed = float(lr), float(beta1), float(beta2), float(eps), int(seed)
-        self.cfg = c
+        c = self._fill_config(batch_size, num_negatives, lambda_, lr, beta1, beta2, eps, seed)
         self.num_new_words, self.word_dim = int(rows.shape[0]), int(rows.shape[1])
+        self._rows_shape = (self.num_new_words, self.word_dim)
         self.vocab_size = int(engine.cfg.vocab_size)
         self.num_entities = int(engine.cfg.num_entities)
         self.window_size = int(engine.cfg.window_size)
@@ -1316,72 +1363,6 @@ class WordFoldIn(object):
         check(self._lib.sert_wfold_create(engine._h, self.num_new_words, rows.ctypes.data if rows.size else None,
                                           ctypes.byref(c), ctypes.byref(h)))
         self._h = h
-
-    def upload(self, x, y, w=None):
-        x = np.ascontiguousarray(x, dtype=np.int32)
-        y = np.ascontiguousarray(y, dtype=np.int32)
-        if x.ndim != 2 or x.shape[1] != self.window_size or y.shape != (x.shape[0],):
-            raise SertError('x must be (M, window_size) and y (M,)')
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            if w.shape != y.shape:
-                raise SertError('w must be (M,)')
-        check(self._lib.sert_wfold_upload(self._h, _addr(x), _addr(y), _addr(w), x.shape[0]))
-
-    def num_batches(self):
-        return int(self._lib.sert_wfold_num_batches(self._h))
-
-    def _negatives(self, negatives):
-        if negatives is not None:
-            negatives = np.ascontiguousarray(negatives, dtype=np.int64)
-            assert negatives.size == self.cfg.batch_size * self.cfg.num_negatives
-        return negatives
-
-    def train_batch(self, batch_index, negatives=None):
-        loss = ctypes.c_float()
-        negatives = self._negatives(negatives)
-        check(self._lib.sert_wfold_train_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
-        return np.float32(loss.value)
-
-    def train_batches(self, batch_indices):
-        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
-        out = np.empty(idx.size, dtype=np.float32)
-        check(self._lib.sert_wfold_train_batches(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
-        return out
-
-    def eval_batch(self, batch_index, negatives=None):
-        loss = ctypes.c_float()
-        negatives = self._negatives(negatives)
-        check(self._lib.sert_wfold_eval_batch(self._h, int(batch_index), _addr(negatives), ctypes.byref(loss)))
-        return np.float32(loss.value)
-
-    def negatives_of_step(self, position, evaluation=False):
-        """(B, z) int64 in [0, num_entities): what the device sampler draws at training position `position` (= get_step()
-        before the step) or for the `position`-th evaluation draw."""
-        out = np.empty((self.cfg.batch_size, self.cfg.num_negatives), dtype=np.int64)
-        check(self._lib.sert_wfold_negatives_of_step(self._h, int(position), int(bool(evaluation)), out.ctypes.data))
-        return out
-
-    def get_rows(self, which=WFOLD_ROWS):
-        out = np.empty((self.num_new_words, self.word_dim), dtype=np.float32)
-        check(self._lib.sert_wfold_get_rows(self._h, int(which), out.ctypes.data, out.size))
-        return out
-
-    def set_rows(self, which, array):
-        a = np.ascontiguousarray(array, dtype=np.float32)
-        check(self._lib.sert_wfold_set_rows(self._h, int(which), a.ctypes.data, a.size))
-
-    def set_step(self, t):
-        check(self._lib.sert_wfold_set_step(self._h, int(t)))
-
-    def get_step(self):
-        return int(self._lib.sert_wfold_get_step(self._h))
-
-    def set_eval_draws(self, n):
-        check(self._lib.sert_wfold_set_eval_draws(self._h, int(n)))
-
-    def get_eval_draws(self):
-        return int(self._lib.sert_wfold_get_eval_draws(self._h))
 
     def plan(self):
         """sert_debug_wfold_plan (test hook): what the last step of this handle launched -- 'project' (none / vector / scalar:
@@ -1394,17 +1375,6 @@ class WordFoldIn(object):
         route = lambda code: GEMM_ROUTES[code - 1] if code >= 1 else 'none'
         return {'project': WFOLD_PROJECT_FORMS[v[0]], 'loss': NCE_FORMS[v[1]], 'k': v[2], 'train': bool(v[3]), 'levels': v[4],
                 'items': v[5:5 + v[4]], 'segsum': WGRAD_FORMS[v[11]], 'gemm_p': route(v[12]), 'gemm_g': route(v[13])}
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sert_wfold_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def debug_wfold_index(tok, num_words, batch=0):
@@ -1428,7 +1398,7 @@ def debug_wfold_index(tok, num_words, batch=0):
             'rows': rows[:nr.value].copy(), 'items': items[:ni.value].copy()}
 
 
-class LlFoldIn(object):
+class LlFoldIn(_FoldHandle):
     """Owner of one sert_ll_foldin handle (include/sert_hip_ll_foldin.h): ``num_new`` columns of W and entries of b learnt
     on top of the frozen parameters of ``engine`` (a loglinear Engine), which are copied at construction -- the engine may
     train on or be closed afterwards.  ``init_W``: (word_dim, num_new); ``init_b``: (num_new,) or None (zeros).
@@ -1437,6 +1407,8 @@ class LlFoldIn(object):
     The trainable columns are then ``num_slots`` = ``num_refresh`` + ``num_new`` SLOTS, the refreshed columns first in the
     order given: integer labels are slots, the tensors are (word_dim, num_slots) / (num_slots,) in slot order, and ``init_W``
     may be None or empty (nothing is new).  Label rows keep the public columns [0, num_entities + num_new)."""
+
+    _prefix = 'sert_ll_foldin_'
 
     def __init__(self, engine, init_W, init_b, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0,
                  refresh_ids=None):
@@ -1466,10 +1438,7 @@ class LlFoldIn(object):
             check(self._lib.sert_ll_foldin_create(engine._h, self.num_new, Wn.ctypes.data if Wn.size else None, _addr(bn),
                                                   ctypes.byref(c), ctypes.byref(h)))
         else:
-            given = np.asarray(refresh_ids)
-            ids = np.ascontiguousarray(given, dtype=np.int32)
-            if ids.ndim != 1 or not np.array_equal(ids, given):
-                raise SertError('refresh_ids must be a 1-d array of int32 entity indices')
+            ids = _refresh_ids(refresh_ids)
             self.num_refresh = int(ids.size)
             check(self._lib.sert_ll_foldin_create_refresh(engine._h, ids.ctypes.data if ids.size else None, self.num_refresh,
                                                           self.num_new, Wn.ctypes.data if Wn.size else None,
@@ -1477,54 +1446,21 @@ class LlFoldIn(object):
         self.num_slots = self.num_refresh + self.num_new        # the trainable columns
         self._h = h
 
-    def upload(self, x, y, w=None):
-        x = np.ascontiguousarray(x, dtype=np.int32)
-        y = np.ascontiguousarray(y, dtype=np.int32)
-        if x.ndim != 2 or x.shape[1] != self.window_size or y.shape != (x.shape[0],):
-            raise SertError('x must be (M, window_size) and y (M,)')
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            if w.shape != y.shape:
-                raise SertError('w must be (M,)')
-        check(self._lib.sert_ll_foldin_upload(self._h, x.ctypes.data, y.ctypes.data, _addr(w), x.shape[0]))
-
     def upload_csr(self, x, indptr, indices, data, w=None):
         """Label ROWS: a canonical CSR matrix (M, num_entities + num_new) -- column e < num_entities is trained entity e (a
         label only), column num_entities + j new entity j (sert_ll_foldin_upload_csr, which validates the rows)."""
-        x = np.ascontiguousarray(x, dtype=np.int32)
+        x, ok = self._x(x)
         indptr = np.ascontiguousarray(indptr, dtype=np.int64)
         indices = np.ascontiguousarray(indices, dtype=np.int32)
         data = np.ascontiguousarray(data, dtype=np.float32)
-        if x.ndim != 2 or x.shape[1] != self.window_size or indptr.shape != (x.shape[0] + 1,):
+        if not ok or indptr.shape != (x.shape[0] + 1,):
             raise SertError('x must be (M, window_size) and indptr (M + 1,)')
         # (what the library cannot see: the arrays must be as long as indptr says before it reads them)
         if indices.ndim != 1 or data.shape != indices.shape or (indptr.size and indices.size < indptr.max()):
             raise SertError('indices and data must be (nnz,) with nnz >= max(indptr)')
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            if w.shape != (x.shape[0],):
-                raise SertError('w must be (M,)')
+        w = self._w(w, x.shape[0])
         check(self._lib.sert_ll_foldin_upload_csr(self._h, x.ctypes.data, indptr.ctypes.data, _addr(indices), _addr(data),
                                                   _addr(w), x.shape[0]))
-
-    def num_batches(self):
-        return int(self._lib.sert_ll_foldin_num_batches(self._h))
-
-    def train_batch(self, batch_index):
-        loss = ctypes.c_float()
-        check(self._lib.sert_ll_foldin_train_batch(self._h, int(batch_index), ctypes.byref(loss)))
-        return np.float32(loss.value)
-
-    def train_batches(self, batch_indices):
-        idx = np.ascontiguousarray(batch_indices, dtype=np.int64)
-        out = np.empty(idx.size, dtype=np.float32)
-        check(self._lib.sert_ll_foldin_train_batches(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
-        return out
-
-    def eval_batch(self, batch_index):
-        loss = ctypes.c_float()
-        check(self._lib.sert_ll_foldin_eval_batch(self._h, int(batch_index), ctypes.byref(loss)))
-        return np.float32(loss.value)
 
     def _shape(self, which):
         if which not in (LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B):
@@ -1549,17 +1485,6 @@ class LlFoldIn(object):
                                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int64]
         check(self._lib.sert_debug_ll_foldin_layout(self._h, ctypes.byref(vf), ctypes.byref(nt), out.ctypes.data, out.size))
         return int(vf.value), int(nt.value), out
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.sert_ll_foldin_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def bench_gemm(M, N, K, ta=0, tb=0, epi=0, splits=1, iters=20, device=0):

@@ -2,62 +2,38 @@
 // into a trained vectorspace model (include/sert_hip_foldin.h: sert_foldin_*; kernels_foldin.h).  The handle copies the
 // model's parameters when it is created and runs on a stream of its own: it shares nothing with the model's step schedule.
 
-struct sert_foldin {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct sert_foldin : FoldNce {
     sert_foldin_config cfg;
-    int Vw = 0, Ve = 0, N = 0, dw = 0, de = 0, n = 0;     // N: the trainable rows E (sert_foldin_create: the new rows)
+    int N = 0;                       // the trainable rows E (sert_foldin_create: the new rows)
     // sert_foldin_create_refresh: E is num_refresh trained rows, then num_new new rows; slot_of (Ve + num_new): the slot of a
     // row of the extended table or -1 (frozen); refresh_ids (num_refresh): the trained row of a slot.  map: the loss kernels
     // that look a candidate up in slot_of (foldin_nce_map*); sert_foldin_create leaves it false and both arrays null.
     int num_new = 0, num_refresh = 0;
     bool map = false;
     int32_t *slot_of = nullptr, *refresh_ids = nullptr;
-    // the frozen snapshot
-    float *rw = nullptr, *W = nullptr, *b = nullptr, *re = nullptr;
-    // the new rows, Adam's moments, the gradient
-    float *E = nullptr, *m1 = nullptr, *m2 = nullptr, *G = nullptr;
-    // the uploaded instances and their projections
-    int64_t M = 0;
-    int32_t* y = nullptr;
-    float* w = nullptr;
-    float* T = nullptr;              // (M, d_e)
+    float* E = nullptr;              // the trainable rows (FoldNce: Adam's moments m1, m2 and the gradient G)
+    float* T = nullptr;              // (M, d_e) the projections of the uploaded instances
     // per-step scratch
-    int32_t* neg = nullptr;          // (B, z)
-    int64_t* neg_stage = nullptr;    // (B, z) host-supplied negatives
-    float* coef = nullptr;           // (B, 1 + z)
     int32_t *key = nullptr, *key_sorted = nullptr, *pair_sorted = nullptr, *k_tmp = nullptr, *v_tmp = nullptr;
     int32_t *sort_hist = nullptr, *sort_bin_total = nullptr;
     int sort_bits = 1;
     int32_t* run_bounds = nullptr;   // run_start (round_up(N, 4)) then run_end (the same)
     float *ehead = nullptr, *etail = nullptr;   // (chunks, d_e) carries
-    float* rowloss = nullptr;        // (B)
-    float* red_loss = nullptr;       // per-workgroup loss partials of foldin_nce
-    float* red_sq = nullptr;         // [kOptBlocks] sums of squares of E
-    float* d_loss = nullptr;         // [3]
-    float* d_losses = nullptr;       // multi-step loss ring
-    int64_t d_losses_cap = 0;
-    int64_t step = 0, eval_draws = 0;
     // what the last step launched, recorded where the launches are made: sert_debug_foldin_plan (sert_hip_debug.h)
     int32_t plan[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+static void foldin_free_upload(sert_foldin* f) {
+    (void)hipFree(f->y); (void)hipFree(f->w); (void)hipFree(f->T);
+    f->y = nullptr; f->w = nullptr; f->T = nullptr; f->M = 0;
+}
+
 int sert_foldin_destroy(sert_foldin* f) {
     if (!f) return 0;
-    if (f->device >= 0) {
-        (void)hipSetDevice(f->device);
-        if (f->stream) (void)hipStreamSynchronize(f->stream);
-    }
-    for (void* p : {(void*)f->rw, (void*)f->W, (void*)f->b, (void*)f->re, (void*)f->E, (void*)f->m1, (void*)f->m2, (void*)f->G,
-                    (void*)f->y, (void*)f->w, (void*)f->T, (void*)f->neg, (void*)f->neg_stage, (void*)f->coef, (void*)f->key,
-                    (void*)f->key_sorted, (void*)f->pair_sorted, (void*)f->k_tmp, (void*)f->v_tmp, (void*)f->sort_hist,
-                    (void*)f->sort_bin_total, (void*)f->run_bounds, (void*)f->ehead, (void*)f->etail, (void*)f->rowloss,
-                    (void*)f->red_loss, (void*)f->red_sq, (void*)f->d_loss, (void*)f->d_losses, (void*)f->slot_of,
-                    (void*)f->refresh_ids})
-        (void)hipFree(p);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
-    return 0;
+    return fold_destroy(f, foldin_free_upload,
+                        {f->rw, f->W, f->b, f->re, f->E, f->m1, f->m2, f->G, f->neg, f->neg_stage, f->coef, f->key, f->key_sorted,
+                         f->pair_sorted, f->k_tmp, f->v_tmp, f->sort_hist, f->sort_bin_total, f->run_bounds, f->ehead, f->etail,
+                         f->rowloss, f->red_loss, f->red_sq, f->slot_of, f->refresh_ids});
 }
 
 // map == false: sert_foldin_create (refresh_ids null, num_refresh 0).  map == true: sert_foldin_create_refresh.
@@ -102,22 +78,8 @@ static int foldin_create(sert_foldin* f, sert_model* m, bool map, const int32_t*
     f->Vw = c.vocab_size; f->Ve = c.num_entities; f->N = num_refresh + num_new; f->dw = c.word_dim; f->de = c.entity_dim; f->n = c.window_size;
     const int B = cfg->batch_size, z = cfg->num_negatives, de = f->de, N = f->N;
     const size_t n_e = (size_t)N * de;
-    // the parameters as a reader must see them (sert_get_tensor, sert_reval_run): every lazily updated word-table row brought
-    // to the model's step, a deferred entity-table update landed
-    SERT_TRY(ensure_full_rw(m));
-    SERT_TRY(ensure_rw_current(m, -1));
-    if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
-    if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
-    SERT_TRY(settle_entity_update(m));
-    flush_pending_tail(m);
-    SERT_TRY(dmalloc(&f->rw, m->n_rw));
-    SERT_TRY(dmalloc(&f->W, m->n_w));
-    SERT_TRY(dmalloc(&f->b, m->n_b));
-    SERT_TRY(dmalloc(&f->re, std::max<size_t>(m->n_re, 4)));
-    SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    if (m->n_re) SERT_HIP(hipMemcpyAsync(f->re, m->re, m->n_re * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_TRY(fold_settle_model(m, true));
+    SERT_TRY(fold_snapshot_vs(f, m, 0));
     SERT_HIP(hipStreamCreate(&f->stream));
     hipStream_t s = f->stream;
     SERT_TRY(dmalloc(&f->E, n_e));
@@ -166,51 +128,28 @@ static int foldin_create(sert_foldin* f, sert_model* m, bool map, const int32_t*
     SERT_TRY(dmalloc(&f->red_loss, (size_t)cdiv(B, 16)));
     SERT_TRY(dmalloc(&f->red_sq, (size_t)kOptBlocks));
     SERT_TRY(dmalloc(&f->d_loss, (size_t)3));
-    SERT_HIP(hipStreamSynchronize(s));             // (init_rows is borrowed for the call only)
-    SERT_HIP(hipStreamSynchronize(m->stream));     // (the snapshot is complete: the model may train or go away)
-    return 0;
+    return fold_created(f, m);      // (init_rows is borrowed for the call only)
 }
 
 int sert_foldin_create(sert_model* m, int32_t num_new, const float* init_rows, const sert_foldin_config* cfg, sert_foldin** out) {
     refresh_gemm_choice();
-    if (!m || !cfg || !out) SERT_FAIL("null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(sert_foldin_config)) SERT_FAIL("sert_foldin_config size mismatch (ABI)");
-    sert_foldin* f = new sert_foldin();
-    const int rc = foldin_create(f, m, false, nullptr, 0, num_new, init_rows, cfg);
-    if (rc != 0) {
-        const std::string keep = g_last_error;
-        sert_foldin_destroy(f);
-        g_last_error = keep;
-        return rc;
-    }
-    *out = f;
-    return 0;
+    return fold_create(m, cfg, out, "sert_foldin_config size mismatch (ABI)", sert_foldin_destroy,
+                       [&](sert_foldin* f) { return foldin_create(f, m, false, nullptr, 0, num_new, init_rows, cfg); });
 }
 
 int sert_foldin_create_refresh(sert_model* m, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
                                const float* init_new_rows, const sert_foldin_config* cfg, sert_foldin** out) {
     refresh_gemm_choice();
-    if (!m || !cfg || !out) SERT_FAIL("null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(sert_foldin_config)) SERT_FAIL("sert_foldin_config size mismatch (ABI)");
-    sert_foldin* f = new sert_foldin();
-    const int rc = foldin_create(f, m, true, refresh_ids, num_refresh, num_new, init_new_rows, cfg);
-    if (rc != 0) {
-        const std::string keep = g_last_error;
-        sert_foldin_destroy(f);
-        g_last_error = keep;
-        return rc;
-    }
-    *out = f;
-    return 0;
+    return fold_create(m, cfg, out, "sert_foldin_config size mismatch (ABI)", sert_foldin_destroy, [&](sert_foldin* f) {
+        return foldin_create(f, m, true, refresh_ids, num_refresh, num_new, init_new_rows, cfg);
+    });
 }
 
 int sert_foldin_upload(sert_foldin* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
     refresh_gemm_choice();
     if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
     if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
-    const int n = f->n, dw = f->dw, de = f->de;
+    const int n = f->n;
     // host-side validation: no kernel is launched on bad ids
     for (int64_t i = 0; i < M; ++i)
         if (y[i] < 0 || y[i] >= f->N)
@@ -219,68 +158,28 @@ int sert_foldin_upload(sert_foldin* f, const int32_t* x, const int32_t* y, const
     for (int64_t i = 0; i < M * n; ++i)
         if (x[i] < 0 || x[i] >= f->Vw) SERT_FAIL("token id out of range [0, vocab_size)");
     SERT_HIP(hipSetDevice(f->device));
-    hipStream_t s = f->stream;
-    SERT_HIP(hipStreamSynchronize(s));
-    (void)hipFree(f->y); (void)hipFree(f->w); (void)hipFree(f->T);
-    f->y = nullptr; f->w = nullptr; f->T = nullptr; f->M = 0;
+    SERT_HIP(hipStreamSynchronize(f->stream));
+    foldin_free_upload(f);
     if (M == 0) return 0;
-    SERT_TRY(dmalloc(&f->y, (size_t)M));
-    SERT_TRY(dmalloc(&f->w, (size_t)M));
-    SERT_TRY(dmalloc(&f->T, (size_t)M * de));
-    SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (w) {
-        SERT_HIP(hipMemcpyAsync(f->w, w, (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
-    } else {
-        const std::vector<float> ones((size_t)M, 1.0f);
-        SERT_HIP(hipMemcpyAsync(f->w, ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
-        SERT_HIP(hipStreamSynchronize(s));
-    }
-    // T = tanh(h W + b) once, by the model's forward (vs_project: vs_gather_mean, the projection GEMM), a slab of rows at a time
-    const int64_t slab = std::min<int64_t>(M, 65536);
-    uint32_t* dx = nullptr;
-    float* H = nullptr;
+    std::vector<float> ones;
     auto body = [&]() -> int {
-        SERT_TRY(dmalloc(&dx, (size_t)slab * n));
-        SERT_TRY(dmalloc(&H, (size_t)slab * dw));
-        for (int64_t r0 = 0; r0 < M; r0 += slab) {
-            const int rows = (int)std::min<int64_t>(slab, M - r0);
-            SERT_HIP(hipMemcpyAsync(dx, x + (size_t)r0 * n, (size_t)rows * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            if (dw % 4 == 0)
-                launch((vs_gather_mean<uint32_t, 4>), dim3(grid_for((int64_t)rows * dw / 4, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
-            else
-                launch((vs_gather_mean<uint32_t, 1>), dim3(grid_for((int64_t)rows * dw, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
-            launch_gemm<false, false, EPI_BIAS_TANH>(s, H, f->W, f->T + (size_t)r0 * de, f->b, rows, de, dw, dw, de, de);
-        }
-        SERT_HIP(hipGetLastError());
-        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w are borrowed for the call only)
-        return 0;
+        SERT_TRY(fold_upload_labels(f, y, w, M, ones));
+        SERT_TRY(dmalloc(&f->T, (size_t)M * f->de));
+        // T = tanh(h W + b) once
+        return fold_project_slabs<EPI_BIAS_TANH>(f, x, M, f->T, nullptr);
     };
     const int rc = body();
-    (void)hipFree(dx); (void)hipFree(H);
-    if (rc != 0) return rc;
+    if (rc != 0) return fold_upload_failed(f, rc, foldin_free_upload);
     f->M = M;
     return 0;
 }
 
-int64_t sert_foldin_num_batches(sert_foldin* f) { return f ? f->M / f->cfg.batch_size : -1; }
+int64_t sert_foldin_num_batches(sert_foldin* f) { return fold_num_batches(f); }
 
-// the step's negatives into f->neg: the caller's (validated before anything is launched) or the Philox sampler's
+// the step's negatives into f->neg, over the extended table
 static int foldin_negatives(sert_foldin* f, const int64_t* negatives, uint64_t stream_pos) {
-    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
-    const int64_t ext = (int64_t)f->Ve + f->num_new;
-    if (negatives) {
-        for (int64_t i = 0; i < count; ++i)
-            if (negatives[i] < 0 || negatives[i] >= ext) SERT_FAIL("negative sample out of range [0, num_entities + num_new)");
-        SERT_HIP(hipMemcpyAsync(f->neg_stage, negatives, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
-        launch(convert_i64_to_i32, dim3(grid_for(count)), dim3(256), 0, f->stream, (const int64_t*)f->neg_stage, f->neg, count);
-    } else {
-        // (even = training draws, odd = evaluation draws, as the model's sampler)
-        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, f->stream, f->neg, count, (int64_t)0,
-               (uint32_t)ext, f->cfg.seed, stream_pos, (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
-    }
-    return 0;
+    return fold_negatives(f, negatives, stream_pos, (int64_t)f->Ve + f->num_new,
+                          "negative sample out of range [0, num_entities + num_new)");
 }
 
 // the loss kernel on batch `batch` (train: weighted, coef and keys written); *parts / *n_parts: the loss partials it left.
@@ -338,149 +237,64 @@ static int foldin_grad(sert_foldin* f, int64_t batch) {
 }
 
 static int foldin_check_batch(sert_foldin* f, int64_t batch) {
-    if (!f) SERT_FAIL("null argument");
-    if (!f->T) SERT_FAIL("no fold-in instances uploaded (sert_foldin_upload)");
-    if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
-    return 0;
+    return fold_check_batch(f, &sert_foldin::T, "sert_foldin_upload", batch);
 }
 
 // one step enqueued on the handle's stream; dst: 3 floats on the device (finalize_loss: loss, data term, regulariser)
 static int foldin_step_async(sert_foldin* f, int64_t batch, const int64_t* negatives, float* dst) {
-    const auto& c = f->cfg;
-    const int B = c.batch_size;
-    hipStream_t s = f->stream;
     SERT_TRY(foldin_negatives(f, negatives, (uint64_t)f->step * 2));
     const float* parts = nullptr;
     int n_parts = 0;
     SERT_TRY(foldin_loss(f, batch, true, &parts, &n_parts));
     SERT_TRY(foldin_grad(f, batch));
-    // Adam over E with the model's arithmetic (adam_l2: L2 folded into the gradient, sum of squares of the values BEFORE
-    // the update from the same pass); a_t on the host in fp32 (optimizer_args)
-    f->step += 1;
-    const float tf = (float)f->step;
-    AdamArgs aa{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr * sqrtf(1.0f - powf(c.beta2, tf)) / (1.0f - powf(c.beta1, tf)),
-                c.beta1, c.beta2, c.eps};
-    const size_t n_e = (size_t)f->N * f->de;
-    const int nb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)n_e, 4), 256)));
-    launch((adam_l2<false>), dim3(nb), dim3(256), 0, s, f->E, f->G, f->m1, f->m2, n_e, aa, f->red_sq, (const uint32_t*)nullptr,
-           1u, (int)kRowsAll, (float*)nullptr);
-    launch(finalize_loss, dim3(1), dim3(256), 0, s, parts, n_parts, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0,
-           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    fold_adam_finalize(f, f->E, (size_t)f->N * f->de, parts, n_parts, dst);
     return 0;
 }
 
 int sert_foldin_train_batch(sert_foldin* f, int64_t batch, const int64_t* negatives, float* loss_out) {
-    SERT_TRY(foldin_check_batch(f, batch));
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_TRY(foldin_step_async(f, batch, negatives, f->d_loss));
-    float host[3] = {0.f, 0.f, 0.f};
-    SERT_HIP(hipGetLastError());
-    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (loss_out) *loss_out = host[0];
-    return 0;
+    return fold_run_batch(f, batch, loss_out, foldin_check_batch,
+                          [&](sert_foldin* h, int64_t b, float* dst) { return foldin_step_async(h, b, negatives, dst); });
 }
 
 int sert_foldin_train_batches(sert_foldin* f, const int64_t* batches, int64_t count, float* losses_out) {
-    if (!f || count < 0 || (count > 0 && !batches)) SERT_FAIL("bad argument");
-    for (int64_t i = 0; i < count; ++i) SERT_TRY(foldin_check_batch(f, batches[i]));    // (before anything is enqueued)
-    if (count == 0) return 0;
-    SERT_HIP(hipSetDevice(f->device));
-    if (count > f->d_losses_cap) {
-        SERT_HIP(hipStreamSynchronize(f->stream));
-        (void)hipFree(f->d_losses);
-        f->d_losses = nullptr; f->d_losses_cap = 0;
-        SERT_TRY(dmalloc(&f->d_losses, (size_t)count * 3));
-        f->d_losses_cap = count;
-    }
-    for (int64_t i = 0; i < count; ++i) SERT_TRY(foldin_step_async(f, batches[i], nullptr, f->d_losses + 3 * i));
-    SERT_HIP(hipGetLastError());
-    std::vector<float> tmp((size_t)count * 3);
-    SERT_HIP(hipMemcpyAsync(tmp.data(), f->d_losses, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (losses_out)
-        for (int64_t i = 0; i < count; ++i) losses_out[i] = tmp[(size_t)3 * i];
-    return 0;
+    return fold_train_batches(f, batches, count, losses_out, foldin_check_batch,
+                              [](sert_foldin* h, int64_t b, float* dst) { return foldin_step_async(h, b, nullptr, dst); });
 }
 
 int sert_foldin_eval_batch(sert_foldin* f, int64_t batch, const int64_t* negatives, float* loss_out) {
-    SERT_TRY(foldin_check_batch(f, batch));
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_TRY(foldin_negatives(f, negatives, (uint64_t)f->eval_draws * 2 + 1));
-    if (!negatives) ++f->eval_draws;
-    const float* parts = nullptr;
-    int n_parts = 0;
-    SERT_TRY(foldin_loss(f, batch, false, &parts, &n_parts));
-    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, parts, n_parts, parts, 0, 1.0f / (float)f->cfg.batch_size, 0.0f,
-           f->d_loss, (unsigned*)nullptr, 0u, (const float*)nullptr);
-    float host[3] = {0.f, 0.f, 0.f};
-    SERT_HIP(hipGetLastError());
-    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (loss_out) *loss_out = host[0];
-    return 0;
+    return fold_run_batch(f, batch, loss_out, foldin_check_batch, [&](sert_foldin* h, int64_t b, float* dst) {
+        SERT_TRY(foldin_negatives(h, negatives, (uint64_t)h->eval_draws * 2 + 1));
+        if (!negatives) ++h->eval_draws;
+        const float* parts = nullptr;
+        int n_parts = 0;
+        SERT_TRY(foldin_loss(h, b, false, &parts, &n_parts));
+        fold_eval_finalize(h, parts, n_parts, dst);
+        return 0;
+    });
 }
 
 int sert_foldin_negatives_of_step(sert_foldin* f, int64_t position, int evaluation, int64_t* out) {
     if (!f || !out || position < 0) SERT_FAIL("bad argument");
-    SERT_HIP(hipSetDevice(f->device));
-    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
-    int32_t* tmp = nullptr;
-    SERT_HIP(hipMalloc((void**)&tmp, (size_t)count * sizeof(int32_t)));
-    // a stream of its own: nothing of the handle's state is touched
-    hipStream_t st = nullptr;
-    if (hipStreamCreate(&st) != hipSuccess) { (void)hipFree(tmp); SERT_FAIL("hipStreamCreate failed"); }
-    launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count, (int64_t)0,
-           (uint32_t)((int64_t)f->Ve + f->num_new), f->cfg.seed, (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0,
-           (uint4*)nullptr, (size_t)0);
-    std::vector<int32_t> host((size_t)count);
-    const hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-    (void)hipFree(tmp);
-    if (e != hipSuccess || e2 != hipSuccess) SERT_FAIL("reading the negatives back failed");
-    for (int64_t i = 0; i < count; ++i) out[i] = host[(size_t)i];
-    return 0;
+    return fold_negatives_of_step(f, position, evaluation, out, (int64_t)f->Ve + f->num_new);
 }
 
-static float* foldin_rows_ref(sert_foldin* f, int which) {
+static float* foldin_rows_ref(sert_foldin* f, int which, size_t* count) {
+    *count = (size_t)f->N * f->de;
     return which == SERT_FOLDIN_ROWS ? f->E : which == SERT_FOLDIN_M ? f->m1 : which == SERT_FOLDIN_V ? f->m2 : nullptr;
 }
+static const char* const kFoldinWhich = "which must be SERT_FOLDIN_ROWS, SERT_FOLDIN_M or SERT_FOLDIN_V";
 
 int sert_foldin_get_rows(sert_foldin* f, int which, float* host, size_t count) {
-    if (!f || !host) SERT_FAIL("null argument");
-    float* p = foldin_rows_ref(f, which);
-    if (!p) SERT_FAIL("which must be SERT_FOLDIN_ROWS, SERT_FOLDIN_M or SERT_FOLDIN_V");
-    if (count != (size_t)f->N * f->de) SERT_FAIL("element count mismatch");
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_HIP(hipMemcpyAsync(host, p, count * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    return 0;
+    return fold_copy_tensor(f, which, host, count, true, foldin_rows_ref, kFoldinWhich);
 }
-
 int sert_foldin_set_rows(sert_foldin* f, int which, const float* host, size_t count) {
-    if (!f || !host) SERT_FAIL("null argument");
-    float* p = foldin_rows_ref(f, which);
-    if (!p) SERT_FAIL("which must be SERT_FOLDIN_ROWS, SERT_FOLDIN_M or SERT_FOLDIN_V");
-    if (count != (size_t)f->N * f->de) SERT_FAIL("element count mismatch");
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    return 0;
+    return fold_copy_tensor(f, which, const_cast<float*>(host), count, false, foldin_rows_ref, kFoldinWhich);
 }
 
-int sert_foldin_set_step(sert_foldin* f, int64_t t) {
-    if (!f || t < 0) SERT_FAIL("bad argument");
-    f->step = t;
-    return 0;
-}
-int64_t sert_foldin_get_step(sert_foldin* f) { return f ? f->step : -1; }
-int sert_foldin_set_eval_draws(sert_foldin* f, int64_t n) {
-    if (!f || n < 0) SERT_FAIL("bad argument");
-    f->eval_draws = n;
-    return 0;
-}
-int64_t sert_foldin_get_eval_draws(sert_foldin* f) { return f ? f->eval_draws : -1; }
+int sert_foldin_set_step(sert_foldin* f, int64_t t) { return fold_set_counter(f, &FoldNce::step, t); }
+int64_t sert_foldin_get_step(sert_foldin* f) { return fold_get_counter(f, &FoldNce::step); }
+int sert_foldin_set_eval_draws(sert_foldin* f, int64_t n) { return fold_set_counter(f, &FoldNce::eval_draws, n); }
+int64_t sert_foldin_get_eval_draws(sert_foldin* f) { return fold_get_counter(f, &FoldNce::eval_draws); }
 
 int sert_debug_foldin_plan(sert_foldin* f, int32_t* out, int n) {
     if (!f || !out || n < 1 || n > 10) SERT_FAIL("bad argument");

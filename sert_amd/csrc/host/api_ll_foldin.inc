@@ -2,9 +2,7 @@
 // into a trained loglinear model (include/sert_hip_ll_foldin.h: sert_ll_foldin_*; kernels_ll_foldin.h).  Like sert_foldin the
 // handle copies the model's parameters when it is created and runs on a stream of its own.
 
-struct sert_ll_foldin {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct sert_ll_foldin : FoldBase {
     sert_ll_foldin_config cfg;
     int Vw = 0, Ve = 0, N = 0, d = 0, n = 0;     // Ve: the FROZEN columns V_f; N: the trainable ones Nt (the kernels' V_e and N)
     // the public columns: Ve_pub trained entities of the model, of which R are refreshed (slots [0, R) of the N trainable
@@ -17,7 +15,7 @@ struct sert_ll_foldin {
     float *Wn = nullptr, *bn = nullptr, *accu_w = nullptr, *accu_b = nullptr, *delta_w = nullptr, *delta_b = nullptr;
     float *g_w = nullptr, *g_b = nullptr;
     // ---- the upload ----
-    int64_t M = 0, D = 0;                // instances; distinct words
+    int64_t D = 0;                       // distinct words of the upload (FoldBase: M instances)
     int32_t* y = nullptr;                // one label per instance (sert_ll_foldin_upload), or ...
     int64_t* indptr = nullptr;           // ... label rows (sert_ll_foldin_upload_csr): (M + 1) offsets, ...
     int32_t* indices = nullptr;          // ... (nnz) columns in [0, V_e + N), strictly increasing per row, ...
@@ -37,9 +35,6 @@ struct sert_ll_foldin {
     float *Gb = nullptr, *Zn = nullptr, *lse = nullptr, *dZ = nullptr, *dZu = nullptr, *part = nullptr;
     float* rowloss = nullptr;            // (B)
     float* red_sq = nullptr;             // [kOptBlocks] sums of squares of Wn, then [kOptBlocks] of bn (not in the loss)
-    float* d_loss = nullptr;             // [3]
-    float* d_losses = nullptr;           // multi-step loss ring
-    int64_t d_losses_cap = 0;
 };
 
 static void llf_free_upload(sert_ll_foldin* f) {
@@ -56,18 +51,8 @@ static void llf_free_upload(sert_ll_foldin* f) {
 
 int sert_ll_foldin_destroy(sert_ll_foldin* f) {
     if (!f) return 0;
-    if (f->device >= 0) {
-        (void)hipSetDevice(f->device);
-        if (f->stream) (void)hipStreamSynchronize(f->stream);
-    }
-    llf_free_upload(f);
-    for (void* p : {(void*)f->rw, (void*)f->W, (void*)f->b, (void*)f->Wn, (void*)f->bn, (void*)f->accu_w, (void*)f->accu_b,
-                    (void*)f->delta_w, (void*)f->delta_b, (void*)f->g_w, (void*)f->g_b, (void*)f->rowloss, (void*)f->red_sq,
-                    (void*)f->d_loss, (void*)f->d_losses})
-        (void)hipFree(p);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
-    return 0;
+    return fold_destroy(f, llf_free_upload, {f->rw, f->W, f->b, f->Wn, f->bn, f->accu_w, f->accu_b, f->delta_w, f->delta_b, f->g_w,
+                                             f->g_b, f->rowloss, f->red_sq});
 }
 
 // Both creators.  refresh == false: sert_ll_foldin_create, its arguments and its wording.  The trainable columns are SLOTS --
@@ -116,19 +101,14 @@ static int llf_create(sert_ll_foldin* f, sert_model* m, bool refresh, const int3
     f->Ve = c.num_entities - num_refresh; f->N = (int)nt;
     const int R = f->R, Vf = f->Ve, Nt = f->N, d = f->d;
     const size_t n_w = (size_t)d * Nt, n_b = (size_t)Nt;
-    // the parameters as a reader must see them (sert_get_tensor): every lazily updated word-table row brought to the model's
-    // step, the side queues drained
-    SERT_TRY(ensure_full_rw(m));
-    SERT_TRY(ensure_rw_current(m, -1));
-    if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
-    if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
-    SERT_TRY(dmalloc(&f->rw, m->n_rw));
-    SERT_TRY(dmalloc(&f->W, (size_t)d * Vf));          // (V_f == 0: no allocation, the pointers stay null and are never read)
-    SERT_TRY(dmalloc(&f->b, (size_t)Vf));
-    SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_TRY(fold_settle_model(m, false));
+    SERT_TRY(fold_snapshot(m, &f->rw, m->rw, m->n_rw, m->n_rw));
     if (R == 0) {
-        SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-        SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+        SERT_TRY(fold_snapshot(m, &f->W, m->W, m->n_w, m->n_w));
+        SERT_TRY(fold_snapshot(m, &f->b, m->b, m->n_b, m->n_b));
+    } else {
+        SERT_TRY(dmalloc(&f->W, (size_t)d * Vf));      // (V_f == 0: no allocation, the pointers stay null and are never read)
+        SERT_TRY(dmalloc(&f->b, (size_t)Vf));
     }
     SERT_HIP(hipStreamCreate(&f->stream));
     hipStream_t s = f->stream;
@@ -172,33 +152,20 @@ static int llf_create(sert_ll_foldin* f, sert_model* m, bool refresh, const int3
     return 0;
 }
 
-static int llf_create_checked(sert_model* m, bool refresh, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
-                              const float* init_W, const float* init_b, const sert_ll_foldin_config* cfg, sert_ll_foldin** out) {
-    refresh_gemm_choice();
-    if (!m || !cfg || !out) SERT_FAIL("null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(sert_ll_foldin_config)) SERT_FAIL("sert_ll_foldin_config size mismatch (ABI)");
-    sert_ll_foldin* f = new sert_ll_foldin();
-    const int rc = llf_create(f, m, refresh, refresh_ids, num_refresh, num_new, init_W, init_b, cfg);
-    if (rc != 0) {
-        const std::string keep = g_last_error;
-        sert_ll_foldin_destroy(f);
-        g_last_error = keep;
-        return rc;
-    }
-    *out = f;
-    return 0;
-}
-
 int sert_ll_foldin_create(sert_model* m, int32_t num_new, const float* init_W, const float* init_b,
                           const sert_ll_foldin_config* cfg, sert_ll_foldin** out) {
-    return llf_create_checked(m, false, nullptr, 0, num_new, init_W, init_b, cfg, out);
+    refresh_gemm_choice();
+    return fold_create(m, cfg, out, "sert_ll_foldin_config size mismatch (ABI)", sert_ll_foldin_destroy,
+                       [&](sert_ll_foldin* f) { return llf_create(f, m, false, nullptr, 0, num_new, init_W, init_b, cfg); });
 }
 
 int sert_ll_foldin_create_refresh(sert_model* m, const int32_t* refresh_ids, int32_t num_refresh, int32_t num_new,
                                   const float* init_new_W, const float* init_new_b, const sert_ll_foldin_config* cfg,
                                   sert_ll_foldin** out) {
-    return llf_create_checked(m, true, refresh_ids, num_refresh, num_new, init_new_W, init_new_b, cfg, out);
+    refresh_gemm_choice();
+    return fold_create(m, cfg, out, "sert_ll_foldin_config size mismatch (ABI)", sert_ll_foldin_destroy, [&](sert_ll_foldin* f) {
+        return llf_create(f, m, true, refresh_ids, num_refresh, num_new, init_new_W, init_new_b, cfg);
+    });
 }
 
 // the split-K shape of dWn = Gb^T dZu over `rows` distinct words (the loglinear step's rule, step_softmax_loglinear.inc)
@@ -335,13 +302,7 @@ static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab,
     };
     const int rc = body();
     (void)hipFree(dwords);
-    if (rc != 0) {
-        const std::string keep = g_last_error;
-        (void)hipStreamSynchronize(s);
-        llf_free_upload(f);
-        g_last_error = keep;
-        return rc;
-    }
+    if (rc != 0) return fold_upload_failed(f, rc, llf_free_upload);
     f->M = M; f->D = D;
     f->lb_off.swap(lb_off); f->ptr_off.swap(ptr_off); f->U.swap(Us);
     return 0;
@@ -404,13 +365,10 @@ int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t
     return llf_upload(f, x, LlfLabels{nullptr, indptr, indices, data}, w, M);
 }
 
-int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f) { return f ? f->M / f->cfg.batch_size : -1; }
+int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f) { return fold_num_batches(f); }
 
 static int llf_check_batch(sert_ll_foldin* f, int64_t batch) {
-    if (!f) SERT_FAIL("null argument");
-    if (!f->G) SERT_FAIL("no fold-in instances uploaded (sert_ll_foldin_upload)");
-    if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
-    return 0;
+    return fold_check_batch(f, &sert_ll_foldin::G, "sert_ll_foldin_upload", batch);
 }
 
 // the forward of batch `batch` on the handle's stream: the new logits, the tokens' log-sum-exp, the row kernel (TRAIN: dZ of
@@ -489,51 +447,19 @@ static int llf_step_async(sert_ll_foldin* f, int64_t batch, float* dst) {
 }
 
 int sert_ll_foldin_train_batch(sert_ll_foldin* f, int64_t batch, float* loss_out) {
-    SERT_TRY(llf_check_batch(f, batch));
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_TRY(llf_step_async(f, batch, f->d_loss));
-    float host[3] = {0.f, 0.f, 0.f};
-    SERT_HIP(hipGetLastError());
-    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (loss_out) *loss_out = host[0];
-    return 0;
+    return fold_run_batch(f, batch, loss_out, llf_check_batch, llf_step_async);
 }
 
 int sert_ll_foldin_train_batches(sert_ll_foldin* f, const int64_t* batches, int64_t count, float* losses_out) {
-    if (!f || count < 0 || (count > 0 && !batches)) SERT_FAIL("bad argument");
-    for (int64_t i = 0; i < count; ++i) SERT_TRY(llf_check_batch(f, batches[i]));    // (before anything is enqueued)
-    if (count == 0) return 0;
-    SERT_HIP(hipSetDevice(f->device));
-    if (count > f->d_losses_cap) {
-        SERT_HIP(hipStreamSynchronize(f->stream));
-        (void)hipFree(f->d_losses);
-        f->d_losses = nullptr; f->d_losses_cap = 0;
-        SERT_TRY(dmalloc(&f->d_losses, (size_t)count * 3));
-        f->d_losses_cap = count;
-    }
-    for (int64_t i = 0; i < count; ++i) SERT_TRY(llf_step_async(f, batches[i], f->d_losses + 3 * i));
-    SERT_HIP(hipGetLastError());
-    std::vector<float> tmp((size_t)count * 3);
-    SERT_HIP(hipMemcpyAsync(tmp.data(), f->d_losses, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (losses_out)
-        for (int64_t i = 0; i < count; ++i) losses_out[i] = tmp[(size_t)3 * i];
-    return 0;
+    return fold_train_batches(f, batches, count, losses_out, llf_check_batch, llf_step_async);
 }
 
 int sert_ll_foldin_eval_batch(sert_ll_foldin* f, int64_t batch, float* loss_out) {
-    SERT_TRY(llf_check_batch(f, batch));
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_TRY(llf_forward(f, batch, false));
-    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, (const float*)f->rowloss, f->cfg.batch_size, (const float*)f->rowloss, 0,
-           1.0f / (float)f->cfg.batch_size, 0.0f, f->d_loss, (unsigned*)nullptr, 0u, (const float*)nullptr);
-    float host[3] = {0.f, 0.f, 0.f};
-    SERT_HIP(hipGetLastError());
-    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (loss_out) *loss_out = host[0];
-    return 0;
+    return fold_run_batch(f, batch, loss_out, llf_check_batch, [](sert_ll_foldin* h, int64_t b, float* dst) {
+        SERT_TRY(llf_forward(h, b, false));
+        fold_eval_finalize(h, (const float*)h->rowloss, h->cfg.batch_size, dst);
+        return 0;
+    });
 }
 
 static float* llf_tensor_ref(sert_ll_foldin* f, int which, size_t* count) {
@@ -549,28 +475,13 @@ static float* llf_tensor_ref(sert_ll_foldin* f, int which, size_t* count) {
     }
 }
 
-int sert_ll_foldin_get_tensor(sert_ll_foldin* f, int which, float* host, size_t count) {
-    if (!f || !host) SERT_FAIL("null argument");
-    size_t have = 0;
-    float* p = llf_tensor_ref(f, which, &have);
-    if (!p) SERT_FAIL("which must be one of SERT_LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B");
-    if (count != have) SERT_FAIL("element count mismatch");
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_HIP(hipMemcpyAsync(host, p, count * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    return 0;
-}
+static const char* const kLlfWhich = "which must be one of SERT_LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B";
 
+int sert_ll_foldin_get_tensor(sert_ll_foldin* f, int which, float* host, size_t count) {
+    return fold_copy_tensor(f, which, host, count, true, llf_tensor_ref, kLlfWhich);
+}
 int sert_ll_foldin_set_tensor(sert_ll_foldin* f, int which, const float* host, size_t count) {
-    if (!f || !host) SERT_FAIL("null argument");
-    size_t have = 0;
-    float* p = llf_tensor_ref(f, which, &have);
-    if (!p) SERT_FAIL("which must be one of SERT_LL_FOLDIN_W, _B, _ACCU_W, _ACCU_B, _DELTA_W, _DELTA_B");
-    if (count != have) SERT_FAIL("element count mismatch");
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    return 0;
+    return fold_copy_tensor(f, which, const_cast<float*>(host), count, false, llf_tensor_ref, kLlfWhich);
 }
 
 int sert_debug_ll_foldin_layout(sert_ll_foldin* f, int32_t* V_f, int32_t* Nt, int32_t* internal_of_public, int64_t count) {

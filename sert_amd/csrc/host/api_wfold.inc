@@ -3,19 +3,12 @@
 // handle copies the model's parameters when it is created and runs on a stream of its own: it shares nothing with the model's
 // step schedule.
 
-struct sert_wfold {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct sert_wfold : FoldNce {
     sert_wfold_config cfg;
-    int Vw = 0, Ve = 0, Nw = 0, dw = 0, de = 0, n = 0;
-    // the frozen snapshot; rw holds V_w + 1 rows: the last one is zero, what a new position gathers at upload
-    float *rw = nullptr, *W = nullptr, *b = nullptr, *re = nullptr;
-    // the new word rows, Adam's moments, the gradient
-    float *Nv = nullptr, *m1 = nullptr, *m2 = nullptr, *G = nullptr;
+    int Nw = 0;
+    // (FoldNce's snapshot: rw holds V_w + 1 rows here; the last one is zero, what a new position gathers at upload)
+    float* Nv = nullptr;             // the new word rows (FoldNce: Adam's moments m1, m2 and the gradient G)
     // the uploaded instances
-    int64_t M = 0;
-    int32_t* y = nullptr;
-    float* w = nullptr;
     float* A0 = nullptr;             // (M, d_e)  hf W + b
     int32_t* tok = nullptr;          // (M, n)    the new word of a position, -1: frozen
     // the inverted index new word -> batch rows (wfold_index.h)
@@ -23,22 +16,12 @@ struct sert_wfold {
     int32_t* idx_rows = nullptr;
     int4* idx_items = nullptr;
     float* part = nullptr;           // (max_part_rows, d_e)
-    // per-step scratch
+    // per-step scratch (FoldNce's coef and this cand: written by the loss kernel, read by nobody -- the entity table is frozen)
     float* P = nullptr;              // (Nw, d_e)  Nv W
     float* T = nullptr;              // (B, d_e)
     float* DA = nullptr;             // (B, d_e)
     float* S = nullptr;              // (Nw, d_e)
-    int32_t* neg = nullptr;          // (B, z)
-    int64_t* neg_stage = nullptr;    // (B, z) host-supplied negatives
-    float* coef = nullptr;           // (B, 1 + z): written by the loss kernel, read by nobody (the entity table is frozen)
-    int32_t* cand = nullptr;         // (B, 1 + z): the same
-    float* rowloss = nullptr;        // (B)
-    float* red_loss = nullptr;       // per-workgroup loss partials of vs_nce
-    float* red_sq = nullptr;         // [kOptBlocks] sums of squares of Nv
-    float* d_loss = nullptr;         // [3]
-    float* d_losses = nullptr;       // multi-step loss ring
-    int64_t d_losses_cap = 0;
-    int64_t step = 0, eval_draws = 0;
+    int32_t* cand = nullptr;         // (B, 1 + z)
     // what the last step launched, recorded where the launches are made: sert_debug_wfold_plan (sert_hip_debug.h)
     int32_t plan[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
@@ -53,18 +36,9 @@ static void wfold_free_upload(sert_wfold* f) {
 
 int sert_wfold_destroy(sert_wfold* f) {
     if (!f) return 0;
-    if (f->device >= 0) {
-        (void)hipSetDevice(f->device);
-        if (f->stream) (void)hipStreamSynchronize(f->stream);
-    }
-    wfold_free_upload(f);
-    for (void* p : {(void*)f->rw, (void*)f->W, (void*)f->b, (void*)f->re, (void*)f->Nv, (void*)f->m1, (void*)f->m2, (void*)f->G,
-                    (void*)f->P, (void*)f->T, (void*)f->DA, (void*)f->S, (void*)f->neg, (void*)f->neg_stage, (void*)f->coef,
-                    (void*)f->cand, (void*)f->rowloss, (void*)f->red_loss, (void*)f->red_sq, (void*)f->d_loss, (void*)f->d_losses})
-        (void)hipFree(p);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
-    return 0;
+    return fold_destroy(f, wfold_free_upload,
+                        {f->rw, f->W, f->b, f->re, f->Nv, f->m1, f->m2, f->G, f->P, f->T, f->DA, f->S, f->neg, f->neg_stage, f->coef,
+                         f->cand, f->rowloss, f->red_loss, f->red_sq});
 }
 
 static int wfold_create(sert_wfold* f, sert_model* m, int32_t num_new_words, const float* init_rows, const sert_wfold_config* cfg) {
@@ -88,22 +62,8 @@ static int wfold_create(sert_wfold* f, sert_model* m, int32_t num_new_words, con
     f->Vw = c.vocab_size; f->Ve = c.num_entities; f->Nw = num_new_words; f->dw = c.word_dim; f->de = c.entity_dim; f->n = c.window_size;
     const int B = cfg->batch_size, z = cfg->num_negatives, de = f->de, dw = f->dw, Nw = f->Nw;
     const size_t n_v = (size_t)Nw * dw;
-    // the parameters as a reader must see them (sert_foldin_create)
-    SERT_TRY(ensure_full_rw(m));
-    SERT_TRY(ensure_rw_current(m, -1));
-    if (m->comm_stream) SERT_HIP(hipStreamSynchronize(m->comm_stream));
-    if (m->stream2) SERT_HIP(hipStreamSynchronize(m->stream2));
-    SERT_TRY(settle_entity_update(m));
-    flush_pending_tail(m);
-    SERT_TRY(dmalloc(&f->rw, round_up(m->n_rw + (size_t)dw, 4)));
-    SERT_TRY(dmalloc(&f->W, m->n_w));
-    SERT_TRY(dmalloc(&f->b, m->n_b));
-    SERT_TRY(dmalloc(&f->re, std::max<size_t>(m->n_re, 4)));
-    SERT_HIP(hipMemcpyAsync(f->rw, m->rw, m->n_rw * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    SERT_HIP(hipMemsetAsync(f->rw + m->n_rw, 0, (round_up(m->n_rw + (size_t)dw, 4) - m->n_rw) * sizeof(float), m->stream));
-    SERT_HIP(hipMemcpyAsync(f->W, m->W, m->n_w * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    SERT_HIP(hipMemcpyAsync(f->b, m->b, m->n_b * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
-    if (m->n_re) SERT_HIP(hipMemcpyAsync(f->re, m->re, m->n_re * sizeof(float), hipMemcpyDeviceToDevice, m->stream));
+    SERT_TRY(fold_settle_model(m, true));
+    SERT_TRY(fold_snapshot_vs(f, m, 1));
     SERT_HIP(hipStreamCreate(&f->stream));
     hipStream_t s = f->stream;
     SERT_TRY(dmalloc(&f->Nv, round_up(n_v, 4)));
@@ -124,26 +84,13 @@ static int wfold_create(sert_wfold* f, sert_model* m, int32_t num_new_words, con
     SERT_TRY(dmalloc(&f->red_loss, (size_t)cdiv(B, 16)));
     SERT_TRY(dmalloc(&f->red_sq, (size_t)kOptBlocks));
     SERT_TRY(dmalloc(&f->d_loss, (size_t)3));
-    SERT_HIP(hipStreamSynchronize(s));             // (init_rows is borrowed for the call only)
-    SERT_HIP(hipStreamSynchronize(m->stream));     // (the snapshot is complete: the model may train or go away)
-    return 0;
+    return fold_created(f, m);      // (init_rows is borrowed for the call only)
 }
 
 int sert_wfold_create(sert_model* m, int32_t num_new_words, const float* init_rows, const sert_wfold_config* cfg, sert_wfold** out) {
     refresh_gemm_choice();
-    if (!m || !cfg || !out) SERT_FAIL("null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(sert_wfold_config)) SERT_FAIL("sert_wfold_config size mismatch (ABI)");
-    sert_wfold* f = new sert_wfold();
-    const int rc = wfold_create(f, m, num_new_words, init_rows, cfg);
-    if (rc != 0) {
-        const std::string keep = g_last_error;
-        sert_wfold_destroy(f);
-        g_last_error = keep;
-        return rc;
-    }
-    *out = f;
-    return 0;
+    return fold_create(m, cfg, out, "sert_wfold_config size mismatch (ABI)", sert_wfold_destroy,
+                       [&](sert_wfold* f) { return wfold_create(f, m, num_new_words, init_rows, cfg); });
 }
 
 // launch_gemm, and the route it takes (gemm.h: GemmRoute) -- asked of the launcher's own predicates, for the plan
@@ -163,7 +110,7 @@ int sert_wfold_upload(sert_wfold* f, const int32_t* x, const int32_t* y, const f
     refresh_gemm_choice();
     if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
     if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
-    const int n = f->n, dw = f->dw, de = f->de, B = f->cfg.batch_size;
+    const int n = f->n, de = f->de, B = f->cfg.batch_size;
     // host-side validation: no kernel is launched on bad ids
     for (int64_t i = 0; i < M; ++i)
         if (y[i] < 0 || y[i] >= f->Ve) SERT_FAIL("fold-in label out of range [0, num_entities)");
@@ -183,77 +130,36 @@ int sert_wfold_upload(sert_wfold* f, const int32_t* x, const int32_t* y, const f
         for (size_t k = 0; k < tok.size(); ++k) tok[k] = x[k] < f->Vw ? -1 : x[k] - f->Vw;
         build_wfold_index(tok.data(), nbatches, B, n, f->Nw, index);
     }
-    uint32_t* dx = nullptr;
-    int32_t* xs = nullptr;
-    float* H = nullptr;
-    const int64_t slab = std::min<int64_t>(M, 65536);
+    std::vector<float> ones;
     auto body = [&]() -> int {
-        SERT_TRY(dmalloc(&f->y, (size_t)M));
-        SERT_TRY(dmalloc(&f->w, (size_t)M));
+        SERT_TRY(fold_upload_labels(f, y, w, M, ones));
         SERT_TRY(dmalloc(&f->A0, (size_t)M * de));
         SERT_TRY(dmalloc(&f->tok, (size_t)M * n));
         SERT_TRY(dmalloc(&f->idx_rows, std::max<size_t>(index.rows.size(), 1)));
         SERT_TRY(dmalloc(&f->idx_items, std::max<size_t>(index.items.size(), 1)));
         SERT_TRY(dmalloc(&f->part, std::max<size_t>((size_t)index.max_part_rows * de, 4)));
-        SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        const std::vector<float> ones(w ? (size_t)0 : (size_t)M, 1.0f);
-        SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
         if (!index.rows.empty())
             SERT_HIP(hipMemcpyAsync(f->idx_rows, index.rows.data(), index.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!index.items.empty())
             SERT_HIP(hipMemcpyAsync(f->idx_items, index.items.data(), index.items.size() * sizeof(SegItem), hipMemcpyHostToDevice, s));
-        // A0 = hf W + b once, by the model's forward (vs_gather_mean on the snapshot, the new positions pointed at its appended
-        // zero row; the projection GEMM), a slab of rows at a time
-        SERT_TRY(dmalloc(&xs, (size_t)slab * n));
-        SERT_TRY(dmalloc(&dx, (size_t)slab * n));
-        SERT_TRY(dmalloc(&H, (size_t)slab * dw));
-        for (int64_t r0 = 0; r0 < M; r0 += slab) {
-            const int rows = (int)std::min<int64_t>(slab, M - r0);
-            SERT_HIP(hipMemcpyAsync(xs, x + (size_t)r0 * n, (size_t)rows * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            launch(wfold_split_ids, dim3(grid_for((int64_t)rows * n)), dim3(256), 0, s, (const int32_t*)xs, dx, f->tok + (size_t)r0 * n,
+        // A0 = hf W + b once: the new positions are pointed at the snapshot's appended zero row
+        return fold_project_slabs<EPI_BIAS>(f, x, M, f->A0, [&](const int32_t* xs, uint32_t* dx, int64_t r0, int rows) {
+            launch(wfold_split_ids, dim3(grid_for((int64_t)rows * n)), dim3(256), 0, s, xs, dx, f->tok + (size_t)r0 * n,
                    (int64_t)rows * n, f->Vw);
-            if (dw % 4 == 0)
-                launch((vs_gather_mean<uint32_t, 4>), dim3(grid_for((int64_t)rows * dw / 4, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
-            else
-                launch((vs_gather_mean<uint32_t, 1>), dim3(grid_for((int64_t)rows * dw, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
-            launch_gemm<false, false, EPI_BIAS>(s, H, f->W, f->A0 + (size_t)r0 * de, f->b, rows, de, dw, dw, de, de);
-        }
-        SERT_HIP(hipGetLastError());
-        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w and the host index are borrowed for the call only)
-        return 0;
+        });
     };
     const int rc = body();
-    (void)hipFree(dx); (void)hipFree(xs); (void)hipFree(H);
-    if (rc != 0) {
-        const std::string keep = g_last_error;
-        (void)hipStreamSynchronize(s);
-        wfold_free_upload(f);
-        g_last_error = keep;
-        return rc;
-    }
+    if (rc != 0) return fold_upload_failed(f, rc, wfold_free_upload);
     f->idx_batches.swap(index.batches);
     f->M = M;
     return 0;
 }
 
-int64_t sert_wfold_num_batches(sert_wfold* f) { return f ? f->M / f->cfg.batch_size : -1; }
+int64_t sert_wfold_num_batches(sert_wfold* f) { return fold_num_batches(f); }
 
-// the step's negatives into f->neg: the caller's (validated before anything is launched) or the Philox sampler's over V_e
+// the step's negatives into f->neg, over V_e
 static int wfold_negatives(sert_wfold* f, const int64_t* negatives, uint64_t stream_pos) {
-    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
-    if (negatives) {
-        for (int64_t i = 0; i < count; ++i)
-            if (negatives[i] < 0 || negatives[i] >= f->Ve) SERT_FAIL("negative sample out of range [0, num_entities)");
-        SERT_HIP(hipMemcpyAsync(f->neg_stage, negatives, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, f->stream));
-        launch(convert_i64_to_i32, dim3(grid_for(count)), dim3(256), 0, f->stream, (const int64_t*)f->neg_stage, f->neg, count);
-    } else {
-        // (even = training draws, odd = evaluation draws, as the model's sampler)
-        launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, f->stream, f->neg, count, (int64_t)0,
-               (uint32_t)f->Ve, f->cfg.seed, stream_pos, (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
-    }
-    return 0;
+    return fold_negatives(f, negatives, stream_pos, (int64_t)f->Ve, "negative sample out of range [0, num_entities)");
 }
 
 // steps 1 to 3 on batch `batch`: P = Nv W, T = tanh(A0 + sum P / n), the model's loss kernel on T (train: weighted, DA
@@ -338,152 +244,69 @@ static int wfold_segsum(sert_wfold* f, int64_t batch) {
 }
 
 static int wfold_check_batch(sert_wfold* f, int64_t batch) {
-    if (!f) SERT_FAIL("null argument");
-    if (!f->A0) SERT_FAIL("no fold-in instances uploaded (sert_wfold_upload)");
-    if (batch < 0 || (batch + 1) * (int64_t)f->cfg.batch_size > f->M) SERT_FAIL("batch index out of range");
-    return 0;
+    return fold_check_batch(f, &sert_wfold::A0, "sert_wfold_upload", batch);
 }
 
 // one step enqueued on the handle's stream; dst: 3 floats on the device (finalize_loss: loss, data term, regulariser)
 static int wfold_step_async(sert_wfold* f, int64_t batch, const int64_t* negatives, float* dst) {
-    const auto& c = f->cfg;
-    const int B = c.batch_size;
-    hipStream_t s = f->stream;
     SERT_TRY(wfold_negatives(f, negatives, (uint64_t)f->step * 2));
     const float* parts = nullptr;
     int n_parts = 0;
     SERT_TRY(wfold_forward_loss(f, batch, true, &parts, &n_parts));
     SERT_TRY(wfold_segsum(f, batch));
     // G = S W^T: the form of the step's dh GEMM
-    f->plan[13] = wfold_gemm<false, true, EPI_STORE>(s, f->S, f->W, f->G, nullptr, f->Nw, f->dw, f->de, f->de, f->de, f->dw);
-    // Adam over Nv with the model's arithmetic, exactly as foldin_step_async runs it
-    f->step += 1;
-    const float tf = (float)f->step;
-    AdamArgs aa{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr * sqrtf(1.0f - powf(c.beta2, tf)) / (1.0f - powf(c.beta1, tf)),
-                c.beta1, c.beta2, c.eps};
-    const size_t n_v = (size_t)f->Nw * f->dw;
-    const int nb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)n_v, 4), 256)));
-    launch((adam_l2<false>), dim3(nb), dim3(256), 0, s, f->Nv, f->G, f->m1, f->m2, n_v, aa, f->red_sq, (const uint32_t*)nullptr,
-           1u, (int)kRowsAll, (float*)nullptr);
-    launch(finalize_loss, dim3(1), dim3(256), 0, s, parts, n_parts, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0,
-           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    f->plan[13] = wfold_gemm<false, true, EPI_STORE>(f->stream, f->S, f->W, f->G, nullptr, f->Nw, f->dw, f->de, f->de, f->de, f->dw);
+    fold_adam_finalize(f, f->Nv, (size_t)f->Nw * f->dw, parts, n_parts, dst);
     return 0;
 }
 
 int sert_wfold_train_batch(sert_wfold* f, int64_t batch, const int64_t* negatives, float* loss_out) {
     refresh_gemm_choice();
-    SERT_TRY(wfold_check_batch(f, batch));
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_TRY(wfold_step_async(f, batch, negatives, f->d_loss));
-    float host[3] = {0.f, 0.f, 0.f};
-    SERT_HIP(hipGetLastError());
-    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (loss_out) *loss_out = host[0];
-    return 0;
+    return fold_run_batch(f, batch, loss_out, wfold_check_batch,
+                          [&](sert_wfold* h, int64_t b, float* dst) { return wfold_step_async(h, b, negatives, dst); });
 }
 
 int sert_wfold_train_batches(sert_wfold* f, const int64_t* batches, int64_t count, float* losses_out) {
     refresh_gemm_choice();
-    if (!f || count < 0 || (count > 0 && !batches)) SERT_FAIL("bad argument");
-    for (int64_t i = 0; i < count; ++i) SERT_TRY(wfold_check_batch(f, batches[i]));    // (before anything is enqueued)
-    if (count == 0) return 0;
-    SERT_HIP(hipSetDevice(f->device));
-    if (count > f->d_losses_cap) {
-        SERT_HIP(hipStreamSynchronize(f->stream));
-        (void)hipFree(f->d_losses);
-        f->d_losses = nullptr; f->d_losses_cap = 0;
-        SERT_TRY(dmalloc(&f->d_losses, (size_t)count * 3));
-        f->d_losses_cap = count;
-    }
-    for (int64_t i = 0; i < count; ++i) SERT_TRY(wfold_step_async(f, batches[i], nullptr, f->d_losses + 3 * i));
-    SERT_HIP(hipGetLastError());
-    std::vector<float> tmp((size_t)count * 3);
-    SERT_HIP(hipMemcpyAsync(tmp.data(), f->d_losses, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (losses_out)
-        for (int64_t i = 0; i < count; ++i) losses_out[i] = tmp[(size_t)3 * i];
-    return 0;
+    return fold_train_batches(f, batches, count, losses_out, wfold_check_batch,
+                              [](sert_wfold* h, int64_t b, float* dst) { return wfold_step_async(h, b, nullptr, dst); });
 }
 
 int sert_wfold_eval_batch(sert_wfold* f, int64_t batch, const int64_t* negatives, float* loss_out) {
     refresh_gemm_choice();
-    SERT_TRY(wfold_check_batch(f, batch));
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_TRY(wfold_negatives(f, negatives, (uint64_t)f->eval_draws * 2 + 1));
-    if (!negatives) ++f->eval_draws;
-    const float* parts = nullptr;
-    int n_parts = 0;
-    SERT_TRY(wfold_forward_loss(f, batch, false, &parts, &n_parts));
-    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, parts, n_parts, parts, 0, 1.0f / (float)f->cfg.batch_size, 0.0f,
-           f->d_loss, (unsigned*)nullptr, 0u, (const float*)nullptr);
-    float host[3] = {0.f, 0.f, 0.f};
-    SERT_HIP(hipGetLastError());
-    SERT_HIP(hipMemcpyAsync(host, f->d_loss, sizeof host, hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    if (loss_out) *loss_out = host[0];
-    return 0;
+    return fold_run_batch(f, batch, loss_out, wfold_check_batch, [&](sert_wfold* h, int64_t b, float* dst) {
+        SERT_TRY(wfold_negatives(h, negatives, (uint64_t)h->eval_draws * 2 + 1));
+        if (!negatives) ++h->eval_draws;
+        const float* parts = nullptr;
+        int n_parts = 0;
+        SERT_TRY(wfold_forward_loss(h, b, false, &parts, &n_parts));
+        fold_eval_finalize(h, parts, n_parts, dst);
+        return 0;
+    });
 }
 
 int sert_wfold_negatives_of_step(sert_wfold* f, int64_t position, int evaluation, int64_t* out) {
     if (!f || !out || position < 0) SERT_FAIL("bad argument");
-    SERT_HIP(hipSetDevice(f->device));
-    const int64_t count = (int64_t)f->cfg.batch_size * f->cfg.num_negatives;
-    int32_t* tmp = nullptr;
-    SERT_HIP(hipMalloc((void**)&tmp, (size_t)count * sizeof(int32_t)));
-    // a stream of its own: nothing of the handle's state is touched
-    hipStream_t st = nullptr;
-    if (hipStreamCreate(&st) != hipSuccess) { (void)hipFree(tmp); SERT_FAIL("hipStreamCreate failed"); }
-    launch(vs_sample_negatives, dim3(grid_for((count + 3) / 4)), dim3(256), 0, st, tmp, count, (int64_t)0, (uint32_t)f->Ve,
-           f->cfg.seed, (uint64_t)position * 2 + (evaluation ? 1 : 0), (float4*)nullptr, (size_t)0, (uint4*)nullptr, (size_t)0);
-    std::vector<int32_t> host((size_t)count);
-    const hipError_t e = hipMemcpyAsync(host.data(), tmp, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-    (void)hipFree(tmp);
-    if (e != hipSuccess || e2 != hipSuccess) SERT_FAIL("reading the negatives back failed");
-    for (int64_t i = 0; i < count; ++i) out[i] = host[(size_t)i];
-    return 0;
+    return fold_negatives_of_step(f, position, evaluation, out, (int64_t)f->Ve);
 }
 
-static float* wfold_rows_ref(sert_wfold* f, int which) {
+static float* wfold_rows_ref(sert_wfold* f, int which, size_t* count) {
+    *count = (size_t)f->Nw * f->dw;
     return which == SERT_WFOLD_ROWS ? f->Nv : which == SERT_WFOLD_M ? f->m1 : which == SERT_WFOLD_V ? f->m2 : nullptr;
 }
+static const char* const kWfoldWhich = "which must be SERT_WFOLD_ROWS, SERT_WFOLD_M or SERT_WFOLD_V";
 
 int sert_wfold_get_rows(sert_wfold* f, int which, float* host, size_t count) {
-    if (!f || !host) SERT_FAIL("null argument");
-    float* p = wfold_rows_ref(f, which);
-    if (!p) SERT_FAIL("which must be SERT_WFOLD_ROWS, SERT_WFOLD_M or SERT_WFOLD_V");
-    if (count != (size_t)f->Nw * f->dw) SERT_FAIL("element count mismatch");
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_HIP(hipMemcpyAsync(host, p, count * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    return 0;
+    return fold_copy_tensor(f, which, host, count, true, wfold_rows_ref, kWfoldWhich);
 }
-
 int sert_wfold_set_rows(sert_wfold* f, int which, const float* host, size_t count) {
-    if (!f || !host) SERT_FAIL("null argument");
-    float* p = wfold_rows_ref(f, which);
-    if (!p) SERT_FAIL("which must be SERT_WFOLD_ROWS, SERT_WFOLD_M or SERT_WFOLD_V");
-    if (count != (size_t)f->Nw * f->dw) SERT_FAIL("element count mismatch");
-    SERT_HIP(hipSetDevice(f->device));
-    SERT_HIP(hipMemcpyAsync(p, host, count * sizeof(float), hipMemcpyHostToDevice, f->stream));
-    SERT_HIP(hipStreamSynchronize(f->stream));
-    return 0;
+    return fold_copy_tensor(f, which, const_cast<float*>(host), count, false, wfold_rows_ref, kWfoldWhich);
 }
 
-int sert_wfold_set_step(sert_wfold* f, int64_t t) {
-    if (!f || t < 0) SERT_FAIL("bad argument");
-    f->step = t;
-    return 0;
-}
-int64_t sert_wfold_get_step(sert_wfold* f) { return f ? f->step : -1; }
-int sert_wfold_set_eval_draws(sert_wfold* f, int64_t n) {
-    if (!f || n < 0) SERT_FAIL("bad argument");
-    f->eval_draws = n;
-    return 0;
-}
-int64_t sert_wfold_get_eval_draws(sert_wfold* f) { return f ? f->eval_draws : -1; }
+int sert_wfold_set_step(sert_wfold* f, int64_t t) { return fold_set_counter(f, &FoldNce::step, t); }
+int64_t sert_wfold_get_step(sert_wfold* f) { return fold_get_counter(f, &FoldNce::step); }
+int sert_wfold_set_eval_draws(sert_wfold* f, int64_t n) { return fold_set_counter(f, &FoldNce::eval_draws, n); }
+int64_t sert_wfold_get_eval_draws(sert_wfold* f) { return fold_get_counter(f, &FoldNce::eval_draws); }
 
 int sert_debug_wfold_plan(sert_wfold* f, int32_t* out, int n) {
     if (!f || !out || n < 1 || n > 16) SERT_FAIL("bad argument");

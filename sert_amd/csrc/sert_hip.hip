@@ -199,6 +199,8 @@ extern "C" {
 
 #include "host/api_reval.inc"
 
+#include "host/foldin_common.inc"   // (in front of its three callers api_foldin.inc / api_ll_foldin.inc / api_wfold.inc)
+
 #include "host/api_foldin.inc"
 
 #include "host/api_ll_foldin.inc"

@@ -22,7 +22,109 @@ from sert_amd import _capi
 from sert_amd import models
 
 
-class EntityFoldIn(models.ModelInterface):
+class _FoldInModel(models.ModelInterface):
+    """What the three fold-in models share: one shuffled pass over the uploaded batches, the evaluation pass, and the life of
+    the device handle ``_foldin`` (a ``_capi`` owner made from an engine that may be a throwaway)."""
+
+    #: callable batch_index -> negatives, or None; only the NCE fold-ins have one
+    negative_sampler = None
+    #: batches issued to the device before their losses are read back (device-drawn negatives only)
+    steps_per_sync = 1
+
+    def _attach(self, engine, make_engine, make_handle):
+        """``_foldin`` = make_handle(engine); engine None: a parameters-only model from make_engine() holds the frozen tensors
+        on the device for the moment of the copy."""
+        owned = engine is None
+        if owned:
+            engine = make_engine()
+        try:
+            self._foldin = make_handle(engine)
+        finally:
+            if owned:
+                engine.close()      # (the handle copied what it needs)
+
+    def train_fn(self, batch_index):
+        return self._foldin.train_batch(batch_index)
+
+    def test_fn(self, batch_index):
+        return self._foldin.eval_batch(batch_index)
+
+    def train(self):
+        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
+        count = self.training_num_instances
+        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
+        if self.steps_per_sync > 1 and self.negative_sampler is None:
+            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
+                                                       report_interval=1000, shuffle=True)
+        else:
+            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
+        return num_batches, np.mean(losses)
+
+    def train_error(self):
+        """(mean, std) of the per-batch evaluation losses on the extended model: unweighted, unregularised."""
+        count = self.training_num_instances
+        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
+        _, losses = self._iterate_batches(self.test_fn, count)
+        return np.mean(losses), np.std(losses)
+
+    def close(self):
+        self._foldin.close()
+
+
+class _NceFoldInModel(_FoldInModel):
+    """The two fold-ins of a vectorspace model on top of it: host-side negative samplers, Adam's and the device sampler's
+    state, and the throwaway engine."""
+
+    #: callable batch_index -> (B, z) int64 negatives in the range the handle draws from, or None (device sampler)
+    negative_sampler = None
+    #: same, for train_error()
+    eval_negative_sampler = None
+    #: the keys of Adam's moments in get_optimizer_state()
+    _moment_keys = None
+
+    @staticmethod
+    def _vs_engine(R_w, R_e, W, b, window_size, device):
+        """A parameters-only vectorspace model on the device that holds the frozen tensors."""
+        R_w, R_e = np.asarray(R_w, dtype=np.float32), np.asarray(R_e, dtype=np.float32)
+        W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
+        assert W.shape == (R_w.shape[1], R_e.shape[1]) and b.shape == (R_e.shape[1],)
+        engine = _capi.Engine(
+            kind=_capi.KIND_VECTORSPACE, batch_size=1, global_batch_size=1, window_size=window_size,
+            vocab_size=R_w.shape[0], num_entities=R_e.shape[0], word_dim=R_w.shape[1], entity_dim=R_e.shape[1],
+            num_negatives=0, id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0,
+            lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0)
+        for which, value in ((_capi.T_RW, R_w), (_capi.T_RE, R_e), (_capi.T_W, W), (_capi.T_B, b)):
+            engine.set_tensor(which, value)
+        return engine
+
+    def train_fn(self, batch_index):
+        sampler = self.negative_sampler
+        return self._foldin.train_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
+
+    def test_fn(self, batch_index):
+        sampler = self.eval_negative_sampler
+        return self._foldin.eval_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
+
+    def get_optimizer_state(self):
+        m, v = self._moment_keys
+        return {'step': self._foldin.get_step(), m: self._foldin.get_rows(_capi.FOLDIN_M), v: self._foldin.get_rows(_capi.FOLDIN_V)}
+
+    def set_optimizer_state(self, st):
+        m, v = self._moment_keys
+        self._foldin.set_step(st['step'])
+        self._foldin.set_rows(_capi.FOLDIN_M, st[m])
+        self._foldin.set_rows(_capi.FOLDIN_V, st[v])
+
+    def get_sampler_state(self):
+        return {'seed': int(self._foldin.cfg.seed), 'eval_draws': self._foldin.get_eval_draws()}
+
+    def set_sampler_state(self, st):
+        if int(st['seed']) != int(self._foldin.cfg.seed):
+            raise RuntimeError('the sampler seed is fixed at construction')
+        self._foldin.set_eval_draws(st['eval_draws'])
+
+
+class EntityFoldIn(_NceFoldInModel):
     """N new entity rows learnt on top of a trained vectorspace model (R_w, R_e, W, b: host arrays, never written).
 
     training_set: (x (M, window_size) token ids of the TRAINED vocabulary, y (M,) in [0, N), w (M,) weights or None).
@@ -36,12 +138,8 @@ class EntityFoldIn(models.ModelInterface):
     Negatives stay ids of the extended table.  A refreshed row starts from its trained value and learns from the
     instances given: to keep its old evidence, pass the entity's old documents along with the new ones."""
 
-    #: callable batch_index -> (B, z) int64 negatives in [0, V_e + N), or None (device sampler)
-    negative_sampler = None
-    #: same, for train_error()
-    eval_negative_sampler = None
-    #: batches issued to the device before their losses are read back (device-drawn negatives only)
-    steps_per_sync = 1
+    #: negative_sampler / eval_negative_sampler draw from [0, V_e + N)
+    _moment_keys = ('m_E', 'v_E')
 
     def __init__(self, R_w, R_e, W, b, new_rows_init, training_set, batch_size, num_negative_samples,
                  regularization_lambda, window_size, seed=None, lr=1e-3, device=0, _engine=None, refresh=None):
@@ -67,26 +165,9 @@ class EntityFoldIn(models.ModelInterface):
         self.num_entities = int(np.shape(R_e)[0])
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
-        engine, owned = _engine, False
-        if engine is None:
-            # a parameters-only model on the device holds the frozen tensors for the moment of the copy
-            R_w, R_e = np.asarray(R_w, dtype=np.float32), np.asarray(R_e, dtype=np.float32)
-            W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
-            assert W.shape == (R_w.shape[1], R_e.shape[1]) and b.shape == (R_e.shape[1],)
-            engine = _capi.Engine(
-                kind=_capi.KIND_VECTORSPACE, batch_size=1, global_batch_size=1, window_size=self.window_size,
-                vocab_size=R_w.shape[0], num_entities=R_e.shape[0], word_dim=R_w.shape[1], entity_dim=R_e.shape[1],
-                num_negatives=0, id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0,
-                lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0)
-            owned = True
-            for which, value in ((_capi.T_RW, R_w), (_capi.T_RE, R_e), (_capi.T_W, W), (_capi.T_B, b)):
-                engine.set_tensor(which, value)
-        try:
-            self._foldin = _capi.FoldIn(engine, new_rows_init, batch_size, num_negative_samples, regularization_lambda,
-                                        lr=lr, seed=seed, refresh_ids=refresh)
-        finally:
-            if owned:
-                engine.close()      # (the handle copied what it needs)
+        self._attach(_engine, lambda: self._vs_engine(R_w, R_e, W, b, self.window_size, device),
+                     lambda engine: _capi.FoldIn(engine, new_rows_init, batch_size, num_negative_samples, regularization_lambda,
+                                                 lr=lr, seed=seed, refresh_ids=refresh))
         self._foldin.upload(x, y, w)
         if refresh is None:
             logging.info('Folding in %d new entities (rows %d .. %d) on %d instances.', self.num_new, self.num_entities,
@@ -105,33 +186,6 @@ class EntityFoldIn(models.ModelInterface):
         shape = (model.num_entities, model.entity_representation_size)
         return cls(None, _Shape(shape), None, None, new_rows_init, training_set, batch_size, num_negative_samples,
                    regularization_lambda, model.window_size, seed=seed, lr=lr, _engine=model._engine, refresh=refresh)
-
-    # -- the step functions ---------------------------------------------------------------------------------------
-    def train_fn(self, batch_index):
-        sampler = self.negative_sampler
-        return self._foldin.train_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
-
-    def test_fn(self, batch_index):
-        sampler = self.eval_negative_sampler
-        return self._foldin.eval_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
-
-    def train(self):
-        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
-        count = self.training_num_instances
-        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
-        if self.steps_per_sync > 1 and self.negative_sampler is None:
-            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
-                                                       report_interval=1000, shuffle=True)
-        else:
-            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
-        return num_batches, np.mean(losses)
-
-    def train_error(self):
-        """(mean, std) of the per-batch evaluation losses on the extended table: unweighted, unregularised."""
-        count = self.training_num_instances
-        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
-        _, losses = self._iterate_batches(self.test_fn, count)
-        return np.mean(losses), np.std(losses)
 
     # -- results and state --------------------------------------------------------------------------------------------
     def get_new_representations(self):
@@ -153,28 +207,8 @@ class EntityFoldIn(models.ModelInterface):
             ext[self.refresh] = rows[:self.num_refresh]
         return ext
 
-    def get_optimizer_state(self):
-        return {'step': self._foldin.get_step(), 'm_E': self._foldin.get_rows(_capi.FOLDIN_M),
-                'v_E': self._foldin.get_rows(_capi.FOLDIN_V)}
 
-    def set_optimizer_state(self, st):
-        self._foldin.set_step(st['step'])
-        self._foldin.set_rows(_capi.FOLDIN_M, st['m_E'])
-        self._foldin.set_rows(_capi.FOLDIN_V, st['v_E'])
-
-    def get_sampler_state(self):
-        return {'seed': int(self._foldin.cfg.seed), 'eval_draws': self._foldin.get_eval_draws()}
-
-    def set_sampler_state(self, st):
-        if int(st['seed']) != int(self._foldin.cfg.seed):
-            raise RuntimeError('the sampler seed is fixed at construction')
-        self._foldin.set_eval_draws(st['eval_draws'])
-
-    def close(self):
-        self._foldin.close()
-
-
-class LogLinearFoldIn(models.ModelInterface):
+class LogLinearFoldIn(_FoldInModel):
     """N new entities learnt on top of a trained loglinear model (R_w, W (d, V_e), b (V_e): host arrays, never written):
     N new columns Wn (d, N) of the output layer and N new biases bn, with the model's own loss over the V_e + N entities
     (include/sert_hip_ll_foldin.h).
@@ -196,9 +230,6 @@ class LogLinearFoldIn(models.ModelInterface):
     their columns: a trained column that is refreshed is a parameter, one that is not stays a frozen co-label.  A refreshed
     column starts from its trained value and bias and learns from the instances given: to keep its old evidence, pass the
     entity's old documents along with the new ones."""
-
-    #: batches issued to the device before their losses are read back
-    steps_per_sync = 1
 
     def __init__(self, R_w, W, b, new_W_init, new_b_init, training_set, batch_size, regularization_lambda, window_size,
                  device=0, max_cache_bytes=0, _engine=None, refresh=None):
@@ -241,25 +272,21 @@ class LogLinearFoldIn(models.ModelInterface):
         self.num_entities = int(np.shape(W)[1])
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
-        engine, owned = _engine, False
-        if engine is None:
-            # a parameters-only model on the device holds the frozen tensors for the moment of the copy
-            R_w, W, b = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
-            assert W.shape[0] == R_w.shape[1] and b.shape == (W.shape[1],)
+
+        def make_engine():
+            Rw, Wt, bt = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
+            assert Wt.shape[0] == Rw.shape[1] and bt.shape == (Wt.shape[1],)
             engine = _capi.Engine(
                 kind=_capi.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=self.window_size,
-                vocab_size=R_w.shape[0], num_entities=W.shape[1], word_dim=R_w.shape[1], entity_dim=0, num_negatives=0,
+                vocab_size=Rw.shape[0], num_entities=Wt.shape[1], word_dim=Rw.shape[1], entity_dim=0, num_negatives=0,
                 id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0, lr=1.0, beta1=0.95,
                 beta2=0.0, eps=1e-6, seed=0)
-            owned = True
-            for which, value in ((_capi.T_RW, R_w), (_capi.T_W, W), (_capi.T_B, b)):
+            for which, value in ((_capi.T_RW, Rw), (_capi.T_W, Wt), (_capi.T_B, bt)):
                 engine.set_tensor(which, value)
-        try:
-            self._foldin = _capi.LlFoldIn(engine, new_W_init, new_b_init, batch_size, regularization_lambda,
-                                          max_cache_bytes=max_cache_bytes, refresh_ids=refresh)
-        finally:
-            if owned:
-                engine.close()      # (the handle copied what it needs)
+            return engine
+        self._attach(_engine, make_engine,
+                     lambda engine: _capi.LlFoldIn(engine, new_W_init, new_b_init, batch_size, regularization_lambda,
+                                                   max_cache_bytes=max_cache_bytes, refresh_ids=refresh))
         if rows:
             self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
         else:
@@ -282,31 +309,6 @@ class LogLinearFoldIn(models.ModelInterface):
         return cls(None, _Shape((model.representation_size, model.output_layer_size)), None, new_W_init, new_b_init,
                    training_set, batch_size, regularization_lambda, model.window_size, max_cache_bytes=max_cache_bytes,
                    _engine=model._engine, refresh=refresh)
-
-    # -- the step functions ---------------------------------------------------------------------------------------
-    def train_fn(self, batch_index):
-        return self._foldin.train_batch(batch_index)
-
-    def test_fn(self, batch_index):
-        return self._foldin.eval_batch(batch_index)
-
-    def train(self):
-        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
-        count = self.training_num_instances
-        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
-        if self.steps_per_sync > 1:
-            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
-                                                       report_interval=1000, shuffle=True)
-        else:
-            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
-        return num_batches, np.mean(losses)
-
-    def train_error(self):
-        """(mean, std) of the per-batch evaluation losses on the extended model: unweighted, unregularised."""
-        count = self.training_num_instances
-        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
-        _, losses = self._iterate_batches(self.test_fn, count)
-        return np.mean(losses), np.std(losses)
 
     # -- results and state --------------------------------------------------------------------------------------------
     def get_new_dense(self):
@@ -345,9 +347,6 @@ class LogLinearFoldIn(models.ModelInterface):
                             ('delta_W', _capi.LL_FOLDIN_DELTA_W), ('delta_b', _capi.LL_FOLDIN_DELTA_B)):
             self._foldin.set_tensor(which, st[name])
 
-    def close(self):
-        self._foldin.close()
-
 
 def new_word_rows(vocab_size, num_new_words, word_dim):
     """(Nw, d_w) initial rows from the global np.random, uniform within the bound bin/train.py drew the trained R_w in:
@@ -357,7 +356,7 @@ def new_word_rows(vocab_size, num_new_words, word_dim):
     return np.random.uniform(low=-a, high=a, size=(num_new_words, word_dim)).astype(np.float32)
 
 
-class WordFoldIn(models.ModelInterface):
+class WordFoldIn(_NceFoldInModel):
     """Nw new word rows learnt on top of a trained vectorspace model (R_w, R_e, W, b: host arrays, never written).
 
     training_set: (x (M, window_size) token ids in [0, V_w + Nw) -- new word v is id V_w + v --, y (M,) trained entity
@@ -365,12 +364,8 @@ class WordFoldIn(models.ModelInterface):
     ``new_word_rows``, at the scale bin/train.py drew the trained rows.  The batch size, the number of negatives, lambda and the
     learning rate are the fold-in's own.  An instance without a new word is legal: it adds to the loss and moves nothing."""
 
-    #: callable batch_index -> (B, z) int64 negatives in [0, V_e), or None (device sampler)
-    negative_sampler = None
-    #: same, for train_error()
-    eval_negative_sampler = None
-    #: batches issued to the device before their losses are read back (device-drawn negatives only)
-    steps_per_sync = 1
+    #: negative_sampler / eval_negative_sampler draw from [0, V_e)
+    _moment_keys = ('m_Nv', 'v_Nv')
 
     def __init__(self, R_w, R_e, W, b, new_rows_init, training_set, batch_size, num_negative_samples,
                  regularization_lambda, window_size, seed=None, lr=1e-3, device=0, _engine=None):
@@ -391,26 +386,9 @@ class WordFoldIn(models.ModelInterface):
         self.vocab_size = vocab_size
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
-        engine, owned = _engine, False
-        if engine is None:
-            # a parameters-only model on the device holds the frozen tensors for the moment of the copy
-            R_w, R_e = np.asarray(R_w, dtype=np.float32), np.asarray(R_e, dtype=np.float32)
-            W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
-            assert W.shape == (R_w.shape[1], R_e.shape[1]) and b.shape == (R_e.shape[1],)
-            engine = _capi.Engine(
-                kind=_capi.KIND_VECTORSPACE, batch_size=1, global_batch_size=1, window_size=self.window_size,
-                vocab_size=R_w.shape[0], num_entities=R_e.shape[0], word_dim=R_w.shape[1], entity_dim=R_e.shape[1],
-                num_negatives=0, id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0,
-                lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=0)
-            owned = True
-            for which, value in ((_capi.T_RW, R_w), (_capi.T_RE, R_e), (_capi.T_W, W), (_capi.T_B, b)):
-                engine.set_tensor(which, value)
-        try:
-            self._foldin = _capi.WordFoldIn(engine, new_rows_init, batch_size, num_negative_samples, regularization_lambda,
-                                            lr=lr, seed=seed)
-        finally:
-            if owned:
-                engine.close()      # (the handle copied what it needs)
+        self._attach(_engine, lambda: self._vs_engine(R_w, R_e, W, b, self.window_size, device),
+                     lambda engine: _capi.WordFoldIn(engine, new_rows_init, batch_size, num_negative_samples,
+                                                     regularization_lambda, lr=lr, seed=seed))
         self._foldin.upload(x, y, w)
         logging.info('Folding in %d new words (token ids %d .. %d) on %d instances.', self.num_new_words, vocab_size,
                      vocab_size + self.num_new_words - 1, self.training_num_instances)
@@ -426,33 +404,6 @@ class WordFoldIn(models.ModelInterface):
         return cls(_Shape((int(cfg.vocab_size), int(cfg.word_dim))), None, None, None, new_rows_init, training_set, batch_size,
                    num_negative_samples, regularization_lambda, model.window_size, seed=seed, lr=lr, _engine=model._engine)
 
-    # -- the step functions ---------------------------------------------------------------------------------------
-    def train_fn(self, batch_index):
-        sampler = self.negative_sampler
-        return self._foldin.train_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
-
-    def test_fn(self, batch_index):
-        sampler = self.eval_negative_sampler
-        return self._foldin.eval_batch(batch_index, None if sampler is None else np.asarray(sampler(batch_index)))
-
-    def train(self):
-        """One pass over the complete batches in shuffled order, as ModelBase.train: (num_batches, mean loss)."""
-        count = self.training_num_instances
-        logging.info('Folding in on %d instances (%d batches).', count, self._number_of_batches(count))
-        if self.steps_per_sync > 1 and self.negative_sampler is None:
-            num_batches, losses = self._iterate_chunks(self._foldin.train_batches, count, int(self.steps_per_sync),
-                                                       report_interval=1000, shuffle=True)
-        else:
-            num_batches, losses = self._iterate_batches(self.train_fn, count, report_interval=1000, shuffle=True)
-        return num_batches, np.mean(losses)
-
-    def train_error(self):
-        """(mean, std) of the per-batch evaluation losses with the extended word table: unweighted, unregularised."""
-        count = self.training_num_instances
-        logging.info('Measuring error on %d fold-in instances (%d batches).', count, self._number_of_batches(count))
-        _, losses = self._iterate_batches(self.test_fn, count)
-        return np.mean(losses), np.std(losses)
-
     # -- results and state --------------------------------------------------------------------------------------------
     def get_new_word_representations(self):
         """(Nw, d_w): the new rows as they are now."""
@@ -463,26 +414,6 @@ class WordFoldIn(models.ModelInterface):
         R_w = np.asarray(R_w, dtype=np.float32)
         assert R_w.shape[0] == self.vocab_size
         return np.concatenate([R_w, self._foldin.get_rows(_capi.WFOLD_ROWS)], axis=0)
-
-    def get_optimizer_state(self):
-        return {'step': self._foldin.get_step(), 'm_Nv': self._foldin.get_rows(_capi.WFOLD_M),
-                'v_Nv': self._foldin.get_rows(_capi.WFOLD_V)}
-
-    def set_optimizer_state(self, st):
-        self._foldin.set_step(st['step'])
-        self._foldin.set_rows(_capi.WFOLD_M, st['m_Nv'])
-        self._foldin.set_rows(_capi.WFOLD_V, st['v_Nv'])
-
-    def get_sampler_state(self):
-        return {'seed': int(self._foldin.cfg.seed), 'eval_draws': self._foldin.get_eval_draws()}
-
-    def set_sampler_state(self, st):
-        if int(st['seed']) != int(self._foldin.cfg.seed):
-            raise RuntimeError('the sampler seed is fixed at construction')
-        self._foldin.set_eval_draws(st['eval_draws'])
-
-    def close(self):
-        self._foldin.close()
 
 
 class _Shape(object):

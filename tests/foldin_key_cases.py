@@ -29,7 +29,7 @@ from tests import foldin_cases as FC
 CHUNK = 16            # csrc/kernels_egrad.h: kEChunk
 SORT_TILE = 2048      # csrc/kernels_sort.h: kSortTile
 SORT_MAX_BITS = 11    # csrc/kernels_sort.h: kSortMaxBits
-SLAB = 65536          # csrc/host/api_foldin.inc: rows projected per slab of sert_foldin_upload
+SLAB = 65536          # csrc/host/foldin_common.inc, fold_project_slabs: rows projected per slab of sert_foldin_upload
 STEPS = 2
 VW, VE, DW, NWIN = 50, 7, 12, 3       # the base case of tests/foldin_cases.py: the forward is not what these cases are about
 LAM, LR = 0.01, 0.01

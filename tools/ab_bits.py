@@ -8,8 +8,12 @@ Each problem runs two training steps and both evaluations (a fold-in: two steps 
 the row losses, every parameter, gradient and optimiser moment, the fold-in rows, and the form the engine reports it
 took.  The entity-chain group runs two steps of every case of tests/egrad_key_cases.py (the sorted cases and, through the
 sort as well as on their own path, the bucket cases), tests/foldin_key_cases.py and tests/refresh_cases.py, and records dR_e
-after each step, or the fold-in's E, m and v, with the losses and the plan of the sorted chain (eg_plan, FoldIn.plan()).  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.  The
-library is chosen by SERT_LIB, read at import, and SERT_LL_NODEDUP once per process: every (library, group) runs in a fresh
+after each step, or the fold-in's E, m and v, with the losses and the plan of the sorted chain (eg_plan, FoldIn.plan()).  The
+fold-ins group runs every case of tests/ll_foldin_cases.py, tests/ll_foldin_label_cases.py, tests/ll_refresh_cases.py and
+tests/wfold_cases.py: two train_batch steps, one train_batches call over two batches and one eval_batch, with the losses and
+every trainable tensor and accumulator after each; a word fold-in once on the case's explicit negatives and once on
+device-drawn ones.  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.
+The library is chosen by SERT_LIB, read at import, and SERT_LL_NODEDUP once per process: every (library, group) runs in a fresh
 child process started with subprocess, one at a time.  The run fails if the forms taken do not cover FAMILIES."""
 import argparse
 import os
@@ -45,7 +49,13 @@ FAMILIES = (['ll %s %s %s' % (f, lab, m) for lab in ('int', 'csr') for f, m in
                                                  ('4,8', 'workgroup')]] +
             ['foldin reduce %s %s' % (i, f) for i, f in [('1,4', 'wave'), ('1,4', 'workgroup'), ('4,1', 'wave'), ('4,1', 'workgroup'),
                                                          ('4,2', 'workgroup'), ('4,5', 'wave'), ('4,5', 'workgroup'), ('4,8', 'wave'),
-                                                         ('4,8', 'workgroup')]])
+                                                         ('4,8', 'workgroup')]] +
+            # the loglinear fold-in: the label form, the creator, the window bucket of llf_row / llf_row_csr
+            ['llf %s plain n<=%d' % (lab, b) for lab in ('int', 'csr') for b in (8, 16, 32)] +
+            ['llf int refresh n<=8', 'llf csr refresh n<=8'] +
+            # the word fold-in, from WordFoldIn.plan(): wfold <project> <loss> <segsum> <train|eval>
+            ['wfold vector per_candidate rows32 train', 'wfold vector per_candidate none train', 'wfold vector per_candidate none eval',
+             'wfold scalar scalar scalar train', 'wfold scalar scalar none eval'])
 
 
 def run_engine(out, tag, eng, kind, uploads, form):
@@ -202,13 +212,80 @@ def chain_child(out):
     return forms
 
 
+def run_fold_steps(out, tag, f, state, form, negs=(None, None), eval_neg=None):
+    """Two train_batch steps, train_batches over two batches, one eval_batch; after each: the losses and state(f)."""
+    with_neg = lambda call, batch, neg: [call(batch)] if neg is None else [call(batch, neg)]      # (LlFoldIn takes none)
+    steps = [('s0', lambda: with_neg(f.train_batch, 0, negs[0])), ('s1', lambda: with_neg(f.train_batch, 1, negs[1])),
+             ('s23', lambda: f.train_batches([2, 0])), ('ev', lambda: with_neg(f.eval_batch, 1, eval_neg))]
+    forms = []
+    for name, call in steps:
+        out['%s/loss_%s' % (tag, name)] = np.asarray(call(), dtype=np.float32)
+        forms.append(form(name != 'ev'))
+        for k, v in state(f).items():
+            out['%s/%s_%s' % (tag, k, name)] = v
+    f.close()
+    return forms
+
+
+def foldins_child(out):
+    from sert_amd import _capi as C
+    from tests import ll_foldin_cases as LC
+    from tests import ll_foldin_label_cases as LL
+    from tests import ll_refresh_cases as RC
+    from tests import util as U
+    from tests import wfold_cases as WC
+    forms = []
+    ll_tensors = (('W', C.LL_FOLDIN_W), ('b', C.LL_FOLDIN_B), ('accu.W', C.LL_FOLDIN_ACCU_W), ('accu.b', C.LL_FOLDIN_ACCU_B),
+                  ('delta.W', C.LL_FOLDIN_DELTA_W), ('delta.b', C.LL_FOLDIN_DELTA_B))
+    for mod, prefix in ((LC, 'llf'), (LL, 'llf_labels'), (RC, 'llf_refresh')):
+        for name in sorted(mod.CASES):
+            c = mod.make_case(name)
+            eng = U.ll_engine(dict(Rw=c['Rw'], W=c['W'], b=c['b'], X=c['X']), 8, c['n'], 0.01, keep_grads=0)
+            refresh = c.get('refresh')
+            f = C.LlFoldIn(eng, c['Wn0'] if c['N'] else None, c['bn0'] if c['N'] else None, c['B'], c['lam'], refresh_ids=refresh)
+            eng.close()
+            csr = 'indptr' in c
+            if csr:
+                f.upload_csr(c['X'], c['indptr'], c['indices'], c['data'], c['w'])
+            else:
+                f.upload(c['X'], c['y'], c['w'])
+            # (no hook: the rule of llf_forward)
+            family = 'llf %s %s n<=%d' % ('csr' if csr else 'int', 'plain' if refresh is None else 'refresh',
+                                          8 if c['n'] <= 8 else 16 if c['n'] <= 16 else 32)
+            forms += run_fold_steps(out, '%s_%s' % (prefix, name), f, lambda h: dict((k, h.get_tensor(w)) for k, w in ll_tensors),
+                                    lambda train: family)
+    for name in sorted(WC.CASES):
+        c = WC.make_case(name)
+        for drawn in (False, True):
+            eng = C.Engine(kind=C.KIND_VECTORSPACE, batch_size=8, global_batch_size=8, window_size=c['n'], vocab_size=c['Vw'],
+                           num_entities=c['Ve'], word_dim=c['dw'], entity_dim=c['de'], num_negatives=2, id_bytes=4, device=0,
+                           keep_grads=0, deterministic=1, lambda_=0.01, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, seed=99)
+            for which, key in ((C.T_RW, 'Rw'), (C.T_RE, 'Re'), (C.T_W, 'W'), (C.T_B, 'b')):
+                eng.set_tensor(which, c[key])
+            f = C.WordFoldIn(eng, c['Nv0'], c['B'], c['z'], c['lam'], lr=c['lr'], seed=WC.SEED)
+            eng.close()
+            f.upload(c['X'], c['y'], c['w'])
+            tag = 'wfold_%s_%s' % (name, 'drawn' if drawn else 'explicit')
+            out[tag + '/neg_train0'], out[tag + '/neg_eval0'] = f.negatives_of_step(0), f.negatives_of_step(0, True)
+
+            def form(train, f=f):
+                pl = f.plan()
+                assert pl['train'] == train, pl
+                return 'wfold %s %s %s %s' % (pl['project'], pl['loss'], pl['segsum'], 'train' if train else 'eval')
+            forms += run_fold_steps(out, tag, f, lambda h: dict((k, h.get_rows(w)) for k, w in
+                                                                 (('Nv', C.WFOLD_ROWS), ('m', C.WFOLD_M), ('v', C.WFOLD_V))),
+                                    form, negs=(None, None) if drawn else (c['neg'][0], c['neg'][1]),
+                                    eval_neg=None if drawn else c['eval_neg'])
+    return forms
+
+
 def child(group, path):
     from sert_amd import _capi as C
     from tests import ll_nonfinite_cases as NF
     from tests import util as U
     out, forms = {}, []
-    if group == 'chain':
-        out['forms'] = np.array(sorted(set(chain_child(out))))
+    if group in ('chain', 'foldins'):
+        out['forms'] = np.array(sorted(set((chain_child if group == 'chain' else foldins_child)(out))))
         np.savez_compressed(path, **out)
         return
     for k, name in enumerate(sorted(LL if group == 'slots' else LL_PER_TOKEN)):
@@ -254,7 +331,7 @@ def main():
     if a.child:
         return child(a.child, a.out)
     merged = {}
-    for group in ('slots', 'tokens', 'chain'):
+    for group in ('slots', 'tokens', 'chain', 'foldins'):
         env = dict(os.environ)
         env.pop('SERT_LL_NODEDUP', None)
         if a.lib:
