@@ -64,6 +64,16 @@ R_w extended by the new rows, ``--meta_output`` the meta with the extended vocab
         --window_size 4 --meta_output new_meta --data_output new.npz
     python bin/fold_in.py --new_words --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
         --model_output model_15_words.bin --meta_output meta_words
+
+With ``--ll_new_words`` (loglinear dumps only) the same happens to an expert-finding model: new documents by people the model
+knows bring project names and acronyms the vocabulary has never seen, which bin/query.py drops from every query.  ``--new_meta``
+/ ``--data`` come from the same bin/prepare.py run (``--vocabulary_from META --extend_vocabulary``); the trained word rows and
+the whole output layer W, b stay as they are and only the rows of the new words learn (sert_amd.foldin.LogLinearWordFoldIn),
+with the model's own loss, one instance per label, on the windows that hold a new word.  ``--model_output`` is a dump whose R_w
+-- in the dump and in its predict function -- has the new rows appended; ``--num_negative_samples`` is not read.
+
+    python bin/fold_in.py --ll_new_words --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
+        --model_output model_15_words.bin --meta_output meta_words
 """
 import argparse
 import logging
@@ -112,6 +122,10 @@ def build_parser():
                         help='vectorspace dumps only: fold in the new WORDS of --new_meta (bin/prepare.py --vocabulary_from META '
                              '--extend_vocabulary) instead of entities: their rows of R_w learn, everything trained stays as it '
                              'is.  Every entity of --new_meta must be known to --meta.')
+    parser.add_argument('--ll_new_words', action='store_true', default=False,
+                        help='loglinear dumps only: fold in the new WORDS of --new_meta (bin/prepare.py --vocabulary_from META '
+                             '--extend_vocabulary) instead of entities: their rows of R_w learn with the model\'s own loss, '
+                             'R_w, W and b stay as they are.  Every entity of --new_meta must be known to --meta.')
     parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     return parser
@@ -261,6 +275,65 @@ def fold_in_words(args):
     fold.close()
 
 
+def fold_in_ll_words(args):
+    """--ll_new_words on a loglinear dump (namespace, LogLinearPredictFn, R_w): the rows of the new words of --new_meta learn
+    (sert_amd.foldin.LogLinearWordFoldIn); there are no negatives to draw, so --num_negative_samples is not read."""
+    if args.refresh or args.unfreeze_known or args.label_distributions:
+        raise RuntimeError('--ll_new_words folds words into a loglinear model, one instance per label: --refresh, '
+                           '--unfreeze_known and --label_distributions do not apply.')
+    dump = training.read_checkpoint(args.model)
+    model_args, predict_fn = dump['args'], dump['predict_fn']
+    if getattr(model_args, 'type', None) is not models.LanguageModel:
+        raise RuntimeError('--ll_new_words needs a loglinear model: the words of a vectorspace model are folded in with '
+                           '--new_words (found %r).' % (getattr(model_args, 'type', None),))
+    R_w = np.asarray(dump['tables'][0])
+    meta = foldin.read_meta(args.meta)
+    new_meta = foldin.read_meta(args.new_meta)
+    V_w = R_w.shape[0]
+    W, b = np.asarray(predict_fn.W), np.asarray(predict_fn.b)
+    if V_w != len(meta[1]) or W.shape[1] != len(meta[3]):
+        raise RuntimeError('%s holds %d word rows and %d entities but %s names %d words and %d entities: they are not of the '
+                           'same model.' % (args.model, V_w, W.shape[1], args.meta, len(meta[1]), len(meta[3])))
+    # (refuses a vocabulary that does not extend the trained one and an entity the model does not know, before anything is computed)
+    extended_meta = foldin.extend_meta_words(meta, new_meta)
+    new_words = foldin.new_words_of(meta, new_meta)
+    if not new_words:
+        raise RuntimeError('nothing to fold in: %s holds no word that %s does not know.' % (args.new_meta, args.meta))
+    x, y, w = one_hot_training_set(args.data)
+    # labels: entity index of --new_meta -> trained index
+    index_of = dict((entity_id, index) for index, entity_id in meta[3].items())
+    trained = np.array([index_of[new_meta[3][e]] for e in range(len(new_meta[3]))], dtype=np.int32)
+    y = trained[y] if y.size else y.astype(np.int32)
+    # a window without a new word cannot move a trainable row
+    keep = (np.asarray(x) >= V_w).any(axis=1)
+    logging.info('Dropped %d of %d windows that hold no new word.', int((~keep).sum()), int(keep.size))
+    if not keep.any():
+        raise RuntimeError('nothing to fold in: no window of %s holds a new word.' % args.data)
+    x, y = np.asarray(x)[keep].astype(np.int32), y[keep]
+    w = None if w is None else np.asarray(w)[keep]
+    new_rows = foldin.new_word_rows(V_w, len(new_words), R_w.shape[1])
+    fold = foldin.LogLinearWordFoldIn(R_w, W, b, new_rows, (x, y, w), batch_size=args.batch_size,
+                                      regularization_lambda=args.regularization_lambda, window_size=meta[0].window_size,
+                                      device=args.device)
+    mean, stddev = fold.train_error()
+    logging.info('Epoch 0: fold-in error %.6f (stddev %.6f).', mean, stddev)
+    for epoch in range(1, args.iterations + 1):
+        num_batches, loss = fold.train()
+        mean, stddev = fold.train_error()
+        logging.info('Epoch %d: %d batches, mean training loss %.6f; fold-in error %.6f (stddev %.6f).',
+                     epoch, num_batches, loss, mean, stddev)
+    for path in (args.model_output, args.meta_output):
+        directory = os.path.dirname(path)
+        if directory and not os.path.exists(directory):
+            os.makedirs(directory)
+    foldin.write_dump(args.model_output, foldin.extend_ll_words_dump(model_args, predict_fn, R_w,
+                                                                     fold.get_new_word_representations()))
+    foldin.write_meta(args.meta_output, extended_meta)
+    logging.info('Saved the extended model "%s" (%d + %d words) and its meta "%s".', args.model_output, V_w, len(new_words),
+                 args.meta_output)
+    fold.close()
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
@@ -270,10 +343,16 @@ def main(argv=None):
     if args.seed is not None:
         np.random.seed(args.seed)
 
+    if args.new_words and args.ll_new_words:
+        raise RuntimeError('--new_words and --ll_new_words exclude each other: --new_words folds words into a vectorspace dump, '
+                           '--ll_new_words into a loglinear one.')
     if args.new_words:
         if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:
-            raise RuntimeError('--new_words needs a vectorspace model: a word fold-in of a loglinear model is not supported.')
+            raise RuntimeError('--new_words needs a vectorspace model: the words of a loglinear model are folded in with '
+                               '--ll_new_words.')
         return fold_in_words(args)
+    if args.ll_new_words:
+        return fold_in_ll_words(args)
 
     # the dump's model type decides: a loglinear dump takes the path of its own, anything else the vectorspace one below
     if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:

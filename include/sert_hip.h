@@ -445,6 +445,12 @@ int sert_score_topk(int device, const float* entities, int64_t num_entities, int
  * calls are declared in sert_hip_wfold.h, which is part of this boundary. */
 #include "sert_hip_wfold.h"
 
+/* ---- folding unseen words into a trained loglinear model ---------------- */
+
+/* The same for the expert-finding model: the trained word rows, W and b stay fixed and only the rows of the new words learn,
+ * with the model's own loss.  The handle and its calls are declared in sert_hip_ll_wfold.h, which is part of this boundary. */
+#include "sert_hip_ll_wfold.h"
+
 /* ---- data parallel (new: the reference is single-device) ---- */
 
 #define SERT_COMM_ID_BYTES 128

@@ -138,6 +138,22 @@ int sert_debug_wfold_index(const int32_t* tok, int64_t num_batches, int B, int n
                            int32_t* rows_out, int64_t rows_cap, int32_t* items_out, int64_t items_cap, int64_t* num_rows,
                            int64_t* num_items);
 
+/* What the LAST step of a loglinear word fold-in handle launched (include/sert_hip_ll_wfold.h; kernels in
+ * csrc/kernels_ll_wfold.h, dispatch in csrc/host/api_ll_wfold.inc: llw_forward, llw_segsum, llw_grad_gemm) -- host record
+ * written where the launches are made, test hook, no device is touched: out[0] the row kernel's form (SERT_LL_WFOLD_FORM_*),
+ * out[1] 1 when it reads and writes 16-byte pieces (V_e % 4 == 0), out[2] 1 for the training instance and 0 for the evaluating
+ * one, out[3] the levels of the batch's reduction (0: the batch holds no new word), out[4 + l] the items of level l < 6, out[10]
+ * the reduction kernel (SERT_WGRAD_FORM_ROWS64 / _SCALAR; 0 without a level), out[11] / out[12] the GEMM kernel chosen for
+ * Zn = Nv W + b and for G = dZ W^T (SERT_GEMM_ROUTE_*), out[13] the k ranges of G (1: one launch, no combine).  n <= 16; all
+ * zero before the first step.  An evaluation runs the forward alone: out[3..10], out[12] and out[13] are zero after it. */
+enum {
+    SERT_LL_WFOLD_FORM_NONE = 0,
+    SERT_LL_WFOLD_FORM_REG = 1,      /* llw_row<TRAIN, LLW_FORM_REG>: V_e <= 1024, J in four registers per thread */
+    SERT_LL_WFOLD_FORM_STREAM = 2    /* llw_row<TRAIN, LLW_FORM_STREAM>: J through DJ, overwritten in place */
+};
+typedef struct sert_ll_wfold sert_ll_wfold;
+int sert_debug_ll_wfold_plan(sert_ll_wfold* f, int32_t* out, int n);
+
 /* The column layout of a loglinear fold-in handle (include/sert_hip_ll_foldin.h: sert_ll_foldin_create_refresh;
  * csrc/ll_label_remap.h) -- host record, test hook, no device is touched: *V_f the frozen columns the step kernels see as
  * V_e, *Nt the trainable ones they see as N (either may be NULL), internal_of_public[e] the internal column of public column e

@@ -27,6 +27,7 @@ def _stale():
     deps.append(os.path.join(INCLUDE, 'sert_hip_foldin.h'))
     deps.append(os.path.join(INCLUDE, 'sert_hip_ll_foldin.h'))
     deps.append(os.path.join(INCLUDE, 'sert_hip_wfold.h'))
+    deps.append(os.path.join(INCLUDE, 'sert_hip_ll_wfold.h'))
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -71,7 +71,7 @@ EXPORTS = [
     'sert_comm_unique_id', 'sert_comm_init', 'sert_comm_init_host', 'sert_comm_destroy', 'sert_comm_stats',
     'sert_synchronize', 'sert_timing_enable', 'sert_timing_reset', 'sert_timing_count',
     'sert_timing_name', 'sert_timing_avg_us', 'sert_timing_launches', 'sert_bench_gemm', 'sert_debug_gemm', 'sert_debug_gemm_splitk', 'sert_debug_gemm_longk', 'sert_debug_gemm_route', 'sert_bench_memory', 'sert_debug_row_lists', 'sert_debug_word_index_sum',
-    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_ll_foldin_layout', 'sert_debug_wfold_plan', 'sert_debug_wfold_index', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
+    'sert_debug_update_counts', 'sert_debug_tail_counts', 'sert_debug_state_counts', 'sert_debug_ll_loss_form', 'sert_debug_egrad_plan', 'sert_debug_nce_form', 'sert_debug_foldin_plan', 'sert_debug_foldin_table', 'sert_debug_ll_foldin_layout', 'sert_debug_wfold_plan', 'sert_debug_wfold_index', 'sert_debug_ll_wfold_plan', 'sert_debug_wgrad_plan', 'sert_debug_vs_plan', 'sert_debug_vs_facts', 'sert_debug_vs_plan_for', 'sert_debug_poison_scratch', 'sert_debug_ll_rank_distributions', 'sert_debug_reval_chunks', 'sert_debug_scorer_counts', 'sert_debug_scorer_select', 'sert_debug_scorer_rank_counts', 'sert_debug_scorer_rank_select', 'sert_debug_scorer_rerank_counts',
     'sert_debug_count_ranks', 'sert_debug_ll_rank_candidates_distributions', 'sert_debug_ll_rerank_counts',
     'sert_profile_range_push', 'sert_profile_range_pop',
 ]
@@ -100,6 +100,14 @@ EXPORTS_WFOLD = [
     'sert_wfold_set_eval_draws', 'sert_wfold_get_eval_draws',
 ]
 WFOLD_ROWS, WFOLD_M, WFOLD_V = 0, 1, 2
+# ... and include/sert_hip_ll_wfold.h, which sert_hip.h includes as well (folding unseen WORDS into a trained loglinear model)
+EXPORTS_LL_WFOLD = [
+    'sert_ll_wfold_create', 'sert_ll_wfold_destroy', 'sert_ll_wfold_upload', 'sert_ll_wfold_num_batches',
+    'sert_ll_wfold_train_batch', 'sert_ll_wfold_train_batches', 'sert_ll_wfold_eval_batch',
+    'sert_ll_wfold_get_rows', 'sert_ll_wfold_set_rows',
+]
+LL_WFOLD_ROWS, LL_WFOLD_ACCU, LL_WFOLD_DELTA = 0, 1, 2
+LL_WFOLD_FORMS = ('none', 'reg', 'stream')             # SERT_LL_WFOLD_FORM_* (include/sert_hip_debug.h)
 WFOLD_PROJECT_FORMS = ('none', 'vector', 'scalar')     # SERT_WFOLD_PROJECT_* (include/sert_hip_debug.h)
 FOLDIN_LOSS_FORMS = ('none', 'vector', 'scalar')       # SERT_FOLDIN_LOSS_* (include/sert_hip_debug.h)
 
@@ -167,6 +175,11 @@ class SertLlFoldInConfig(ctypes.Structure):
         ('eps', ctypes.c_float),
         ('max_cache_bytes', ctypes.c_uint64),
     ]
+
+
+class SertLlWFoldConfig(ctypes.Structure):
+    """sert_ll_wfold_config (include/sert_hip_ll_wfold.h)."""
+    _fields_ = list(SertLlFoldInConfig._fields_)
 
 
 class SertError(RuntimeError):
@@ -269,6 +282,17 @@ def load():
     lib.sert_wfold_set_eval_draws.argtypes = [vp, i64]
     lib.sert_wfold_get_eval_draws.argtypes = [vp]
     lib.sert_wfold_get_eval_draws.restype = i64
+    lib.sert_ll_wfold_create.argtypes = [vp, i32, fp, ctypes.POINTER(SertLlWFoldConfig), ctypes.POINTER(vp)]
+    lib.sert_ll_wfold_destroy.argtypes = [vp]
+    lib.sert_ll_wfold_upload.argtypes = [vp, fp, fp, fp, i64]
+    lib.sert_ll_wfold_num_batches.argtypes = [vp]
+    lib.sert_ll_wfold_num_batches.restype = i64
+    lib.sert_ll_wfold_train_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_ll_wfold_train_batches.argtypes = [vp, fp, i64, fp]
+    lib.sert_ll_wfold_eval_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
+    lib.sert_ll_wfold_get_rows.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_ll_wfold_set_rows.argtypes = [vp, ctypes.c_int, fp, sz]
+    lib.sert_debug_ll_wfold_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
     lib.sert_debug_wfold_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
     lib.sert_debug_wfold_index.argtypes = [fp, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, fp, fp, i64, fp, i64,
                                            ctypes.POINTER(i64), ctypes.POINTER(i64)]
@@ -1152,10 +1176,10 @@ class RetrievalEval(object):
 
 
 class _FoldHandle(object):
-    """What the owners of the three fold-in handles share: the handle ``_h``, the prefix of its library functions, the
+    """What the owners of the four fold-in handles share: the handle ``_h``, the prefix of its library functions, the
     (x, y, w) upload validation, the batch calls and the destruction."""
 
-    _prefix = None          # 'sert_foldin_', 'sert_wfold_', 'sert_ll_foldin_'
+    _prefix = None          # 'sert_foldin_', 'sert_wfold_', 'sert_ll_foldin_', 'sert_ll_wfold_'
 
     def _fn(self, name):
         return getattr(self._lib, self._prefix + name)
@@ -1485,6 +1509,57 @@ class LlFoldIn(_FoldHandle):
                                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_int64]
         check(self._lib.sert_debug_ll_foldin_layout(self._h, ctypes.byref(vf), ctypes.byref(nt), out.ctypes.data, out.size))
         return int(vf.value), int(nt.value), out
+
+
+class LlWordFoldIn(_FoldHandle):
+    """Owner of one sert_ll_wfold handle (include/sert_hip_ll_wfold.h): ``num_new_words`` word rows learnt on top of the frozen
+    parameters of ``engine`` (a loglinear Engine), which are copied at construction -- the engine may train on or be closed
+    afterwards.  New word v is token id ``vocab_size + v``; labels are trained entities."""
+
+    _prefix = 'sert_ll_wfold_'
+
+    def __init__(self, engine, new_rows_init, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0):
+        self._lib = load()
+        self._h = None
+        rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != engine.cfg.word_dim:
+            raise SertError('new_rows_init must be (num_new_words, word_dim)')
+        c = SertLlWFoldConfig()
+        c.struct_size = ctypes.sizeof(SertLlWFoldConfig)
+        c.batch_size, c.lambda_ = int(batch_size), float(lambda_)
+        c.lr, c.rho, c.eps, c.max_cache_bytes = float(lr), float(rho), float(eps), int(max_cache_bytes)
+        self.cfg = c
+        self.num_new_words, self.word_dim = int(rows.shape[0]), int(rows.shape[1])
+        self._rows_shape = (self.num_new_words, self.word_dim)
+        self.vocab_size = int(engine.cfg.vocab_size)
+        self.num_entities = int(engine.cfg.num_entities)
+        self.window_size = int(engine.cfg.window_size)
+        h = ctypes.c_void_p()
+        check(self._lib.sert_ll_wfold_create(engine._h, self.num_new_words, rows.ctypes.data if rows.size else None,
+                                             ctypes.byref(c), ctypes.byref(h)))
+        self._h = h
+
+    def get_rows(self, which=0):
+        """``which``: LL_WFOLD_ROWS (Nv) / LL_WFOLD_ACCU / LL_WFOLD_DELTA (Adadelta's accumulators of Nv)."""
+        out = np.empty(self._rows_shape, dtype=np.float32)
+        check(self._lib.sert_ll_wfold_get_rows(self._h, int(which), out.ctypes.data, out.size))
+        return out
+
+    def set_rows(self, which, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        check(self._lib.sert_ll_wfold_set_rows(self._h, int(which), a.ctypes.data, a.size))
+
+    def plan(self):
+        """sert_debug_ll_wfold_plan (test hook): what the last step of this handle launched -- 'form' (none / reg / stream: the
+        instance of llw_row), 'vec' (16-byte rows), 'train', 'levels' of the batch's reduction and its 'items' per level,
+        'segsum' (rows64 / scalar; none without a level), 'gemm_z' / 'gemm_g' (GEMM_ROUTES; gemm_g is 'none' after an
+        evaluation), 'splits' (the k ranges of G).  All zero before the first step."""
+        v = (ctypes.c_int32 * 16)()
+        check(self._lib.sert_debug_ll_wfold_plan(self._h, v, 16))
+        v = [int(x) for x in v]
+        route = lambda code: GEMM_ROUTES[code - 1] if code >= 1 else 'none'
+        return {'form': LL_WFOLD_FORMS[v[0]], 'vec': bool(v[1]), 'train': bool(v[2]), 'levels': v[3], 'items': v[4:4 + v[3]],
+                'segsum': WGRAD_FORMS[v[10]], 'gemm_z': route(v[11]), 'gemm_g': route(v[12]), 'splits': v[13]}
 
 
 def bench_gemm(M, N, K, ta=0, tb=0, epi=0, splits=1, iters=20, device=0):

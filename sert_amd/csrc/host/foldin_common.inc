@@ -1,10 +1,10 @@
 // Part of sert_hip.hip (one translation unit; included there, inside its extern "C" block, in front of api_foldin.inc): the
-// runtime the three fold-in handles share (api_foldin.inc: sert_foldin; api_ll_foldin.inc: sert_ll_foldin; api_wfold.inc:
-// sert_wfold).  Every piece below is stated once; what a handle validates, its own buffers, its forward, its gradient and its
+// runtime the four fold-in handles share (api_foldin.inc: sert_foldin; api_ll_foldin.inc: sert_ll_foldin; api_wfold.inc:
+// sert_wfold; api_ll_wfold.inc: sert_ll_wfold).  Every piece below is stated once; what a handle validates, its own buffers, its forward, its gradient and its
 // plan stay in its file.  Nothing here calls refresh_gemm_choice(): that is the public entry points' business.
 extern "C++" {
 
-// What every fold-in handle holds.  (cfg stays in the handle: the three config structs are distinct ABI structs.)
+// What every fold-in handle holds.  (cfg stays in the handle: the four config structs are distinct ABI structs.)
 struct FoldBase {
     int device = -1;
     hipStream_t stream = nullptr;

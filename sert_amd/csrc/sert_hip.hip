@@ -42,6 +42,7 @@
 #include "kernels_foldin.h"
 #include "kernels_ll_foldin.h"
 #include "kernels_wfold.h"
+#include "kernels_ll_wfold.h"
 #include "wfold_index.h"
 #include "ll_label_remap.h"
 #ifdef SERT_VARIANTS
@@ -199,13 +200,15 @@ extern "C" {
 
 #include "host/api_reval.inc"
 
-#include "host/foldin_common.inc"   // (in front of its three callers api_foldin.inc / api_ll_foldin.inc / api_wfold.inc)
+#include "host/foldin_common.inc"   // (in front of its four callers api_foldin.inc / api_ll_foldin.inc / api_wfold.inc / api_ll_wfold.inc)
 
 #include "host/api_foldin.inc"
 
 #include "host/api_ll_foldin.inc"
 
 #include "host/api_wfold.inc"
+
+#include "host/api_ll_wfold.inc"
 
 #include "host/api_comm.inc"
 

@@ -11,6 +11,9 @@ columns and biases of trained entities that gained documents learn too (bin/fold
 ``WordFoldIn`` is the other half of a catalogue that changes after training (include/sert_hip_wfold.h): the VOCABULARY grows.
 The trained word rows, the projection and the whole entity table stay fixed and only the rows of the new words learn
 (bin/prepare.py --extend_vocabulary, bin/fold_in.py --new_words).
+
+``LogLinearWordFoldIn`` is the same for a trained loglinear model (include/sert_hip_ll_wfold.h): the trained word rows, W and b
+stay fixed and the rows of the new words learn with the model's own loss (bin/fold_in.py --ll_new_words).
 """
 import logging
 import pickle
@@ -23,7 +26,7 @@ from sert_amd import models
 
 
 class _FoldInModel(models.ModelInterface):
-    """What the three fold-in models share: one shuffled pass over the uploaded batches, the evaluation pass, and the life of
+    """What the four fold-in models share: one shuffled pass over the uploaded batches, the evaluation pass, and the life of
     the device handle ``_foldin`` (a ``_capi`` owner made from an engine that may be a throwaway)."""
 
     #: callable batch_index -> negatives, or None; only the NCE fold-ins have one
@@ -416,6 +419,81 @@ class WordFoldIn(_NceFoldInModel):
         return np.concatenate([R_w, self._foldin.get_rows(_capi.WFOLD_ROWS)], axis=0)
 
 
+class LogLinearWordFoldIn(_FoldInModel):
+    """Nw new word rows learnt on top of a trained loglinear model (R_w, W (d, V_e), b (V_e): host arrays, never written), with
+    the model's own loss (include/sert_hip_ll_wfold.h).
+
+    training_set: (x (M, window_size) token ids in [0, V_w + Nw) -- new word v is id V_w + v --, y (M,) trained entity
+    indices in [0, V_e), w (M,) weights or None).  ``new_rows_init`` None: Nw = x.max() + 1 - V_w rows drawn by
+    ``new_word_rows``, at the scale bin/train.py drew the trained rows.  The batch size and lambda are the fold-in's own.
+    ``max_cache_bytes``: a cap on the frozen table of the upload (0: none).  An instance without a new word is legal: it adds to
+    the loss and moves nothing."""
+
+    def __init__(self, R_w, W, b, new_rows_init, training_set, batch_size, regularization_lambda, window_size, device=0,
+                 max_cache_bytes=0, _engine=None):
+        super(LogLinearWordFoldIn, self).__init__(batch_size)
+        x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
+        w = training_set[2] if len(training_set) > 2 else None
+        assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        vocab_size, word_dim = int(np.shape(R_w)[0]), int(np.shape(R_w)[1])
+        if new_rows_init is None:
+            if not x.size or int(x.max()) < vocab_size:
+                raise RuntimeError('no token of a new word and no initial rows: nothing says how many words are new')
+            new_rows_init = new_word_rows(vocab_size, int(x.max()) + 1 - vocab_size, word_dim)
+        new_rows_init = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        self.window_size = int(window_size)
+        self.num_new_words = int(new_rows_init.shape[0])
+        self.vocab_size = vocab_size
+        self.training_num_instances = int(y.shape[0])
+        _capi.require_gpu()
+
+        def make_engine():
+            Rw, Wt, bt = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
+            assert Wt.shape[0] == Rw.shape[1] and bt.shape == (Wt.shape[1],)
+            engine = _capi.Engine(
+                kind=_capi.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=self.window_size,
+                vocab_size=Rw.shape[0], num_entities=Wt.shape[1], word_dim=Rw.shape[1], entity_dim=0, num_negatives=0,
+                id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0, lr=1.0, beta1=0.95,
+                beta2=0.0, eps=1e-6, seed=0)
+            for which, value in ((_capi.T_RW, Rw), (_capi.T_W, Wt), (_capi.T_B, bt)):
+                engine.set_tensor(which, value)
+            return engine
+        self._attach(_engine, make_engine,
+                     lambda engine: _capi.LlWordFoldIn(engine, new_rows_init, batch_size, regularization_lambda,
+                                                       max_cache_bytes=max_cache_bytes))
+        self._foldin.upload(x, y, w)
+        logging.info('Folding in %d new words (token ids %d .. %d) on %d instances.', self.num_new_words, vocab_size,
+                     vocab_size + self.num_new_words - 1, self.training_num_instances)
+
+    @classmethod
+    def from_model(cls, model, new_rows_init, training_set, batch_size, regularization_lambda, max_cache_bytes=0):
+        """From a live ``models.LanguageModel``: its parameters as they are now are copied on the device (the model may train
+        on or be dropped afterwards)."""
+        if not isinstance(model, models.LanguageModel):
+            raise RuntimeError('a loglinear word fold-in needs a LanguageModel')
+        cfg = model._engine.cfg
+        return cls(_Shape((int(cfg.vocab_size), int(cfg.word_dim))), None, None, new_rows_init, training_set, batch_size,
+                   regularization_lambda, model.window_size, max_cache_bytes=max_cache_bytes, _engine=model._engine)
+
+    # -- results and state --------------------------------------------------------------------------------------------
+    def get_new_word_representations(self):
+        """(Nw, d): the new rows as they are now."""
+        return self._foldin.get_rows(_capi.LL_WFOLD_ROWS)
+
+    def get_extended_word_representations(self, R_w):
+        """(V_w + Nw, d): the trained rows ``R_w`` (the caller's: never modified) with the new rows behind."""
+        R_w = np.asarray(R_w, dtype=np.float32)
+        assert R_w.shape[0] == self.vocab_size
+        return np.concatenate([R_w, self._foldin.get_rows(_capi.LL_WFOLD_ROWS)], axis=0)
+
+    def get_optimizer_state(self):
+        return {'accu_Nv': self._foldin.get_rows(_capi.LL_WFOLD_ACCU), 'delta_Nv': self._foldin.get_rows(_capi.LL_WFOLD_DELTA)}
+
+    def set_optimizer_state(self, st):
+        self._foldin.set_rows(_capi.LL_WFOLD_ACCU, st['accu_Nv'])
+        self._foldin.set_rows(_capi.LL_WFOLD_DELTA, st['delta_Nv'])
+
+
 class _Shape(object):
     """Stands in for a table the constructor only asks the shape of (from_model: the table itself stays on the device)."""
 
@@ -467,6 +545,20 @@ def extend_words_dump(args, predict_fn, R_w, R_e, new_rows):
     new_rows = np.asarray(new_rows, dtype=R_w.dtype)
     assert new_rows.ndim == 2 and new_rows.shape[1] == R_w.shape[1]
     return [args, predict_fn, np.concatenate([R_w, new_rows], axis=0), R_e]
+
+
+def extend_ll_words_dump(args, predict_fn, R_w, new_rows):
+    """The objects of a loglinear model dump (args, LogLinearPredictFn, R_w) with the word table extended by the rows of the
+    new words, in the dump and in the predict function alike; the caller's R_w and ``predict_fn`` are not modified, W and b are
+    the trained ones.  bin/query.py and LogLinearPredictFn.rank_queries serve it unchanged."""
+    st = predict_fn.__getstate__()
+    R_w = np.asarray(R_w)
+    trained = np.asarray(st['R_w'])
+    new_rows = np.asarray(new_rows, dtype=R_w.dtype)
+    assert new_rows.ndim == 2 and new_rows.shape[1] == R_w.shape[1] and trained.shape == R_w.shape
+    extended = models.LogLinearPredictFn(R_w=np.concatenate([trained, new_rows.astype(trained.dtype)], axis=0), W=np.asarray(st['W']),
+                                         b=np.asarray(st['b']), window_size=st['window_size'])
+    return [args, extended, np.concatenate([R_w, new_rows], axis=0)]
 
 
 WORDS_FIRST_ADVICE = ('fold the entities in first (bin/fold_in.py without --new_words) and prepare the documents against the '
