@@ -74,6 +74,17 @@ with the model's own loss, one instance per label, on the windows that hold a ne
 
     python bin/fold_in.py --ll_new_words --meta meta --model model_15.bin --new_meta new_meta --data new.npz --iterations 10 \\
         --model_output model_15_words.bin --meta_output meta_words
+
+With ``--ll_new_words --label_rows`` the new word rows learn from the loss the expert-finding recipe trains with: ``y_train`` of
+``--data`` stays the sparse matrix it is -- one instance per window, its labels a distribution over the document's people, as
+bin/train.py --type loglinear learns without ``--one_hot_classes`` -- instead of one instance per label.  The columns are moved
+from ``--new_meta``'s entity index to the trained one; an entity the trained meta does not know stays refused (fold the entities
+in first).  This is the loss that produced the frozen R_w, W and b beside the new rows, and there are as many instances as
+windows, not windows times co-authors.  ``--label_rows`` is not ``--label_distributions``, which is the entity fold-in's flag
+(unknown ids become new columns) and stays refused with ``--ll_new_words``.
+
+    python bin/fold_in.py --ll_new_words --label_rows --meta meta --model model_15.bin --new_meta new_meta --data new.npz \\
+        --iterations 10 --model_output model_15_words.bin --meta_output meta_words
 """
 import argparse
 import logging
@@ -126,6 +137,10 @@ def build_parser():
                         help='loglinear dumps only: fold in the new WORDS of --new_meta (bin/prepare.py --vocabulary_from META '
                              '--extend_vocabulary) instead of entities: their rows of R_w learn with the model\'s own loss, '
                              'R_w, W and b stay as they are.  Every entity of --new_meta must be known to --meta.')
+    parser.add_argument('--label_rows', action='store_true', default=False,
+                        help='with --ll_new_words only: learn from the label rows of --data (y_train as the sparse matrix it is, '
+                             'as bin/train.py --type loglinear does without --one_hot_classes) instead of one instance per '
+                             'label.  Every entity of --new_meta must be known to --meta.')
     parser.add_argument('--model_output', type=au.nonexisting_file_path, required=True)
     parser.add_argument('--meta_output', type=au.nonexisting_file_path, required=True)
     return parser
@@ -277,7 +292,8 @@ def fold_in_words(args):
 
 def fold_in_ll_words(args):
     """--ll_new_words on a loglinear dump (namespace, LogLinearPredictFn, R_w): the rows of the new words of --new_meta learn
-    (sert_amd.foldin.LogLinearWordFoldIn); there are no negatives to draw, so --num_negative_samples is not read."""
+    (sert_amd.foldin.LogLinearWordFoldIn); there are no negatives to draw, so --num_negative_samples is not read.
+    --label_rows: the instances keep their label rows, columns moved to the trained entity index."""
     if args.refresh or args.unfreeze_known or args.label_distributions:
         raise RuntimeError('--ll_new_words folds words into a loglinear model, one instance per label: --refresh, '
                            '--unfreeze_known and --label_distributions do not apply.')
@@ -299,11 +315,16 @@ def fold_in_ll_words(args):
     new_words = foldin.new_words_of(meta, new_meta)
     if not new_words:
         raise RuntimeError('nothing to fold in: %s holds no word that %s does not know.' % (args.new_meta, args.meta))
-    x, y, w = one_hot_training_set(args.data)
     # labels: entity index of --new_meta -> trained index
     index_of = dict((entity_id, index) for index, entity_id in meta[3].items())
     trained = np.array([index_of[new_meta[3][e]] for e in range(len(new_meta[3]))], dtype=np.int32)
-    y = trained[y] if y.size else y.astype(np.int32)
+    if args.label_rows:
+        (x, y, w), _ = training.load_data_sets(args.data)
+        assert y.shape[1] <= trained.size
+        y = foldin.remap_label_columns(y, trained, W.shape[1])
+    else:
+        x, y, w = one_hot_training_set(args.data)
+        y = trained[y] if y.size else y.astype(np.int32)
     # a window without a new word cannot move a trainable row
     keep = (np.asarray(x) >= V_w).any(axis=1)
     logging.info('Dropped %d of %d windows that hold no new word.', int((~keep).sum()), int(keep.size))
@@ -346,6 +367,10 @@ def main(argv=None):
     if args.new_words and args.ll_new_words:
         raise RuntimeError('--new_words and --ll_new_words exclude each other: --new_words folds words into a vectorspace dump, '
                            '--ll_new_words into a loglinear one.')
+    if args.label_rows and (args.new_words or not args.ll_new_words):
+        raise RuntimeError('--label_rows needs --ll_new_words: it keeps the label rows of --data for a word fold-in into a '
+                           'loglinear model.  A vectorspace model (--new_words) learns from one entity per instance (NCE); an '
+                           'entity fold-in into a loglinear model takes label rows with --label_distributions.')
     if args.new_words:
         if getattr(training.read_checkpoint(args.model)['args'], 'type', None) is models.LanguageModel:
             raise RuntimeError('--new_words needs a vectorspace model: the words of a loglinear model are folded in with '

@@ -144,8 +144,13 @@ int sert_debug_wfold_index(const int32_t* tok, int64_t num_batches, int B, int n
  * out[1] 1 when it reads and writes 16-byte pieces (V_e % 4 == 0), out[2] 1 for the training instance and 0 for the evaluating
  * one, out[3] the levels of the batch's reduction (0: the batch holds no new word), out[4 + l] the items of level l < 6, out[10]
  * the reduction kernel (SERT_WGRAD_FORM_ROWS64 / _SCALAR; 0 without a level), out[11] / out[12] the GEMM kernel chosen for
- * Zn = Nv W + b and for G = dZ W^T (SERT_GEMM_ROUTE_*), out[13] the k ranges of G (1: one launch, no combine).  n <= 16; all
- * zero before the first step.  An evaluation runs the forward alone: out[3..10], out[12] and out[13] are zero after it. */
+ * Zn = Nv W + b and for G = dZ W^T (SERT_GEMM_ROUTE_*), out[13] the k ranges of G (1: one launch, no combine), out[14] the
+ * label kind of the upload the step ran on (SERT_LL_WFOLD_LABELS_*: llw_row or llw_row_csr).  n <= 16; all zero before the first
+ * step.  An evaluation runs the forward alone: out[3..10], out[12] and out[13] are zero after it. */
+enum {
+    SERT_LL_WFOLD_LABELS_INT = 0,    /* sert_ll_wfold_upload: llw_row */
+    SERT_LL_WFOLD_LABELS_ROWS = 1    /* sert_ll_wfold_upload_csr: llw_row_csr */
+};
 enum {
     SERT_LL_WFOLD_FORM_NONE = 0,
     SERT_LL_WFOLD_FORM_REG = 1,      /* llw_row<TRAIN, LLW_FORM_REG>: V_e <= 1024, J in four registers per thread */

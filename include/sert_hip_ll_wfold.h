@@ -16,8 +16,14 @@
  *     update         oracle.Adadelta over the single tensor Nv, zero accumulators at creation, lr / rho / eps from the config;
  *                    dense -- a row that no token touched still moves by its L2 term
  * The clips are part of the contract: log clip(P) per token, clip(Q) on the label and both inclusive gradient masks, exactly
- * as in the model's step.  y holds integer labels in [0, V_e), one per instance.  R_w, W and b are never written.  An instance
- * without a new word is legal: it adds to the loss and moves nothing.  A new word twice in one window is two occurrences.
+ * as in the model's step.  y holds integer labels in [0, V_e), one per instance (sert_ll_wfold_upload), or label ROWS
+ * (sert_ll_wfold_upload_csr): instance i's labels are row i of a CSR matrix (M, V_e) over the trained entities, the label
+ * distributions the model learns when it is trained without one-hot classes.  The contract is the same with y the dense
+ * (B, V_e) slice of the rows (LogLinearOracle takes y.ndim == 2):
+ *     loss_i = -sum_l Y_l log clip(Q_l),   dJ_e = Q_e (dQ_e - sum_l Q_l dQ_l),   dQ_l = -g Y_l / clip(Q_l) under the mask
+ * A row may hold 0 .. V_e entries (no entry: loss 0, no gradient), a stored 0 is legal, and the values need not sum to 1.
+ * R_w, W and b are never written.  An instance without a new word is legal: it adds to the loss and moves nothing.  A new
+ * word twice in one window is two occurrences.
  *
  * A token's distribution depends on its word only: L_t = log softmax(row_t W + b).  The rows of the upload's distinct FROZEN
  * words Df cannot change, so they are computed once per upload by the model's own forward kernels (the frozen table,
@@ -34,8 +40,8 @@
  * no state with the model's step schedule.  Later training or destruction of the model does not change it.
  *
  * The design's limits, and out of scope: the step table covers ALL Nw rows, not the batch's distinct new words, and three
- * V_e-wide float tables exist per handle (Ln and S / dZ of Nw rows, DJ of B rows); label rows (CSR); a per-instance cache of
- * the frozen share of J; a wave-per-row form of the row kernel for small V_e; data-parallel handles; a frozen table that
+ * V_e-wide float tables exist per handle (Ln and S / dZ of Nw rows, DJ of B rows); new entity columns in a word fold-in (fold the
+ * entities in first); a per-instance cache of the frozen share of J; a wave-per-row form of the row kernel for small V_e; data-parallel handles; a frozen table that
  * spills or is recomputed.
  */
 #ifndef SERT_HIP_LL_WFOLD_H
@@ -79,6 +85,15 @@ int sert_ll_wfold_destroy(sert_ll_wfold* f);
  * it held.  Batch i is rows [iB, (i + 1)B); a trailing M mod B instances are never visited, as in training.  Replaces an earlier
  * upload; the optimiser state is kept. */
 int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, const float* w, int64_t M);
+/* The same with label ROWS: instance i owns entries indptr[i] .. indptr[i + 1] of (indices, data); indptr (M + 1,) int64,
+ * indices (nnz,) int32 columns in [0, V_e) -- a word fold-in has no new entity column --, data (nnz,) float32.  Refused on the
+ * host with a message, before any launch: indptr[0] != 0, indptr not non-decreasing, more than 2^31 - 1 entries, a column
+ * outside [0, V_e), a row whose columns are not strictly increasing (the message names the row and the column), null arrays,
+ * and everything sert_ll_wfold_upload refuses about x and M.  Everything else -- the frozen table, max_cache_bytes, the index,
+ * "keeps the earlier upload" on every failure -- is sert_ll_wfold_upload's.  An upload of either kind replaces an upload of
+ * either kind and keeps the optimiser state. */
+int sert_ll_wfold_upload_csr(sert_ll_wfold* f, const int32_t* x, const int64_t* indptr, const int32_t* indices,
+                             const float* data, const float* w, int64_t M);
 /* number of complete batches of the upload, floor(M / B); < 0 on a null handle */
 int64_t sert_ll_wfold_num_batches(sert_ll_wfold* f);
 

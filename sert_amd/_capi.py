@@ -102,12 +102,13 @@ EXPORTS_WFOLD = [
 WFOLD_ROWS, WFOLD_M, WFOLD_V = 0, 1, 2
 # ... and include/sert_hip_ll_wfold.h, which sert_hip.h includes as well (folding unseen WORDS into a trained loglinear model)
 EXPORTS_LL_WFOLD = [
-    'sert_ll_wfold_create', 'sert_ll_wfold_destroy', 'sert_ll_wfold_upload', 'sert_ll_wfold_num_batches',
+    'sert_ll_wfold_create', 'sert_ll_wfold_destroy', 'sert_ll_wfold_upload', 'sert_ll_wfold_upload_csr', 'sert_ll_wfold_num_batches',
     'sert_ll_wfold_train_batch', 'sert_ll_wfold_train_batches', 'sert_ll_wfold_eval_batch',
     'sert_ll_wfold_get_rows', 'sert_ll_wfold_set_rows',
 ]
 LL_WFOLD_ROWS, LL_WFOLD_ACCU, LL_WFOLD_DELTA = 0, 1, 2
 LL_WFOLD_FORMS = ('none', 'reg', 'stream')             # SERT_LL_WFOLD_FORM_* (include/sert_hip_debug.h)
+LL_WFOLD_LABELS = ('int', 'rows')                      # SERT_LL_WFOLD_LABELS_* (include/sert_hip_debug.h)
 WFOLD_PROJECT_FORMS = ('none', 'vector', 'scalar')     # SERT_WFOLD_PROJECT_* (include/sert_hip_debug.h)
 FOLDIN_LOSS_FORMS = ('none', 'vector', 'scalar')       # SERT_FOLDIN_LOSS_* (include/sert_hip_debug.h)
 
@@ -285,6 +286,7 @@ def load():
     lib.sert_ll_wfold_create.argtypes = [vp, i32, fp, ctypes.POINTER(SertLlWFoldConfig), ctypes.POINTER(vp)]
     lib.sert_ll_wfold_destroy.argtypes = [vp]
     lib.sert_ll_wfold_upload.argtypes = [vp, fp, fp, fp, i64]
+    lib.sert_ll_wfold_upload_csr.argtypes = [vp, fp, fp, fp, fp, fp, i64]
     lib.sert_ll_wfold_num_batches.argtypes = [vp]
     lib.sert_ll_wfold_num_batches.restype = i64
     lib.sert_ll_wfold_train_batch.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_float)]
@@ -1539,6 +1541,22 @@ class LlWordFoldIn(_FoldHandle):
                                              ctypes.byref(c), ctypes.byref(h)))
         self._h = h
 
+    def upload_csr(self, x, indptr, indices, data, w=None):
+        """Label ROWS: a canonical CSR matrix (M, num_entities) over the trained entities, as the model's own training without
+        one-hot classes learns them (sert_ll_wfold_upload_csr, which validates the rows)."""
+        x, ok = self._x(x)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if not ok or indptr.shape != (x.shape[0] + 1,):
+            raise SertError('x must be (M, window_size) and indptr (M + 1,)')
+        # (what the library cannot see: the arrays must be as long as indptr says before it reads them)
+        if indices.ndim != 1 or data.shape != indices.shape or (indptr.size and indices.size < indptr.max()):
+            raise SertError('indices and data must be (nnz,) with nnz >= max(indptr)')
+        w = self._w(w, x.shape[0])
+        check(self._lib.sert_ll_wfold_upload_csr(self._h, x.ctypes.data, indptr.ctypes.data, _addr(indices), _addr(data),
+                                                 _addr(w), x.shape[0]))
+
     def get_rows(self, which=0):
         """``which``: LL_WFOLD_ROWS (Nv) / LL_WFOLD_ACCU / LL_WFOLD_DELTA (Adadelta's accumulators of Nv)."""
         out = np.empty(self._rows_shape, dtype=np.float32)
@@ -1553,13 +1571,15 @@ class LlWordFoldIn(_FoldHandle):
         """sert_debug_ll_wfold_plan (test hook): what the last step of this handle launched -- 'form' (none / reg / stream: the
         instance of llw_row), 'vec' (16-byte rows), 'train', 'levels' of the batch's reduction and its 'items' per level,
         'segsum' (rows64 / scalar; none without a level), 'gemm_z' / 'gemm_g' (GEMM_ROUTES; gemm_g is 'none' after an
-        evaluation), 'splits' (the k ranges of G).  All zero before the first step."""
+        evaluation), 'splits' (the k ranges of G), 'labels' (int / rows: the upload's label kind, which picks llw_row or
+        llw_row_csr).  All zero before the first step."""
         v = (ctypes.c_int32 * 16)()
         check(self._lib.sert_debug_ll_wfold_plan(self._h, v, 16))
         v = [int(x) for x in v]
         route = lambda code: GEMM_ROUTES[code - 1] if code >= 1 else 'none'
         return {'form': LL_WFOLD_FORMS[v[0]], 'vec': bool(v[1]), 'train': bool(v[2]), 'levels': v[3], 'items': v[4:4 + v[3]],
-                'segsum': WGRAD_FORMS[v[10]], 'gemm_z': route(v[11]), 'gemm_g': route(v[12]), 'splits': v[13]}
+                'segsum': WGRAD_FORMS[v[10]], 'gemm_z': route(v[11]), 'gemm_g': route(v[12]), 'splits': v[13],
+                'labels': LL_WFOLD_LABELS[v[14]]}
 
 
 def bench_gemm(M, N, K, ta=0, tb=0, epi=0, splits=1, iters=20, device=0):

@@ -12,7 +12,11 @@ struct sert_ll_wfold : FoldBase {
     float *Nv = nullptr, *accu = nullptr, *delta = nullptr, *G = nullptr;
     // ---- the upload ----
     int64_t Df = 0;                  // distinct frozen words of the upload (FoldBase: M instances)
-    int32_t* y = nullptr;            // (M)
+    int32_t* y = nullptr;            // (M) integer labels (sert_ll_wfold_upload), or ...
+    int64_t* indptr = nullptr;       // ... label rows (sert_ll_wfold_upload_csr): (M + 1) offsets, ...
+    int32_t* indices = nullptr;      // ... their columns in [0, V_e), strictly increasing per row, ...
+    float* data = nullptr;           // ... and values (nnz each)
+    float* labfix = nullptr;         // label rows: per entry Q_e dQ_e of the step (nnz)
     float* w = nullptr;              // (M)
     int32_t* slot = nullptr;         // (M, n)  >= 0: row of Lf; < 0: new word ~slot
     float* Lf = nullptr;             // (Df, V_e) the frozen table (null when the upload holds no frozen word)
@@ -33,9 +37,10 @@ struct sert_ll_wfold : FoldBase {
 };
 
 static void llw_free_upload(sert_ll_wfold* f) {
-    for (void* p : {(void*)f->y, (void*)f->w, (void*)f->slot, (void*)f->Lf, (void*)f->idx_rows, (void*)f->idx_items, (void*)f->part})
+    for (void* p : {(void*)f->y, (void*)f->indptr, (void*)f->indices, (void*)f->data, (void*)f->labfix, (void*)f->w, (void*)f->slot,
+                    (void*)f->Lf, (void*)f->idx_rows, (void*)f->idx_items, (void*)f->part})
         (void)hipFree(p);
-    f->y = nullptr; f->w = nullptr; f->slot = nullptr; f->Lf = nullptr; f->idx_rows = nullptr; f->idx_items = nullptr;
+    f->y = nullptr; f->indptr = nullptr; f->indices = nullptr; f->data = nullptr; f->labfix = nullptr; f->w = nullptr; f->slot = nullptr; f->Lf = nullptr; f->idx_rows = nullptr; f->idx_items = nullptr;
     f->part = nullptr;
     f->idx_batches.clear();
     f->M = 0; f->Df = 0;
@@ -109,14 +114,20 @@ static void llw_logsoftmax(hipStream_t s, float* Z, int64_t rows, int V) {
     else                   launch((ll_logsoftmax_rows<0>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
 }
 
-int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
-    refresh_gemm_choice();
-    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
-    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+// The labels of an upload, already validated: y (one per instance), or the CSR rows (indptr, indices, data).
+struct LlwLabels {
+    const int32_t* y;
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float* data;
+};
+
+// What an upload of either label form does once its labels are known to be good: the tokens are validated; then the distinct
+// frozen words, the frozen table in slabs, the slots, the inverted index, and the copies of those, of the labels and of w.
+// Nothing of the handle is touched before every host-side check has passed and the new table is allocated.
+static int llw_upload(sert_ll_wfold* f, const int32_t* x, const LlwLabels& lab, const float* w, int64_t M) {
     const int n = f->n, d = f->d, Ve = f->Ve, B = f->cfg.batch_size;
-    // host-side validation: no kernel is launched on bad ids
-    for (int64_t i = 0; i < M; ++i)
-        if (y[i] < 0 || y[i] >= Ve) SERT_FAIL("fold-in label out of range [0, num_entities)");
+    const int64_t nnz = (lab.y || M == 0) ? 0 : lab.indptr[M];      // (M == 0: an empty upload of either form)
     const int64_t ext = (int64_t)f->Vw + f->Nw;
     for (int64_t i = 0; i < M * n; ++i)
         if (x[i] < 0 || x[i] >= ext) SERT_FAIL("token id out of range [0, vocab_size + num_new_words)");
@@ -161,13 +172,25 @@ int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, c
     float* Gs = nullptr;
     std::vector<float> ones;
     auto body = [&]() -> int {
-        SERT_TRY(dmalloc(&f->y, (size_t)M));
+        if (lab.y) {
+            SERT_TRY(dmalloc(&f->y, (size_t)M));
+            SERT_HIP(hipMemcpyAsync(f->y, lab.y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        } else {
+            SERT_TRY(dmalloc(&f->indptr, (size_t)M + 1));
+            SERT_TRY(dmalloc(&f->indices, (size_t)std::max<int64_t>(1, nnz)));
+            SERT_TRY(dmalloc(&f->data, (size_t)std::max<int64_t>(1, nnz)));
+            SERT_TRY(dmalloc(&f->labfix, (size_t)std::max<int64_t>(1, nnz)));
+            SERT_HIP(hipMemcpyAsync(f->indptr, lab.indptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (nnz) {
+                SERT_HIP(hipMemcpyAsync(f->indices, lab.indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                SERT_HIP(hipMemcpyAsync(f->data, lab.data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, s));
+            }
+        }
         SERT_TRY(dmalloc(&f->w, (size_t)M));
         SERT_TRY(dmalloc(&f->slot, (size_t)M * n));
         SERT_TRY(dmalloc(&f->idx_rows, std::max<size_t>(index.rows.size(), 1)));
         SERT_TRY(dmalloc(&f->idx_items, std::max<size_t>(index.items.size(), 1)));
         SERT_TRY(dmalloc(&f->part, std::max<size_t>((size_t)index.max_part_rows * Ve, 4)));
-        SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!w) ones.assign((size_t)M, 1.0f);
         SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
         SERT_HIP(hipMemcpyAsync(f->slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -196,7 +219,7 @@ int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, c
             llw_logsoftmax(s, dst, rows, Ve);
         }
         SERT_HIP(hipGetLastError());
-        SERT_HIP(hipStreamSynchronize(s));     // (x, y, w and the host lists are borrowed for the call only)
+        SERT_HIP(hipStreamSynchronize(s));     // (x, the labels, w and the host lists are borrowed for the call only)
         return 0;
     };
     const int rc = body();
@@ -205,6 +228,50 @@ int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, c
     f->idx_batches.swap(index.batches);
     f->M = M; f->Df = Df;
     return 0;
+}
+
+static int llw_upload_check_sizes(int64_t M) {
+    if (M > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 fold-in instances");
+    return 0;
+}
+
+int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !y))) SERT_FAIL("bad argument");
+    SERT_TRY(llw_upload_check_sizes(M));
+    // host-side validation: no kernel is launched on bad ids
+    for (int64_t i = 0; i < M; ++i)
+        if (y[i] < 0 || y[i] >= f->Ve) SERT_FAIL("fold-in label out of range [0, num_entities)");
+    return llw_upload(f, x, LlwLabels{y, nullptr, nullptr, nullptr}, w, M);
+}
+
+int sert_ll_wfold_upload_csr(sert_ll_wfold* f, const int32_t* x, const int64_t* indptr, const int32_t* indices, const float* data,
+                             const float* w, int64_t M) {
+    refresh_gemm_choice();
+    if (!f || M < 0 || (M > 0 && (!x || !indptr))) SERT_FAIL("bad argument");
+    SERT_TRY(llw_upload_check_sizes(M));
+    // host-side validation, worded as sert_upload_dataset words it for csr_*: no kernel is launched on a bad row
+    if (M > 0) {
+        if (indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
+        for (int64_t r = 0; r < M; ++r)
+            if (indptr[r + 1] < indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
+        const int64_t nnz = indptr[M];
+        if (nnz > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 label entries");
+        if (nnz > 0 && (!indices || !data)) SERT_FAIL("bad argument");
+        // (a word fold-in has no new entity: column V_e is refused)
+        for (int64_t i = 0; i < nnz; ++i)
+            if (indices[i] < 0 || indices[i] >= f->Ve) SERT_FAIL("label column out of range [0, num_entities) in csr_indices");
+        // strictly increasing columns per row: llw_row_csr adds a row's entries to DJ from different threads without atomics
+        for (int64_t r = 0; r < M; ++r)
+            for (int64_t i = indptr[r] + 1; i < indptr[r + 1]; ++i)
+                if (indices[i] <= indices[i - 1]) {
+                    char msg[160];
+                    snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
+                             (long long)r, (int)indices[i]);
+                    SERT_FAIL(msg);
+                }
+    }
+    return llw_upload(f, x, LlwLabels{nullptr, indptr, indices, data}, w, M);
 }
 
 int64_t sert_ll_wfold_num_batches(sert_ll_wfold* f) { return fold_num_batches(f); }
@@ -225,16 +292,25 @@ static int llw_forward(sert_ll_wfold* f, int64_t batch, bool train) {
     const int vec = Ve % 4 == 0 ? 1 : 0;
     const bool reg = Ve <= 1024;
     const int32_t* slot = f->slot + row0 * n;
-    const int32_t* y = f->y + row0;
     const float* w = train ? f->w + row0 : (const float*)nullptr;
     const float inv_batch = 1.0f / (float)B;
     auto go = [&](auto kernel) {
-        launch(kernel, dim3(B), dim3(256), 0, s, (const float*)f->Lf, (const float*)f->Ln, slot, y, w, f->rowloss, f->DJ, n, Ve, vec,
+        launch(kernel, dim3(B), dim3(256), 0, s, (const float*)f->Lf, (const float*)f->Ln, slot, (const int32_t*)(f->y + row0), w,
+               f->rowloss, f->DJ, n, Ve, vec, inv_batch);
+    };
+    // label rows (sert_ll_wfold_upload_csr): the same launch shape, the batch's slice of indptr
+    auto go_csr = [&](auto kernel) {
+        launch(kernel, dim3(B), dim3(256), 0, s, (const float*)f->Lf, (const float*)f->Ln, slot, (const int64_t*)(f->indptr + row0),
+               (const int32_t*)f->indices, (const float*)f->data, w, f->rowloss, train ? f->labfix : (float*)nullptr, f->DJ, n, Ve, vec,
                inv_batch);
     };
-    if (reg) { if (train) go(llw_row<true, LLW_FORM_REG>); else go(llw_row<false, LLW_FORM_REG>); }
+    if (f->indptr) {
+        if (reg) { if (train) go_csr(llw_row_csr<true, LLW_FORM_REG>); else go_csr(llw_row_csr<false, LLW_FORM_REG>); }
+        else { if (train) go_csr(llw_row_csr<true, LLW_FORM_STREAM>); else go_csr(llw_row_csr<false, LLW_FORM_STREAM>); }
+    } else if (reg) { if (train) go(llw_row<true, LLW_FORM_REG>); else go(llw_row<false, LLW_FORM_REG>); }
     else { if (train) go(llw_row<true, LLW_FORM_STREAM>); else go(llw_row<false, LLW_FORM_STREAM>); }
     f->plan[0] = reg ? SERT_LL_WFOLD_FORM_REG : SERT_LL_WFOLD_FORM_STREAM; f->plan[1] = vec; f->plan[2] = train ? 1 : 0;
+    f->plan[14] = f->indptr ? SERT_LL_WFOLD_LABELS_ROWS : SERT_LL_WFOLD_LABELS_INT;
     return 0;
 }
 

@@ -427,14 +427,28 @@ class LogLinearWordFoldIn(_FoldInModel):
     indices in [0, V_e), w (M,) weights or None).  ``new_rows_init`` None: Nw = x.max() + 1 - V_w rows drawn by
     ``new_word_rows``, at the scale bin/train.py drew the trained rows.  The batch size and lambda are the fold-in's own.
     ``max_cache_bytes``: a cap on the frozen table of the upload (0: none).  An instance without a new word is legal: it adds to
-    the loss and moves nothing."""
+    the loss and moves nothing.
+
+    Label rows: y may be a ``scipy.sparse`` matrix (M, V_e) instead -- the label DISTRIBUTIONS the model was trained on
+    without --one_hot_classes, over the trained entities (a word fold-in has no new column).  The matrix is brought to
+    canonical CSR (``tocsr``, ``sum_duplicates``, ``sort_indices``) and uploaded as rows: the new word rows are then fitted
+    with the loss that produced the frozen parameters beside them."""
 
     def __init__(self, R_w, W, b, new_rows_init, training_set, batch_size, regularization_lambda, window_size, device=0,
                  max_cache_bytes=0, _engine=None):
         super(LogLinearWordFoldIn, self).__init__(batch_size)
-        x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
+        x = np.asarray(training_set[0])
         w = training_set[2] if len(training_set) > 2 else None
-        assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        rows = scipy.sparse.issparse(training_set[1])
+        if rows:
+            # label rows: canonical CSR over the V_e trained columns (a copy: the caller's matrix is not modified)
+            y = scipy.sparse.csr_matrix(training_set[1], dtype=np.float32, copy=True)
+            y.sum_duplicates()
+            y.sort_indices()
+            assert x.ndim == 2 and x.shape[1] == window_size and y.shape[0] == x.shape[0]
+        else:
+            y = np.asarray(training_set[1])
+            assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
         vocab_size, word_dim = int(np.shape(R_w)[0]), int(np.shape(R_w)[1])
         if new_rows_init is None:
             if not x.size or int(x.max()) < vocab_size:
@@ -461,9 +475,16 @@ class LogLinearWordFoldIn(_FoldInModel):
         self._attach(_engine, make_engine,
                      lambda engine: _capi.LlWordFoldIn(engine, new_rows_init, batch_size, regularization_lambda,
                                                        max_cache_bytes=max_cache_bytes))
-        self._foldin.upload(x, y, w)
-        logging.info('Folding in %d new words (token ids %d .. %d) on %d instances.', self.num_new_words, vocab_size,
-                     vocab_size + self.num_new_words - 1, self.training_num_instances)
+        if rows:
+            if y.shape[1] != self._foldin.num_entities:
+                raise RuntimeError('label rows must have V_e = %d columns, not %d: a word fold-in has no new entity'
+                                   % (self._foldin.num_entities, y.shape[1]))
+            self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
+        else:
+            self._foldin.upload(x, y, w)
+        logging.info('Folding in %d new words (token ids %d .. %d) on %d instances%s.', self.num_new_words, vocab_size,
+                     vocab_size + self.num_new_words - 1, self.training_num_instances,
+                     ' with %d label entries' % y.nnz if rows else '')
 
     @classmethod
     def from_model(cls, model, new_rows_init, training_set, batch_size, regularization_lambda, max_cache_bytes=0):

@@ -10,6 +10,13 @@ probability 1/2) hold a new word, uniform over the Nw -- the record states the s
 each, then --repeats alternations of --steps steps; a time is a host clock around a call that ends in its one host
 synchronisation.  The one-time upload of the fold-in (sert_ll_wfold_upload: host validation, the inverted index, copies, the
 frozen table -- gather, GEMM and log-softmax over the distinct frozen words) is timed apart, with the size of the table.
+
+    python tools/ll_wfold_bench.py --labels 8 --out profiles/r22_ll_wfold_rows.json
+
+--labels K: label ROWS (sert_ll_wfold_upload_csr) of K distinct trained entries of value 1 / K per instance.  Three steps
+alternate in the one process: the fold-in on the rows, the fold-in of a second handle on the integer labels y (the first
+column of every row), and the step the rows fold-in replaces -- sert_train_batches of the full model with V_w + Nw words
+trained on the same CSR rows.
 """
 import argparse
 import json
@@ -18,6 +25,7 @@ import sys
 import time
 
 import numpy as np
+import scipy.sparse
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -62,6 +70,56 @@ def tokens(rng, Vw, Nw, M, n):
     return X
 
 
+def label_rows(rng, M, Ve, K):
+    """(M, Ve) canonical CSR: K distinct columns per row -- a random start, then V_e // K apart, modulo V_e, ascending -- of
+    value 1 / K."""
+    cols = (rng.randint(0, Ve, M)[:, None] + (Ve // K) * np.arange(K)[None, :]) % Ve
+    cols = np.sort(cols, axis=1).astype(np.int32)
+    assert (np.diff(cols, axis=1) > 0).all()
+    return scipy.sparse.csr_matrix((np.full(M * K, 1.0 / K, np.float32), cols.reshape(-1), np.arange(0, M * K + 1, K)),
+                                   shape=(M, Ve))
+
+
+def rows_setting(name, B, Vw, Ve, Nw, d, n, steps, repeats, num_batches, K):
+    """--labels K: the rows fold-in, the integer fold-in and the full model on the rows, alternating."""
+    rng = np.random.RandomState(0)
+    M = B * num_batches
+    X = tokens(rng, Vw, Nw, M, n)
+    Y = label_rows(rng, M, Ve, K)
+    y = Y.indices[::K].copy()
+    Rw = glorot(rng, (Vw + Nw, d))
+    W = glorot(rng, (d, Ve))
+    full = engine(B, Rw, W, n)
+    full.upload_dataset(C.SPLIT_TRAIN, X.astype(np.uint32), csr=Y, w=np.ones(M, np.float32))
+    frozen = engine(1, Rw[:Vw], W, n, inference_only=1)
+    rows = C.LlWordFoldIn(frozen, Rw[Vw:], B, 0.01)
+    ints = C.LlWordFoldIn(frozen, Rw[Vw:], B, 0.01)
+    frozen.close()
+    t_upload_rows, _ = timed(lambda: rows.upload_csr(X, Y.indptr, Y.indices, Y.data, None))
+    t_upload_int, _ = timed(lambda: ints.upload(X, y, None))
+    order = np.arange(steps, dtype=np.int64) % num_batches
+    for h in (rows, ints, full):
+        h.train_batches(order)
+    t_rows, t_int, t_full = [], [], []
+    for _ in range(repeats):
+        t_rows.append(timed(lambda: rows.train_batches(order))[0] / steps)
+        t_int.append(timed(lambda: ints.train_batches(order))[0] / steps)
+        t_full.append(timed(lambda: full.train_batches(order))[0] / steps)
+    plan_rows, plan_int = rows.plan(), ints.plan()
+    for h in (full, rows, ints):
+        h.close()
+    med = lambda t: 1e3 * float(np.median(t))
+    rec = dict(setting=name, B=B, V_w=Vw, V_e=Ve, Nw=Nw, d=d, window=n, steps=steps, instances=M, labels_per_row=K,
+               label_entries=int(Y.nnz), new_position_share=float((X >= Vw).mean()), plan_rows=plan_rows, plan_int=plan_int,
+               rows_step_ms=[1e3 * t for t in t_rows], int_step_ms=[1e3 * t for t in t_int],
+               full_rows_step_ms=[1e3 * t for t in t_full], rows_step_ms_median=med(t_rows), int_step_ms_median=med(t_int),
+               full_rows_step_ms_median=med(t_full), upload_rows_ms=1e3 * t_upload_rows, upload_int_ms=1e3 * t_upload_int)
+    rec['rows_over_int_median'] = rec['rows_step_ms_median'] / rec['int_step_ms_median']
+    rec['speedup_over_full_median'] = rec['full_rows_step_ms_median'] / rec['rows_step_ms_median']
+    rec['rows_faster_than_full_in_every_alternation'] = bool(all(a < b for a, b in zip(t_rows, t_full)))
+    return rec
+
+
 def step_setting(name, B, Vw, Ve, Nw, d, n, steps, repeats, num_batches):
     rng = np.random.RandomState(0)
     M = B * num_batches
@@ -103,12 +161,18 @@ def main(argv=None):
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--num_batches', type=int, default=8)
     ap.add_argument('--settings', nargs='+', default=[s[0] for s in SETTINGS])
+    ap.add_argument('--labels', type=int, default=0,
+                    help='K > 0: label rows of K trained entries of value 1 / K (sert_ll_wfold_upload_csr) beside the integer '
+                         'upload and the full model on the same rows; 0: integer labels against the full model')
     args = ap.parse_args(argv)
     C.require_gpu()
     out = dict(device=C.device_info(0), steps=[])
     for s in SETTINGS:
         if s[0] in args.settings:
-            rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches)
+            if args.labels > 0:
+                rec = rows_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches, K=args.labels)
+            else:
+                rec = step_setting(*s, steps=args.steps, repeats=args.repeats, num_batches=args.num_batches)
             print(json.dumps(rec))
             out['steps'].append(rec)
             with open(args.out, 'w') as f:
