@@ -1179,7 +1179,7 @@ class RetrievalEval(object):
 
 class _FoldHandle(object):
     """What the owners of the four fold-in handles share: the handle ``_h``, the prefix of its library functions, the
-    (x, y, w) upload validation, the batch calls and the destruction."""
+    (x, y, w) upload validation, the batch calls and the destruction (_NceFoldHandle, _LlFoldHandle: what two of them share)."""
 
     _prefix = None          # 'sert_foldin_', 'sert_wfold_', 'sert_ll_foldin_', 'sert_ll_wfold_'
 
@@ -1294,6 +1294,37 @@ class _NceFoldHandle(_FoldHandle):
 
     def get_eval_draws(self):
         return int(self._fn('get_eval_draws')(self._h))
+
+
+class _LlFoldHandle(_FoldHandle):
+    """The two handles of a loglinear model on top of it: the Adadelta config (sert_ll_foldin_config and sert_ll_wfold_config
+    have the same fields) and the upload of label rows."""
+
+    _config = None          # SertLlFoldInConfig, SertLlWFoldConfig
+
+    def _fill_config(self, batch_size, lambda_, lr, rho, eps, max_cache_bytes):
+        c = self._config()
+        c.struct_size = ctypes.sizeof(self._config)
+        c.batch_size, c.lambda_ = int(batch_size), float(lambda_)
+        c.lr, c.rho, c.eps, c.max_cache_bytes = float(lr), float(rho), float(eps), int(max_cache_bytes)
+        self.cfg = c
+        return c
+
+    def upload_csr(self, x, indptr, indices, data, w=None):
+        """Label ROWS: a canonical CSR matrix whose column e < num_entities is trained entity e.  LlFoldIn: (M, num_entities +
+        num_new), a trained column is a label only and column num_entities + j is new entity j; LlWordFoldIn: (M,
+        num_entities), as the model's own training without one-hot classes learns them.  The library validates the rows."""
+        x, ok = self._x(x)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if not ok or indptr.shape != (x.shape[0] + 1,):
+            raise SertError('x must be (M, window_size) and indptr (M + 1,)')
+        # (what the library cannot see: the arrays must be as long as indptr says before it reads them)
+        if indices.ndim != 1 or data.shape != indices.shape or (indptr.size and indices.size < indptr.max()):
+            raise SertError('indices and data must be (nnz,) with nnz >= max(indptr)')
+        w = self._w(w, x.shape[0])
+        check(self._fn('upload_csr')(self._h, x.ctypes.data, indptr.ctypes.data, _addr(indices), _addr(data), _addr(w), x.shape[0]))
 
 
 def _refresh_ids(refresh_ids):
@@ -1424,7 +1455,7 @@ def debug_wfold_index(tok, num_words, batch=0):
             'rows': rows[:nr.value].copy(), 'items': items[:ni.value].copy()}
 
 
-class LlFoldIn(_FoldHandle):
+class LlFoldIn(_LlFoldHandle):
     """Owner of one sert_ll_foldin handle (include/sert_hip_ll_foldin.h): ``num_new`` columns of W and entries of b learnt
     on top of the frozen parameters of ``engine`` (a loglinear Engine), which are copied at construction -- the engine may
     train on or be closed afterwards.  ``init_W``: (word_dim, num_new); ``init_b``: (num_new,) or None (zeros).
@@ -1434,7 +1465,7 @@ class LlFoldIn(_FoldHandle):
     order given: integer labels are slots, the tensors are (word_dim, num_slots) / (num_slots,) in slot order, and ``init_W``
     may be None or empty (nothing is new).  Label rows keep the public columns [0, num_entities + num_new)."""
 
-    _prefix = 'sert_ll_foldin_'
+    _prefix, _config = 'sert_ll_foldin_', SertLlFoldInConfig
 
     def __init__(self, engine, init_W, init_b, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0,
                  refresh_ids=None):
@@ -1450,11 +1481,7 @@ class LlFoldIn(_FoldHandle):
             bn = np.ascontiguousarray(init_b, dtype=np.float32)
             if bn.shape != (Wn.shape[1],):
                 raise SertError('init_b must be (num_new,)')
-        c = SertLlFoldInConfig()
-        c.struct_size = ctypes.sizeof(SertLlFoldInConfig)
-        c.batch_size, c.lambda_ = int(batch_size), float(lambda_)
-        c.lr, c.rho, c.eps, c.max_cache_bytes = float(lr), float(rho), float(eps), int(max_cache_bytes)
-        self.cfg = c
+        c = self._fill_config(batch_size, lambda_, lr, rho, eps, max_cache_bytes)
         self.word_dim, self.num_new = int(Wn.shape[0]), int(Wn.shape[1])
         self.num_entities = int(engine.cfg.num_entities)
         self.window_size = int(engine.cfg.window_size)
@@ -1471,22 +1498,6 @@ class LlFoldIn(_FoldHandle):
                                                           _addr(bn) if Wn.size else None, ctypes.byref(c), ctypes.byref(h)))
         self.num_slots = self.num_refresh + self.num_new        # the trainable columns
         self._h = h
-
-    def upload_csr(self, x, indptr, indices, data, w=None):
-        """Label ROWS: a canonical CSR matrix (M, num_entities + num_new) -- column e < num_entities is trained entity e (a
-        label only), column num_entities + j new entity j (sert_ll_foldin_upload_csr, which validates the rows)."""
-        x, ok = self._x(x)
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(indices, dtype=np.int32)
-        data = np.ascontiguousarray(data, dtype=np.float32)
-        if not ok or indptr.shape != (x.shape[0] + 1,):
-            raise SertError('x must be (M, window_size) and indptr (M + 1,)')
-        # (what the library cannot see: the arrays must be as long as indptr says before it reads them)
-        if indices.ndim != 1 or data.shape != indices.shape or (indptr.size and indices.size < indptr.max()):
-            raise SertError('indices and data must be (nnz,) with nnz >= max(indptr)')
-        w = self._w(w, x.shape[0])
-        check(self._lib.sert_ll_foldin_upload_csr(self._h, x.ctypes.data, indptr.ctypes.data, _addr(indices), _addr(data),
-                                                  _addr(w), x.shape[0]))
 
     def _shape(self, which):
         if which not in (LL_FOLDIN_W, LL_FOLDIN_B, LL_FOLDIN_ACCU_W, LL_FOLDIN_ACCU_B, LL_FOLDIN_DELTA_W, LL_FOLDIN_DELTA_B):
@@ -1513,12 +1524,12 @@ class LlFoldIn(_FoldHandle):
         return int(vf.value), int(nt.value), out
 
 
-class LlWordFoldIn(_FoldHandle):
+class LlWordFoldIn(_LlFoldHandle):
     """Owner of one sert_ll_wfold handle (include/sert_hip_ll_wfold.h): ``num_new_words`` word rows learnt on top of the frozen
     parameters of ``engine`` (a loglinear Engine), which are copied at construction -- the engine may train on or be closed
     afterwards.  New word v is token id ``vocab_size + v``; labels are trained entities."""
 
-    _prefix = 'sert_ll_wfold_'
+    _prefix, _config = 'sert_ll_wfold_', SertLlWFoldConfig
 
     def __init__(self, engine, new_rows_init, batch_size, lambda_, lr=1.0, rho=0.95, eps=1e-6, max_cache_bytes=0):
         self._lib = load()
@@ -1526,11 +1537,7 @@ class LlWordFoldIn(_FoldHandle):
         rows = np.ascontiguousarray(new_rows_init, dtype=np.float32)
         if rows.ndim != 2 or rows.shape[1] != engine.cfg.word_dim:
             raise SertError('new_rows_init must be (num_new_words, word_dim)')
-        c = SertLlWFoldConfig()
-        c.struct_size = ctypes.sizeof(SertLlWFoldConfig)
-        c.batch_size, c.lambda_ = int(batch_size), float(lambda_)
-        c.lr, c.rho, c.eps, c.max_cache_bytes = float(lr), float(rho), float(eps), int(max_cache_bytes)
-        self.cfg = c
+        c = self._fill_config(batch_size, lambda_, lr, rho, eps, max_cache_bytes)
         self.num_new_words, self.word_dim = int(rows.shape[0]), int(rows.shape[1])
         self._rows_shape = (self.num_new_words, self.word_dim)
         self.vocab_size = int(engine.cfg.vocab_size)
@@ -1540,22 +1547,6 @@ class LlWordFoldIn(_FoldHandle):
         check(self._lib.sert_ll_wfold_create(engine._h, self.num_new_words, rows.ctypes.data if rows.size else None,
                                              ctypes.byref(c), ctypes.byref(h)))
         self._h = h
-
-    def upload_csr(self, x, indptr, indices, data, w=None):
-        """Label ROWS: a canonical CSR matrix (M, num_entities) over the trained entities, as the model's own training without
-        one-hot classes learns them (sert_ll_wfold_upload_csr, which validates the rows)."""
-        x, ok = self._x(x)
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(indices, dtype=np.int32)
-        data = np.ascontiguousarray(data, dtype=np.float32)
-        if not ok or indptr.shape != (x.shape[0] + 1,):
-            raise SertError('x must be (M, window_size) and indptr (M + 1,)')
-        # (what the library cannot see: the arrays must be as long as indptr says before it reads them)
-        if indices.ndim != 1 or data.shape != indices.shape or (indptr.size and indices.size < indptr.max()):
-            raise SertError('indices and data must be (nnz,) with nnz >= max(indptr)')
-        w = self._w(w, x.shape[0])
-        check(self._lib.sert_ll_wfold_upload_csr(self._h, x.ctypes.data, indptr.ctypes.data, _addr(indices), _addr(data),
-                                                 _addr(w), x.shape[0]))
 
     def get_rows(self, which=0):
         """``which``: LL_WFOLD_ROWS (Nv) / LL_WFOLD_ACCU / LL_WFOLD_DELTA (Adadelta's accumulators of Nv)."""

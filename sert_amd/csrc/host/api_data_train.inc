@@ -1,5 +1,31 @@
 // Part of sert_hip.hip (one translation unit; included there, inside its namespace / extern "C" block): C ABI: sert_upload_dataset, training, evaluation, prediction.
 
+// Label rows as a CSR matrix (rows, cols), validated on the host before any kernel indexes with them: indptr starts at 0 and
+// never decreases, at most max_nnz entries, every column in [0, cols) (col_error: the caller's wording of that range) and
+// strictly increasing within a row -- the loss kernels add a row's label entries from different threads without atomics, two
+// entries of one column would race, and the fold-in's row kernel finds a column by bisection.  The one statement behind
+// sert_upload_dataset, sert_ll_foldin_upload_csr and sert_ll_wfold_upload_csr.
+static int check_csr_rows(const int64_t* indptr, const int32_t* indices, const float* data, int64_t rows, int64_t cols,
+                          const char* col_error, int64_t max_nnz) {
+    if (indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
+    for (int64_t r = 0; r < rows; ++r)
+        if (indptr[r + 1] < indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
+    const int64_t nnz = indptr[rows];
+    if (nnz > max_nnz) SERT_FAIL("more than 2^31 - 1 label entries");
+    if (nnz > 0 && (!indices || !data)) SERT_FAIL("bad argument");
+    for (int64_t i = 0; i < nnz; ++i)
+        if (indices[i] < 0 || indices[i] >= cols) SERT_FAIL(col_error);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t i = indptr[r] + 1; i < indptr[r + 1]; ++i)
+            if (indices[i] <= indices[i - 1]) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
+                         (long long)r, (int)indices[i]);
+                SERT_FAIL(msg);
+            }
+    return 0;
+}
+
 int sert_upload_dataset(sert_model* m, int split, const void* x, const int32_t* y_int,
                         const int64_t* csr_indptr, const int32_t* csr_indices,
                         const float* csr_data, const float* w, int64_t N) {
@@ -31,22 +57,9 @@ int sert_upload_dataset(sert_model* m, int split, const void* x, const int32_t* 
             for (int64_t i = 0; i < N; ++i)
                 if (y_int[i] < 0 || y_int[i] >= Ve) SERT_FAIL("label out of range [0, num_entities) in y");
         } else {
-            if (csr_indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
-            for (int64_t r = 0; r < N; ++r)
-                if (csr_indptr[r + 1] < csr_indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
-            const int64_t nnz = csr_indptr[N];
-            for (int64_t i = 0; i < nnz; ++i)
-                if (csr_indices[i] < 0 || csr_indices[i] >= Ve) SERT_FAIL("label column out of range [0, num_entities) in csr_indices");
-            // strictly increasing columns per row (include/sert_hip.h): the loss kernels add a row's label entries to dJ from
-            // different threads without atomics -- two entries of one column would race
-            for (int64_t r = 0; r < N; ++r)
-                for (int64_t i = csr_indptr[r] + 1; i < csr_indptr[r + 1]; ++i)
-                    if (csr_indices[i] <= csr_indices[i - 1]) {
-                        char msg[160];
-                        snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
-                                 (long long)r, (int)csr_indices[i]);
-                        SERT_FAIL(msg);
-                    }
+            // (the model's split states no limit on its label entries: none is checked here, as before)
+            SERT_TRY(check_csr_rows(csr_indptr, csr_indices, csr_data, N, Ve, "label column out of range [0, num_entities) in csr_indices",
+                                    INT64_MAX));
         }
     }
     DataSplit& d = m->split[split];
@@ -503,10 +516,7 @@ int sert_predict_tokens(sert_model* m, const void* ids, int64_t rows, float* out
     SERT_HIP(hipMemcpyAsync(m->pred_ids, ids, (size_t)toks * c.id_bytes, hipMemcpyHostToDevice, m->stream));
     SERT_ID_DISPATCH(c.id_bytes, {
         const IdT* X = (const IdT*)m->pred_ids;
-        if (d % 4 == 0)
-            launch((ll_gather_rows<IdT, 4>), dim3(grid_for(toks * d / 4, 256, 1 << 20)), dim3(256), 0, m->stream, X, m->rw, dG, toks, d);
-        else
-            launch((ll_gather_rows<IdT, 1>), dim3(grid_for(toks * d, 256, 1 << 20)), dim3(256), 0, m->stream, X, m->rw, dG, toks, d);
+        gather_rows(m->stream, X, m->rw, dG, toks, d);
     });
     launch_gemm<false, false, EPI_BIAS>(m->stream, dG, m->W, dZ, m->b, (int)toks, V, d, d, V, V);
     launch(ll_softmax_rows, dim3(cdiv(toks, 4)), dim3(256), 0, m->stream, dZ, toks, V);

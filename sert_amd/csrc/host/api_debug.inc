@@ -432,9 +432,7 @@ int sert_debug_gemm_route(int form, int ta, int tb, int M, int N, int K, int spl
         if (splits <= 1) { splits = 1; kper = K; }      // (launch_gemm: one k range is no split)
     }
     const int lda = ta ? M : K, ldb = tb ? K : N;
-    if (gemm_takes_x3(ta != 0, tb != 0, EPI_STORE, csb, false, A, B, M, N, K, lda, ldb, splits, kper))
-        return ta ? x3_ta_route(M, N) : x3_route(tb != 0, A, B, M, N, K, lda, ldb, splits);
-    return gemm_f32_route(ta != 0, tb != 0, EPI_STORE, csb, A, B, M, N, K, lda, ldb, splits, kper);
+    return gemm_route(ta != 0, tb != 0, EPI_STORE, csb, false, A, B, M, N, K, lda, ldb, splits, kper);
 }
 
 // C = epi(op(A).op(B)) for host arrays, through launch_gemm -- i.e. through whichever kernel a shape is routed to in a

@@ -2,26 +2,19 @@
 // into a trained loglinear model (include/sert_hip_ll_foldin.h: sert_ll_foldin_*; kernels_ll_foldin.h).  Like sert_foldin the
 // handle copies the model's parameters when it is created and runs on a stream of its own.
 
-struct sert_ll_foldin : FoldBase {
+struct sert_ll_foldin : FoldLl {
     sert_ll_foldin_config cfg;
-    int Vw = 0, Ve = 0, N = 0, d = 0, n = 0;     // Ve: the FROZEN columns V_f; N: the trainable ones Nt (the kernels' V_e and N)
+    int N = 0;                           // FoldLl::Ve: the FROZEN columns V_f; N: the trainable ones Nt (the kernels' V_e and N)
     // the public columns: Ve_pub trained entities of the model, of which R are refreshed (slots [0, R) of the N trainable
     // columns), and N - R new ones; internal_of (Ve_pub + N - R): public column -> internal column (ll_label_remap.h)
     int Ve_pub = 0, R = 0;
     std::vector<int32_t> internal_of;
-    // the frozen snapshot (W (d, Ve), b (Ve): null when every trained column is refreshed)
-    float *rw = nullptr, *W = nullptr, *b = nullptr;
+    // (the frozen snapshot's W (d, Ve) and b (Ve) are null when every trained column is refreshed)
     // the new columns Wn (d, N) and biases bn (N), Adadelta's accumulators, the gradients
     float *Wn = nullptr, *bn = nullptr, *accu_w = nullptr, *accu_b = nullptr, *delta_w = nullptr, *delta_b = nullptr;
     float *g_w = nullptr, *g_b = nullptr;
-    // ---- the upload ----
-    int64_t D = 0;                       // distinct words of the upload (FoldBase: M instances)
-    int32_t* y = nullptr;                // one label per instance (sert_ll_foldin_upload), or ...
-    int64_t* indptr = nullptr;           // ... label rows (sert_ll_foldin_upload_csr): (M + 1) offsets, ...
-    int32_t* indices = nullptr;          // ... (nnz) columns in [0, V_e + N), strictly increasing per row, ...
-    float* data = nullptr;               // ... (nnz) values
-    float* labfix = nullptr;             // label rows: per entry Q_e dQ_e of the step (nnz)
-    float* w = nullptr;
+    // ---- the upload (FoldBase: M instances; FoldLl: the labels, INTERNAL columns in [0, V_f + Nt), and w) ----
+    int64_t D = 0;                       // distinct words of the upload
     float* G = nullptr;                  // (D, d) = R_w[distinct words]
     float* Zold = nullptr;               // (D, V_e) the logit cache
     float2* stat = nullptr;              // (D) (max, sum exp) of a cache row
@@ -33,16 +26,15 @@ struct sert_ll_foldin : FoldBase {
     std::vector<int32_t> U;                  // a batch's number of distinct words
     // per-step scratch, sized by the upload's largest U
     float *Gb = nullptr, *Zn = nullptr, *lse = nullptr, *dZ = nullptr, *dZu = nullptr, *part = nullptr;
-    float* rowloss = nullptr;            // (B)
-    float* red_sq = nullptr;             // [kOptBlocks] sums of squares of Wn, then [kOptBlocks] of bn (not in the loss)
+    // (FoldLl::red_sq: [kOptBlocks] sums of squares of Wn, then [kOptBlocks] of bn, which are not in the loss)
 };
 
 static void llf_free_upload(sert_ll_foldin* f) {
-    for (void* p : {(void*)f->y, (void*)f->indptr, (void*)f->indices, (void*)f->data, (void*)f->labfix, (void*)f->w, (void*)f->G,
-                    (void*)f->Zold, (void*)f->stat, (void*)f->Lb, (void*)f->tok, (void*)f->wptr, (void*)f->wpos, (void*)f->Gb, (void*)f->Zn, (void*)f->lse, (void*)f->dZ, (void*)f->dZu, (void*)f->part})
+    fold_free_labels(f);
+    for (void* p : {(void*)f->G, (void*)f->Zold, (void*)f->stat, (void*)f->Lb, (void*)f->tok, (void*)f->wptr, (void*)f->wpos, (void*)f->Gb,
+                    (void*)f->Zn, (void*)f->lse, (void*)f->dZ, (void*)f->dZu, (void*)f->part})
         (void)hipFree(p);
-    f->y = nullptr; f->indptr = nullptr; f->indices = nullptr; f->data = nullptr; f->labfix = nullptr;
-    f->w = nullptr; f->G = nullptr; f->Zold = nullptr; f->stat = nullptr; f->Lb = nullptr; f->tok = nullptr;
+    f->G = nullptr; f->Zold = nullptr; f->stat = nullptr; f->Lb = nullptr; f->tok = nullptr;
     f->wptr = nullptr; f->wpos = nullptr; f->Gb = nullptr; f->Zn = nullptr; f->lse = nullptr; f->dZ = nullptr; f->dZu = nullptr;
     f->part = nullptr;
     f->lb_off.clear(); f->ptr_off.clear(); f->U.clear();
@@ -177,33 +169,18 @@ static void llf_dw_splits(const sert_ll_foldin* f, int64_t rows, int* splits, in
     *splits = sp; *kper = kp;
 }
 
-// The labels of an upload, already validated: y (one per instance), or the CSR rows (indptr, indices, data).
-struct LlfLabels {
-    const int32_t* y;
-    const int64_t* indptr;
-    const int32_t* indices;
-    const float* data;
-};
-
 // What an upload of either label form does once its labels are known to be good: the tokens are validated; then the distinct
 // words, the per-batch word lists (Lb, tok, wptr / wpos), the logit cache with llf_row_stat, and the copies of those lists, of
 // the labels and of w.  Nothing of the handle is touched before every host-side check has passed.
-static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab, const float* w, int64_t M) {
+static int llf_upload(sert_ll_foldin* f, const int32_t* x, const FoldLabels& lab, const float* w, int64_t M) {
     const int n = f->n, d = f->d, Ve = f->Ve, N = f->N, B = f->cfg.batch_size;
-    const int64_t nnz = (lab.y || M == 0) ? 0 : lab.indptr[M];      // (M == 0: an empty upload of either form)
     for (int64_t i = 0; i < M * n; ++i)
         if (x[i] < 0 || x[i] >= f->Vw) SERT_FAIL("token id out of range [0, vocab_size)");
     // ---- the distinct words D of x (sorted) and the row of the cache of every token ----
-    std::vector<int32_t> row_of((size_t)f->Vw, -1), words;
-    for (int64_t i = 0; i < M * n; ++i) row_of[(size_t)x[i]] = 0;
-    for (int32_t v = 0; v < f->Vw; ++v)
-        if (row_of[(size_t)v] == 0) { row_of[(size_t)v] = (int32_t)words.size(); words.push_back(v); }
-    const int64_t D = (int64_t)words.size();
-    const unsigned long long need = (unsigned long long)D * (unsigned long long)Ve * sizeof(float);
-    if (f->cfg.max_cache_bytes != 0 && need > f->cfg.max_cache_bytes)
-        SERT_FAIL("the logit cache of this upload needs " + std::to_string(need) + " bytes (" + std::to_string(D) +
-                  " distinct words x " + std::to_string(Ve) + " entities), more than max_cache_bytes = " +
-                  std::to_string((unsigned long long)f->cfg.max_cache_bytes));
+    FoldWordTable cache;
+    SERT_TRY(fold_word_table(x, M * n, f->Vw, Ve, f->cfg.max_cache_bytes, "logit cache", "distinct words", &cache));
+    const std::vector<int32_t>& row_of = cache.row_of;
+    const int64_t D = (int64_t)cache.words.size();
     // ---- per batch: the sorted list of its distinct words, a slot per token, the token positions per word ----
     const int64_t nb = M / B, bt = (int64_t)B * n;
     std::vector<int32_t> Lb, tok((size_t)(nb * bt)), wptr, wpos((size_t)(nb * bt)), local((size_t)D, -1), fill;
@@ -238,28 +215,11 @@ static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab,
     llf_free_upload(f);
     if (M == 0) return 0;
     uint32_t* dwords = nullptr;
+    std::vector<float> ones;
     auto body = [&]() -> int {
         // (V_f == 0, every trained column refreshed: no cache -- Zold stays null and no kernel reads a column of it)
-        if (need != 0 && hipMalloc((void**)&f->Zold, (size_t)need) != hipSuccess) {
-            (void)hipGetLastError();
-            f->Zold = nullptr;
-            SERT_FAIL("the logit cache of this upload needs " + std::to_string(need) + " bytes, which cannot be allocated");
-        }
-        if (lab.y) {
-            SERT_TRY(dmalloc(&f->y, (size_t)M));
-            SERT_HIP(hipMemcpyAsync(f->y, lab.y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        } else {
-            SERT_TRY(dmalloc(&f->indptr, (size_t)M + 1));
-            SERT_TRY(dmalloc(&f->indices, (size_t)std::max<int64_t>(1, nnz)));
-            SERT_TRY(dmalloc(&f->data, (size_t)std::max<int64_t>(1, nnz)));
-            SERT_TRY(dmalloc(&f->labfix, (size_t)std::max<int64_t>(1, nnz)));
-            SERT_HIP(hipMemcpyAsync(f->indptr, lab.indptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            if (nnz) {
-                SERT_HIP(hipMemcpyAsync(f->indices, lab.indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                SERT_HIP(hipMemcpyAsync(f->data, lab.data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, s));
-            }
-        }
-        SERT_TRY(dmalloc(&f->w, (size_t)M));
+        SERT_TRY(fold_alloc_table(cache, &f->Zold));
+        SERT_TRY(fold_upload_labels(f, lab, w, M, ones));
         SERT_TRY(dmalloc(&f->G, (size_t)D * d));
         SERT_TRY(dmalloc(&f->stat, (size_t)D));
         SERT_TRY(dmalloc(&f->Lb, std::max<size_t>(Lb.size(), 1)));
@@ -275,21 +235,14 @@ static int llf_upload(sert_ll_foldin* f, const int32_t* x, const LlfLabels& lab,
         SERT_TRY(dmalloc(&f->dZ, (size_t)bt * N));
         SERT_TRY(dmalloc(&f->dZu, (size_t)Umax * N));
         SERT_TRY(dmalloc(&f->part, (size_t)max_splits * ((size_t)d * N + N)));
-        const std::vector<float> ones(w ? 0 : (size_t)M, 1.0f);
-        SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
-        SERT_HIP(hipMemcpyAsync(dwords, words.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SERT_HIP(hipMemcpyAsync(dwords, cache.words.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!Lb.empty()) SERT_HIP(hipMemcpyAsync(f->Lb, Lb.data(), Lb.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!tok.empty()) SERT_HIP(hipMemcpyAsync(f->tok, tok.data(), tok.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!wptr.empty()) SERT_HIP(hipMemcpyAsync(f->wptr, wptr.data(), wptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!wpos.empty()) SERT_HIP(hipMemcpyAsync(f->wpos, wpos.data(), wpos.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         // G = R_w[D]; Zold = G W + b, a slab of rows at a time so that no launch sees 2 GiB of either operand: the slabs'
         // offsets into the cache are 64 bits wide
-        if (d % 4 == 0)
-            launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(D * d / 4, 256, 1 << 20)), dim3(256), 0, s, (const uint32_t*)dwords,
-                   (const float*)f->rw, f->G, D, d);
-        else
-            launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(D * d, 256, 1 << 20)), dim3(256), 0, s, (const uint32_t*)dwords,
-                   (const float*)f->rw, f->G, D, d);
+        gather_rows(s, (const uint32_t*)dwords, f->rw, f->G, D, d);
         const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(D, (((int64_t)1 << 29) - 1) / std::max(Ve, d)));
         for (int64_t r0 = 0; Ve > 0 && r0 < D; r0 += slab) {
             const int rows = (int)std::min<int64_t>(slab, D - r0);
@@ -324,7 +277,7 @@ int sert_ll_foldin_upload(sert_ll_foldin* f, const int32_t* x, const int32_t* y,
             SERT_FAIL(f->R > 0 ? "fold-in label out of range [0, num_refresh + num_new): y is a slot"
                                : "fold-in label out of range [0, num_new)");
     // (a slot is the label's trainable column as the step counts it, behind the V_f frozen ones: nothing to remap)
-    return llf_upload(f, x, LlfLabels{y, nullptr, nullptr, nullptr}, w, M);
+    return llf_upload(f, x, FoldLabels{y, nullptr, nullptr, nullptr}, w, M);
 }
 
 int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t* indptr, const int32_t* indices,
@@ -332,37 +285,19 @@ int sert_ll_foldin_upload_csr(sert_ll_foldin* f, const int32_t* x, const int64_t
     refresh_gemm_choice();
     if (!f || M < 0 || (M > 0 && (!x || !indptr))) SERT_FAIL("bad argument");
     SERT_TRY(llf_upload_check_sizes(f, M));
-    // host-side validation, worded as sert_upload_dataset words it for csr_*: no kernel is launched on a bad row
-    if (M > 0) {
-        const int64_t cols = (int64_t)f->internal_of.size();      // the PUBLIC columns V_e + num_new
-        if (indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
-        for (int64_t r = 0; r < M; ++r)
-            if (indptr[r + 1] < indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
-        const int64_t nnz = indptr[M];
-        if (nnz > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 label entries");
-        if (nnz > 0 && (!indices || !data)) SERT_FAIL("bad argument");
-        for (int64_t i = 0; i < nnz; ++i)
-            if (indices[i] < 0 || indices[i] >= cols) SERT_FAIL("label column out of range [0, V_e + num_new) in csr_indices");
-        // strictly increasing columns per row: llf_row_csr looks a new column's entry up by bisection and adds a row's entries
-        // from different threads without atomics
-        for (int64_t r = 0; r < M; ++r)
-            for (int64_t i = indptr[r] + 1; i < indptr[r + 1]; ++i)
-                if (indices[i] <= indices[i - 1]) {
-                    char msg[160];
-                    snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
-                             (long long)r, (int)indices[i]);
-                    SERT_FAIL(msg);
-                }
-    }
+    // host-side validation over the PUBLIC columns V_e + num_new: no kernel is launched on a bad row
+    if (M > 0)
+        SERT_TRY(check_csr_rows(indptr, indices, data, M, (int64_t)f->internal_of.size(),
+                                "label column out of range [0, V_e + num_new) in csr_indices", INT32_MAX));
     if (f->R > 0 && M > 0 && indptr[M] > 0) {
         // public -> internal columns: a refreshed column leaves the frozen ones for the trainable tail, which llf_row_csr
         // finds by bisection at V_f, so every row is brought back to strictly increasing columns (ll_label_remap.h)
         std::vector<int32_t> cols((size_t)indptr[M]);
         std::vector<float> vals((size_t)indptr[M]);
         ll_remap_csr(indptr, indices, data, M, f->internal_of, f->Ve, cols.data(), vals.data());
-        return llf_upload(f, x, LlfLabels{nullptr, indptr, cols.data(), vals.data()}, w, M);
+        return llf_upload(f, x, FoldLabels{nullptr, indptr, cols.data(), vals.data()}, w, M);
     }
-    return llf_upload(f, x, LlfLabels{nullptr, indptr, indices, data}, w, M);
+    return llf_upload(f, x, FoldLabels{nullptr, indptr, indices, data}, w, M);
 }
 
 int64_t sert_ll_foldin_num_batches(sert_ll_foldin* f) { return fold_num_batches(f); }
@@ -379,12 +314,7 @@ static int llf_forward(sert_ll_foldin* f, int64_t batch, bool train) {
     const int32_t* Lb = f->Lb + f->lb_off[(size_t)batch];
     const int32_t* tok = f->tok + (size_t)batch * B * n;
     // Gb = G[L_b]; Zn = Gb Wn + bn
-    if (d % 4 == 0)
-        launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for((int64_t)U * d / 4, 256, 1 << 20)), dim3(256), 0, s,
-               reinterpret_cast<const uint32_t*>(Lb), (const float*)f->G, f->Gb, (int64_t)U, d);
-    else
-        launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for((int64_t)U * d, 256, 1 << 20)), dim3(256), 0, s,
-               reinterpret_cast<const uint32_t*>(Lb), (const float*)f->G, f->Gb, (int64_t)U, d);
+    gather_rows(s, reinterpret_cast<const uint32_t*>(Lb), f->G, f->Gb, U, d);
     launch_gemm<false, false, EPI_BIAS>(s, f->Gb, f->Wn, f->Zn, f->bn, U, N, d, d, N, N);
     launch(llf_lse, dim3(cdiv(U, 4)), dim3(256), 0, s, f->Zn, (const float2*)f->stat, Lb, f->lse, U, N);
     const size_t row0 = (size_t)batch * B;
@@ -431,18 +361,10 @@ static int llf_step_async(sert_ll_foldin* f, int64_t batch, float* dst) {
     const size_t mn = (size_t)d * N, stride = mn + N;
     launch_gemm<true, false, EPI_STORE, true>(s, f->Gb, f->dZu, f->part, nullptr, d, N, U, d, N, N, splits, kper, stride);
     launch_reduce_partials(s, f->part, splits, stride, stride, f->g_w, mn, f->g_b);
-    // Adadelta with the model's arithmetic (adadelta_l2: L2 folded into the gradient of Wn, none for bn; the sum of squares of
-    // the values BEFORE the update from the same pass)
-    const AdadeltaArgs aw{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr, c.rho, c.eps};
-    const AdadeltaArgs ab{0.f, c.lr, c.rho, c.eps};
-    const int nbw = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)mn, 4), 256)));
-    const int nbb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)N, 4), 256)));
-    launch((adadelta_l2<false>), dim3(nbw), dim3(256), 0, s, f->Wn, f->g_w, f->accu_w, f->delta_w, mn, aw, f->red_sq,
-           (const uint32_t*)nullptr, 1u, (int)kRowsAll);
-    launch((adadelta_l2<false>), dim3(nbb), dim3(256), 0, s, f->bn, f->g_b, f->accu_b, f->delta_b, (size_t)N, ab,
-           f->red_sq + kOptBlocks, (const uint32_t*)nullptr, 1u, (int)kRowsAll);
-    launch(finalize_loss, dim3(1), dim3(256), 0, s, (const float*)f->rowloss, B, (const float*)f->red_sq, c.lambda_ > 0.f ? nbw : 0,
-           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    // Adadelta: L2 on Wn, none on bn, whose sums of squares are not in the loss
+    const int nb = fold_adadelta(f, f->Wn, f->g_w, f->accu_w, f->delta_w, mn, true, f->red_sq);
+    fold_adadelta(f, f->bn, f->g_b, f->accu_b, f->delta_b, (size_t)N, false, f->red_sq + kOptBlocks);
+    fold_finalize(f, f->rowloss, B, nb, dst);
     return 0;
 }
 

@@ -189,10 +189,7 @@ static int64_t ll_rank_chunk_inputs(const int32_t* tokens, const int64_t* offset
 // distinct tokens (`rows` with the padding) into w.P, and their entropies
 static void ll_rank_chunk_distributions(sert_model* m, hipStream_t s, LLRankScratch& w, int64_t Dc, int64_t rows) {
     const int V = m->cfg.num_entities, d = m->cfg.word_dim;
-    if (d % 4 == 0)
-        launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
-    else
-        launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, w.ids, m->rw, w.G, rows, d);
+    gather_rows(s, w.ids, m->rw, w.G, rows, d);
     for (int64_t r0 = 0; r0 < rows; r0 += kLLRankRows)
         launch_gemm<false, false, EPI_BIAS>(s, w.G + (size_t)r0 * d, m->W, w.P + (size_t)r0 * V, m->b, kLLRankRows, V, d, d, V, V);
     launch(ll_softmax_rows, dim3(cdiv(Dc, 4)), dim3(256), 0, s, w.P, Dc, V);

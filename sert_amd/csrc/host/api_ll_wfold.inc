@@ -3,21 +3,13 @@
 // wfold_index.h).  Like sert_wfold the handle copies the model's parameters when it is created and runs on a stream of its
 // own: it shares nothing with the model's step schedule.
 
-struct sert_ll_wfold : FoldBase {
+struct sert_ll_wfold : FoldLl {
     sert_ll_wfold_config cfg;
-    int Vw = 0, Ve = 0, Nw = 0, d = 0, n = 0;
-    // the frozen snapshot
-    float *rw = nullptr, *W = nullptr, *b = nullptr;
+    int Nw = 0;
     // the new word rows, Adadelta's accumulators, the gradient
     float *Nv = nullptr, *accu = nullptr, *delta = nullptr, *G = nullptr;
-    // ---- the upload ----
-    int64_t Df = 0;                  // distinct frozen words of the upload (FoldBase: M instances)
-    int32_t* y = nullptr;            // (M) integer labels (sert_ll_wfold_upload), or ...
-    int64_t* indptr = nullptr;       // ... label rows (sert_ll_wfold_upload_csr): (M + 1) offsets, ...
-    int32_t* indices = nullptr;      // ... their columns in [0, V_e), strictly increasing per row, ...
-    float* data = nullptr;           // ... and values (nnz each)
-    float* labfix = nullptr;         // label rows: per entry Q_e dQ_e of the step (nnz)
-    float* w = nullptr;              // (M)
+    // ---- the upload (FoldBase: M instances; FoldLl: the labels, columns in [0, V_e), and w) ----
+    int64_t Df = 0;                  // distinct frozen words of the upload
     int32_t* slot = nullptr;         // (M, n)  >= 0: row of Lf; < 0: new word ~slot
     float* Lf = nullptr;             // (Df, V_e) the frozen table (null when the upload holds no frozen word)
     // the inverted index new word -> batch rows (wfold_index.h)
@@ -29,19 +21,15 @@ struct sert_ll_wfold : FoldBase {
     float* Ln = nullptr;             // (Nw, V_e)  the step table
     float* S = nullptr;              // (Nw, V_e)  sums of dJ, then dZ
     float* DJ = nullptr;             // (B, V_e)
-    float* rowloss = nullptr;        // (B)
-    float* red_sq = nullptr;         // [kOptBlocks] sums of squares of Nv
-    DevBuf<float> skbuf;             // the k ranges of G = dZ W^T
+    DevBuf<float> skbuf;             // the k ranges of G = dZ W^T (gemm_long_k)
     // what the last step launched, recorded where the launches are made: sert_debug_ll_wfold_plan (sert_hip_debug.h)
     int32_t plan[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 static void llw_free_upload(sert_ll_wfold* f) {
-    for (void* p : {(void*)f->y, (void*)f->indptr, (void*)f->indices, (void*)f->data, (void*)f->labfix, (void*)f->w, (void*)f->slot,
-                    (void*)f->Lf, (void*)f->idx_rows, (void*)f->idx_items, (void*)f->part})
-        (void)hipFree(p);
-    f->y = nullptr; f->indptr = nullptr; f->indices = nullptr; f->data = nullptr; f->labfix = nullptr; f->w = nullptr; f->slot = nullptr; f->Lf = nullptr; f->idx_rows = nullptr; f->idx_items = nullptr;
-    f->part = nullptr;
+    fold_free_labels(f);
+    for (void* p : {(void*)f->slot, (void*)f->Lf, (void*)f->idx_rows, (void*)f->idx_items, (void*)f->part}) (void)hipFree(p);
+    f->slot = nullptr; f->Lf = nullptr; f->idx_rows = nullptr; f->idx_items = nullptr; f->part = nullptr;
     f->idx_batches.clear();
     f->M = 0; f->Df = 0;
 }
@@ -107,44 +95,20 @@ int sert_ll_wfold_create(sert_model* m, int32_t num_new_words, const float* init
                        [&](sert_ll_wfold* f) { return llw_create(f, m, num_new_words, init_rows, cfg); });
 }
 
-// rows of Z (rows, V_e) -> log softmax, in place: the model's own launch (step_softmax_loglinear.inc)
-static void llw_logsoftmax(hipStream_t s, float* Z, int64_t rows, int V) {
-    if (V <= 64 * 16)      launch((ll_logsoftmax_rows<16>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
-    else if (V <= 64 * 32) launch((ll_logsoftmax_rows<32>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
-    else                   launch((ll_logsoftmax_rows<0>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
-}
-
-// The labels of an upload, already validated: y (one per instance), or the CSR rows (indptr, indices, data).
-struct LlwLabels {
-    const int32_t* y;
-    const int64_t* indptr;
-    const int32_t* indices;
-    const float* data;
-};
-
 // What an upload of either label form does once its labels are known to be good: the tokens are validated; then the distinct
 // frozen words, the frozen table in slabs, the slots, the inverted index, and the copies of those, of the labels and of w.
 // Nothing of the handle is touched before every host-side check has passed and the new table is allocated.
-static int llw_upload(sert_ll_wfold* f, const int32_t* x, const LlwLabels& lab, const float* w, int64_t M) {
+static int llw_upload(sert_ll_wfold* f, const int32_t* x, const FoldLabels& lab, const float* w, int64_t M) {
     const int n = f->n, d = f->d, Ve = f->Ve, B = f->cfg.batch_size;
-    const int64_t nnz = (lab.y || M == 0) ? 0 : lab.indptr[M];      // (M == 0: an empty upload of either form)
     const int64_t ext = (int64_t)f->Vw + f->Nw;
     for (int64_t i = 0; i < M * n; ++i)
         if (x[i] < 0 || x[i] >= ext) SERT_FAIL("token id out of range [0, vocab_size + num_new_words)");
     // ---- the distinct frozen words Df of x (sorted) and the row of its table of every position ----
-    std::vector<int32_t> row_of((size_t)f->Vw, -1), words;
-    for (int64_t i = 0; i < M * n; ++i)
-        if (x[i] < f->Vw) row_of[(size_t)x[i]] = 0;
-    for (int32_t v = 0; v < f->Vw; ++v)
-        if (row_of[(size_t)v] == 0) { row_of[(size_t)v] = (int32_t)words.size(); words.push_back(v); }
-    const int64_t Df = (int64_t)words.size();
-    const unsigned long long need = (unsigned long long)Df * (unsigned long long)Ve * sizeof(float);
-    if (f->cfg.max_cache_bytes != 0 && need > f->cfg.max_cache_bytes)
-        SERT_FAIL("the frozen table of this upload needs " + std::to_string(need) + " bytes (" + std::to_string(Df) +
-                  " distinct frozen words x " + std::to_string(Ve) + " entities), more than max_cache_bytes = " +
-                  std::to_string((unsigned long long)f->cfg.max_cache_bytes));
+    FoldWordTable t;
+    SERT_TRY(fold_word_table(x, M * n, f->Vw, Ve, f->cfg.max_cache_bytes, "frozen table", "distinct frozen words", &t));
+    const int64_t Df = (int64_t)t.words.size();
     std::vector<int32_t> slot((size_t)(M * n));
-    for (size_t k = 0; k < slot.size(); ++k) slot[k] = x[k] < f->Vw ? row_of[(size_t)x[k]] : ~(x[k] - f->Vw);
+    for (size_t k = 0; k < slot.size(); ++k) slot[k] = x[k] < f->Vw ? t.row_of[(size_t)x[k]] : ~(x[k] - f->Vw);
     // the inverted index of the complete batches (host; a function of the upload alone)
     const int64_t nbatches = M / B;
     WfoldIndex index;
@@ -157,10 +121,7 @@ static int llw_upload(sert_ll_wfold* f, const int32_t* x, const LlwLabels& lab, 
     hipStream_t s = f->stream;
     // the new table first: an upload whose table cannot be allocated keeps the earlier one
     float* table = nullptr;
-    if (M > 0 && need != 0 && hipMalloc((void**)&table, (size_t)need) != hipSuccess) {
-        (void)hipGetLastError();
-        SERT_FAIL("the frozen table of this upload needs " + std::to_string(need) + " bytes, which cannot be allocated");
-    }
+    SERT_TRY(fold_alloc_table(t, &table));
     if (hipStreamSynchronize(s) != hipSuccess) {
         (void)hipFree(table);
         SERT_FAIL("hipStreamSynchronize failed");
@@ -172,27 +133,11 @@ static int llw_upload(sert_ll_wfold* f, const int32_t* x, const LlwLabels& lab, 
     float* Gs = nullptr;
     std::vector<float> ones;
     auto body = [&]() -> int {
-        if (lab.y) {
-            SERT_TRY(dmalloc(&f->y, (size_t)M));
-            SERT_HIP(hipMemcpyAsync(f->y, lab.y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        } else {
-            SERT_TRY(dmalloc(&f->indptr, (size_t)M + 1));
-            SERT_TRY(dmalloc(&f->indices, (size_t)std::max<int64_t>(1, nnz)));
-            SERT_TRY(dmalloc(&f->data, (size_t)std::max<int64_t>(1, nnz)));
-            SERT_TRY(dmalloc(&f->labfix, (size_t)std::max<int64_t>(1, nnz)));
-            SERT_HIP(hipMemcpyAsync(f->indptr, lab.indptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            if (nnz) {
-                SERT_HIP(hipMemcpyAsync(f->indices, lab.indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                SERT_HIP(hipMemcpyAsync(f->data, lab.data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, s));
-            }
-        }
-        SERT_TRY(dmalloc(&f->w, (size_t)M));
+        SERT_TRY(fold_upload_labels(f, lab, w, M, ones));
         SERT_TRY(dmalloc(&f->slot, (size_t)M * n));
         SERT_TRY(dmalloc(&f->idx_rows, std::max<size_t>(index.rows.size(), 1)));
         SERT_TRY(dmalloc(&f->idx_items, std::max<size_t>(index.items.size(), 1)));
         SERT_TRY(dmalloc(&f->part, std::max<size_t>((size_t)index.max_part_rows * Ve, 4)));
-        if (!w) ones.assign((size_t)M, 1.0f);
-        SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, s));
         SERT_HIP(hipMemcpyAsync(f->slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if (!index.rows.empty())
             SERT_HIP(hipMemcpyAsync(f->idx_rows, index.rows.data(), index.rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -204,19 +149,14 @@ static int llw_upload(sert_ll_wfold* f, const int32_t* x, const LlwLabels& lab, 
         if (Df > 0) {
             SERT_TRY(dmalloc(&dwords, (size_t)Df));
             SERT_TRY(dmalloc(&Gs, (size_t)slab * d));
-            SERT_HIP(hipMemcpyAsync(dwords, words.data(), (size_t)Df * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            SERT_HIP(hipMemcpyAsync(dwords, t.words.data(), (size_t)Df * sizeof(int32_t), hipMemcpyHostToDevice, s));
         }
         for (int64_t r0 = 0; r0 < Df; r0 += slab) {
             const int64_t rows = std::min<int64_t>(slab, Df - r0);
-            if (d % 4 == 0)
-                launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)(dwords + r0), (const float*)f->rw, Gs, rows, d);
-            else
-                launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)(dwords + r0), (const float*)f->rw, Gs, rows, d);
+            gather_rows(s, (const uint32_t*)(dwords + r0), f->rw, Gs, rows, d);
             float* dst = f->Lf + (size_t)r0 * Ve;
             launch_gemm<false, false, EPI_BIAS>(s, Gs, f->W, dst, f->b, (int)rows, Ve, d, d, Ve, Ve);
-            llw_logsoftmax(s, dst, rows, Ve);
+            logsoftmax_rows(s, dst, rows, Ve);
         }
         SERT_HIP(hipGetLastError());
         SERT_HIP(hipStreamSynchronize(s));     // (x, the labels, w and the host lists are borrowed for the call only)
@@ -242,7 +182,7 @@ int sert_ll_wfold_upload(sert_ll_wfold* f, const int32_t* x, const int32_t* y, c
     // host-side validation: no kernel is launched on bad ids
     for (int64_t i = 0; i < M; ++i)
         if (y[i] < 0 || y[i] >= f->Ve) SERT_FAIL("fold-in label out of range [0, num_entities)");
-    return llw_upload(f, x, LlwLabels{y, nullptr, nullptr, nullptr}, w, M);
+    return llw_upload(f, x, FoldLabels{y, nullptr, nullptr, nullptr}, w, M);
 }
 
 int sert_ll_wfold_upload_csr(sert_ll_wfold* f, const int32_t* x, const int64_t* indptr, const int32_t* indices, const float* data,
@@ -250,28 +190,10 @@ int sert_ll_wfold_upload_csr(sert_ll_wfold* f, const int32_t* x, const int64_t* 
     refresh_gemm_choice();
     if (!f || M < 0 || (M > 0 && (!x || !indptr))) SERT_FAIL("bad argument");
     SERT_TRY(llw_upload_check_sizes(M));
-    // host-side validation, worded as sert_upload_dataset words it for csr_*: no kernel is launched on a bad row
-    if (M > 0) {
-        if (indptr[0] != 0) SERT_FAIL("csr_indptr[0] != 0");
-        for (int64_t r = 0; r < M; ++r)
-            if (indptr[r + 1] < indptr[r]) SERT_FAIL("csr_indptr is not non-decreasing");
-        const int64_t nnz = indptr[M];
-        if (nnz > ((int64_t)1 << 31) - 1) SERT_FAIL("more than 2^31 - 1 label entries");
-        if (nnz > 0 && (!indices || !data)) SERT_FAIL("bad argument");
-        // (a word fold-in has no new entity: column V_e is refused)
-        for (int64_t i = 0; i < nnz; ++i)
-            if (indices[i] < 0 || indices[i] >= f->Ve) SERT_FAIL("label column out of range [0, num_entities) in csr_indices");
-        // strictly increasing columns per row: llw_row_csr adds a row's entries to DJ from different threads without atomics
-        for (int64_t r = 0; r < M; ++r)
-            for (int64_t i = indptr[r] + 1; i < indptr[r + 1]; ++i)
-                if (indices[i] <= indices[i - 1]) {
-                    char msg[160];
-                    snprintf(msg, sizeof msg, "csr_indices of row %lld are not strictly increasing (duplicate or unsorted label column %d)",
-                             (long long)r, (int)indices[i]);
-                    SERT_FAIL(msg);
-                }
-    }
-    return llw_upload(f, x, LlwLabels{nullptr, indptr, indices, data}, w, M);
+    // host-side validation: no kernel is launched on a bad row (a word fold-in has no new entity: column V_e is refused)
+    if (M > 0)
+        SERT_TRY(check_csr_rows(indptr, indices, data, M, f->Ve, "label column out of range [0, num_entities) in csr_indices", INT32_MAX));
+    return llw_upload(f, x, FoldLabels{nullptr, indptr, indices, data}, w, M);
 }
 
 int64_t sert_ll_wfold_num_batches(sert_ll_wfold* f) { return fold_num_batches(f); }
@@ -287,7 +209,7 @@ static int llw_forward(sert_ll_wfold* f, int64_t batch, bool train) {
     hipStream_t s = f->stream;
     for (int32_t& v : f->plan) v = 0;
     f->plan[11] = wfold_gemm<false, false, EPI_BIAS>(s, f->Nv, f->W, f->Ln, f->b, Nw, Ve, d, d, Ve, Ve);
-    llw_logsoftmax(s, f->Ln, Nw, Ve);
+    logsoftmax_rows(s, f->Ln, Nw, Ve);
     const size_t row0 = (size_t)batch * B;
     const int vec = Ve % 4 == 0 ? 1 : 0;
     const bool reg = Ve <= 1024;
@@ -343,60 +265,19 @@ static int llw_segsum(sert_ll_wfold* f, int64_t batch) {
     return 0;
 }
 
-// step 5: G (Nw, d) = dZ W^T, the form of the model's dG: K = V_e is the long side, cut into k ranges by gemm_long_k's rule
-// (lazy_segsum.inc) with an order-fixed combine; the ranges live in the handle's own buffer
-static int llw_grad_gemm(sert_ll_wfold* f) {
-    const int M = f->Nw, N = f->d, K = f->Ve;
-    hipStream_t s = f->stream;
-    const float *A = f->S, *Bm = f->W;
-    const int tiles = cdiv(M, GM) * cdiv(N, GN);
-    int splits = 1;
-    if (tiles < 512 && K >= 4096) splits = std::min(cdiv(1024, tiles), K / 1024);
-    else if (tiles < 256 && K >= 512) splits = std::min(cdiv(1024, tiles), K / 128);
-    if (K >= 4096 && gemm_x3_enabled()) {
-        const int t3 = cdiv(M, N <= 128 ? 128 : 256) * cdiv(N, N <= 128 ? 128 : 320);
-        const int s3 = std::max(1, std::min(cdiv(512, t3), K / 1024));
-        if (s3 > 1 && x3_shape_ok(false, true, A, Bm, M, N, K, K, K, s3)) splits = s3;
-    }
-    if (splits <= 1) {
-        f->plan[12] = wfold_gemm<false, true, EPI_STORE>(s, A, Bm, f->G, nullptr, M, N, K, K, K, N);
-        f->plan[13] = 1;
-        return 0;
-    }
-    const int kper = (int)round_up(cdiv(K, splits), GK);
-    splits = cdiv(K, kper);
-    const size_t mn = (size_t)M * N;
-    if ((int64_t)(mn * splits) > f->skbuf.cap) {
-        SERT_HIP(hipStreamSynchronize(s));      // (DevBuf::reserve frees the old buffer without synchronising)
-        SERT_TRY(f->skbuf.reserve((int64_t)(mn * splits)));
-    }
-    f->plan[12] = gemm_takes_x3(false, true, EPI_STORE, false, false, A, Bm, M, N, K, K, K, splits, kper)
-                      ? x3_route(true, A, Bm, M, N, K, K, K, splits)
-                      : gemm_f32_route(false, true, EPI_STORE, false, A, Bm, M, N, K, K, K, splits, kper);
-    f->plan[13] = splits;
-    launch_gemm<false, true, EPI_STORE>(s, A, Bm, f->skbuf.p, nullptr, M, N, K, K, K, N, splits, kper, mn);
-    launch_reduce_partials(s, f->skbuf.p, splits, mn, mn, f->G, mn, f->G);
-    return 0;
-}
-
 // one step enqueued on the handle's stream; dst: 3 floats on the device (finalize_loss: loss, data term, regulariser)
 static int llw_step_async(sert_ll_wfold* f, int64_t batch, float* dst) {
-    const auto& c = f->cfg;
-    const int B = c.batch_size, Ve = f->Ve, Nw = f->Nw;
+    const int Ve = f->Ve, Nw = f->Nw;
     hipStream_t s = f->stream;
     SERT_TRY(llw_forward(f, batch, true));
     SERT_TRY(llw_segsum(f, batch));
     launch(llw_finish, dim3(cdiv(Nw, 4)), dim3(256), 0, s, (const float*)f->Ln, f->S, Nw, Ve);
-    SERT_TRY(llw_grad_gemm(f));
-    // Adadelta with the model's arithmetic (adadelta_l2: L2 folded into the gradient, the sum of squares of the values BEFORE
-    // the update from the same pass), then the step's three losses -- exactly as api_ll_foldin.inc runs them
-    const size_t count = (size_t)Nw * f->d;
-    const AdadeltaArgs a{c.lambda_ > 0.f ? c.lambda_ / (float)B : 0.f, c.lr, c.rho, c.eps};
-    const int nb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)count, 4), 256)));
-    launch((adadelta_l2<false>), dim3(nb), dim3(256), 0, s, f->Nv, f->G, f->accu, f->delta, count, a, f->red_sq,
-           (const uint32_t*)nullptr, 1u, (int)kRowsAll);
-    launch(finalize_loss, dim3(1), dim3(256), 0, s, (const float*)f->rowloss, B, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0,
-           1.0f / (float)B, c.lambda_ > 0.f ? c.lambda_ / (2.0f * (float)B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    // step 5: G (Nw, d) = dZ W^T, the form of the model's dG: K = V_e is the long side, cut into k ranges with an order-fixed
+    // combine; the ranges live in the handle's own buffer
+    SERT_TRY((gemm_long_k<false, true>(f->skbuf, s, f->S, f->W, f->G, Nw, f->d, Ve, Ve, Ve, nullptr, nullptr, nullptr, &f->plan[12],
+                                       &f->plan[13])));
+    const int nb = fold_adadelta(f, f->Nv, f->G, f->accu, f->delta, (size_t)Nw * f->d, true, f->red_sq);
+    fold_finalize(f, f->rowloss, f->cfg.batch_size, nb, dst);
     return 0;
 }
 

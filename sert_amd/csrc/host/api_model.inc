@@ -416,7 +416,7 @@ int sert_destroy(sert_model* m) {
     if (m->comm_stream) (void)hipStreamDestroy(m->comm_stream);
     float* bufs[] = {m->rw, m->re, m->W, m->b, m->s0_rw, m->s0_re, m->s0_w, m->s0_b, m->s1_rw,
                      m->s1_re, m->s1_w, m->s1_b, m->gflat, m->H, m->T, m->T_alt, m->DA, m->DH, m->rowloss,
-                     m->G, m->Z, m->J, m->DG, m->DH2, m->part, m->skbuf, m->wpart, m->hpart, m->red_loss, m->red_sq, m->re_sq, m->d_loss,
+                     m->G, m->Z, m->J, m->DG, m->DH2, m->part, m->skbuf.p, m->wpart, m->hpart, m->red_loss, m->red_sq, m->re_sq, m->d_loss,
                      m->d_losses};
     for (float* p : bufs) (void)hipFree(p);
     (void)hipFree(m->ll_tokstat); (void)hipFree(m->ll_lse); (void)hipFree(m->ll_jstat);

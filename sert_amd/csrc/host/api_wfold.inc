@@ -98,9 +98,7 @@ extern "C++" {
 template <bool TA, bool TB, int EPI>
 static int wfold_gemm(hipStream_t s, const float* A, const float* Bm, float* C, const float* bias, int M, int N, int K, int lda,
                       int ldb, int ldc) {
-    const int route = gemm_takes_x3(TA, TB, EPI, false, false, A, Bm, M, N, K, lda, ldb, 1, K)
-                          ? (TA ? x3_ta_route(M, N) : x3_route(TB, A, Bm, M, N, K, lda, ldb, 1))
-                          : gemm_f32_route(TA, TB, EPI, false, A, Bm, M, N, K, lda, ldb, 1, K);
+    const int route = gemm_route(TA, TB, EPI, false, false, A, Bm, M, N, K, lda, ldb, 1, K);
     launch_gemm<TA, TB, EPI>(s, A, Bm, C, bias, M, N, K, lda, ldb, ldc);
     return route;
 }

@@ -1,7 +1,10 @@
 // Part of sert_hip.hip (one translation unit; included there, inside its extern "C" block, in front of api_foldin.inc): the
-// runtime the four fold-in handles share (api_foldin.inc: sert_foldin; api_ll_foldin.inc: sert_ll_foldin; api_wfold.inc:
-// sert_wfold; api_ll_wfold.inc: sert_ll_wfold).  Every piece below is stated once; what a handle validates, its own buffers, its forward, its gradient and its
-// plan stay in its file.  Nothing here calls refresh_gemm_choice(): that is the public entry points' business.
+// runtime the four fold-in handles share (api_foldin.inc: sert_foldin; api_wfold.inc: sert_wfold -- the two NCE handles of a
+// vectorspace model, on FoldNce; api_ll_foldin.inc: sert_ll_foldin; api_ll_wfold.inc: sert_ll_wfold -- the two Adadelta handles
+// of a loglinear model, on FoldLl).  Every piece below is stated once; what a handle validates, its own buffers, its forward,
+// its gradient and its plan stay in its file.  The launchers the handles share with the training step (gather_rows,
+// gather_mean, logsoftmax_rows, gemm_long_k) are in lazy_segsum.inc, the CSR row validator (check_csr_rows) in
+// api_data_train.inc.  Nothing here calls refresh_gemm_choice(): that is the public entry points' business.
 extern "C++" {
 
 // What every fold-in handle holds.  (cfg stays in the handle: the four config structs are distinct ABI structs.)
@@ -31,6 +34,30 @@ struct FoldNce : FoldBase {
     float* red_loss = nullptr;       // per-workgroup loss partials of the loss kernel
     float* red_sq = nullptr;         // [kOptBlocks] sums of squares of the trainable rows
     int64_t step = 0, eval_draws = 0;
+};
+
+// ... and the two Adadelta handles of a loglinear model.  (Ve: the columns of the frozen W the handle's kernels see.)
+struct FoldLl : FoldBase {
+    int Vw = 0, Ve = 0, d = 0, n = 0;
+    // the frozen snapshot
+    float *rw = nullptr, *W = nullptr, *b = nullptr;
+    // the uploaded labels: one per instance (*_upload), or label rows (*_upload_csr) -- (M + 1) offsets, the (nnz) columns,
+    // strictly increasing per row, and their values -- with labfix, per entry Q_e dQ_e of the step (nnz); the weights (M)
+    int32_t* y = nullptr;
+    int64_t* indptr = nullptr;
+    int32_t* indices = nullptr;
+    float *data = nullptr, *labfix = nullptr, *w = nullptr;
+    // per-step scratch
+    float* rowloss = nullptr;        // (B)
+    float* red_sq = nullptr;         // [kOptBlocks] sums of squares per parameter block (fold_adadelta)
+};
+
+// The labels of a loglinear upload, already validated: y (one per instance), or the CSR rows (indptr, indices, data).
+struct FoldLabels {
+    const int32_t* y;
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float* data;
 };
 
 // ---- create and destroy ----------------------------------------------------------------------------------------------
@@ -116,14 +143,79 @@ static int fold_upload_failed(F* f, int rc, FreeUpload free_upload) {
     return rc;
 }
 
-// y and w of an upload of M > 0 instances into a vectorspace handle; ones: the weights of an upload without w -- the
-// caller's vector, because it must live until the upload's final synchronisation
+// *dst = the weights of an upload of M > 0 instances; ones: the weights of an upload without w -- the caller's vector,
+// because it must live until the upload's final synchronisation
+static int fold_upload_weights(FoldBase* f, float** dst, const float* w, int64_t M, std::vector<float>& ones) {
+    SERT_TRY(dmalloc(dst, (size_t)M));
+    if (!w) ones.assign((size_t)M, 1.0f);
+    SERT_HIP(hipMemcpyAsync(*dst, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, f->stream));
+    return 0;
+}
+
+// y and w of an upload of M > 0 instances into a vectorspace handle
 static int fold_upload_labels(FoldNce* f, const int32_t* y, const float* w, int64_t M, std::vector<float>& ones) {
     SERT_TRY(dmalloc(&f->y, (size_t)M));
-    SERT_TRY(dmalloc(&f->w, (size_t)M));
     SERT_HIP(hipMemcpyAsync(f->y, y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
-    if (!w) ones.assign((size_t)M, 1.0f);
-    SERT_HIP(hipMemcpyAsync(f->w, w ? w : ones.data(), (size_t)M * sizeof(float), hipMemcpyHostToDevice, f->stream));
+    return fold_upload_weights(f, &f->w, w, M, ones);
+}
+
+// ... and the labels of either form and w into a loglinear handle
+static int fold_upload_labels(FoldLl* f, const FoldLabels& lab, const float* w, int64_t M, std::vector<float>& ones) {
+    hipStream_t s = f->stream;
+    if (lab.y) {
+        SERT_TRY(dmalloc(&f->y, (size_t)M));
+        SERT_HIP(hipMemcpyAsync(f->y, lab.y, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    } else {
+        const int64_t nnz = lab.indptr[M];
+        SERT_TRY(dmalloc(&f->indptr, (size_t)M + 1));
+        SERT_TRY(dmalloc(&f->indices, (size_t)std::max<int64_t>(1, nnz)));
+        SERT_TRY(dmalloc(&f->data, (size_t)std::max<int64_t>(1, nnz)));
+        SERT_TRY(dmalloc(&f->labfix, (size_t)std::max<int64_t>(1, nnz)));
+        SERT_HIP(hipMemcpyAsync(f->indptr, lab.indptr, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        if (nnz) {
+            SERT_HIP(hipMemcpyAsync(f->indices, lab.indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            SERT_HIP(hipMemcpyAsync(f->data, lab.data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+    }
+    return fold_upload_weights(f, &f->w, w, M, ones);
+}
+
+static void fold_free_labels(FoldLl* f) {
+    for (void* p : {(void*)f->y, (void*)f->indptr, (void*)f->indices, (void*)f->data, (void*)f->labfix, (void*)f->w}) (void)hipFree(p);
+    f->y = nullptr; f->indptr = nullptr; f->indices = nullptr; f->data = nullptr; f->labfix = nullptr; f->w = nullptr;
+}
+
+// The distinct words of an upload that have a row in a device table of V_e columns (the logit cache, the frozen table):
+// the ids below Vw among x's `count` tokens, ascending, and the row of each (-1: none); the table's bytes, refused above
+// max_cache_bytes (0: no limit).  noun, unit: the handle's words for the table and for its rows.
+struct FoldWordTable {
+    std::vector<int32_t> row_of, words;
+    unsigned long long need = 0;
+    const char* noun = "";
+};
+static int fold_word_table(const int32_t* x, int64_t count, int Vw, int Ve, unsigned long long max_cache_bytes, const char* noun,
+                           const char* unit, FoldWordTable* t) {
+    t->noun = noun;
+    t->row_of.assign((size_t)Vw, -1);
+    for (int64_t i = 0; i < count; ++i)
+        if (x[i] < Vw) t->row_of[(size_t)x[i]] = 0;
+    for (int32_t v = 0; v < Vw; ++v)
+        if (t->row_of[(size_t)v] == 0) { t->row_of[(size_t)v] = (int32_t)t->words.size(); t->words.push_back(v); }
+    const unsigned long long D = t->words.size();
+    t->need = D * (unsigned long long)Ve * sizeof(float);
+    if (max_cache_bytes != 0 && t->need > max_cache_bytes)
+        SERT_FAIL(std::string("the ") + noun + " of this upload needs " + std::to_string(t->need) + " bytes (" + std::to_string(D) + " " +
+                  unit + " x " + std::to_string(Ve) + " entities), more than max_cache_bytes = " + std::to_string(max_cache_bytes));
+    return 0;
+}
+// ... and its allocation (an empty table: *table stays null), refused with the bytes it needs
+static int fold_alloc_table(const FoldWordTable& t, float** table) {
+    *table = nullptr;
+    if (t.need != 0 && hipMalloc((void**)table, (size_t)t.need) != hipSuccess) {
+        (void)hipGetLastError();
+        *table = nullptr;
+        SERT_FAIL(std::string("the ") + t.noun + " of this upload needs " + std::to_string(t.need) + " bytes, which cannot be allocated");
+    }
     return 0;
 }
 
@@ -148,12 +240,7 @@ static int fold_project_slabs(FoldNce* f, const int32_t* x, int64_t M, float* ou
             SERT_HIP(hipMemcpyAsync(has_split ? (void*)xs : (void*)dx, x + (size_t)r0 * n, (size_t)rows * n * sizeof(int32_t),
                                     hipMemcpyHostToDevice, s));
             if constexpr (has_split) split((const int32_t*)xs, dx, r0, rows);
-            if (dw % 4 == 0)
-                launch((vs_gather_mean<uint32_t, 4>), dim3(grid_for((int64_t)rows * dw / 4, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
-            else
-                launch((vs_gather_mean<uint32_t, 1>), dim3(grid_for((int64_t)rows * dw, 256, 1 << 20)), dim3(256), 0, s,
-                       (const uint32_t*)dx, (const float*)f->rw, H, rows, n, dw);
+            gather_mean(s, (const uint32_t*)dx, f->rw, H, rows, n, dw);
             launch_gemm<false, false, EPI>(s, H, f->W, out + (size_t)r0 * de, f->b, rows, de, dw, dw, de, de);
         }
         SERT_HIP(hipGetLastError());
@@ -262,6 +349,20 @@ static int fold_negatives_of_step(F* f, int64_t position, int evaluation, int64_
 }
 
 // ---- the end of a step ---------------------------------------------------------------------------------------------------
+// the workgroups of an optimiser launch over `count` floats: each leaves one partial sum of squares
+static int fold_opt_blocks(size_t count) {
+    return (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)count, 4), 256)));
+}
+
+// the step's three losses at dst: the mean of the partials and, with an L2 term, the nb partial sums of squares at f->red_sq
+template <class F>
+static void fold_finalize(F* f, const float* parts, int n_parts, int nb, float* dst) {
+    const auto& c = f->cfg;
+    const float B = (float)c.batch_size;
+    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, parts, n_parts, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0, 1.0f / B,
+           c.lambda_ > 0.f ? c.lambda_ / (2.0f * B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+}
+
 // Adam over the `count` trainable floats at P with the model's arithmetic (adam_l2: L2 folded into the gradient, sum of squares
 // of the values BEFORE the update from the same pass); a_t on the host in fp32 (optimizer_args); then the step's three losses
 template <class F>
@@ -272,11 +373,23 @@ static void fold_adam_finalize(F* f, float* P, size_t count, const float* parts,
     const float tf = (float)f->step;
     AdamArgs aa{c.lambda_ > 0.f ? c.lambda_ / B : 0.f, c.lr * sqrtf(1.0f - powf(c.beta2, tf)) / (1.0f - powf(c.beta1, tf)), c.beta1,
                 c.beta2, c.eps};
-    const int nb = (int)std::min<int64_t>(kOptBlocks, std::max<int64_t>(1, cdiv(cdiv((int64_t)count, 4), 256)));
+    const int nb = fold_opt_blocks(count);
     launch((adam_l2<false>), dim3(nb), dim3(256), 0, f->stream, P, f->G, f->m1, f->m2, count, aa, f->red_sq, (const uint32_t*)nullptr,
            1u, (int)kRowsAll, (float*)nullptr);
-    launch(finalize_loss, dim3(1), dim3(256), 0, f->stream, parts, n_parts, (const float*)f->red_sq, c.lambda_ > 0.f ? nb : 0, 1.0f / B,
-           c.lambda_ > 0.f ? c.lambda_ / (2.0f * B) : 0.f, dst, (unsigned*)nullptr, 0u, (const float*)nullptr);
+    fold_finalize(f, parts, n_parts, nb, dst);
+}
+
+// Adadelta over one parameter block of a loglinear handle, `count` floats at P, with the model's arithmetic (adadelta_l2: L2
+// folded into the gradient where the block has an L2 term, the sum of squares of the values BEFORE the update from the same
+// pass, into sq); -> the workgroups that wrote a partial sum to sq, for fold_finalize
+template <class F>
+static int fold_adadelta(F* f, float* P, float* G, float* accu, float* delta, size_t count, bool l2, float* sq) {
+    const auto& c = f->cfg;
+    const AdadeltaArgs a{l2 && c.lambda_ > 0.f ? c.lambda_ / (float)c.batch_size : 0.f, c.lr, c.rho, c.eps};
+    const int nb = fold_opt_blocks(count);
+    launch((adadelta_l2<false>), dim3(nb), dim3(256), 0, f->stream, P, G, accu, delta, count, a, sq, (const uint32_t*)nullptr, 1u,
+           (int)kRowsAll);
+    return nb;
 }
 
 // an evaluation's loss: the mean of the partials, unregularised

@@ -1,4 +1,4 @@
-// Part of sert_hip.hip (one translation unit; included there, inside its namespace / extern "C" block): the lazy word-table update's host state, the tensor table, the word-gradient tree, the loglinear per-word sums, the sorted entity-gradient chain, long-K GEMMs.
+// Part of sert_hip.hip (one translation unit; included there, inside its namespace / extern "C" block): the lazy word-table update's host state, the tensor table, the word-gradient tree, the loglinear per-word sums, the sorted entity-gradient chain, the gather and log-softmax launchers, long-K GEMMs.
 
 // ---- lazy dense update of the word table (kernels_opt.h: dense_update_lazy) ----------------------------------------
 static void optimizer_args(const sert_model* m, int64_t t, AdamArgs* aa, AdadeltaArgs* da);
@@ -430,14 +430,46 @@ static EntityChain vs_entity_chain(const sert_model* m) {
             c.num_negatives + 1, c.batch_size * (c.num_negatives + 1)};
 }
 
+// ---- launchers that the training steps, the rankers and the fold-ins share ----------------------------------------------
+// out (rows, d) = table[ids]: 16-byte pieces when d allows them
+template <typename IdT>
+static void gather_rows(hipStream_t s, const IdT* ids, const float* table, float* out, int64_t rows, int d) {
+    if (d % 4 == 0) launch((ll_gather_rows<IdT, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, ids, table, out, rows, d);
+    else            launch((ll_gather_rows<IdT, 1>), dim3(grid_for(rows * d, 256, 1 << 20)), dim3(256), 0, s, ids, table, out, rows, d);
+}
+// out (rows, d) = the mean of the n rows table[ids[r, :]]
+template <typename IdT>
+static void gather_mean(hipStream_t s, const IdT* ids, const float* table, float* out, int rows, int n, int d) {
+    if (d % 4 == 0)
+        launch((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)rows * d / 4, 256, 1 << 20)), dim3(256), 0, s, ids, table, out, rows, n, d);
+    else
+        launch((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)rows * d, 256, 1 << 20)), dim3(256), 0, s, ids, table, out, rows, n, d);
+}
+// rows of Z (rows, V) -> log softmax, in place; a wave per row, the row in registers up to V = 2048
+static void logsoftmax_rows(hipStream_t s, float* Z, int64_t rows, int V) {
+    if (V <= 64 * 16)      launch((ll_logsoftmax_rows<16>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
+    else if (V <= 64 * 32) launch((ll_logsoftmax_rows<32>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
+    else                   launch((ll_logsoftmax_rows<0>), dim3(cdiv(rows, 4)), dim3(256), 0, s, Z, rows, V);
+}
+
+// the kernel a launch_gemm call goes to (gemm.h: GemmRoute), asked of the launcher's own predicates; splits, kper as launch_gemm
+// normalises them: one k range = (1, K)
+static int gemm_route(bool ta, bool tb, int epi, bool csb, bool rowmap, const float* A, const float* Bm, int M, int N, int K,
+                      int lda, int ldb, int splits, int kper) {
+    if (gemm_takes_x3(ta, tb, epi, csb, rowmap, A, Bm, M, N, K, lda, ldb, splits, kper))
+        return ta ? x3_ta_route(M, N) : x3_route(tb, A, Bm, M, N, K, lda, ldb, splits);
+    return gemm_f32_route(ta, tb, epi, csb, A, Bm, M, N, K, lda, ldb, splits, kper);
+}
+
 // C (M,N, contiguous) = op(A).op(B) for a contraction over a LONG K (the entity
 // vocabulary in the dX GEMMs of the full-softmax models) whose output has too few
 // 128x128 tiles to fill 256 CUs: split K so that ~1024 workgroup items exist, then an
-// order-fixed combine (deterministic).
+// order-fixed combine (deterministic).  skbuf: the caller's buffer for the k ranges, grown here; route, k_ranges
+// (optional): the GemmRoute of the GEMM launch and the number of k ranges it was cut into.
 template <bool TA, bool TB>
-static int gemm_long_k(sert_model* m, hipStream_t s, const float* A, const float* Bm, float* C, int M,
+static int gemm_long_k(DevBuf<float>& skbuf, hipStream_t s, const float* A, const float* Bm, float* C, int M,
                        int N, int K, int lda, int ldb, const int32_t* rowmap = nullptr, float* mapped_C = nullptr,
-                       bool* mapped = nullptr) {
+                       bool* mapped = nullptr, int* route = nullptr, int* k_ranges = nullptr) {
     if (mapped) *mapped = false;
     const int tiles = cdiv(M, GM) * cdiv(N, GN);
     int splits = 1;
@@ -453,6 +485,8 @@ static int gemm_long_k(sert_model* m, hipStream_t s, const float* A, const float
     // (between one and two tiles per CU -- the loglinear dG at C2 dims, 347 tiles -- a three-way split was
     //  tried: 162 -> 175 us with its combine; co-resident workgroups share the matrix pipe without loss)
     if (splits <= 1) {
+        if (route) *route = gemm_route(TA, TB, EPI_STORE, false, rowmap != nullptr, A, Bm, M, N, K, lda, ldb, 1, K);
+        if (k_ranges) *k_ranges = 1;
         launch_gemm<TA, TB, EPI_STORE>(s, A, Bm, C, nullptr, M, N, K, lda, ldb, N, 1, 0, 0, nullptr, nullptr, 0, rowmap, mapped_C,
                                        mapped);
         return 0;
@@ -460,18 +494,17 @@ static int gemm_long_k(sert_model* m, hipStream_t s, const float* A, const float
     const int kper = (int)round_up(cdiv(K, splits), GK);
     splits = cdiv(K, kper);
     const size_t mn = (size_t)M * N;
-    if (mn * splits > m->skbuf_count) {
-        SERT_HIP(hipStreamSynchronize(s));
-        if (m->skbuf) (void)hipFree(m->skbuf);
-        m->skbuf = nullptr;
-        m->skbuf_count = mn * splits;
-        SERT_TRY(dmalloc(&m->skbuf, m->skbuf_count));
+    if ((int64_t)(mn * splits) > skbuf.cap) {
+        SERT_HIP(hipStreamSynchronize(s));      // (DevBuf::reserve frees the old buffer without synchronising)
+        SERT_TRY(skbuf.reserve((int64_t)(mn * splits)));
     }
-    launch_gemm<TA, TB, EPI_STORE>(s, A, Bm, m->skbuf, nullptr, M, N, K, lda, ldb, N, splits, kper, mn);
+    if (route) *route = gemm_route(TA, TB, EPI_STORE, false, false, A, Bm, M, N, K, lda, ldb, splits, kper);
+    if (k_ranges) *k_ranges = splits;
+    launch_gemm<TA, TB, EPI_STORE>(s, A, Bm, skbuf.p, nullptr, M, N, K, lda, ldb, N, splits, kper, mn);
     if (rowmap && mapped_C) {
         // (the combine stores row r as row rowmap[r] of mapped_C: no copy kernel behind it)
-        launch_reduce_partials(s, m->skbuf, splits, mn, mn, mapped_C, mn, mapped_C, rowmap, N);
+        launch_reduce_partials(s, skbuf.p, splits, mn, mn, mapped_C, mn, mapped_C, rowmap, N);
         if (mapped) *mapped = true;
-    } else launch_reduce_partials(s, m->skbuf, splits, mn, mn, C, mn, C);
+    } else launch_reduce_partials(s, skbuf.p, splits, mn, mn, C, mn, C);
     return 0;
 }

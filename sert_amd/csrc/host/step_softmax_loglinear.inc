@@ -10,12 +10,7 @@ static int fs_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         ScopedTimer t(m, TG_GATHER);
         SERT_ID_DISPATCH(c.id_bytes, {
             const IdT* X = (const IdT*)ds.x + row0 * n;
-            if (dw % 4 == 0)
-                launch((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
-                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
-            else
-                launch((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
-                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+            gather_mean(m->stream, X, m->rw, m->H, B, n, dw);
         });
     }
     {
@@ -56,7 +51,7 @@ static int fs_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
             }
             {
                 ScopedTimer t(m, TG_GEMM_DX);
-                SERT_TRY((gemm_long_k<false, false>(m, m->stream, m->Z, m->re, m->DA + (size_t)r0 * de, rows, de, V, V, de)));
+                SERT_TRY((gemm_long_k<false, false>(m->skbuf, m->stream, m->Z, m->re, m->DA + (size_t)r0 * de, rows, de, V, V, de)));
             }
         }
     }
@@ -83,7 +78,7 @@ static int fs_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
     {
         // dp = dZ.R_e (B, d_e) ; da = dp * clip'(t) * tanh'(a)
         ScopedTimer t(m, TG_GEMM_DX);
-        if (!tiled) SERT_TRY((gemm_long_k<false, false>(m, m->stream, m->Z, m->re, m->DA, B, de, V, V, de)));
+        if (!tiled) SERT_TRY((gemm_long_k<false, false>(m->skbuf, m->stream, m->Z, m->re, m->DA, B, de, V, V, de)));
         launch(vs_tanh_backward, dim3(grid_for((int64_t)B * de)), dim3(256), 0, m->stream, m->DA,
                m->T, (size_t)B * de);
     }
@@ -182,21 +177,11 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
         ScopedTimer t(m, TG_GATHER);
         if (m->ll_dedup) {
             const uint32_t* U = reinterpret_cast<const uint32_t*>(ds.idx_uwords + bx->uw_off);
-            if (d % 4 == 0)
-                launch((ll_gather_rows<uint32_t, 4>), dim3(grid_for(grows * d / 4, 256, 1 << 20)),
-                       dim3(256), 0, m->stream, U, m->rw, m->G, grows, d);
-            else
-                launch((ll_gather_rows<uint32_t, 1>), dim3(grid_for(grows * d, 256, 1 << 20)),
-                       dim3(256), 0, m->stream, U, m->rw, m->G, grows, d);
+            gather_rows(m->stream, U, m->rw, m->G, grows, d);
         } else {
             SERT_ID_DISPATCH(c.id_bytes, {
                 const IdT* X = (const IdT*)ds.x + row0 * n;
-                if (d % 4 == 0)
-                    launch((ll_gather_rows<IdT, 4>), dim3(grid_for(rows * d / 4, 256, 1 << 20)),
-                           dim3(256), 0, m->stream, X, m->rw, m->G, rows, d);
-                else
-                    launch((ll_gather_rows<IdT, 1>), dim3(grid_for(rows * d, 256, 1 << 20)),
-                           dim3(256), 0, m->stream, X, m->rw, m->G, rows, d);
+                gather_rows(m->stream, X, m->rw, m->G, rows, d);
             });
         }
     }
@@ -215,12 +200,7 @@ static int ll_forward(sert_model* m, const DataSplit& ds, int64_t batch_index) {
     // fused path: the row's (n, V) slab lives in LDS; a split with a CSR row of > kLlFusedLabels labels falls back
     if (fused) {
         ScopedTimer t(m, TG_LOSS);
-        if (m->ll_dedup)   // the per-token log-softmax, once per distinct word
-        {
-            if (V <= 64 * 16)      launch((ll_logsoftmax_rows<16>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
-            else if (V <= 64 * 32) launch((ll_logsoftmax_rows<32>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
-            else                   launch((ll_logsoftmax_rows<0>), dim3(cdiv(grows, 4)), dim3(256), 0, m->stream, m->Zu, grows, V);
-        }
+        if (m->ll_dedup) logsoftmax_rows(m->stream, m->Zu, grows, V);   // the per-token log-softmax, once per distinct word
         // 512 threads per row: 302 us at 256 (too few waves to hide the slab load), 228 at
         // 512, 320 at 640 (one wave per token, but only two workgroups fit a CU)
         // (distinct-word mode: the kernel writes dJ_i into J and r_ik into ll_r instead of dL/dZ)
@@ -334,7 +314,7 @@ static int ll_backward(sert_model* m, const DataSplit& ds, int64_t batch_index) 
             static const bool no_map = variant_knob("SERT_LL_NO_ROWMAP") != nullptr;   // cross-check knob
             const int32_t* rowmap = (m->ll_dedup && !c.keep_grads && !no_map)
                                         ? ds.idx_uwords + ds.idx_batches[(size_t)batch_index].uw_off : nullptr;
-            SERT_TRY((gemm_long_k<false, true>(m, m->stream, dZ, m->W, m->DG, (int)rows, d, V, V, V, rowmap, m->g_rw, &dg_mapped)));
+            SERT_TRY((gemm_long_k<false, true>(m->skbuf, m->stream, dZ, m->W, m->DG, (int)rows, d, V, V, V, rowmap, m->g_rw, &dg_mapped)));
         }
     }
     if (!dg_mapped) {

@@ -81,13 +81,9 @@ static int vs_project(sert_model* m, const DataSplit& ds, int64_t batch_index) {
                 ++m->tail_counts[1];
                 launch((vs_gather_mean_tail<IdT>), dim3(m->tail_nb + grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
                        dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw, m->tail_args, (unsigned)m->tail_nb);
-            } else if (dw % 4 == 0) {
-                launch((vs_gather_mean<IdT, 4>), dim3(grid_for((int64_t)B * dw / 4, 256, 1 << 20)),
-                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
             } else {
-                flush_pending_tail(m);
-                launch((vs_gather_mean<IdT, 1>), dim3(grid_for((int64_t)B * dw, 256, 1 << 20)),
-                       dim3(256), 0, m->stream, X, m->rw, m->H, B, n, dw);
+                if (dw % 4 != 0) flush_pending_tail(m);
+                gather_mean(m->stream, X, m->rw, m->H, B, n, dw);
             }
         });
     }

@@ -235,8 +235,7 @@ struct sert_model {
     float* ll_rsum = nullptr;     // (U) per-word sums of r_ik
     int ll_U = 0;
     int32_t ll_form[5] = {0, 0, 0, 0, 0};   // the loss form ll_forward launched last: sert_debug_ll_loss_form (sert_hip_debug.h)
-    float* skbuf = nullptr;       // split-K partials of the long-K dX GEMMs (grown on demand)
-    size_t skbuf_count = 0;
+    sert::DevBuf<float> skbuf;    // split-K partials of the long-K dX GEMMs (gemm_long_k grows it on demand)
     // single-GPU vectorspace step: split-K combine + W, b update + loss finalisation as one launch
     // (kernels_opt.h: vs_tail).  plan.combine_in_tail: this step's dW / db still sit in `part` as
     // dw_splits partial slabs, tail_stride elements apart

@@ -211,7 +211,46 @@ class EntityFoldIn(_NceFoldInModel):
         return ext
 
 
-class LogLinearFoldIn(_FoldInModel):
+class _LlFoldInModel(_FoldInModel):
+    """The two fold-ins of a loglinear model on top of it: the throwaway engine and the labels of either form."""
+
+    @staticmethod
+    def _ll_engine(R_w, W, b, window_size, device):
+        """A parameters-only loglinear model on the device that holds the frozen tensors."""
+        Rw, Wt, bt = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
+        assert Wt.shape[0] == Rw.shape[1] and bt.shape == (Wt.shape[1],)
+        engine = _capi.Engine(
+            kind=_capi.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=window_size,
+            vocab_size=Rw.shape[0], num_entities=Wt.shape[1], word_dim=Rw.shape[1], entity_dim=0, num_negatives=0,
+            id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0, lr=1.0, beta1=0.95,
+            beta2=0.0, eps=1e-6, seed=0)
+        for which, value in ((_capi.T_RW, Rw), (_capi.T_W, Wt), (_capi.T_B, bt)):
+            engine.set_tensor(which, value)
+        return engine
+
+    @staticmethod
+    def _labels(x, y, window_size):
+        """-> (y, rows).  rows: y is a ``scipy.sparse`` matrix of label rows, returned as canonical CSR (a copy: the caller's
+        matrix is not modified); otherwise y is returned as the (M,) array of one label per instance."""
+        rows = scipy.sparse.issparse(y)
+        if rows:
+            y = scipy.sparse.csr_matrix(y, dtype=np.float32, copy=True)
+            y.sum_duplicates()
+            y.sort_indices()
+            assert x.ndim == 2 and x.shape[1] == window_size and y.shape[0] == x.shape[0]
+        else:
+            y = np.asarray(y)
+            assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
+        return y, rows
+
+    def _upload(self, x, y, w, rows):
+        if rows:
+            self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
+        else:
+            self._foldin.upload(x, y, w)
+
+
+class LogLinearFoldIn(_LlFoldInModel):
     """N new entities learnt on top of a trained loglinear model (R_w, W (d, V_e), b (V_e): host arrays, never written):
     N new columns Wn (d, N) of the output layer and N new biases bn, with the model's own loss over the V_e + N entities
     (include/sert_hip_ll_foldin.h).
@@ -242,13 +281,8 @@ class LogLinearFoldIn(_FoldInModel):
         x = np.asarray(training_set[0])
         w = training_set[2] if len(training_set) > 2 else None
         word_dim, num_entities = int(np.shape(W)[0]), int(np.shape(W)[1])
-        rows = scipy.sparse.issparse(training_set[1])
+        y, rows = self._labels(x, training_set[1], window_size)     # (label rows: over the V_e + N columns)
         if rows:
-            # label rows: canonical CSR over the V_e + N columns (a copy: the caller's matrix is not modified)
-            y = scipy.sparse.csr_matrix(training_set[1], dtype=np.float32, copy=True)
-            y.sum_duplicates()
-            y.sort_indices()
-            assert x.ndim == 2 and x.shape[1] == window_size and y.shape[0] == x.shape[0]
             if new_W_init is None:
                 if y.shape[1] - num_entities < (1 if refresh is None else 0):
                     raise RuntimeError('label rows of %d columns on a model of %d entities: no column is new'
@@ -256,8 +290,6 @@ class LogLinearFoldIn(_FoldInModel):
                 new_W_init = (models._glorot_uniform((word_dim, y.shape[1] - num_entities)) if y.shape[1] > num_entities
                               else np.zeros((word_dim, 0), dtype=np.float32))
         else:
-            y = np.asarray(training_set[1])
-            assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
             if new_W_init is None and refresh is not None:
                 new_W_init = np.zeros((word_dim, 0), dtype=np.float32)
             if new_W_init is None:
@@ -275,25 +307,10 @@ class LogLinearFoldIn(_FoldInModel):
         self.num_entities = int(np.shape(W)[1])
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
-
-        def make_engine():
-            Rw, Wt, bt = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
-            assert Wt.shape[0] == Rw.shape[1] and bt.shape == (Wt.shape[1],)
-            engine = _capi.Engine(
-                kind=_capi.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=self.window_size,
-                vocab_size=Rw.shape[0], num_entities=Wt.shape[1], word_dim=Rw.shape[1], entity_dim=0, num_negatives=0,
-                id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0, lr=1.0, beta1=0.95,
-                beta2=0.0, eps=1e-6, seed=0)
-            for which, value in ((_capi.T_RW, Rw), (_capi.T_W, Wt), (_capi.T_B, bt)):
-                engine.set_tensor(which, value)
-            return engine
-        self._attach(_engine, make_engine,
+        self._attach(_engine, lambda: self._ll_engine(R_w, W, b, self.window_size, device),
                      lambda engine: _capi.LlFoldIn(engine, new_W_init, new_b_init, batch_size, regularization_lambda,
                                                    max_cache_bytes=max_cache_bytes, refresh_ids=refresh))
-        if rows:
-            self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
-        else:
-            self._foldin.upload(x, y, w)
+        self._upload(x, y, w, rows)
         if refresh is None:
             logging.info('Folding in %d new entities (columns %d .. %d) on %d instances%s.', self.num_new, self.num_entities,
                          self.num_entities + self.num_new - 1, self.training_num_instances,
@@ -359,6 +376,17 @@ def new_word_rows(vocab_size, num_new_words, word_dim):
     return np.random.uniform(low=-a, high=a, size=(num_new_words, word_dim)).astype(np.float32)
 
 
+def _word_rows_init(new_rows_init, x, table_shape):
+    """The initial rows of a word fold-in as a float32 array; None: as many rows as x names new words, drawn by
+    ``new_word_rows``.  table_shape: (V_w, d) of the trained word table."""
+    vocab_size, word_dim = int(table_shape[0]), int(table_shape[1])
+    if new_rows_init is None:
+        if not x.size or int(x.max()) < vocab_size:
+            raise RuntimeError('no token of a new word and no initial rows: nothing says how many words are new')
+        new_rows_init = new_word_rows(vocab_size, int(x.max()) + 1 - vocab_size, word_dim)
+    return np.ascontiguousarray(new_rows_init, dtype=np.float32)
+
+
 class WordFoldIn(_NceFoldInModel):
     """Nw new word rows learnt on top of a trained vectorspace model (R_w, R_e, W, b: host arrays, never written).
 
@@ -376,12 +404,8 @@ class WordFoldIn(_NceFoldInModel):
         x, y = np.asarray(training_set[0]), np.asarray(training_set[1])
         w = training_set[2] if len(training_set) > 2 else None
         assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
-        vocab_size, word_dim = int(np.shape(R_w)[0]), int(np.shape(R_w)[1])
-        if new_rows_init is None:
-            if not x.size or int(x.max()) < vocab_size:
-                raise RuntimeError('no token of a new word and no initial rows: nothing says how many words are new')
-            new_rows_init = new_word_rows(vocab_size, int(x.max()) + 1 - vocab_size, word_dim)
-        new_rows_init = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        vocab_size = int(np.shape(R_w)[0])
+        new_rows_init = _word_rows_init(new_rows_init, x, np.shape(R_w))
         if seed is None:
             seed = int(np.random.randint(low=0, high=(1 << 30)))
         self.window_size = int(window_size)
@@ -419,7 +443,7 @@ class WordFoldIn(_NceFoldInModel):
         return np.concatenate([R_w, self._foldin.get_rows(_capi.WFOLD_ROWS)], axis=0)
 
 
-class LogLinearWordFoldIn(_FoldInModel):
+class LogLinearWordFoldIn(_LlFoldInModel):
     """Nw new word rows learnt on top of a trained loglinear model (R_w, W (d, V_e), b (V_e): host arrays, never written), with
     the model's own loss (include/sert_hip_ll_wfold.h).
 
@@ -439,49 +463,21 @@ class LogLinearWordFoldIn(_FoldInModel):
         super(LogLinearWordFoldIn, self).__init__(batch_size)
         x = np.asarray(training_set[0])
         w = training_set[2] if len(training_set) > 2 else None
-        rows = scipy.sparse.issparse(training_set[1])
-        if rows:
-            # label rows: canonical CSR over the V_e trained columns (a copy: the caller's matrix is not modified)
-            y = scipy.sparse.csr_matrix(training_set[1], dtype=np.float32, copy=True)
-            y.sum_duplicates()
-            y.sort_indices()
-            assert x.ndim == 2 and x.shape[1] == window_size and y.shape[0] == x.shape[0]
-        else:
-            y = np.asarray(training_set[1])
-            assert x.ndim == 2 and x.shape[1] == window_size and y.ndim == 1 and y.shape[0] == x.shape[0]
-        vocab_size, word_dim = int(np.shape(R_w)[0]), int(np.shape(R_w)[1])
-        if new_rows_init is None:
-            if not x.size or int(x.max()) < vocab_size:
-                raise RuntimeError('no token of a new word and no initial rows: nothing says how many words are new')
-            new_rows_init = new_word_rows(vocab_size, int(x.max()) + 1 - vocab_size, word_dim)
-        new_rows_init = np.ascontiguousarray(new_rows_init, dtype=np.float32)
+        y, rows = self._labels(x, training_set[1], window_size)     # (label rows: over the V_e trained columns)
+        vocab_size = int(np.shape(R_w)[0])
+        new_rows_init = _word_rows_init(new_rows_init, x, np.shape(R_w))
         self.window_size = int(window_size)
         self.num_new_words = int(new_rows_init.shape[0])
         self.vocab_size = vocab_size
         self.training_num_instances = int(y.shape[0])
         _capi.require_gpu()
-
-        def make_engine():
-            Rw, Wt, bt = (np.asarray(a, dtype=np.float32) for a in (R_w, W, b))
-            assert Wt.shape[0] == Rw.shape[1] and bt.shape == (Wt.shape[1],)
-            engine = _capi.Engine(
-                kind=_capi.KIND_LOGLINEAR, batch_size=1, global_batch_size=1, window_size=self.window_size,
-                vocab_size=Rw.shape[0], num_entities=Wt.shape[1], word_dim=Rw.shape[1], entity_dim=0, num_negatives=0,
-                id_bytes=4, device=device, keep_grads=0, deterministic=1, inference_only=1, lambda_=0.0, lr=1.0, beta1=0.95,
-                beta2=0.0, eps=1e-6, seed=0)
-            for which, value in ((_capi.T_RW, Rw), (_capi.T_W, Wt), (_capi.T_B, bt)):
-                engine.set_tensor(which, value)
-            return engine
-        self._attach(_engine, make_engine,
+        self._attach(_engine, lambda: self._ll_engine(R_w, W, b, self.window_size, device),
                      lambda engine: _capi.LlWordFoldIn(engine, new_rows_init, batch_size, regularization_lambda,
                                                        max_cache_bytes=max_cache_bytes))
-        if rows:
-            if y.shape[1] != self._foldin.num_entities:
-                raise RuntimeError('label rows must have V_e = %d columns, not %d: a word fold-in has no new entity'
-                                   % (self._foldin.num_entities, y.shape[1]))
-            self._foldin.upload_csr(x, y.indptr, y.indices, y.data, w)
-        else:
-            self._foldin.upload(x, y, w)
+        if rows and y.shape[1] != self._foldin.num_entities:
+            raise RuntimeError('label rows must have V_e = %d columns, not %d: a word fold-in has no new entity'
+                               % (self._foldin.num_entities, y.shape[1]))
+        self._upload(x, y, w, rows)
         logging.info('Folding in %d new words (token ids %d .. %d) on %d instances%s.', self.num_new_words, vocab_size,
                      vocab_size + self.num_new_words - 1, self.training_num_instances,
                      ' with %d label entries' % y.nnz if rows else '')

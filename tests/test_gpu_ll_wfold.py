@@ -68,6 +68,8 @@ def test_parity_and_plan(hip_lib, case):
             for key, want in LW.expected_plan(c, s).items():
                 assert plan[key] == want, (c['name'], s, key, plan[key], want)
             assert plan['gemm_z'] != 'none' and plan['gemm_g'] != 'none' and plan['splits'] >= 1
+            if c['name'] == 've4100':
+                assert plan['splits'] == c['Ve'] // 1024, plan           # (the K >= 4096 rule of gemm_long_k)
         _check_against_twins(f, t32, t64, c['name'])
         f.close()
     finally:

@@ -22,6 +22,7 @@ case (bound: tests.util.ROW_TOL64 = 5e-5 for all three):
     three_levels      1.6e-07  6.1e-06  4.0e-06
     ve1024            6.8e-08  3.8e-07  2.4e-07
     ve1025            4.9e-08  3.9e-07  2.5e-07
+    ve4100            5.0e-08  6.3e-07  5.3e-07
     ve700             6.1e-08  3.9e-07  2.7e-07
     ve8               5.5e-08  3.2e-07  2.1e-07
 """
@@ -59,7 +60,7 @@ def test_case_has_its_structure(cases, name):
     per_batch = [tok[i * B:(i + 1) * B] for i in range(c['batches'])]
     counts = [np.bincount(t[t >= 0], minlength=Nw) for t in per_batch]
     plans = [LW.expected_plan(c, i) for i in range(c['batches'])]
-    assert all(p['form'] == ('stream' if name == 've1025' else 'reg') for p in plans)
+    assert all(p['form'] == ('stream' if name in ('ve1025', 've4100') else 'reg') for p in plans)
     if name == 'base':
         assert counts[0][Nw - 1] == 0 and counts[0][:Nw - 1].min() > 0
         assert any((r < 0).all() for r in per_batch[0])
@@ -72,6 +73,9 @@ def test_case_has_its_structure(cases, name):
         assert Ve == LW.REG_MAX_VE and plans[0]['vec']
     elif name == 've1025':
         assert Ve == LW.REG_MAX_VE + 1 and not plans[0]['vec'] and plans[0]['segsum'] == 'scalar'
+    elif name == 've4100':
+        # K = V_e >= 4096 with one output tile: the first rule of gemm_long_k, V_e // 1024 k ranges, the last one ragged
+        assert 4096 <= Ve < 4096 + 16 and Ve // 1024 == 4 and Ve % 1024 != 0 and Nw <= 128 and d <= 128 and plans[0]['vec']
     elif name == 'n1':
         assert n == 1
     elif name == 'n32':

@@ -10,9 +10,10 @@ took.  The entity-chain group runs two steps of every case of tests/egrad_key_ca
 sort as well as on their own path, the bucket cases), tests/foldin_key_cases.py and tests/refresh_cases.py, and records dR_e
 after each step, or the fold-in's E, m and v, with the losses and the plan of the sorted chain (eg_plan, FoldIn.plan()).  The
 fold-ins group runs every case of tests/ll_foldin_cases.py, tests/ll_foldin_label_cases.py, tests/ll_refresh_cases.py and
-tests/wfold_cases.py: two train_batch steps, one train_batches call over two batches and one eval_batch, with the losses and
-every trainable tensor and accumulator after each; a word fold-in once on the case's explicit negatives and once on
-device-drawn ones.  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.
+tests/wfold_cases.py, and through LlWordFoldIn every case of tests/ll_wfold_cases.py (integer labels) and
+tests/ll_wfold_rows_cases.py (label rows): two train_batch steps, one train_batches call over two batches and one eval_batch,
+with the losses and every trainable tensor and accumulator after each; a vectorspace word fold-in once on the case's explicit
+negatives and once on device-drawn ones.  --against compares the uint32 views element by element (NaN payloads count) and fails on any difference.
 The library is chosen by SERT_LIB, read at import, and SERT_LL_NODEDUP once per process: every (library, group) runs in a fresh
 child process started with subprocess, one at a time.  The run fails if the forms taken do not cover FAMILIES."""
 import argparse
@@ -55,7 +56,15 @@ FAMILIES = (['ll %s %s %s' % (f, lab, m) for lab in ('int', 'csr') for f, m in
             ['llf int refresh n<=8', 'llf csr refresh n<=8'] +
             # the word fold-in, from WordFoldIn.plan(): wfold <project> <loss> <segsum> <train|eval>
             ['wfold vector per_candidate rows32 train', 'wfold vector per_candidate none train', 'wfold vector per_candidate none eval',
-             'wfold scalar scalar scalar train', 'wfold scalar scalar none eval'])
+             'wfold scalar scalar scalar train', 'wfold scalar scalar none eval'] +
+            # the loglinear word fold-in, from LlWordFoldIn.plan(): llw <form> <vec|scalar> <labels> <segsum> <gemm_g> <split|whole>
+            # <train|eval> -- split: G = dZ W^T cut into k ranges by gemm_long_k (ve4100: its K >= 4096 rule)
+            ['llw %s %s %s' % (fv, lab, rest) for lab in ('int', 'rows') for fv, rest in
+             [('reg scalar', 'none f32_tile128 whole train'), ('reg scalar', 'scalar f32_tile128 whole train'),
+              ('reg scalar', 'none none whole eval'), ('reg vec', 'rows64 f32_tile128 whole train'),
+              ('reg vec', 'rows64 f32_tile128 split train'), ('reg vec', 'none none whole eval'),
+              ('stream scalar', 'scalar f32_tile128 split train'), ('stream scalar', 'none none whole eval'),
+              ('stream vec', 'rows64 f32_tile128 split train'), ('stream vec', 'none none whole eval')]])
 
 
 def run_engine(out, tag, eng, kind, uploads, form):
@@ -232,6 +241,8 @@ def foldins_child(out):
     from tests import ll_foldin_cases as LC
     from tests import ll_foldin_label_cases as LL
     from tests import ll_refresh_cases as RC
+    from tests import ll_wfold_cases as LWC
+    from tests import ll_wfold_rows_cases as LWR
     from tests import util as U
     from tests import wfold_cases as WC
     forms = []
@@ -276,6 +287,26 @@ def foldins_child(out):
                                                                  (('Nv', C.WFOLD_ROWS), ('m', C.WFOLD_M), ('v', C.WFOLD_V))),
                                     form, negs=(None, None) if drawn else (c['neg'][0], c['neg'][1]),
                                     eval_neg=None if drawn else c['eval_neg'])
+    # the loglinear word fold-in on integer labels and on label rows; from LlWordFoldIn.plan():
+    # llw <form> <vec|scalar> <labels> <segsum> <gemm_g> <split|whole> <train|eval>
+    llw_rows = (('Nv', C.LL_WFOLD_ROWS), ('accu', C.LL_WFOLD_ACCU), ('delta', C.LL_WFOLD_DELTA))
+    for mod, prefix in ((LWC, 'llw'), (LWR, 'llw_rows')):
+        for name in sorted(mod.CASES):
+            c = mod.make_case(name)
+            eng = U.ll_engine(dict(Rw=c['Rw'], W=c['W'], b=c['b'], X=c['X']), 8, c['n'], 0.01, keep_grads=0)
+            f = C.LlWordFoldIn(eng, c['Nv0'], c['B'], c['lam'])
+            eng.close()
+            if 'indptr' in c:
+                f.upload_csr(c['X'], c['indptr'], c['indices'], c['data'], c['w'])
+            else:
+                f.upload(c['X'], c['y'], c['w'])
+
+            def form(train, f=f):
+                pl = f.plan()
+                assert pl['train'] == train, pl
+                return 'llw %s %s %s %s %s %s %s' % (pl['form'], 'vec' if pl['vec'] else 'scalar', pl['labels'], pl['segsum'], pl['gemm_g'],
+                                                     'split' if pl['splits'] > 1 else 'whole', 'train' if train else 'eval')
+            forms += run_fold_steps(out, '%s_%s' % (prefix, name), f, lambda h: dict((k, h.get_rows(w)) for k, w in llw_rows), form)
     return forms
 
 
